@@ -17,6 +17,7 @@ Scaling: strong by default -- BASELINE config 4 is the FIXED 3600 x 1800 x 75 x 
 At N=1 the line also carries a float32 sub-record (the dtype of real NEMO files) and the CPU baseline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its own N ranks, see self_launch)
+    python bench.py ... --dump-outputs DIR      (the rows of the last timed step as DIR/*.npy, to compare two builds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 import argparse
@@ -185,6 +186,7 @@ def run_workload(args, dtype, scaling, rank, world, local, want_totals=False, em
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    last_rows = rows.cpu().numpy() if args.dump_outputs else None     # the rows of the last timed step (reduced for N>1)
     nlaunch, kernel_ms, flux_ms, expand_ms = fld.readKernelTiming(split=True)
     k3_ms = fld.readTransectTiming()
     fld.enableKernelTiming(False)
@@ -265,6 +267,8 @@ def run_workload(args, dtype, scaling, rank, world, local, want_totals=False, em
                      'singular_transect_t0': float(res[0, nseg + 0]), 'transect_steps_checked': len(polys) * nt_global}
     if want_totals:
         m['totals'] = res[:, nseg:nseg + len(polys)].tolist()
+    if last_rows is not None:   # what Field.computeAll hands its caller: (nt, ntransect) totals and (nt, nseg) segment sums
+        m['outputs'] = {'transect_totals': last_rows[:, nseg:nseg + len(polys)], 'segment_fluxes': last_rows[:, :nseg]}
 
     # ---- roofline of the dominant kernel (vertical integral + edge flux), HIP events on its stream
     s = 8 if dtype == 'f64' else 4
@@ -317,6 +321,9 @@ def main():
     ap.add_argument('--no-c3', action='store_true', help='skip the ORCA025-like C3 sub-record (N=1)')
     ap.add_argument('--only-c3', action='store_true', help='print the C3 sub-record alone (for profiling it: scripts/gpu_profile.sh)')
     ap.add_argument('--dump-totals', action='store_true', help='add the (nt, ntransect) totals to the JSON (small grids)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most '
+                         '64 MB in all: larger outputs are cut to a fixed seeded sample of their columns)')
     ap.add_argument('--emulate-rank', default=None, metavar='r/N',
                     help='NOT a scaling run: on ONE GPU, do exactly what rank r of an N-rank strong-scaling run does (its slab '
                          'range, its launches; no reduce) and report its ms per pass -- per-rank compute evidence for N > 1')
@@ -326,6 +333,8 @@ def main():
                     help='NOT the headline configuration: keep only (eU, eV) resident per step (nf_field_set_compact); the '
                          '(ncell,4) copies and |.| arrays are derived at read-back, which a batch driver never asks for')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has made no GPU call and never will
@@ -349,10 +358,14 @@ def main():
         name, val = kv.split('=')
         check(lib.nf_tuning_set(name.encode(), int(val)))
 
+    dumped = {}
     if args.only_c3:
         if world != 1:
             raise SystemExit('bench.py: --only-c3 needs --gpus 1')
-        print(json.dumps({'c3': c3_record(args.steps)}))
+        out = {'c3': c3_record(args.steps, args.warmup, dumped if args.dump_outputs else None)}
+        if args.dump_outputs:
+            out['dumped_outputs'] = write_outputs(args.dump_outputs, dumped)
+        print(json.dumps(out))
         return
     nx, ny, nz = args.nx, args.ny, args.nz
     emulate = None
@@ -363,6 +376,7 @@ def main():
         emulate = (r, n)
         args.no_cpu = args.no_f32 = args.no_ingest = args.no_c3 = True
     m = run_workload(args, args.dtype, args.scaling, rank, world, local, want_totals=args.dump_totals, emulate=emulate)
+    dumped.update(m.pop('outputs', {}))
     slabs = m['nt_global'] * nz
     out = {
         'metric': 'edge-flux integrals/sec', 'value': m['value'], 'unit': 'integrals/s', 'n_gpus': world,
@@ -412,6 +426,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
         m32 = run_workload(args, 'f32', args.scaling, rank, world, local)
+        dumped.update(('f32_' + k, a) for k, a in m32.pop('outputs', {}).items())
         r = m32['roofline']
         out['f32'] = {'value': m32['value'], 'unit': 'integrals/s', 'ms_per_step': m32['ms_per_step'], 'dtype': 'f32',
                       'roofline': {k: r[k] for k in ('achieved', 'peak', 'unit', 'frac', 'traffic', 'traffic_source',
@@ -428,21 +443,47 @@ def main():
     # ---- BASELINE config C3 (ORCA025-like, one time step) beside the headline: the mid-size grid most real files have
     if world == 1 and not args.no_c3 and not emulate:
         try:
-            out['c3'] = c3_record()
+            out['c3'] = c3_record(args.steps, args.warmup, dumped if args.dump_outputs else None)
         except Exception as e:
             out['c3'] = {'error': f'{type(e).__name__}: {e}'}
     if rank == 0:
+        if args.dump_outputs:
+            out['dumped_outputs'] = write_outputs(args.dump_outputs, dumped)
         print(json.dumps(out))
     if world > 1:
         nfdist.destroy_native_comms()
         dist.destroy_process_group()
 
 
-def c3_record(steps=20):
+def write_outputs(dirname, arrays, budget=64 << 20, seed=20261015):
+    """--dump-outputs: every (rows, columns) array of `arrays` as dirname/<name>.npy in float64.  Past `budget` bytes in all,
+    each array keeps a seeded sample of its columns (the same columns for the same shape, run after run), in proportion to
+    its share of the total, and dirname/<name>_columns.npy says which.  Returns {name: shape written}."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size * 8 for a in arrays.values())
+    whole = sum(a.size * 8 for a in arrays.values() if a.shape[1] <= 1)       # single columns are written whole
+    headers = 512 * len(arrays)     # a header of at most 256 bytes per file, two files per sampled array
+    written = {}
+    for name, a in arrays.items():
+        a = numpy.ascontiguousarray(a, dtype=numpy.float64)
+        if total + headers > budget and a.shape[1] > 1:
+            share = (budget - whole - headers) * (a.size * 8) / (total - whole)
+            k = max(1, min(a.shape[1], int(share // (8 * (a.shape[0] + 1)))))
+            cols = numpy.sort(numpy.random.default_rng(seed).choice(a.shape[1], k, replace=False))
+            a = numpy.ascontiguousarray(a[:, cols])
+            numpy.save(os.path.join(dirname, name + '_columns.npy'), cols.astype(numpy.float64))
+            written[name + '_columns'] = list(cols.shape)
+        numpy.save(os.path.join(dirname, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def c3_record(steps=20, warmup=3, outputs=None):
     """BASELINE config C3 beside the headline (N=1): the ORCA025-like 1440 x 1021 x 75 grid, ONE time step, the 50-station
     transect data/S3_sta_bdep.txt (tests/golden/stations.json holds the reference's own parse of it), float64 and float32.
     A step of this grid is only 2.2 / 1.1 rounds of resident wavefronts, so K1 runs in its one-field form
-    (nf::k_flux_field, DESIGN.md section 4); same events, same algorithmic bytes per unit as the headline."""
+    (nf::k_flux_field, DESIGN.md section 4); same events, same algorithmic bytes per unit as the headline.
+    outputs: a dict that receives the rows of the last timed step (c3_<dtype>_transect_totals, c3_<dtype>_segment_fluxes)."""
     import contextlib
     import ctypes
     import io
@@ -467,7 +508,7 @@ def c3_record(steps=20):
             fld = Field.fromArrays(dg.bounds_lon, dg.bounds_lat, dg.deptht_bounds, u, v, [xyz], readback=False,
                                    stream=torch.cuda.current_stream().cuda_stream)
         rows = torch.zeros((1, fld._rowlen), dtype=torch.float64, device='cuda')
-        for _ in range(3):
+        for _ in range(warmup):
             check(lib.nf_field_compute_all_async(ctypes.byref(fld._h), ctypes.c_void_p(rows.data_ptr())))
         fld.enableKernelTiming(True, reserve=steps)
         torch.cuda.synchronize()
@@ -476,6 +517,10 @@ def c3_record(steps=20):
             check(lib.nf_field_compute_all_async(ctypes.byref(fld._h), ctypes.c_void_p(rows.data_ptr())))
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t0) / steps
+        if outputs is not None:
+            last = rows.cpu().numpy()
+            outputs[f'c3_{dtype}_transect_totals'] = last[:, fld._nseg:fld._nseg + 1]
+            outputs[f'c3_{dtype}_segment_fluxes'] = last[:, :fld._nseg]
         nl, kms, flux_ms, expand_ms = fld.readKernelTiming(split=True)
         k3 = fld.readTransectTiming()
         fld.enableKernelTiming(False)

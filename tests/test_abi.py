@@ -164,18 +164,12 @@ def test_get_sizes_and_flux_text_format():
 
 
 def test_netcdf4_ingest_of_the_reference_t_file():
-    """nemoflux_amd.io reads the reference's real NetCDF-4 T file (data/sa/T.nc) when some interpreter with h5py exists
-    (this image: /opt/conda/bin/python3.9) and agrees with the committed fixture.  Skipped where the reference tree or
-    h5py is absent (the GPU box has no /root/reference)."""
-    from conftest import load_golden
+    """nemoflux_amd.io reads the reference's real NetCDF-4 T file (data/sa/T.nc, stored as tests/golden/h5/sa_T.nc) in
+    process and agrees with the bounds the reference's own stack read from it (sa_T_bounds.npz)."""
+    from conftest import GOLDEN, load_golden
     from nemoflux_amd import io
-    src = '/root/reference/data/sa/T.nc'
-    if not os.path.exists(src):
-        pytest.skip('reference tree not present')
-    try:
-        d = io.open_tfile(src)
-    except RuntimeError as e:
-        pytest.skip(str(e))
+    src = os.path.join(GOLDEN, 'h5', 'sa_T.nc')
+    d = io.open_tfile(src)
     g = load_golden('sa_T_bounds')
     for k in ('bounds_lon', 'bounds_lat', 'deptht_bounds'):
         assert d[k].dtype == numpy.float32 and numpy.array_equal(d[k], g[k])

@@ -53,7 +53,15 @@ def _partial_rows(oracle, g, m, srange, weights):
     return rows
 
 
+def _cpu_only_rank():
+    """A gloo rank of this suite opens no GPU, also on a machine that has one: it reduces host tensors, and
+    nemoflux_amd.dist.init_from_env asks for devices only through torch.cuda.is_available() (which initialises HIP).  This
+    keeps the 8-rank case from holding the device in 8 processes at once."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, name, out_path):
+    _cpu_only_rank()
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, 'oracle'))
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -126,6 +134,29 @@ def test_bench_transects_are_seeded_and_clear_of_column_zero():
         assert numpy.abs(xy[:, 1]).max() <= 80. + 1e-9
         assert numpy.allclose(numpy.round((xy[:, 0] + 180.) / dx) * dx - 180., xy[:, 0], atol=1e-9)   # on nodes
         assert (poly[0] == poly[-1]) == (k % 2 == 1)                                              # half are closed
+
+
+def test_bench_dump_outputs_within_budget_and_seeded(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files; small outputs are written whole, larger ones as the same seeded sample of
+    columns run after run (with the columns it kept), and the files never exceed the budget in all."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = numpy.random.default_rng(3)
+    small = {'transect_totals': rng.standard_normal((12, 65)), 'segment_fluxes': rng.standard_normal((12, 2229))}
+    assert bench.write_outputs(str(tmp_path / 's'), small) == {'transect_totals': [12, 65], 'segment_fluxes': [12, 2229]}
+    for k, a in small.items():
+        got = numpy.load(tmp_path / 's' / f'{k}.npy')
+        assert got.dtype == numpy.float64 and numpy.array_equal(got, a)
+    big = {'segment_fluxes': rng.standard_normal((40, 3000)), 'c3_transect_totals': numpy.ones((1, 1))}
+    budget = 400000
+    for d in ('b1', 'b2'):
+        bench.write_outputs(str(tmp_path / d), big, budget=budget)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= budget
+    cols = numpy.load(tmp_path / 'b1' / 'segment_fluxes_columns.npy')
+    assert numpy.array_equal(cols, numpy.load(tmp_path / 'b2' / 'segment_fluxes_columns.npy'))
+    assert 0 < cols.size < 3000 and numpy.all(numpy.diff(cols) > 0)
+    assert numpy.array_equal(numpy.load(tmp_path / 'b1' / 'segment_fluxes.npy'), big['segment_fluxes'][:, cols.astype(int)])
+    assert numpy.array_equal(numpy.load(tmp_path / 'b1' / 'c3_transect_totals.npy'), numpy.ones((1, 1)))
 
 
 def test_bench_refuses_more_gpus_than_the_node_has():
@@ -295,6 +326,7 @@ def test_rank_refuses_over_subscription_before_the_rendezvous(monkeypatch, capsy
 
 
 def _agree_worker(rank, world, port, out_dir):
+    _cpu_only_rank()
     import json
     from nemoflux_amd import dist as nfdist
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),

@@ -1,6 +1,6 @@
 """CPU suite, part 4: nemoflux_amd/hdf5min.py (the in-process NetCDF-4/HDF5 reader) against files written by the real
 HDF5 library through h5py (oracle/gen_hdf5_fixtures.py, run under /opt/conda/bin/python3.9) and against the reference's
-own data/sa/T.nc.  Expected values are recomputed from the generator's formula."""
+own data/sa/T.nc (stored as tests/golden/h5/sa_T.nc).  Expected values are recomputed from the generator's formula."""
 import os
 
 import numpy
@@ -158,11 +158,10 @@ def test_cf_decoding_like_xarray():
 
 
 def test_reference_t_file_in_process():
-    """The reference's real NetCDF-4 file (superblock 0, v2 object headers, dense links): hdf5min == committed fixture."""
+    """The reference's real NetCDF-4 file (superblock 0, v2 object headers, dense links; data/sa/T.nc, stored as
+    tests/golden/h5/sa_T.nc): hdf5min == committed fixture."""
     from nemoflux_amd import hdf5min
-    src = '/root/reference/data/sa/T.nc'
-    if not os.path.exists(src):
-        pytest.skip('reference tree not present')
+    src = os.path.join(H5, 'sa_T.nc')
     d = hdf5min.read_variables(src)
     g = load_golden('sa_T_bounds')
     for k in g.files:
