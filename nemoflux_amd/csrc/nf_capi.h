@@ -1,5 +1,5 @@
 // nf_capi.h -- what the three files of the C ABI share (nf_capi_util.hip: plumbing, nf_capi_mint.hip: Level 1,
-// nf_capi_field.hip: Level 2): the exception barrier, per-call device scratch, the sparse host staging, and the Grid_t that
+// nf_capi_field.hip: Level 2): the exception barrier, the sparse host staging, and the Grid_t that
 // Level 1 owns and a Field lends (nf_field_grid).  Internal: nothing here is exported.
 #pragma once
 #include <algorithm>
@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <thread>
 #include <vector>
@@ -28,34 +29,6 @@ int field_tuning_set(const char *name, int value);
 // Exception barrier of the C ABI: every entry point is a function-try-block ending in NF_API_CATCH, so a
 // std::bad_alloc (or any other C++ exception) raised by the host-side containers becomes NF_ERR_HOST.
 #define NF_API_CATCH catch (...) { return nf::trap_exception(); }
-
-// device scratch that lives for one call: freed on every return path
-struct DevTmp {
-    void *p = nullptr;
-    DevTmp() = default;
-    DevTmp(const DevTmp &) = delete;
-    DevTmp &operator=(const DevTmp &) = delete;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes)
-    {
-        NF_HIP(hipMalloc(&p, bytes ? bytes : 16));
-        return NF_OK;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
-template <typename T>
-static int dev_alloc(T **p, size_t count)
-{
-    NF_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
-    return NF_OK;
-}
-template <typename T>
-static void dev_free(T *&p)
-{
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
 
 // Sparse staging of a caller's HOST (ncell,4) array for the Level-1 entry points: the 32 bytes of every cell an object
 // touches (the records of a PolylineIntegral, the located cells of a VectorInterp) are gathered into a pinned buffer in
@@ -85,23 +58,19 @@ static void host_gather_rows4(const double *data, const I *ids, long n, double *
     for (auto &th : pool) th.join();
 }
 
-// pinned host buffer + its HBM twin, sized once per weight build / point search
+// pinned host buffer + its HBM twin, sized once per weight build / point search; both are freed with the stage
 struct GatherStage {
-    double *h = nullptr, *d = nullptr;
+    std::unique_ptr<double, hipError_t (*)(void *)> h{nullptr, hipHostFree};
+    DevArray<double> d;
     long rows = 0;
-    void release()
-    {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = nullptr;
-        rows = 0;
-    }
     int resize(long n)
     {
-        release();
+        *this = GatherStage();
         if (n <= 0) return NF_OK;
-        NF_HIP(hipHostMalloc((void **)&h, sizeof(double) * 4 * (size_t)n, hipHostMallocDefault));
-        NF_HIP(hipMalloc((void **)&d, sizeof(double) * 4 * (size_t)n));
+        double *p = nullptr;
+        NF_HIP(hipHostMalloc((void **)&p, sizeof(double) * 4 * (size_t)n, hipHostMallocDefault));
+        h.reset(p);
+        NF_TRY(d.alloc(4 * (size_t)n));
         rows = n;
         return NF_OK;
     }
@@ -109,8 +78,8 @@ struct GatherStage {
     int upload(const double *data, const I *ids)   // gather on the host, one copy of rows x 32 B; complete at return
     {
         if (rows == 0) return NF_OK;
-        host_gather_rows4(data, ids, rows, h);
-        NF_HIP(hipMemcpy(d, h, sizeof(double) * 4 * (size_t)rows, hipMemcpyHostToDevice));
+        host_gather_rows4(data, ids, rows, h.get());
+        NF_HIP(hipMemcpy(d.get(), h.get(), sizeof(double) * 4 * (size_t)rows, hipMemcpyHostToDevice));
         return NF_OK;
     }
 };
@@ -120,8 +89,8 @@ struct GatherStage {
 struct Grid_t {
     long ncell = 0;
     double *host_points = nullptr;  // borrowed (ncell,4,3)
-    double *d_xy = nullptr;         // corner table (ncell,4,2)
-    bool owns_xy = true;
+    double *d_xy = nullptr;         // corner table (ncell,4,2): own_xy, or the one a Field lends (nf_field_grid)
+    nf::DevArray<double> own_xy;    // mnt_grid_build's corner table
     long version = 0;               // bumped by every build: weights / located points of an older build are refused
     nf::LocatorBoxes boxes;             // the locator of this grid (filled by the first computeWeights, dropped when the points change)
     long row_length = 0;            // mnt_grid_setRowLength: the cells are rows of this many (0 = a flat list, like mint's)

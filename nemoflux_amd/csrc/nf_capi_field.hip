@@ -44,32 +44,34 @@ int field_tuning_set(const char *name, int value)
 struct nf_field {
     hipStream_t stream = nullptr;
     long ny = 0, nx = 0, ncell = 0, nz = 0, nt = 0;
-    // geometry
-    double *d_xy = nullptr, *d_arc4 = nullptr, *d_arcE = nullptr, *d_arcN = nullptr;
-    unsigned long long *d_box = nullptr;
+    // everything sized by the grid: allocated by set_bounds (and on demand after it), dropped together by field_free_geometry
+    struct Geometry {
+        DevArray<double> xy, arc4, arcE, arcN;
+        DevArray<unsigned long long> box;
+        // resident per-step outputs
+        DevArray<double> iV;    // [4][ncell]
+        DevArray<double> abs;   // [2][ncell]
+        DevArray<double> aos;   // (ncell,4) re-pack buffer for read_step, allocated on first use
+        DevArray<unsigned long long> maxbits;
+        // multi-step launches for small grids (compute_all): per-step planes, scratch and z ranges
+        DevArray<double> iVb, absb, scratchb;
+        DevArray<int> zr;
+        long batch_steps = 0, batch_version = -1;
+    } geo;
     double box[4] = {0, 0, 0, 0};
-    double *d_thick = nullptr;
+    DevArray<double> thick;
     // velocity fields
     const void *u = nullptr, *v = nullptr;
     int uv_dtype = NF_F64, uv_on_device = 1;
     double fill = std::numeric_limits<double>::quiet_NaN();
     double fill2 = std::numeric_limits<double>::quiet_NaN();   // nf_field_set_missing_value
-    void *d_stage_u = nullptr, *d_stage_v = nullptr;
+    DevArray<char> stage_u, stage_v;   // host-resident fields: the slabs of one step, grown to the largest step staged
     int sverdrup = 0;
     long s_begin = 0, s_end = -1;
-    // resident per-step outputs
-    double *d_iV = nullptr;   // [4][ncell]
-    double *d_abs = nullptr;  // [2][ncell]
-    double *d_aos = nullptr;  // (ncell,4) re-pack buffer for read_step, allocated on first use
     // compact resident mode (nf_field_set_compact): the flux kernel stores only eU and eV; the neighbour-copy planes and
     // the two |.| planes are derived when somebody asks for them (read_step, device_ptr)
     int compact = 0;
     bool derived_stale = false;
-    // multi-step launches for small grids (compute_all): per-step planes, scratch and z ranges
-    double *d_iVb = nullptr, *d_absb = nullptr, *d_scratchb = nullptr;
-    int *d_zr = nullptr;
-    long batch_steps = 0, batch_version = -1;
-    unsigned long long *d_maxbits = nullptr;
     // transects
     std::vector<std::vector<double>> polylines;
     std::vector<int> poly_cc;
@@ -78,8 +80,8 @@ struct nf_field {
     bool weights_built = false;
     int skip_unsupported = 0;   // nf_field_set_unsupported_cells
     int overlap_warn = 0;       // nf_field_set_overlapping_cells
-    int *d_tr_off = nullptr;
-    double *d_scratch = nullptr, *d_row = nullptr;
+    DevArray<int> tr_off_dev;
+    DevArray<double> scratch, row;
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -107,21 +109,7 @@ static void field_drop_graph(nf_field *f)
 
 static int field_free_geometry(nf_field *f)
 {
-    dev_free(f->d_xy);
-    dev_free(f->d_arc4);
-    dev_free(f->d_arcE);
-    dev_free(f->d_arcN);
-    dev_free(f->d_box);
-    dev_free(f->d_iV);
-    dev_free(f->d_abs);
-    dev_free(f->d_aos);
-    dev_free(f->d_iVb);
-    dev_free(f->d_absb);
-    dev_free(f->d_scratchb);
-    dev_free(f->d_zr);
-    f->batch_steps = 0;
-    f->batch_version = -1;
-    dev_free(f->d_maxbits);
+    f->geo = {};
     // the locator cache and the lent grid describe the corner table that was just freed: gone with it, on EVERY path out of
     // set_bounds (an early return used to leave boxes keyed on the freed pointer, which hipMalloc often hands out again:
     // round-5 advisor)
@@ -206,7 +194,7 @@ static int field_timed_k3_end(nf_field *f)
 static int field_ensure_derived(nf_field *f)
 {
     if (!f->derived_stale) return NF_OK;
-    NF_TRY(launch_expand_planes(f->d_iV, f->d_abs, f->ncell, f->ny, f->nx, f->stream));
+    NF_TRY(launch_expand_planes(f->geo.iV.get(), f->geo.abs.get(), f->ncell, f->ny, f->nx, f->stream));
     f->derived_stale = false;
     return NF_OK;
 }
@@ -216,7 +204,7 @@ static int field_row_length(const nf_field *f) { return f->ws.nseg + (int)f->pol
 // one time step on the field's stream; row_dev receives [segments | transects]
 static int field_step_async(nf_field *f, long t, double *row_dev)
 {
-    NF_REQUIRE(f->d_arcE && f->d_thick && f->u && f->v, NF_ERR_STATE,
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
                "compute: set_bounds, set_thickness and set_uv first");
     NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute: time index out of range");
     const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
@@ -236,17 +224,15 @@ static int field_step_async(nf_field *f, long t, double *row_dev)
         ut = (const char *)f->u + (size_t)t * step_bytes;
         vt = (const char *)f->v + (size_t)t * step_bytes;
     } else {  // host-resident fields: stage the owned slabs of this step (PCIe-inclusive path)
-        if (!f->d_stage_u) {
-            NF_HIP(hipMalloc(&f->d_stage_u, step_bytes));
-            NF_HIP(hipMalloc(&f->d_stage_v, step_bytes));
-        }
+        NF_TRY(f->stage_u.reserve(step_bytes));
+        NF_TRY(f->stage_v.reserve(step_bytes));
         const size_t off = (size_t)z0 * f->ncell * es, len = (size_t)(z1 - z0) * f->ncell * es;
-        NF_HIP(hipMemcpyAsync((char *)f->d_stage_u + off, (const char *)f->u + (size_t)t * step_bytes + off, len,
+        NF_HIP(hipMemcpyAsync(f->stage_u.get() + off, (const char *)f->u + (size_t)t * step_bytes + off, len,
                               hipMemcpyHostToDevice, f->stream));
-        NF_HIP(hipMemcpyAsync((char *)f->d_stage_v + off, (const char *)f->v + (size_t)t * step_bytes + off, len,
+        NF_HIP(hipMemcpyAsync(f->stage_v.get() + off, (const char *)f->v + (size_t)t * step_bytes + off, len,
                               hipMemcpyHostToDevice, f->stream));
-        ut = f->d_stage_u;
-        vt = f->d_stage_v;
+        ut = f->stage_u.get();
+        vt = f->stage_v.get();
     }
     FluxArgs a{};
     a.u = ut;
@@ -257,17 +243,17 @@ static int field_step_async(nf_field *f, long t, double *row_dev)
     a.nx = f->nx;
     a.z0 = z0;
     a.z1 = z1;
-    a.thickness = f->d_thick;
-    a.arcE = f->d_arcE;
-    a.arcN = f->d_arcN;
+    a.thickness = f->thick.get();
+    a.arcE = f->geo.arcE.get();
+    a.arcN = f->geo.arcN.get();
     a.fill = f->fill;
     a.fill2 = f->fill2;
     a.scale = kEarthRadiusSv / 1.e6;  // field.py:226
     a.sverdrup = f->sverdrup;
-    a.iV = f->d_iV;
-    a.absU = f->d_abs;
-    a.absV = f->d_abs + f->ncell;
-    a.maxbits = f->d_maxbits;
+    a.iV = f->geo.iV.get();
+    a.absU = f->geo.abs.get();
+    a.absV = f->geo.abs.get() + f->ncell;
+    a.maxbits = f->geo.maxbits.get();
     // A rank of a sharded run that owns only PART of this step's levels (slab sharding cuts inside a time step) produces
     // partial sums: its south / west copies and |.| planes mean nothing (only a step owned whole has full-field outputs),
     // the transect reduction reads the two signed planes only, so the step runs in the signed-only form and the four derived
@@ -284,8 +270,8 @@ static int field_step_async(nf_field *f, long t, double *row_dev)
     }
     if (row_dev && rowlen > 0) {
         NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute: build_weights first");
-        NF_TRY(launch_integral(f->ws, f->d_iV, f->ncell, 2, f->nx, f->d_tr_off, (int)f->polylines.size(),
-                               f->d_scratch, row_dev, f->stream));
+        NF_TRY(launch_integral(f->ws, f->geo.iV.get(), f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(),
+                               f->scratch.get(), row_dev, f->stream));
         NF_TRY(field_timed_k3_end(f));
     }
     return NF_OK;
@@ -330,21 +316,18 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
 {
     const int rowlen = field_row_length(f);
     const size_t n = (size_t)f->ncell;
-    if (f->batch_steps != f->nt) {
-        dev_free(f->d_iVb);
-        dev_free(f->d_absb);
-        dev_free(f->d_zr);
-        NF_TRY(dev_alloc(&f->d_iVb, n * 4 * f->nt));
-        NF_TRY(dev_alloc(&f->d_absb, n * 2 * f->nt));
-        NF_TRY(dev_alloc(&f->d_zr, (size_t)2 * f->nt));
+    nf_field::Geometry &g = f->geo;
+    if (g.batch_steps != f->nt) {
+        NF_TRY(g.iVb.alloc(n * 4 * f->nt));
+        NF_TRY(g.absb.alloc(n * 2 * f->nt));
+        NF_TRY(g.zr.alloc((size_t)2 * f->nt));
         // south slots of row 0 are never written (field.py:219): every step's planes start as zeros
-        NF_HIP(hipMemsetAsync(f->d_iVb, 0, sizeof(double) * n * 4 * f->nt, f->stream));
-        f->batch_steps = f->nt;
-        f->batch_version = -1;
+        NF_HIP(hipMemsetAsync(g.iVb.get(), 0, sizeof(double) * n * 4 * f->nt, f->stream));
+        g.batch_steps = f->nt;
+        g.batch_version = -1;
     }
-    if (f->batch_version != f->version) {  // scratch follows the weight set, z ranges follow the slab ownership
-        dev_free(f->d_scratchb);
-        NF_TRY(dev_alloc(&f->d_scratchb, (size_t)std::max(f->ws.nrec, f->ws.nent) * f->nt));
+    if (g.batch_version != f->version) {  // scratch follows the weight set, z ranges follow the slab ownership
+        NF_TRY(g.scratchb.alloc((size_t)std::max(f->ws.nrec, f->ws.nent) * f->nt));
         std::vector<int> zr((size_t)2 * f->nt);
         const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
         for (long t = 0; t < f->nt; ++t) {
@@ -355,8 +338,8 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
             zr[2 * t] = (int)(lo - t * f->nz);
             zr[2 * t + 1] = (int)(hi - t * f->nz);
         }
-        NF_HIP(hipMemcpy(f->d_zr, zr.data(), sizeof(int) * zr.size(), hipMemcpyHostToDevice));
-        f->batch_version = f->version;
+        NF_HIP(hipMemcpy(g.zr.get(), zr.data(), sizeof(int) * zr.size(), hipMemcpyHostToDevice));
+        g.batch_version = f->version;
     }
     FluxArgs a{};
     a.u = f->u;
@@ -367,34 +350,34 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
     a.nx = f->nx;
     a.z0 = 0;
     a.z1 = (int)f->nz;
-    a.thickness = f->d_thick;
-    a.arcE = f->d_arcE;
-    a.arcN = f->d_arcN;
+    a.thickness = f->thick.get();
+    a.arcE = g.arcE.get();
+    a.arcN = g.arcN.get();
     a.fill = f->fill;
     a.fill2 = f->fill2;
     a.scale = kEarthRadiusSv / 1.e6;
     a.sverdrup = f->sverdrup;
-    a.iV = f->d_iVb;
-    a.absU = f->d_absb;
-    a.absV = f->d_absb + f->ncell;
-    a.maxbits = f->d_maxbits;
+    a.iV = g.iVb.get();
+    a.absU = g.absb.get();
+    a.absV = g.absb.get() + f->ncell;
+    a.maxbits = g.maxbits.get();
     a.batch.nsteps = (int)f->nt;
     a.batch.in_stride = f->nz * f->ncell;
-    a.batch.zr = f->d_zr;
+    a.batch.zr = g.zr.get();
     if (f->timing) {
         NF_TRY(field_timed_flux(f, a));
     } else {
         NF_TRY(launch_flux(a, f->stream));
     }
     if (rowlen > 0) {
-        NF_TRY(launch_integral(f->ws, f->d_iVb, f->ncell, 2, f->nx, f->d_tr_off, (int)f->polylines.size(), f->d_scratchb,
-                               rows_dev, f->stream, (int)f->nt, (long)(4 * n), rowlen));
+        NF_TRY(launch_integral(f->ws, g.iVb.get(), f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(),
+                               g.scratchb.get(), rows_dev, f->stream, (int)f->nt, (long)(4 * n), rowlen));
         NF_TRY(field_timed_k3_end(f));
     }
     // the resident single-step arrays keep their meaning: they hold the LAST step (what read_step returns)
-    NF_HIP(hipMemcpyAsync(f->d_iV, f->d_iVb + (size_t)(f->nt - 1) * 4 * n, sizeof(double) * 4 * n,
+    NF_HIP(hipMemcpyAsync(g.iV.get(), g.iVb.get() + (size_t)(f->nt - 1) * 4 * n, sizeof(double) * 4 * n,
                           hipMemcpyDeviceToDevice, f->stream));
-    NF_HIP(hipMemcpyAsync(f->d_abs, f->d_absb + (size_t)(f->nt - 1) * 2 * n, sizeof(double) * 2 * n,
+    NF_HIP(hipMemcpyAsync(g.abs.get(), g.absb.get() + (size_t)(f->nt - 1) * 2 * n, sizeof(double) * 2 * n,
                           hipMemcpyDeviceToDevice, f->stream));
     f->derived_stale = false;
     return NF_OK;
@@ -406,7 +389,6 @@ int nf_field_new(nf_field **self)
 try {
     NF_REQUIRE(self, NF_ERR_ARG, "nf_field_new: null argument");
     *self = new nf_field();
-    (*self)->grid_view.owns_xy = false;
     return NF_OK;
 }
 NF_API_CATCH
@@ -414,14 +396,6 @@ int nf_field_del(nf_field **self)
 try {
     if (self && *self) {
         nf_field *f = *self;
-        field_free_geometry(f);
-        dev_free(f->d_thick);
-        if (f->d_stage_u) (void)hipFree(f->d_stage_u);
-        if (f->d_stage_v) (void)hipFree(f->d_stage_v);
-        f->ws.release();
-        dev_free(f->d_tr_off);
-        dev_free(f->d_scratch);
-        dev_free(f->d_row);
         field_drop_events(f);
         field_drop_graph(f);
         delete f;
@@ -452,39 +426,40 @@ try {
     f->nx = nx;
     f->ncell = ny * nx;
     const size_t n = (size_t)f->ncell;
-    NF_TRY(dev_alloc(&f->d_xy, n * 8));
-    NF_TRY(dev_alloc(&f->d_arc4, n * 4));
-    NF_TRY(dev_alloc(&f->d_arcE, n));
-    NF_TRY(dev_alloc(&f->d_arcN, n));
-    NF_TRY(dev_alloc(&f->d_box, 4));
-    NF_TRY(dev_alloc(&f->d_iV, n * 4));
-    NF_TRY(dev_alloc(&f->d_abs, n * 2));
-    NF_TRY(dev_alloc(&f->d_maxbits, 1));
+    nf_field::Geometry &g = f->geo;
+    NF_TRY(g.xy.alloc(n * 8));
+    NF_TRY(g.arc4.alloc(n * 4));
+    NF_TRY(g.arcE.alloc(n));
+    NF_TRY(g.arcN.alloc(n));
+    NF_TRY(g.box.alloc(4));
+    NF_TRY(g.iV.alloc(n * 4));
+    NF_TRY(g.abs.alloc(n * 2));
+    NF_TRY(g.maxbits.alloc(1));
     // field.py:59-63: the per-step arrays start as zeros (row 0's south slot stays zero for ever)
-    NF_HIP(hipMemsetAsync(f->d_iV, 0, sizeof(double) * n * 4, f->stream));
-    NF_HIP(hipMemsetAsync(f->d_abs, 0, sizeof(double) * n * 2, f->stream));
-    NF_HIP(hipMemsetAsync(f->d_maxbits, 0, sizeof(unsigned long long), f->stream));
+    NF_HIP(hipMemsetAsync(g.iV.get(), 0, sizeof(double) * n * 4, f->stream));
+    NF_HIP(hipMemsetAsync(g.abs.get(), 0, sizeof(double) * n * 2, f->stream));
+    NF_HIP(hipMemsetAsync(g.maxbits.get(), 0, sizeof(unsigned long long), f->stream));
     const size_t bytes = n * 4 * elem_size(dtype);
-    DevTmp d_lon, d_lat;   // hipFree waits for the stream's work before releasing
+    DevArray<char> d_lon, d_lat;   // hipFree waits for the stream's work before releasing
     const void *plon = bounds_lon, *plat = bounds_lat;
     if (!on_device) {
         NF_TRY(d_lon.alloc(bytes));
         NF_TRY(d_lat.alloc(bytes));
-        NF_HIP(hipMemcpyAsync(d_lon.p, bounds_lon, bytes, hipMemcpyHostToDevice, f->stream));
-        NF_HIP(hipMemcpyAsync(d_lat.p, bounds_lat, bytes, hipMemcpyHostToDevice, f->stream));
-        plon = d_lon.p;
-        plat = d_lat.p;
+        NF_HIP(hipMemcpyAsync(d_lon.get(), bounds_lon, bytes, hipMemcpyHostToDevice, f->stream));
+        NF_HIP(hipMemcpyAsync(d_lat.get(), bounds_lat, bytes, hipMemcpyHostToDevice, f->stream));
+        plon = d_lon.get();
+        plat = d_lat.get();
     }
-    NF_TRY(launch_geometry(plon, plat, dtype, f->ncell, f->d_xy, f->d_arc4, f->d_arcE, f->d_arcN, f->d_box, f->stream));
+    NF_TRY(launch_geometry(plon, plat, dtype, f->ncell, g.xy.get(), g.arc4.get(), g.arcE.get(), g.arcN.get(), g.box.get(),
+                           f->stream));
     unsigned long long keys[4] = {0, 0, 0, 0};
-    NF_HIP(hipMemcpyAsync(keys, f->d_box, sizeof keys, hipMemcpyDeviceToHost, f->stream));
+    NF_HIP(hipMemcpyAsync(keys, g.box.get(), sizeof keys, hipMemcpyDeviceToHost, f->stream));
     NF_HIP(hipStreamSynchronize(f->stream));
     for (int k = 0; k < 4; ++k) f->box[k] = box_key_to_double(keys[k]);
     f->grid_view.ncell = f->ncell;
-    f->grid_view.d_xy = f->d_xy;
+    f->grid_view.d_xy = g.xy.get();
     f->grid_view.row_length = f->nx;  // (field_free_geometry above dropped the locator of the old corner table)
     ++f->grid_view.version;
-    f->grid_view.owns_xy = false;
     f->weights_built = false;
     ++f->version;
     return NF_OK;
@@ -497,9 +472,8 @@ try {
     NF_REQUIRE(nz > 0 && nz < (1l << 30), NF_ERR_ARG, "nf_field_set_thickness: bad nz");
     NF_NEED_DEVICE();
     nf_field *f = *self;
-    dev_free(f->d_thick);
-    NF_TRY(dev_alloc(&f->d_thick, (size_t)nz));
-    NF_HIP(hipMemcpy(f->d_thick, thickness, sizeof(double) * nz, hipMemcpyHostToDevice));
+    NF_TRY(f->thick.alloc((size_t)nz));
+    NF_HIP(hipMemcpy(f->thick.get(), thickness, sizeof(double) * nz, hipMemcpyHostToDevice));
     f->nz = nz;
     ++f->version;
     return NF_OK;
@@ -513,11 +487,6 @@ try {
     NF_REQUIRE(nt > 0, NF_ERR_ARG, "nf_field_set_uv: nt must be positive");
     NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_uv: dtype must be NF_F64/NF_F32");
     nf_field *f = *self;
-    if (f->uv_dtype != dtype) {  // the staging slabs of host-resident fields are sized by the dtype
-        if (f->d_stage_u) (void)hipFree(f->d_stage_u);
-        if (f->d_stage_v) (void)hipFree(f->d_stage_v);
-        f->d_stage_u = f->d_stage_v = nullptr;
-    }
     f->u = u;
     f->v = v;
     f->nt = nt;
@@ -551,7 +520,7 @@ int nf_field_set_compact(nf_field **self, int compact)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_compact: null field");
     nf_field *f = *self;
-    if (!compact && f->d_iV) NF_TRY(field_ensure_derived(f));   // leaving the mode: the planes become whole again
+    if (!compact && f->geo.iV.get()) NF_TRY(field_ensure_derived(f));   // leaving the mode: the planes become whole again
     f->compact = compact ? 1 : 0;
     ++f->version;
     return NF_OK;
@@ -611,7 +580,7 @@ int nf_field_build_weights(nf_field **self, int numCellsPerBucket, double period
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_build_weights: null field");
     nf_field *f = *self;
-    NF_REQUIRE(f->d_xy, NF_ERR_STATE, "nf_field_build_weights: set_bounds first");
+    NF_REQUIRE(f->geo.xy.get(), NF_ERR_STATE, "nf_field_build_weights: set_bounds first");
     NF_REQUIRE(numCellsPerBucket > 0 && periodX >= 0.0, NF_ERR_ARG, "nf_field_build_weights: bad locator arguments");
     NF_NEED_DEVICE();
     std::vector<double> segs;
@@ -622,7 +591,7 @@ try {
         f->tr_off.push_back((int)cc.size());
     }
     f->weights_built = false;
-    const int bw = build_weights(f->d_xy, f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
+    const int bw = build_weights(f->geo.xy.get(), f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
                                  f->skip_unsupported, f->overlap_warn, nullptr, f->nx);
     if (bw != NF_OK) {
         // over-covered segment (overlapping cells): name the transect and its own segment index, not the batch's
@@ -644,13 +613,10 @@ try {
     // the engine reduces its own planes: fold the (cell, edge) weights onto the unique edges of (eU, eV) (field.py:219-223)
     // (only on request -- nf_tuning_set("edge_weights", 1) -- because the records measure faster: see nf_integral.hip)
     if (integral_uses_edges()) NF_TRY(fold_weights(&f->ws, f->ncell, f->nx, f->stream));
-    dev_free(f->d_tr_off);
-    dev_free(f->d_scratch);
-    dev_free(f->d_row);
-    NF_TRY(dev_alloc(&f->d_tr_off, f->tr_off.size()));
-    NF_TRY(dev_alloc(&f->d_scratch, (size_t)std::max(f->ws.nrec, f->ws.nent)));
-    NF_TRY(dev_alloc(&f->d_row, (size_t)field_row_length(f)));
-    NF_HIP(hipMemcpy(f->d_tr_off, f->tr_off.data(), sizeof(int) * f->tr_off.size(), hipMemcpyHostToDevice));
+    NF_TRY(f->tr_off_dev.alloc(f->tr_off.size()));
+    NF_TRY(f->scratch.alloc((size_t)std::max(f->ws.nrec, f->ws.nent)));
+    NF_TRY(f->row.alloc((size_t)field_row_length(f)));
+    NF_HIP(hipMemcpy(f->tr_off_dev.get(), f->tr_off.data(), sizeof(int) * f->tr_off.size(), hipMemcpyHostToDevice));
     f->weights_built = true;
     ++f->version;
     return NF_OK;
@@ -719,7 +685,7 @@ try {
     if (ws.nent == 0) return NF_OK;
     NF_NEED_DEVICE();
     std::vector<WeightSet::EdgeEntry> h((size_t)ws.nent);
-    NF_HIP(hipMemcpy(h.data(), ws.ent, sizeof(WeightSet::EdgeEntry) * h.size(), hipMemcpyDeviceToHost));
+    NF_HIP(hipMemcpy(h.data(), ws.ent.get(), sizeof(WeightSet::EdgeEntry) * h.size(), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < h.size(); ++k) {   // pure re-indexing of the device result for the caller
         if (elem) elem[k] = h[k].elem;
         if (seg_global) seg_global[k] = h[k].seg;
@@ -742,9 +708,9 @@ try {
     NF_NEED_DEVICE();
     nf_field *f = *self;
     const int rowlen = field_row_length(f);
-    NF_TRY(field_step_async(f, tIndex, (f->weights_built && rowlen > 0) ? f->d_row : nullptr));
+    NF_TRY(field_step_async(f, tIndex, (f->weights_built && rowlen > 0) ? f->row.get() : nullptr));
     if (row_host && rowlen > 0 && f->weights_built)
-        NF_HIP(hipMemcpyAsync(row_host, f->d_row, sizeof(double) * rowlen, hipMemcpyDeviceToHost, f->stream));
+        NF_HIP(hipMemcpyAsync(row_host, f->row.get(), sizeof(double) * rowlen, hipMemcpyDeviceToHost, f->stream));
     NF_HIP(hipStreamSynchronize(f->stream));
     return NF_OK;
 }
@@ -793,20 +759,21 @@ int nf_field_read_step(nf_field **self, double *iV_host, double *eU_host, double
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_read_step: null field");
     nf_field *f = *self;
-    NF_REQUIRE(f->d_iV, NF_ERR_STATE, "nf_field_read_step: set_bounds first");
+    nf_field::Geometry &g = f->geo;
+    NF_REQUIRE(g.iV.get(), NF_ERR_STATE, "nf_field_read_step: set_bounds first");
     NF_NEED_DEVICE();
     if (iV_host || eU_host || eV_host) NF_TRY(field_ensure_derived(f));
     const size_t n = (size_t)f->ncell;
     if (iV_host) {  // re-pack the planes into the reference's (ncell,4) layout, then one D2H into the caller's array
-        if (!f->d_aos) NF_TRY(dev_alloc(&f->d_aos, n * 4));
-        NF_TRY(launch_planes_to_aos(f->d_iV, f->ncell, f->d_aos, f->stream));
-        NF_HIP(hipMemcpyAsync(iV_host, f->d_aos, sizeof(double) * n * 4, hipMemcpyDeviceToHost, f->stream));
+        NF_TRY(g.aos.reserve(n * 4));
+        NF_TRY(launch_planes_to_aos(g.iV.get(), f->ncell, g.aos.get(), f->stream));
+        NF_HIP(hipMemcpyAsync(iV_host, g.aos.get(), sizeof(double) * n * 4, hipMemcpyDeviceToHost, f->stream));
     }
-    if (eU_host) NF_HIP(hipMemcpyAsync(eU_host, f->d_abs, sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
-    if (eV_host) NF_HIP(hipMemcpyAsync(eV_host, f->d_abs + n, sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
+    if (eU_host) NF_HIP(hipMemcpyAsync(eU_host, g.abs.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
+    if (eV_host) NF_HIP(hipMemcpyAsync(eV_host, g.abs.get() + n, sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
     if (max_abs) {
         unsigned long long b = 0;
-        NF_HIP(hipMemcpyAsync(&b, f->d_maxbits, sizeof b, hipMemcpyDeviceToHost, f->stream));
+        NF_HIP(hipMemcpyAsync(&b, g.maxbits.get(), sizeof b, hipMemcpyDeviceToHost, f->stream));
         NF_HIP(hipStreamSynchronize(f->stream));
         memcpy(max_abs, &b, 8);
     }
@@ -817,8 +784,8 @@ NF_API_CATCH
 
 int nf_field_reset_max(nf_field **self)
 try {
-    NF_REQUIRE(self && *self && (*self)->d_maxbits, NF_ERR_STATE, "nf_field_reset_max: set_bounds first");
-    NF_HIP(hipMemsetAsync((*self)->d_maxbits, 0, sizeof(unsigned long long), (*self)->stream));
+    NF_REQUIRE(self && *self && (*self)->geo.maxbits.get(), NF_ERR_STATE, "nf_field_reset_max: set_bounds first");
+    NF_HIP(hipMemsetAsync((*self)->geo.maxbits.get(), 0, sizeof(unsigned long long), (*self)->stream));
     return NF_OK;
 }
 NF_API_CATCH
@@ -826,8 +793,8 @@ NF_API_CATCH
 int nf_field_get_arclengths(nf_field **self, double *arc_host)
 try {
     NF_REQUIRE(self && *self && arc_host, NF_ERR_ARG, "nf_field_get_arclengths: null argument");
-    NF_REQUIRE((*self)->d_arc4, NF_ERR_STATE, "nf_field_get_arclengths: set_bounds first");
-    NF_HIP(hipMemcpy(arc_host, (*self)->d_arc4, sizeof(double) * 4 * (size_t)(*self)->ncell, hipMemcpyDeviceToHost));
+    NF_REQUIRE((*self)->geo.arc4.get(), NF_ERR_STATE, "nf_field_get_arclengths: set_bounds first");
+    NF_HIP(hipMemcpy(arc_host, (*self)->geo.arc4.get(), sizeof(double) * 4 * (size_t)(*self)->ncell, hipMemcpyDeviceToHost));
     return NF_OK;
 }
 NF_API_CATCH
@@ -836,11 +803,11 @@ int nf_field_get_points(nf_field **self, double *points_host)
 try {
     NF_REQUIRE(self && *self && points_host, NF_ERR_ARG, "nf_field_get_points: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->d_xy, NF_ERR_STATE, "nf_field_get_points: set_bounds first");
-    DevTmp points;
-    NF_TRY(points.alloc(sizeof(double) * 12 * (size_t)f->ncell));
-    NF_TRY(launch_points_from_corner_table(f->d_xy, f->ncell, points.as<double>(), f->stream));
-    NF_HIP(hipMemcpyAsync(points_host, points.p, sizeof(double) * 12 * (size_t)f->ncell, hipMemcpyDeviceToHost,
+    NF_REQUIRE(f->geo.xy.get(), NF_ERR_STATE, "nf_field_get_points: set_bounds first");
+    DevArray<double> points;
+    NF_TRY(points.alloc(12 * (size_t)f->ncell));
+    NF_TRY(launch_points_from_corner_table(f->geo.xy.get(), f->ncell, points.get(), f->stream));
+    NF_HIP(hipMemcpyAsync(points_host, points.get(), sizeof(double) * 12 * (size_t)f->ncell, hipMemcpyDeviceToHost,
                           f->stream));
     NF_HIP(hipStreamSynchronize(f->stream));
     return NF_OK;
@@ -851,7 +818,7 @@ int nf_field_get_box(nf_field **self, double *lonmin, double *lonmax, double *la
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_get_box: null field");
     NF_REQUIRE(lonmin && lonmax && latmin && latmax, NF_ERR_ARG, "nf_field_get_box: null argument");
-    NF_REQUIRE((*self)->d_xy, NF_ERR_STATE, "nf_field_get_box: set_bounds first");
+    NF_REQUIRE((*self)->geo.xy.get(), NF_ERR_STATE, "nf_field_get_box: set_bounds first");
     *lonmin = (*self)->box[0];
     *lonmax = (*self)->box[1];
     *latmin = (*self)->box[2];
@@ -866,11 +833,11 @@ try {
     nf_field *f = *self;
     if (which >= 0 && which <= 2) NF_TRY(field_ensure_derived(f));   // compact mode: the derived planes on demand
     switch (which) {
-        case 0: *dev = f->d_iV; break;
-        case 1: *dev = f->d_abs; break;
-        case 2: *dev = f->d_abs ? f->d_abs + f->ncell : nullptr; break;
-        case 3: *dev = f->d_arc4; break;
-        case 4: *dev = f->d_xy; break;
+        case 0: *dev = f->geo.iV.get(); break;
+        case 1: *dev = f->geo.abs.get(); break;
+        case 2: *dev = f->geo.abs.get() ? f->geo.abs.get() + f->ncell : nullptr; break;
+        case 3: *dev = f->geo.arc4.get(); break;
+        case 4: *dev = f->geo.xy.get(); break;
         default: NF_REQUIRE(false, NF_ERR_ARG, "nf_field_device_ptr: unknown array id");
     }
     return NF_OK;
@@ -880,7 +847,7 @@ NF_API_CATCH
 int nf_field_grid(nf_field **self, Grid_t **grid)
 try {
     NF_REQUIRE(self && *self && grid, NF_ERR_ARG, "nf_field_grid: null argument");
-    NF_REQUIRE((*self)->d_xy, NF_ERR_STATE, "nf_field_grid: set_bounds first");
+    NF_REQUIRE((*self)->geo.xy.get(), NF_ERR_STATE, "nf_field_grid: set_bounds first");
     *grid = &(*self)->grid_view;
     return NF_OK;
 }

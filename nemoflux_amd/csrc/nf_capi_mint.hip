@@ -13,14 +13,16 @@ struct PolylineIntegral_t {
     bool locator = false;
     double periodX = 0.0;
     WeightSet ws;
-    int *d_tr_off = nullptr;
-    double *d_scratch = nullptr;
-    double *d_row = nullptr;
-    // getIntegral on a HOST array stages only the cells the weights touch (GatherStage): the record cell ids stay on the
-    // host after computeWeights, the gathered (nrec,4) rows are indexed by RECORD NUMBER on the device (d_iota = 0..nrec-1)
-    std::vector<int> h_cell;
-    GatherStage stage;
-    int *d_iota = nullptr;
+    struct Reduction {          // what computeWeights builds besides the weights: replaced whole by the next one
+        DevArray<int> tr_off;
+        DevArray<double> scratch;
+        DevArray<double> row;   // allocated last: its presence means "weights are ready"
+        // getIntegral on a HOST array stages only the cells the weights touch (GatherStage): the record cell ids stay on the
+        // host after computeWeights, the gathered (nrec,4) rows are indexed by RECORD NUMBER on the device (iota = 0..nrec-1)
+        std::vector<int> h_cell;
+        GatherStage stage;
+        DevArray<int> iota;
+    } r;
     long grid_version = -1;     // the grid build the weights belong to
     int nseg = 0;
     int skip_unsupported = 1;   // mnt_polylineintegral_setUnsupportedCells (default 'skip': mint's computeWeights never fails there)
@@ -40,7 +42,6 @@ int mnt_grid_del(Grid_t **self)
 try {
     if (self && *self) {
         { std::lock_guard<std::mutex> lock((*self)->boxes.mtx); (*self)->boxes.release(); }   // waits for a build that walks them
-        if ((*self)->owns_xy) dev_free((*self)->d_xy);
         delete *self;
         *self = nullptr;
     }
@@ -64,14 +65,14 @@ try {
     NF_NEED_DEVICE();
     std::lock_guard<std::mutex> lock(g->boxes.mtx);   // no computeWeights / findPoints of another thread is inside the locator
     g->boxes.release();             // they describe the old points
-    if (g->owns_xy) dev_free(g->d_xy);
-    g->owns_xy = true;
+    g->d_xy = nullptr;
     g->ncell = (long)ncells;
-    DevTmp points;
-    NF_TRY(points.alloc(sizeof(double) * 12 * (size_t)ncells));
-    NF_TRY(dev_alloc(&g->d_xy, (size_t)ncells * 8));
-    NF_HIP(hipMemcpy(points.p, g->host_points, sizeof(double) * 12 * (size_t)ncells, hipMemcpyHostToDevice));
-    NF_TRY(launch_corner_table_from_points(points.as<double>(), g->ncell, g->d_xy, nullptr));
+    DevArray<double> points;
+    NF_TRY(points.alloc(12 * (size_t)ncells));
+    NF_TRY(g->own_xy.alloc((size_t)ncells * 8));
+    g->d_xy = g->own_xy.get();
+    NF_HIP(hipMemcpy(points.get(), g->host_points, sizeof(double) * 12 * (size_t)ncells, hipMemcpyHostToDevice));
+    NF_TRY(launch_corner_table_from_points(points.get(), g->ncell, g->d_xy, nullptr));
     NF_HIP(hipDeviceSynchronize());
     ++g->version;
     return NF_OK;
@@ -103,11 +104,11 @@ try {
     const double *p = g->host_points;
     if (!p) {  // grid view of a Field: rebuild (lon,lat,0) from the corner table
         NF_NEED_DEVICE();
-        DevTmp points;
-        NF_TRY(points.alloc(sizeof(double) * 12 * (size_t)g->ncell));
-        NF_TRY(launch_points_from_corner_table(g->d_xy, g->ncell, points.as<double>(), nullptr));
+        DevArray<double> points;
+        NF_TRY(points.alloc(12 * (size_t)g->ncell));
+        NF_TRY(launch_points_from_corner_table(g->d_xy, g->ncell, points.get(), nullptr));
         pts.resize((size_t)g->ncell * 12);
-        NF_HIP(hipMemcpy(pts.data(), points.p, sizeof(double) * pts.size(), hipMemcpyDeviceToHost));
+        NF_HIP(hipMemcpy(pts.data(), points.get(), sizeof(double) * pts.size(), hipMemcpyDeviceToHost));
         p = pts.data();
     }
     FILE *f = fopen(fileName, "w");
@@ -135,14 +136,7 @@ NF_API_CATCH
 int mnt_polylineintegral_del(PolylineIntegral_t **self)
 try {
     if (self && *self) {
-        PolylineIntegral_t *p = *self;
-        p->ws.release();
-        dev_free(p->d_tr_off);
-        dev_free(p->d_scratch);
-        dev_free(p->d_row);
-        dev_free(p->d_iota);
-        p->stage.release();
-        delete p;
+        delete *self;
         *self = nullptr;
     }
     return NF_OK;
@@ -209,12 +203,7 @@ try {
     p->nseg = polyline_segments(xyz, npoints, counterclock, segs, cc);
     // whatever a previous computeWeights left is gone first: after a refused build getIntegral must say "computeWeights
     // first", not launch on buffers sized for another polyline
-    dev_free(p->d_tr_off);
-    dev_free(p->d_scratch);
-    dev_free(p->d_row);
-    dev_free(p->d_iota);
-    p->stage.release();
-    p->h_cell.clear();
+    p->r = {};
     {
         // objects on one Grid share its locator cache: (re)built and walked under the grid's lock, which is held until the
         // build's kernels have finished (build_weights returns drained) -- two host threads, each with its own
@@ -223,33 +212,36 @@ try {
         NF_TRY(build_weights(p->grid->d_xy, p->grid->ncell, segs.data(), cc.data(), p->nseg, p->periodX, &p->ws, nullptr,
                              p->skip_unsupported, p->overlap_warn, &p->grid->boxes, p->grid->row_length));
     }
-    NF_TRY(dev_alloc(&p->d_tr_off, 2));
-    NF_TRY(dev_alloc(&p->d_scratch, (size_t)p->ws.nrec));
+    auto &r = p->r;
+    NF_TRY(r.tr_off.alloc(2));
+    NF_TRY(r.scratch.alloc((size_t)p->ws.nrec));
     const int off[2] = {0, p->nseg};
-    NF_HIP(hipMemcpy(p->d_tr_off, off, sizeof off, hipMemcpyHostToDevice));
+    NF_HIP(hipMemcpy(r.tr_off.get(), off, sizeof off, hipMemcpyHostToDevice));
     // what getIntegral needs to stage a host array sparsely: the cells of the records, here; their row numbers, there
-    p->h_cell.resize((size_t)p->ws.nrec);
-    NF_TRY(dev_alloc(&p->d_iota, (size_t)p->ws.nrec));
+    r.h_cell.resize((size_t)p->ws.nrec);
+    NF_TRY(r.iota.alloc((size_t)p->ws.nrec));
     if (p->ws.nrec > 0) {
-        NF_HIP(hipMemcpy(p->h_cell.data(), p->ws.cell, sizeof(int) * (size_t)p->ws.nrec, hipMemcpyDeviceToHost));
+        NF_HIP(hipMemcpy(r.h_cell.data(), p->ws.cell.get(), sizeof(int) * (size_t)p->ws.nrec, hipMemcpyDeviceToHost));
         std::vector<int> iota((size_t)p->ws.nrec);
         for (long k = 0; k < p->ws.nrec; ++k) iota[(size_t)k] = (int)k;
-        NF_HIP(hipMemcpy(p->d_iota, iota.data(), sizeof(int) * iota.size(), hipMemcpyHostToDevice));
+        NF_HIP(hipMemcpy(r.iota.get(), iota.data(), sizeof(int) * iota.size(), hipMemcpyHostToDevice));
     }
-    NF_TRY(p->stage.resize(p->ws.nrec));
-    NF_TRY(dev_alloc(&p->d_row, (size_t)p->nseg + 1));   // last: its presence means "weights are ready"
+    NF_TRY(r.stage.resize(p->ws.nrec));
+    NF_TRY(r.row.alloc((size_t)p->nseg + 1));   // last: its presence means "weights are ready"
     p->grid_version = p->grid->version;
     return NF_OK;
 }
 NF_API_CATCH
 
 // the reduction of one object: gather + wavefront segmented scan + the two finalize kernels, then the row comes back
-static int pli_reduce(PolylineIntegral_t *p, const WeightSet &ws, const double *data_dev, long nrows, double *result,
+// rec_cells: the row of data_dev each record reads (nullptr: its cell)
+static int pli_reduce(PolylineIntegral_t *p, const int *rec_cells, const double *data_dev, long nrows, double *result,
                       double *seg_totals_host)
 {
-    NF_TRY(launch_integral(ws, data_dev, nrows, 0, 0, p->d_tr_off, 1, p->d_scratch, p->d_row, nullptr));
+    NF_TRY(launch_integral(p->ws, data_dev, nrows, 0, 0, p->r.tr_off.get(), 1, p->r.scratch.get(), p->r.row.get(), nullptr, 1, 0,
+                           0, rec_cells));
     std::vector<double> row((size_t)p->nseg + 1);
-    NF_HIP(hipMemcpy(row.data(), p->d_row, sizeof(double) * row.size(), hipMemcpyDeviceToHost));
+    NF_HIP(hipMemcpy(row.data(), p->r.row.get(), sizeof(double) * row.size(), hipMemcpyDeviceToHost));
     *result = row[p->nseg];
     if (seg_totals_host) memcpy(seg_totals_host, row.data(), sizeof(double) * p->nseg);
     return NF_OK;
@@ -257,7 +249,7 @@ static int pli_reduce(PolylineIntegral_t *p, const WeightSet &ws, const double *
 
 static int pli_ready(PolylineIntegral_t *p, int placement)
 {
-    NF_REQUIRE(p->d_row, NF_ERR_STATE, "mnt_polylineintegral_getIntegral: computeWeights first");
+    NF_REQUIRE(p->r.row.get(), NF_ERR_STATE, "mnt_polylineintegral_getIntegral: computeWeights first");
     NF_REQUIRE(p->grid && p->grid_version == p->grid->version, NF_ERR_STATE,
                "mnt_polylineintegral_getIntegral: the grid was rebuilt after computeWeights (the weights index the old cells): computeWeights again");
     NF_REQUIRE(placement == MNT_CELL_BY_CELL_DATA, NF_ERR_ARG,
@@ -272,7 +264,7 @@ try {
     PolylineIntegral_t *p = *self;
     NF_TRY(pli_ready(p, placement));
     NF_NEED_DEVICE();
-    return pli_reduce(p, p->ws, data_dev, p->grid->ncell, result, seg_totals_host);
+    return pli_reduce(p, nullptr, data_dev, p->grid->ncell, result, seg_totals_host);
 }
 NF_API_CATCH
 
@@ -288,15 +280,8 @@ try {
     NF_REQUIRE(p->grid, NF_ERR_STATE, "mnt_polylineintegral_getIntegral: setGrid first");
     NF_TRY(pli_ready(p, placement));
     NF_NEED_DEVICE();
-    NF_TRY(p->stage.upload(data, p->h_cell.data()));
-    WeightSet rows;              // a view of the object's records whose cell index is the record number
-    rows.nrec = p->ws.nrec;
-    rows.cell = p->d_iota;
-    rows.w4 = p->ws.w4;
-    rows.seg = p->ws.seg;
-    rows.nseg = p->ws.nseg;
-    rows.seg_start = p->ws.seg_start;
-    return pli_reduce(p, rows, p->stage.d, p->ws.nrec, result, nullptr);
+    NF_TRY(p->r.stage.upload(data, p->r.h_cell.data()));
+    return pli_reduce(p, p->r.iota.get(), p->r.stage.d.get(), p->ws.nrec, result, nullptr);   // record k reads row k
 }
 NF_API_CATCH
 
@@ -304,7 +289,7 @@ int mnt_polylineintegral_getCoverage(PolylineIntegral_t **self, double *coverage
 try {
     NF_REQUIRE(self && *self && coverage, NF_ERR_ARG, "mnt_polylineintegral_getCoverage: null argument");
     // also readable after a build that was refused for over-coverage (the message names one segment; this has them all)
-    NF_REQUIRE((*self)->d_row || !(*self)->ws.coverage.empty(), NF_ERR_STATE,
+    NF_REQUIRE((*self)->r.row.get() || !(*self)->ws.coverage.empty(), NF_ERR_STATE,
                "mnt_polylineintegral_getCoverage: computeWeights first");
     const std::vector<double> &c = (*self)->ws.coverage;
     if (!c.empty()) memcpy(coverage, c.data(), sizeof(double) * c.size());
@@ -334,27 +319,17 @@ struct VectorInterp_t {
     Grid_t *grid = nullptr;
     bool locator = false;
     double periodX = 0.0;
-    long npts = 0;
-    double *d_targets = nullptr, *d_pcoords = nullptr, *d_vectors = nullptr;
-    long *d_cell = nullptr;
-    unsigned long long *d_best = nullptr;
-    // getFaceVectors on a HOST array stages only the located cells, one (4) row per target point (GatherStage)
-    std::vector<long> h_cell;
-    GatherStage stage;
+    struct Points {             // what findPoints builds: replaced whole by the next one
+        long n = 0;
+        DevArray<double> targets, pcoords, vectors;
+        DevArray<long> cell;
+        DevArray<unsigned long long> best;
+        // getFaceVectors on a HOST array stages only the located cells, one (4) row per target point (GatherStage)
+        std::vector<long> h_cell;
+        GatherStage stage;
+    } pts;
     long grid_version = -1;     // the grid build the located cells belong to
 };
-
-static void vi_free_points(VectorInterp_t *v)
-{
-    dev_free(v->d_targets);
-    dev_free(v->d_pcoords);
-    dev_free(v->d_vectors);
-    dev_free(v->d_cell);
-    dev_free(v->d_best);
-    v->stage.release();
-    v->h_cell.clear();
-    v->npts = 0;
-}
 
 extern "C" {
 
@@ -368,7 +343,6 @@ NF_API_CATCH
 int mnt_vectorinterp_del(VectorInterp_t **self)
 try {
     if (self && *self) {
-        vi_free_points(*self);
         delete *self;
         *self = nullptr;
     }
@@ -402,28 +376,29 @@ try {
     NF_REQUIRE(v->grid && v->locator, NF_ERR_STATE, "mnt_vectorinterp_findPoints: setGrid/buildLocator first");
     NF_REQUIRE(tol2 >= 0.0, NF_ERR_ARG, "mnt_vectorinterp_findPoints: negative tolerance");
     NF_NEED_DEVICE();
-    vi_free_points(v);
-    v->npts = (long)numPoints;
+    v->pts = {};
+    auto &q = v->pts;
+    q.n = (long)numPoints;
     if (numNotFound) *numNotFound = 0;
     if (numPoints == 0) return NF_OK;
-    NF_TRY(dev_alloc(&v->d_targets, numPoints * 3));
-    NF_TRY(dev_alloc(&v->d_pcoords, numPoints * 2));
-    NF_TRY(dev_alloc(&v->d_vectors, numPoints * 3));
-    NF_TRY(dev_alloc(&v->d_cell, numPoints));
-    NF_TRY(dev_alloc(&v->d_best, numPoints));
-    NF_HIP(hipMemcpy(v->d_targets, targetPoints, sizeof(double) * 3 * numPoints, hipMemcpyHostToDevice));
-    v->h_cell.resize(numPoints);      // the located cells stay on the host too: they address the caller's host arrays
+    NF_TRY(q.targets.alloc(numPoints * 3));
+    NF_TRY(q.pcoords.alloc(numPoints * 2));
+    NF_TRY(q.vectors.alloc(numPoints * 3));
+    NF_TRY(q.cell.alloc(numPoints));
+    NF_TRY(q.best.alloc(numPoints));
+    NF_HIP(hipMemcpy(q.targets.get(), targetPoints, sizeof(double) * 3 * numPoints, hipMemcpyHostToDevice));
+    q.h_cell.resize(numPoints);      // the located cells stay on the host too: they address the caller's host arrays
     {
         std::lock_guard<std::mutex> lock(v->grid->boxes.mtx);   // the grid's locator cache: see computeWeights
-        NF_TRY(launch_find_points(v->grid->d_xy, v->grid->ncell, v->grid->row_length, &v->grid->boxes, v->d_targets, v->npts,
-                                  v->periodX, tol2, v->d_best, v->d_cell, v->d_pcoords, nullptr));
+        NF_TRY(launch_find_points(v->grid->d_xy, v->grid->ncell, v->grid->row_length, &v->grid->boxes, q.targets.get(), q.n,
+                                  v->periodX, tol2, q.best.get(), q.cell.get(), q.pcoords.get(), nullptr));
         // (the blocking copy on the null stream orders itself behind the search: the walk is over when it returns)
-        NF_HIP(hipMemcpy(v->h_cell.data(), v->d_cell, sizeof(long) * numPoints, hipMemcpyDeviceToHost));
+        NF_HIP(hipMemcpy(q.h_cell.data(), q.cell.get(), sizeof(long) * numPoints, hipMemcpyDeviceToHost));
     }
-    NF_TRY(v->stage.resize((long)numPoints));
+    NF_TRY(q.stage.resize((long)numPoints));
     if (numNotFound) {
         size_t n = 0;
-        for (long c : v->h_cell) n += (c < 0);
+        for (long c : q.h_cell) n += (c < 0);
         *numNotFound = n;
     }
     v->grid_version = v->grid->version;
@@ -437,9 +412,10 @@ static int vi_vectors(VectorInterp_t *v, const double *data_dev, int layout, dou
     NF_REQUIRE(v->grid_version == v->grid->version, NF_ERR_STATE,
                "mnt_vectorinterp_getFaceVectors: the grid was rebuilt after findPoints (the located cells are the old grid's): findPoints again");
     NF_NEED_DEVICE();
-    NF_TRY(launch_face_vectors(v->grid->d_xy, v->d_cell, v->d_pcoords, v->npts, data_dev, v->grid->ncell, layout,
-                               v->periodX, v->d_vectors, nullptr));
-    NF_HIP(hipMemcpy(vectors, v->d_vectors, sizeof(double) * 3 * v->npts, hipMemcpyDeviceToHost));
+    const auto &q = v->pts;
+    NF_TRY(launch_face_vectors(v->grid->d_xy, q.cell.get(), q.pcoords.get(), q.n, data_dev, v->grid->ncell, layout, v->periodX,
+                               q.vectors.get(), nullptr));
+    NF_HIP(hipMemcpy(vectors, q.vectors.get(), sizeof(double) * 3 * q.n, hipMemcpyDeviceToHost));
     return NF_OK;
 }
 int mnt_vectorinterp_getFaceVectorsDev(VectorInterp_t **self, const double *data_dev, int layout, double vectors[])
@@ -448,7 +424,7 @@ try {
     VectorInterp_t *v = *self;
     NF_REQUIRE(v->grid, NF_ERR_STATE, "mnt_vectorinterp_getFaceVectors: setGrid first");
     NF_REQUIRE(layout == 0 || layout == 1, NF_ERR_ARG, "mnt_vectorinterp_getFaceVectorsDev: layout must be 0 ((ncell,4)) or 1 ([4][ncell] planes)");
-    if (v->npts == 0) return NF_OK;
+    if (v->pts.n == 0) return NF_OK;
     return vi_vectors(v, data_dev, layout, vectors);
 }
 NF_API_CATCH
@@ -461,20 +437,20 @@ try {
     NF_REQUIRE(v->grid, NF_ERR_STATE, "mnt_vectorinterp_getFaceVectors: setGrid first");
     NF_REQUIRE(placement == MNT_CELL_BY_CELL_DATA, NF_ERR_ARG,
                "mnt_vectorinterp_getFaceVectors: only CELL_BY_CELL_DATA (placement=0) is supported (field.py:94-95)");
-    if (v->npts == 0) return NF_OK;
+    if (v->pts.n == 0) return NF_OK;
     NF_NEED_DEVICE();
-    NF_TRY(v->stage.upload(data, v->h_cell.data()));
-    return vi_vectors(v, v->stage.d, 2, vectors);
+    NF_TRY(v->pts.stage.upload(data, v->pts.h_cell.data()));
+    return vi_vectors(v, v->pts.stage.d.get(), 2, vectors);
 }
 NF_API_CATCH
 int mnt_vectorinterp_getCells(VectorInterp_t **self, long long *cell_ids, double *pcoords)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "mnt_vectorinterp_getCells: null argument");
     VectorInterp_t *v = *self;
-    if (v->npts == 0) return NF_OK;
+    if (v->pts.n == 0) return NF_OK;
     NF_NEED_DEVICE();
-    if (cell_ids) NF_HIP(hipMemcpy(cell_ids, v->d_cell, sizeof(long) * v->npts, hipMemcpyDeviceToHost));
-    if (pcoords) NF_HIP(hipMemcpy(pcoords, v->d_pcoords, sizeof(double) * 2 * v->npts, hipMemcpyDeviceToHost));
+    if (cell_ids) NF_HIP(hipMemcpy(cell_ids, v->pts.cell.get(), sizeof(long) * v->pts.n, hipMemcpyDeviceToHost));
+    if (pcoords) NF_HIP(hipMemcpy(pcoords, v->pts.pcoords.get(), sizeof(double) * 2 * v->pts.n, hipMemcpyDeviceToHost));
     return NF_OK;
 }
 NF_API_CATCH

@@ -187,14 +187,63 @@ long tuning_version();
 int launch_planes_to_aos(const double *planes, long ncell, double *aos, hipStream_t s);
 // [flux-fingerprint-end]
 
+// The one owner of a device allocation: a pointer and its element count, freed by the destructor (hipFree waits for the
+// device).  Move-only.  size() == 0 means nothing is held -- also after a failed allocation, so the next call tries again.
+template <typename T>
+class DevArray {
+public:
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    DevArray(DevArray &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    DevArray &operator=(DevArray &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = o.p_, n_ = o.n_;
+            o.p_ = nullptr, o.n_ = 0;
+        }
+        return *this;
+    }
+    ~DevArray() { reset(); }
+    // free, then allocate exactly n elements (n == 0: one element, at least 16 bytes)
+    int alloc(size_t n)
+    {
+        reset();
+        void *q = nullptr;
+        NF_HIP(hipMalloc(&q, n ? sizeof(T) * n : (sizeof(T) > 16 ? sizeof(T) : 16)));
+        p_ = static_cast<T *>(q);
+        n_ = n ? n : 1;
+        return NF_OK;
+    }
+    // grow only: re-allocates (the contents are lost) when fewer than n elements are held; *grown says whether it did
+    int reserve(size_t n, bool *grown = nullptr)
+    {
+        const bool g = n_ == 0 || n_ < n;
+        if (grown) *grown = g;
+        return g ? alloc(n) : NF_OK;
+    }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr, n_ = 0;
+    }
+    T *get() const { return p_; }
+    size_t size() const { return n_; }
+
+private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+
 // K2: batched polyline weights.
 struct WeightSet {  // device-resident result: one record per (target segment, crossed cell), sorted by segment, ta
     long nrec = 0;
-    int *cell = nullptr;       // cell id of the record
-    double *w4 = nullptr;      // 4 edge weights per record (S,E,N,W), multiplicity applied
-    int *seg = nullptr;        // global segment id of the record
+    DevArray<int> cell;        // cell id of the record
+    DevArray<double> w4;       // 4 edge weights per record (S,E,N,W), multiplicity applied
+    DevArray<int> seg;         // global segment id of the record
     int nseg = 0;              // total target segments
-    int *seg_start = nullptr;  // (nseg+1) CSR over records
+    DevArray<int> seg_start;   // (nseg+1) CSR over records
     // host: fraction of every target segment that lies inside cells of the grid (sum of coef*(tb-ta) over its records);
     // 1 = inside the grid, each point counted once; < 1 = part of the segment is outside (contributes 0, like mint)
     std::vector<double> coverage;
@@ -210,10 +259,10 @@ struct WeightSet {  // device-resident result: one record per (target segment, c
         double w;   // summed weight
     };
     long nent = 0;
-    EdgeEntry *ent = nullptr;    // sorted by (segment, elem)
-    int *ent_start = nullptr;    // (nseg+1) CSR over entries
+    DevArray<EdgeEntry> ent;     // sorted by (segment, elem)
+    DevArray<int> ent_start;     // (nseg+1) CSR over entries
     long entries() const { return 4 * nrec; }  // mint's view: (cell*4+edge, weight) entries
-    void release();
+    void release() { *this = WeightSet(); }
 };
 // builds ws.ent / ws.ent_start from the records, for a grid of nx columns (row-0 south slots carry no flux: dropped)
 int fold_weights(WeightSet *ws, long ncell, long nx, hipStream_t s);
@@ -226,8 +275,9 @@ int weights_to_host(const WeightSet &ws, int64_t *cell_edge, double *weight, int
 // period, kept by whoever owns the corner table -- mint's buildLocator builds it once per PolylineIntegral; here a Grid_t keeps
 // it for all the PolylineIntegral objects made on it (fluxviz / fluxplot make one per transect).  build_weights fills it when
 // it does not match the grid it is called with.
+struct Box4;   // nf_locator.h
 struct LocatorBoxes {
-    std::vector<void *> level;   // level[l]: HBM array of the boxes of level l (0 = cells)
+    std::vector<DevArray<Box4>> level;   // level[l]: the boxes of level l (0 = cells)
     std::vector<long> count;
     const double *xy = nullptr;  // the corner table the boxes were built from
     long ncell = 0;
@@ -238,7 +288,6 @@ struct LocatorBoxes {
     // PolylineIntegral objects on one Grid are serialised here instead of racing on release() (round-5 advisor).
     std::mutex mtx;
     void release();
-    ~LocatorBoxes() { release(); }
 };
 // overlap_warn: 0 = a target segment covered more than once (over_covered) is an error (default); 1 = the build goes through,
 // out->over_seg names the first such segment and the coverage says how much (the caller warns)
@@ -258,11 +307,12 @@ void weights_trim_scratch();
 // signed members only (planes = 2; needs nx for the neighbour indexing).
 // nsteps > 1: step tb gathers from data + tb*data_stride and writes row + tb*row_stride (scratch: nsteps*ws.nrec).
 // planes = 2 uses the unique-edge entries when fold_weights built them (scratch: nsteps * max(ws.nrec, ws.nent)).
+// rec_cells: the row of data each record reads (nullptr = ws.cell; a Level-1 object's rows gathered per record: 0..nrec-1).
 void integral_use_edges(int on);
 int integral_uses_edges();
 int launch_integral(const WeightSet &ws, const double *data, long ncell, int planes, long nx,
                     const int *tr_offsets_dev, int ntransect, double *scratch, double *row, hipStream_t s,
-                    int nsteps = 1, long data_stride = 0, long row_stride = 0);
+                    int nsteps = 1, long data_stride = 0, long row_stride = 0, const int *rec_cells = nullptr);
 
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q

@@ -293,18 +293,11 @@ int launch_datagen_uv(void *u, void *v, int dtype, long t0, long t1, long nt, lo
     const double dyy = lat_uses_dx ? dx : dy;
     const double dz = (zmax - zmin) / (double)nz;  // datagen.py:35
     const long ncell = ny * nx, nnode = (ny + 1) * (nx + 1);
-    double *h = nullptr, *ds21 = nullptr, *ds23 = nullptr, *gtab = nullptr;
-    struct FreeOnExit {       // every return path, the early ones of NF_HIP included (round-4 advisor)
-        double *&a, *&b, *&c, *&d;
-        ~FreeOnExit()
-        {
-            for (double *p : {a, b, c, d})
-                if (p) (void)hipFree(p);
-        }
-    } cleanup{h, ds21, ds23, gtab};
-    NF_HIP(hipMalloc((void **)&h, sizeof(double) * nnode));
-    NF_HIP(hipMalloc((void **)&ds21, sizeof(double) * ncell));
-    NF_HIP(hipMalloc((void **)&ds23, sizeof(double) * ncell));
+    DevArray<double> d_h, d_ds21, d_ds23, d_gtab;   // freed on every return path, the early ones of NF_HIP included
+    NF_TRY(d_h.alloc((size_t)nnode));
+    NF_TRY(d_ds21.alloc((size_t)ncell));
+    NF_TRY(d_ds23.alloc((size_t)ncell));
+    double *const h = d_h.get(), *const ds21 = d_ds21.get(), *const ds23 = d_ds23.get();
     hipLaunchKernelGGL(k_node_h, dim3((unsigned)((nnode + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, h,
                        (unsigned)(ny + 1), (unsigned)(nx + 1), xmin, ymin, dx, dyy, psi);
     const unsigned nb = (unsigned)((ncell + kBlock - 1) / kBlock);
@@ -317,8 +310,9 @@ int launch_datagen_uv(void *u, void *v, int dtype, long t0, long t1, long nt, lo
         const long t = t0 + sl / nz, k = sl % nz;
         gh[(size_t)sl] = psi_g(psi, zmin + ((double)k + 0.5) * dz, t, nt);   // z: datagen.py:38
     }
-    NF_HIP(hipMalloc((void **)&gtab, sizeof(double) * gh.size()));
-    NF_HIP(hipMemcpyAsync(gtab, gh.data(), sizeof(double) * gh.size(), hipMemcpyHostToDevice, s));
+    NF_TRY(d_gtab.alloc(gh.size()));
+    const double *const gtab = d_gtab.get();
+    NF_HIP(hipMemcpyAsync(d_gtab.get(), gh.data(), sizeof(double) * gh.size(), hipMemcpyHostToDevice, s));
     if (nslab > 0) {
         const int vec = dtype == NF_F64 ? 2 : 4;
         const bool rows = g_uv_rows && nx % vec == 0 && (uintptr_t)u % 16 == 0 && (uintptr_t)v % 16 == 0;

@@ -191,10 +191,9 @@ __global__ __launch_bounds__(kBlock) void k_place16(const uint8_t *__restrict__ 
 }
 
 struct Inflater {
-    uint8_t *d_comp = nullptr, *d_tmp = nullptr;
-    InflateJob *d_jobs = nullptr;
-    int *d_status = nullptr;
-    size_t comp_cap = 0, tmp_cap = 0, jobs_cap = 0;
+    DevArray<uint8_t> d_comp, d_tmp;
+    DevArray<InflateJob> d_jobs;
+    DevArray<int> d_status;
     // early upload (nf_inflater_upload, typically from a staging thread while the GPU decodes another group)
     hipStream_t copy_stream = nullptr;
     size_t uploaded = 0;          // bytes of compressed data sitting in d_comp, 0 = none
@@ -205,16 +204,9 @@ struct Inflater {
     // overlap in time can share the rest (a file-backed Field then holds one decoded-group scratch, not two).
     Inflater *scratch_owner = nullptr;
     std::vector<Inflater *> borrowers;   // the inflaters that use THIS one's scratch: detached when this one is deleted
-    void release()
+    ~Inflater()
     {
-        for (void *p : {(void *)d_comp, (void *)d_tmp, (void *)d_jobs, (void *)d_status})
-            if (p) (void)hipFree(p);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        copy_stream = nullptr;
-        d_comp = d_tmp = nullptr;
-        d_jobs = nullptr;
-        d_status = nullptr;
-        comp_cap = tmp_cap = jobs_cap = uploaded = 0;
     }
 };
 
@@ -222,15 +214,10 @@ static size_t comp_padded(size_t comp_bytes) { return ((comp_bytes + 3) & ~(size
 
 static int comp_reserve(Inflater *h, size_t comp_pad)
 {
-    if (h->comp_cap < comp_pad) {
-        if (h->d_comp) (void)hipFree(h->d_comp);
-        h->d_comp = nullptr;
-        h->comp_cap = 0;
-        h->uploaded = 0;
-        NF_HIP(hipMalloc((void **)&h->d_comp, comp_pad));
-        h->comp_cap = comp_pad;
-    }
-    return NF_OK;
+    bool grown = false;
+    const int rc = h->d_comp.reserve(comp_pad, &grown);
+    if (grown) h->uploaded = 0;      // what was uploaded is gone with the old buffer
+    return rc;
 }
 
 // compressed bytes -> HBM, on the inflater's own stream, complete at return: the call a staging thread makes while the GPU
@@ -244,8 +231,8 @@ int inflater_upload(Inflater *h, const void *comp_host, size_t comp_bytes)
     h->uploaded = 0;
     NF_TRY_RC(comp_reserve(h, comp_pad));
     const size_t tail = comp_bytes & ~(size_t)3;
-    NF_HIP(hipMemsetAsync(h->d_comp + tail, 0, comp_pad - tail, h->copy_stream));
-    NF_HIP(hipMemcpyAsync(h->d_comp, comp_host, comp_bytes, hipMemcpyHostToDevice, h->copy_stream));
+    NF_HIP(hipMemsetAsync(h->d_comp.get() + tail, 0, comp_pad - tail, h->copy_stream));
+    NF_HIP(hipMemcpyAsync(h->d_comp.get(), comp_host, comp_bytes, hipMemcpyHostToDevice, h->copy_stream));
     NF_HIP(hipStreamSynchronize(h->copy_stream));
     h->uploaded = comp_bytes;
     return NF_OK;
@@ -282,10 +269,10 @@ int inflater_upload_ranges(Inflater *h, const unsigned long long *src_addr, cons
     for (long long i = 0; i < n; ++i)
         NF_REQUIRE(len[i] >= 0 && dst_off[i] >= 0 && (size_t)(dst_off[i] + len[i]) <= comp_bytes, NF_ERR_ARG,
                    "inflate upload: a range lies outside the compressed buffer");
-    NF_HIP(hipMemsetAsync(h->d_comp, 0, comp_pad, h->copy_stream));      // gaps between the ranges and the padding read as zeros
+    NF_HIP(hipMemsetAsync(h->d_comp.get(), 0, comp_pad, h->copy_stream));      // gaps between the ranges and the padding read as zeros
     for (long long i = 0; i < n; ++i)
         if (len[i])
-            NF_HIP(hipMemcpyAsync(h->d_comp + dst_off[i], (const void *)(uintptr_t)src_addr[i], (size_t)len[i],
+            NF_HIP(hipMemcpyAsync(h->d_comp.get() + dst_off[i], (const void *)(uintptr_t)src_addr[i], (size_t)len[i],
                                   hipMemcpyHostToDevice, h->copy_stream));
     NF_HIP(hipStreamSynchronize(h->copy_stream));
     h->uploaded = comp_bytes;
@@ -328,23 +315,11 @@ int inflater_run(Inflater *h, const void *comp_host, size_t comp_bytes, const lo
     const size_t tmp_bytes = (size_t)chunk_bytes * (size_t)n;
     if (comp_host) NF_TRY_RC(comp_reserve(h, comp_pad));
     Inflater *so = h->scratch_owner ? h->scratch_owner : h;    // whose decode scratch this run uses
-    if (so->tmp_cap < tmp_bytes) {
-        if (so->d_tmp) (void)hipFree(so->d_tmp);
-        so->d_tmp = nullptr;
-        so->tmp_cap = 0;
-        NF_HIP(hipMalloc((void **)&so->d_tmp, tmp_bytes));
-        so->tmp_cap = tmp_bytes;
-    }
-    if (so->jobs_cap < (size_t)n) {
-        if (so->d_jobs) (void)hipFree(so->d_jobs);
-        if (so->d_status) (void)hipFree(so->d_status);
-        so->d_jobs = nullptr;
-        so->d_status = nullptr;
-        so->jobs_cap = 0;
-        NF_HIP(hipMalloc((void **)&so->d_jobs, sizeof(InflateJob) * (size_t)n));
-        NF_HIP(hipMalloc((void **)&so->d_status, sizeof(int) * (size_t)n));
-        so->jobs_cap = (size_t)n;
-    }
+    NF_TRY_RC(so->d_tmp.reserve(tmp_bytes));
+    NF_TRY_RC(so->d_jobs.reserve((size_t)n));
+    NF_TRY_RC(so->d_status.reserve((size_t)n));
+    uint8_t *const d_tmp = so->d_tmp.get();
+    InflateJob *const d_jobs = so->d_jobs.get();
     // From here on work is queued on `s` that reads `jobs` (pageable host memory) and writes the scratch -- which another
     // inflater may share and use from ITS stream next: whatever makes this function return early, the stream is drained first
     struct DrainOnExit {
@@ -354,12 +329,12 @@ int inflater_run(Inflater *h, const void *comp_host, size_t comp_bytes, const lo
     if (comp_host) {
         const size_t tail = comp_bytes & ~(size_t)3;                    // zero the last partial word and the padding behind the data
         h->uploaded = 0;
-        NF_HIP(hipMemsetAsync(h->d_comp + tail, 0, comp_pad - tail, s));
-        NF_HIP(hipMemcpyAsync(h->d_comp, comp_host, comp_bytes, hipMemcpyHostToDevice, s));
+        NF_HIP(hipMemsetAsync(h->d_comp.get() + tail, 0, comp_pad - tail, s));
+        NF_HIP(hipMemcpyAsync(h->d_comp.get(), comp_host, comp_bytes, hipMemcpyHostToDevice, s));
     }
-    NF_HIP(hipMemcpyAsync(so->d_jobs, jobs.data(), sizeof(InflateJob) * (size_t)n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_inflate, dim3((unsigned)n), dim3(64), 0, s, h->d_comp, (unsigned long long)comp_pad,
-                       so->d_jobs, n, so->d_tmp, (unsigned)chunk_bytes, so->d_status);
+    NF_HIP(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(InflateJob) * (size_t)n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_inflate, dim3((unsigned)n), dim3(64), 0, s, h->d_comp.get(), (unsigned long long)comp_pad,
+                       d_jobs, n, d_tmp, (unsigned)chunk_bytes, so->d_status.get());
     const SlabGeom g{(unsigned)chunk_dims[0], (unsigned)chunk_dims[1], (unsigned)chunk_dims[2], (unsigned)slab_dims[0],
                      (unsigned)slab_dims[1], (unsigned)slab_dims[2]};
     const bool four = shuffled && chunk_dims[2] % 4 == 0;             // four elements per lane (k_place4)
@@ -371,19 +346,19 @@ int inflater_run(Inflater *h, const void *comp_host, size_t comp_bytes, const lo
     if (gx == 0) gx = 1;
     const dim3 grid(gx, (unsigned)std::min(n, 65535)), block(kBlock);  // gridDim.y is capped: the kernels walk the chunks
     uint8_t *dst = (uint8_t *)out_dev;
-    if (elem_size == 1) hipLaunchKernelGGL((k_place<1, false>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (sixteen) hipLaunchKernelGGL(k_place16, grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (elem_size == 4 && four && planes) hipLaunchKernelGGL((k_place4<4, true>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (elem_size == 8 && four && planes) hipLaunchKernelGGL((k_place4<8, true>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (elem_size == 4 && four) hipLaunchKernelGGL((k_place4<4, false>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (elem_size == 8 && four) hipLaunchKernelGGL((k_place4<8, false>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (elem_size == 4 && shuffled) hipLaunchKernelGGL((k_place<4, true>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (elem_size == 4) hipLaunchKernelGGL((k_place<4, false>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else if (shuffled) hipLaunchKernelGGL((k_place<8, true>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
-    else hipLaunchKernelGGL((k_place<8, false>), grid, block, 0, s, so->d_tmp, (unsigned)chunk_bytes, so->d_jobs, n, g, dst);
+    if (elem_size == 1) hipLaunchKernelGGL((k_place<1, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (sixteen) hipLaunchKernelGGL(k_place16, grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (elem_size == 4 && four && planes) hipLaunchKernelGGL((k_place4<4, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (elem_size == 8 && four && planes) hipLaunchKernelGGL((k_place4<8, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (elem_size == 4 && four) hipLaunchKernelGGL((k_place4<4, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (elem_size == 8 && four) hipLaunchKernelGGL((k_place4<8, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (elem_size == 4 && shuffled) hipLaunchKernelGGL((k_place<4, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (elem_size == 4) hipLaunchKernelGGL((k_place<4, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else if (shuffled) hipLaunchKernelGGL((k_place<8, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+    else hipLaunchKernelGGL((k_place<8, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
     NF_HIP(hipGetLastError());
     std::vector<int> status((size_t)n, 0);
-    NF_HIP(hipMemcpyAsync(status.data(), so->d_status, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+    NF_HIP(hipMemcpyAsync(status.data(), so->d_status.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
     NF_HIP(hipStreamSynchronize(s));    // jobs / status vectors are pageable host memory: the copies above are done now
     int bad = -1;
     for (int i = 0; i < n; ++i) {
@@ -434,12 +409,9 @@ int nf_inflater_share_scratch(nf_inflater **self, nf_inflater **owner)
         auto &b = h->scratch_owner->borrowers;
         b.erase(std::remove(b.begin(), b.end(), h), b.end());
     }
-    for (void *p : {(void *)h->d_tmp, (void *)h->d_jobs, (void *)h->d_status})   // its own scratch is not needed any more
-        if (p) (void)hipFree(p);
-    h->d_tmp = nullptr;
-    h->d_jobs = nullptr;
-    h->d_status = nullptr;
-    h->tmp_cap = h->jobs_cap = 0;
+    h->d_tmp.reset();        // its own scratch is not needed any more
+    h->d_jobs.reset();
+    h->d_status.reset();
     h->scratch_owner = o;
     return NF_OK;
 }
@@ -530,7 +502,6 @@ int nf_inflater_del(nf_inflater **self)
             auto &b = h->scratch_owner->borrowers;
             b.erase(std::remove(b.begin(), b.end(), h), b.end());
         }
-        h->release();
         delete h;
         *self = nullptr;
     }

@@ -154,16 +154,16 @@ int integral_uses_edges() { return g_use_edges; }
 
 int launch_integral(const WeightSet &ws, const double *data, long ncell, int planes, long nx,
                     const int *tr_offsets_dev, int ntransect, double *scratch, double *row, hipStream_t s, int nsteps,
-                    long data_stride, long row_stride)
+                    long data_stride, long row_stride, const int *rec_cells)
 {
     const unsigned ny = (unsigned)(nsteps > 1 ? nsteps : 1);
-    if (planes == 2 && ws.ent_start && g_use_edges) {   // the engine's own planes through the unique-edge entries
+    if (planes == 2 && ws.ent_start.get() && g_use_edges) {   // the engine's own planes through the unique-edge entries
         if (ws.nent > 0)
             hipLaunchKernelGGL(k_gather_edges, dim3((unsigned)((ws.nent + kBlock - 1) / kBlock), ny), dim3(kBlock), 0, s,
-                               ws.ent, ws.nent, data, ncell, scratch, data_stride);
+                               ws.ent.get(), ws.nent, data, ncell, scratch, data_stride);
         if (ws.nseg > 0) {
             const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_finalize_seg, dim3(nb, ny), dim3(kBlock), 0, s, scratch, ws.ent_start, ws.nseg, row,
+            hipLaunchKernelGGL(k_finalize_seg, dim3(nb, ny), dim3(kBlock), 0, s, scratch, ws.ent_start.get(), ws.nseg, row,
                                ws.nent, row_stride);
         }
         if (ntransect > 0) {
@@ -176,12 +176,12 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
     }
     if (ws.nrec > 0) {
         hipLaunchKernelGGL(k_gather_segscan, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock), ny), dim3(kBlock), 0, s,
-                           ws.cell, ws.w4, ws.seg, ws.nrec, data, ncell, planes, (unsigned)(nx > 0 ? nx : 1), scratch,
-                           data_stride);
+                           rec_cells ? rec_cells : ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, data, ncell, planes,
+                           (unsigned)(nx > 0 ? nx : 1), scratch, data_stride);
     }
     if (ws.nseg > 0) {
         const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, ny), dim3(kBlock), 0, s, scratch, ws.seg_start, ws.nseg, row,
+        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, ny), dim3(kBlock), 0, s, scratch, ws.seg_start.get(), ws.nseg, row,
                            ws.nrec, row_stride);
     }
     if (ntransect > 0) {

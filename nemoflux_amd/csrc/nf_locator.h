@@ -306,16 +306,16 @@ struct Walker {
         const bool cached = keep && keep->xy == xy && keep->ncell == ncell && keep->period == period && keep->count == nlev &&
                             keep->level.size() == nlev.size();
         if (cached) {
-            for (size_t l = 0; l < nlev.size(); ++l) boxes[l] = static_cast<Box4 *>(keep->level[l]);
+            for (size_t l = 0; l < nlev.size(); ++l) boxes[l] = keep->level[l].get();
             return NF_OK;
         }
         if (keep) {      // the grid's own copy: plain allocations that outlive this build
             keep->release();
-            keep->level.assign(nlev.size(), nullptr);
+            keep->level.resize(nlev.size());
             keep->count = nlev;
             for (size_t l = 0; l < nlev.size(); ++l) {
-                NF_HIP(hipMalloc(&keep->level[l], sizeof(Box4) * (size_t)nlev[l]));
-                boxes[l] = static_cast<Box4 *>(keep->level[l]);
+                NF_TRY(keep->level[l].alloc((size_t)nlev[l]));
+                boxes[l] = keep->level[l].get();
             }
         } else {
             for (size_t l = 0; l < nlev.size(); ++l) NF_HIP(sc.misc.take(&boxes[l], (size_t)nlev[l]));

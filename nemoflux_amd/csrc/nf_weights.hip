@@ -497,35 +497,13 @@ __global__ __launch_bounds__(kBlock) void k_ent_bounds(const WeightSet::EdgeEntr
     ent_start[s] = (int)lo;
 }
 
-void WeightSet::release()
-{
-    if (ent) (void)hipFree(ent);
-    if (ent_start) (void)hipFree(ent_start);
-    ent = nullptr;
-    ent_start = nullptr;
-    nent = 0;
-    if (cell) (void)hipFree(cell);
-    if (w4) (void)hipFree(w4);
-    if (seg) (void)hipFree(seg);
-    if (seg_start) (void)hipFree(seg_start);
-    coverage.clear();
-    over_seg = -1;
-    dropped = 0;
-    cell = nullptr;
-    w4 = nullptr;
-    seg = nullptr;
-    seg_start = nullptr;
-    nrec = 0;
-    nseg = 0;
-}
-
 int weights_to_host(const WeightSet &ws, int64_t *cell_edge, double *weight, int *seg)
 {
     if (ws.nrec == 0) return NF_OK;
     std::vector<int> c((size_t)ws.nrec), sg((size_t)ws.nrec);
-    NF_HIP(hipMemcpy(c.data(), ws.cell, sizeof(int) * ws.nrec, hipMemcpyDeviceToHost));
-    NF_HIP(hipMemcpy(sg.data(), ws.seg, sizeof(int) * ws.nrec, hipMemcpyDeviceToHost));
-    if (weight) NF_HIP(hipMemcpy(weight, ws.w4, sizeof(double) * 4 * ws.nrec, hipMemcpyDeviceToHost));
+    NF_HIP(hipMemcpy(c.data(), ws.cell.get(), sizeof(int) * ws.nrec, hipMemcpyDeviceToHost));
+    NF_HIP(hipMemcpy(sg.data(), ws.seg.get(), sizeof(int) * ws.nrec, hipMemcpyDeviceToHost));
+    if (weight) NF_HIP(hipMemcpy(weight, ws.w4.get(), sizeof(double) * 4 * ws.nrec, hipMemcpyDeviceToHost));
     for (long i = 0; i < ws.nrec; ++i)  // pure re-indexing of the device result for the caller
         for (int e = 0; e < 4; ++e) {
             if (cell_edge) cell_edge[4 * i + e] = (int64_t)c[i] * 4 + e;
@@ -571,8 +549,6 @@ void weights_trim_scratch()
 
 void LocatorBoxes::release()
 {
-    for (void *p : level)
-        if (p) (void)hipFree(p);
     level.clear();
     count.clear();
     xy = nullptr;
@@ -580,67 +556,55 @@ void LocatorBoxes::release()
     period = -1.0;
 }
 
-namespace {
-struct DevBuf {  // frees on scope exit
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T> T *as() { return reinterpret_cast<T *>(p); }
-};
-}  // namespace
-
 int fold_weights(WeightSet *ws, long ncell, long nx, hipStream_t s)
 {
-    if (ws->ent) (void)hipFree(ws->ent);
-    if (ws->ent_start) (void)hipFree(ws->ent_start);
-    ws->ent = nullptr;
-    ws->ent_start = nullptr;
+    ws->ent.reset();
+    ws->ent_start.reset();
     ws->nent = 0;
     NF_REQUIRE(nx > 0 && ncell > 0 && ncell % nx == 0 && 2 * ncell < (long)kNoElem, NF_ERR_ARG, "fold_weights: bad grid sizes");
     NF_REQUIRE(ws->nrec < (1l << 29), NF_ERR_ARG, "fold_weights: too many records");
-    NF_HIP(hipMalloc((void **)&ws->ent_start, sizeof(int) * (size_t)(ws->nseg + 1)));
+    NF_TRY(ws->ent_start.alloc((size_t)(ws->nseg + 1)));
     if (ws->nrec == 0) {
-        NF_HIP(hipMemsetAsync(ws->ent_start, 0, sizeof(int) * (size_t)(ws->nseg + 1), s));
+        NF_HIP(hipMemsetAsync(ws->ent_start.get(), 0, sizeof(int) * (size_t)(ws->nseg + 1), s));
         return NF_OK;
     }
     const long n = 4 * ws->nrec;
     const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
-    DevBuf k_in, k_out, v_in, v_out, tmp, head, pos;
-    NF_HIP(k_in.alloc(sizeof(unsigned long long) * n));
-    NF_HIP(k_out.alloc(sizeof(unsigned long long) * n));
-    NF_HIP(v_in.alloc(sizeof(double) * n));
-    NF_HIP(v_out.alloc(sizeof(double) * n));
-    hipLaunchKernelGGL(k_fold_keys, dim3(nb), dim3(kBlock), 0, s, ws->cell, ws->w4, ws->seg, ws->nrec, ncell, (unsigned)nx,
-                       k_in.as<unsigned long long>(), v_in.as<double>());
+    DevArray<unsigned long long> k_in, k_out;
+    DevArray<double> v_in, v_out;
+    DevArray<char> tmp, tmp2;
+    DevArray<int> head, pos;
+    NF_TRY(k_in.alloc((size_t)n));
+    NF_TRY(k_out.alloc((size_t)n));
+    NF_TRY(v_in.alloc((size_t)n));
+    NF_TRY(v_out.alloc((size_t)n));
+    hipLaunchKernelGGL(k_fold_keys, dim3(nb), dim3(kBlock), 0, s, ws->cell.get(), ws->w4.get(), ws->seg.get(), ws->nrec, ncell,
+                       (unsigned)nx, k_in.get(), v_in.get());
     int bits = 1;
     while ((1l << bits) < (long)ws->nseg + 1 && bits < 24) ++bits;
     size_t tmp_bytes = 0;
-    NF_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const unsigned long long *)k_in.p, k_out.as<unsigned long long>(),
-                                     (const double *)v_in.p, v_out.as<double>(), (size_t)n, 0u, (unsigned)(32 + bits), s));
-    NF_HIP(tmp.alloc(tmp_bytes));
-    NF_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, (const unsigned long long *)k_in.p, k_out.as<unsigned long long>(),
-                                     (const double *)v_in.p, v_out.as<double>(), (size_t)n, 0u, (unsigned)(32 + bits), s));
-    NF_HIP(head.alloc(sizeof(int) * n));
-    NF_HIP(pos.alloc(sizeof(int) * n));
-    hipLaunchKernelGGL(k_fold_heads, dim3(nb), dim3(kBlock), 0, s, k_out.as<unsigned long long>(), n, head.as<int>());
-    DevBuf tmp2;
+    NF_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const unsigned long long *)k_in.get(), k_out.get(),
+                                     (const double *)v_in.get(), v_out.get(), (size_t)n, 0u, (unsigned)(32 + bits), s));
+    NF_TRY(tmp.alloc(tmp_bytes));
+    NF_HIP(rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, (const unsigned long long *)k_in.get(), k_out.get(),
+                                     (const double *)v_in.get(), v_out.get(), (size_t)n, 0u, (unsigned)(32 + bits), s));
+    NF_TRY(head.alloc((size_t)n));
+    NF_TRY(pos.alloc((size_t)n));
+    hipLaunchKernelGGL(k_fold_heads, dim3(nb), dim3(kBlock), 0, s, k_out.get(), n, head.get());
     size_t tmp2_bytes = 0;
-    NF_HIP(rocprim::exclusive_scan(nullptr, tmp2_bytes, head.as<int>(), pos.as<int>(), 0, (size_t)n, rocprim::plus<int>(), s));
-    NF_HIP(tmp2.alloc(tmp2_bytes));
-    NF_HIP(rocprim::exclusive_scan(tmp2.p, tmp2_bytes, head.as<int>(), pos.as<int>(), 0, (size_t)n, rocprim::plus<int>(), s));
+    NF_HIP(rocprim::exclusive_scan(nullptr, tmp2_bytes, head.get(), pos.get(), 0, (size_t)n, rocprim::plus<int>(), s));
+    NF_TRY(tmp2.alloc(tmp2_bytes));
+    NF_HIP(rocprim::exclusive_scan(tmp2.get(), tmp2_bytes, head.get(), pos.get(), 0, (size_t)n, rocprim::plus<int>(), s));
     int last_pos = 0, last_head = 0;
-    NF_HIP(hipMemcpyAsync(&last_pos, pos.as<int>() + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-    NF_HIP(hipMemcpyAsync(&last_head, head.as<int>() + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+    NF_HIP(hipMemcpyAsync(&last_pos, pos.get() + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+    NF_HIP(hipMemcpyAsync(&last_head, head.get() + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
     NF_HIP(hipStreamSynchronize(s));
     ws->nent = (long)last_pos + last_head;
-    NF_HIP(hipMalloc((void **)&ws->ent, sizeof(WeightSet::EdgeEntry) * (size_t)(ws->nent ? ws->nent : 1)));
-    hipLaunchKernelGGL(k_fold_merge, dim3(nb), dim3(kBlock), 0, s, k_out.as<unsigned long long>(), v_out.as<double>(),
-                       head.as<int>(), pos.as<int>(), n, ws->ent);
-    hipLaunchKernelGGL(k_ent_bounds, dim3((unsigned)((ws->nseg + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ws->ent,
-                       ws->nent, ws->nseg, ws->ent_start);
+    NF_TRY(ws->ent.alloc((size_t)ws->nent));
+    hipLaunchKernelGGL(k_fold_merge, dim3(nb), dim3(kBlock), 0, s, k_out.get(), v_out.get(), head.get(), pos.get(), n,
+                       ws->ent.get());
+    hipLaunchKernelGGL(k_ent_bounds, dim3((unsigned)((ws->nseg + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ws->ent.get(),
+                       ws->nent, ws->nseg, ws->ent_start.get());
     NF_HIP(hipGetLastError());
     NF_HIP(hipStreamSynchronize(s));
     return NF_OK;
@@ -731,9 +695,9 @@ int build_weights(const double *xy, long ncell, const double *segs_host, const i
     out->dropped = (long)err_pair[1];
     NF_REQUIRE(nrec < (1l << 31), NF_ERR_ARG, "weights: more than 2^31 (segment, cell) records; split the transect set");
 
-    NF_HIP(hipMalloc((void **)&out->seg_start, sizeof(int) * (size_t)(nseg + 1)));
+    NF_TRY(out->seg_start.alloc((size_t)(nseg + 1)));
     if (nrec == 0) {
-        NF_HIP(hipMemsetAsync(out->seg_start, 0, sizeof(int) * (size_t)(nseg + 1), s));
+        NF_HIP(hipMemsetAsync(out->seg_start.get(), 0, sizeof(int) * (size_t)(nseg + 1), s));
         NF_HIP(hipStreamSynchronize(s));
         lease.drained = true;
         for (int q = 0; q < nseg; ++q)
@@ -785,21 +749,21 @@ int build_weights(const double *xy, long ncell, const double *segs_host, const i
                        (const unsigned long long *)k_out, nrec, nseg, rstart);
 
     out->nrec = nrec;
-    NF_HIP(hipMalloc((void **)&out->cell, sizeof(int) * (size_t)nrec));
-    NF_HIP(hipMalloc((void **)&out->w4, sizeof(double) * 4 * (size_t)nrec));
-    NF_HIP(hipMalloc((void **)&out->seg, sizeof(int) * (size_t)nrec));
+    NF_TRY(out->cell.alloc((size_t)nrec));
+    NF_TRY(out->w4.alloc(4 * (size_t)nrec));
+    NF_TRY(out->seg.alloc((size_t)nrec));
     double *d_len = nullptr, *d_cov = nullptr;
     NF_HIP(level[0].take(&d_len, (size_t)nrec));
     NF_HIP(misc.take(&d_cov, (size_t)(nseg + 1)));
     hipLaunchKernelGGL(k_expand, dim3(nb_rec), dim3(kBlock), 0, s, (const unsigned long long *)k_out, (const unsigned *)v_tie, nrec,
-                       rec, xy, period, (const double *)d_segs, (const int *)d_cc, nshift, periodX, d_err, out->cell, out->w4,
-                       out->seg, d_len);
+                       rec, xy, period, (const double *)d_segs, (const int *)d_cc, nshift, periodX, d_err, out->cell.get(), out->w4.get(),
+                       out->seg.get(), d_len);
     if (nseg > 0) {
         hipLaunchKernelGGL(k_seg_coverage, dim3((unsigned)(((long)nseg * kWave + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                            (const double *)d_len, (const int *)rstart, nseg, d_cov);
         NF_HIP(hipMemcpyAsync(out->coverage.data(), d_cov, sizeof(double) * (size_t)nseg, hipMemcpyDeviceToHost, s));
     }
-    NF_HIP(hipMemcpyAsync(out->seg_start, rstart, sizeof(int) * (size_t)(nseg + 1), hipMemcpyDeviceToDevice, s));
+    NF_HIP(hipMemcpyAsync(out->seg_start.get(), rstart, sizeof(int) * (size_t)(nseg + 1), hipMemcpyDeviceToDevice, s));
     NF_HIP(hipMemcpyAsync(&err_word, d_err, sizeof err_word, hipMemcpyDeviceToHost, s));
     NF_HIP(hipGetLastError());
     NF_HIP(hipStreamSynchronize(s));
