@@ -12,13 +12,22 @@ static int g_batch_steps = 1;
 //   "partial_step_planes"  1 = a rank's PARTIAL time steps keep the six-plane epilogue (the code before round 4: the before
 //                          leg of profiles/r04_rank_emulation.txt); 0 = signed planes only (default)
 //   "graph"                0 = nf_field_compute_all_async never replays a captured graph of the pass (default 1)
+//   "pass_inner_signed"    1 = inside one per-step pass, every owned step but the last stores only the two signed planes
+//                          (K3 reads nothing else and the next step overwrites all six); 0 = every step stores what it
+//                          stores on its own (default 1)
+//   "pass_k3_pairs"        1 = the per-step pass reduces its whole steps two at a time: one gather launch reads the record
+//                          stream once for both steps; 0 = one reduction per step (default 1)
 static long g_batch_cellsteps = 32l << 20;
 static int g_partial_full = 0;
 static int g_use_graph = 1;
+static int g_inner_signed = 1;
+static int g_k3_pairs = 1;
+static long g_knob_version = 0;   // bumped by every knob of this file: a captured pass bakes them in
 
 namespace nf {
 int field_tuning_set(const char *name, int value)
 {
+    ++g_knob_version;
     if (!strcmp(name, "batch_steps")) {
         g_batch_steps = value;
         return NF_OK;
@@ -34,6 +43,14 @@ int field_tuning_set(const char *name, int value)
     }
     if (!strcmp(name, "graph")) {
         g_use_graph = value != 0;
+        return NF_OK;
+    }
+    if (!strcmp(name, "pass_inner_signed")) {
+        g_inner_signed = value != 0;
+        return NF_OK;
+    }
+    if (!strcmp(name, "pass_k3_pairs")) {
+        g_k3_pairs = value != 0;
         return NF_OK;
     }
     return -1;
@@ -52,6 +69,7 @@ struct nf_field {
         DevArray<double> iV;    // [4][ncell]
         DevArray<double> abs;   // [2][ncell]
         DevArray<double> aos;   // (ncell,4) re-pack buffer for read_step, allocated on first use
+        DevArray<double> uv2;   // [2][ncell] eU, eV of the first step of a pair ("pass_k3_pairs"), allocated on first use
         DevArray<unsigned long long> maxbits;
         // multi-step launches for small grids (compute_all): per-step planes, scratch and z ranges
         DevArray<double> iVb, absb, scratchb;
@@ -81,7 +99,7 @@ struct nf_field {
     int skip_unsupported = 0;   // nf_field_set_unsupported_cells
     int overlap_warn = 0;       // nf_field_set_overlapping_cells
     DevArray<int> tr_off_dev;
-    DevArray<double> scratch, row;
+    DevArray<double> scratch, row;   // scratch: the run sums of two steps (a pair of the per-step pass)
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -98,6 +116,9 @@ struct nf_field {
     double *graph_rows = nullptr;
     long graph_version = -1, version = 0;  // version is bumped by every call that changes what a pass launches
 };
+
+// what a captured graph of the pass depends on: the field's own settings and every tuning knob
+static long field_pass_version(const nf_field *f) { return f->version + tuning_version() + g_knob_version; }
 
 static void field_drop_graph(nf_field *f)
 {
@@ -201,8 +222,18 @@ static int field_ensure_derived(nf_field *f)
 
 static int field_row_length(const nf_field *f) { return f->ws.nseg + (int)f->polylines.size(); }
 
+// how field_step_async runs a step of a per-step pass
+struct StepForm {
+    // a step of the pass that another step follows: its planes are overwritten before anybody but K3 can read them, so
+    // only the two signed planes are stored (the f64 flux kernel in its signed-only form, no f32 expansion)
+    bool inner = false;
+    // the step's signed planes go to geo.uv2 instead of the resident planes, and no reduction is launched: the first step
+    // of a pair, reduced together with the next one (field_pair_async)
+    bool to_uv2 = false;
+};
+
 // one time step on the field's stream; row_dev receives [segments | transects]
-static int field_step_async(nf_field *f, long t, double *row_dev)
+static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form = {})
 {
     NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
                "compute: set_bounds, set_thickness and set_uv first");
@@ -251,6 +282,8 @@ static int field_step_async(nf_field *f, long t, double *row_dev)
     a.scale = kEarthRadiusSv / 1.e6;  // field.py:226
     a.sverdrup = f->sverdrup;
     a.iV = f->geo.iV.get();
+    // uv2 holds planes 1 and 2 only: the signed-only kernel stores to iV + ncell and iV + 2 * ncell, nothing below
+    if (form.to_uv2) a.iV = f->geo.uv2.get() - f->ncell;
     a.absU = f->geo.abs.get();
     a.absV = f->geo.abs.get() + f->ncell;
     a.maxbits = f->geo.maxbits.get();
@@ -261,19 +294,37 @@ static int field_step_async(nf_field *f, long t, double *row_dev)
     // the C4 size; the rows are bit-identical (test_slab_sharding_sums_to_full).  nf_tuning_set("partial_step_planes", 1) keeps the
     // six-plane epilogue on partial steps (the before / after measurement of profiles/r04_rank_emulation.txt).
     const bool partial = (z0 > 0 || z1 < (int)f->nz) && !g_partial_full;
-    a.signed_only = (f->compact || partial) && flux_supports_signed_only(a);
-    f->derived_stale = a.signed_only != 0;
+    a.signed_only = (f->compact || partial || form.inner) && flux_supports_signed_only(a);
+    NF_REQUIRE(!form.to_uv2 || a.signed_only, NF_ERR_STATE, "compute: a step into the second planes must be signed-only");
+    if (!form.to_uv2) f->derived_stale = a.signed_only != 0;
     if (f->timing) {
         NF_TRY(field_timed_flux(f, a));
     } else {
         NF_TRY(launch_flux(a, f->stream));
     }
-    if (row_dev && rowlen > 0) {
+    if (row_dev && rowlen > 0 && !form.to_uv2) {
         NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute: build_weights first");
         NF_TRY(launch_integral(f->ws, f->geo.iV.get(), f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(),
                                f->scratch.get(), row_dev, f->stream));
         NF_TRY(field_timed_k3_end(f));
     }
+    return NF_OK;
+}
+
+// steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
+// step, as after two single steps), then ONE reduction of both; rows t and t+1 are contiguous in rows_dev.  last: t+1 is the
+// last owned step of the pass, which stores what it stores on its own.
+static int field_pair_async(nf_field *f, long t, double *rows_dev, bool last)
+{
+    const int rowlen = field_row_length(f);
+    StepForm first, second;
+    first.inner = first.to_uv2 = true;
+    second.inner = g_inner_signed && !last;
+    NF_TRY(field_step_async(f, t, nullptr, first));
+    NF_TRY(field_step_async(f, t + 1, nullptr, second));
+    NF_TRY(launch_integral_pair(f->ws, f->geo.uv2.get(), f->geo.iV.get() + f->ncell, f->ncell, f->nx, f->tr_off_dev.get(),
+                                (int)f->polylines.size(), f->scratch.get(), rows_dev + (size_t)t * rowlen, rowlen, f->stream));
+    NF_TRY(field_timed_k3_end(f));   // the pair's reduction is timed with the second step's launch
     return NF_OK;
 }
 
@@ -289,6 +340,34 @@ static bool field_can_batch(const nf_field *f)
     // 1144 at float64; 2160 x 1080: 1035 vs 1187 and 1863 vs 1928 (tools/size_sweep.py, profiles/r04_size_sweep.txt)
     return g_batch_steps && f->uv_on_device && f->nt >= 2 && f->nt < 65536 && f->nt * f->ncell <= batch_cell_steps() &&
            f->ncell <= (1l << 20) && f->weights_built;
+}
+
+// the per-step pass reduces its whole steps in pairs: needs the record form of K3 (the unique-edge entries have no pair
+// kernel), the second signed planes (field_prepare_pass) and the signed-only flux kernel for the first step of a pair
+static bool field_pass_pairs(const nf_field *f)
+{
+    if (!g_k3_pairs || integral_uses_edges() || !f->geo.uv2.get() || !f->weights_built) return false;
+    // every step starts 16-byte aligned when the first one does: resident fields with a step size that is a multiple of
+    // 16 bytes, or steps staged into the (allocation-aligned) staging buffers
+    const size_t step_bytes = (size_t)f->nz * f->ncell * elem_size(f->uv_dtype);
+    FluxArgs a{};
+    a.u = f->uv_on_device ? f->u : nullptr;
+    a.v = f->uv_on_device ? f->v : nullptr;
+    a.dtype = f->uv_dtype;
+    a.ncell = f->ncell;
+    return flux_supports_signed_only(a) && (!f->uv_on_device || step_bytes % 16 == 0);
+}
+
+// device memory a per-step pass may need, allocated before the pass is launched or captured: the second signed planes of
+// a pair.  Nothing is allocated for a pass that takes no pairs (knob off, a single owned step, the edge-entry form of K3).
+static int field_prepare_pass(nf_field *f)
+{
+    if (!g_k3_pairs || integral_uses_edges() || f->geo.uv2.get() || !f->geo.iV.get() || f->nz <= 0) return NF_OK;
+    const long total = f->nt * f->nz;
+    const long s_end = f->s_end < 0 ? total : std::min(f->s_end, total);
+    if (s_end - std::min(f->s_begin, s_end) < 2 * f->nz) return NF_OK;   // fewer than two whole steps can be owned
+    NF_TRY(f->geo.uv2.alloc((size_t)f->ncell * 2));
+    return NF_OK;
 }
 
 // every time step of a pass, one after the other.  A rank of a multi-GPU run owns a contiguous range of steps (slab
@@ -308,7 +387,25 @@ static int field_all_steps_direct(nf_field *f, double *rows_dev)
             NF_HIP(hipMemsetAsync(rows_dev + (size_t)tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nt - tb),
                                   f->stream));
     }
-    for (long t = ta; t < tb; ++t) NF_TRY(field_step_async(f, t, rows_dev + (size_t)t * rowlen));
+    // whole steps [wa, wb): the ones a pair may take (a partial first or last step is reduced on its own)
+    const long wa = (ta < tb && s_begin > ta * f->nz) ? ta + 1 : ta;
+    const long wb = std::max(wa, (ta < tb && s_end < tb * f->nz) ? tb - 1 : tb);
+    const bool pairs = field_pass_pairs(f) && rowlen > 0;
+    // an odd number of whole steps leaves one of them single: the first, so that the last pair ends on the last whole step
+    // and every pair's second step lands in the resident planes
+    const long pa = pairs ? wa + (wb - wa) % 2 : wb;
+    for (long t = ta; t < tb;) {
+        const bool last = t + 1 == tb;
+        if (t >= pa && t + 1 < wb) {
+            NF_TRY(field_pair_async(f, t, rows_dev, t + 2 == tb));
+            t += 2;
+        } else {
+            StepForm form;
+            form.inner = g_inner_signed && !last;
+            NF_TRY(field_step_async(f, t, rows_dev + (size_t)t * rowlen, form));
+            t += 1;
+        }
+    }
     return NF_OK;
 }
 
@@ -614,7 +711,7 @@ try {
     // (only on request -- nf_tuning_set("edge_weights", 1) -- because the records measure faster: see nf_integral.hip)
     if (integral_uses_edges()) NF_TRY(fold_weights(&f->ws, f->ncell, f->nx, f->stream));
     NF_TRY(f->tr_off_dev.alloc(f->tr_off.size()));
-    NF_TRY(f->scratch.alloc((size_t)std::max(f->ws.nrec, f->ws.nent)));
+    NF_TRY(f->scratch.alloc((size_t)2 * std::max(f->ws.nrec, f->ws.nent)));
     NF_TRY(f->row.alloc((size_t)field_row_length(f)));
     NF_HIP(hipMemcpy(f->tr_off_dev.get(), f->tr_off.data(), sizeof(int) * f->tr_off.size(), hipMemcpyHostToDevice));
     f->weights_built = true;
@@ -723,10 +820,11 @@ try {
     nf_field *f = *self;
     NF_REQUIRE(f->weights_built, NF_ERR_STATE, "nf_field_compute_all_async: build_weights first");
     if (field_can_batch(f)) return field_all_steps_batched(f, rows_dev);
+    NF_TRY(field_prepare_pass(f));   // allocations stay out of a graph capture
     // Replay a captured graph of the whole pass when nothing changed since it was captured.  Capture needs a real
     // (non-null) stream, resident fields, and no per-launch timing events.
     const bool can_graph = g_use_graph && f->stream != nullptr && f->uv_on_device && !f->timing;
-    if (can_graph && f->graph_exec && f->graph_rows == rows_dev && f->graph_version == f->version + tuning_version()) {
+    if (can_graph && f->graph_exec && f->graph_rows == rows_dev && f->graph_version == field_pass_version(f)) {
         NF_HIP(hipGraphLaunch(f->graph_exec, f->stream));
         return NF_OK;
     }
@@ -740,7 +838,7 @@ try {
                 hipGraphInstantiate(&f->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                 (void)hipGraphDestroy(graph);
                 f->graph_rows = rows_dev;
-                f->graph_version = f->version + tuning_version();
+                f->graph_version = field_pass_version(f);
                 NF_HIP(hipGraphLaunch(f->graph_exec, f->stream));
                 return NF_OK;
             }

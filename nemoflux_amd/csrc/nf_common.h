@@ -313,6 +313,12 @@ int integral_uses_edges();
 int launch_integral(const WeightSet &ws, const double *data, long ncell, int planes, long nx,
                     const int *tr_offsets_dev, int ntransect, double *scratch, double *row, hipStream_t s,
                     int nsteps = 1, long data_stride = 0, long row_stride = 0, const int *rec_cells = nullptr);
+// two time steps of the engine's own planes through the (cell, 4 weights) records in ONE gather launch (the record stream is
+// read once for both): uvA -> row, uvB -> row + row_stride, where uvX is a step's eU plane followed by its eV plane.
+// scratch: 2 * ws.nrec doubles.  The same summation tree per step as launch_integral(planes = 2): the same bits.
+int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *uvB, long ncell, long nx,
+                         const int *tr_offsets_dev, int ntransect, double *scratch, double *row, long row_stride,
+                         hipStream_t s);
 
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q

@@ -73,6 +73,55 @@ __global__ __launch_bounds__(kBlock) void k_gather_segscan(const int *__restrict
     if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) runsum[k] = val;
 }
 
+// Stage A for TWO time steps of the engine's own planes at once (the per-step pass takes its whole steps in pairs): the
+// 40-byte record is read once, the same four elements are gathered from both steps' signed planes, and the two weighted
+// sums go through the segmented scan side by side.  Each step's sum is formed and scanned exactly as in k_gather_segscan
+// (planes = 2): bit-identical rows.  uvA / uvB: a step's eU plane, its eV plane right behind it; runsum: 2 * n doubles.
+__global__ __launch_bounds__(kBlock) void k_gather_segscan_pair(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                                const int *__restrict__ seg, long n,
+                                                                const double *__restrict__ uvA,
+                                                                const double *__restrict__ uvB, long ncell, unsigned nx,
+                                                                double *__restrict__ runsum)
+{
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    double va = 0.0, vb = 0.0;
+    int key = -1;
+    if (k < n) {
+        typedef double dvec2 __attribute__((ext_vector_type(2)));
+        const long c = __builtin_nontemporal_load(cell + k);
+        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
+        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
+        const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
+        const long cw = i > 0 ? c - 1 : c - 1 + nx;
+        {
+            const double *eU = uvA, *eV = uvA + ncell;
+            const double d1 = eU[c], d2 = eV[c], d0 = j > 0 ? eV[c - nx] : 0.0, d3 = eU[cw];
+            va = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
+        }
+        {
+            const double *eU = uvB, *eV = uvB + ncell;
+            const double d1 = eU[c], d2 = eV[c], d0 = j > 0 ? eV[c - nx] : 0.0, d3 = eU[cw];
+            vb = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
+        }
+        key = __builtin_nontemporal_load(seg + k);
+    }
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const double pa = __shfl_up(va, o, kWave), pb = __shfl_up(vb, o, kWave);
+        const int pk = __shfl_up(key, o, kWave);
+        if (lane >= o && pk == key) {
+            va += pa;
+            vb += pb;
+        }
+    }
+    const int nk = __shfl_down(key, 1, kWave);
+    if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) {
+        runsum[k] = va;
+        runsum[n + k] = vb;
+    }
+}
+
 // Unique-edge form of stage A for the engine's own planes (WeightSet::EdgeEntry): one lane per (segment, plane element)
 // entry -- ONE 16-byte record load and ONE 8-byte gather from [eU | eV] -- then the same wavefront segmented scan.
 // Entries are sorted by (segment, element), so the gathers of neighbouring lanes walk the planes in ascending order.
@@ -187,6 +236,28 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
     if (ntransect > 0) {
         const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_finalize_tr, dim3(nb, ny), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
+                           row_stride);
+    }
+    NF_HIP(hipGetLastError());
+    return NF_OK;
+}
+
+int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *uvB, long ncell, long nx,
+                         const int *tr_offsets_dev, int ntransect, double *scratch, double *row, long row_stride,
+                         hipStream_t s)
+{
+    if (ws.nrec > 0)
+        hipLaunchKernelGGL(k_gather_segscan_pair, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, uvA, uvB, ncell, (unsigned)(nx > 0 ? nx : 1),
+                           scratch);
+    if (ws.nseg > 0) {
+        const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, 2), dim3(kBlock), 0, s, scratch, ws.seg_start.get(), ws.nseg, row,
+                           ws.nrec, row_stride);
+    }
+    if (ntransect > 0) {
+        const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_finalize_tr, dim3(nb, 2), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
                            row_stride);
     }
     NF_HIP(hipGetLastError());

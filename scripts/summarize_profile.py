@@ -85,8 +85,10 @@ for dtype, roof in legs:
     xfetch = counter('pmc_fetch', 'FETCH_SIZE', 'k_expand_planes') if split else []
     xwrite = counter('pmc_write', 'WRITE_SIZE', 'k_expand_planes') if split else []
     f_kb, w_kb = sum(fetch) / len(fetch), sum(write) / len(write)
-    xf_kb = sum(xfetch) / len(xfetch) if xfetch else 0.0
-    xw_kb = sum(xwrite) / len(xwrite) if xwrite else 0.0
+    # the expansion runs behind the LAST step of a pass only (the inner steps store the two signed planes): its bytes are
+    # spread over all flux launches, as bench.py's per-launch figures are
+    xf_kb = sum(xfetch) / len(fetch) if xfetch else 0.0
+    xw_kb = sum(xwrite) / len(write) if xwrite else 0.0
     # MI355X_MICROARCH.md (HBM): FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports exactly half of the
     # bytes of a wide coalesced (16 B/lane) streaming read -> double it; WRITE_SIZE is exact for 16 B/lane stores.
     hbm = 2.0 * f_kb * 1024 + w_kb * 1024 + 2.0 * xf_kb * 1024 + xw_kb * 1024
@@ -113,7 +115,7 @@ for dtype, kname, es in (('f64', 'k_flux_field<double', 8), ('f32', 'k_flux_fiel
 # gfx950), the gathers are 8-B accesses that pull whole 64-B requests (counted in full): the true figure lies between the
 # raw and the doubled counter; both are recorded.
 nrec = c.get('weight_entries', 0) // 4
-kf, kw = counter('pmc_fetch', 'FETCH_SIZE', 'k_gather_segscan'), counter('pmc_write', 'WRITE_SIZE', 'k_gather_segscan')
+kf, kw = counter('pmc_fetch', 'FETCH_SIZE', 'k_gather_segscan('), counter('pmc_write', 'WRITE_SIZE', 'k_gather_segscan(')
 if kf and nrec:       # (rocprofv3 leaves a kernel out of the WRITE_SIZE file when the counter reads 0: run sums go out non-temporal)
     f_kb, w_kb = sum(kf) / len(kf), (sum(kw) / len(kw) if kw else 0.0)
     alg = 80.0 * nrec

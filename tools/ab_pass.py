@@ -11,10 +11,11 @@ from nemoflux_amd._lib import lib, check
 from nemoflux_amd.datagen import DataGen, STREAM_FUNCTIONS
 from nemoflux_amd.field import Field
 
-# runs: "variant[:knob=value[:knob=value]]" separated by commas, e.g. "0:overlap=1,0:overlap=0,13"
+# runs: "variant[:knob=value[:knob=value]]" separated by commas, e.g. "0:overlap=1,0:overlap=0,13"; then the dtype (float64)
 variants = (sys.argv[1] if len(sys.argv) > 1 else '0:overlap=1,0:overlap=0').split(',')
+real = sys.argv[2] if len(sys.argv) > 2 else 'float64'    # dtype of the generated u, v: float64 or float32
 nx, ny, nz, nt = 3600, 1800, 75, 6
-dg = DataGen(); dg.setSizes(nx, ny, nz, nt); dg.setBoundingBox(-180, 180, -90, 90, 0, 1); dg.build()
+dg = DataGen(real=real); dg.setSizes(nx, ny, nz, nt); dg.setBoundingBox(-180, 180, -90, 90, 0, 1); dg.build()
 dg.applyStreamFunction(STREAM_FUNCTIONS[5])
 u, v = dg.computeUVFromPotential()
 polys = bench.make_transects(nx, ny, -180., 180., -90., 90., 64)
