@@ -260,6 +260,12 @@ int nf_field_compute_flux(nf_field **self, long tIndex, double *row_host);
 /* All nt steps back to back, asynchronously on the field's stream; rows_dev: HBM (nt, row_length),
  * fully overwritten (zeros where this rank owns no slab).  This is the timed "step" of bench.py. */
 int nf_field_compute_all_async(nf_field **self, double *rows_dev);
+/* Depth-resolved rows of time step tIndex: prof (nz, row_length) doubles, level z's row = [segments | transects] of the
+ * flux carried by that level alone.  Levels this rank does not own (slab range) get exact zeros, so the RCCL / gloo
+ * sum of the ranks' profiles is the full profile.  Leaves the resident planes, |.| arrays, running max and a captured
+ * pass untouched. */
+int nf_field_compute_profile(nf_field **self, long tIndex, double *prof_host);        /* synchronous, host */
+int nf_field_compute_profile_async(nf_field **self, long tIndex, double *prof_dev);   /* HBM, on the field's stream */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

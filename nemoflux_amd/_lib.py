@@ -116,6 +116,8 @@ _sig('nf_field_get_edge_weights', [_pp, c_int_p, c_int_p, c_double_p])
 _sig('nf_field_row_length', [_pp, c_int_p])
 _sig('nf_field_compute_flux', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_all_async', [_pp, ctypes.c_void_p])
+_sig('nf_field_compute_profile', [_pp, ctypes.c_long, c_double_p])
+_sig('nf_field_compute_profile_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_read_step', [_pp, c_double_p, c_double_p, c_double_p, c_double_p])
 _sig('nf_field_reset_max', [_pp])
 _sig('nf_field_get_arclengths', [_pp, c_double_p])

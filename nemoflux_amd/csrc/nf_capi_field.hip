@@ -100,6 +100,9 @@ struct nf_field {
     int overlap_warn = 0;       // nf_field_set_overlapping_cells
     DevArray<int> tr_off_dev;
     DevArray<double> scratch, row;   // scratch: the run sums of two steps (a pair of the per-step pass)
+    // depth-resolved rows (nf_field_compute_profile): the run sums of one chunk of levels (ws.nrec * kProfileChunk, allocated
+    // on first use, dropped with the weights) and the (nz, row_length) block of the synchronous call
+    DevArray<double> prof_scratch, prof;
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -232,6 +235,29 @@ struct StepForm {
     bool to_uv2 = false;
 };
 
+// the base of step t's (nz, ncell) fields on the device: resident fields in place, host-resident ones staged, owned levels
+// [z0, z1) only (PCIe-inclusive path)
+static int field_step_input(nf_field *f, long t, int z0, int z1, const void **ut, const void **vt)
+{
+    const size_t es = elem_size(f->uv_dtype);
+    const size_t step_bytes = (size_t)f->nz * f->ncell * es;
+    if (f->uv_on_device) {
+        *ut = (const char *)f->u + (size_t)t * step_bytes;
+        *vt = (const char *)f->v + (size_t)t * step_bytes;
+        return NF_OK;
+    }
+    NF_TRY(f->stage_u.reserve(step_bytes));
+    NF_TRY(f->stage_v.reserve(step_bytes));
+    const size_t off = (size_t)z0 * f->ncell * es, len = (size_t)(z1 - z0) * f->ncell * es;
+    NF_HIP(hipMemcpyAsync(f->stage_u.get() + off, (const char *)f->u + (size_t)t * step_bytes + off, len,
+                          hipMemcpyHostToDevice, f->stream));
+    NF_HIP(hipMemcpyAsync(f->stage_v.get() + off, (const char *)f->v + (size_t)t * step_bytes + off, len,
+                          hipMemcpyHostToDevice, f->stream));
+    *ut = f->stage_u.get();
+    *vt = f->stage_v.get();
+    return NF_OK;
+}
+
 // one time step on the field's stream; row_dev receives [segments | transects]
 static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form = {})
 {
@@ -248,23 +274,8 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
         return NF_OK;
     }
     const int z0 = (int)(lo - t * f->nz), z1 = (int)(hi - t * f->nz);
-    const size_t es = elem_size(f->uv_dtype);
-    const size_t step_bytes = (size_t)f->nz * f->ncell * es;
     const void *ut, *vt;
-    if (f->uv_on_device) {
-        ut = (const char *)f->u + (size_t)t * step_bytes;
-        vt = (const char *)f->v + (size_t)t * step_bytes;
-    } else {  // host-resident fields: stage the owned slabs of this step (PCIe-inclusive path)
-        NF_TRY(f->stage_u.reserve(step_bytes));
-        NF_TRY(f->stage_v.reserve(step_bytes));
-        const size_t off = (size_t)z0 * f->ncell * es, len = (size_t)(z1 - z0) * f->ncell * es;
-        NF_HIP(hipMemcpyAsync(f->stage_u.get() + off, (const char *)f->u + (size_t)t * step_bytes + off, len,
-                              hipMemcpyHostToDevice, f->stream));
-        NF_HIP(hipMemcpyAsync(f->stage_v.get() + off, (const char *)f->v + (size_t)t * step_bytes + off, len,
-                              hipMemcpyHostToDevice, f->stream));
-        ut = f->stage_u.get();
-        vt = f->stage_v.get();
-    }
+    NF_TRY(field_step_input(f, t, z0, z1, &ut, &vt));
     FluxArgs a{};
     a.u = ut;
     a.v = vt;
@@ -309,6 +320,53 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
         NF_TRY(field_timed_k3_end(f));
     }
     return NF_OK;
+}
+
+// Depth-resolved rows of step t on the field's stream: prof_dev (nz, row_length), row z = the flux carried by level z alone.
+// Reads the raw fields and the records; leaves the resident planes, |.| arrays, running max, version and a captured pass
+// alone.  Levels this rank does not own get zeros.
+static int field_profile_async(nf_field *f, long t, double *prof_dev)
+{
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
+               "compute_profile: set_bounds, set_thickness and set_uv first");
+    NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute_profile: build_weights first");
+    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_profile: time index out of range");
+    const int rowlen = field_row_length(f);
+    if (rowlen == 0) return NF_OK;
+    const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
+    long lo = t * f->nz, hi = (t + 1) * f->nz;
+    if (lo < f->s_begin) lo = f->s_begin;
+    if (hi > s_end) hi = s_end;
+    if (hi < lo) hi = lo;
+    const int z0 = (int)(lo - t * f->nz), z1 = (int)(hi - t * f->nz);
+    // levels outside [z0, z1): exact zeros, so that the ranks' profiles add up to the full one
+    if (z0 > 0) NF_HIP(hipMemsetAsync(prof_dev, 0, sizeof(double) * rowlen * (size_t)z0, f->stream));
+    if (z1 < f->nz)
+        NF_HIP(hipMemsetAsync(prof_dev + (size_t)z1 * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nz - z1), f->stream));
+    if (z1 <= z0) return NF_OK;
+    NF_TRY(f->prof_scratch.reserve((size_t)f->ws.nrec * kProfileChunk));
+    ProfileArgs a;
+    a.ws = &f->ws;
+    NF_TRY(field_step_input(f, t, z0, z1, &a.u, &a.v));
+    a.dtype = f->uv_dtype;
+    a.ncell = f->ncell;
+    a.nx = f->nx;
+    a.z0 = z0;
+    a.z1 = z1;
+    a.thickness = f->thick.get();
+    a.arcE = f->geo.arcE.get();
+    a.arcN = f->geo.arcN.get();
+    a.fill = f->fill;
+    a.fill2 = f->fill2;
+    a.scale = kEarthRadiusSv / 1.e6;   // field.py:226
+    a.sverdrup = f->sverdrup;
+    a.tr_offsets_dev = f->tr_off_dev.get();
+    a.ntransect = (int)f->polylines.size();
+    a.row_length = rowlen;
+    a.scratch = f->prof_scratch.get();
+    a.scratch_len = f->prof_scratch.size();
+    a.prof = prof_dev;
+    return launch_profile(a, f->stream);
 }
 
 // steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
@@ -688,6 +746,7 @@ try {
         f->tr_off.push_back((int)cc.size());
     }
     f->weights_built = false;
+    f->prof_scratch.reset();
     const int bw = build_weights(f->geo.xy.get(), f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
                                  f->skip_unsupported, f->overlap_warn, nullptr, f->nx);
     if (bw != NF_OK) {
@@ -850,6 +909,35 @@ try {
         }
     }
     return field_all_steps_direct(f, rows_dev);
+}
+NF_API_CATCH
+
+int nf_field_compute_profile(nf_field **self, long tIndex, double *prof_host)
+try {
+    NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_profile: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
+               "compute_profile: set_bounds, set_thickness and set_uv first");
+    NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute_profile: build_weights first");
+    NF_NEED_DEVICE();
+    const size_t n = (size_t)f->nz * field_row_length(f);
+    if (n == 0) return NF_OK;
+    NF_TRY(f->prof.reserve(n));
+    NF_TRY(field_profile_async(f, tIndex, f->prof.get()));
+    NF_HIP(hipMemcpyAsync(prof_host, f->prof.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
+    NF_HIP(hipStreamSynchronize(f->stream));
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_profile_async(nf_field **self, long tIndex, double *prof_dev)
+try {
+    NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_profile_async: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
+               "compute_profile: set_bounds, set_thickness and set_uv first");
+    NF_NEED_DEVICE();
+    return field_profile_async(f, tIndex, prof_dev);
 }
 NF_API_CATCH
 

@@ -320,6 +320,29 @@ int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *u
                          const int *tr_offsets_dev, int ntransect, double *scratch, double *row, long row_stride,
                          hipStream_t s);
 
+// Depth-resolved rows (nf_field_compute_profile): the per-level form of the record path of K3, reading the raw fields of
+// one time step.  prof: (nz, row_length) doubles; the kernels write rows [z0, z1) only.  Levels are processed
+// kProfileChunk at a time: scratch holds the run sums of one chunk, ws.nrec * kProfileChunk doubles.
+constexpr int kProfileChunk = 8;
+struct ProfileArgs {
+    const WeightSet *ws = nullptr;
+    const void *u = nullptr, *v = nullptr;   // base of the time step: (nz, ncell) of the field dtype
+    int dtype = NF_F64;
+    long ncell = 0, nx = 0;
+    int z0 = 0, z1 = 0;
+    const double *thickness = nullptr, *arcE = nullptr, *arcN = nullptr;   // device
+    double fill = __builtin_nan(""), fill2 = __builtin_nan("");
+    double scale = 1.0;
+    int sverdrup = 0;
+    const int *tr_offsets_dev = nullptr;
+    int ntransect = 0;
+    long row_length = 0;
+    double *scratch = nullptr;
+    size_t scratch_len = 0;
+    double *prof = nullptr;
+};
+int launch_profile(const ProfileArgs &a, hipStream_t s);
+
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q
 int launch_find_points(const double *xy, long ncell, long row_length, LocatorBoxes *keep, const double *targets_dev, long npts,

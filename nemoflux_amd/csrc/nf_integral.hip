@@ -264,4 +264,131 @@ int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *u
     return NF_OK;
 }
 
+// ---- depth-resolved rows: stage A of the record form, one level at a time, straight from the raw fields ------------------
+// Level z's edge values are formed on the fly exactly as K1 forms them for a field whose only non-zero layer is z:
+// eU(c) = +fma(th[z], fixed(u[z,c]), 0) * arcE[c], eV(c) = -fma(th[z], fixed(v[z,c]), 0) * arcN[c], times the Sverdrup
+// scale; south = eV(c - nx) (0 on row 0), west = eU(c - 1) (periodic on column 0), the weighted sum with K3's association
+// and K3's wavefront segmented scan (the flags of the scan depend on the keys only: computed once for all levels).  A lane
+// owns one record and up to kProfileChunk levels: the 40-byte record and the four arc lengths are read once per chunk, the
+// 4 x LZ gathers of a lane are all in flight together.  runsum: (levels of the launch) x n doubles, level-major.
+template <typename T>
+__device__ inline double profile_fixed(T x, T fill, T fill2, bool two)
+{
+    return (x != x || x == fill || (two && x == fill2)) ? 0.0 : (double)x;
+}
+
+template <typename T, int LZ>
+__global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                            const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                            const T *__restrict__ v, long ncell, unsigned nx, int z0,
+                                                            int nlev, const double *__restrict__ thickness,
+                                                            const double *__restrict__ arcE,
+                                                            const double *__restrict__ arcN, T fill, T fill2, int two,
+                                                            double scale, int sverdrup, double *__restrict__ runsum)
+{
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    double val[LZ];
+#pragma unroll
+    for (int l = 0; l < LZ; ++l) val[l] = 0.0;
+    int key = -1;
+    if (k < n) {
+        typedef double dvec2 __attribute__((ext_vector_type(2)));
+        const long c = __builtin_nontemporal_load(cell + k);
+        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
+        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
+        key = __builtin_nontemporal_load(seg + k);
+        const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
+        const bool south = j > 0;
+        const long cs = south ? c - nx : c;             // row 0: no south value (read, then discarded)
+        const long cw = i > 0 ? c - 1 : c - 1 + nx;
+        const double aEc = arcE[c], aNc = arcN[c], aNs = arcN[cs], aEw = arcE[cw];
+        T uc[LZ], uw[LZ], vc[LZ], vs[LZ];
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {   // launch-uniform
+                const long o = (long)(z0 + l) * ncell;
+                uc[l] = u[o + c];
+                uw[l] = u[o + cw];
+                vc[l] = v[o + c];
+                vs[l] = v[o + cs];
+            }
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {
+                const double th = thickness[z0 + l];
+                double d1 = +fma(th, profile_fixed<T>(uc[l], fill, fill2, two), 0.0) * aEc;
+                double d3 = +fma(th, profile_fixed<T>(uw[l], fill, fill2, two), 0.0) * aEw;
+                double d2 = -fma(th, profile_fixed<T>(vc[l], fill, fill2, two), 0.0) * aNc;
+                double d0 = -fma(th, profile_fixed<T>(vs[l], fill, fill2, two), 0.0) * aNs;
+                if (sverdrup) {
+                    d0 *= scale;
+                    d1 *= scale;
+                    d2 *= scale;
+                    d3 *= scale;
+                }
+                if (!south) d0 = 0.0;
+                // the library is built with -ffp-contract=off: the same rounded products and sums as k_gather_segscan
+                val[l] = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
+            }
+    }
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int pk = __shfl_up(key, o, kWave);
+        const bool take = lane >= o && pk == key;
+#pragma unroll
+        for (int l = 0; l < LZ; ++l) {
+            const double pv = __shfl_up(val[l], o, kWave);
+            if (take) val[l] += pv;
+        }
+    }
+    const int nk = __shfl_down(key, 1, kWave);
+    if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) {
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) runsum[(long)l * n + k] = val[l];
+    }
+}
+
+template <typename T>
+static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
+{
+    const WeightSet &ws = *a.ws;
+    const T fill = (T)a.fill, fill2 = (T)a.fill2;
+    const int two = fill2 == fill2 && !(fill2 == fill);   // K1's rule: a second marker that differs from the first
+    for (int zc = a.z0; zc < a.z1; zc += kProfileChunk) {
+        const int nlev = a.z1 - zc < kProfileChunk ? a.z1 - zc : kProfileChunk;
+        double *rows = a.prof + (long)zc * a.row_length;
+        if (ws.nrec > 0)
+            hipLaunchKernelGGL((k_profile_segscan<T, kProfileChunk>), dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)),
+                               dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)a.u,
+                               (const T *)a.v, a.ncell, (unsigned)a.nx, zc, nlev, a.thickness, a.arcE, a.arcN, fill, fill2,
+                               two, a.scale, a.sverdrup, a.scratch);
+        if (ws.nseg > 0) {
+            const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
+            hipLaunchKernelGGL(k_finalize_seg, dim3(nb, (unsigned)nlev), dim3(kBlock), 0, s, a.scratch, ws.seg_start.get(),
+                               ws.nseg, rows, ws.nrec, a.row_length);
+        }
+        if (a.ntransect > 0) {
+            const unsigned nb = (unsigned)(((long)a.ntransect * kWave + kBlock - 1) / kBlock);
+            hipLaunchKernelGGL(k_finalize_tr, dim3(nb, (unsigned)nlev), dim3(kBlock), 0, s, a.tr_offsets_dev, a.ntransect,
+                               ws.nseg, rows, a.row_length);
+        }
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+int launch_profile(const ProfileArgs &a, hipStream_t s)
+{
+    NF_REQUIRE(a.ws && a.ncell > 0 && a.nx > 0 && a.ncell % a.nx == 0 && a.ncell < (1l << 31), NF_ERR_ARG,
+               "profile: bad grid sizes");
+    NF_REQUIRE(a.z0 >= 0 && a.z1 >= a.z0 && a.row_length == a.ws->nseg + a.ntransect, NF_ERR_ARG, "profile: bad arguments");
+    NF_REQUIRE(a.scratch_len >= (size_t)a.ws->nrec * kProfileChunk, NF_ERR_ARG, "profile: scratch too small");
+    if (a.row_length == 0) return NF_OK;
+    if (a.dtype == NF_F64) return launch_profile_t<double>(a, s);
+    if (a.dtype == NF_F32) return launch_profile_t<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
+}
+
 }  // namespace nf

@@ -60,6 +60,21 @@ def _geometry_only(bounds_lon, bounds_lat):
         lib.nf_field_del(ctypes.byref(h))
 
 
+def _band_sum(P, bounds_depth, ztop, zbot):
+    """sum_z P[z] * overlap([ztop, zbot], layer z) / thickness[z], in level order; layers outside the band or of zero
+    thickness are skipped, a layer inside it whole enters with the factor 1 (so the band of whole layers is the plain sum)."""
+    b = numpy.asarray(bounds_depth, dtype=numpy.float64)
+    acc = numpy.zeros(P.shape[1:], numpy.float64)
+    for z in range(P.shape[0]):
+        lo, hi = min(b[z, 0], b[z, 1]), max(b[z, 0], b[z, 1])
+        th = hi - lo
+        ov = min(zbot, hi) - max(ztop, lo)
+        if not (th > 0.0 and ov > 0.0):
+            continue
+        acc = acc + (P[z] if ov >= th else P[z] * (ov / th))
+    return acc
+
+
 class _TimeObj(object):
     """timeobj.TimeObj stand-in that tolerates a missing time axis."""
 
@@ -416,7 +431,8 @@ class Field(object):
         return int(nt), int(nz), int(ny), int(nx)
 
     # ------------------------------------------------------------------------------------------
-    def _compute(self, tIndex, readback=None, prefetch_next=None):
+    def _stage(self, tIndex, prefetch_next=None):
+        """Make step tIndex of a file-backed Field the one the engine reads (no-op for in-memory / HBM fields)."""
         if not (0 <= tIndex < self.nt):
             raise RuntimeError(f'ERROR: time index {tIndex} out of range [0, {self.nt})')
         if self._lazy is not None and self._lazy_step != tIndex:
@@ -430,6 +446,9 @@ class Field(object):
             # on this one: the blocking C call below releases the GIL
             nxt = self._stager.next_after(tIndex)
             self._stager.prefetch(nxt % self.nt if prefetch_next is None else (nxt if nxt < self.nt else -1))
+
+    def _compute(self, tIndex, readback=None, prefetch_next=None):
+        self._stage(tIndex, prefetch_next)
         check(lib.nf_field_compute_flux(ctypes.byref(self._h), int(tIndex), _lib.dptr(self._row)))
         self._row_valid = True
         if self._readback if readback is None else readback:
@@ -479,6 +498,36 @@ class Field(object):
         check(lib.nf_field_compute_all_async(ctypes.byref(self._h), ctypes.c_void_p(out.data_ptr())))
         rows = out.cpu().numpy()
         return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+
+    def computeFluxProfile(self, tIndex, out=None, prefetch_next=None):
+        """Depth-resolved fluxes of time step tIndex: (nz, ntransect) totals and (nz, nseg) per-segment sums, row z = the
+        flux carried by level z alone (the rows of computeFlux, one per level; their sum over z is the full-depth row up to
+        rounding).  Levels this rank does not own (slab_range) are zeros.  The resident edge fluxes, the running max and the
+        row of the last computeFlux are left as they are.  `out`: optional torch CUDA tensor (nz, row_length) that receives
+        the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        self._stage(tIndex, prefetch_next)
+        if out is not None:
+            if tuple(out.shape) != (self.nz, max(self._rowlen, 1)) or not out.is_cuda or not out.is_contiguous():
+                raise RuntimeError(f'ERROR: out must be a contiguous CUDA tensor of shape ({self.nz}, {max(self._rowlen, 1)})')
+            check(lib.nf_field_compute_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((self.nz, max(self._rowlen, 1)), numpy.float64)
+            check(lib.nf_field_compute_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+
+    def depthBandFlux(self, profile, ztop, zbot):
+        """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile (totals or
+        segments, levels first): level z contributes profile[z] * overlap([ztop, zbot], layer z) / thickness[z], exact
+        because a level's flux is linear in its thickness; layers of zero thickness contribute nothing."""
+        ztop, zbot = float(ztop), float(zbot)
+        if not ztop <= zbot:
+            raise ValueError(f'depthBandFlux: need ztop <= zbot, got {ztop}, {zbot}')
+        P = numpy.asarray(profile, dtype=numpy.float64)
+        if P.shape[:1] != (self.nz,):
+            raise ValueError(f'depthBandFlux: the profile must have {self.nz} levels first, got shape {P.shape}')
+        return _band_sum(P, self.bounds_depth, ztop, zbot)
 
     def getFluxText(self):
         """field.py:98-109."""

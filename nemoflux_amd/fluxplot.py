@@ -7,6 +7,7 @@ only with --show): the table is always printed or written as CSV, which is what 
 
     python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -l "[(-100,-80),(100,-80),(0,80)],[...]" [-s] [-o out.csv]
     python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -i "data/nz/*.txt"
+    python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -l "..." --zrange 0,1000   (flux above 1000 m only)
 """
 import argparse
 import glob
@@ -53,10 +54,32 @@ def fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup=False):
     return totals, fld
 
 
-def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False):
+def bandSeries(tFile, uFile, vFile, lonLatZPoints, ztop, zbot, sverdrup=False):
+    """(nt, ntransect) fluxes inside the depth band [ztop, zbot] and the Field: one depth-resolved step per time step."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    totals = numpy.array([fld.depthBandFlux(fld.computeFluxProfile(t, prefetch_next=True)[0], ztop, zbot)
+                          for t in range(fld.nt)]).reshape(fld.nt, len(lonLatZPoints))
+    return totals, fld
+
+
+def parseZRange(zrange):
+    """'ZTOP,ZBOT' -> (ztop, zbot) floats with ztop <= zbot."""
+    try:
+        ztop, zbot = (float(x) for x in zrange.split(','))
+    except ValueError:
+        raise RuntimeError(f'ERROR: --zrange must be ZTOP,ZBOT (two numbers), got {zrange!r}')
+    if not ztop <= zbot:
+        raise RuntimeError(f'ERROR: --zrange needs ZTOP <= ZBOT, got {zrange!r}')
+    return ztop, zbot
+
+
+def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange=''):
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
-    totals, fld = fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup)
+    if zrange:
+        totals, fld = bandSeries(tFile, uFile, vFile, lonLatZPoints, *parseZRange(zrange), sverdrup=sverdrup)
+    else:
+        totals, fld = fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup)
     timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
     unit = 'Sv' if sverdrup else 'A m^2/s'
     header = 'time,' + ','.join(names)
@@ -94,4 +117,6 @@ if __name__ == '__main__':
     ap.add_argument('-s', '--sverdrup', action='store_true')
     ap.add_argument('-o', '--output', default='')
     ap.add_argument('--show', action='store_true')
+    ap.add_argument('--zrange', default='', metavar='ZTOP,ZBOT',
+                    help='flux inside this depth band only (units of deptht_bounds), one depth-resolved step per time step')
     main(**vars(ap.parse_args()))
