@@ -266,6 +266,23 @@ int nf_field_compute_all_async(nf_field **self, double *rows_dev);
  * pass untouched. */
 int nf_field_compute_profile(nf_field **self, long tIndex, double *prof_host);        /* synchronous, host */
 int nf_field_compute_profile_async(nf_field **self, long tIndex, double *prof_dev);   /* HBM, on the field's stream */
+/* Tracer transport across the transects (heat, salt): rows [segments | transects] of the integral of u * tau_face over the
+ * owned levels.  tau sits at T-points; for cell (j, i) and level z, a = tau[t,z,j,i], the east (U) face's b = tau[t,z,j,i+1]
+ * (column nx-1: tau[t,z,j,0] when wrap_x is on, else no b), the north (V) face's b = tau[t,z,j+1,i] (last row: no b).  A
+ * value is present when it is not NaN and not one of the tracer's own two markers (compared in its dtype).  Face value, in
+ * double: both present 0.5*(a+b) - ref, one present that value - ref, neither 0.  acc = fma(th_z, fixed(u) * tf, acc) over
+ * the owned levels, z ascending (fixed = the masking of uo/vo with their markers), eU_tau = +accU * arcE, eV_tau = -accV *
+ * arcN, each times the Sverdrup scale when it is on; the transect reduction is the one of the volume rows.  Units: tracer x
+ * volume-flux units (watts: times rho0 * c_p, and 1e6 in Sverdrup mode).  tau == ref + 1 gives the volume rows bit for bit.
+ * Steps this rank does not touch (slab range) get exact zeros, so the ranks' rows sum to the full ones.  None of these calls
+ * changes the resident planes, |.| arrays, running max or a captured pass; the setters do not invalidate a captured pass. */
+/* tracer at T-points (nt,nz,ny,nx), same nt/nz/ny/nx and dtype as uo/vo; host (staged per step, owned levels only) or HBM */
+int nf_field_set_tracer(nf_field **self, const void *tracer, long nt, int dtype, int on_device, double fill_value);
+int nf_field_set_tracer_missing_value(nf_field **self, double missing_value);  /* NaN = none */
+int nf_field_set_tracer_reference(nf_field **self, double ref);                /* default 0 */
+int nf_field_set_tracer_wrap(nf_field **self, int wrap_x);                     /* default 1 */
+int nf_field_compute_tracer_flux(nf_field **self, long tIndex, double *row_host);   /* row_length doubles */
+int nf_field_compute_tracer_all_async(nf_field **self, double *rows_dev);           /* (nt, row_length) in HBM */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

@@ -70,6 +70,7 @@ struct nf_field {
         DevArray<double> abs;   // [2][ncell]
         DevArray<double> aos;   // (ncell,4) re-pack buffer for read_step, allocated on first use
         DevArray<double> uv2;   // [2][ncell] eU, eV of the first step of a pair ("pass_k3_pairs"), allocated on first use
+        DevArray<double> tr_planes;   // [2][ncell] eU_tau, eV_tau of the last tracer step, allocated on first use
         DevArray<unsigned long long> maxbits;
         // multi-step launches for small grids (compute_all): per-step planes, scratch and z ranges
         DevArray<double> iVb, absb, scratchb;
@@ -103,6 +104,17 @@ struct nf_field {
     // depth-resolved rows (nf_field_compute_profile): the run sums of one chunk of levels (ws.nrec * kProfileChunk, allocated
     // on first use, dropped with the weights) and the (nz, row_length) block of the synchronous call
     DevArray<double> prof_scratch, prof;
+    // tracer at T-points (nf_field_set_tracer*): same (nt, nz, ny, nx) and dtype as uo / vo; none of its setters changes
+    // `version`, and nothing of it enters a captured pass
+    const void *tau = nullptr;
+    long tau_nt = 0;
+    int tau_dtype = NF_F64, tau_on_device = 1;
+    double tau_fill = std::numeric_limits<double>::quiet_NaN();
+    double tau_fill2 = std::numeric_limits<double>::quiet_NaN();
+    double tau_ref = 0.0;
+    int tau_wrap = 1;
+    DevArray<char> stage_tau;   // host-resident tracer: the owned levels of one step
+    DevArray<double> tr_row;    // the row of the synchronous tracer call
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -367,6 +379,66 @@ static int field_profile_async(nf_field *f, long t, double *prof_dev)
     a.scratch_len = f->prof_scratch.size();
     a.prof = prof_dev;
     return launch_profile(a, f->stream);
+}
+
+// Tracer transport of step t on the field's stream: K1tau into geo.tr_planes, then K3 over them into row_dev
+// [segments | transects].  Owned levels only (partial sums), zeros for a step this rank does not touch.  Reads the raw fields
+// and the records; the resident planes, |.| arrays, running max, version and a captured pass stay as they are.
+static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
+{
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
+               "compute_tracer: set_bounds, set_thickness and set_uv first");
+    NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute_tracer: build_weights first");
+    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_tracer: time index out of range");
+    NF_REQUIRE(f->tau_dtype == f->uv_dtype, NF_ERR_ARG, "compute_tracer: the tracer's dtype differs from the dtype of uo/vo");
+    NF_REQUIRE(f->tau_nt == f->nt, NF_ERR_ARG, "compute_tracer: the tracer's nt differs from the nt of uo/vo");
+    const int rowlen = field_row_length(f);
+    if (rowlen == 0) return NF_OK;
+    const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
+    long lo = t * f->nz, hi = (t + 1) * f->nz;
+    if (lo < f->s_begin) lo = f->s_begin;
+    if (hi > s_end) hi = s_end;
+    if (hi <= lo) {   // this rank owns no slab of step t: contributes zeros
+        NF_HIP(hipMemsetAsync(row_dev, 0, sizeof(double) * rowlen, f->stream));
+        return NF_OK;
+    }
+    const int z0 = (int)(lo - t * f->nz), z1 = (int)(hi - t * f->nz);
+    TracerArgs a;
+    NF_TRY(field_step_input(f, t, z0, z1, &a.u, &a.v));
+    const size_t es = elem_size(f->uv_dtype);
+    const size_t step_bytes = (size_t)f->nz * f->ncell * es;
+    if (f->tau_on_device) {
+        a.tau = (const char *)f->tau + (size_t)t * step_bytes;
+    } else {
+        NF_TRY(f->stage_tau.reserve(step_bytes));
+        const size_t off = (size_t)z0 * f->ncell * es, len = (size_t)(z1 - z0) * f->ncell * es;
+        NF_HIP(hipMemcpyAsync(f->stage_tau.get() + off, (const char *)f->tau + (size_t)t * step_bytes + off, len,
+                              hipMemcpyHostToDevice, f->stream));
+        a.tau = f->stage_tau.get();
+    }
+    NF_TRY(f->geo.tr_planes.reserve((size_t)f->ncell * 2));
+    a.dtype = f->uv_dtype;
+    a.ncell = f->ncell;
+    a.ny = f->ny;
+    a.nx = f->nx;
+    a.z0 = z0;
+    a.z1 = z1;
+    a.thickness = f->thick.get();
+    a.arcE = f->geo.arcE.get();
+    a.arcN = f->geo.arcN.get();
+    a.fill = f->fill;
+    a.fill2 = f->fill2;
+    a.tfill = f->tau_fill;
+    a.tfill2 = f->tau_fill2;
+    a.ref = f->tau_ref;
+    a.wrap_x = f->tau_wrap;
+    a.scale = kEarthRadiusSv / 1.e6;   // field.py:226
+    a.sverdrup = f->sverdrup;
+    a.planes = f->geo.tr_planes.get();
+    NF_TRY(launch_tracer_flux(a, f->stream));
+    // K3 reads the two signed members of [4][ncell] planes at +ncell and +2 ncell: the tracer planes sit at +ncell
+    return launch_integral(f->ws, f->geo.tr_planes.get() - f->ncell, f->ncell, 2, f->nx, f->tr_off_dev.get(),
+                           (int)f->polylines.size(), f->scratch.get(), row_dev, f->stream);
 }
 
 // steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
@@ -938,6 +1010,81 @@ try {
                "compute_profile: set_bounds, set_thickness and set_uv first");
     NF_NEED_DEVICE();
     return field_profile_async(f, tIndex, prof_dev);
+}
+NF_API_CATCH
+
+int nf_field_set_tracer(nf_field **self, const void *tracer, long nt, int dtype, int on_device, double fill_value)
+try {
+    NF_REQUIRE(self && *self && tracer, NF_ERR_ARG, "nf_field_set_tracer: null argument");
+    NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_tracer: dtype must be NF_F64/NF_F32");
+    nf_field *f = *self;
+    NF_REQUIRE(f->u && f->v, NF_ERR_STATE, "nf_field_set_tracer: set_uv first");
+    NF_REQUIRE(dtype == f->uv_dtype, NF_ERR_ARG, "nf_field_set_tracer: the tracer's dtype differs from the dtype of uo/vo");
+    if (nt != f->nt) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "nf_field_set_tracer: the tracer has nt = %ld time steps, uo/vo have %ld", nt, f->nt);
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    f->tau = tracer;
+    f->tau_nt = nt;
+    f->tau_dtype = dtype;
+    f->tau_on_device = on_device ? 1 : 0;
+    f->tau_fill = fill_value;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_tracer_missing_value(nf_field **self, double missing_value)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_tracer_missing_value: null field");
+    (*self)->tau_fill2 = missing_value;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_tracer_reference(nf_field **self, double ref)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_tracer_reference: null field");
+    NF_REQUIRE(std::isfinite(ref), NF_ERR_ARG, "nf_field_set_tracer_reference: the reference must be a finite number");
+    (*self)->tau_ref = ref;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_tracer_wrap(nf_field **self, int wrap_x)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_tracer_wrap: null field");
+    NF_REQUIRE(wrap_x == 0 || wrap_x == 1, NF_ERR_ARG, "nf_field_set_tracer_wrap: wrap_x must be 0 or 1");
+    (*self)->tau_wrap = wrap_x;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_tracer_flux(nf_field **self, long tIndex, double *row_host)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_compute_tracer_flux: null field");
+    nf_field *f = *self;
+    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_flux: set_tracer first");
+    NF_NEED_DEVICE();
+    const int rowlen = field_row_length(f);
+    NF_TRY(f->tr_row.reserve((size_t)(rowlen > 0 ? rowlen : 1)));
+    NF_TRY(field_tracer_step_async(f, tIndex, f->tr_row.get()));
+    if (row_host && rowlen > 0)
+        NF_HIP(hipMemcpyAsync(row_host, f->tr_row.get(), sizeof(double) * rowlen, hipMemcpyDeviceToHost, f->stream));
+    NF_HIP(hipStreamSynchronize(f->stream));
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_tracer_all_async(nf_field **self, double *rows_dev)
+try {
+    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_tracer_all_async: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_all_async: set_tracer first");
+    NF_NEED_DEVICE();
+    const int rowlen = field_row_length(f);
+    for (long t = 0; t < f->nt; ++t) NF_TRY(field_tracer_step_async(f, t, rows_dev + (size_t)t * rowlen));
+    return NF_OK;
 }
 NF_API_CATCH
 

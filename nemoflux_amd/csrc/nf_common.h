@@ -343,6 +343,25 @@ struct ProfileArgs {
 };
 int launch_profile(const ProfileArgs &a, hipStream_t s);
 
+// Tracer transport (nf_field_compute_tracer_flux, nf_tracer.hip): K1's vertical integral with every level's velocity
+// multiplied by the tracer interpolated to the face, tf = 0.5 (a + b) - ref (DESIGN.md section 4 has the face rule).  Writes
+// the two signed planes [eU_tau | eV_tau] of one time step, nothing else; K3 (planes = 2) reduces them.
+struct TracerArgs {
+    const void *u = nullptr, *v = nullptr, *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
+    int dtype = NF_F64;
+    long ncell = 0, ny = 0, nx = 0;
+    int z0 = 0, z1 = 0;
+    const double *thickness = nullptr, *arcE = nullptr, *arcN = nullptr;   // device
+    double fill = __builtin_nan(""), fill2 = __builtin_nan("");     // uo / vo markers (as in FluxArgs)
+    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");   // the tracer's own _FillValue / missing_value
+    double ref = 0.0;         // reference value subtracted from every face value
+    int wrap_x = 1;           // 1: the east face of column nx-1 takes column 0 as its neighbour
+    double scale = 1.0;
+    int sverdrup = 0;
+    double *planes = nullptr; // [2][ncell]: eU_tau, eV_tau
+};
+int launch_tracer_flux(const TracerArgs &a, hipStream_t s);
+
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q
 int launch_find_points(const double *xy, long ncell, long row_length, LocatorBoxes *keep, const double *targets_dev, long npts,

@@ -1,0 +1,223 @@
+// nf_tracer.hip -- K1tau: tracer transport across the cell faces of one time step (heat, salt): the vertical integral of
+// u * tau_face over the owned levels, fused with the edge-flux assembly of K1.  K3 (planes = 2) reduces its two planes.
+//
+// Definition.  tau sits at T-points, (nt, nz, ny, nx) like uo / vo.  For cell c = (j, i) and level z,
+// a = tau[z, j, i]; the east face's b = tau[z, j, i+1] (column nx-1: tau[z, j, 0] when wrap_x, else none), the north face's
+// b = tau[z, j+1, i] (last row: none).  A value is present when it is not NaN and not one of the tracer's two markers.
+//   tf = 0.5 (a + b) - ref  (both present),  the present one - ref  (one),  0  (neither)
+//   accU = fma(th_z, fixed(u) * tfE, accU), z ascending; eU_tau = +accU * arcE (* scale), eV_tau = -accV * arcN (* scale)
+// fixed() is K1's masking of uo / vo.  With tau == ref + 1 every tf is exactly 1 and the planes are K1's eU, eV bit for bit.
+//
+// Access pattern: K1's.  A lane owns VEC consecutive cells (16 B of the field dtype) and walks z with stride ncell, issuing
+// all loads of a batch of UZ levels before the first use.  Per level it loads u, v, tau and the tau of the row above (a second
+// contiguous stream at +nx, which the waves nx cells further on read as their own row at about the same time: served on
+// die).  The east neighbour of a lane's last cell is the first cell of the next lane (a cross-lane shift); the last lane of
+// a wavefront loads it itself, and the lane that holds a row's last column loads the row's first cell for the wrap.
+//
+// Algorithmic bytes per (t,z,j,i): 3*sizeof(T) read + (16 arc + 16 planes)/nz.
+#include "nf_common.h"
+
+namespace nf {
+
+namespace {
+
+typedef double tr_dvec2 __attribute__((ext_vector_type(2)));
+typedef float tr_fvec4 __attribute__((ext_vector_type(4)));
+template <typename T, int VEC> struct tr_vec;
+template <> struct tr_vec<double, 2> { using type = tr_dvec2; };
+template <> struct tr_vec<float, 4> { using type = tr_fvec4; };
+template <> struct tr_vec<double, 1> { using type = double; };
+template <> struct tr_vec<float, 1> { using type = float; };
+
+template <typename T, int VEC> struct TrLanes {
+    T x[VEC];
+};
+
+// VEC consecutive values at p (16-byte aligned when ALIGNED)
+template <typename T, int VEC, bool NT, bool ALIGNED = true>
+__device__ inline TrLanes<T, VEC> tr_load(const T *p)
+{
+    TrLanes<T, VEC> r;
+    if (ALIGNED) {
+        using V = typename tr_vec<T, VEC>::type;
+        V v = NT ? __builtin_nontemporal_load(reinterpret_cast<const V *>(p)) : *reinterpret_cast<const V *>(p);
+        __builtin_memcpy(&r, &v, sizeof(V));
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) r.x[k] = p[k];
+    }
+    return r;
+}
+
+// K1's masking of uo / vo (nf_flux.hip fixed2): NaN or one of the two markers -> 0
+template <typename T>
+__device__ inline double tr_fixed(T x, T fill, T fill2)
+{
+    return (x != x || x == fill || x == fill2) ? 0.0 : (double)x;
+}
+
+template <typename T>
+__device__ inline bool tr_present(T x, T m1, T m2)
+{
+    return !(x != x || x == m1 || x == m2);
+}
+
+// the face value of the definition above; has_b = false: the face has no second cell
+template <typename T>
+__device__ inline double tr_face(T a, T b, bool has_b, T m1, T m2, double ref)
+{
+    const bool pa = tr_present(a, m1, m2), pb = has_b && tr_present(b, m1, m2);
+    const double s = (pa && pb) ? 0.5 * ((double)a + (double)b) : (pa ? (double)a : (double)b);
+    return (pa || pb) ? s - ref : 0.0;
+}
+
+}  // namespace
+
+// 256 threads, one chunk of VEC cells per lane: lane c0 = (tile * 256 + tid) * VEC.  ncell % VEC == 0 and nx >= VEC (the
+// launcher picks VEC = 1 otherwise), so a lane's cells hold at most one row end.  NAL: nx % VEC == 0, the north stream is
+// 16-byte aligned too.
+template <typename T, int VEC, int UZ, bool NAL>
+__global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, const T *__restrict__ v,
+                                                     const T *__restrict__ tau, long ncell, unsigned nx, int z0, int z1,
+                                                     const double *__restrict__ thickness, const double *__restrict__ arcE,
+                                                     const double *__restrict__ arcN, T fill, T fill2, T tfill, T tfill2,
+                                                     double ref, int wrap_x, double scale, int sverdrup,
+                                                     double *__restrict__ planes, unsigned ntiles)
+{
+    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
+    if (tile >= ntiles) return;   // workgroup-uniform
+    const int lane = threadIdx.x & (kWave - 1);
+    const long c0 = ((long)tile * 256 + threadIdx.x) * VEC;
+    const bool on = c0 < ncell;   // a lane's cells are all there or all absent
+    // neighbour bookkeeping, once per lane
+    const long cs = on ? c0 : 0;
+    const unsigned i0 = (unsigned)(cs % nx);
+    const int kend = (nx - 1 - i0 < (unsigned)VEC) ? (int)(nx - 1 - i0) : -1;   // the cell in column nx-1, if any
+    const bool wrap = on && kend >= 0 && wrap_x;                                // it loads its row's first cell
+    const long cwrap = cs + kend + 1 - (long)nx;
+    // the east neighbour of the last cell comes from the next lane, except at the end of a wavefront
+    const bool own_next = on && lane == kWave - 1 && kend != VEC - 1 && c0 + VEC < ncell;
+    const bool north_all = on && c0 + VEC - 1 + (long)nx < ncell;
+    bool has_n[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) has_n[k] = on && c0 + k + (long)nx < ncell;
+
+    double accU[VEC], accV[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) accU[k] = accV[k] = 0.0;
+    const T *pu = u + (long)z0 * ncell + cs;
+    const T *pv = v + (long)z0 * ncell + cs;
+    const T *pt = tau + (long)z0 * ncell + cs;
+    for (int z = z0; z < z1; z += UZ) {
+        const int nlev = z1 - z < UZ ? z1 - z : UZ;
+        TrLanes<T, VEC> lu[UZ], lv[UZ], lt[UZ], ln[UZ];
+        T nx1[UZ], wv[UZ];
+#pragma unroll
+        for (int r = 0; r < UZ; ++r)
+            if (r < nlev) {
+                const long o = (long)r * ncell;
+                if (on) {
+                    lu[r] = tr_load<T, VEC, true>(pu + o);
+                    lv[r] = tr_load<T, VEC, true>(pv + o);
+                    lt[r] = tr_load<T, VEC, false>(pt + o);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) lu[r].x[k] = lv[r].x[k] = lt[r].x[k] = T(0);
+                }
+                if (north_all) {
+                    ln[r] = tr_load<T, VEC, false, NAL>(pt + o + nx);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) ln[r].x[k] = has_n[k] ? pt[o + nx + k] : T(0);
+                }
+                nx1[r] = own_next ? pt[o + VEC] : T(0);
+                wv[r] = wrap ? pt[o + (cwrap - cs)] : T(0);
+            }
+#pragma unroll
+        for (int r = 0; r < UZ; ++r)
+            if (r < nlev) {
+                const double th = thickness[z + r];
+                // every lane takes part in the shift (inactive lanes hand on zeros)
+                const T sh = __shfl_down(lt[r].x[0], 1, kWave);
+                const T next = own_next ? nx1[r] : sh;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const T a = lt[r].x[k];
+                    const T be = k == kend ? wv[r] : (k + 1 < VEC ? lt[r].x[k + 1 < VEC ? k + 1 : k] : next);
+                    const bool has_e = k != kend || wrap_x;
+                    const double tfE = tr_face<T>(a, be, has_e, tfill, tfill2, ref);
+                    const double tfN = tr_face<T>(a, ln[r].x[k], has_n[k], tfill, tfill2, ref);
+                    accU[k] = fma(th, tr_fixed<T>(lu[r].x[k], fill, fill2) * tfE, accU[k]);
+                    accV[k] = fma(th, tr_fixed<T>(lv[r].x[k], fill, fill2) * tfN, accV[k]);
+                }
+            }
+        pu += (long)UZ * ncell;
+        pv += (long)UZ * ncell;
+        pt += (long)UZ * ncell;
+    }
+    if (!on) return;
+    // edge terms in K1's order (field.py:195-196, 225-228)
+    double eU[VEC], eV[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        eU[k] = +accU[k] * arcE[c0 + k];
+        eV[k] = -accV[k] * arcN[c0 + k];
+        if (sverdrup) {
+            eU[k] *= scale;
+            eV[k] *= scale;
+        }
+    }
+    double *pU = planes + c0, *pV = planes + ncell + c0;
+    if (VEC == 1) {
+        pU[0] = eU[0];
+        pV[0] = eV[0];
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; k += 2) {
+            *reinterpret_cast<double2 *>(pU + k) = make_double2(eU[k], eU[k + 1 < VEC ? k + 1 : k]);
+            *reinterpret_cast<double2 *>(pV + k) = make_double2(eV[k], eV[k + 1 < VEC ? k + 1 : k]);
+        }
+    }
+}
+
+namespace {
+// levels per batch: four 16-byte streams per level.  Four levels: 110 VGPRs, 4 waves per SIMD, no scratch
+// (-Rpass-analysis=kernel-resource-usage); five levels take 133 VGPRs and 3 waves
+constexpr int kTracerLevels = 4;
+
+template <typename T, int VEC, bool NAL>
+int launch_tracer_t(const TracerArgs &a, hipStream_t s)
+{
+    const long per_tile = 256l * VEC;
+    const unsigned ntiles = (unsigned)((a.ncell + per_tile - 1) / per_tile);
+    const unsigned grid = xcd_grid(ntiles);
+    hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevels, NAL>), dim3(grid), dim3(256), 0, s, (const T *)a.u,
+                       (const T *)a.v, (const T *)a.tau, a.ncell, (unsigned)a.nx, a.z0, a.z1, a.thickness, a.arcE, a.arcN,
+                       (T)a.fill, (T)a.fill2, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0, a.scale, a.sverdrup,
+                       a.planes, ntiles);
+    NF_HIP(hipGetLastError());
+    return NF_OK;
+}
+
+template <typename T, int VEC>
+int launch_tracer_v(const TracerArgs &a, hipStream_t s)
+{
+    const bool al16 = ((uintptr_t)a.u % 16 == 0) && ((uintptr_t)a.v % 16 == 0) && ((uintptr_t)a.tau % 16 == 0);
+    if (al16 && a.ncell % VEC == 0 && a.nx >= VEC)
+        return a.nx % VEC == 0 ? launch_tracer_t<T, VEC, true>(a, s) : launch_tracer_t<T, VEC, false>(a, s);
+    return launch_tracer_t<T, 1, true>(a, s);   // odd sizes / unaligned fields: one cell per lane
+}
+}  // namespace
+
+int launch_tracer_flux(const TracerArgs &a, hipStream_t s)
+{
+    NF_REQUIRE(a.ncell > 0 && a.nx > 0 && a.ncell == a.ny * a.nx && a.ncell < (1l << 31), NF_ERR_ARG,
+               "tracer flux: bad grid sizes");
+    NF_REQUIRE(a.z1 > a.z0 && a.z0 >= 0, NF_ERR_ARG, "tracer flux: empty z range");
+    NF_REQUIRE(a.u && a.v && a.tau && a.planes && a.thickness && a.arcE && a.arcN, NF_ERR_ARG, "tracer flux: null argument");
+    if (a.dtype == NF_F64) return launch_tracer_v<double, 2>(a, s);
+    if (a.dtype == NF_F32) return launch_tracer_v<float, 4>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "tracer flux: dtype must be NF_F64 or NF_F32");
+}
+
+}  // namespace nf

@@ -517,6 +517,101 @@ class Field(object):
             check(lib.nf_field_compute_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
 
+    def setTracer(self, tracer, fill_value=None, missing_value=None, reference=0.0, wrapX=True):
+        """A tracer at T-points (potential temperature, salinity) for computeTracerFlux / computeTracerAll: the same
+        (nt, nz, ny, nx) and dtype as uo / vo.  `tracer`: a host array (staged one time step at a time), a torch CUDA tensor
+        or a DeviceArray (used in place), or a (path, name) pair read with nemoflux_amd.io one time step at a time, its CF
+        markers and scale / offset decoded as for uo.  fill_value / missing_value: the tracer's own missing markers (a file's
+        _FillValue / missing_value when not given; NaN always counts as missing).  reference: subtracted from every face value
+        (theta_ref of a heat transport).  wrapX: the east face of the last column takes the first column as its neighbour
+        (the periodic rule of the volume rows)."""
+        self._tracer_lazy = None
+        self._tracer_keep = None
+        self._tracer_step = -1
+        if isinstance(tracer, tuple) and len(tracer) == 2 and isinstance(tracer[1], str):
+            path, name = tracer
+            var, _, d = open_uvfile(path, name, with_all=True)
+            markers = list(d['_markers_' + name])
+            if fill_value is None:
+                fill_value = markers[0] if markers else None
+            if missing_value is None:
+                missing_value = markers[1] if len(markers) > 1 else None
+            if len(markers) > 2:
+                raise RuntimeError(f'ERROR: tracer {name} carries {len(markers)} different _FillValue / missing_value markers '
+                                   f'({markers}); the engine masks at most two')
+            tracer = var
+        shape = tuple(int(x) for x in tracer.shape)
+        if self.getSizes(shape) != (self.nt, self.nz, self.ny, self.nx):
+            raise RuntimeError(f'ERROR: the tracer has shape {shape}; uo/vo have (nt, nz, ny, nx) = '
+                               f'{(self.nt, self.nz, self.ny, self.nx)}')
+        code = _dtype_code(tracer)
+        fill = numpy.nan if fill_value is None else float(fill_value)
+        ptr = _lib.device_pointer(tracer)
+        on_dev = 1
+        if hasattr(tracer, 'read_step'):
+            # file-backed: step t is read into one pinned host buffer and handed over as a host-resident tracer through a
+            # virtual (nt, nz, ny, nx) base that the engine only dereferences at step t (as _stage does for uo / vo)
+            self._tracer_lazy = tracer
+            self._tracer_buf = self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('='))
+            self._tracer_code, self._tracer_fill = code, fill
+            ptr = None
+        elif ptr is None:
+            tracer = _native(tracer)
+            ptr, on_dev = tracer.ctypes.data, 0
+        self._tracer_keep = tracer
+        if ptr is not None:
+            check(lib.nf_field_set_tracer(ctypes.byref(self._h), ptr, self.nt, code, on_dev, fill))
+        check(lib.nf_field_set_tracer_missing_value(ctypes.byref(self._h),
+                                                    numpy.nan if missing_value is None else float(missing_value)))
+        check(lib.nf_field_set_tracer_reference(ctypes.byref(self._h), float(reference)))
+        check(lib.nf_field_set_tracer_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
+        self._tracer_set = True
+
+    def _stage_tracer(self, tIndex):
+        if not getattr(self, '_tracer_set', False):
+            raise RuntimeError('ERROR: call setTracer first')
+        if self._tracer_lazy is not None and self._tracer_step != tIndex:
+            self._tracer_lazy.read_step(tIndex, out=self._tracer_buf)
+            off = tIndex * self._tracer_buf.nbytes
+            check(lib.nf_field_set_tracer(ctypes.byref(self._h), self._tracer_buf.ctypes.data - off, self.nt,
+                                          self._tracer_code, 0, self._tracer_fill))
+            self._tracer_step = tIndex
+
+    def computeTracerFlux(self, tIndex):
+        """Tracer transport of time step tIndex across the transects (setTracer first): (ntransect,) totals and (nseg,)
+        per-segment sums in tracer x flux units (x rho0 * c_p for a heat transport in W, and x 1e6 in Sverdrup mode).  Levels
+        this rank does not own (slab_range) contribute nothing.  The volume rows, resident edge fluxes and the running max are
+        left as they are."""
+        tIndex = int(tIndex)
+        self._stage(tIndex)
+        self._stage_tracer(tIndex)
+        row = numpy.zeros(max(self._rowlen, 1), numpy.float64)
+        check(lib.nf_field_compute_tracer_flux(ctypes.byref(self._h), tIndex, _lib.dptr(row)))
+        return row[self._nseg:self._nseg + len(self.plis)], row[:self._nseg]
+
+    def computeTracerAll(self, out=None):
+        """Tracer transport of all nt steps: (nt, ntransect) totals and (nt, nseg) per-segment sums.  `out`: optional torch
+        CUDA tensor (nt, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        import torch
+        if out is not None and (tuple(out.shape) != (self.nt, max(self._rowlen, 1)) or not out.is_cuda or
+                                not out.is_contiguous() or out.dtype != torch.float64):
+            raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape ({self.nt}, {max(self._rowlen, 1)})')
+        if self._lazy is not None or getattr(self, '_tracer_lazy', None) is not None:
+            # file-backed fields or tracer: one step at a time through the host
+            rows = numpy.zeros((self.nt, max(self._rowlen, 1)), numpy.float64)
+            for t in range(self.nt):
+                tot, seg = self.computeTracerFlux(t)
+                rows[t, :self._nseg], rows[t, self._nseg:self._nseg + len(self.plis)] = seg, tot
+            if out is not None:
+                out.copy_(torch.from_numpy(rows))
+        else:
+            self._stage_tracer(0)
+            if out is None:
+                out = torch.empty((self.nt, max(self._rowlen, 1)), dtype=torch.float64, device='cuda')
+            check(lib.nf_field_compute_tracer_all_async(ctypes.byref(self._h), ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+
     def depthBandFlux(self, profile, ztop, zbot):
         """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile (totals or
         segments, levels first): level z contributes profile[z] * overlap([ztop, zbot], layer z) / thickness[z], exact

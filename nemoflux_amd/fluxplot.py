@@ -8,6 +8,8 @@ only with --show): the table is always printed or written as CSV, which is what 
     python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -l "[(-100,-80),(100,-80),(0,80)],[...]" [-s] [-o out.csv]
     python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -i "data/nz/*.txt"
     python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -l "..." --zrange 0,1000   (flux above 1000 m only)
+    python -m nemoflux_amd.fluxplot -t T.nc -u U.nc -v V.nc -l "..." -s --tracer thetao --tracer-scale 4.1e-3
+                                  (heat transport in PW: Sv degC x 1e6 m^3/s x rho0 c_p (4.1e6 J/m^3/K) x 1e-15 PW/W)
 """
 import argparse
 import glob
@@ -62,6 +64,31 @@ def bandSeries(tFile, uFile, vFile, lonLatZPoints, ztop, zbot, sverdrup=False):
     return totals, fld
 
 
+def tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False):
+    """(nt, ntransect) tracer transports (Field.computeTracerAll) of the variable `tracer` of tracerFile (default: the T
+    file) and the Field."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    totals, _ = fld.computeTracerAll()
+    return totals, fld
+
+
+def checkTracerArgs(tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, zrange=''):
+    """the tracer options of the command line: refused combinations raise RuntimeError"""
+    if not tracer:
+        if tracerFile:
+            raise RuntimeError('ERROR: --tracer-file needs --tracer NAME (the variable to read from it)')
+        if float(tracerRef) != 0.0 or float(tracerScale) != 1.0:
+            raise RuntimeError('ERROR: --tracer-ref / --tracer-scale need --tracer NAME')
+        return
+    if zrange:
+        raise RuntimeError('ERROR: --tracer and --zrange cannot be combined: depth-resolved tracer transports are not '
+                           'available')
+    for name, x in (('--tracer-ref', tracerRef), ('--tracer-scale', tracerScale)):
+        if not numpy.isfinite(float(x)):
+            raise RuntimeError(f'ERROR: {name} must be a finite number, got {x!r}')
+
+
 def parseZRange(zrange):
     """'ZTOP,ZBOT' -> (ztop, zbot) floats with ztop <= zbot."""
     try:
@@ -73,22 +100,31 @@ def parseZRange(zrange):
     return ztop, zbot
 
 
-def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange=''):
+def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
+         tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0):
+    checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, zrange)
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
-    if zrange:
+    if tracer:
+        totals, fld = tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup)
+        totals = totals * float(tracerScale)
+    elif zrange:
         totals, fld = bandSeries(tFile, uFile, vFile, lonLatZPoints, *parseZRange(zrange), sverdrup=sverdrup)
     else:
         totals, fld = fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup)
     timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
     unit = 'Sv' if sverdrup else 'A m^2/s'
+    title, what = 'Water flow', 'water flow'
+    if tracer:
+        title = what = f'Transport of {tracer}'
+        unit = f'{tracer} x {unit}' + (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '')
     header = 'time,' + ','.join(names)
     lines = [header] + [f'{timeVals[t]},' + ','.join(f'{x:.15g}' for x in totals[t]) for t in range(fld.nt)]
     if output:
         with open(output, 'w') as f:
-            f.write(f'# water flow [{unit}]\n' + '\n'.join(lines) + '\n')
+            f.write(f'# {what} [{unit}]\n' + '\n'.join(lines) + '\n')
     else:
-        print(f'# water flow [{unit}]')
+        print(f'# {what} [{unit}]')
         print('\n'.join(lines))
     if show:
         try:
@@ -101,7 +137,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
             plt.plot(timeVals, totals[:, i], lineTypes[i % len(lineTypes)])
         if len(names) > 1:
             plt.legend(names)
-        plt.title('Water flow')
+        plt.title(title)
         plt.ylabel(unit)
         plt.show()
     return totals
@@ -119,4 +155,11 @@ if __name__ == '__main__':
     ap.add_argument('--show', action='store_true')
     ap.add_argument('--zrange', default='', metavar='ZTOP,ZBOT',
                     help='flux inside this depth band only (units of deptht_bounds), one depth-resolved step per time step')
+    ap.add_argument('--tracer', default='', metavar='NAME',
+                    help='tracer transport (e.g. heat: thetao) instead of the water flow: NAME is read from the T file')
+    ap.add_argument('--tracer-file', dest='tracerFile', default='', metavar='FILE', help='read --tracer from FILE instead')
+    ap.add_argument('--tracer-ref', dest='tracerRef', type=float, default=0.0, metavar='X',
+                    help='reference value subtracted from the tracer (theta_ref of a heat transport across an open section)')
+    ap.add_argument('--tracer-scale', dest='tracerScale', type=float, default=1.0, metavar='S',
+                    help='multiply the tracer transport by S (with -s: 1e6 * rho0 * c_p * 1e-15 = 4.1e-3 turns Sv degC into PW)')
     main(**vars(ap.parse_args()))
