@@ -3,7 +3,7 @@
 
 Metric (BASELINE.json): edge-flux integrals/sec = (t,z,j,i) grid points per wall-second through the full-field
 pass  A4 (missing->0, vertical integral) + A5 (edge fluxes, 4-slot array, |.|, running max) + A7 (all transects),
-inputs resident in HBM; plus the absolute error of every transect total against the closed form (fluxexact).
+inputs resident in HBM; with --full also the absolute error of every transect total against the closed form (fluxexact).
 
 Workload at N=1 (config C4 of BASELINE.json, the one the metric is quoted on; it fits one 288 GB GPU):
     3600 x 1800 x 75 levels x 12 time steps, float64, psi = (1+10z)(t+1) arctan2(y, x+180)/(2 pi) (singular),
@@ -14,9 +14,12 @@ reduction per time step), followed -- for N>1 -- by ONE RCCL all-reduce of the (
 Scaling: strong by default -- BASELINE config 4 is the FIXED 3600 x 1800 x 75 x 12 problem "nt x nz sharded over
 8 x MI355X": its 900 (t,z) slabs are cut into N contiguous ranges, one per rank (11.7 GB of u,v per GPU at N=8).
 --scaling weak gives every rank a C4-sized block of 12 time steps of a 12*N-step series instead.
-At N=1 the line also carries a float32 sub-record (the dtype of real NEMO files) and the CPU baseline.
+A plain run sets up, warms up, times the steps and prints the line (with the roofline of the HIP events of those steps).
+Everything else is --full: the accuracy check, the timed weight build, (N=1) a float32 sub-record (the dtype of real NEMO
+files), the CPU baseline, the ingest and C3 sub-records, (N>1) the timed all-reduce and the per-rank records.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its own N ranks, see self_launch)
+    python bench.py ... --full                  (everything the benchmark measures and checks; --no-* trim it)
     python bench.py ... --dump-outputs DIR      (the rows of the last timed step as DIR/*.npy, to compare two builds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
@@ -151,13 +154,17 @@ def run_workload(args, dtype, scaling, rank, world, local, want_totals=False, em
         fld = Field.fromArrays(dg.bounds_lon, dg.bounds_lat, dg.deptht_bounds, ug, vg, xyzs, slab_range=srange,
                                readback=False, stream=stream, compact=args.compact)
     setup_s = time.time() - t0
-    # the weight build (K2) of this transect batch on its own: a second build of the same weights, timed (the first one above
-    # also paid the first-use costs of the process)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    check(lib.nf_field_build_weights(ctypes.byref(fld._h), 128, ctypes.c_double(360.)))
-    torch.cuda.synchronize()
-    weights_build_ms = (time.perf_counter() - t0) * 1e3
+    weights_build_ms = None
+    if args.full:
+        # the weight build (K2) of this transect batch on its own: a second build of the same weights, timed (the first one
+        # above also paid the first-use costs of the process)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        check(lib.nf_field_build_weights(ctypes.byref(fld._h), 128, ctypes.c_double(360.)))
+        torch.cuda.synchronize()
+        weights_build_ms = (time.perf_counter() - t0) * 1e3
+    nweights = ctypes.c_size_t()
+    check(lib.nf_field_num_weights(ctypes.byref(fld._h), ctypes.byref(nweights)))
     rows = torch.zeros((nt_global, fld._rowlen), dtype=torch.float64, device='cuda')
 
     def step():
@@ -200,10 +207,10 @@ def run_workload(args, dtype, scaling, rank, world, local, want_totals=False, em
         units_total = float(srange[1] - srange[0]) * ny * nx
     m = {'value': units_total * args.steps / elapsed, 'ms_per_step': elapsed / args.steps * 1e3,
          'nt_global': nt_global, 'setup_s': setup_s, 'weights_build_ms': weights_build_ms, 'psi': psi, 'polys': polys, 'nseg': fld._nseg,
-         'weight_entries': int(fld.getWeights()[0].size), 'dg': dg, 'u': u, 'v': v, 'xyz0': xyzs[0]}
+         'weight_entries': int(nweights.value), 'dg': dg, 'u': u, 'v': v, 'xyz0': xyzs[0]}
 
     # ---- the one collective of the N>1 path, timed on its own after the timed region (message = the rows)
-    if world > 1:
+    if world > 1 and args.full:
         reps = 20
         torch.cuda.synchronize()
         barrier()
@@ -245,17 +252,20 @@ def run_workload(args, dtype, scaling, rank, world, local, want_totals=False, em
         m['ranks'] = recs
         step()                       # the rows the accuracy block reads: one clean pass after the repeated reduces
 
-    # ---- accuracy: every transect total of every time step vs the closed form (fluxexact.py:36-46)
-    res = rows.cpu().numpy()
     nseg = fld._nseg
-    max_err, max_ref = 0.0, 0.0
-    for p, pts in enumerate(polys if rank == 0 and not emulate else []):     # rank 0 prints the line: only it needs the check
-        ex = exactFlux(psi, pts, nz, nt_global)
-        got = res[:, nseg + p]
-        max_err = max(max_err, float(numpy.abs(got - numpy.array(ex)).max()))
-        max_ref = max(max_ref, float(numpy.abs(ex).max()))
-    if emulate:     # partial rows of one rank: nothing to compare with the closed form
-        max_err, max_ref = None, None
+    res = rows.cpu().numpy() if args.full or want_totals else None
+    if args.full:   # ---- accuracy: every transect total of every time step vs the closed form (fluxexact.py:36-46)
+        max_err, max_ref = 0.0, 0.0
+        for p, pts in enumerate(polys if rank == 0 and not emulate else []):     # rank 0 prints the line: only it checks
+            ex = exactFlux(psi, pts, nz, nt_global)
+            got = res[:, nseg + p]
+            max_err = max(max_err, float(numpy.abs(got - numpy.array(ex)).max()))
+            max_ref = max(max_ref, float(numpy.abs(ex).max()))
+        if emulate:     # partial rows of one rank: nothing to compare with the closed form
+            max_err, max_ref = None, None
+        m['accuracy'] = {'max_abs_err_vs_fluxexact': max_err, 'max_abs_exact': max_ref,
+                         'singular_transect_t0': float(res[0, nseg + 0]), 'transect_steps_checked': len(polys) * nt_global}
+    if emulate:
         m['emulated'] = {'rank': emulate[0], 'of': emulate[1], 'slabs': [int(srange[0]), int(srange[1])],
                          'steps_touched': [int(t_begin), int(t_end)], 'launches_per_pass': nlaunch // max(1, args.steps),
                          'ms_per_pass': round(elapsed / args.steps * 1e3, 4),
@@ -263,8 +273,6 @@ def run_workload(args, dtype, scaling, rank, world, local, want_totals=False, em
                          'k_expand_ms': round(expand_ms / max(1, args.steps), 4),
                          'k3_ms': round(k3_ms / max(1, args.steps), 4),
                          'partial_step_planes': 'full (knob)' if 'partial_step_planes=1' in args.knob else 'signed-only (default)'}
-    m['accuracy'] = {'max_abs_err_vs_fluxexact': max_err, 'max_abs_exact': max_ref,
-                     'singular_transect_t0': float(res[0, nseg + 0]), 'transect_steps_checked': len(polys) * nt_global}
     if want_totals:
         m['totals'] = res[:, nseg:nseg + len(polys)].tolist()
     if last_rows is not None:   # what Field.computeAll hands its caller: (nt, ntransect) totals and (nt, nseg) segment sums
@@ -315,6 +323,11 @@ def main():
     ap.add_argument('--scaling', default='strong', choices=['weak', 'strong'],
                     help='strong (default): the nt*nz slabs of the stated problem are cut N ways; weak: nt steps per rank')
     ap.add_argument('--batch', type=int, default=64, help='number of extra seeded transects')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: the accuracy of every transect total '
+                         'against the closed form, a timed second weight build, the timed all-reduce and per-rank records '
+                         '(N>1), the CPU baseline, the float32, file-ingest and C3 sub-records (N=1; the --no-* options skip '
+                         'them)')
     ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
     ap.add_argument('--no-f32', action='store_true', help='skip the float32 sub-record (N=1, --dtype f64 only)')
     ap.add_argument('--no-ingest', action='store_true', help='skip the file-ingest sub-record (N=1)')
@@ -323,7 +336,8 @@ def main():
     ap.add_argument('--dump-totals', action='store_true', help='add the (nt, ntransect) totals to the JSON (small grids)')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most '
-                         '64 MB in all: larger outputs are cut to a fixed seeded sample of their columns)')
+                         '64 MB in all: larger outputs are cut to a fixed seeded sample of their columns); the same arrays with '
+                         'or without --full, so the float32 and C3 workloads run for it (N=1)')
     ap.add_argument('--emulate-rank', default=None, metavar='r/N',
                     help='NOT a scaling run: on ONE GPU, do exactly what rank r of an N-rank strong-scaling run does (its slab '
                          'range, its launches; no reduce) and report its ms per pass -- per-rank compute evidence for N > 1')
@@ -392,10 +406,12 @@ def main():
                    'parallelism': f'(t,z)-slab sharding x{world}, 1 all-reduce',
                    'resident_outputs': 'eU,eV only (compact, non-headline)' if args.compact else
                                        'integratedVelocity [4][ncell] + |eU|,|eV| every step',
-                   'setup_s': round(m['setup_s'], 3), 'weights_build_ms': round(m['weights_build_ms'], 3)},
+                   'setup_s': round(m['setup_s'], 3)},
         'roofline': m['roofline'],
-        'accuracy': m['accuracy'],
     }
+    if args.full:
+        out['config']['weights_build_ms'] = round(m['weights_build_ms'], 3)
+        out['accuracy'] = m['accuracy']
     if emulate:
         out['emulated_rank'] = m['emulated']
         out['config']['workload'] += (f' -- EMULATION of rank {emulate[0]} of {emulate[1]} on one GPU: value = this rank\'s own '
@@ -407,7 +423,7 @@ def main():
         out['totals'] = m['totals']
 
     # ---- CPU baseline (rank 0, N=1 only): the reference's numpy statements on one time step
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out['cpu_baseline'] = cpu_baseline(m['dg'], m['u'], m['v'], nz, ny, nx, m['polys'], args)
         # the CPU leg integrates time step 0 across the README transect with the oracle's own weights: the same number as the
         # GPU's row, from an independent implementation end to end (geometry, vertical integral, weights, reduction)
@@ -418,8 +434,9 @@ def main():
                   f'{m["accuracy"]["singular_transect_t0"]!r}', file=sys.stderr, flush=True)
             raise SystemExit(5)
 
-    # ---- float32 inputs (real NEMO files are float32: SURVEY 2 row 13): same workload, same checks, short record
-    if world == 1 and args.dtype == 'f64' and not args.no_f32:
+    # ---- float32 inputs (real NEMO files are float32: SURVEY 2 row 13): same workload, short record.
+    # It and the C3 record below also run for --dump-outputs alone, whose arrays are the same with or without --full.
+    if world == 1 and args.dtype == 'f64' and not args.no_f32 and (args.full or args.dump_outputs):
         import gc
         for k in ('dg', 'u', 'v'):
             m.pop(k, None)
@@ -431,17 +448,18 @@ def main():
         out['f32'] = {'value': m32['value'], 'unit': 'integrals/s', 'ms_per_step': m32['ms_per_step'], 'dtype': 'f32',
                       'roofline': {k: r[k] for k in ('achieved', 'peak', 'unit', 'frac', 'traffic', 'traffic_source',
                                                     'kernel', 'avg_launch_ms', 'launches', 'avg_ms_by_kernel',
-                                                    'algorithmic_bytes_per_unit', 'wall_frac')},
-                      'accuracy': m32['accuracy']}
+                                                    'algorithmic_bytes_per_unit', 'wall_frac')}}
+        if args.full:
+            out['f32']['accuracy'] = m32['accuracy']
     # ---- file ingest (N=1): what a file-backed pass adds in front of the kernels above -- one launch of the device DEFLATE
     # decoder on 256 copies of a NEMO-like level (field.py:149's lazy NetCDF read: HDF5 shuffle + deflate)
-    if world == 1 and not args.no_ingest:
+    if world == 1 and args.full and not args.no_ingest:
         try:
             out['ingest'] = ingest_record()
         except Exception as e:      # never costs the headline line
             out['ingest'] = {'error': f'{type(e).__name__}: {e}'}
     # ---- BASELINE config C3 (ORCA025-like, one time step) beside the headline: the mid-size grid most real files have
-    if world == 1 and not args.no_c3 and not emulate:
+    if world == 1 and not args.no_c3 and not emulate and (args.full or args.dump_outputs):
         try:
             out['c3'] = c3_record(args.steps, args.warmup, dumped if args.dump_outputs else None)
         except Exception as e:

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 R=$1
 mkdir -p gpurun_out/$R
-COMMON="--steps 3 --warmup 1 --no-cpu --dump-totals"
+COMMON="--steps 3 --warmup 1 --full --no-cpu --dump-totals"
 timeout -k 10 400 python bench.py --gpus 1 $COMMON --no-f32 --no-ingest --no-c3 > gpurun_out/$R/rehearsal_n1.json 2> gpurun_out/$R/rehearsal_n1.err || { tail -30 gpurun_out/$R/rehearsal_n1.err; exit 1; }
 for N in 5; do
   NF_FORCE_DEVICE=0 NF_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus $N $COMMON > gpurun_out/$R/rehearsal_n$N.out 2> gpurun_out/$R/rehearsal_n$N.err || { tail -40 gpurun_out/$R/rehearsal_n$N.err; exit 1; }
@@ -30,7 +30,7 @@ for N in (5,):
     assert rel <= 1e-13 and d['accuracy']['max_abs_err_vs_fluxexact'] <= 1e-11 and got == want and d['n_gpus'] == N
     d.pop('totals')
     head = {'what_this_is': f'{N} ranks SHARING ONE GPU over gloo (NF_FORCE_DEVICE=0 NF_DIST_BACKEND=gloo python bench.py --gpus {N} '
-                            '--steps 3 --warmup 1 --no-cpu --dump-totals): a rehearsal of the launcher, the slab bookkeeping, the reduce '
+                            '--steps 3 --warmup 1 --full --no-cpu --dump-totals): a rehearsal of the launcher, the slab bookkeeping, the reduce '
                             'and the accuracy block at the headline size -- NOT a scaling measurement, the value is meaningless as a rate',
             'totals_max_rel_diff_vs_n1': rel, 'n1_ms_per_step': one['ms_per_step']}
     with open('gpurun_out/$R/rehearsal%d.json' % N, 'w') as f:

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 R=$1
 mkdir -p gpurun_out/$R
-ARGS="--nx 144 --ny 72 --nz 9 --nt 5 --batch 6 --steps 2 --warmup 1 --no-cpu --no-f32 --no-ingest --no-c3 --dump-totals"
+ARGS="--nx 144 --ny 72 --nz 9 --nt 5 --batch 6 --steps 2 --warmup 1 --full --no-cpu --no-f32 --no-ingest --no-c3 --dump-totals"
 python bench.py --gpus 1 $ARGS > gpurun_out/$R/n1.json 2> gpurun_out/$R/n1.err
 for N in 4 6; do
   NF_FORCE_DEVICE=0 NF_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500+N)) bench.py --gpus $N $ARGS > gpurun_out/$R/n$N.json 2> gpurun_out/$R/n$N.err || { tail -30 gpurun_out/$R/n$N.err; exit 1; }

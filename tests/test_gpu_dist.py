@@ -83,11 +83,11 @@ def test_two_ranks_one_gpu_gloo(tmp_path):
 
 
 def test_bench_contract_small_workload():
-    """bench.py prints exactly one JSON line with the contract's keys (tiny workload, CPU leg included)."""
+    """bench.py --full prints exactly one JSON line with the contract's keys (tiny workload, CPU leg included)."""
     import json
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--nx', '144',
-                          '--ny', '72', '--nz', '9', '--nt', '3', '--batch', '6'], capture_output=True, text=True,
+                          '--ny', '72', '--nz', '9', '--nt', '3', '--batch', '6', '--full'], capture_output=True, text=True,
                          timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -113,6 +113,37 @@ def test_bench_contract_small_workload():
     assert f['accuracy']['max_abs_err_vs_fluxexact'] <= 1e-5 * max(1.0, f['accuracy']['max_abs_exact'])
     g = d['ingest']                                                   # file-ingest sub-record: one launch of the device decoder
     assert g.get('bit_identical') is True and g['MB_per_s_per_stream'] > 10 and g['inflate_unshuffle_place_ms'] > 0, g
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """A plain bench.py line carries the headline and the roofline of its own timed steps, none of what --full adds; with
+    --dump-outputs a plain run writes the same arrays as a --full run (the float32 and C3 workloads run for it)."""
+    import json
+    import subprocess
+    small = ['--steps', '2', '--warmup', '1', '--nx', '144', '--ny', '72', '--nz', '9', '--nt', '3', '--batch', '6']
+    lines = {}
+    for name, extra in (('plain', []), ('plain_dump', ['--dump-outputs', str(tmp_path / 'plain')]),
+                        ('full_dump', ['--full', '--no-cpu', '--no-ingest', '--dump-outputs', str(tmp_path / 'full')])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + small + extra, capture_output=True,
+                             text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(got) == 1
+        lines[name] = json.loads(got[0])
+    d = lines['plain']
+    assert d['metric'] == 'edge-flux integrals/sec' and d['unit'] == 'integrals/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f64' and d['steps'] == 2 and d['warmup'] == 1 and d['roofline']['launches'] >= 2
+    assert abs(d['value'] - 144 * 72 * 9 * 3 * 2 / (d['ms_per_step'] * 2e-3)) <= 1e-6 * d['value']
+    for k in ('accuracy', 'cpu_baseline', 'f32', 'ingest', 'c3', 'dumped_outputs'):
+        assert k not in d, k
+    assert 'weights_build_ms' not in d['config'] and 'accuracy' in lines['full_dump']
+    assert lines['plain_dump']['dumped_outputs'] == lines['full_dump']['dumped_outputs']
+    names = sorted(f.name for f in (tmp_path / 'full').iterdir())
+    assert names == sorted(f.name for f in (tmp_path / 'plain').iterdir()) and 'f32_transect_totals.npy' in names
+    assert 'c3_f64_segment_fluxes.npy' in names
+    for f in names:
+        a, b = numpy.load(tmp_path / 'plain' / f), numpy.load(tmp_path / 'full' / f)
+        assert a.shape == b.shape and numpy.allclose(a, b, rtol=0, atol=1e-13 * max(1.0, float(numpy.abs(b).max()))), f
 
 
 def test_readme_examples_script():
@@ -154,7 +185,7 @@ def _bench_json(extra, nproc=1, launcher='torchrun', env_extra=None, with_stderr
     Returns the parsed JSON line."""
     import json
     import subprocess
-    small = ['--nx', '144', '--ny', '72', '--nz', '9', '--batch', '6', '--steps', '2', '--warmup', '1', '--no-cpu',
+    small = ['--nx', '144', '--ny', '72', '--nz', '9', '--batch', '6', '--steps', '2', '--warmup', '1', '--full', '--no-cpu',
              '--no-f32', '--no-ingest', '--no-c3', '--dump-totals'] + extra
     env = dict(os.environ)
     if nproc == 1:
