@@ -100,10 +100,11 @@ struct nf_field {
     int skip_unsupported = 0;   // nf_field_set_unsupported_cells
     int overlap_warn = 0;       // nf_field_set_overlapping_cells
     DevArray<int> tr_off_dev;
-    DevArray<double> scratch, row;   // scratch: the run sums of two steps (a pair of the per-step pass)
+    DevArray<double> scratch;   // the run sums of two steps (a pair of the per-step pass)
     // depth-resolved rows (nf_field_compute_profile): the run sums of one chunk of levels (ws.nrec * kProfileChunk, allocated
-    // on first use, dropped with the weights) and the (nz, row_length) block of the synchronous call
-    DevArray<double> prof_scratch, prof;
+    // on first use, dropped with the weights)
+    DevArray<double> prof_scratch;
+    DevArray<double> row;   // the result of a synchronous call (field_sync): a row, or the (nz, row_length) block of a profile
     // tracer at T-points (nf_field_set_tracer*): same (nt, nz, ny, nx) and dtype as uo / vo; none of its setters changes
     // `version`, and nothing of it enters a captured pass
     const void *tau = nullptr;
@@ -114,7 +115,6 @@ struct nf_field {
     double tau_ref = 0.0;
     int tau_wrap = 1;
     DevArray<char> stage_tau;   // host-resident tracer: the owned levels of one step
-    DevArray<double> tr_row;    // the row of the synchronous tracer call
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -193,9 +193,11 @@ static int field_reserve_events(nf_field *f, size_t n)
     return NF_OK;
 }
 
-// one flux launch (and, in the default step, the expansion behind it) bracketed by events on the field's stream
-static int field_timed_flux(nf_field *f, FluxArgs &a)
+// one flux launch (and, in the default step, the expansion behind it) on the field's stream; with timing on, bracketed by
+// events
+static int field_launch_flux(nf_field *f, FluxArgs &a)
 {
+    if (!f->timing) return launch_flux(a, f->stream);
     if (f->ev_used >= kMaxTimedLaunches) {   // nobody reads the timing: keep computing, stop recording
         ++f->ev_dropped;
         return launch_flux(a, f->stream);
@@ -237,6 +239,117 @@ static int field_ensure_derived(nf_field *f)
 
 static int field_row_length(const nf_field *f) { return f->ws.nseg + (int)f->polylines.size(); }
 
+// the state every per-step computation needs; `what` prefixes the message ("compute", "compute_profile", ...)
+static int field_ready(const nf_field *f, const char *what, bool weights)
+{
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
+               std::string(what) + ": set_bounds, set_thickness and set_uv first");
+    NF_REQUIRE(!weights || f->weights_built, NF_ERR_STATE, std::string(what) + ": build_weights first");
+    return NF_OK;
+}
+
+// the end of the slabs [s_begin, s_end) of the nt * nz that this rank owns (set_slab_range; s_end < 0: up to the last one)
+static long field_slab_end(const nf_field *f)
+{
+    const long total = f->nt * f->nz;
+    return f->s_end < 0 ? total : std::min(f->s_end, total);
+}
+
+// the levels [z0, z1) of step t that this rank owns; z0 == z1 (inside [0, nz]) when it owns none of them
+struct Levels {
+    int z0 = 0, z1 = 0;
+};
+static Levels field_levels(const nf_field *f, long t)
+{
+    const long s_end = field_slab_end(f);
+    long lo = t * f->nz, hi = (t + 1) * f->nz;
+    if (lo < f->s_begin) lo = std::min(f->s_begin, hi);
+    if (hi > s_end) hi = std::max(s_end, lo);
+    return {(int)(lo - t * f->nz), (int)(hi - t * f->nz)};
+}
+
+// the steps of a pass with an owned slab, [ta, tb), and the whole steps [wa, wb) among them: the ones a pair may take (a
+// partial first or last step is reduced on its own).  All zero when the rank owns nothing.
+struct PassSteps {
+    long ta = 0, tb = 0, wa = 0, wb = 0;
+};
+static PassSteps field_pass_steps(const nf_field *f)
+{
+    const long s_end = field_slab_end(f), s_begin = std::min(f->s_begin, s_end);
+    PassSteps p;
+    if (s_end <= s_begin) return p;
+    p.ta = s_begin / f->nz;            // first step with an owned slab
+    p.tb = (s_end - 1) / f->nz + 1;    // one past the last
+    p.wa = s_begin > p.ta * f->nz ? p.ta + 1 : p.ta;
+    p.wb = std::max(p.wa, s_end < p.tb * f->nz ? p.tb - 1 : p.tb);
+    return p;
+}
+
+// Step t of a (nt, nz, ncell) array of the field dtype as the kernels read it: a device-resident array in place, a
+// host-resident one staged into `buf` -- the owned levels only, at their place in one step (PCIe-inclusive path)
+static int field_stage(nf_field *f, const void *src, int on_device, long t, Levels lv, DevArray<char> *buf, const void **out)
+{
+    const size_t es = elem_size(f->uv_dtype), step_bytes = (size_t)f->nz * f->ncell * es;
+    const char *base = (const char *)src + (size_t)t * step_bytes;
+    if (on_device) {
+        *out = base;
+        return NF_OK;
+    }
+    NF_TRY(buf->reserve(step_bytes));
+    const size_t off = (size_t)lv.z0 * f->ncell * es, len = (size_t)(lv.z1 - lv.z0) * f->ncell * es;
+    NF_HIP(hipMemcpyAsync(buf->get() + off, base + off, len, hipMemcpyHostToDevice, f->stream));
+    *out = buf->get();
+    return NF_OK;
+}
+
+// what the per-step kernels read of step t: uo / vo (staged when host-resident), the grid and the levels lv
+static int field_step_input(nf_field *f, long t, Levels lv, StepInput *in)
+{
+    NF_TRY(field_stage(f, f->u, f->uv_on_device, t, lv, &f->stage_u, &in->u));
+    NF_TRY(field_stage(f, f->v, f->uv_on_device, t, lv, &f->stage_v, &in->v));
+    in->dtype = f->uv_dtype;
+    in->ncell = f->ncell;
+    in->ny = f->ny;
+    in->nx = f->nx;
+    in->z0 = lv.z0;
+    in->z1 = lv.z1;
+    in->thickness = f->thick.get();
+    in->arcE = f->geo.arcE.get();
+    in->arcN = f->geo.arcN.get();
+    in->fill = f->fill;
+    in->fill2 = f->fill2;
+    in->scale = kEarthRadiusSv / 1.e6;   // field.py:226
+    in->sverdrup = f->sverdrup;
+    return NF_OK;
+}
+
+// K1's arguments for a step: FluxArgs begins with the fields of StepInput, in the same order; its outputs are the caller's
+static FluxArgs flux_args(const StepInput &in)
+{
+    return FluxArgs{in.u, in.v, in.dtype, in.ncell, in.ny, in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, in.fill,
+                    in.fill2, in.scale, in.sverdrup};
+}
+
+// K3 over planes of this field's grid, read through their two signed members, with the field's weights and transects
+static int field_integral(nf_field *f, const double *planes, double *scratch, double *rows, int nsteps = 1,
+                          long data_stride = 0, long row_stride = 0)
+{
+    return launch_integral(f->ws, planes, f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(), scratch, rows,
+                           f->stream, nsteps, data_stride, row_stride);
+}
+
+// a synchronous entry point: `step` writes n doubles into the field's own device buffer, which are copied to `host` (nullptr:
+// not copied); the stream is synchronized either way
+template <typename Step>
+static int field_sync(nf_field *f, size_t n, double *host, Step step)
+{
+    NF_TRY(f->row.reserve(n > 0 ? n : 1));
+    NF_TRY(step(f->row.get()));
+    if (host && n > 0) NF_HIP(hipMemcpyAsync(host, f->row.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
+    NF_HIP(hipStreamSynchronize(f->stream));
+    return NF_OK;
+}
+
 // how field_step_async runs a step of a per-step pass
 struct StepForm {
     // a step of the pass that another step follows: its planes are overwritten before anybody but K3 can read them, so
@@ -247,63 +360,21 @@ struct StepForm {
     bool to_uv2 = false;
 };
 
-// the base of step t's (nz, ncell) fields on the device: resident fields in place, host-resident ones staged, owned levels
-// [z0, z1) only (PCIe-inclusive path)
-static int field_step_input(nf_field *f, long t, int z0, int z1, const void **ut, const void **vt)
-{
-    const size_t es = elem_size(f->uv_dtype);
-    const size_t step_bytes = (size_t)f->nz * f->ncell * es;
-    if (f->uv_on_device) {
-        *ut = (const char *)f->u + (size_t)t * step_bytes;
-        *vt = (const char *)f->v + (size_t)t * step_bytes;
-        return NF_OK;
-    }
-    NF_TRY(f->stage_u.reserve(step_bytes));
-    NF_TRY(f->stage_v.reserve(step_bytes));
-    const size_t off = (size_t)z0 * f->ncell * es, len = (size_t)(z1 - z0) * f->ncell * es;
-    NF_HIP(hipMemcpyAsync(f->stage_u.get() + off, (const char *)f->u + (size_t)t * step_bytes + off, len,
-                          hipMemcpyHostToDevice, f->stream));
-    NF_HIP(hipMemcpyAsync(f->stage_v.get() + off, (const char *)f->v + (size_t)t * step_bytes + off, len,
-                          hipMemcpyHostToDevice, f->stream));
-    *ut = f->stage_u.get();
-    *vt = f->stage_v.get();
-    return NF_OK;
-}
-
 // one time step on the field's stream; row_dev receives [segments | transects]
 static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form = {})
 {
-    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
-               "compute: set_bounds, set_thickness and set_uv first");
-    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute: time index out of range");
-    const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
-    long lo = t * f->nz, hi = (t + 1) * f->nz;
-    if (lo < f->s_begin) lo = f->s_begin;
-    if (hi > s_end) hi = s_end;
     const int rowlen = field_row_length(f);
-    if (hi <= lo) {  // this rank owns no slab of step t: contributes zeros
+    const bool reduce = row_dev && rowlen > 0 && !form.to_uv2;
+    NF_TRY(field_ready(f, "compute", reduce));
+    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute: time index out of range");
+    const Levels lv = field_levels(f, t);
+    if (lv.z1 <= lv.z0) {  // this rank owns no slab of step t: contributes zeros
         if (row_dev && rowlen > 0) NF_HIP(hipMemsetAsync(row_dev, 0, sizeof(double) * rowlen, f->stream));
         return NF_OK;
     }
-    const int z0 = (int)(lo - t * f->nz), z1 = (int)(hi - t * f->nz);
-    const void *ut, *vt;
-    NF_TRY(field_step_input(f, t, z0, z1, &ut, &vt));
-    FluxArgs a{};
-    a.u = ut;
-    a.v = vt;
-    a.dtype = f->uv_dtype;
-    a.ncell = f->ncell;
-    a.ny = f->ny;
-    a.nx = f->nx;
-    a.z0 = z0;
-    a.z1 = z1;
-    a.thickness = f->thick.get();
-    a.arcE = f->geo.arcE.get();
-    a.arcN = f->geo.arcN.get();
-    a.fill = f->fill;
-    a.fill2 = f->fill2;
-    a.scale = kEarthRadiusSv / 1.e6;  // field.py:226
-    a.sverdrup = f->sverdrup;
+    StepInput in;
+    NF_TRY(field_step_input(f, t, lv, &in));
+    FluxArgs a = flux_args(in);
     a.iV = f->geo.iV.get();
     // uv2 holds planes 1 and 2 only: the signed-only kernel stores to iV + ncell and iV + 2 * ncell, nothing below
     if (form.to_uv2) a.iV = f->geo.uv2.get() - f->ncell;
@@ -316,19 +387,13 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     // planes are written on demand (read_step / device_ptr), exactly as in the compact mode.  0.116 ms per such launch at
     // the C4 size; the rows are bit-identical (test_slab_sharding_sums_to_full).  nf_tuning_set("partial_step_planes", 1) keeps the
     // six-plane epilogue on partial steps (the before / after measurement of profiles/r04_rank_emulation.txt).
-    const bool partial = (z0 > 0 || z1 < (int)f->nz) && !g_partial_full;
+    const bool partial = (lv.z0 > 0 || lv.z1 < (int)f->nz) && !g_partial_full;
     a.signed_only = (f->compact || partial || form.inner) && flux_supports_signed_only(a);
     NF_REQUIRE(!form.to_uv2 || a.signed_only, NF_ERR_STATE, "compute: a step into the second planes must be signed-only");
     if (!form.to_uv2) f->derived_stale = a.signed_only != 0;
-    if (f->timing) {
-        NF_TRY(field_timed_flux(f, a));
-    } else {
-        NF_TRY(launch_flux(a, f->stream));
-    }
-    if (row_dev && rowlen > 0 && !form.to_uv2) {
-        NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute: build_weights first");
-        NF_TRY(launch_integral(f->ws, f->geo.iV.get(), f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(),
-                               f->scratch.get(), row_dev, f->stream));
+    NF_TRY(field_launch_flux(f, a));
+    if (reduce) {
+        NF_TRY(field_integral(f, f->geo.iV.get(), f->scratch.get(), row_dev));
         NF_TRY(field_timed_k3_end(f));
     }
     return NF_OK;
@@ -336,42 +401,23 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
 
 // Depth-resolved rows of step t on the field's stream: prof_dev (nz, row_length), row z = the flux carried by level z alone.
 // Reads the raw fields and the records; leaves the resident planes, |.| arrays, running max, version and a captured pass
-// alone.  Levels this rank does not own get zeros.
+// alone.  Levels this rank does not own get zeros.  The caller has checked field_ready (with the weights).
 static int field_profile_async(nf_field *f, long t, double *prof_dev)
 {
-    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
-               "compute_profile: set_bounds, set_thickness and set_uv first");
-    NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute_profile: build_weights first");
     NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_profile: time index out of range");
     const int rowlen = field_row_length(f);
     if (rowlen == 0) return NF_OK;
-    const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
-    long lo = t * f->nz, hi = (t + 1) * f->nz;
-    if (lo < f->s_begin) lo = f->s_begin;
-    if (hi > s_end) hi = s_end;
-    if (hi < lo) hi = lo;
-    const int z0 = (int)(lo - t * f->nz), z1 = (int)(hi - t * f->nz);
+    const Levels lv = field_levels(f, t);
     // levels outside [z0, z1): exact zeros, so that the ranks' profiles add up to the full one
-    if (z0 > 0) NF_HIP(hipMemsetAsync(prof_dev, 0, sizeof(double) * rowlen * (size_t)z0, f->stream));
-    if (z1 < f->nz)
-        NF_HIP(hipMemsetAsync(prof_dev + (size_t)z1 * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nz - z1), f->stream));
-    if (z1 <= z0) return NF_OK;
+    if (lv.z0 > 0) NF_HIP(hipMemsetAsync(prof_dev, 0, sizeof(double) * rowlen * (size_t)lv.z0, f->stream));
+    if (lv.z1 < f->nz)
+        NF_HIP(hipMemsetAsync(prof_dev + (size_t)lv.z1 * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nz - lv.z1),
+                              f->stream));
+    if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->prof_scratch.reserve((size_t)f->ws.nrec * kProfileChunk));
     ProfileArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
     a.ws = &f->ws;
-    NF_TRY(field_step_input(f, t, z0, z1, &a.u, &a.v));
-    a.dtype = f->uv_dtype;
-    a.ncell = f->ncell;
-    a.nx = f->nx;
-    a.z0 = z0;
-    a.z1 = z1;
-    a.thickness = f->thick.get();
-    a.arcE = f->geo.arcE.get();
-    a.arcN = f->geo.arcN.get();
-    a.fill = f->fill;
-    a.fill2 = f->fill2;
-    a.scale = kEarthRadiusSv / 1.e6;   // field.py:226
-    a.sverdrup = f->sverdrup;
     a.tr_offsets_dev = f->tr_off_dev.get();
     a.ntransect = (int)f->polylines.size();
     a.row_length = rowlen;
@@ -386,59 +432,29 @@ static int field_profile_async(nf_field *f, long t, double *prof_dev)
 // and the records; the resident planes, |.| arrays, running max, version and a captured pass stay as they are.
 static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
 {
-    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
-               "compute_tracer: set_bounds, set_thickness and set_uv first");
-    NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute_tracer: build_weights first");
+    NF_TRY(field_ready(f, "compute_tracer", true));
     NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_tracer: time index out of range");
     NF_REQUIRE(f->tau_dtype == f->uv_dtype, NF_ERR_ARG, "compute_tracer: the tracer's dtype differs from the dtype of uo/vo");
     NF_REQUIRE(f->tau_nt == f->nt, NF_ERR_ARG, "compute_tracer: the tracer's nt differs from the nt of uo/vo");
     const int rowlen = field_row_length(f);
     if (rowlen == 0) return NF_OK;
-    const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
-    long lo = t * f->nz, hi = (t + 1) * f->nz;
-    if (lo < f->s_begin) lo = f->s_begin;
-    if (hi > s_end) hi = s_end;
-    if (hi <= lo) {   // this rank owns no slab of step t: contributes zeros
+    const Levels lv = field_levels(f, t);
+    if (lv.z1 <= lv.z0) {   // this rank owns no slab of step t: contributes zeros
         NF_HIP(hipMemsetAsync(row_dev, 0, sizeof(double) * rowlen, f->stream));
         return NF_OK;
     }
-    const int z0 = (int)(lo - t * f->nz), z1 = (int)(hi - t * f->nz);
     TracerArgs a;
-    NF_TRY(field_step_input(f, t, z0, z1, &a.u, &a.v));
-    const size_t es = elem_size(f->uv_dtype);
-    const size_t step_bytes = (size_t)f->nz * f->ncell * es;
-    if (f->tau_on_device) {
-        a.tau = (const char *)f->tau + (size_t)t * step_bytes;
-    } else {
-        NF_TRY(f->stage_tau.reserve(step_bytes));
-        const size_t off = (size_t)z0 * f->ncell * es, len = (size_t)(z1 - z0) * f->ncell * es;
-        NF_HIP(hipMemcpyAsync(f->stage_tau.get() + off, (const char *)f->tau + (size_t)t * step_bytes + off, len,
-                              hipMemcpyHostToDevice, f->stream));
-        a.tau = f->stage_tau.get();
-    }
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_stage(f, f->tau, f->tau_on_device, t, lv, &f->stage_tau, &a.tau));
     NF_TRY(f->geo.tr_planes.reserve((size_t)f->ncell * 2));
-    a.dtype = f->uv_dtype;
-    a.ncell = f->ncell;
-    a.ny = f->ny;
-    a.nx = f->nx;
-    a.z0 = z0;
-    a.z1 = z1;
-    a.thickness = f->thick.get();
-    a.arcE = f->geo.arcE.get();
-    a.arcN = f->geo.arcN.get();
-    a.fill = f->fill;
-    a.fill2 = f->fill2;
     a.tfill = f->tau_fill;
     a.tfill2 = f->tau_fill2;
     a.ref = f->tau_ref;
     a.wrap_x = f->tau_wrap;
-    a.scale = kEarthRadiusSv / 1.e6;   // field.py:226
-    a.sverdrup = f->sverdrup;
     a.planes = f->geo.tr_planes.get();
     NF_TRY(launch_tracer_flux(a, f->stream));
     // K3 reads the two signed members of [4][ncell] planes at +ncell and +2 ncell: the tracer planes sit at +ncell
-    return launch_integral(f->ws, f->geo.tr_planes.get() - f->ncell, f->ncell, 2, f->nx, f->tr_off_dev.get(),
-                           (int)f->polylines.size(), f->scratch.get(), row_dev, f->stream);
+    return field_integral(f, f->geo.tr_planes.get() - f->ncell, f->scratch.get(), row_dev);
 }
 
 // steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
@@ -489,13 +505,13 @@ static bool field_pass_pairs(const nf_field *f)
 }
 
 // device memory a per-step pass may need, allocated before the pass is launched or captured: the second signed planes of
-// a pair.  Nothing is allocated for a pass that takes no pairs (knob off, a single owned step, the edge-entry form of K3).
+// a pair.  Nothing is allocated for a pass that takes no pairs (knob off, fewer than two whole steps owned, the edge-entry
+// form of K3).
 static int field_prepare_pass(nf_field *f)
 {
-    if (!g_k3_pairs || integral_uses_edges() || f->geo.uv2.get() || !f->geo.iV.get() || f->nz <= 0) return NF_OK;
-    const long total = f->nt * f->nz;
-    const long s_end = f->s_end < 0 ? total : std::min(f->s_end, total);
-    if (s_end - std::min(f->s_begin, s_end) < 2 * f->nz) return NF_OK;   // fewer than two whole steps can be owned
+    if (!g_k3_pairs || integral_uses_edges() || f->geo.uv2.get() || !f->geo.iV.get()) return NF_OK;
+    const PassSteps p = field_pass_steps(f);
+    if (p.wb - p.wa < 2) return NF_OK;
     NF_TRY(f->geo.uv2.alloc((size_t)f->ncell * 2));
     return NF_OK;
 }
@@ -506,28 +522,21 @@ static int field_prepare_pass(nf_field *f)
 static int field_all_steps_direct(nf_field *f, double *rows_dev)
 {
     const int rowlen = field_row_length(f);
-    const long total = f->nt * f->nz;
-    const long s_end = f->s_end < 0 ? total : std::min(f->s_end, total);
-    const long s_begin = std::min(f->s_begin, s_end);
-    const long ta = s_end > s_begin ? s_begin / f->nz : 0;                    // first step with an owned slab
-    const long tb = s_end > s_begin ? (s_end - 1) / f->nz + 1 : 0;            // one past the last
+    const PassSteps p = field_pass_steps(f);
     if (rowlen > 0) {
-        if (ta > 0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)ta, f->stream));
-        if (tb < f->nt)
-            NF_HIP(hipMemsetAsync(rows_dev + (size_t)tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nt - tb),
+        if (p.ta > 0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)p.ta, f->stream));
+        if (p.tb < f->nt)
+            NF_HIP(hipMemsetAsync(rows_dev + (size_t)p.tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nt - p.tb),
                                   f->stream));
     }
-    // whole steps [wa, wb): the ones a pair may take (a partial first or last step is reduced on its own)
-    const long wa = (ta < tb && s_begin > ta * f->nz) ? ta + 1 : ta;
-    const long wb = std::max(wa, (ta < tb && s_end < tb * f->nz) ? tb - 1 : tb);
     const bool pairs = field_pass_pairs(f) && rowlen > 0;
     // an odd number of whole steps leaves one of them single: the first, so that the last pair ends on the last whole step
     // and every pair's second step lands in the resident planes
-    const long pa = pairs ? wa + (wb - wa) % 2 : wb;
-    for (long t = ta; t < tb;) {
-        const bool last = t + 1 == tb;
-        if (t >= pa && t + 1 < wb) {
-            NF_TRY(field_pair_async(f, t, rows_dev, t + 2 == tb));
+    const long pa = pairs ? p.wa + (p.wb - p.wa) % 2 : p.wb;
+    for (long t = p.ta; t < p.tb;) {
+        const bool last = t + 1 == p.tb;
+        if (t >= pa && t + 1 < p.wb) {
+            NF_TRY(field_pair_async(f, t, rows_dev, t + 2 == p.tb));
             t += 2;
         } else {
             StepForm form;
@@ -556,34 +565,17 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
     if (g.batch_version != f->version) {  // scratch follows the weight set, z ranges follow the slab ownership
         NF_TRY(g.scratchb.alloc((size_t)std::max(f->ws.nrec, f->ws.nent) * f->nt));
         std::vector<int> zr((size_t)2 * f->nt);
-        const long s_end = f->s_end < 0 ? f->nt * f->nz : f->s_end;
         for (long t = 0; t < f->nt; ++t) {
-            long lo = t * f->nz, hi = (t + 1) * f->nz;
-            if (lo < f->s_begin) lo = f->s_begin;
-            if (hi > s_end) hi = s_end;
-            if (hi < lo) hi = lo;
-            zr[2 * t] = (int)(lo - t * f->nz);
-            zr[2 * t + 1] = (int)(hi - t * f->nz);
+            const Levels lv = field_levels(f, t);
+            zr[2 * t] = lv.z0;
+            zr[2 * t + 1] = lv.z1;
         }
         NF_HIP(hipMemcpy(g.zr.get(), zr.data(), sizeof(int) * zr.size(), hipMemcpyHostToDevice));
         g.batch_version = f->version;
     }
-    FluxArgs a{};
-    a.u = f->u;
-    a.v = f->v;
-    a.dtype = f->uv_dtype;
-    a.ncell = f->ncell;
-    a.ny = f->ny;
-    a.nx = f->nx;
-    a.z0 = 0;
-    a.z1 = (int)f->nz;
-    a.thickness = f->thick.get();
-    a.arcE = g.arcE.get();
-    a.arcN = g.arcN.get();
-    a.fill = f->fill;
-    a.fill2 = f->fill2;
-    a.scale = kEarthRadiusSv / 1.e6;
-    a.sverdrup = f->sverdrup;
+    StepInput in;   // resident fields: step 0 is the base of all of them
+    NF_TRY(field_step_input(f, 0, {0, (int)f->nz}, &in));
+    FluxArgs a = flux_args(in);
     a.iV = g.iVb.get();
     a.absU = g.absb.get();
     a.absV = g.absb.get() + f->ncell;
@@ -591,14 +583,9 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
     a.batch.nsteps = (int)f->nt;
     a.batch.in_stride = f->nz * f->ncell;
     a.batch.zr = g.zr.get();
-    if (f->timing) {
-        NF_TRY(field_timed_flux(f, a));
-    } else {
-        NF_TRY(launch_flux(a, f->stream));
-    }
+    NF_TRY(field_launch_flux(f, a));
     if (rowlen > 0) {
-        NF_TRY(launch_integral(f->ws, g.iVb.get(), f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(),
-                               g.scratchb.get(), rows_dev, f->stream, (int)f->nt, (long)(4 * n), rowlen));
+        NF_TRY(field_integral(f, g.iVb.get(), g.scratchb.get(), rows_dev, (int)f->nt, (long)(4 * n), rowlen));
         NF_TRY(field_timed_k3_end(f));
     }
     // the resident single-step arrays keep their meaning: they hold the LAST step (what read_step returns)
@@ -843,7 +830,6 @@ try {
     if (integral_uses_edges()) NF_TRY(fold_weights(&f->ws, f->ncell, f->nx, f->stream));
     NF_TRY(f->tr_off_dev.alloc(f->tr_off.size()));
     NF_TRY(f->scratch.alloc((size_t)2 * std::max(f->ws.nrec, f->ws.nent)));
-    NF_TRY(f->row.alloc((size_t)field_row_length(f)));
     NF_HIP(hipMemcpy(f->tr_off_dev.get(), f->tr_off.data(), sizeof(int) * f->tr_off.size(), hipMemcpyHostToDevice));
     f->weights_built = true;
     ++f->version;
@@ -935,12 +921,8 @@ try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_compute_flux: null field");
     NF_NEED_DEVICE();
     nf_field *f = *self;
-    const int rowlen = field_row_length(f);
-    NF_TRY(field_step_async(f, tIndex, (f->weights_built && rowlen > 0) ? f->row.get() : nullptr));
-    if (row_host && rowlen > 0 && f->weights_built)
-        NF_HIP(hipMemcpyAsync(row_host, f->row.get(), sizeof(double) * rowlen, hipMemcpyDeviceToHost, f->stream));
-    NF_HIP(hipStreamSynchronize(f->stream));
-    return NF_OK;
+    const size_t n = f->weights_built ? field_row_length(f) : 0;   // no weights: the step alone, no row
+    return field_sync(f, n, row_host, [&](double *row) { return field_step_async(f, tIndex, n > 0 ? row : nullptr); });
 }
 NF_API_CATCH
 
@@ -988,17 +970,11 @@ int nf_field_compute_profile(nf_field **self, long tIndex, double *prof_host)
 try {
     NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_profile: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
-               "compute_profile: set_bounds, set_thickness and set_uv first");
-    NF_REQUIRE(f->weights_built, NF_ERR_STATE, "compute_profile: build_weights first");
+    NF_TRY(field_ready(f, "compute_profile", true));
     NF_NEED_DEVICE();
     const size_t n = (size_t)f->nz * field_row_length(f);
     if (n == 0) return NF_OK;
-    NF_TRY(f->prof.reserve(n));
-    NF_TRY(field_profile_async(f, tIndex, f->prof.get()));
-    NF_HIP(hipMemcpyAsync(prof_host, f->prof.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
-    NF_HIP(hipStreamSynchronize(f->stream));
-    return NF_OK;
+    return field_sync(f, n, prof_host, [&](double *prof) { return field_profile_async(f, tIndex, prof); });
 }
 NF_API_CATCH
 
@@ -1006,8 +982,7 @@ int nf_field_compute_profile_async(nf_field **self, long tIndex, double *prof_de
 try {
     NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_profile_async: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
-               "compute_profile: set_bounds, set_thickness and set_uv first");
+    NF_TRY(field_ready(f, "compute_profile", true));
     NF_NEED_DEVICE();
     return field_profile_async(f, tIndex, prof_dev);
 }
@@ -1066,13 +1041,7 @@ try {
     nf_field *f = *self;
     NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_flux: set_tracer first");
     NF_NEED_DEVICE();
-    const int rowlen = field_row_length(f);
-    NF_TRY(f->tr_row.reserve((size_t)(rowlen > 0 ? rowlen : 1)));
-    NF_TRY(field_tracer_step_async(f, tIndex, f->tr_row.get()));
-    if (row_host && rowlen > 0)
-        NF_HIP(hipMemcpyAsync(row_host, f->tr_row.get(), sizeof(double) * rowlen, hipMemcpyDeviceToHost, f->stream));
-    NF_HIP(hipStreamSynchronize(f->stream));
-    return NF_OK;
+    return field_sync(f, field_row_length(f), row_host, [&](double *row) { return field_tracer_step_async(f, tIndex, row); });
 }
 NF_API_CATCH
 

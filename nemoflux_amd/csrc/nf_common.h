@@ -320,20 +320,26 @@ int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *u
                          const int *tr_offsets_dev, int ntransect, double *scratch, double *row, long row_stride,
                          hipStream_t s);
 
+// What every per-step kernel of a Field reads of one time step (K1's FluxArgs has the same fields, filled from this): the
+// fields, the grid, the levels [z0, z1) and the masking / unit settings of uo / vo.
+struct StepInput {
+    const void *u = nullptr, *v = nullptr;   // base of the time step: (nz, ncell) of the field dtype
+    int dtype = NF_F64;
+    long ncell = 0, ny = 0, nx = 0;
+    int z0 = 0, z1 = 0;
+    const double *thickness = nullptr, *arcE = nullptr, *arcN = nullptr;   // device
+    double fill = __builtin_nan(""), fill2 = __builtin_nan("");   // NaN = none
+    double scale = 1.0;       // 1 or 6371000/1e6
+    int sverdrup = 0;
+};
+
 // Depth-resolved rows (nf_field_compute_profile): the per-level form of the record path of K3, reading the raw fields of
 // one time step.  prof: (nz, row_length) doubles; the kernels write rows [z0, z1) only.  Levels are processed
 // kProfileChunk at a time: scratch holds the run sums of one chunk, ws.nrec * kProfileChunk doubles.
 constexpr int kProfileChunk = 8;
 struct ProfileArgs {
+    StepInput in;
     const WeightSet *ws = nullptr;
-    const void *u = nullptr, *v = nullptr;   // base of the time step: (nz, ncell) of the field dtype
-    int dtype = NF_F64;
-    long ncell = 0, nx = 0;
-    int z0 = 0, z1 = 0;
-    const double *thickness = nullptr, *arcE = nullptr, *arcN = nullptr;   // device
-    double fill = __builtin_nan(""), fill2 = __builtin_nan("");
-    double scale = 1.0;
-    int sverdrup = 0;
     const int *tr_offsets_dev = nullptr;
     int ntransect = 0;
     long row_length = 0;
@@ -347,17 +353,11 @@ int launch_profile(const ProfileArgs &a, hipStream_t s);
 // multiplied by the tracer interpolated to the face, tf = 0.5 (a + b) - ref (DESIGN.md section 4 has the face rule).  Writes
 // the two signed planes [eU_tau | eV_tau] of one time step, nothing else; K3 (planes = 2) reduces them.
 struct TracerArgs {
-    const void *u = nullptr, *v = nullptr, *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
-    int dtype = NF_F64;
-    long ncell = 0, ny = 0, nx = 0;
-    int z0 = 0, z1 = 0;
-    const double *thickness = nullptr, *arcE = nullptr, *arcN = nullptr;   // device
-    double fill = __builtin_nan(""), fill2 = __builtin_nan("");     // uo / vo markers (as in FluxArgs)
+    StepInput in;
+    const void *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
     double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");   // the tracer's own _FillValue / missing_value
     double ref = 0.0;         // reference value subtracted from every face value
     int wrap_x = 1;           // 1: the east face of column nx-1 takes column 0 as its neighbour
-    double scale = 1.0;
-    int sverdrup = 0;
     double *planes = nullptr; // [2][ncell]: eU_tau, eV_tau
 };
 int launch_tracer_flux(const TracerArgs &a, hipStream_t s);

@@ -193,6 +193,24 @@ __global__ __launch_bounds__(kBlock) void k_finalize_tr(const int *__restrict__ 
     if (lane == 0) row[nseg + p] = part;
 }
 
+// stages B and C for nrows rows (blockIdx.y): row r stitches the run sums at runsum + r * nrun over the CSR run_start of
+// ws.nseg segments (seg_start for the records, ent_start for the unique-edge entries) and goes to row + r * row_stride
+static void launch_finalize(const WeightSet &ws, const int *run_start, long nrun, const double *runsum,
+                            const int *tr_offsets_dev, int ntransect, double *row, long row_stride, unsigned nrows,
+                            hipStream_t s)
+{
+    if (ws.nseg > 0) {
+        const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, nrows), dim3(kBlock), 0, s, runsum, run_start, ws.nseg, row, nrun,
+                           row_stride);
+    }
+    if (ntransect > 0) {
+        const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_finalize_tr, dim3(nb, nrows), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
+                           row_stride);
+    }
+}
+
 // "edge_weights" tuning knob.  Default 0: measured in-process on the 65-transect bench batch (tools/ab_pass.py,
 // profiles/r02_ab_pass_edges.txt) the unique-edge form is 0.4 % SLOWER per pass than the records (90 vs 85.5 us per step): a
 // line shares only the edge it crosses with the next cell, so folding leaves 3 entries per record, not 2 -- 48 B of stream
@@ -210,16 +228,7 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
         if (ws.nent > 0)
             hipLaunchKernelGGL(k_gather_edges, dim3((unsigned)((ws.nent + kBlock - 1) / kBlock), ny), dim3(kBlock), 0, s,
                                ws.ent.get(), ws.nent, data, ncell, scratch, data_stride);
-        if (ws.nseg > 0) {
-            const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_finalize_seg, dim3(nb, ny), dim3(kBlock), 0, s, scratch, ws.ent_start.get(), ws.nseg, row,
-                               ws.nent, row_stride);
-        }
-        if (ntransect > 0) {
-            const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_finalize_tr, dim3(nb, ny), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
-                               row_stride);
-        }
+        launch_finalize(ws, ws.ent_start.get(), ws.nent, scratch, tr_offsets_dev, ntransect, row, row_stride, ny, s);
         NF_HIP(hipGetLastError());
         return NF_OK;
     }
@@ -228,16 +237,7 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
                            rec_cells ? rec_cells : ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, data, ncell, planes,
                            (unsigned)(nx > 0 ? nx : 1), scratch, data_stride);
     }
-    if (ws.nseg > 0) {
-        const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, ny), dim3(kBlock), 0, s, scratch, ws.seg_start.get(), ws.nseg, row,
-                           ws.nrec, row_stride);
-    }
-    if (ntransect > 0) {
-        const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_tr, dim3(nb, ny), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
-                           row_stride);
-    }
+    launch_finalize(ws, ws.seg_start.get(), ws.nrec, scratch, tr_offsets_dev, ntransect, row, row_stride, ny, s);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
@@ -250,16 +250,7 @@ int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *u
         hipLaunchKernelGGL(k_gather_segscan_pair, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                            ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, uvA, uvB, ncell, (unsigned)(nx > 0 ? nx : 1),
                            scratch);
-    if (ws.nseg > 0) {
-        const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, 2), dim3(kBlock), 0, s, scratch, ws.seg_start.get(), ws.nseg, row,
-                           ws.nrec, row_stride);
-    }
-    if (ntransect > 0) {
-        const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_tr, dim3(nb, 2), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
-                           row_stride);
-    }
+    launch_finalize(ws, ws.seg_start.get(), ws.nrec, scratch, tr_offsets_dev, ntransect, row, row_stride, 2, s);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
@@ -354,26 +345,19 @@ template <typename T>
 static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 {
     const WeightSet &ws = *a.ws;
-    const T fill = (T)a.fill, fill2 = (T)a.fill2;
+    const StepInput &in = a.in;
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
     const int two = fill2 == fill2 && !(fill2 == fill);   // K1's rule: a second marker that differs from the first
-    for (int zc = a.z0; zc < a.z1; zc += kProfileChunk) {
-        const int nlev = a.z1 - zc < kProfileChunk ? a.z1 - zc : kProfileChunk;
+    for (int zc = in.z0; zc < in.z1; zc += kProfileChunk) {
+        const int nlev = in.z1 - zc < kProfileChunk ? in.z1 - zc : kProfileChunk;
         double *rows = a.prof + (long)zc * a.row_length;
         if (ws.nrec > 0)
             hipLaunchKernelGGL((k_profile_segscan<T, kProfileChunk>), dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)),
-                               dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)a.u,
-                               (const T *)a.v, a.ncell, (unsigned)a.nx, zc, nlev, a.thickness, a.arcE, a.arcN, fill, fill2,
-                               two, a.scale, a.sverdrup, a.scratch);
-        if (ws.nseg > 0) {
-            const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_finalize_seg, dim3(nb, (unsigned)nlev), dim3(kBlock), 0, s, a.scratch, ws.seg_start.get(),
-                               ws.nseg, rows, ws.nrec, a.row_length);
-        }
-        if (a.ntransect > 0) {
-            const unsigned nb = (unsigned)(((long)a.ntransect * kWave + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_finalize_tr, dim3(nb, (unsigned)nlev), dim3(kBlock), 0, s, a.tr_offsets_dev, a.ntransect,
-                               ws.nseg, rows, a.row_length);
-        }
+                               dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u,
+                               (const T *)in.v, in.ncell, (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill,
+                               fill2, two, in.scale, in.sverdrup, a.scratch);
+        launch_finalize(ws, ws.seg_start.get(), ws.nrec, a.scratch, a.tr_offsets_dev, a.ntransect, rows, a.row_length,
+                        (unsigned)nlev, s);
         NF_HIP(hipGetLastError());
     }
     return NF_OK;
@@ -381,13 +365,14 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 
 int launch_profile(const ProfileArgs &a, hipStream_t s)
 {
-    NF_REQUIRE(a.ws && a.ncell > 0 && a.nx > 0 && a.ncell % a.nx == 0 && a.ncell < (1l << 31), NF_ERR_ARG,
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.ws && in.ncell > 0 && in.nx > 0 && in.ncell % in.nx == 0 && in.ncell < (1l << 31), NF_ERR_ARG,
                "profile: bad grid sizes");
-    NF_REQUIRE(a.z0 >= 0 && a.z1 >= a.z0 && a.row_length == a.ws->nseg + a.ntransect, NF_ERR_ARG, "profile: bad arguments");
+    NF_REQUIRE(in.z0 >= 0 && in.z1 >= in.z0 && a.row_length == a.ws->nseg + a.ntransect, NF_ERR_ARG, "profile: bad arguments");
     NF_REQUIRE(a.scratch_len >= (size_t)a.ws->nrec * kProfileChunk, NF_ERR_ARG, "profile: scratch too small");
     if (a.row_length == 0) return NF_OK;
-    if (a.dtype == NF_F64) return launch_profile_t<double>(a, s);
-    if (a.dtype == NF_F32) return launch_profile_t<float>(a, s);
+    if (in.dtype == NF_F64) return launch_profile_t<double>(a, s);
+    if (in.dtype == NF_F32) return launch_profile_t<float>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
 }
 

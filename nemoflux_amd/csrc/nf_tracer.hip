@@ -188,13 +188,14 @@ constexpr int kTracerLevels = 4;
 template <typename T, int VEC, bool NAL>
 int launch_tracer_t(const TracerArgs &a, hipStream_t s)
 {
+    const StepInput &in = a.in;
     const long per_tile = 256l * VEC;
-    const unsigned ntiles = (unsigned)((a.ncell + per_tile - 1) / per_tile);
+    const unsigned ntiles = (unsigned)((in.ncell + per_tile - 1) / per_tile);
     const unsigned grid = xcd_grid(ntiles);
-    hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevels, NAL>), dim3(grid), dim3(256), 0, s, (const T *)a.u,
-                       (const T *)a.v, (const T *)a.tau, a.ncell, (unsigned)a.nx, a.z0, a.z1, a.thickness, a.arcE, a.arcN,
-                       (T)a.fill, (T)a.fill2, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0, a.scale, a.sverdrup,
-                       a.planes, ntiles);
+    hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevels, NAL>), dim3(grid), dim3(256), 0, s, (const T *)in.u,
+                       (const T *)in.v, (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
+                       in.arcN, (T)in.fill, (T)in.fill2, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0, in.scale,
+                       in.sverdrup, a.planes, ntiles);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
@@ -202,21 +203,24 @@ int launch_tracer_t(const TracerArgs &a, hipStream_t s)
 template <typename T, int VEC>
 int launch_tracer_v(const TracerArgs &a, hipStream_t s)
 {
-    const bool al16 = ((uintptr_t)a.u % 16 == 0) && ((uintptr_t)a.v % 16 == 0) && ((uintptr_t)a.tau % 16 == 0);
-    if (al16 && a.ncell % VEC == 0 && a.nx >= VEC)
-        return a.nx % VEC == 0 ? launch_tracer_t<T, VEC, true>(a, s) : launch_tracer_t<T, VEC, false>(a, s);
+    const StepInput &in = a.in;
+    const bool al16 = ((uintptr_t)in.u % 16 == 0) && ((uintptr_t)in.v % 16 == 0) && ((uintptr_t)a.tau % 16 == 0);
+    if (al16 && in.ncell % VEC == 0 && in.nx >= VEC)
+        return in.nx % VEC == 0 ? launch_tracer_t<T, VEC, true>(a, s) : launch_tracer_t<T, VEC, false>(a, s);
     return launch_tracer_t<T, 1, true>(a, s);   // odd sizes / unaligned fields: one cell per lane
 }
 }  // namespace
 
 int launch_tracer_flux(const TracerArgs &a, hipStream_t s)
 {
-    NF_REQUIRE(a.ncell > 0 && a.nx > 0 && a.ncell == a.ny * a.nx && a.ncell < (1l << 31), NF_ERR_ARG,
+    const StepInput &in = a.in;
+    NF_REQUIRE(in.ncell > 0 && in.nx > 0 && in.ncell == in.ny * in.nx && in.ncell < (1l << 31), NF_ERR_ARG,
                "tracer flux: bad grid sizes");
-    NF_REQUIRE(a.z1 > a.z0 && a.z0 >= 0, NF_ERR_ARG, "tracer flux: empty z range");
-    NF_REQUIRE(a.u && a.v && a.tau && a.planes && a.thickness && a.arcE && a.arcN, NF_ERR_ARG, "tracer flux: null argument");
-    if (a.dtype == NF_F64) return launch_tracer_v<double, 2>(a, s);
-    if (a.dtype == NF_F32) return launch_tracer_v<float, 4>(a, s);
+    NF_REQUIRE(in.z1 > in.z0 && in.z0 >= 0, NF_ERR_ARG, "tracer flux: empty z range");
+    NF_REQUIRE(in.u && in.v && a.tau && a.planes && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+               "tracer flux: null argument");
+    if (in.dtype == NF_F64) return launch_tracer_v<double, 2>(a, s);
+    if (in.dtype == NF_F32) return launch_tracer_v<float, 4>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "tracer flux: dtype must be NF_F64 or NF_F32");
 }
 

@@ -477,6 +477,10 @@ class Field(object):
         row = self._compute(self.timeIndex, readback=readback)
         return [float(row[self._nseg + i]) for i in range(len(self.plis))]
 
+    def _split_rows(self, rows):
+        """(transect totals, per-segment sums) of rows laid out [segments | transects] along their last axis."""
+        return rows[..., self._nseg:self._nseg + len(self.plis)], rows[..., :self._nseg]
+
     def getSegmentFluxes(self):
         """Per-target-segment sums of the last computed step, one array per transect."""
         return [numpy.array(self._row[self._tr_off[i]:self._tr_off[i + 1]]) for i in range(len(self.plis))]
@@ -492,12 +496,12 @@ class Field(object):
             rows = numpy.array([self._compute(t, readback=False, prefetch_next=True).copy() for t in range(self.nt)])
             if out is not None:
                 out.copy_(torch.from_numpy(rows))
-            return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+            return self._split_rows(rows)
         if out is None:
             out = torch.empty((self.nt, max(self._rowlen, 1)), dtype=torch.float64, device='cuda')
         check(lib.nf_field_compute_all_async(ctypes.byref(self._h), ctypes.c_void_p(out.data_ptr())))
         rows = out.cpu().numpy()
-        return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+        return self._split_rows(rows)
 
     def computeFluxProfile(self, tIndex, out=None, prefetch_next=None):
         """Depth-resolved fluxes of time step tIndex: (nz, ntransect) totals and (nz, nseg) per-segment sums, row z = the
@@ -515,7 +519,7 @@ class Field(object):
         else:
             rows = numpy.zeros((self.nz, max(self._rowlen, 1)), numpy.float64)
             check(lib.nf_field_compute_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
-        return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+        return self._split_rows(rows)
 
     def setTracer(self, tracer, fill_value=None, missing_value=None, reference=0.0, wrapX=True):
         """A tracer at T-points (potential temperature, salinity) for computeTracerFlux / computeTracerAll: the same
@@ -587,7 +591,7 @@ class Field(object):
         self._stage_tracer(tIndex)
         row = numpy.zeros(max(self._rowlen, 1), numpy.float64)
         check(lib.nf_field_compute_tracer_flux(ctypes.byref(self._h), tIndex, _lib.dptr(row)))
-        return row[self._nseg:self._nseg + len(self.plis)], row[:self._nseg]
+        return self._split_rows(row)
 
     def computeTracerAll(self, out=None):
         """Tracer transport of all nt steps: (nt, ntransect) totals and (nt, nseg) per-segment sums.  `out`: optional torch
@@ -610,7 +614,7 @@ class Field(object):
                 out = torch.empty((self.nt, max(self._rowlen, 1)), dtype=torch.float64, device='cuda')
             check(lib.nf_field_compute_tracer_all_async(ctypes.byref(self._h), ctypes.c_void_p(out.data_ptr())))
             rows = out.cpu().numpy()
-        return rows[:, self._nseg:self._nseg + len(self.plis)], rows[:, :self._nseg]
+        return self._split_rows(rows)
 
     def depthBandFlux(self, profile, ztop, zbot):
         """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile (totals or
