@@ -283,6 +283,22 @@ int nf_field_set_tracer_reference(nf_field **self, double ref);                /
 int nf_field_set_tracer_wrap(nf_field **self, int wrap_x);                     /* default 1 */
 int nf_field_compute_tracer_flux(nf_field **self, long tIndex, double *row_host);   /* row_length doubles */
 int nf_field_compute_tracer_all_async(nf_field **self, double *rows_dev);           /* (nt, row_length) in HBM */
+/* Volume transport in tracer classes (by temperature, salinity or potential density: overturning in density space).  The
+ * tracer of nf_field_set_tracer (its markers and wrap_x; NOT its reference) gives every U / V face a class value x: 0.5*(a+b)
+ * in double when both cells beside the face have a value, the present one when one has, none when neither has (a and b as
+ * in the tracer block above).  With the class edges e[0] < ... < e[nedges-1] one time step gives nedges + 2 rows, each
+ * [segments | transects]: row 0 x < e[0]; row k (1 <= k <= nedges-1) e[k-1] <= x < e[k]; row nedges x >= e[nedges-1] (+inf
+ * included); row nedges+1 no class value (also NaN: +inf beside -inf).  The flux that is binned is the per-level term of
+ * nf_field_compute_profile: each (record, level, slot) term goes to the row of its own face (the west slot is the east face
+ * of the west cell, the south slot the north face of the south cell), so the sum of all rows is the volume row up to
+ * rounding, and tau = level index with edges -0.5, 0.5, ... gives the profile rows bit for bit.  Summation order is fixed
+ * (levels ascending, slots in order, then the transect reduction): no atomics, bitwise reproducible.  Owned levels only;
+ * steps this rank does not touch get exact zeros.  None of these calls changes the resident planes, |.| arrays, running max,
+ * the tracer rows or a captured pass.  Compute before set_tracer or set_class_edges: NF_ERR_STATE. */
+/* 2 <= nedges <= 1025, finite, strictly increasing (else NF_ERR_ARG); host copy, uploaded by the next compute */
+int nf_field_set_class_edges(nf_field **self, const double *edges, int nedges);
+int nf_field_compute_class_transport(nf_field **self, long tIndex, double *rows_host);        /* (nedges+2, row_length) */
+int nf_field_compute_class_transport_async(nf_field **self, long tIndex, double *rows_dev);   /* HBM, field's stream */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

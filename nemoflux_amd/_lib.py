@@ -124,6 +124,9 @@ _sig('nf_field_set_tracer_reference', [_pp, ctypes.c_double])
 _sig('nf_field_set_tracer_wrap', [_pp, ctypes.c_int])
 _sig('nf_field_compute_tracer_flux', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_tracer_all_async', [_pp, ctypes.c_void_p])
+_sig('nf_field_set_class_edges', [_pp, c_double_p, ctypes.c_int])
+_sig('nf_field_compute_class_transport', [_pp, ctypes.c_long, c_double_p])
+_sig('nf_field_compute_class_transport_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_read_step', [_pp, c_double_p, c_double_p, c_double_p, c_double_p])
 _sig('nf_field_reset_max', [_pp])
 _sig('nf_field_get_arclengths', [_pp, c_double_p])

@@ -17,11 +17,13 @@ static int g_batch_steps = 1;
 //                          stores on its own (default 1)
 //   "pass_k3_pairs"        1 = the per-step pass reduces its whole steps two at a time: one gather launch reads the record
 //                          stream once for both steps; 0 = one reduction per step (default 1)
+//   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
 static long g_batch_cellsteps = 32l << 20;
 static int g_partial_full = 0;
 static int g_use_graph = 1;
 static int g_inner_signed = 1;
 static int g_k3_pairs = 1;
+static int g_class_window = 32;
 static long g_knob_version = 0;   // bumped by every knob of this file: a captured pass bakes them in
 
 namespace nf {
@@ -51,6 +53,11 @@ int field_tuning_set(const char *name, int value)
     }
     if (!strcmp(name, "pass_k3_pairs")) {
         g_k3_pairs = value != 0;
+        return NF_OK;
+    }
+    if (!strcmp(name, "class_window")) {
+        if (!(value >= 1 && value <= kClassWindowMax)) return -1;
+        g_class_window = value;
         return NF_OK;
     }
     return -1;
@@ -115,6 +122,12 @@ struct nf_field {
     double tau_ref = 0.0;
     int tau_wrap = 1;
     DevArray<char> stage_tau;   // host-resident tracer: the owned levels of one step
+    // class transport (nf_field_set_class_edges): the edges on the host, uploaded by the next compute after a change; the run
+    // sums of one window of rows (ws.nrec * window, allocated on first use, dropped with the weights)
+    std::vector<double> class_edges;
+    bool class_edges_stale = false;
+    DevArray<double> class_edges_dev;
+    DevArray<double> class_scratch;
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -455,6 +468,59 @@ static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
     NF_TRY(launch_tracer_flux(a, f->stream));
     // K3 reads the two signed members of [4][ncell] planes at +ncell and +2 ncell: the tracer planes sit at +ncell
     return field_integral(f, f->geo.tr_planes.get() - f->ncell, f->scratch.get(), row_dev);
+}
+
+// the calls of the class transport need a tracer and class edges: checked before a device is needed
+static int field_class_ready(const nf_field *f, const char *what)
+{
+    NF_REQUIRE(f->tau, NF_ERR_STATE, std::string(what) + ": set_tracer first");
+    NF_REQUIRE(!f->class_edges.empty(), NF_ERR_STATE, std::string(what) + ": set_class_edges first");
+    return field_ready(f, what, true);
+}
+
+// Volume transport in tracer classes of step t on the field's stream: rows_dev (nedges + 2, row_length), written whole.
+// Owned levels only, exact zeros for a step this rank does not touch.  Reads the raw fields, the tracer and the records; the
+// resident planes, |.| arrays, running max, last row, tracer planes, version and a captured pass stay as they are.
+static int field_class_step_async(nf_field *f, long t, double *rows_dev)
+{
+    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_class_transport: time index out of range");
+    NF_REQUIRE(f->tau_dtype == f->uv_dtype, NF_ERR_ARG,
+               "compute_class_transport: the tracer's dtype differs from the dtype of uo/vo");
+    NF_REQUIRE(f->tau_nt == f->nt, NF_ERR_ARG, "compute_class_transport: the tracer's nt differs from the nt of uo/vo");
+    const int rowlen = field_row_length(f), nedges = (int)f->class_edges.size();
+    if (rowlen == 0) return NF_OK;
+    const Levels lv = field_levels(f, t);
+    if (lv.z1 <= lv.z0) {   // this rank owns no slab of step t: contributes zeros
+        NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)(nedges + 2), f->stream));
+        return NF_OK;
+    }
+    if (f->class_edges_stale) {
+        // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
+        NF_TRY(f->class_edges_dev.reserve((size_t)kMaxClassEdges));
+        NF_HIP(hipMemcpyAsync(f->class_edges_dev.get(), f->class_edges.data(), sizeof(double) * nedges, hipMemcpyHostToDevice,
+                              f->stream));
+        NF_HIP(hipStreamSynchronize(f->stream));
+        f->class_edges_stale = false;
+    }
+    const int window = g_class_window;
+    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
+    ClassArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_stage(f, f->tau, f->tau_on_device, t, lv, &f->stage_tau, &a.tau));
+    a.tfill = f->tau_fill;
+    a.tfill2 = f->tau_fill2;
+    a.wrap_x = f->tau_wrap;
+    a.edges = f->class_edges_dev.get();
+    a.nedges = nedges;
+    a.window = window;
+    a.ws = &f->ws;
+    a.tr_offsets_dev = f->tr_off_dev.get();
+    a.ntransect = (int)f->polylines.size();
+    a.row_length = rowlen;
+    a.scratch = f->class_scratch.get();
+    a.scratch_len = f->class_scratch.size();
+    a.rows = rows_dev;
+    return launch_class_transport(a, f->stream);
 }
 
 // steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
@@ -806,6 +872,7 @@ try {
     }
     f->weights_built = false;
     f->prof_scratch.reset();
+    f->class_scratch.reset();
     const int bw = build_weights(f->geo.xy.get(), f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
                                  f->skip_unsupported, f->overlap_warn, nullptr, f->nx);
     if (bw != NF_OK) {
@@ -1054,6 +1121,48 @@ try {
     const int rowlen = field_row_length(f);
     for (long t = 0; t < f->nt; ++t) NF_TRY(field_tracer_step_async(f, t, rows_dev + (size_t)t * rowlen));
     return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_class_edges(nf_field **self, const double *edges, int nedges)
+try {
+    NF_REQUIRE(self && *self && edges, NF_ERR_ARG, "nf_field_set_class_edges: null argument");
+    if (!(nedges >= 2 && nedges <= kMaxClassEdges)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "nf_field_set_class_edges: need 2 <= nedges <= %d, got %d", kMaxClassEdges, nedges);
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    for (int k = 0; k < nedges; ++k) {
+        NF_REQUIRE(std::isfinite(edges[k]), NF_ERR_ARG, "nf_field_set_class_edges: every edge must be a finite number");
+        NF_REQUIRE(k == 0 || edges[k] > edges[k - 1], NF_ERR_ARG,
+                   "nf_field_set_class_edges: the edges must be strictly increasing");
+    }
+    nf_field *f = *self;
+    f->class_edges.assign(edges, edges + nedges);
+    f->class_edges_stale = true;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_class_transport(nf_field **self, long tIndex, double *rows_host)
+try {
+    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_transport: null argument");
+    nf_field *f = *self;
+    NF_TRY(field_class_ready(f, "nf_field_compute_class_transport"));
+    NF_NEED_DEVICE();
+    const size_t n = (f->class_edges.size() + 2) * (size_t)field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_class_transport_async(nf_field **self, long tIndex, double *rows_dev)
+try {
+    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_transport_async: null argument");
+    nf_field *f = *self;
+    NF_TRY(field_class_ready(f, "nf_field_compute_class_transport_async"));
+    NF_NEED_DEVICE();
+    return field_class_step_async(f, tIndex, rows_dev);
 }
 NF_API_CATCH
 

@@ -362,6 +362,55 @@ struct TracerArgs {
 };
 int launch_tracer_flux(const TracerArgs &a, hipStream_t s);
 
+// The tracer face rule, shared by the tracer transport and the class transport.  A value is present
+// when it is not NaN and not one of the tracer's two markers (compared in its dtype).  The raw face value of (a, b), b the
+// second cell of the face (has_b = false: the face has none): 0.5 (a + b) in double when both are present, the present one
+// when one is; tr_face_raw returns false when neither is (*s is then not a value).
+template <typename T>
+__device__ inline bool tr_present(T x, T m1, T m2)
+{
+    return !(x != x || x == m1 || x == m2);
+}
+template <typename T>
+__device__ inline bool tr_face_raw(T a, T b, bool has_b, T m1, T m2, double *s)
+{
+    const bool pa = tr_present(a, m1, m2), pb = has_b && tr_present(b, m1, m2);
+    *s = (pa && pb) ? 0.5 * ((double)a + (double)b) : (pa ? (double)a : (double)b);
+    return pa || pb;
+}
+// the face value of the tracer transport: the raw value minus the reference, 0 without a value
+template <typename T>
+__device__ inline double tr_face(T a, T b, bool has_b, T m1, T m2, double ref)
+{
+    double s;
+    return tr_face_raw(a, b, has_b, m1, m2, &s) ? s - ref : 0.0;
+}
+
+// Volume transport in tracer classes (nf_field_compute_class_transport, nf_integral.hip): rows 0 .. nedges+1 of one time
+// step -- row 0: class value x < e[0]; row k: e[k-1] <= x < e[k]; row nedges: x >= e[nedges-1]; row nedges+1: no value
+// (tracer missing on both sides of the face, or NaN from +inf beside -inf).  The class value of a face is tr_face_raw of
+// the tracer (no reference).  Each per-level term of the profile kernel goes to the row of its own face; the rows are
+// built `window` at a time: scratch holds ws.nrec * window run sums.
+constexpr int kMaxClassEdges = 1025;
+constexpr int kClassWindowMax = 32;
+struct ClassArgs {
+    StepInput in;
+    const void *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
+    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
+    int wrap_x = 1;
+    const double *edges = nullptr;   // device, nedges
+    int nedges = 0;
+    int window = 0;              // rows per pass over the fields, 1 .. kClassWindowMax
+    const WeightSet *ws = nullptr;
+    const int *tr_offsets_dev = nullptr;
+    int ntransect = 0;
+    long row_length = 0;
+    double *scratch = nullptr;
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // (nedges + 2, row_length)
+};
+int launch_class_transport(const ClassArgs &a, hipStream_t s);
+
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q
 int launch_find_points(const double *xy, long ncell, long row_length, LocatorBoxes *keep, const double *targets_dev, long npts,

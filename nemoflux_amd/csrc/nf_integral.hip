@@ -376,4 +376,179 @@ int launch_profile(const ProfileArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
 }
 
+// ---- volume transport in tracer classes: the profile kernel's terms, each sent to the row of its face's class ----------------
+// One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are the
+// ones of k_profile_segscan; each is added, in slot order (south, east, north, west), to the lane's accumulator of the row
+// that its own face's class value selects, when that row lies in the window [r0, r0 + nwin).  The accumulators are a column
+// of LDS per lane (a dynamic row index in registers would go to scratch).  Then K3's segmented scan runs once per row of the
+// window.  With one class per level (tau = z) a row gets exactly one level's four terms, added as ((0 + t0) + t1) + t2) + t3:
+// the profile's ((t0 + t1) + t2) + t3, bit for bit.
+//   faces: east(c) = (tau[c], tau[c+1]; column nx-1: tau[c+1-nx] when wrap_x, else none), north(c) = (tau[c], tau[c+nx];
+//   last row: none), the west slot is east(cw), the south slot north(cs).
+// LDS: the edges (nedges doubles, padded to even), then nwin x kBlock accumulators.
+constexpr int kClassLevels = 4;   // levels whose 9 gathers are issued together
+
+// row of class value x among the n edges in LDS: the number of edges <= x (binary lifting, `top` = the largest power of two
+// <= n: the same number of steps in every lane); no value or NaN: row n + 1
+__device__ inline int class_row(bool has, double x, const double *e, int n, int top)
+{
+    if (!has || x != x) return n + 1;
+    int pos = 0;
+    for (int step = top; step > 0; step >>= 1)
+        if (pos + step <= n && e[pos + step - 1] <= x) pos += step;
+    return pos;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                          const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                          const T *__restrict__ v, const T *__restrict__ tau, long ncell,
+                                                          unsigned nx, int z0, int z1, const double *__restrict__ thickness,
+                                                          const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                          T fill, T fill2, int two, T tfill, T tfill2, int wrap_x,
+                                                          double scale, int sverdrup, const double *__restrict__ edges,
+                                                          int nedges, int top, int r0, int nwin, double *__restrict__ runsum)
+{
+    extern __shared__ double class_lds[];
+    double *e = class_lds;
+    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
+    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
+    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
+    __syncthreads();   // the edges; every lane touches only its own accumulators
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    int key = -1;
+    if (k < n) {
+        typedef double dvec2 __attribute__((ext_vector_type(2)));
+        const long c = __builtin_nontemporal_load(cell + k);
+        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
+        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
+        key = __builtin_nontemporal_load(seg + k);
+        const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
+        const bool south = j > 0;
+        const bool has_e = i + 1 < nx || wrap_x, has_n = c + (long)nx < ncell, has_w = i > 0 || wrap_x;
+        const long cs = south ? c - nx : c;             // row 0: no south value (read, then discarded)
+        const long cw = i > 0 ? c - 1 : c - 1 + nx;
+        const long ce = i + 1 < nx ? c + 1 : (wrap_x ? c + 1 - (long)nx : c);
+        const long cn = has_n ? c + nx : c;
+        const double aEc = arcE[c], aNc = arcN[c], aNs = arcN[cs], aEw = arcE[cw];
+        auto add = [&](int row, double x) {
+            const int r = row - r0;
+            if (r >= 0 && r < nwin) acc[r * kBlock] += x;
+        };
+        for (int z = z0; z < z1; z += kClassLevels) {
+            const int nlev = z1 - z < kClassLevels ? z1 - z : kClassLevels;
+            T uc[kClassLevels], uw[kClassLevels], vc[kClassLevels], vs[kClassLevels];
+            T tc[kClassLevels], te[kClassLevels], tn[kClassLevels], tw[kClassLevels], ts[kClassLevels];
+#pragma unroll
+            for (int l = 0; l < kClassLevels; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    uc[l] = u[o + c];
+                    uw[l] = u[o + cw];
+                    vc[l] = v[o + c];
+                    vs[l] = v[o + cs];
+                    tc[l] = tau[o + c];
+                    te[l] = tau[o + ce];
+                    tn[l] = tau[o + cn];
+                    tw[l] = tau[o + cw];
+                    ts[l] = tau[o + cs];
+                }
+#pragma unroll
+            for (int l = 0; l < kClassLevels; ++l)
+                if (l < nlev) {
+                    const double th = thickness[z + l];
+                    double d1 = +fma(th, profile_fixed<T>(uc[l], fill, fill2, two), 0.0) * aEc;
+                    double d3 = +fma(th, profile_fixed<T>(uw[l], fill, fill2, two), 0.0) * aEw;
+                    double d2 = -fma(th, profile_fixed<T>(vc[l], fill, fill2, two), 0.0) * aNc;
+                    double d0 = -fma(th, profile_fixed<T>(vs[l], fill, fill2, two), 0.0) * aNs;
+                    if (sverdrup) {
+                        d0 *= scale;
+                        d1 *= scale;
+                        d2 *= scale;
+                        d3 *= scale;
+                    }
+                    double x;
+                    bool h;
+                    if (south) {
+                        h = tr_face_raw<T>(ts[l], tc[l], true, tfill, tfill2, &x);
+                        add(class_row(h, x, e, nedges, top), wa.x * d0);
+                    }
+                    h = tr_face_raw<T>(tc[l], te[l], has_e, tfill, tfill2, &x);
+                    add(class_row(h, x, e, nedges, top), wa.y * d1);
+                    h = tr_face_raw<T>(tc[l], tn[l], has_n, tfill, tfill2, &x);
+                    add(class_row(h, x, e, nedges, top), wb.x * d2);
+                    h = tr_face_raw<T>(tw[l], tc[l], has_w, tfill, tfill2, &x);
+                    add(class_row(h, x, e, nedges, top), wb.y * d3);
+                }
+        }
+    }
+    // K3's segmented scan, once per row of the window; its flags depend on the keys only
+    unsigned take = 0;
+#pragma unroll
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) {
+        const int pk = __shfl_up(key, o, kWave);
+        if (lane >= o && pk == key) take |= 1u << b;
+    }
+    const int nk = __shfl_down(key, 1, kWave);
+    const bool store = k < n && (lane == kWave - 1 || k == n - 1 || nk != key);
+    for (int r = 0; r < nwin; ++r) {
+        double val = k < n ? acc[r * kBlock] : 0.0;
+#pragma unroll
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) {
+            const double pv = __shfl_up(val, o, kWave);
+            if (take & (1u << b)) val += pv;
+        }
+        if (store) runsum[(long)r * n + k] = val;
+    }
+}
+
+template <typename T>
+static int launch_class_t(const ClassArgs &a, hipStream_t s)
+{
+    const WeightSet &ws = *a.ws;
+    const StepInput &in = a.in;
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    const int two = fill2 == fill2 && !(fill2 == fill);   // K1's rule: a second marker that differs from the first
+    int top = 1;
+    while (2 * top <= a.nedges) top *= 2;
+    const int nrows = a.nedges + 2;
+    for (int r0 = 0; r0 < nrows; r0 += a.window) {
+        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
+        const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
+        if (ws.nrec > 0) {
+            if (lds > 65536)
+                NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_class_segscan<T>, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)), dim3(kBlock), lds, s,
+                               ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v,
+                               (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN,
+                               fill, fill2, two, (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.edges,
+                               a.nedges, top, r0, nwin, a.scratch);
+        }
+        launch_finalize(ws, ws.seg_start.get(), ws.nrec, a.scratch, a.tr_offsets_dev, a.ntransect,
+                        a.rows + (long)r0 * a.row_length, a.row_length, (unsigned)nwin, s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+int launch_class_transport(const ClassArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.ws && in.ncell > 0 && in.nx > 0 && in.ncell % in.nx == 0 && in.ncell < (1l << 31), NF_ERR_ARG,
+               "class transport: bad grid sizes");
+    NF_REQUIRE(in.z0 >= 0 && in.z1 >= in.z0 && a.row_length == a.ws->nseg + a.ntransect, NF_ERR_ARG,
+               "class transport: bad arguments");
+    NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "class transport: bad class edges");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "class transport: bad window");
+    NF_REQUIRE(a.scratch_len >= (size_t)a.ws->nrec * a.window, NF_ERR_ARG, "class transport: scratch too small");
+    NF_REQUIRE(in.u && in.v && a.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+               "class transport: null argument");
+    if (a.row_length == 0) return NF_OK;
+    if (in.dtype == NF_F64) return launch_class_t<double>(a, s);
+    if (in.dtype == NF_F32) return launch_class_t<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "class transport: dtype must be NF_F64 or NF_F32");
+}
+
 }  // namespace nf

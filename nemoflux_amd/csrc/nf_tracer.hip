@@ -56,21 +56,6 @@ __device__ inline double tr_fixed(T x, T fill, T fill2)
     return (x != x || x == fill || x == fill2) ? 0.0 : (double)x;
 }
 
-template <typename T>
-__device__ inline bool tr_present(T x, T m1, T m2)
-{
-    return !(x != x || x == m1 || x == m2);
-}
-
-// the face value of the definition above; has_b = false: the face has no second cell
-template <typename T>
-__device__ inline double tr_face(T a, T b, bool has_b, T m1, T m2, double ref)
-{
-    const bool pa = tr_present(a, m1, m2), pb = has_b && tr_present(b, m1, m2);
-    const double s = (pa && pb) ? 0.5 * ((double)a + (double)b) : (pa ? (double)a : (double)b);
-    return (pa || pb) ? s - ref : 0.0;
-}
-
 }  // namespace
 
 // 256 threads, one chunk of VEC cells per lane: lane c0 = (tile * 256 + tid) * VEC.  ncell % VEC == 0 and nx >= VEC (the

@@ -616,6 +616,51 @@ class Field(object):
             rows = out.cpu().numpy()
         return self._split_rows(rows)
 
+    def setClassEdges(self, edges):
+        """Class edges e[0] < ... < e[n-1] (2 <= n <= 1025, finite) for computeClassTransport: the classes of the tracer of
+        setTracer (potential density, temperature, salinity) that the volume transport is binned by."""
+        e = numpy.array(edges, dtype=numpy.float64).reshape(-1)
+        check(lib.nf_field_set_class_edges(ctypes.byref(self._h), _lib.dptr(e), int(e.size)))
+        self._class_edges = e
+
+    def computeClassTransport(self, tIndex, out=None, prefetch_next=None):
+        """Volume transport of time step tIndex binned by the class of the tracer at each U / V face (setTracer and
+        setClassEdges first): (nedges+2, ntransect) totals and (nedges+2, nseg) per-segment sums.  Row 0: class value
+        x < e[0]; row k: e[k-1] <= x < e[k]; row nedges: x >= e[nedges-1]; row nedges+1: faces without a class value (the
+        tracer missing on both sides).  The class value of a face is the mean of the tracer in the two cells beside it (the
+        present one when only one has a value); the tracer's reference is NOT used for it.  Every per-level term of
+        computeFluxProfile goes to the row of its face, so the rows add up to the computeFlux row (up to rounding).  Levels
+        this rank does not own (slab_range) contribute nothing.  Leaves the resident edge fluxes, the running max, the row of
+        the last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
+        (nedges+2, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        import torch
+        tIndex = int(tIndex)
+        edges = getattr(self, '_class_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setClassEdges first')
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        shape = (edges.size + 2, max(self._rowlen, 1))
+        if out is not None:
+            if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
+                raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
+            check(lib.nf_field_compute_class_transport_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros(shape, numpy.float64)
+            check(lib.nf_field_compute_class_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        return self._split_rows(rows)
+
+    @staticmethod
+    def classStreamfunction(rows):
+        """Overturning streamfunction in class space from the rows of computeClassTransport (totals or segments, classes
+        first): psi[k] = rows[0] + ... + rows[k], k = 0 .. nedges-1, the transport of the faces whose class value is below
+        e[k].  Host only."""
+        R = numpy.asarray(rows, dtype=numpy.float64)
+        if R.ndim < 1 or R.shape[0] < 4:
+            raise ValueError(f'classStreamfunction: need the nedges + 2 >= 4 rows of computeClassTransport, got shape {R.shape}')
+        return numpy.cumsum(R[:R.shape[0] - 2], axis=0)
+
     def depthBandFlux(self, profile, ztop, zbot):
         """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile (totals or
         segments, levels first): level z contributes profile[z] * overlap([ztop, zbot], layer z) / thickness[z], exact

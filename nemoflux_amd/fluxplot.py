@@ -10,6 +10,8 @@ only with --show): the table is always printed or written as CSV, which is what 
     python -m nemoflux_amd.fluxplot -t T.npz -u U.npz -v V.npz -l "..." --zrange 0,1000   (flux above 1000 m only)
     python -m nemoflux_amd.fluxplot -t T.nc -u U.nc -v V.nc -l "..." -s --tracer thetao --tracer-scale 4.1e-3
                                   (heat transport in PW: Sv degC x 1e6 m^3/s x rho0 c_p (4.1e6 J/m^3/K) x 1e-15 PW/W)
+    python -m nemoflux_amd.fluxplot -t T.nc -u U.nc -v V.nc -l "..." -s --tracer sigma0 --tracer-file S.nc --classes 26,27,28
+                                  (water flow by sigma0 class: one CSV line per time step and class)
 """
 import argparse
 import glob
@@ -73,6 +75,44 @@ def tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', trac
     return totals, fld
 
 
+def classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', sverdrup=False):
+    """(nt, nedges+2, ntransect) water flow by class of the variable `tracer` of tracerFile (default: the T file), one
+    Field.computeClassTransport per time step, and the Field."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld.setTracer((tracerFile or tFile, tracer))
+    fld.setClassEdges(edges)
+    totals = numpy.array([fld.computeClassTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
+
+
+def parseClasses(classes):
+    """'E0,E1,...,EN' -> the class edges (a list of at least two finite, strictly increasing numbers)."""
+    try:
+        edges = [float(x) for x in classes.split(',')]
+    except ValueError:
+        raise RuntimeError(f'ERROR: --classes must be E0,E1,...,EN (numbers), got {classes!r}')
+    if len(edges) < 2 or not all(numpy.isfinite(edges)) or not all(a < b for a, b in zip(edges, edges[1:])):
+        raise RuntimeError(f'ERROR: --classes needs at least two finite, strictly increasing edges, got {classes!r}')
+    return edges
+
+
+def checkClassArgs(classes='', tracer='', tracerRef=0.0, tracerScale=1.0, zrange='', show=False):
+    """the --classes option of the command line: refused combinations raise RuntimeError"""
+    if not classes:
+        return
+    if not tracer:
+        raise RuntimeError('ERROR: --classes needs --tracer NAME (the class field, e.g. sigma0 or thetao)')
+    if zrange:
+        raise RuntimeError('ERROR: --classes and --zrange cannot be combined: depth-resolved class transports are not '
+                           'available')
+    if float(tracerRef) != 0.0 or float(tracerScale) != 1.0:
+        raise RuntimeError('ERROR: --classes bins the water flow by the raw tracer: --tracer-ref / --tracer-scale do not '
+                           'apply')
+    if show:
+        raise RuntimeError('ERROR: --classes and --show cannot be combined: the class table is written as CSV only')
+    parseClasses(classes)
+
+
 def checkTracerArgs(tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, zrange=''):
     """the tracer options of the command line: refused combinations raise RuntimeError"""
     if not tracer:
@@ -101,10 +141,26 @@ def parseZRange(zrange):
 
 
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
-         tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0):
+         tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes=''):
+    checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
     checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, zrange)
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
+    if classes:
+        edges = parseClasses(classes)
+        totals, fld = classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, sverdrup)
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
+        lines = ['time,lower,upper,' + ','.join(names)]
+        lines += [f'{timeVals[t]},{lo:.15g},{hi:.15g},' + ','.join(f'{x:.15g}' for x in totals[t, k])
+                  for t in range(fld.nt) for k, (lo, hi) in enumerate(bounds)]
+        text = f'# water flow by {tracer} class [{"Sv" if sverdrup else "A m^2/s"}]\n' + '\n'.join(lines) + '\n'
+        if output:
+            with open(output, 'w') as f:
+                f.write(text)
+        else:
+            print(text, end='')
+        return totals
     if tracer:
         totals, fld = tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup)
         totals = totals * float(tracerScale)
@@ -162,4 +218,7 @@ if __name__ == '__main__':
                     help='reference value subtracted from the tracer (theta_ref of a heat transport across an open section)')
     ap.add_argument('--tracer-scale', dest='tracerScale', type=float, default=1.0, metavar='S',
                     help='multiply the tracer transport by S (with -s: 1e6 * rho0 * c_p * 1e-15 = 4.1e-3 turns Sv degC into PW)')
+    ap.add_argument('--classes', default='', metavar='E0,E1,...,EN',
+                    help='water flow binned by the class of --tracer NAME (e.g. sigma0): one CSV line per time step and '
+                         'class [-inf,E0), [E0,E1), ..., [EN,inf), and a last one (nan,nan) for faces without a value')
     main(**vars(ap.parse_args()))
