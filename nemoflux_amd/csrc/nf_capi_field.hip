@@ -250,7 +250,8 @@ static int field_ensure_derived(nf_field *f)
     return NF_OK;
 }
 
-static int field_row_length(const nf_field *f) { return f->ws.nseg + (int)f->polylines.size(); }
+static Transects field_transects(const nf_field *f) { return Transects{&f->ws, f->tr_off_dev.get(), (int)f->polylines.size()}; }
+static int field_row_length(const nf_field *f) { return (int)field_transects(f).row_length(); }
 
 // the state every per-step computation needs; `what` prefixes the message ("compute", "compute_profile", ...)
 static int field_ready(const nf_field *f, const char *what, bool weights)
@@ -347,8 +348,9 @@ static FluxArgs flux_args(const StepInput &in)
 static int field_integral(nf_field *f, const double *planes, double *scratch, double *rows, int nsteps = 1,
                           long data_stride = 0, long row_stride = 0)
 {
-    return launch_integral(f->ws, planes, f->ncell, 2, f->nx, f->tr_off_dev.get(), (int)f->polylines.size(), scratch, rows,
-                           f->stream, nsteps, data_stride, row_stride);
+    const Transects tr = field_transects(f);
+    return launch_integral(f->ws, planes, f->ncell, 2, f->nx, tr.tr_offsets_dev, tr.ntransect, scratch, rows, f->stream, nsteps,
+                           data_stride, row_stride);
 }
 
 // a synchronous entry point: `step` writes n doubles into the field's own device buffer, which are copied to `host` (nullptr:
@@ -412,28 +414,49 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     return NF_OK;
 }
 
+// The opening of the calls that reduce the raw fields of step t into `nrows` rows at rows_dev (`what` prefixes the messages):
+// checks the time index and, where a tracer is read, its dtype and nt; *lv: the levels to run the kernels on.  None when a row
+// is empty or this rank owns no slab of step t: its rows are then exact zeros, so that the ranks' rows add up to the full ones.
+static int field_raw_step_begin(nf_field *f, const char *what, long t, bool tracer, double *rows_dev, size_t nrows, Levels *lv)
+{
+    const std::string w(what);
+    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, w + ": time index out of range");
+    NF_REQUIRE(!tracer || f->tau_dtype == f->uv_dtype, NF_ERR_ARG, w + ": the tracer's dtype differs from the dtype of uo/vo");
+    NF_REQUIRE(!tracer || f->tau_nt == f->nt, NF_ERR_ARG, w + ": the tracer's nt differs from the nt of uo/vo");
+    const size_t rowlen = field_row_length(f);
+    *lv = rowlen > 0 ? field_levels(f, t) : Levels{};
+    if (rowlen > 0 && lv->z1 <= lv->z0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * nrows, f->stream));
+    return NF_OK;
+}
+
+// the tracer of step t (staged when host-resident), its markers and wrap rule: the members TracerArgs and ClassArgs share
+template <typename Args>
+static int field_tracer_input(nf_field *f, long t, Levels lv, Args *a)
+{
+    NF_TRY(field_stage(f, f->tau, f->tau_on_device, t, lv, &f->stage_tau, &a->tau));
+    a->tfill = f->tau_fill;
+    a->tfill2 = f->tau_fill2;
+    a->wrap_x = f->tau_wrap;
+    return NF_OK;
+}
+
 // Depth-resolved rows of step t on the field's stream: prof_dev (nz, row_length), row z = the flux carried by level z alone.
 // Reads the raw fields and the records; leaves the resident planes, |.| arrays, running max, version and a captured pass
 // alone.  Levels this rank does not own get zeros.  The caller has checked field_ready (with the weights).
 static int field_profile_async(nf_field *f, long t, double *prof_dev)
 {
-    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_profile: time index out of range");
-    const int rowlen = field_row_length(f);
-    if (rowlen == 0) return NF_OK;
-    const Levels lv = field_levels(f, t);
-    // levels outside [z0, z1): exact zeros, so that the ranks' profiles add up to the full one
-    if (lv.z0 > 0) NF_HIP(hipMemsetAsync(prof_dev, 0, sizeof(double) * rowlen * (size_t)lv.z0, f->stream));
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_profile", t, false, prof_dev, (size_t)f->nz, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    const size_t rowlen = field_row_length(f);
+    if (lv.z0 > 0) NF_HIP(hipMemsetAsync(prof_dev, 0, sizeof(double) * rowlen * (size_t)lv.z0, f->stream));   // not owned
     if (lv.z1 < f->nz)
         NF_HIP(hipMemsetAsync(prof_dev + (size_t)lv.z1 * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nz - lv.z1),
                               f->stream));
-    if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->prof_scratch.reserve((size_t)f->ws.nrec * kProfileChunk));
     ProfileArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    a.ws = &f->ws;
-    a.tr_offsets_dev = f->tr_off_dev.get();
-    a.ntransect = (int)f->polylines.size();
-    a.row_length = rowlen;
+    a.tr = field_transects(f);
     a.scratch = f->prof_scratch.get();
     a.scratch_len = f->prof_scratch.size();
     a.prof = prof_dev;
@@ -446,24 +469,14 @@ static int field_profile_async(nf_field *f, long t, double *prof_dev)
 static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
 {
     NF_TRY(field_ready(f, "compute_tracer", true));
-    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_tracer: time index out of range");
-    NF_REQUIRE(f->tau_dtype == f->uv_dtype, NF_ERR_ARG, "compute_tracer: the tracer's dtype differs from the dtype of uo/vo");
-    NF_REQUIRE(f->tau_nt == f->nt, NF_ERR_ARG, "compute_tracer: the tracer's nt differs from the nt of uo/vo");
-    const int rowlen = field_row_length(f);
-    if (rowlen == 0) return NF_OK;
-    const Levels lv = field_levels(f, t);
-    if (lv.z1 <= lv.z0) {   // this rank owns no slab of step t: contributes zeros
-        NF_HIP(hipMemsetAsync(row_dev, 0, sizeof(double) * rowlen, f->stream));
-        return NF_OK;
-    }
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_tracer", t, true, row_dev, 1, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
     TracerArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_stage(f, f->tau, f->tau_on_device, t, lv, &f->stage_tau, &a.tau));
+    NF_TRY(field_tracer_input(f, t, lv, &a));
     NF_TRY(f->geo.tr_planes.reserve((size_t)f->ncell * 2));
-    a.tfill = f->tau_fill;
-    a.tfill2 = f->tau_fill2;
     a.ref = f->tau_ref;
-    a.wrap_x = f->tau_wrap;
     a.planes = f->geo.tr_planes.get();
     NF_TRY(launch_tracer_flux(a, f->stream));
     // K3 reads the two signed members of [4][ncell] planes at +ncell and +2 ncell: the tracer planes sit at +ncell
@@ -483,17 +496,10 @@ static int field_class_ready(const nf_field *f, const char *what)
 // resident planes, |.| arrays, running max, last row, tracer planes, version and a captured pass stay as they are.
 static int field_class_step_async(nf_field *f, long t, double *rows_dev)
 {
-    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute_class_transport: time index out of range");
-    NF_REQUIRE(f->tau_dtype == f->uv_dtype, NF_ERR_ARG,
-               "compute_class_transport: the tracer's dtype differs from the dtype of uo/vo");
-    NF_REQUIRE(f->tau_nt == f->nt, NF_ERR_ARG, "compute_class_transport: the tracer's nt differs from the nt of uo/vo");
-    const int rowlen = field_row_length(f), nedges = (int)f->class_edges.size();
-    if (rowlen == 0) return NF_OK;
-    const Levels lv = field_levels(f, t);
-    if (lv.z1 <= lv.z0) {   // this rank owns no slab of step t: contributes zeros
-        NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)(nedges + 2), f->stream));
-        return NF_OK;
-    }
+    const int nedges = (int)f->class_edges.size();
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_class_transport", t, true, rows_dev, (size_t)nedges + 2, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
     if (f->class_edges_stale) {
         // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
         NF_TRY(f->class_edges_dev.reserve((size_t)kMaxClassEdges));
@@ -506,17 +512,11 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev)
     NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
     ClassArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_stage(f, f->tau, f->tau_on_device, t, lv, &f->stage_tau, &a.tau));
-    a.tfill = f->tau_fill;
-    a.tfill2 = f->tau_fill2;
-    a.wrap_x = f->tau_wrap;
+    NF_TRY(field_tracer_input(f, t, lv, &a));
     a.edges = f->class_edges_dev.get();
     a.nedges = nedges;
     a.window = window;
-    a.ws = &f->ws;
-    a.tr_offsets_dev = f->tr_off_dev.get();
-    a.ntransect = (int)f->polylines.size();
-    a.row_length = rowlen;
+    a.tr = field_transects(f);
     a.scratch = f->class_scratch.get();
     a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
@@ -534,8 +534,8 @@ static int field_pair_async(nf_field *f, long t, double *rows_dev, bool last)
     second.inner = g_inner_signed && !last;
     NF_TRY(field_step_async(f, t, nullptr, first));
     NF_TRY(field_step_async(f, t + 1, nullptr, second));
-    NF_TRY(launch_integral_pair(f->ws, f->geo.uv2.get(), f->geo.iV.get() + f->ncell, f->ncell, f->nx, f->tr_off_dev.get(),
-                                (int)f->polylines.size(), f->scratch.get(), rows_dev + (size_t)t * rowlen, rowlen, f->stream));
+    NF_TRY(launch_integral_pair(field_transects(f), f->geo.uv2.get(), f->geo.iV.get() + f->ncell, f->ncell, f->nx,
+                                f->scratch.get(), rows_dev + (size_t)t * rowlen, rowlen, f->stream));
     NF_TRY(field_timed_k3_end(f));   // the pair's reduction is timed with the second step's launch
     return NF_OK;
 }

@@ -300,6 +300,13 @@ int build_weights(const double *xy, long ncell, const double *segs_host, const i
 // scratches of at most 1 GiB each) back to the system
 void weights_trim_scratch();
 
+struct Transects {   // the transect side of K3: the records of all target segments, and the segments of every transect
+    const WeightSet *ws = nullptr;
+    const int *tr_offsets_dev = nullptr;   // device, (ntransect + 1) segment offsets
+    int ntransect = 0;
+    long row_length() const { return ws->nseg + ntransect; }   // a row: [ per-segment sums | per-transect sums ]
+};
+
 // K3: gather + wavefront segmented reduction -> per-segment sums, then per-transect sums.
 // row: (nseg + ntransect) doubles in HBM; tr_offsets_dev: (ntransect+1) segment offsets.
 // scratch: at least ws.nrec doubles.
@@ -316,9 +323,8 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
 // two time steps of the engine's own planes through the (cell, 4 weights) records in ONE gather launch (the record stream is
 // read once for both): uvA -> row, uvB -> row + row_stride, where uvX is a step's eU plane followed by its eV plane.
 // scratch: 2 * ws.nrec doubles.  The same summation tree per step as launch_integral(planes = 2): the same bits.
-int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *uvB, long ncell, long nx,
-                         const int *tr_offsets_dev, int ntransect, double *scratch, double *row, long row_stride,
-                         hipStream_t s);
+int launch_integral_pair(const Transects &tr, const double *uvA, const double *uvB, long ncell, long nx, double *scratch,
+                         double *row, long row_stride, hipStream_t s);
 
 // What every per-step kernel of a Field reads of one time step (K1's FluxArgs has the same fields, filled from this): the
 // fields, the grid, the levels [z0, z1) and the masking / unit settings of uo / vo.
@@ -339,10 +345,7 @@ struct StepInput {
 constexpr int kProfileChunk = 8;
 struct ProfileArgs {
     StepInput in;
-    const WeightSet *ws = nullptr;
-    const int *tr_offsets_dev = nullptr;
-    int ntransect = 0;
-    long row_length = 0;
+    Transects tr;
     double *scratch = nullptr;
     size_t scratch_len = 0;
     double *prof = nullptr;
@@ -361,6 +364,17 @@ struct TracerArgs {
     double *planes = nullptr; // [2][ncell]: eU_tau, eV_tau
 };
 int launch_tracer_flux(const TracerArgs &a, hipStream_t s);
+
+// K1's masking of uo / vo outside K1 (profile, class and tracer kernels): NaN or one of the two markers -> 0.  `two`: the second
+// marker counts (uv_two_markers: a number that differs from the first; NaN never compares equal, so a kernel without the flag
+// passes true).  K1 keeps its own fixed / fixed2: nf_flux.hip is fingerprinted by the benchmark and stays byte for byte.
+template <typename T>
+inline bool uv_two_markers(T fill, T fill2) { return fill2 == fill2 && !(fill2 == fill); }
+template <typename T>
+__device__ inline double uv_fixed(T x, T fill, T fill2, bool two = true)
+{
+    return (x != x || x == fill || (two && x == fill2)) ? 0.0 : (double)x;
+}
 
 // The tracer face rule, shared by the tracer transport and the class transport.  A value is present
 // when it is not NaN and not one of the tracer's two markers (compared in its dtype).  The raw face value of (a, b), b the
@@ -401,10 +415,7 @@ struct ClassArgs {
     const double *edges = nullptr;   // device, nedges
     int nedges = 0;
     int window = 0;              // rows per pass over the fields, 1 .. kClassWindowMax
-    const WeightSet *ws = nullptr;
-    const int *tr_offsets_dev = nullptr;
-    int ntransect = 0;
-    long row_length = 0;
+    Transects tr;
     double *scratch = nullptr;
     size_t scratch_len = 0;
     double *rows = nullptr;      // (nedges + 2, row_length)

@@ -3,21 +3,125 @@
 // Replaces  mint.PolylineIntegral.getIntegral(data, mint.CELL_BY_CELL_DATA) as driven by
 //           nemoflux/field.py:102 and nemoflux/fluxplot.py:56, for ALL transects of a Field at once.
 //
-// Two forms of stage A.  For the engine's own resident planes the weights come folded onto the unique edges
-// (k_gather_edges, below: one gather per entry); for caller-supplied (ncell,4) data -- mint's getIntegral -- the records
-// are used as they are:
-// Records (cell, 4 edge weights, global segment id) are sorted by segment (K2).  Stage A: one lane per
-// record gathers the cell's 4 edge values (either the reference's (ncell,4) AoS: one 32-B read, or the engine's
-// resident [4][ncell] planes), forms the weighted sum and runs a WAVEFRONT SEGMENTED SCAN keyed by the
-// segment id (6 shuffle steps); the last lane of every run inside the wave stores the run's sum.  Stage B: one
-// wavefront per target segment stitches the run sums of the waves the segment spans.  Stage C: one wavefront
-// per transect adds its segments.  No atomics: the summation tree is fixed, so results are bitwise
-// reproducible.
+// Records (cell, 4 edge weights, global segment id) are sorted by segment (K2).  Stage A: one lane per record loads it
+// (load_record), forms one or more values from the cell's edge values (neighbours, weighted_sum) and runs a WAVEFRONT
+// SEGMENTED SCAN keyed by the segment id (seg_scan); the last lane of every run inside the wave stores the run's sums.  The
+// five stage-A kernels (gather, pair, unique edges, per-level profile, tracer classes) are made of these same pieces, which is
+// why their rows can be compared bit for bit.  Stage B: one wavefront per target segment stitches the run sums of the waves
+// the segment spans.  Stage C: one wavefront per transect adds its segments.  No atomics: the summation tree is fixed, so
+// results are bitwise reproducible.
 //
 // Output row: [ per-segment sums (nseg) | per-transect sums (ntransect) ].
 #include "nf_common.h"
 
 namespace nf {
+
+// ---- the pieces of stage A: load record -> form value(s) -> scan -> store --------------------------------------------------
+typedef double dvec2 __attribute__((ext_vector_type(2)));
+
+// A (cell, 4 weights) record without its key.  The record stream is read once per launch: non-temporal, so that it does not
+// push the plane sectors its neighbours gather -- nor the arc lengths the next flux kernel re-reads -- out of the caches
+// (-0.7 % per pass).  The key has a load of its own: where it sits among a kernel's gathers decides the kernel's registers.
+struct Record {
+    long c;         // cell
+    dvec2 wa, wb;   // the weights of the south and east slots, of the north and west slots
+};
+__device__ inline Record load_record(const int *__restrict__ cell, const double *__restrict__ w4, long k)
+{
+    const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
+    return Record{__builtin_nontemporal_load(cell + k), __builtin_nontemporal_load(pw), __builtin_nontemporal_load(pw + 1)};
+}
+__device__ inline int load_key(const int *__restrict__ seg, long k) { return __builtin_nontemporal_load(seg + k); }
+
+// The neighbour rule of cell c = (j, i) on rows of nx.  The south and west slots of a cell are copies of the neighbours' north
+// and east values (field.py:219-223): south = eV(cs), cs = c - nx; west = eU(cw), cw = c - 1.  Row 0's south slot is never
+// written (south = false; cs = c may then be read and is discarded), column 0 takes the periodic copy of column nx - 1.
+struct Neighbours {
+    unsigned j, i;
+    bool south;
+    long cs, cw;
+};
+__device__ inline Neighbours neighbours(long c, unsigned nx)
+{
+    const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
+    return Neighbours{j, i, j > 0, j > 0 ? c - nx : c, i > 0 ? c - 1 : c - 1 + nx};
+}
+
+// A record's four slot values, in the order the kernels load them, and their sum times the weights (south, east, north, west)
+// with K3's association; the library is built with -ffp-contract=off: these rounded products and sums wherever it is used.
+struct Slots { double e, n, s, w; };
+__device__ inline double weighted_sum(const Record &r, const Slots &d)
+{
+    return ((r.wa.x * d.s + r.wa.y * d.e) + r.wb.x * d.n) + r.wb.y * d.w;
+}
+
+// the slot values from the engine's own planes, read through the two signed ones only (eU, with eV right behind it at + ncell):
+// eU[c-1], eU[c] share a sector and eV[c-nx] is the eV[c] of the record one row below -- about half the sectors of four planes
+__device__ inline Slots signed_plane_slots(const double *__restrict__ eU, long ncell, long c, const Neighbours &nb)
+{
+    const double *eV = eU + ncell;
+    return Slots{eU[c], eV[c], nb.south ? eV[nb.cs] : 0.0, eU[nb.cw]};
+}
+
+// The wavefront segmented scan keyed by the segment id (key -1: a lane without a record), 6 shuffle steps.  seg_scan_take: the
+// lane o below is in the same run -- it depends on the keys only, so it is formed once per step for any number of values;
+// seg_scan_step adds the values from o below where it holds; seg_run_end: record k is the last of its run inside the wave.
+__device__ inline bool seg_scan_take(int key, int lane, int o)
+{
+    const int pk = __shfl_up(key, o, kWave);
+    return lane >= o && pk == key;
+}
+template <int N>
+__device__ inline void seg_scan_step(double (&val)[N], int o, bool take)
+{
+#pragma unroll
+    for (int l = 0; l < N; ++l) {
+        const double pv = __shfl_up(val[l], o, kWave);
+        val[l] = take ? val[l] + pv : val[l];
+    }
+}
+__device__ inline bool seg_run_end(int key, int lane, long k, long n)
+{
+    const int nk = __shfl_down(key, 1, kWave);
+    return k < n && (lane == kWave - 1 || k == n - 1 || nk != key);
+}
+template <int N>
+__device__ inline bool seg_scan(double (&val)[N], int key, long k, long n)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) seg_scan_step(val, o, seg_scan_take(key, lane, o));
+    return seg_run_end(key, lane, k, n);
+}
+
+// One level's slot values from the raw fields, formed as K1 forms them for a field whose only non-zero layer is that level:
+// eU(c) = +fma(th, uv_fixed(u[c]), 0) * arcE[c], eV(c) = -fma(th, uv_fixed(v[c]), 0) * arcN[c], times the Sverdrup scale;
+// east = eU(c), north = eV(c), south = eV(cs) (0 on row 0), west = eU(cw).  Arcs, LevelUV: what is gathered for them.
+struct Arcs { double Ec, Nc, Ns, Ew; };
+__device__ inline Arcs load_arcs(const double *__restrict__ arcE, const double *__restrict__ arcN, long c, const Neighbours &nb)
+{
+    return Arcs{arcE[c], arcN[c], arcN[nb.cs], arcE[nb.cw]};
+}
+template <typename T>
+struct LevelUV {
+    T uc, uw, vc, vs;
+};
+template <typename T>
+__device__ inline LevelUV<T> load_level_uv(const T *__restrict__ u, const T *__restrict__ v, long o, long c,
+                                           const Neighbours &nb)
+{
+    return LevelUV<T>{u[o + c], u[o + nb.cw], v[o + c], v[o + nb.cs]};
+}
+template <typename T>
+__device__ inline Slots level_slots(double th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2, bool two, double scale,
+                                    int sverdrup, bool south)
+{
+    auto term = [&](T x, double a) { return fma(th, uv_fixed<T>(x, fill, fill2, two), 0.0) * a; };
+    Slots d{+term(x.uc, arc.Ec), -term(x.vc, arc.Nc), -term(x.vs, arc.Ns), +term(x.uw, arc.Ew)};
+    if (sverdrup) d = Slots{d.e * scale, d.n * scale, d.s * scale, d.w * scale};
+    if (!south) d.s = 0.0;
+    return d;
+}
 
 __global__ __launch_bounds__(kBlock) void k_gather_segscan(const int *__restrict__ cell,
                                                            const double *__restrict__ w4,
@@ -29,54 +133,28 @@ __global__ __launch_bounds__(kBlock) void k_gather_segscan(const int *__restrict
     data += (long)blockIdx.y * data_stride;  // blockIdx.y = time step of a multi-step launch
     runsum += (long)blockIdx.y * n;
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & (kWave - 1);
-    double val = 0.0;
+    double val[1] = {0.0};
     int key = -1;
     if (k < n) {
-        // the record stream is read once per launch: non-temporal, so that it does not push the plane sectors its
-        // neighbours gather -- nor the arc lengths the next flux kernel re-reads -- out of the caches (-0.7 % per pass)
-        typedef double dvec2 __attribute__((ext_vector_type(2)));
-        const long c = __builtin_nontemporal_load(cell + k);
-        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
-        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
-        double d0, d1, d2, d3;
-        if (planes == 2) {
-            // the engine's own planes: the south and west slots are copies of the neighbours' north and east values
-            // (field.py:219-223), so only the two signed planes are touched: eU[c-1], eU[c] share a sector and
-            // eV[c-nx] is the eV[c] of the record one row below -- about half the sectors of four separate planes
-            const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
-            const double *eU = data + ncell, *eV = data + 2 * ncell;
-            d1 = eU[c];
-            d2 = eV[c];
-            d0 = j > 0 ? eV[c - nx] : 0.0;               // row 0's south slot is never written (field.py:219)
-            d3 = eU[i > 0 ? c - 1 : c - 1 + nx];         // column 0: periodic copy of column nx-1 (field.py:223)
+        const Record r = load_record(cell, w4, k);
+        Slots d;
+        if (planes == 2) {   // the engine's own planes
+            d = signed_plane_slots(data + ncell, ncell, r.c, neighbours(r.c, nx));
         } else if (planes) {
-            d0 = data[c];
-            d1 = data[ncell + c];
-            d2 = data[2 * ncell + c];
-            d3 = data[3 * ncell + c];
+            d.s = data[r.c], d.e = data[ncell + r.c], d.n = data[2 * ncell + r.c], d.w = data[3 * ncell + r.c];
         } else {
-            const double2 *pd = reinterpret_cast<const double2 *>(data + 4 * c);
+            const double2 *pd = reinterpret_cast<const double2 *>(data + 4 * r.c);
             const double2 da = pd[0], db = pd[1];
-            d0 = da.x; d1 = da.y; d2 = db.x; d3 = db.y;
+            d = Slots{da.y, db.x, da.x, db.y};
         }
-        val = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
-        key = __builtin_nontemporal_load(seg + k);
+        val[0] = weighted_sum(r, d);
+        key = load_key(seg, k);
     }
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const double pv = __shfl_up(val, o, kWave);
-        const int pk = __shfl_up(key, o, kWave);
-        if (lane >= o && pk == key) val += pv;
-    }
-    const int nk = __shfl_down(key, 1, kWave);
-    if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) runsum[k] = val;
+    if (seg_scan(val, key, k, n)) runsum[k] = val[0];
 }
 
-// Stage A for TWO time steps of the engine's own planes at once (the per-step pass takes its whole steps in pairs): the
-// 40-byte record is read once, the same four elements are gathered from both steps' signed planes, and the two weighted
-// sums go through the segmented scan side by side.  Each step's sum is formed and scanned exactly as in k_gather_segscan
-// (planes = 2): bit-identical rows.  uvA / uvB: a step's eU plane, its eV plane right behind it; runsum: 2 * n doubles.
+// Stage A for TWO time steps of the engine's own planes at once (the per-step pass takes its whole steps in pairs): the record
+// is read once and both steps' sums go through seg_scan side by side.  uvA / uvB: a step's [eU | eV]; runsum: 2 * n doubles.
 __global__ __launch_bounds__(kBlock) void k_gather_segscan_pair(const int *__restrict__ cell, const double *__restrict__ w4,
                                                                 const int *__restrict__ seg, long n,
                                                                 const double *__restrict__ uvA,
@@ -84,46 +162,23 @@ __global__ __launch_bounds__(kBlock) void k_gather_segscan_pair(const int *__res
                                                                 double *__restrict__ runsum)
 {
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & (kWave - 1);
-    double va = 0.0, vb = 0.0;
+    double val[2] = {0.0, 0.0};
     int key = -1;
     if (k < n) {
-        typedef double dvec2 __attribute__((ext_vector_type(2)));
-        const long c = __builtin_nontemporal_load(cell + k);
-        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
-        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
-        const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
-        const long cw = i > 0 ? c - 1 : c - 1 + nx;
-        {
-            const double *eU = uvA, *eV = uvA + ncell;
-            const double d1 = eU[c], d2 = eV[c], d0 = j > 0 ? eV[c - nx] : 0.0, d3 = eU[cw];
-            va = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
-        }
-        {
-            const double *eU = uvB, *eV = uvB + ncell;
-            const double d1 = eU[c], d2 = eV[c], d0 = j > 0 ? eV[c - nx] : 0.0, d3 = eU[cw];
-            vb = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
-        }
-        key = __builtin_nontemporal_load(seg + k);
+        const Record r = load_record(cell, w4, k);
+        const Neighbours nb = neighbours(r.c, nx);
+        val[0] = weighted_sum(r, signed_plane_slots(uvA, ncell, r.c, nb));
+        val[1] = weighted_sum(r, signed_plane_slots(uvB, ncell, r.c, nb));
+        key = load_key(seg, k);
     }
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const double pa = __shfl_up(va, o, kWave), pb = __shfl_up(vb, o, kWave);
-        const int pk = __shfl_up(key, o, kWave);
-        if (lane >= o && pk == key) {
-            va += pa;
-            vb += pb;
-        }
-    }
-    const int nk = __shfl_down(key, 1, kWave);
-    if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) {
-        runsum[k] = va;
-        runsum[n + k] = vb;
+    if (seg_scan(val, key, k, n)) {
+        runsum[k] = val[0];
+        runsum[n + k] = val[1];
     }
 }
 
 // Unique-edge form of stage A for the engine's own planes (WeightSet::EdgeEntry): one lane per (segment, plane element)
-// entry -- ONE 16-byte record load and ONE 8-byte gather from [eU | eV] -- then the same wavefront segmented scan.
+// entry -- ONE 16-byte record load and ONE 8-byte gather from [eU | eV] -- then seg_scan.
 // Entries are sorted by (segment, element), so the gathers of neighbouring lanes walk the planes in ascending order.
 __global__ __launch_bounds__(kBlock) void k_gather_edges(const WeightSet::EdgeEntry *__restrict__ ent, long n,
                                                          const double *__restrict__ data, long ncell,
@@ -132,8 +187,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_edges(const WeightSet::EdgeEn
     data += (long)blockIdx.y * data_stride + ncell;   // planes 1 (eU) and 2 (eV) are contiguous: one array of 2*ncell
     runsum += (long)blockIdx.y * n;
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & (kWave - 1);
-    double val = 0.0;
+    double val[1] = {0.0};
     int key = -1;
     if (k < n) {
         typedef int ivec4 __attribute__((ext_vector_type(4)));
@@ -141,17 +195,10 @@ __global__ __launch_bounds__(kBlock) void k_gather_edges(const WeightSet::EdgeEn
         double w;
         const int wbits[2] = {r.z, r.w};
         __builtin_memcpy(&w, wbits, 8);
-        val = w * data[(unsigned)r.x];
+        val[0] = w * data[(unsigned)r.x];
         key = r.y;
     }
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const double pv = __shfl_up(val, o, kWave);
-        const int pk = __shfl_up(key, o, kWave);
-        if (lane >= o && pk == key) val += pv;
-    }
-    const int nk = __shfl_down(key, 1, kWave);
-    if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) runsum[k] = val;
+    if (seg_scan(val, key, k, n)) runsum[k] = val[0];
 }
 
 // one wavefront per target segment: stitch the per-wave run sums of the segment (one per 64-record wave it
@@ -194,22 +241,23 @@ __global__ __launch_bounds__(kBlock) void k_finalize_tr(const int *__restrict__ 
 }
 
 // stages B and C for nrows rows (blockIdx.y): row r stitches the run sums at runsum + r * nrun over the CSR run_start of
-// ws.nseg segments (seg_start for the records, ent_start for the unique-edge entries) and goes to row + r * row_stride
-static void launch_finalize(const WeightSet &ws, const int *run_start, long nrun, const double *runsum,
-                            const int *tr_offsets_dev, int ntransect, double *row, long row_stride, unsigned nrows,
-                            hipStream_t s)
+// the nseg segments (seg_start for the records, ent_start for the unique-edge entries) and goes to row + r * row_stride
+static void launch_finalize(const Transects &tr, const int *run_start, long nrun, const double *runsum, double *row,
+                            long row_stride, unsigned nrows, hipStream_t s)
 {
-    if (ws.nseg > 0) {
-        const unsigned nb = (unsigned)(((long)ws.nseg * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, nrows), dim3(kBlock), 0, s, runsum, run_start, ws.nseg, row, nrun,
-                           row_stride);
+    const int nseg = tr.ws->nseg;
+    if (nseg > 0) {
+        const unsigned nb = (unsigned)(((long)nseg * kWave + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_finalize_seg, dim3(nb, nrows), dim3(kBlock), 0, s, runsum, run_start, nseg, row, nrun, row_stride);
     }
-    if (ntransect > 0) {
-        const unsigned nb = (unsigned)(((long)ntransect * kWave + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_finalize_tr, dim3(nb, nrows), dim3(kBlock), 0, s, tr_offsets_dev, ntransect, ws.nseg, row,
+    if (tr.ntransect > 0) {
+        const unsigned nb = (unsigned)(((long)tr.ntransect * kWave + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_finalize_tr, dim3(nb, nrows), dim3(kBlock), 0, s, tr.tr_offsets_dev, tr.ntransect, nseg, row,
                            row_stride);
     }
 }
+
+static dim3 record_grid(const WeightSet &ws, unsigned ny = 1) { return dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock), ny); }
 
 // "edge_weights" tuning knob.  Default 0: measured in-process on the 65-transect bench batch (tools/ab_pass.py,
 // profiles/r02_ab_pass_edges.txt) the unique-edge form is 0.4 % SLOWER per pass than the records (90 vs 85.5 us per step): a
@@ -223,51 +271,49 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
                     const int *tr_offsets_dev, int ntransect, double *scratch, double *row, hipStream_t s, int nsteps,
                     long data_stride, long row_stride, const int *rec_cells)
 {
+    const Transects tr{&ws, tr_offsets_dev, ntransect};
     const unsigned ny = (unsigned)(nsteps > 1 ? nsteps : 1);
-    if (planes == 2 && ws.ent_start.get() && g_use_edges) {   // the engine's own planes through the unique-edge entries
-        if (ws.nent > 0)
-            hipLaunchKernelGGL(k_gather_edges, dim3((unsigned)((ws.nent + kBlock - 1) / kBlock), ny), dim3(kBlock), 0, s,
-                               ws.ent.get(), ws.nent, data, ncell, scratch, data_stride);
-        launch_finalize(ws, ws.ent_start.get(), ws.nent, scratch, tr_offsets_dev, ntransect, row, row_stride, ny, s);
-        NF_HIP(hipGetLastError());
-        return NF_OK;
-    }
-    if (ws.nrec > 0) {
-        hipLaunchKernelGGL(k_gather_segscan, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock), ny), dim3(kBlock), 0, s,
+    const bool edges = planes == 2 && ws.ent_start.get() && g_use_edges;   // the engine's own planes through the unique edges
+    if (edges && ws.nent > 0)
+        hipLaunchKernelGGL(k_gather_edges, dim3((unsigned)((ws.nent + kBlock - 1) / kBlock), ny), dim3(kBlock), 0, s,
+                           ws.ent.get(), ws.nent, data, ncell, scratch, data_stride);
+    if (!edges && ws.nrec > 0)
+        hipLaunchKernelGGL(k_gather_segscan, record_grid(ws, ny), dim3(kBlock), 0, s,
                            rec_cells ? rec_cells : ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, data, ncell, planes,
                            (unsigned)(nx > 0 ? nx : 1), scratch, data_stride);
-    }
-    launch_finalize(ws, ws.seg_start.get(), ws.nrec, scratch, tr_offsets_dev, ntransect, row, row_stride, ny, s);
+    launch_finalize(tr, edges ? ws.ent_start.get() : ws.seg_start.get(), edges ? ws.nent : ws.nrec, scratch, row, row_stride,
+                    ny, s);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
 
-int launch_integral_pair(const WeightSet &ws, const double *uvA, const double *uvB, long ncell, long nx,
-                         const int *tr_offsets_dev, int ntransect, double *scratch, double *row, long row_stride,
-                         hipStream_t s)
+int launch_integral_pair(const Transects &tr, const double *uvA, const double *uvB, long ncell, long nx, double *scratch,
+                         double *row, long row_stride, hipStream_t s)
 {
+    const WeightSet &ws = *tr.ws;
     if (ws.nrec > 0)
-        hipLaunchKernelGGL(k_gather_segscan_pair, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, uvA, uvB, ncell, (unsigned)(nx > 0 ? nx : 1),
-                           scratch);
-    launch_finalize(ws, ws.seg_start.get(), ws.nrec, scratch, tr_offsets_dev, ntransect, row, row_stride, 2, s);
+        hipLaunchKernelGGL(k_gather_segscan_pair, record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(),
+                           ws.seg.get(), ws.nrec, uvA, uvB, ncell, (unsigned)(nx > 0 ? nx : 1), scratch);
+    launch_finalize(tr, ws.seg_start.get(), ws.nrec, scratch, row, row_stride, 2, s);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
 
-// ---- depth-resolved rows: stage A of the record form, one level at a time, straight from the raw fields ------------------
-// Level z's edge values are formed on the fly exactly as K1 forms them for a field whose only non-zero layer is z:
-// eU(c) = +fma(th[z], fixed(u[z,c]), 0) * arcE[c], eV(c) = -fma(th[z], fixed(v[z,c]), 0) * arcN[c], times the Sverdrup
-// scale; south = eV(c - nx) (0 on row 0), west = eU(c - 1) (periodic on column 0), the weighted sum with K3's association
-// and K3's wavefront segmented scan (the flags of the scan depend on the keys only: computed once for all levels).  A lane
-// owns one record and up to kProfileChunk levels: the 40-byte record and the four arc lengths are read once per chunk, the
-// 4 x LZ gathers of a lane are all in flight together.  runsum: (levels of the launch) x n doubles, level-major.
-template <typename T>
-__device__ inline double profile_fixed(T x, T fill, T fill2, bool two)
+// the launchers that read the raw fields check alike: grid sizes, level range, transects, `per_record` run sums of scratch each
+static int check_raw_step(const char *what, const StepInput &in, const Transects &tr, size_t scratch_len, size_t per_record)
 {
-    return (x != x || x == fill || (two && x == fill2)) ? 0.0 : (double)x;
+    const std::string w(what);
+    NF_REQUIRE(tr.ws && in.ncell > 0 && in.nx > 0 && in.ncell % in.nx == 0 && in.ncell < (1l << 31), NF_ERR_ARG,
+               w + ": bad grid sizes");
+    NF_REQUIRE(in.z0 >= 0 && in.z1 >= in.z0 && tr.ntransect >= 0, NF_ERR_ARG, w + ": bad arguments");
+    NF_REQUIRE(scratch_len >= (size_t)tr.ws->nrec * per_record, NF_ERR_ARG, w + ": scratch too small");
+    return NF_OK;
 }
 
+// ---- depth-resolved rows: one value per level, straight from the raw fields -------------------------------------------
+// A lane owns one record and up to kProfileChunk levels: the 40-byte record and the four arc lengths are read once per chunk,
+// the 4 x LZ gathers of a lane are all in flight together; then level_slots and weighted_sum per level and one seg_scan<LZ>.
+// runsum: (levels of the launch) x n doubles, level-major.
 template <typename T, int LZ>
 __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
                                                             const int *__restrict__ seg, long n, const T *__restrict__ u,
@@ -278,63 +324,26 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
                                                             double scale, int sverdrup, double *__restrict__ runsum)
 {
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & (kWave - 1);
     double val[LZ];
 #pragma unroll
     for (int l = 0; l < LZ; ++l) val[l] = 0.0;
     int key = -1;
     if (k < n) {
-        typedef double dvec2 __attribute__((ext_vector_type(2)));
-        const long c = __builtin_nontemporal_load(cell + k);
-        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
-        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
-        key = __builtin_nontemporal_load(seg + k);
-        const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
-        const bool south = j > 0;
-        const long cs = south ? c - nx : c;             // row 0: no south value (read, then discarded)
-        const long cw = i > 0 ? c - 1 : c - 1 + nx;
-        const double aEc = arcE[c], aNc = arcN[c], aNs = arcN[cs], aEw = arcE[cw];
-        T uc[LZ], uw[LZ], vc[LZ], vs[LZ];
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const Neighbours nb = neighbours(r.c, nx);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        LevelUV<T> x[LZ];
 #pragma unroll
         for (int l = 0; l < LZ; ++l)
-            if (l < nlev) {   // launch-uniform
-                const long o = (long)(z0 + l) * ncell;
-                uc[l] = u[o + c];
-                uw[l] = u[o + cw];
-                vc[l] = v[o + c];
-                vs[l] = v[o + cs];
-            }
+            if (l < nlev) x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);   // nlev is launch-uniform
 #pragma unroll
         for (int l = 0; l < LZ; ++l)
-            if (l < nlev) {
-                const double th = thickness[z0 + l];
-                double d1 = +fma(th, profile_fixed<T>(uc[l], fill, fill2, two), 0.0) * aEc;
-                double d3 = +fma(th, profile_fixed<T>(uw[l], fill, fill2, two), 0.0) * aEw;
-                double d2 = -fma(th, profile_fixed<T>(vc[l], fill, fill2, two), 0.0) * aNc;
-                double d0 = -fma(th, profile_fixed<T>(vs[l], fill, fill2, two), 0.0) * aNs;
-                if (sverdrup) {
-                    d0 *= scale;
-                    d1 *= scale;
-                    d2 *= scale;
-                    d3 *= scale;
-                }
-                if (!south) d0 = 0.0;
-                // the library is built with -ffp-contract=off: the same rounded products and sums as k_gather_segscan
-                val[l] = ((wa.x * d0 + wa.y * d1) + wb.x * d2) + wb.y * d3;
-            }
+            if (l < nlev)
+                val[l] = weighted_sum(r, level_slots<T>(thickness[z0 + l], x[l], arc, fill, fill2, two, scale, sverdrup,
+                                                        nb.south));
     }
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int pk = __shfl_up(key, o, kWave);
-        const bool take = lane >= o && pk == key;
-#pragma unroll
-        for (int l = 0; l < LZ; ++l) {
-            const double pv = __shfl_up(val[l], o, kWave);
-            if (take) val[l] += pv;
-        }
-    }
-    const int nk = __shfl_down(key, 1, kWave);
-    if (k < n && (lane == kWave - 1 || k == n - 1 || nk != key)) {
+    if (seg_scan(val, key, k, n)) {
 #pragma unroll
         for (int l = 0; l < LZ; ++l)
             if (l < nlev) runsum[(long)l * n + k] = val[l];
@@ -344,19 +353,18 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
 template <typename T>
 static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 {
-    const WeightSet &ws = *a.ws;
+    const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    const int two = fill2 == fill2 && !(fill2 == fill);   // K1's rule: a second marker that differs from the first
     for (int zc = in.z0; zc < in.z1; zc += kProfileChunk) {
         const int nlev = in.z1 - zc < kProfileChunk ? in.z1 - zc : kProfileChunk;
-        double *rows = a.prof + (long)zc * a.row_length;
         if (ws.nrec > 0)
-            hipLaunchKernelGGL((k_profile_segscan<T, kProfileChunk>), dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)),
-                               dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u,
-                               (const T *)in.v, in.ncell, (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill,
-                               fill2, two, in.scale, in.sverdrup, a.scratch);
-        launch_finalize(ws, ws.seg_start.get(), ws.nrec, a.scratch, a.tr_offsets_dev, a.ntransect, rows, a.row_length,
+            hipLaunchKernelGGL((k_profile_segscan<T, kProfileChunk>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
+                               ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx,
+                               zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2),
+                               in.scale, in.sverdrup, a.scratch);
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.prof + (long)zc * row_length, row_length,
                         (unsigned)nlev, s);
         NF_HIP(hipGetLastError());
     }
@@ -365,28 +373,41 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 
 int launch_profile(const ProfileArgs &a, hipStream_t s)
 {
-    const StepInput &in = a.in;
-    NF_REQUIRE(a.ws && in.ncell > 0 && in.nx > 0 && in.ncell % in.nx == 0 && in.ncell < (1l << 31), NF_ERR_ARG,
-               "profile: bad grid sizes");
-    NF_REQUIRE(in.z0 >= 0 && in.z1 >= in.z0 && a.row_length == a.ws->nseg + a.ntransect, NF_ERR_ARG, "profile: bad arguments");
-    NF_REQUIRE(a.scratch_len >= (size_t)a.ws->nrec * kProfileChunk, NF_ERR_ARG, "profile: scratch too small");
-    if (a.row_length == 0) return NF_OK;
-    if (in.dtype == NF_F64) return launch_profile_t<double>(a, s);
-    if (in.dtype == NF_F32) return launch_profile_t<float>(a, s);
+    NF_TRY(check_raw_step("profile", a.in, a.tr, a.scratch_len, kProfileChunk));
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (a.in.dtype == NF_F64) return launch_profile_t<double>(a, s);
+    if (a.in.dtype == NF_F32) return launch_profile_t<float>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
 }
 
-// ---- volume transport in tracer classes: the profile kernel's terms, each sent to the row of its face's class ----------------
-// One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are the
-// ones of k_profile_segscan; each is added, in slot order (south, east, north, west), to the lane's accumulator of the row
-// that its own face's class value selects, when that row lies in the window [r0, r0 + nwin).  The accumulators are a column
-// of LDS per lane (a dynamic row index in registers would go to scratch).  Then K3's segmented scan runs once per row of the
-// window.  With one class per level (tau = z) a row gets exactly one level's four terms, added as ((0 + t0) + t1) + t2) + t3:
-// the profile's ((t0 + t1) + t2) + t3, bit for bit.
+// ---- volume transport in tracer classes: level_slots, each term sent to the row of its face's class -------------------
+// One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are
+// level_slots' times their weights; each is added, in slot order (south, east, north, west), to the lane's accumulator of the
+// row that its own face's class value selects, when that row lies in the window [r0, r0 + nwin).  The accumulators are a column
+// of LDS per lane (a dynamic row index in registers would go to scratch).  Then seg_scan_step runs once per row of the
+// window with the one set of flags.  With one class per level (tau = z) a row gets exactly one level's four terms, added as
+// ((0 + t0) + t1) + t2) + t3: weighted_sum's ((t0 + t1) + t2) + t3, bit for bit.
 //   faces: east(c) = (tau[c], tau[c+1]; column nx-1: tau[c+1-nx] when wrap_x, else none), north(c) = (tau[c], tau[c+nx];
 //   last row: none), the west slot is east(cw), the south slot north(cs).
 // LDS: the edges (nedges doubles, padded to even), then nwin x kBlock accumulators.
 constexpr int kClassLevels = 4;   // levels whose 9 gathers are issued together
+
+// the neighbour rule with the east and north cells that the faces of the tracer need (ce, cn: c itself where there is none)
+struct ClassNeighbours : Neighbours {
+    bool has_e, has_n, has_w;
+    long ce, cn;
+};
+__device__ inline ClassNeighbours class_neighbours(long c, unsigned nx, long ncell, int wrap_x)
+{
+    ClassNeighbours nb;
+    static_cast<Neighbours &>(nb) = neighbours(c, nx);
+    nb.has_e = nb.i + 1 < nx || wrap_x;
+    nb.has_n = c + (long)nx < ncell;
+    nb.has_w = nb.i > 0 || wrap_x;
+    nb.ce = nb.i + 1 < nx ? c + 1 : (wrap_x ? c + 1 - (long)nx : c);
+    nb.cn = nb.has_n ? c + nx : c;
+    return nb;
+}
 
 // row of class value x among the n edges in LDS: the number of edges <= x (binary lifting, `top` = the largest power of two
 // <= n: the same number of steps in every lane); no value or NaN: row n + 1
@@ -419,97 +440,68 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
     const int lane = threadIdx.x & (kWave - 1);
     int key = -1;
     if (k < n) {
-        typedef double dvec2 __attribute__((ext_vector_type(2)));
-        const long c = __builtin_nontemporal_load(cell + k);
-        const dvec2 *pw = reinterpret_cast<const dvec2 *>(w4 + 4 * k);
-        const dvec2 wa = __builtin_nontemporal_load(pw), wb = __builtin_nontemporal_load(pw + 1);
-        key = __builtin_nontemporal_load(seg + k);
-        const unsigned j = (unsigned)(c / nx), i = (unsigned)(c - (long)j * nx);
-        const bool south = j > 0;
-        const bool has_e = i + 1 < nx || wrap_x, has_n = c + (long)nx < ncell, has_w = i > 0 || wrap_x;
-        const long cs = south ? c - nx : c;             // row 0: no south value (read, then discarded)
-        const long cw = i > 0 ? c - 1 : c - 1 + nx;
-        const long ce = i + 1 < nx ? c + 1 : (wrap_x ? c + 1 - (long)nx : c);
-        const long cn = has_n ? c + nx : c;
-        const double aEc = arcE[c], aNc = arcN[c], aNs = arcN[cs], aEw = arcE[cw];
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
         auto add = [&](int row, double x) {
-            const int r = row - r0;
-            if (r >= 0 && r < nwin) acc[r * kBlock] += x;
+            const int q = row - r0;
+            if (q >= 0 && q < nwin) acc[q * kBlock] += x;
         };
         for (int z = z0; z < z1; z += kClassLevels) {
             const int nlev = z1 - z < kClassLevels ? z1 - z : kClassLevels;
-            T uc[kClassLevels], uw[kClassLevels], vc[kClassLevels], vs[kClassLevels];
+            LevelUV<T> x[kClassLevels];
             T tc[kClassLevels], te[kClassLevels], tn[kClassLevels], tw[kClassLevels], ts[kClassLevels];
 #pragma unroll
             for (int l = 0; l < kClassLevels; ++l)
                 if (l < nlev) {
                     const long o = (long)(z + l) * ncell;
-                    uc[l] = u[o + c];
-                    uw[l] = u[o + cw];
-                    vc[l] = v[o + c];
-                    vs[l] = v[o + cs];
-                    tc[l] = tau[o + c];
-                    te[l] = tau[o + ce];
-                    tn[l] = tau[o + cn];
-                    tw[l] = tau[o + cw];
-                    ts[l] = tau[o + cs];
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    tc[l] = tau[o + r.c];
+                    te[l] = tau[o + nb.ce];
+                    tn[l] = tau[o + nb.cn];
+                    tw[l] = tau[o + nb.cw];
+                    ts[l] = tau[o + nb.cs];
                 }
 #pragma unroll
             for (int l = 0; l < kClassLevels; ++l)
                 if (l < nlev) {
-                    const double th = thickness[z + l];
-                    double d1 = +fma(th, profile_fixed<T>(uc[l], fill, fill2, two), 0.0) * aEc;
-                    double d3 = +fma(th, profile_fixed<T>(uw[l], fill, fill2, two), 0.0) * aEw;
-                    double d2 = -fma(th, profile_fixed<T>(vc[l], fill, fill2, two), 0.0) * aNc;
-                    double d0 = -fma(th, profile_fixed<T>(vs[l], fill, fill2, two), 0.0) * aNs;
-                    if (sverdrup) {
-                        d0 *= scale;
-                        d1 *= scale;
-                        d2 *= scale;
-                        d3 *= scale;
-                    }
-                    double x;
+                    const Slots d = level_slots<T>(thickness[z + l], x[l], arc, fill, fill2, two, scale, sverdrup, nb.south);
+                    double f;
                     bool h;
-                    if (south) {
-                        h = tr_face_raw<T>(ts[l], tc[l], true, tfill, tfill2, &x);
-                        add(class_row(h, x, e, nedges, top), wa.x * d0);
+                    if (nb.south) {
+                        h = tr_face_raw<T>(ts[l], tc[l], true, tfill, tfill2, &f);
+                        add(class_row(h, f, e, nedges, top), r.wa.x * d.s);
                     }
-                    h = tr_face_raw<T>(tc[l], te[l], has_e, tfill, tfill2, &x);
-                    add(class_row(h, x, e, nedges, top), wa.y * d1);
-                    h = tr_face_raw<T>(tc[l], tn[l], has_n, tfill, tfill2, &x);
-                    add(class_row(h, x, e, nedges, top), wb.x * d2);
-                    h = tr_face_raw<T>(tw[l], tc[l], has_w, tfill, tfill2, &x);
-                    add(class_row(h, x, e, nedges, top), wb.y * d3);
+                    h = tr_face_raw<T>(tc[l], te[l], nb.has_e, tfill, tfill2, &f);
+                    add(class_row(h, f, e, nedges, top), r.wa.y * d.e);
+                    h = tr_face_raw<T>(tc[l], tn[l], nb.has_n, tfill, tfill2, &f);
+                    add(class_row(h, f, e, nedges, top), r.wb.x * d.n);
+                    h = tr_face_raw<T>(tw[l], tc[l], nb.has_w, tfill, tfill2, &f);
+                    add(class_row(h, f, e, nedges, top), r.wb.y * d.w);
                 }
         }
     }
-    // K3's segmented scan, once per row of the window; its flags depend on the keys only
-    unsigned take = 0;
+    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
 #pragma unroll
-    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) {
-        const int pk = __shfl_up(key, o, kWave);
-        if (lane >= o && pk == key) take |= 1u << b;
-    }
-    const int nk = __shfl_down(key, 1, kWave);
-    const bool store = k < n && (lane == kWave - 1 || k == n - 1 || nk != key);
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
+        if (seg_scan_take(key, lane, o)) take |= 1u << b;
+    const bool store = seg_run_end(key, lane, k, n);
     for (int r = 0; r < nwin; ++r) {
-        double val = k < n ? acc[r * kBlock] : 0.0;
+        double val[1] = {k < n ? acc[r * kBlock] : 0.0};
 #pragma unroll
-        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) {
-            const double pv = __shfl_up(val, o, kWave);
-            if (take & (1u << b)) val += pv;
-        }
-        if (store) runsum[(long)r * n + k] = val;
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
+        if (store) runsum[(long)r * n + k] = val[0];
     }
 }
 
 template <typename T>
 static int launch_class_t(const ClassArgs &a, hipStream_t s)
 {
-    const WeightSet &ws = *a.ws;
+    const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    const int two = fill2 == fill2 && !(fill2 == fill);   // K1's rule: a second marker that differs from the first
     int top = 1;
     while (2 * top <= a.nedges) top *= 2;
     const int nrows = a.nedges + 2;
@@ -520,14 +512,14 @@ static int launch_class_t(const ClassArgs &a, hipStream_t s)
             if (lds > 65536)
                 NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_class_segscan<T>, dim3((unsigned)((ws.nrec + kBlock - 1) / kBlock)), dim3(kBlock), lds, s,
-                               ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v,
-                               (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN,
-                               fill, fill2, two, (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.edges,
-                               a.nedges, top, r0, nwin, a.scratch);
+            hipLaunchKernelGGL(k_class_segscan<T>, record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
+                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.tau, in.ncell,
+                               (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
+                               (int)uv_two_markers(fill, fill2), (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale,
+                               in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch);
         }
-        launch_finalize(ws, ws.seg_start.get(), ws.nrec, a.scratch, a.tr_offsets_dev, a.ntransect,
-                        a.rows + (long)r0 * a.row_length, a.row_length, (unsigned)nwin, s);
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
+                        (unsigned)nwin, s);
         NF_HIP(hipGetLastError());
     }
     return NF_OK;
@@ -536,16 +528,12 @@ static int launch_class_t(const ClassArgs &a, hipStream_t s)
 int launch_class_transport(const ClassArgs &a, hipStream_t s)
 {
     const StepInput &in = a.in;
-    NF_REQUIRE(a.ws && in.ncell > 0 && in.nx > 0 && in.ncell % in.nx == 0 && in.ncell < (1l << 31), NF_ERR_ARG,
-               "class transport: bad grid sizes");
-    NF_REQUIRE(in.z0 >= 0 && in.z1 >= in.z0 && a.row_length == a.ws->nseg + a.ntransect, NF_ERR_ARG,
-               "class transport: bad arguments");
     NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "class transport: bad class edges");
     NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "class transport: bad window");
-    NF_REQUIRE(a.scratch_len >= (size_t)a.ws->nrec * a.window, NF_ERR_ARG, "class transport: scratch too small");
+    NF_TRY(check_raw_step("class transport", in, a.tr, a.scratch_len, (size_t)a.window));
     NF_REQUIRE(in.u && in.v && a.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
                "class transport: null argument");
-    if (a.row_length == 0) return NF_OK;
+    if (a.tr.row_length() == 0) return NF_OK;
     if (in.dtype == NF_F64) return launch_class_t<double>(a, s);
     if (in.dtype == NF_F32) return launch_class_t<float>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "class transport: dtype must be NF_F64 or NF_F32");

@@ -49,13 +49,6 @@ __device__ inline TrLanes<T, VEC> tr_load(const T *p)
     return r;
 }
 
-// K1's masking of uo / vo (nf_flux.hip fixed2): NaN or one of the two markers -> 0
-template <typename T>
-__device__ inline double tr_fixed(T x, T fill, T fill2)
-{
-    return (x != x || x == fill || x == fill2) ? 0.0 : (double)x;
-}
-
 }  // namespace
 
 // 256 threads, one chunk of VEC cells per lane: lane c0 = (tile * 256 + tid) * VEC.  ncell % VEC == 0 and nx >= VEC (the
@@ -132,8 +125,8 @@ __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, co
                     const bool has_e = k != kend || wrap_x;
                     const double tfE = tr_face<T>(a, be, has_e, tfill, tfill2, ref);
                     const double tfN = tr_face<T>(a, ln[r].x[k], has_n[k], tfill, tfill2, ref);
-                    accU[k] = fma(th, tr_fixed<T>(lu[r].x[k], fill, fill2) * tfE, accU[k]);
-                    accV[k] = fma(th, tr_fixed<T>(lv[r].x[k], fill, fill2) * tfN, accV[k]);
+                    accU[k] = fma(th, uv_fixed<T>(lu[r].x[k], fill, fill2) * tfE, accU[k]);
+                    accV[k] = fma(th, uv_fixed<T>(lv[r].x[k], fill, fill2) * tfN, accV[k]);
                 }
             }
         pu += (long)UZ * ncell;

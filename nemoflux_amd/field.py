@@ -291,7 +291,7 @@ class Field(object):
         check(lib.nf_field_segment_offsets(ctypes.byref(self._h), self._tr_off.ctypes.data_as(_lib.c_int_p)))
         check(lib.nf_field_row_length(ctypes.byref(self._h), ctypes.byref(n)))
         self._rowlen = n.value
-        self._row = numpy.zeros(max(self._rowlen, 1), numpy.float64)
+        self._row = numpy.zeros(self._row_width, numpy.float64)
         self._row_valid = False
         # coverage > 1 (overlapping cells: a stretch of the line would be counted twice) was refused by build_weights above
         # unless overlappingCells='warn'; coverage < 1 means part of the line lies in no cell: mint only warns there [recall],
@@ -477,6 +477,22 @@ class Field(object):
         row = self._compute(self.timeIndex, readback=readback)
         return [float(row[self._nseg + i]) for i in range(len(self.plis))]
 
+    @property
+    def _row_width(self):
+        """columns of the arrays that hold raw rows: row_length, but never 0 (a Field without transects)"""
+        return max(self._rowlen, 1)
+
+    def _rows_out(self, out, nrows):
+        """The `out=` tensor of the calls that leave raw rows in HBM: (nrows, row_length) float64, contiguous, on the GPU -- the
+        library writes that many doubles through its pointer.  A new one when out is None."""
+        import torch
+        shape = (nrows, self._row_width)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float64, device='cuda')
+        if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
+            raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
+        return out
+
     def _split_rows(self, rows):
         """(transect totals, per-segment sums) of rows laid out [segments | transects] along their last axis."""
         return rows[..., self._nseg:self._nseg + len(self.plis)], rows[..., :self._nseg]
@@ -490,6 +506,8 @@ class Field(object):
         totals and (nt, nseg) per-segment sums.  `out`: optional torch CUDA tensor (nt, row_length) to
         receive the raw rows in HBM (for the RCCL reduce of nemoflux_amd.dist)."""
         import torch
+        if out is not None or self._lazy is None:
+            out = self._rows_out(out, self.nt)
         if self._lazy is not None:
             # file-backed: one step on the GPU, the next one inflating into the other pinned slot (no wrap-around prefetch
             # after the last step)
@@ -497,8 +515,6 @@ class Field(object):
             if out is not None:
                 out.copy_(torch.from_numpy(rows))
             return self._split_rows(rows)
-        if out is None:
-            out = torch.empty((self.nt, max(self._rowlen, 1)), dtype=torch.float64, device='cuda')
         check(lib.nf_field_compute_all_async(ctypes.byref(self._h), ctypes.c_void_p(out.data_ptr())))
         rows = out.cpu().numpy()
         return self._split_rows(rows)
@@ -512,12 +528,11 @@ class Field(object):
         tIndex = int(tIndex)
         self._stage(tIndex, prefetch_next)
         if out is not None:
-            if tuple(out.shape) != (self.nz, max(self._rowlen, 1)) or not out.is_cuda or not out.is_contiguous():
-                raise RuntimeError(f'ERROR: out must be a contiguous CUDA tensor of shape ({self.nz}, {max(self._rowlen, 1)})')
+            out = self._rows_out(out, self.nz)
             check(lib.nf_field_compute_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
             rows = out.cpu().numpy()
         else:
-            rows = numpy.zeros((self.nz, max(self._rowlen, 1)), numpy.float64)
+            rows = numpy.zeros((self.nz, self._row_width), numpy.float64)
             check(lib.nf_field_compute_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return self._split_rows(rows)
 
@@ -589,7 +604,7 @@ class Field(object):
         tIndex = int(tIndex)
         self._stage(tIndex)
         self._stage_tracer(tIndex)
-        row = numpy.zeros(max(self._rowlen, 1), numpy.float64)
+        row = numpy.zeros(self._row_width, numpy.float64)
         check(lib.nf_field_compute_tracer_flux(ctypes.byref(self._h), tIndex, _lib.dptr(row)))
         return self._split_rows(row)
 
@@ -597,12 +612,12 @@ class Field(object):
         """Tracer transport of all nt steps: (nt, ntransect) totals and (nt, nseg) per-segment sums.  `out`: optional torch
         CUDA tensor (nt, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
         import torch
-        if out is not None and (tuple(out.shape) != (self.nt, max(self._rowlen, 1)) or not out.is_cuda or
-                                not out.is_contiguous() or out.dtype != torch.float64):
-            raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape ({self.nt}, {max(self._rowlen, 1)})')
-        if self._lazy is not None or getattr(self, '_tracer_lazy', None) is not None:
+        lazy = self._lazy is not None or getattr(self, '_tracer_lazy', None) is not None
+        if out is not None or not lazy:
+            out = self._rows_out(out, self.nt)
+        if lazy:
             # file-backed fields or tracer: one step at a time through the host
-            rows = numpy.zeros((self.nt, max(self._rowlen, 1)), numpy.float64)
+            rows = numpy.zeros((self.nt, self._row_width), numpy.float64)
             for t in range(self.nt):
                 tot, seg = self.computeTracerFlux(t)
                 rows[t, :self._nseg], rows[t, self._nseg:self._nseg + len(self.plis)] = seg, tot
@@ -610,8 +625,6 @@ class Field(object):
                 out.copy_(torch.from_numpy(rows))
         else:
             self._stage_tracer(0)
-            if out is None:
-                out = torch.empty((self.nt, max(self._rowlen, 1)), dtype=torch.float64, device='cuda')
             check(lib.nf_field_compute_tracer_all_async(ctypes.byref(self._h), ctypes.c_void_p(out.data_ptr())))
             rows = out.cpu().numpy()
         return self._split_rows(rows)
@@ -633,21 +646,18 @@ class Field(object):
         this rank does not own (slab_range) contribute nothing.  Leaves the resident edge fluxes, the running max, the row of
         the last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
         (nedges+2, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        import torch
         tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
         self._stage(tIndex, prefetch_next)
         self._stage_tracer(tIndex)
-        shape = (edges.size + 2, max(self._rowlen, 1))
         if out is not None:
-            if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
-                raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
+            out = self._rows_out(out, edges.size + 2)
             check(lib.nf_field_compute_class_transport_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
             rows = out.cpu().numpy()
         else:
-            rows = numpy.zeros(shape, numpy.float64)
+            rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
             check(lib.nf_field_compute_class_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return self._split_rows(rows)
 

@@ -357,6 +357,34 @@ def test_rows_are_reproducible_and_the_same_for_host_and_hbm_inputs(real):
     assert (numpy.abs(got[0][1:-2]).max(axis=1) > 0).sum() > 20
 
 
+def test_out_tensors_are_checked_by_all_four_calls():
+    """computeAll, computeFluxProfile, computeTracerAll and computeClassTransport write (rows, row_length) doubles through
+    the pointer of `out`: each refuses a float32 and a mis-shaped tensor and accepts the right one"""
+    import torch
+    u = _case('float64')[3]
+    f = _field(*_args('float64', True), **_kw(False))
+    f.setTracer(_on(_level_tau(u.shape, u.dtype), True))
+    f.setClassEdges(LEVEL_EDGES)
+    calls = [(NT, lambda out: f.computeAll(out=out)),
+             (NZ, lambda out: f.computeFluxProfile(1, out=out)),
+             (NT, lambda out: f.computeTracerAll(out=out)),
+             (LEVEL_EDGES.size + 2, lambda out: f.computeClassTransport(1, out=out))]
+    for nrows, call in calls:
+        want = _rows(call(None))
+        assert want.shape == (nrows, f._rowlen)
+        for shape, dtype in (((nrows, f._rowlen), torch.float32), ((nrows + 1, f._rowlen), torch.float64),
+                             ((nrows, f._rowlen + 1), torch.float64), ((nrows * f._rowlen,), torch.float64)):
+            with pytest.raises(RuntimeError, match='out must be'):
+                call(torch.zeros(shape, dtype=dtype, device='cuda'))
+        with pytest.raises(RuntimeError, match='out must be'):
+            call(torch.zeros((nrows, f._rowlen), dtype=torch.float64))                      # not on the GPU
+        with pytest.raises(RuntimeError, match='out must be'):
+            call(torch.zeros((f._rowlen, nrows), dtype=torch.float64, device='cuda').t())   # not contiguous
+        out = torch.full((nrows, f._rowlen), numpy.nan, dtype=torch.float64, device='cuda')
+        assert numpy.array_equal(_rows(call(out)), want)
+        assert numpy.array_equal(out.cpu().numpy(), want)
+
+
 @pytest.mark.parametrize('compact', [False, True])
 @pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
 def test_class_calls_leave_everything_else_alone(compact, resident):
