@@ -299,6 +299,35 @@ int nf_field_compute_tracer_all_async(nf_field **self, double *rows_dev);       
 int nf_field_set_class_edges(nf_field **self, const double *edges, int nedges);
 int nf_field_compute_class_transport(nf_field **self, long tIndex, double *rows_host);        /* (nedges+2, row_length) */
 int nf_field_compute_class_transport_async(nf_field **self, long tIndex, double *rows_dev);   /* HBM, field's stream */
+/* Depth- and class-resolved tracer transports: the two forms above with the tracer of nf_field_set_tracer carried by the flow.
+ * Every per-level term fma(th_z, fixed(x), 0) * arc of nf_field_compute_profile becomes fma(th_z, fixed(x) * tf, 0) * arc, tf
+ * the face value of the tracer block (markers, reference and wrap_x included) at the slot's own face: east slot = east face
+ * of the cell, north slot = its north face, west slot = east face of the west cell, south slot = north face of the south cell.
+ * That is one level of the tracer transport's accumulation, so tau == ref + 1 gives the volume forms bit for bit, and level
+ * z's row of the tracer profile is the nf_field_compute_tracer_flux row of a field whose only layer with a thickness is z.
+ * Tracer profile: prof (nz, row_length), row z = [segments | transects] of the tracer transport of level z alone; levels this
+ * rank does not own get exact zeros; the sum over z is the tracer row up to rounding. */
+int nf_field_compute_tracer_profile(nf_field **self, long tIndex, double *prof_host);        /* synchronous, host */
+int nf_field_compute_tracer_profile_async(nf_field **self, long tIndex, double *prof_dev);   /* HBM, on the field's stream */
+/* Class tracer: a second, optional tracer at T-points (potential density sigma) that gives the faces their class value
+ * instead of the tracer of nf_field_set_tracer, which is then only carried (heat by density class).  Same (nt,nz,ny,nx) and
+ * dtype as uo/vo (else NF_ERR_ARG, the message naming both; set_uv first: NF_ERR_STATE); host (staged per step into a buffer
+ * of its own, owned levels only) or HBM; its own two missing markers; no reference; wrap_x is the tracer's.  When it is set,
+ * nf_field_compute_class_transport* bin by it too (MOC(sigma) and heat-by-sigma from one setup); tracer == NULL goes back to
+ * "the class field is the tracer" and forgets the markers.  Setting the tracer itself here, with its markers, gives the rows
+ * of not setting it, bit for bit.  The setters change neither a captured pass nor any resident array. */
+int nf_field_set_class_tracer(nf_field **self, const void *tracer, long nt, int dtype, int on_device, double fill_value);
+int nf_field_set_class_tracer_missing_value(nf_field **self, double missing_value);  /* NaN = none */
+/* Tracer transport in classes: the rows of nf_field_compute_class_transport with every term times tf of the carried tracer at
+ * its own face; the row is chosen by the class field (the class tracer when set, else the tracer itself, without its
+ * reference).  A face whose carried tracer is missing on both sides adds 0 to the row of its class.  Same accumulation order
+ * (levels ascending, slots south, east, north, west), windows and reduction as the volume form: no atomics, bitwise
+ * reproducible, independent of the window; class field = level index with edges -0.5, 0.5, ... gives the tracer profile bit
+ * for bit, and the sum of all rows is the tracer row up to rounding.  Owned levels only; steps this rank does not touch get
+ * exact zeros.  Compute before set_tracer or set_class_edges: NF_ERR_STATE.  None of the calls of this block changes the
+ * resident planes, |.| arrays, running max, last row, tracer planes or a captured pass. */
+int nf_field_compute_class_tracer_transport(nf_field **self, long tIndex, double *rows_host);        /* (nedges+2, row_length) */
+int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, double *rows_dev);   /* HBM, field's stream */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

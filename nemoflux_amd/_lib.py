@@ -127,6 +127,12 @@ _sig('nf_field_compute_tracer_all_async', [_pp, ctypes.c_void_p])
 _sig('nf_field_set_class_edges', [_pp, c_double_p, ctypes.c_int])
 _sig('nf_field_compute_class_transport', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_class_transport_async', [_pp, ctypes.c_long, ctypes.c_void_p])
+_sig('nf_field_compute_tracer_profile', [_pp, ctypes.c_long, c_double_p])
+_sig('nf_field_compute_tracer_profile_async', [_pp, ctypes.c_long, ctypes.c_void_p])
+_sig('nf_field_set_class_tracer', [_pp, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double])
+_sig('nf_field_set_class_tracer_missing_value', [_pp, ctypes.c_double])
+_sig('nf_field_compute_class_tracer_transport', [_pp, ctypes.c_long, c_double_p])
+_sig('nf_field_compute_class_tracer_transport_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_read_step', [_pp, c_double_p, c_double_p, c_double_p, c_double_p])
 _sig('nf_field_reset_max', [_pp])
 _sig('nf_field_get_arclengths', [_pp, c_double_p])

@@ -122,6 +122,16 @@ struct nf_field {
     double tau_ref = 0.0;
     int tau_wrap = 1;
     DevArray<char> stage_tau;   // host-resident tracer: the owned levels of one step
+    // class tracer at T-points (nf_field_set_class_tracer*): the field whose classes the class calls bin by; nullptr: the
+    // tracer above.  No reference; the wrap rule is the tracer's.  Its setters change neither `version` nor a captured pass.
+    const void *sig = nullptr;
+    long sig_nt = 0;
+    int sig_dtype = NF_F64, sig_on_device = 1;
+    double sig_fill = std::numeric_limits<double>::quiet_NaN();
+    double sig_fill2 = std::numeric_limits<double>::quiet_NaN();
+    DevArray<char> stage_sig;   // host-resident class tracer: the owned levels of one step, sized in bytes like stage_tau
+    // tracer profile (nf_field_compute_tracer_profile): the run sums of one chunk (ws.nrec * tracer_profile_chunk(dtype))
+    DevArray<double> tprof_scratch;
     // class transport (nf_field_set_class_edges): the edges on the host, uploaded by the next compute after a change; the run
     // sums of one window of rows (ws.nrec * window, allocated on first use, dropped with the weights)
     std::vector<double> class_edges;
@@ -415,14 +425,18 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
 }
 
 // The opening of the calls that reduce the raw fields of step t into `nrows` rows at rows_dev (`what` prefixes the messages):
-// checks the time index and, where a tracer is read, its dtype and nt; *lv: the levels to run the kernels on.  None when a row
+// checks the time index and, where a tracer is read (tracer = 1; 2: the class field too), its dtype and nt; *lv: the levels to run the kernels on.  None when a row
 // is empty or this rank owns no slab of step t: its rows are then exact zeros, so that the ranks' rows add up to the full ones.
-static int field_raw_step_begin(nf_field *f, const char *what, long t, bool tracer, double *rows_dev, size_t nrows, Levels *lv)
+static int field_raw_step_begin(nf_field *f, const char *what, long t, int tracer, double *rows_dev, size_t nrows, Levels *lv)
 {
     const std::string w(what);
     NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, w + ": time index out of range");
     NF_REQUIRE(!tracer || f->tau_dtype == f->uv_dtype, NF_ERR_ARG, w + ": the tracer's dtype differs from the dtype of uo/vo");
     NF_REQUIRE(!tracer || f->tau_nt == f->nt, NF_ERR_ARG, w + ": the tracer's nt differs from the nt of uo/vo");
+    if (tracer == 2 && f->sig) {   // a call that reads the class field
+        NF_REQUIRE(f->sig_dtype == f->uv_dtype, NF_ERR_ARG, w + ": the class tracer's dtype differs from the dtype of uo/vo");
+        NF_REQUIRE(f->sig_nt == f->nt, NF_ERR_ARG, w + ": the class tracer's nt differs from the nt of uo/vo");
+    }
     const size_t rowlen = field_row_length(f);
     *lv = rowlen > 0 ? field_levels(f, t) : Levels{};
     if (rowlen > 0 && lv->z1 <= lv->z0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * nrows, f->stream));
@@ -443,22 +457,29 @@ static int field_tracer_input(nf_field *f, long t, Levels lv, Args *a)
 // Depth-resolved rows of step t on the field's stream: prof_dev (nz, row_length), row z = the flux carried by level z alone.
 // Reads the raw fields and the records; leaves the resident planes, |.| arrays, running max, version and a captured pass
 // alone.  Levels this rank does not own get zeros.  The caller has checked field_ready (with the weights).
-static int field_profile_async(nf_field *f, long t, double *prof_dev)
+// tracer = true: every term times the carried tracer at its face (nf_field_compute_tracer_profile), with a scratch of its own.
+static int field_profile_async(nf_field *f, long t, double *prof_dev, bool tracer = false)
 {
     Levels lv;
-    NF_TRY(field_raw_step_begin(f, "compute_profile", t, false, prof_dev, (size_t)f->nz, &lv));
+    NF_TRY(field_raw_step_begin(f, tracer ? "compute_tracer_profile" : "compute_profile", t, tracer ? 1 : 0, prof_dev,
+                                (size_t)f->nz, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     const size_t rowlen = field_row_length(f);
     if (lv.z0 > 0) NF_HIP(hipMemsetAsync(prof_dev, 0, sizeof(double) * rowlen * (size_t)lv.z0, f->stream));   // not owned
     if (lv.z1 < f->nz)
         NF_HIP(hipMemsetAsync(prof_dev + (size_t)lv.z1 * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nz - lv.z1),
                               f->stream));
-    NF_TRY(f->prof_scratch.reserve((size_t)f->ws.nrec * kProfileChunk));
+    DevArray<double> &scratch = tracer ? f->tprof_scratch : f->prof_scratch;
+    NF_TRY(scratch.reserve((size_t)f->ws.nrec * (tracer ? tracer_profile_chunk(f->uv_dtype) : kProfileChunk)));
     ProfileArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
+    if (tracer) {
+        NF_TRY(field_tracer_input(f, t, lv, &a));
+        a.ref = f->tau_ref;
+    }
     a.tr = field_transects(f);
-    a.scratch = f->prof_scratch.get();
-    a.scratch_len = f->prof_scratch.size();
+    a.scratch = scratch.get();
+    a.scratch_len = scratch.size();
     a.prof = prof_dev;
     return launch_profile(a, f->stream);
 }
@@ -470,7 +491,7 @@ static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
 {
     NF_TRY(field_ready(f, "compute_tracer", true));
     Levels lv;
-    NF_TRY(field_raw_step_begin(f, "compute_tracer", t, true, row_dev, 1, &lv));
+    NF_TRY(field_raw_step_begin(f, "compute_tracer", t, 1, row_dev, 1, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     TracerArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
@@ -494,11 +515,14 @@ static int field_class_ready(const nf_field *f, const char *what)
 // Volume transport in tracer classes of step t on the field's stream: rows_dev (nedges + 2, row_length), written whole.
 // Owned levels only, exact zeros for a step this rank does not touch.  Reads the raw fields, the tracer and the records; the
 // resident planes, |.| arrays, running max, last row, tracer planes, version and a captured pass stay as they are.
-static int field_class_step_async(nf_field *f, long t, double *rows_dev)
+// The class field is the class tracer when one is set, else the tracer.  carry = true: the transport of the tracer instead
+// of the volume (nf_field_compute_class_tracer_transport).
+static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool carry = false)
 {
     const int nedges = (int)f->class_edges.size();
     Levels lv;
-    NF_TRY(field_raw_step_begin(f, "compute_class_transport", t, true, rows_dev, (size_t)nedges + 2, &lv));
+    NF_TRY(field_raw_step_begin(f, carry ? "compute_class_tracer_transport" : "compute_class_transport", t, 2, rows_dev,
+                                (size_t)nedges + 2, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     if (f->class_edges_stale) {
         // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
@@ -513,6 +537,17 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev)
     ClassArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
     NF_TRY(field_tracer_input(f, t, lv, &a));
+    if (carry) {   // the tracer is carried ...
+        a.carry = a.tau;
+        a.cfill = a.tfill;
+        a.cfill2 = a.tfill2;
+        a.ref = f->tau_ref;
+    }
+    if (f->sig) {   // ... and binned by the class tracer
+        NF_TRY(field_stage(f, f->sig, f->sig_on_device, t, lv, &f->stage_sig, &a.tau));
+        a.tfill = f->sig_fill;
+        a.tfill2 = f->sig_fill2;
+    }
     a.edges = f->class_edges_dev.get();
     a.nedges = nedges;
     a.window = window;
@@ -872,6 +907,7 @@ try {
     }
     f->weights_built = false;
     f->prof_scratch.reset();
+    f->tprof_scratch.reset();
     f->class_scratch.reset();
     const int bw = build_weights(f->geo.xy.get(), f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
                                  f->skip_unsupported, f->overlap_warn, nullptr, f->nx);
@@ -1163,6 +1199,92 @@ try {
     NF_TRY(field_class_ready(f, "nf_field_compute_class_transport_async"));
     NF_NEED_DEVICE();
     return field_class_step_async(f, tIndex, rows_dev);
+}
+NF_API_CATCH
+
+int nf_field_compute_tracer_profile(nf_field **self, long tIndex, double *prof_host)
+try {
+    NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_tracer_profile: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_profile: set_tracer first");
+    NF_TRY(field_ready(f, "compute_tracer_profile", true));
+    NF_NEED_DEVICE();
+    const size_t n = (size_t)f->nz * field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, prof_host, [&](double *prof) { return field_profile_async(f, tIndex, prof, true); });
+}
+NF_API_CATCH
+
+int nf_field_compute_tracer_profile_async(nf_field **self, long tIndex, double *prof_dev)
+try {
+    NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_tracer_profile_async: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_profile_async: set_tracer first");
+    NF_TRY(field_ready(f, "compute_tracer_profile", true));
+    NF_NEED_DEVICE();
+    return field_profile_async(f, tIndex, prof_dev, true);
+}
+NF_API_CATCH
+
+int nf_field_set_class_tracer(nf_field **self, const void *tracer, long nt, int dtype, int on_device, double fill_value)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_class_tracer: null field");
+    nf_field *f = *self;
+    if (!tracer) {   // back to "the class field is the carried tracer"
+        f->sig = nullptr;
+        f->sig_nt = 0;
+        f->sig_fill = f->sig_fill2 = std::numeric_limits<double>::quiet_NaN();
+        return NF_OK;
+    }
+    NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_class_tracer: dtype must be NF_F64/NF_F32");
+    NF_REQUIRE(f->u && f->v, NF_ERR_STATE, "nf_field_set_class_tracer: set_uv first");
+    if (dtype != f->uv_dtype) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "nf_field_set_class_tracer: the class tracer's dtype is %s, uo/vo are %s",
+                 dtype == NF_F32 ? "float32" : "float64", f->uv_dtype == NF_F32 ? "float32" : "float64");
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    if (nt != f->nt) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "nf_field_set_class_tracer: the class tracer has nt = %ld time steps, uo/vo have %ld", nt, f->nt);
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    f->sig = tracer;
+    f->sig_nt = nt;
+    f->sig_dtype = dtype;
+    f->sig_on_device = on_device ? 1 : 0;
+    f->sig_fill = fill_value;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_class_tracer_missing_value(nf_field **self, double missing_value)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_class_tracer_missing_value: null field");
+    (*self)->sig_fill2 = missing_value;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_class_tracer_transport(nf_field **self, long tIndex, double *rows_host)
+try {
+    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_tracer_transport: null argument");
+    nf_field *f = *self;
+    NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport"));
+    NF_NEED_DEVICE();
+    const size_t n = (f->class_edges.size() + 2) * (size_t)field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows, true); });
+}
+NF_API_CATCH
+
+int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, double *rows_dev)
+try {
+    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_tracer_transport_async: null argument");
+    nf_field *f = *self;
+    NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport_async"));
+    NF_NEED_DEVICE();
+    return field_class_step_async(f, tIndex, rows_dev, true);
 }
 NF_API_CATCH
 

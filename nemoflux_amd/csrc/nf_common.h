@@ -342,13 +342,23 @@ struct StepInput {
 // Depth-resolved rows (nf_field_compute_profile): the per-level form of the record path of K3, reading the raw fields of
 // one time step.  prof: (nz, row_length) doubles; the kernels write rows [z0, z1) only.  Levels are processed
 // kProfileChunk at a time: scratch holds the run sums of one chunk, ws.nrec * kProfileChunk doubles.
+// With a carried tracer (tau != nullptr; nf_field_compute_tracer_profile) every term is multiplied by tr_face of the tracer at
+// its own face, as one level of the tracer transport: 4 + 5 gathers per level, kTracerProfileChunk levels at a time (float64)
+// or kTracerProfileChunkF32 (float32: half the registers per gathered value): tracer_profile_chunk(dtype), measured.
 constexpr int kProfileChunk = 8;
+constexpr int kTracerProfileChunk = 4;
+constexpr int kTracerProfileChunkF32 = 8;
+inline int tracer_profile_chunk(int dtype) { return dtype == NF_F32 ? kTracerProfileChunkF32 : kTracerProfileChunk; }
 struct ProfileArgs {
     StepInput in;
     Transects tr;
     double *scratch = nullptr;
     size_t scratch_len = 0;
     double *prof = nullptr;
+    const void *tau = nullptr;   // the carried tracer of the time step, (nz, ncell) of the field dtype; nullptr: volume rows
+    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
+    double ref = 0.0;
+    int wrap_x = 1;
 };
 int launch_profile(const ProfileArgs &a, hipStream_t s);
 
@@ -419,6 +429,12 @@ struct ClassArgs {
     double *scratch = nullptr;
     size_t scratch_len = 0;
     double *rows = nullptr;      // (nedges + 2, row_length)
+    // tracer transport in classes (nf_field_compute_class_tracer_transport): every term times tr_face of the carried tracer
+    // at its own face.  nullptr: volume transport.  The carried tracer may be the class field itself (carry == tau with the
+    // same markers: one set of gathers) or another array; it shares wrap_x with the class field.
+    const void *carry = nullptr;
+    double cfill = __builtin_nan(""), cfill2 = __builtin_nan("");
+    double ref = 0.0;
 };
 int launch_class_transport(const ClassArgs &a, hipStream_t s);
 

@@ -112,15 +112,86 @@ __device__ inline LevelUV<T> load_level_uv(const T *__restrict__ u, const T *__r
 {
     return LevelUV<T>{u[o + c], u[o + nb.cw], v[o + c], v[o + nb.cs]};
 }
+// The carried-tracer form multiplies every masked velocity by the tracer at the slot's own face (FaceTf: east face of c, north
+// face of c, north face of cs, east face of cw): fma(th, fixed(x) * tf, 0) * arc, one level of k_tracer_flux's accumulation.
+struct FaceTf { double e, n, s, w; };
+template <typename T, bool TR>
+__device__ inline Slots level_slots_tf(double th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2, bool two, double scale,
+                                       int sverdrup, bool south, const FaceTf &tf)
+{
+    auto term = [&](T x, double a, double f) {
+        const double xf = uv_fixed<T>(x, fill, fill2, two);
+        return fma(th, TR ? xf * f : xf, 0.0) * a;
+    };
+    Slots d{+term(x.uc, arc.Ec, tf.e), -term(x.vc, arc.Nc, tf.n), -term(x.vs, arc.Ns, tf.s), +term(x.uw, arc.Ew, tf.w)};
+    if (sverdrup) d = Slots{d.e * scale, d.n * scale, d.s * scale, d.w * scale};
+    if (!south) d.s = 0.0;
+    return d;
+}
 template <typename T>
 __device__ inline Slots level_slots(double th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2, bool two, double scale,
                                     int sverdrup, bool south)
 {
-    auto term = [&](T x, double a) { return fma(th, uv_fixed<T>(x, fill, fill2, two), 0.0) * a; };
-    Slots d{+term(x.uc, arc.Ec), -term(x.vc, arc.Nc), -term(x.vs, arc.Ns), +term(x.uw, arc.Ew)};
-    if (sverdrup) d = Slots{d.e * scale, d.n * scale, d.s * scale, d.w * scale};
-    if (!south) d.s = 0.0;
-    return d;
+    return level_slots_tf<T, false>(th, x, arc, fill, fill2, two, scale, sverdrup, south, FaceTf{});
+}
+
+// The neighbour rule with the east and north cells that the faces of a tracer need (ce, cn: c itself where there is none).
+//   faces: east(c) = (tau[c], tau[c+1]; column nx-1: tau[c+1-nx] when wrap_x, else none), north(c) = (tau[c], tau[c+nx];
+//   last row: none), the west slot is east(cw), the south slot north(cs).
+struct ClassNeighbours : Neighbours {
+    bool has_e, has_n, has_w;
+    long ce, cn;
+};
+__device__ inline ClassNeighbours class_neighbours(long c, unsigned nx, long ncell, int wrap_x)
+{
+    ClassNeighbours nb;
+    static_cast<Neighbours &>(nb) = neighbours(c, nx);
+    nb.has_e = nb.i + 1 < nx || wrap_x;
+    nb.has_n = c + (long)nx < ncell;
+    nb.has_w = nb.i > 0 || wrap_x;
+    nb.ce = nb.i + 1 < nx ? c + 1 : (wrap_x ? c + 1 - (long)nx : c);
+    nb.cn = nb.has_n ? c + nx : c;
+    return nb;
+}
+
+// One level of a tracer around a record's cell: the five values that its four faces need, in the order they are loaded
+template <typename T>
+struct LevelTau {
+    T c, e, n, w, s;
+};
+template <typename T>
+__device__ inline LevelTau<T> load_level_tau(const T *__restrict__ tau, long o, long c, const ClassNeighbours &nb)
+{
+    return LevelTau<T>{tau[o + c], tau[o + nb.ce], tau[o + nb.cn], tau[o + nb.cw], tau[o + nb.cs]};
+}
+// the carried tracer of the tracer forms: its step base, its two markers, its reference and the wrap rule of its faces
+template <typename T>
+struct TauIn {
+    const T *tau;
+    T m1, m2;
+    double ref;
+    int wrap_x;
+};
+// the trailing arguments of a kernel that has a volume form (none) and a carried-tracer form (one TauIn)
+template <typename T>
+__device__ inline TauIn<T> tau_in() { return TauIn<T>{}; }
+template <typename T>
+__device__ inline TauIn<T> tau_in(const TauIn<T> &ti) { return ti; }
+// tr_face at the four slots' faces.  Row 0 has no south face: cs = c there and level_slots_tf discards the slot.
+template <typename T>
+__device__ inline FaceTf level_tf(const LevelTau<T> &t, const ClassNeighbours &nb, const TauIn<T> &ti)
+{
+    return FaceTf{tr_face<T>(t.c, t.e, nb.has_e, ti.m1, ti.m2, ti.ref), tr_face<T>(t.c, t.n, nb.has_n, ti.m1, ti.m2, ti.ref),
+                  tr_face<T>(t.s, t.c, true, ti.m1, ti.m2, ti.ref), tr_face<T>(t.w, t.c, nb.has_w, ti.m1, ti.m2, ti.ref)};
+}
+// the neighbour rule a form needs: the volume forms' (TR = false) or the one with the tracer's faces
+template <bool TR>
+__device__ inline auto step_neighbours(long c, unsigned nx, long ncell, int wrap_x)
+{
+    if constexpr (TR)
+        return class_neighbours(c, nx, ncell, wrap_x);
+    else
+        return neighbours(c, nx);
 }
 
 __global__ __launch_bounds__(kBlock) void k_gather_segscan(const int *__restrict__ cell,
@@ -311,18 +382,23 @@ static int check_raw_step(const char *what, const StepInput &in, const Transects
 }
 
 // ---- depth-resolved rows: one value per level, straight from the raw fields -------------------------------------------
-// A lane owns one record and up to kProfileChunk levels: the 40-byte record and the four arc lengths are read once per chunk,
-// the 4 x LZ gathers of a lane are all in flight together; then level_slots and weighted_sum per level and one seg_scan<LZ>.
-// runsum: (levels of the launch) x n doubles, level-major.
-template <typename T, int LZ>
+// A lane owns one record and up to LZ levels: the 40-byte record and the four arc lengths are read once per chunk, the
+// 4 x LZ gathers of a lane (4 + 5 with a carried tracer, TR) are all in flight together; then level_slots_tf and weighted_sum
+// per level and one seg_scan<LZ>.  runsum: (levels of the launch) x n doubles, level-major.
+// The volume form takes no trailing argument, the carried-tracer form (row z = the tracer transport of level z alone) one
+// TauIn<T>: TI is empty or TauIn<T>.
+template <typename T, int LZ, typename... TI>
 __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
                                                             const int *__restrict__ seg, long n, const T *__restrict__ u,
                                                             const T *__restrict__ v, long ncell, unsigned nx, int z0,
                                                             int nlev, const double *__restrict__ thickness,
                                                             const double *__restrict__ arcE,
                                                             const double *__restrict__ arcN, T fill, T fill2, int two,
-                                                            double scale, int sverdrup, double *__restrict__ runsum)
+                                                            double scale, int sverdrup, double *__restrict__ runsum,
+                                                            TI... tracer)
 {
+    constexpr bool TR = sizeof...(TI) > 0;
+    const TauIn<T> ti = tau_in<T>(tracer...);
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
     double val[LZ];
 #pragma unroll
@@ -331,17 +407,24 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
     if (k < n) {
         const Record r = load_record(cell, w4, k);
         key = load_key(seg, k);
-        const Neighbours nb = neighbours(r.c, nx);
+        const auto nb = step_neighbours<TR>(r.c, nx, ncell, ti.wrap_x);
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
         LevelUV<T> x[LZ];
+        LevelTau<T> tt[TR ? LZ : 1];
 #pragma unroll
         for (int l = 0; l < LZ; ++l)
-            if (l < nlev) x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);   // nlev is launch-uniform
+            if (l < nlev) {   // nlev is launch-uniform
+                x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);
+                if constexpr (TR) tt[l] = load_level_tau(ti.tau, (long)(z0 + l) * ncell, r.c, nb);
+            }
 #pragma unroll
         for (int l = 0; l < LZ; ++l)
-            if (l < nlev)
-                val[l] = weighted_sum(r, level_slots<T>(thickness[z0 + l], x[l], arc, fill, fill2, two, scale, sverdrup,
-                                                        nb.south));
+            if (l < nlev) {
+                FaceTf tf{};
+                if constexpr (TR) tf = level_tf(tt[l], nb, ti);
+                val[l] = weighted_sum(r, level_slots_tf<T, TR>(thickness[z0 + l], x[l], arc, fill, fill2, two, scale, sverdrup,
+                                                               nb.south, tf));
+            }
     }
     if (seg_scan(val, key, k, n)) {
 #pragma unroll
@@ -350,20 +433,30 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
     }
 }
 
-template <typename T>
+
+template <typename T, bool TR>
 static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 {
+    constexpr int chunk = !TR ? kProfileChunk : sizeof(T) == 4 ? kTracerProfileChunkF32 : kTracerProfileChunk;
     const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
     const long row_length = a.tr.row_length();
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    for (int zc = in.z0; zc < in.z1; zc += kProfileChunk) {
-        const int nlev = in.z1 - zc < kProfileChunk ? in.z1 - zc : kProfileChunk;
-        if (ws.nrec > 0)
-            hipLaunchKernelGGL((k_profile_segscan<T, kProfileChunk>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
-                               ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx,
-                               zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2),
-                               in.scale, in.sverdrup, a.scratch);
+    for (int zc = in.z0; zc < in.z1; zc += chunk) {
+        const int nlev = in.z1 - zc < chunk ? in.z1 - zc : chunk;
+        if (ws.nrec > 0) {
+            if constexpr (TR)
+                hipLaunchKernelGGL((k_profile_segscan<T, chunk, TauIn<T>>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
+                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
+                                   (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2,
+                                   (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, a.scratch,
+                                   TauIn<T>{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0});
+            else
+                hipLaunchKernelGGL((k_profile_segscan<T, chunk>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
+                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
+                                   (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2,
+                                   (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, a.scratch);
+        }
         launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.prof + (long)zc * row_length, row_length,
                         (unsigned)nlev, s);
         NF_HIP(hipGetLastError());
@@ -373,10 +466,11 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 
 int launch_profile(const ProfileArgs &a, hipStream_t s)
 {
-    NF_TRY(check_raw_step("profile", a.in, a.tr, a.scratch_len, kProfileChunk));
+    const bool tr = a.tau != nullptr;
+    NF_TRY(check_raw_step("profile", a.in, a.tr, a.scratch_len, tr ? tracer_profile_chunk(a.in.dtype) : kProfileChunk));
     if (a.tr.row_length() == 0) return NF_OK;
-    if (a.in.dtype == NF_F64) return launch_profile_t<double>(a, s);
-    if (a.in.dtype == NF_F32) return launch_profile_t<float>(a, s);
+    if (a.in.dtype == NF_F64) return tr ? launch_profile_t<double, true>(a, s) : launch_profile_t<double, false>(a, s);
+    if (a.in.dtype == NF_F32) return tr ? launch_profile_t<float, true>(a, s) : launch_profile_t<float, false>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
 }
 
@@ -390,24 +484,11 @@ int launch_profile(const ProfileArgs &a, hipStream_t s)
 //   faces: east(c) = (tau[c], tau[c+1]; column nx-1: tau[c+1-nx] when wrap_x, else none), north(c) = (tau[c], tau[c+nx];
 //   last row: none), the west slot is east(cw), the south slot north(cs).
 // LDS: the edges (nedges doubles, padded to even), then nwin x kBlock accumulators.
-constexpr int kClassLevels = 4;   // levels whose 9 gathers are issued together
-
-// the neighbour rule with the east and north cells that the faces of the tracer need (ce, cn: c itself where there is none)
-struct ClassNeighbours : Neighbours {
-    bool has_e, has_n, has_w;
-    long ce, cn;
-};
-__device__ inline ClassNeighbours class_neighbours(long c, unsigned nx, long ncell, int wrap_x)
-{
-    ClassNeighbours nb;
-    static_cast<Neighbours &>(nb) = neighbours(c, nx);
-    nb.has_e = nb.i + 1 < nx || wrap_x;
-    nb.has_n = c + (long)nx < ncell;
-    nb.has_w = nb.i > 0 || wrap_x;
-    nb.ce = nb.i + 1 < nx ? c + 1 : (wrap_x ? c + 1 - (long)nx : c);
-    nb.cn = nb.has_n ? c + nx : c;
-    return nb;
-}
+// CARRY: the carried-tracer form, every term times tr_face of the carried tracer at its own face (level_slots_tf).  TWO: the
+// class field and the carried tracer are different arrays (5 more gathers per level); otherwise the one set of values serves
+// both.
+constexpr int kClassLevels = 4;        // levels whose 9 gathers are issued together (volume form, one-tracer carry form)
+constexpr int kClassLevelsTwo = 4;     // ... whose 14 gathers are (carry form with a class field of its own)
 
 // row of class value x among the n edges in LDS: the number of edges <= x (binary lifting, `top` = the largest power of two
 // <= n: the same number of steps in every lane); no value or NaN: row n + 1
@@ -420,7 +501,8 @@ __device__ inline int class_row(bool has, double x, const double *e, int n, int 
     return pos;
 }
 
-template <typename T>
+// TI: empty (volume form; TWO = false) or TauIn<T>, the carried tracer; tau, tfill, tfill2 are the class field's
+template <typename T, bool TWO, typename... TI>
 __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
                                                           const int *__restrict__ seg, long n, const T *__restrict__ u,
                                                           const T *__restrict__ v, const T *__restrict__ tau, long ncell,
@@ -428,8 +510,12 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
                                                           const double *__restrict__ arcE, const double *__restrict__ arcN,
                                                           T fill, T fill2, int two, T tfill, T tfill2, int wrap_x,
                                                           double scale, int sverdrup, const double *__restrict__ edges,
-                                                          int nedges, int top, int r0, int nwin, double *__restrict__ runsum)
+                                                          int nedges, int top, int r0, int nwin, double *__restrict__ runsum,
+                                                          TI... tracer)
 {
+    constexpr bool CARRY = sizeof...(TI) > 0;
+    constexpr int CL = TWO ? kClassLevelsTwo : kClassLevels;
+    const TauIn<T> ti = tau_in<T>(tracer...);
     extern __shared__ double class_lds[];
     double *e = class_lds;
     double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
@@ -448,12 +534,13 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
             const int q = row - r0;
             if (q >= 0 && q < nwin) acc[q * kBlock] += x;
         };
-        for (int z = z0; z < z1; z += kClassLevels) {
-            const int nlev = z1 - z < kClassLevels ? z1 - z : kClassLevels;
-            LevelUV<T> x[kClassLevels];
-            T tc[kClassLevels], te[kClassLevels], tn[kClassLevels], tw[kClassLevels], ts[kClassLevels];
+        for (int z = z0; z < z1; z += CL) {
+            const int nlev = z1 - z < CL ? z1 - z : CL;
+            LevelUV<T> x[CL];
+            T tc[CL], te[CL], tn[CL], tw[CL], ts[CL];   // the class field
+            LevelTau<T> tt[TWO ? CL : 1];               // the carried tracer, when it is another array
 #pragma unroll
-            for (int l = 0; l < kClassLevels; ++l)
+            for (int l = 0; l < CL; ++l)
                 if (l < nlev) {
                     const long o = (long)(z + l) * ncell;
                     x[l] = load_level_uv(u, v, o, r.c, nb);
@@ -462,11 +549,15 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
                     tn[l] = tau[o + nb.cn];
                     tw[l] = tau[o + nb.cw];
                     ts[l] = tau[o + nb.cs];
+                    if constexpr (TWO) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
                 }
 #pragma unroll
-            for (int l = 0; l < kClassLevels; ++l)
+            for (int l = 0; l < CL; ++l)
                 if (l < nlev) {
-                    const Slots d = level_slots<T>(thickness[z + l], x[l], arc, fill, fill2, two, scale, sverdrup, nb.south);
+                    FaceTf tf{};
+                    if constexpr (CARRY) tf = level_tf(TWO ? tt[l] : LevelTau<T>{tc[l], te[l], tn[l], tw[l], ts[l]}, nb, ti);
+                    const Slots d = level_slots_tf<T, CARRY>(thickness[z + l], x[l], arc, fill, fill2, two, scale, sverdrup,
+                                                             nb.south, tf);
                     double f;
                     bool h;
                     if (nb.south) {
@@ -495,7 +586,12 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
     }
 }
 
-template <typename T>
+
+// same bits of two doubles (NaN included): the markers of two tracer slots agree
+static bool same_bits(double a, double b) { return __builtin_memcmp(&a, &b, sizeof a) == 0; }
+
+// FORM: 0 = volume, 1 = carried tracer that is the class field, 2 = carried tracer and a class field of its own
+template <typename T, int FORM>
 static int launch_class_t(const ClassArgs &a, hipStream_t s)
 {
     const WeightSet &ws = *a.tr.ws;
@@ -509,20 +605,40 @@ static int launch_class_t(const ClassArgs &a, hipStream_t s)
         const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
         const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
         if (ws.nrec > 0) {
-            if (lds > 65536)
-                NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_class_segscan<T>, record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
-                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.tau, in.ncell,
-                               (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
-                               (int)uv_two_markers(fill, fill2), (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale,
-                               in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch);
+            if constexpr (FORM == 0) {
+                if (lds > 65536)
+                    NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T, false>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL((k_class_segscan<T, false>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
+                                   ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.tau, in.ncell,
+                                   (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
+                                   (int)uv_two_markers(fill, fill2), (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale,
+                                   in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch);
+            } else {
+                if (lds > 65536)
+                    NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T, FORM == 2, TauIn<T>>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL((k_class_segscan<T, FORM == 2, TauIn<T>>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(),
+                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.tau,
+                                   in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
+                                   (int)uv_two_markers(fill, fill2), (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale,
+                                   in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch,
+                                   TauIn<T>{(const T *)a.carry, (T)a.cfill, (T)a.cfill2, a.ref, a.wrap_x ? 1 : 0});
+            }
         }
         launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
                         (unsigned)nwin, s);
         NF_HIP(hipGetLastError());
     }
     return NF_OK;
+}
+
+template <typename T>
+static int launch_class_form(const ClassArgs &a, hipStream_t s)
+{
+    if (!a.carry) return launch_class_t<T, 0>(a, s);
+    const bool one = a.carry == a.tau && same_bits(a.cfill, a.tfill) && same_bits(a.cfill2, a.tfill2);
+    return one ? launch_class_t<T, 1>(a, s) : launch_class_t<T, 2>(a, s);
 }
 
 int launch_class_transport(const ClassArgs &a, hipStream_t s)
@@ -534,8 +650,8 @@ int launch_class_transport(const ClassArgs &a, hipStream_t s)
     NF_REQUIRE(in.u && in.v && a.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
                "class transport: null argument");
     if (a.tr.row_length() == 0) return NF_OK;
-    if (in.dtype == NF_F64) return launch_class_t<double>(a, s);
-    if (in.dtype == NF_F32) return launch_class_t<float>(a, s);
+    if (in.dtype == NF_F64) return launch_class_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_class_form<float>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "class transport: dtype must be NF_F64 or NF_F32");
 }
 

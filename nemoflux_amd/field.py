@@ -544,9 +544,15 @@ class Field(object):
         _FillValue / missing_value when not given; NaN always counts as missing).  reference: subtracted from every face value
         (theta_ref of a heat transport).  wrapX: the east face of the last column takes the first column as its neighbour
         (the periodic rule of the volume rows)."""
-        self._tracer_lazy = None
-        self._tracer_keep = None
-        self._tracer_step = -1
+        self._tracer = self._tracer_slot(tracer, fill_value, missing_value, lib.nf_field_set_tracer,
+                                         lib.nf_field_set_tracer_missing_value)
+        check(lib.nf_field_set_tracer_reference(ctypes.byref(self._h), float(reference)))
+        check(lib.nf_field_set_tracer_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
+
+    def _tracer_slot(self, tracer, fill_value, missing_value, set_tracer, set_missing):
+        """Hand a tracer at T-points to one of the engine's two tracer slots (set_tracer / set_missing: the slot's C calls) and
+        return what staging it needs: host arrays and device arrays are set once; a (path, name) pair is opened with its CF
+        markers and read one time step at a time into one pinned host buffer by _stage_slot."""
         if isinstance(tracer, tuple) and len(tracer) == 2 and isinstance(tracer[1], str):
             path, name = tracer
             var, _, d = open_uvfile(path, name, with_all=True)
@@ -563,38 +569,52 @@ class Field(object):
         if self.getSizes(shape) != (self.nt, self.nz, self.ny, self.nx):
             raise RuntimeError(f'ERROR: the tracer has shape {shape}; uo/vo have (nt, nz, ny, nx) = '
                                f'{(self.nt, self.nz, self.ny, self.nx)}')
-        code = _dtype_code(tracer)
-        fill = numpy.nan if fill_value is None else float(fill_value)
+        slot = dict(lazy=None, step=-1, set=set_tracer, code=_dtype_code(tracer),
+                    fill=numpy.nan if fill_value is None else float(fill_value))
         ptr = _lib.device_pointer(tracer)
         on_dev = 1
         if hasattr(tracer, 'read_step'):
             # file-backed: step t is read into one pinned host buffer and handed over as a host-resident tracer through a
             # virtual (nt, nz, ny, nx) base that the engine only dereferences at step t (as _stage does for uo / vo)
-            self._tracer_lazy = tracer
-            self._tracer_buf = self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('='))
-            self._tracer_code, self._tracer_fill = code, fill
+            slot['lazy'] = tracer
+            slot['buf'] = self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('='))
             ptr = None
         elif ptr is None:
             tracer = _native(tracer)
             ptr, on_dev = tracer.ctypes.data, 0
-        self._tracer_keep = tracer
+        slot['keep'] = tracer    # a borrowed buffer must outlive the handle
         if ptr is not None:
-            check(lib.nf_field_set_tracer(ctypes.byref(self._h), ptr, self.nt, code, on_dev, fill))
-        check(lib.nf_field_set_tracer_missing_value(ctypes.byref(self._h),
-                                                    numpy.nan if missing_value is None else float(missing_value)))
-        check(lib.nf_field_set_tracer_reference(ctypes.byref(self._h), float(reference)))
-        check(lib.nf_field_set_tracer_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
-        self._tracer_set = True
+            check(set_tracer(ctypes.byref(self._h), ptr, self.nt, slot['code'], on_dev, slot['fill']))
+        check(set_missing(ctypes.byref(self._h), numpy.nan if missing_value is None else float(missing_value)))
+        return slot
+
+    def _stage_slot(self, slot, tIndex):
+        """make step tIndex of a file-backed tracer slot the one the engine reads (no-op for in-memory / HBM tracers)"""
+        if slot is not None and slot['lazy'] is not None and slot['step'] != tIndex:
+            buf = slot['buf']
+            slot['lazy'].read_step(tIndex, out=buf)
+            check(slot['set'](ctypes.byref(self._h), buf.ctypes.data - tIndex * buf.nbytes, self.nt, slot['code'], 0,
+                              slot['fill']))
+            slot['step'] = tIndex
 
     def _stage_tracer(self, tIndex):
-        if not getattr(self, '_tracer_set', False):
+        if getattr(self, '_tracer', None) is None:
             raise RuntimeError('ERROR: call setTracer first')
-        if self._tracer_lazy is not None and self._tracer_step != tIndex:
-            self._tracer_lazy.read_step(tIndex, out=self._tracer_buf)
-            off = tIndex * self._tracer_buf.nbytes
-            check(lib.nf_field_set_tracer(ctypes.byref(self._h), self._tracer_buf.ctypes.data - off, self.nt,
-                                          self._tracer_code, 0, self._tracer_fill))
-            self._tracer_step = tIndex
+        self._stage_slot(self._tracer, tIndex)
+        self._stage_slot(getattr(self, '_class_tracer', None), tIndex)
+
+    def setClassTracer(self, tracer, fill_value=None, missing_value=None):
+        """A second tracer at T-points (potential density) whose classes computeClassTransport and
+        computeClassTracerTransport bin by, instead of the tracer of setTracer -- which is then only carried: heat by density
+        class.  Same (nt, nz, ny, nx) and dtype as uo / vo; a host array, a torch CUDA tensor or DeviceArray, or a
+        (path, name) pair read one time step at a time, as in setTracer.  It has its own missing markers, no reference, and
+        the wrapX of setTracer.  setClassTracer(None): back to the tracer of setTracer as the class field."""
+        self._class_tracer = None
+        if tracer is None:
+            check(lib.nf_field_set_class_tracer(ctypes.byref(self._h), None, 0, NF_F64, 0, numpy.nan))
+            return
+        self._class_tracer = self._tracer_slot(tracer, fill_value, missing_value, lib.nf_field_set_class_tracer,
+                                               lib.nf_field_set_class_tracer_missing_value)
 
     def computeTracerFlux(self, tIndex):
         """Tracer transport of time step tIndex across the transects (setTracer first): (ntransect,) totals and (nseg,)
@@ -612,7 +632,7 @@ class Field(object):
         """Tracer transport of all nt steps: (nt, ntransect) totals and (nt, nseg) per-segment sums.  `out`: optional torch
         CUDA tensor (nt, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
         import torch
-        lazy = self._lazy is not None or getattr(self, '_tracer_lazy', None) is not None
+        lazy = self._lazy is not None or (getattr(self, '_tracer', None) or {}).get('lazy') is not None
         if out is not None or not lazy:
             out = self._rows_out(out, self.nt)
         if lazy:
@@ -629,9 +649,54 @@ class Field(object):
             rows = out.cpu().numpy()
         return self._split_rows(rows)
 
+    def computeTracerProfile(self, tIndex, out=None, prefetch_next=None):
+        """Depth-resolved tracer transport of time step tIndex (setTracer first): (nz, ntransect) totals and (nz, nseg)
+        per-segment sums, row z = the tracer transport carried by level z alone -- the rows of computeFluxProfile with every
+        term times the tracer at its face (reference subtracted), and the computeTracerFlux row of a field whose only layer is
+        level z, bit for bit; their sum over z is the computeTracerFlux row up to rounding.  Levels this rank does not own
+        (slab_range) are zeros.  Leaves the resident edge fluxes, the running max, the row of the last computeFlux and the
+        tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor (nz, row_length) that receives the raw
+        rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        if out is not None:
+            out = self._rows_out(out, self.nz)
+            check(lib.nf_field_compute_tracer_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((self.nz, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_tracer_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        return self._split_rows(rows)
+
+    def computeClassTracerTransport(self, tIndex, out=None, prefetch_next=None):
+        """Transport of the tracer of setTracer (reference subtracted) of time step tIndex, binned by the class of each U / V
+        face (setTracer and setClassEdges first): (nedges+2, ntransect) totals and (nedges+2, nseg) per-segment sums, rows as in
+        computeClassTransport.  The class field is the tracer of setClassTracer when one is set (heat by density class), else
+        the carried tracer itself (heat by temperature class).  Every per-level term of computeTracerProfile goes to the row
+        of its face, so the rows add up to the computeTracerFlux row (up to rounding); a face whose carried tracer is missing
+        on both sides adds nothing.  Levels this rank does not own (slab_range) contribute nothing.  Leaves everything else
+        as it is.  `out`: as in computeClassTransport."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_class_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setClassEdges first')
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        if out is not None:
+            out = self._rows_out(out, edges.size + 2)
+            check(lib.nf_field_compute_class_tracer_transport_async(ctypes.byref(self._h), tIndex,
+                                                                    ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_class_tracer_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        return self._split_rows(rows)
+
     def setClassEdges(self, edges):
-        """Class edges e[0] < ... < e[n-1] (2 <= n <= 1025, finite) for computeClassTransport: the classes of the tracer of
-        setTracer (potential density, temperature, salinity) that the volume transport is binned by."""
+        """Class edges e[0] < ... < e[n-1] (2 <= n <= 1025, finite) for computeClassTransport and computeClassTracerTransport:
+        the classes of the tracer of setTracer (potential density, temperature, salinity) -- or of setClassTracer, when one is
+        set -- that the transport is binned by."""
         e = numpy.array(edges, dtype=numpy.float64).reshape(-1)
         check(lib.nf_field_set_class_edges(ctypes.byref(self._h), _lib.dptr(e), int(e.size)))
         self._class_edges = e
@@ -640,7 +705,8 @@ class Field(object):
         """Volume transport of time step tIndex binned by the class of the tracer at each U / V face (setTracer and
         setClassEdges first): (nedges+2, ntransect) totals and (nedges+2, nseg) per-segment sums.  Row 0: class value
         x < e[0]; row k: e[k-1] <= x < e[k]; row nedges: x >= e[nedges-1]; row nedges+1: faces without a class value (the
-        tracer missing on both sides).  The class value of a face is the mean of the tracer in the two cells beside it (the
+        tracer missing on both sides).  The class field is the tracer of setClassTracer when one is set, else the tracer of
+        setTracer.  The class value of a face is the mean of the class field in the two cells beside it (the
         present one when only one has a value); the tracer's reference is NOT used for it.  Every per-level term of
         computeFluxProfile goes to the row of its face, so the rows add up to the computeFlux row (up to rounding).  Levels
         this rank does not own (slab_range) contribute nothing.  Leaves the resident edge fluxes, the running max, the row of
@@ -663,8 +729,8 @@ class Field(object):
 
     @staticmethod
     def classStreamfunction(rows):
-        """Overturning streamfunction in class space from the rows of computeClassTransport (totals or segments, classes
-        first): psi[k] = rows[0] + ... + rows[k], k = 0 .. nedges-1, the transport of the faces whose class value is below
+        """Overturning streamfunction in class space from the rows of computeClassTransport or computeClassTracerTransport
+        (totals or segments, classes first): psi[k] = rows[0] + ... + rows[k], k = 0 .. nedges-1, the transport of the faces whose class value is below
         e[k].  Host only."""
         R = numpy.asarray(rows, dtype=numpy.float64)
         if R.ndim < 1 or R.shape[0] < 4:
@@ -672,8 +738,8 @@ class Field(object):
         return numpy.cumsum(R[:R.shape[0] - 2], axis=0)
 
     def depthBandFlux(self, profile, ztop, zbot):
-        """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile (totals or
-        segments, levels first): level z contributes profile[z] * overlap([ztop, zbot], layer z) / thickness[z], exact
+        """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile or
+        computeTracerProfile (totals or segments, levels first): level z contributes profile[z] * overlap([ztop, zbot], layer z) / thickness[z], exact
         because a level's flux is linear in its thickness; layers of zero thickness contribute nothing."""
         ztop, zbot = float(ztop), float(zbot)
         if not ztop <= zbot:

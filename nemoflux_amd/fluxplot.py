@@ -12,6 +12,8 @@ only with --show): the table is always printed or written as CSV, which is what 
                                   (heat transport in PW: Sv degC x 1e6 m^3/s x rho0 c_p (4.1e6 J/m^3/K) x 1e-15 PW/W)
     python -m nemoflux_amd.fluxplot -t T.nc -u U.nc -v V.nc -l "..." -s --tracer sigma0 --tracer-file S.nc --classes 26,27,28
                                   (water flow by sigma0 class: one CSV line per time step and class)
+    ... --tracer sigma0 --tracer-file S.nc --classes 26,27,28 --carry thetao --carry-scale 4.1e-3   (heat by sigma0 class)
+    ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
 """
 import argparse
 import glob
@@ -85,6 +87,29 @@ def classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile=''
     return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
 
 
+def carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracerFile='', carryFile='', carryRef=0.0,
+                sverdrup=False):
+    """(nt, nedges+2, ntransect) transport of the variable `carry` of carryFile by class of the variable `tracer` of
+    tracerFile (default for both: the T file), one Field.computeClassTracerTransport per time step, and the Field."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld.setTracer((carryFile or tFile, carry), reference=carryRef)
+    fld.setClassTracer((tracerFile or tFile, tracer))
+    fld.setClassEdges(edges)
+    totals = numpy.array([fld.computeClassTracerTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
+
+
+def levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tracerRef=0.0, sverdrup=False):
+    """(nt, nz, ntransect) water flow of every level (Field.computeFluxProfile) or, with `tracer`, the transport of that
+    variable of tracerFile (default: the T file) of every level (Field.computeTracerProfile), and the Field."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    if tracer:
+        fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    profile = fld.computeTracerProfile if tracer else fld.computeFluxProfile
+    totals = numpy.array([profile(t, prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, fld.nz, len(lonLatZPoints)), fld
+
+
 def parseClasses(classes):
     """'E0,E1,...,EN' -> the class edges (a list of at least two finite, strictly increasing numbers)."""
     try:
@@ -111,6 +136,46 @@ def checkClassArgs(classes='', tracer='', tracerRef=0.0, tracerScale=1.0, zrange
     if show:
         raise RuntimeError('ERROR: --classes and --show cannot be combined: the class table is written as CSV only')
     parseClasses(classes)
+
+
+def checkCarryArgs(carry='', carryFile='', carryRef=0.0, carryScale=1.0, classes='', tracer='', levels=False):
+    """the --carry options of the command line (the transport of a second tracer by class): refused combinations raise
+    RuntimeError"""
+    if not carry:
+        if carryFile:
+            raise RuntimeError('ERROR: --carry-file needs --carry NAME (the variable to read from it)')
+        if float(carryRef) != 0.0 or float(carryScale) != 1.0:
+            raise RuntimeError('ERROR: --carry-ref / --carry-scale need --carry NAME')
+        return
+    if levels:
+        raise RuntimeError('ERROR: --carry and --levels cannot be combined: --levels --tracer NAME gives the transport of NAME '
+                           'per level')
+    if not classes or not tracer:
+        raise RuntimeError('ERROR: --carry needs --classes E0,...,EN and --tracer NAME (the class field); the transport of a '
+                           'tracer alone is --tracer NAME')
+    for name, x in (('--carry-ref', carryRef), ('--carry-scale', carryScale)):
+        if not numpy.isfinite(float(x)):
+            raise RuntimeError(f'ERROR: {name} must be a finite number, got {x!r}')
+
+
+def checkLevelsArgs(levels=False, zrange='', classes='', show=False):
+    """the --levels option of the command line (one line per time step and level): refused combinations raise RuntimeError"""
+    if not levels:
+        return
+    if zrange:
+        raise RuntimeError('ERROR: --levels and --zrange cannot be combined: --levels lists every level, --zrange sums a band')
+    if classes:
+        raise RuntimeError('ERROR: --levels and --classes cannot be combined: depth-resolved class transports are not available')
+    if show:
+        raise RuntimeError('ERROR: --levels and --show cannot be combined: the level table is written as CSV only')
+
+
+def _emit(text, output):
+    if output:
+        with open(output, 'w') as f:
+            f.write(text)
+    else:
+        print(text, end='')
 
 
 def checkTracerArgs(tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, zrange=''):
@@ -141,25 +206,45 @@ def parseZRange(zrange):
 
 
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
-         tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes=''):
+         tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
+         carryRef=0.0, carryScale=1.0):
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
     checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, zrange)
+    checkLevelsArgs(levels, zrange, classes, show)
+    checkCarryArgs(carry, carryFile, carryRef, carryScale, classes, tracer, levels)
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
+    unit = 'Sv' if sverdrup else 'A m^2/s'
+    if levels:
+        totals, fld = levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup)
+        what = 'water flow'
+        if tracer:
+            totals = totals * float(tracerScale)
+            what = f'transport of {tracer}'
+            unit = f'{tracer} x {unit}' + (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '')
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        lines = ['time,ztop,zbot,' + ','.join(names)]
+        lines += [f'{timeVals[t]},{fld.bounds_depth[z, 0]:.15g},{fld.bounds_depth[z, 1]:.15g},' +
+                  ','.join(f'{x:.15g}' for x in totals[t, z]) for t in range(fld.nt) for z in range(fld.nz)]
+        _emit(f'# {what} per level [{unit}]\n' + '\n'.join(lines) + '\n', output)
+        return totals
     if classes:
         edges = parseClasses(classes)
-        totals, fld = classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, sverdrup)
+        if carry:
+            totals, fld = carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracerFile, carryFile,
+                                      float(carryRef), sverdrup)
+            totals = totals * float(carryScale)
+            title = (f'# transport of {carry} by {tracer} class [{carry} x {unit}' +
+                     (f' x {float(carryScale):g}' if float(carryScale) != 1.0 else '') + ']\n')
+        else:
+            totals, fld = classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, sverdrup)
+            title = f'# water flow by {tracer} class [{unit}]\n'
         timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
         bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
         lines = ['time,lower,upper,' + ','.join(names)]
         lines += [f'{timeVals[t]},{lo:.15g},{hi:.15g},' + ','.join(f'{x:.15g}' for x in totals[t, k])
                   for t in range(fld.nt) for k, (lo, hi) in enumerate(bounds)]
-        text = f'# water flow by {tracer} class [{"Sv" if sverdrup else "A m^2/s"}]\n' + '\n'.join(lines) + '\n'
-        if output:
-            with open(output, 'w') as f:
-                f.write(text)
-        else:
-            print(text, end='')
+        _emit(title + '\n'.join(lines) + '\n', output)
         return totals
     if tracer:
         totals, fld = tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup)
@@ -169,7 +254,6 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     else:
         totals, fld = fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup)
     timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
-    unit = 'Sv' if sverdrup else 'A m^2/s'
     title, what = 'Water flow', 'water flow'
     if tracer:
         title = what = f'Transport of {tracer}'
@@ -221,4 +305,15 @@ if __name__ == '__main__':
     ap.add_argument('--classes', default='', metavar='E0,E1,...,EN',
                     help='water flow binned by the class of --tracer NAME (e.g. sigma0): one CSV line per time step and '
                          'class [-inf,E0), [E0,E1), ..., [EN,inf), and a last one (nan,nan) for faces without a value')
+    ap.add_argument('--carry', default='', metavar='NAME',
+                    help='with --classes: the transport of tracer NAME (e.g. heat: thetao) by class of --tracer, in place of '
+                         'the water flow; NAME is read from the T file')
+    ap.add_argument('--carry-file', dest='carryFile', default='', metavar='FILE', help='read --carry from FILE instead')
+    ap.add_argument('--carry-ref', dest='carryRef', type=float, default=0.0, metavar='X',
+                    help='reference value subtracted from the carried tracer')
+    ap.add_argument('--carry-scale', dest='carryScale', type=float, default=1.0, metavar='S',
+                    help='multiply the carried transport by S')
+    ap.add_argument('--levels', action='store_true',
+                    help='one CSV line per time step and level (time,ztop,zbot,...): the water flow of each level, or with '
+                         '--tracer NAME the transport of NAME of each level (--tracer-ref, --tracer-scale apply)')
     main(**vars(ap.parse_args()))

@@ -1,0 +1,701 @@
+"""Depth- and class-resolved tracer transports (Field.computeTracerProfile, setClassTracer, computeClassTracerTransport and
+the nf_field_* calls behind them): the volume profile and the volume class transport with every per-level term multiplied by
+the carried tracer at its own face.  Anchored bit for bit to the volume forms (tau = ref + 1), to the tracer transport of a
+one-layer field, to each other (class field = level index) and to the one-tracer form (the same field in both slots); checked
+to stated bounds against a float64 numpy restatement of the definitions on odd grids, for conservation against the tracer
+row and against K1tau + K3 on class-masked uo / vo; unchanged state, sharding, file-backed inputs, `out=` and fluxplot."""
+import contextlib
+import ctypes
+import io
+import os
+
+import numpy
+import pytest
+
+from conftest import GOLDEN, transect_xyz
+
+pytestmark = pytest.mark.gpu
+
+PSI_ZT = "(1+10*z)*(t+1)*(cos(2*pi*y/360) + sin(2*pi*x/360))"
+T_TRI = "(-100,-80),(100,-80),(0,80),(-100,-80)"
+T_OPEN = "(-100,-80),(100,-80),(0,80)"
+T_SEAM = "(150,-30),(179.5,-20),(179.9,10),(175,40)"     # crosses the periodic seam: east faces of the last column
+NX, NY, NZ, NT = 72, 36, 7, 3
+FILL, MISSING = 1.e20, -999.                 # markers of uo / vo
+TFILL, TMISSING = -32768., 12345.            # markers of the class field
+CFILL, CMISSING = 9999., -7777.              # markers of the carried tracer
+REF = 7.5
+R_SV = 6371000.0 / 1.e6
+EPS = numpy.finfo(numpy.float64).eps
+LEVEL_EDGES = numpy.arange(NZ + 1) - 0.5          # -0.5, 0.5, ..., NZ - 0.5
+SMALL_EDGES = numpy.array([0., 5., 8., 10., 12., 15., 20.])
+DEFAULT_WINDOW = 32     # nf_tuning_set("class_window") default
+
+
+def _quiet(fn, *a, **kw):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return fn(*a, **kw)
+
+
+def _field(*a, **kw):
+    from nemoflux_amd.field import Field
+    return _quiet(Field.fromArrays, *a, **kw)
+
+
+_CASES = {}
+
+
+def _case(real, fill=True):
+    """host u, v (nt, nz, ny, nx) of the PSI_ZT case; with `fill`, land blocks marked by _FillValue, NaN and a second
+    missing value"""
+    key = (real, fill)
+    if key not in _CASES:
+        from nemoflux_amd.datagen import DataGen
+        dg = DataGen(real=real)
+        dg.setSizes(NX, NY, NZ, NT)
+        dg.setBoundingBox(-180., 180., -90., 90., 0., 1.)
+        dg.build()
+        dg.applyStreamFunction(PSI_ZT)
+        dg.computeUVFromPotential()
+        u, v = dg.u.cpu().numpy().copy(), dg.v.cpu().numpy().copy()
+        v[:, :, -1, :] = 0                     # datagen's pole row is 1e13-sized garbage
+        if fill:
+            dt = u.dtype.type
+            u[:, 3:, 4:9, 10:20] = dt(FILL)
+            v[:, 3:, 4:9, 10:20] = numpy.nan
+            u[:, :2, 20:24, 30:40] = dt(MISSING)
+            v[:, 5:, 20:24, 30:40] = dt(MISSING)
+        _CASES[key] = (dg.bounds_lon.cpu().numpy(), dg.bounds_lat.cpu().numpy(), numpy.asarray(dg.deptht_bounds), u, v)
+    return _CASES[key]
+
+
+LINES = [T_OPEN, T_TRI, T_SEAM]
+
+
+def _on(a, resident):
+    import torch
+    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
+
+
+def _args(real, resident, fill=True, db=None):
+    blon, blat, db0, u, v = _case(real, fill)
+    return (blon, blat, db0 if db is None else db, _on(u, resident), _on(v, resident), [transect_xyz(s) for s in LINES])
+
+
+def _kw(sverdrup, fill=True, **kw):
+    kw.update(sverdrup=sverdrup, readback=False)
+    if fill:
+        kw.update(fill_value=FILL, missing_value=MISSING)
+    return kw
+
+
+def _rows(pair):
+    """[segments | transects] rows of a (totals, segments) pair"""
+    tot, seg = pair
+    return numpy.concatenate([seg, tot], axis=-1)
+
+
+def _tprof(f, t, out=None):
+    return _rows(f.computeTracerProfile(t, out=out))
+
+
+def _trows(f, t, out=None):
+    return _rows(f.computeClassTracerTransport(t, out=out))
+
+
+def _tracer_row(f, t):
+    return _rows(f.computeTracerFlux(t))
+
+
+def _level_tau(shape, dtype):
+    return numpy.broadcast_to(numpy.arange(shape[1], dtype=dtype)[None, :, None, None], shape).copy()
+
+
+def _class_field(shape, dtype, seed):
+    """a random class field: markers, NaN, +-inf and neighbour pairs whose face value lies exactly on an edge"""
+    rng = numpy.random.default_rng(seed)
+    dt = numpy.dtype(dtype).type
+    sig = (10. + 5. * rng.standard_normal(shape)).astype(dt)
+    flat = sig.reshape(-1)
+    flat[rng.choice(sig.size, sig.size // 5, replace=False)] = rng.choice([8., 12.], sig.size // 5)
+    flat[rng.choice(sig.size, sig.size // 10, replace=False)] = numpy.inf
+    flat[rng.choice(sig.size, sig.size // 25, replace=False)] = -numpy.inf
+    for m in (TFILL, TMISSING, numpy.nan):
+        flat[rng.choice(sig.size, sig.size // 7, replace=False)] = dt(m)
+    return sig
+
+
+def _carried(shape, dtype, seed):
+    """a random carried tracer: finite values, its own two markers and NaN (faces with one and with both sides missing)"""
+    rng = numpy.random.default_rng(seed)
+    dt = numpy.dtype(dtype).type
+    tau = (REF + 2. * rng.standard_normal(shape)).astype(dt)
+    flat = tau.reshape(-1)
+    for m in (CFILL, CMISSING, numpy.nan):
+        flat[rng.choice(tau.size, tau.size // 12, replace=False)] = dt(m)
+    return tau
+
+
+@contextlib.contextmanager
+def _window(w):
+    from nemoflux_amd._lib import lib, check
+    check(lib.nf_tuning_set(b'class_window', int(w)))
+    try:
+        yield
+    finally:
+        check(lib.nf_tuning_set(b'class_window', DEFAULT_WINDOW))
+
+
+# ---- 1 .. 4: bit for bit ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+@pytest.mark.parametrize('fill', [True, False], ids=['markers', 'nomarkers'])
+@pytest.mark.parametrize('sverdrup', [False, True], ids=['m2', 'sv'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_unit_tracer_gives_the_volume_forms_bit_for_bit(real, sverdrup, fill, resident):
+    """tau == ref + 1: every face value is exactly 1, the tracer profile is the volume profile and the tracer rows by class
+    of a second, random field are the volume rows by that class"""
+    f = _field(*_args(real, resident, fill), **_kw(sverdrup, fill))
+    u = _case(real, fill)[3]
+    f.setTracer(_on(numpy.full(u.shape, REF + 1., u.dtype), resident), reference=REF)
+    f.setClassTracer(_on(_class_field(u.shape, u.dtype, 3), resident), fill_value=TFILL, missing_value=TMISSING)
+    f.setClassEdges(SMALL_EDGES)
+    for t in (2, 0, 1):
+        prof = _rows(f.computeFluxProfile(t))
+        assert numpy.abs(prof).max() > 0
+        assert numpy.array_equal(_tprof(f, t), prof), t
+        vol = _rows(f.computeClassTransport(t))
+        assert (numpy.abs(vol).max(axis=1) > 0).all(), 'every class, the top one and the no-value row carry flux'
+        assert numpy.array_equal(_trows(f, t), vol), t
+
+
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+@pytest.mark.parametrize('fill', [True, False], ids=['markers', 'nomarkers'])
+@pytest.mark.parametrize('sverdrup', [False, True], ids=['m2', 'sv'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_tracer_profile_level_is_the_one_layer_tracer_flux_bit_for_bit(real, sverdrup, fill, resident):
+    """row z of computeTracerProfile(t) == the computeTracerFlux(t) row of a field whose deptht_bounds are collapsed so that
+    only level z has a thickness (fma(0, x, acc) == acc for finite x: no +-inf in this tracer; markers and NaN are fine).
+    k_tracer_flux + K3 share no gather code with the profile kernel."""
+    db = numpy.asarray(_case(real, fill)[2], dtype=numpy.float64)
+    u = _case(real, fill)[3]
+    tau = _on(_carried(u.shape, u.dtype, 29) if fill else (REF + numpy.random.default_rng(29).random(u.shape)).astype(u.dtype),
+              resident)
+    tkw = dict(fill_value=CFILL, missing_value=CMISSING, reference=REF) if fill else dict(reference=REF)
+    f = _field(*_args(real, resident, fill), **_kw(sverdrup, fill))
+    f.setTracer(tau, **tkw)
+    profiles = [_tprof(f, t) for t in range(NT)]
+    assert all(numpy.abs(p).max(axis=1).min() > 0 for p in profiles)
+    for z in range(NZ):
+        dz = db.copy()
+        for k in range(NZ):
+            if k != z:
+                dz[k, 1] = dz[k, 0]
+        assert (dz[:, 1] - dz[:, 0] != 0).sum() == 1
+        one = _field(*_args(real, resident, fill, db=dz), **_kw(sverdrup, fill))
+        one.setTracer(tau, **tkw)
+        for t in range(NT):
+            assert numpy.array_equal(profiles[t][z], _tracer_row(one, t)), (z, t)
+
+
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+@pytest.mark.parametrize('fill', [True, False], ids=['markers', 'nomarkers'])
+@pytest.mark.parametrize('sverdrup', [False, True], ids=['m2', 'sv'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_level_index_classes_are_the_tracer_profile_bit_for_bit(real, sverdrup, fill, resident):
+    """class field = z, edges -0.5, 0.5, ..., nz - 0.5, a random carried tracer: class row z + 1 is tracer-profile row z bit
+    for bit; rows 0, nz + 1 and nz + 2 are exact zeros; for every window"""
+    f = _field(*_args(real, resident, fill), **_kw(sverdrup, fill))
+    u = _case(real, fill)[3]
+    f.setTracer(_on(_carried(u.shape, u.dtype, 31), resident), fill_value=CFILL, missing_value=CMISSING, reference=REF)
+    f.setClassTracer(_on(_level_tau(u.shape, u.dtype), resident))
+    f.setClassEdges(LEVEL_EDGES)
+    for t in (2, 0, 1):
+        prof = _tprof(f, t)
+        assert numpy.abs(prof).max(axis=1).min() > 0
+        for w in (DEFAULT_WINDOW,) if t else (1, 3, 16, 32):
+            with _window(w):
+                rows = _trows(f, t)
+            assert rows.shape == (NZ + 3, f._rowlen)
+            assert numpy.array_equal(rows[1:NZ + 1], prof), (t, w)
+            assert not rows[0].any() and not rows[NZ + 1:].any(), (t, w)
+
+
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_the_same_field_in_both_slots_changes_nothing(real, resident):
+    """setClassTracer(tau) with tau's markers gives the rows of not setting it, for the volume and for the tracer rows, and
+    setClassTracer(None) goes back"""
+    f = _field(*_args(real, resident), **_kw(True))
+    u = _case(real)[3]
+    tau = _class_field(u.shape, u.dtype, 37)
+    tau = _on(numpy.where(numpy.isinf(tau), tau.dtype.type(11.), tau), resident)      # finite: it is carried too
+    f.setTracer(tau, fill_value=TFILL, missing_value=TMISSING, reference=REF)
+    f.setClassEdges(SMALL_EDGES)
+    vol = [_rows(f.computeClassTransport(t)) for t in range(NT)]
+    tra = [_trows(f, t) for t in range(NT)]
+    assert (numpy.abs(tra[1][:-1]).max(axis=1) > 0).all()
+    assert not tra[1][-1].any(), 'a face without a class value has no carried value either: tf = 0'
+    other = _on(_class_field(u.shape, u.dtype, 38), resident)
+    for sig in (tau, _on(tau.cpu().numpy().copy() if resident else tau.copy(), resident)):   # the array itself, and a copy
+        f.setClassTracer(other, fill_value=TFILL, missing_value=TMISSING)
+        assert not numpy.array_equal(_trows(f, 1), tra[1])
+        f.setClassTracer(sig, fill_value=TFILL, missing_value=TMISSING)
+        for t in (2, 0, 1):
+            assert numpy.array_equal(_rows(f.computeClassTransport(t)), vol[t]), t
+            assert numpy.array_equal(_trows(f, t), tra[t]), t
+    f.setClassTracer(other, fill_value=TFILL, missing_value=TMISSING)
+    f.setClassTracer(None)
+    assert numpy.array_equal(_rows(f.computeClassTransport(1)), vol[1])
+    assert numpy.array_equal(_trows(f, 1), tra[1])
+
+
+# ---- the definitions, restated in float64 numpy ----------------------------------------------------------------------------
+def _restated(f, u, v, tau, sig, umark, cmark, smark, ref, wrap, sverdrup, edges):
+    """One step from the definitions: u, v, tau (carried), sig (class field) are (nz, ny, nx) in their own dtype, markers
+    compared in that dtype.  Returns the class-tracer rows (nedges + 2, row_length), the tracer profile (nz, row_length) and,
+    for each, the bound sum |terms| per value."""
+    dt = tau.dtype.type
+
+    def present(x, marks):
+        ok = ~numpy.isnan(x)
+        for m in marks:
+            if m == m:
+                ok &= x != dt(m)
+        return ok
+
+    def fixed(x):
+        return numpy.where(present(x, umark), x.astype(numpy.float64), 0.0)
+
+    def face(a, b, has_b, marks):
+        """(has a value, raw face value): 0.5 (a + b), the present one, or none"""
+        pa, pb = present(a, marks), has_b & present(b, marks)
+        a64, b64 = a.astype(numpy.float64), b.astype(numpy.float64)
+        with numpy.errstate(invalid='ignore', over='ignore'):
+            x = numpy.where(pa & pb, 0.5 * (a64 + b64), numpy.where(pa, a64, b64))
+        return pa | pb, x
+
+    def face_row(a, b, has_b):
+        has, x = face(a, b, has_b, smark)
+        row = numpy.searchsorted(edges, numpy.where(numpy.isnan(x), 0.0, x), side='right')   # the number of edges <= x
+        return numpy.where(has & ~numpy.isnan(x), row, len(edges) + 1)
+
+    def face_tf(a, b, has_b):
+        has, x = face(a, b, has_b, cmark)
+        return numpy.where(has, numpy.where(has, x, 0.0) - ref, 0.0)
+
+    nz, ny, nx = tau.shape
+    has_e = numpy.ones((nz, ny, nx), bool)
+    if not wrap:
+        has_e[:, :, -1] = False
+    has_n = numpy.ones((nz, ny, nx), bool)
+    has_n[:, -1, :] = False
+    east = lambda a: numpy.roll(a, -1, axis=2)      # the second cell of the east face of every cell (wrap: column 0)
+    north = lambda a: numpy.roll(a, -1, axis=1)
+    rowE, rowN = face_row(sig, east(sig), has_e).reshape(nz, -1), face_row(sig, north(sig), has_n).reshape(nz, -1)
+    tfE, tfN = face_tf(tau, east(tau), has_e).reshape(nz, -1), face_tf(tau, north(tau), has_n).reshape(nz, -1)
+    arc = f.arcLengths
+    aE, aN = arc[:, 1], arc[:, 2]
+    th = f.thickness
+    ce, w, sg = f.getWeights()
+    c, slot = ce // 4, ce % 4
+    j, i = c // nx, c % nx
+    cw = numpy.where(i > 0, c - 1, c - 1 + nx)
+    cs = numpy.where(j > 0, c - nx, c)
+    keep = (slot != 0) | (j > 0)               # row 0's south slots carry nothing
+    cell = numpy.select([slot == 0, slot == 1, slot == 2], [cs, c, c], cw)     # the cell whose east / north face the slot is
+    is_u = (slot == 1) | (slot == 3)
+    nrow = len(edges) + 2
+    rows, mag = numpy.zeros((nrow, f._nseg)), numpy.zeros((nrow, f._nseg))
+    prof, pmag = numpy.zeros((nz, f._nseg)), numpy.zeros((nz, f._nseg))
+    for z in range(nz):
+        U, V = fixed(u[z]).reshape(-1), fixed(v[z]).reshape(-1)
+        d = numpy.where(is_u, th[z] * (U[cell] * tfE[z][cell]) * aE[cell], -(th[z] * (V[cell] * tfN[z][cell])) * aN[cell])
+        if sverdrup:
+            d = d * R_SV
+        r = numpy.where(is_u, rowE[z][cell], rowN[z][cell])
+        terms = numpy.where(keep, w * d, 0.0)
+        numpy.add.at(rows, (r, sg), terms)
+        numpy.add.at(mag, (r, sg), numpy.abs(terms))
+        numpy.add.at(prof[z], sg, terms)
+        numpy.add.at(pmag[z], sg, numpy.abs(terms))
+    o = f._tr_off
+
+    def with_totals(a):
+        return numpy.concatenate([a] + [a[:, o[p]:o[p + 1]].sum(axis=1, keepdims=True) for p in range(len(o) - 1)], axis=1)
+
+    return with_totals(rows), with_totals(mag), with_totals(prof), with_totals(pmag)
+
+
+def _small_grid(real, nx, ny, nz, nt, seed):
+    """bounds of a regular 1-degree grid on [0, nx] x [0, ny], random u, v with markers, a class field with markers, values on
+    the edges and +-inf, and a carried tracer with a different marker set"""
+    from nemoflux_amd.datagen import DataGen
+    dg = DataGen(real=real)
+    dg.setSizes(nx, ny, nz, nt)
+    dg.setBoundingBox(0., float(nx), 0., float(ny), 0., 1.)
+    dg.build()
+    rng = numpy.random.default_rng(seed)
+    dt = numpy.dtype(real).type
+    shape = (nt, nz, ny, nx)
+    u = rng.standard_normal(shape).astype(dt)
+    v = rng.standard_normal(shape).astype(dt)
+    u.reshape(-1)[rng.choice(u.size, u.size // 9, replace=False)] = dt(FILL)
+    v.reshape(-1)[rng.choice(v.size, v.size // 9, replace=False)] = numpy.nan
+    u.reshape(-1)[rng.choice(u.size, u.size // 11, replace=False)] = dt(MISSING)
+    tau, sig = _carried(shape, real, seed + 1), _class_field(shape, real, seed + 2)
+    # whatever the seed, on level 0 of every step: the north face of the last cell (on two of _small_lines) is in the top class
+    # and the north face of the first cell (on the first line) has no class value, both with a flow and a carried value
+    for a, val in ((u, 1.), (v, 1.), (tau, REF + 1.)):
+        a[:, 0, -1, -1] = a[:, 0, 0, 0] = dt(val)
+    sig[:, 0, -1, -1] = numpy.inf
+    sig[:, 0, :2, 0] = numpy.nan
+    return dg.bounds_lon.cpu().numpy(), dg.bounds_lat.cpu().numpy(), dg.deptht_bounds, u, v, tau, sig
+
+
+def _small_lines(nx, ny):
+    x1, y1 = nx - 0.37, ny - 0.41
+    return [transect_xyz(f"(0.3,0.2),({x1},{0.6 * ny}),({0.5 * nx},{y1})"),
+            transect_xyz(f"({x1},0.45),({x1 - 0.02},{y1})"),
+            transect_xyz(f"(0.61,{y1}),({x1},{y1 - 0.03})")]
+
+
+@pytest.mark.parametrize('wrap', [True, False], ids=['wrap', 'nowrap'])
+@pytest.mark.parametrize('grid', [(37, 11), (38, 12), (1, 11), (37, 1), (5, 3)], ids=lambda g: f'{g[0]}x{g[1]}')
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_against_the_numpy_restatement(real, grid, wrap):
+    """tracer profile and class-tracer rows within 1e-12 sum |terms| of the restated definitions; the sums over levels and
+    over classes are the tracer row within 32 eps sum |terms| (only the summation order differs)"""
+    nx, ny = grid
+    nz, nt = 5, 2
+    blon, blat, db, u, v, tau, sig = _small_grid(real, nx, ny, nz, nt, seed=nx * 100 + ny + wrap)
+    sverdrup = nx % 2 == 1
+    f = _field(blon, blat, db, u, v, _small_lines(nx, ny), sverdrup=sverdrup, readback=False, fill_value=FILL,
+               missing_value=MISSING, periodX=0.)
+    f.setTracer(tau, fill_value=CFILL, missing_value=CMISSING, reference=3.25, wrapX=wrap)
+    f.setClassTracer(sig, fill_value=TFILL, missing_value=TMISSING)
+    f.setClassEdges(SMALL_EDGES)
+    nrow = SMALL_EDGES.size + 2
+    for t in range(nt):
+        want, mag, pwant, pmag = _restated(f, u[t], v[t], tau[t], sig[t], (FILL, MISSING), (CFILL, CMISSING),
+                                           (TFILL, TMISSING), 3.25, wrap, sverdrup, SMALL_EDGES)
+        got, prof = _trows(f, t), _tprof(f, t)
+        assert got.shape == (nrow, f._rowlen) and prof.shape == (nz, f._rowlen)
+        print(f'{real} {nx}x{ny} wrap={wrap} t={t}: rows max |err|/mag = '
+              f'{(numpy.abs(got - want) / numpy.maximum(mag, 1e-300)).max():.3g}, profile '
+              f'{(numpy.abs(prof - pwant) / numpy.maximum(pmag, 1e-300)).max():.3g}')
+        assert numpy.all(numpy.abs(got - want) <= 1e-12 * mag), (t, numpy.abs(got - want).max())
+        assert numpy.all(numpy.abs(prof - pwant) <= 1e-12 * pmag), (t, numpy.abs(prof - pwant).max())
+        assert pmag.max() > 0
+        assert mag[-1].max() > 0, 'faces without a class value must carry flux'
+        assert mag[SMALL_EDGES.size].max() > 0, 'the top class (+inf) must carry flux'
+        row = _tracer_row(f, t)
+        assert numpy.all(numpy.abs(got.sum(axis=0) - row) <= 32 * EPS * mag.sum(axis=0)), t
+        assert numpy.all(numpy.abs(prof.sum(axis=0) - row) <= 32 * EPS * pmag.sum(axis=0)), t
+
+
+def test_class_masked_tracer_rows_are_the_class_rows():
+    """independent of the per-level terms: for every class, K1tau + K3 (computeTracerFlux) of uo / vo with the faces of the
+    other classes set to zero gives that class row within 1e-12 sum |terms|"""
+    import torch
+    real = 'float64'
+    blon, blat, db, u, v = _case(real)
+    rng = numpy.random.default_rng(17)
+    sig = (10. + 6. * rng.standard_normal(u.shape)).astype(u.dtype)
+    sig.reshape(-1)[rng.choice(sig.size, sig.size // 6, replace=False)] = numpy.nan
+    tau = _carried(u.shape, u.dtype, 19)
+    edges = numpy.array([4., 7., 9., 10., 11., 13., 16.])
+    ut, vt = _on(u, True), _on(v, True)
+    f = _field(blon, blat, db, ut, vt, [transect_xyz(s) for s in LINES], **_kw(False))
+    f.setTracer(_on(tau, True), fill_value=CFILL, missing_value=CMISSING, reference=REF, wrapX=True)
+    f.setClassTracer(_on(sig, True))
+    f.setClassEdges(edges)
+
+    def face_rows(a, b, has_b):
+        pa, pb = ~numpy.isnan(a), has_b & ~numpy.isnan(b)
+        x = numpy.where(pa & pb, 0.5 * (a + b), numpy.where(pa, a, b))
+        return numpy.where(pa | pb, numpy.searchsorted(edges, numpy.where(pa | pb, x, 0.), side='right'), edges.size + 1)
+
+    has_n = numpy.ones(sig.shape, bool)
+    has_n[:, :, -1, :] = False
+    rowE = face_rows(sig, numpy.roll(sig, -1, axis=3), numpy.ones(sig.shape, bool))
+    rowN = face_rows(sig, numpy.roll(sig, -1, axis=2), has_n)
+    for t in (0, 2):
+        got = _trows(f, t)
+        _, mag, _, _ = _restated(f, u[t], v[t], tau[t], sig[t], (FILL, MISSING), (CFILL, CMISSING), (), REF, True, False, edges)
+        for k in range(edges.size + 2):
+            ut.copy_(torch.from_numpy(numpy.where(rowE == k, u, 0.)))
+            vt.copy_(torch.from_numpy(numpy.where(rowN == k, v, 0.)))
+            want = _tracer_row(f, t)
+            assert numpy.all(numpy.abs(got[k] - want) <= 1e-12 * mag[k]), (t, k)
+        ut.copy_(torch.from_numpy(u))
+        vt.copy_(torch.from_numpy(v))
+        assert (numpy.abs(got).max(axis=1) > 0).all()
+
+
+# ---- state and plumbing -----------------------------------------------------------------------------------------------------
+def _resident(f):
+    from nemoflux_amd import _lib
+    from nemoflux_amd._lib import lib, check
+    n = f.ny * f.nx
+    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
+    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
+    return iV, eU, eV, mx.value
+
+
+@pytest.mark.parametrize('compact', [False, True])
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+def test_new_calls_leave_everything_else_alone(compact, resident):
+    """tracer-profile and class-tracer calls between computeFlux, computeAll, tracer rows, class rows and read-backs: rows,
+    planes, |.| arrays, the running max, the tracer rows and the class rows equal those of a field that never saw one"""
+    args = _args('float64', resident)
+    a = _field(*args, compact=compact, **_kw(False))
+    b = _field(*args, compact=compact, **_kw(False))
+    rng = numpy.random.default_rng(7)
+    shape = _case('float64')[3].shape
+    tau, sig = _on(4. + rng.random(shape), resident), _on(4. + rng.random(shape), resident)
+    edges = numpy.linspace(4., 5., 9)
+    for f in (a, b):
+        f.setTracer(tau, reference=4.)
+        f.setClassTracer(sig)
+        f.setClassEdges(edges)
+    p0, r0 = _tprof(a, 1), _trows(a, 1)
+    for step in ('flux1', 'all', 'tracer0', 'class1', 'flux0', 'read', 'all', 'flux2', 'read', 'tracer2', 'class0'):
+        _trows(a, 2)
+        _tprof(a, 0)
+        if step == 'all':
+            assert all(numpy.array_equal(x, y) for x, y in zip(a.computeAll(), b.computeAll()))
+        elif step == 'read':
+            for x, y in zip(_resident(a), _resident(b)):
+                assert numpy.array_equal(x, y)
+        elif step.startswith('tracer'):
+            t = int(step[-1])
+            assert numpy.array_equal(_tracer_row(a, t), _tracer_row(b, t))
+        elif step.startswith('class'):
+            t = int(step[-1])
+            assert numpy.array_equal(_rows(a.computeClassTransport(t)), _rows(b.computeClassTransport(t)))
+        else:
+            t = int(step[-1])
+            assert a.computeFlux(t) == b.computeFlux(t)
+            _tprof(a, 2)
+            _trows(a, 0)
+            assert numpy.array_equal(numpy.array(a._row[:a._rowlen]), numpy.array(b._row[:b._rowlen]))
+            assert a.getSegmentFluxes()[0].tolist() == b.getSegmentFluxes()[0].tolist()
+    for x, y in zip(_resident(a), _resident(b)):
+        assert numpy.array_equal(x, y)
+    assert numpy.array_equal(_tprof(a, 1), p0) and numpy.array_equal(_trows(a, 1), r0)
+
+
+@pytest.mark.parametrize('world', [2, 3])
+def test_sharded_rows_add_up(world):
+    """slab ranges that cut inside steps: steps a rank does not touch are exact zeros (through `out` too, which is what
+    dist.reduce_rows sums), the ranks' rows sum to the single-rank rows; with the level-index class field, bit for bit"""
+    import torch
+    from nemoflux_amd.dist import slab_range, reduce_rows
+    args = _args('float64', True)
+    u = _case('float64')[3]
+    rng = numpy.random.default_rng(11)
+    tau = _on(_carried(u.shape, u.dtype, 13), True)
+    sigs = {'random': _on(10. + 5. * rng.standard_normal(u.shape), True), 'level': _on(_level_tau(u.shape, u.dtype), True)}
+    edges = {'random': numpy.linspace(0., 20., 17), 'level': LEVEL_EDGES}
+
+    def make(name, **kw):
+        f = _field(*args, **_kw(False), **kw)
+        f.setTracer(tau, fill_value=CFILL, missing_value=CMISSING, reference=REF)
+        f.setClassTracer(sigs[name])
+        f.setClassEdges(edges[name])
+        return f
+
+    for name in sigs:
+        full = make(name)
+        want = numpy.array([_trows(full, t) for t in range(NT)])
+        pwant = numpy.array([_tprof(full, t) for t in range(NT)])
+        assert numpy.abs(want).max() > 0 and numpy.abs(pwant).max() > 0
+        acc, pacc = numpy.zeros_like(want), numpy.zeros_like(pwant)
+        for r in range(world):
+            sr = slab_range(NT, NZ, r, world)
+            part = make(name, slab_range=sr)
+            for t in range(NT):
+                out = torch.full((edges[name].size + 2, part._rowlen), numpy.nan, dtype=torch.float64, device='cuda')
+                pout = torch.full((NZ, part._rowlen), numpy.nan, dtype=torch.float64, device='cuda')
+                rows, prof = _trows(part, t, out=out), _tprof(part, t, out=pout)
+                assert numpy.array_equal(rows, reduce_rows(out).cpu().numpy())
+                assert numpy.array_equal(prof, reduce_rows(pout).cpu().numpy())
+                assert numpy.array_equal(rows, _trows(part, t)) and numpy.array_equal(prof, _tprof(part, t))
+                lo, hi = max(sr[0], t * NZ), min(sr[1], (t + 1) * NZ)
+                if hi <= lo:
+                    assert numpy.all(rows == 0) and numpy.all(prof == 0), (name, r, t)
+                owned = numpy.zeros(NZ, bool)
+                owned[max(lo - t * NZ, 0):max(hi - t * NZ, 0)] = True
+                assert numpy.all(prof[~owned] == 0), (name, r, t)
+                acc[t] += rows
+                pacc[t] += prof
+        assert numpy.array_equal(pacc, pwant)         # every level is owned by exactly one rank
+        if name == 'level':
+            assert numpy.array_equal(acc, want)
+        else:
+            assert numpy.allclose(acc, want, rtol=1e-13, atol=1e-13 * numpy.abs(want).max())
+
+
+def _h5_files():
+    h5 = os.path.join(GOLDEN, 'h5')
+    return dict(tFile=os.path.join(h5, 'nemo_T.h5'), uFile=os.path.join(h5, 'nemo_U.h5'), vFile=os.path.join(h5, 'nemo_V.h5'))
+
+
+H5_LINES = "[(-100,-80),(100,-80),(0,80)],[(-180,-70),(-160,-10),(-35,40),(20,-50),(60,50),(180,40)]"
+H5_EDGES = [-0.3, -0.1, 0., 0.05, 0.2]
+
+
+def _h5_arrays():
+    from nemoflux_amd import hdf5min
+    files = _h5_files()
+    with hdf5min.File(files['tFile']) as f:
+        blon, blat = f.datasets['bounds_lon'].read(), f.datasets['bounds_lat'].read()
+        db = f.datasets['deptht_bounds'].read()
+    with hdf5min.File(files['uFile']) as f:
+        u = numpy.array(f.datasets['uo'].read())
+        ufill = float(f.datasets['uo'].fill_value)
+    with hdf5min.File(files['vFile']) as f:
+        v = numpy.array(f.datasets['vo'].read())
+        vfill = f.datasets['vo'].fill_value
+    return blon, blat, db, u, v, ufill, (numpy.nan if vfill is None else float(vfill))
+
+
+def test_file_backed_fields_and_both_tracers_equal_from_arrays():
+    """file-backed uo / vo, carried tracer (uo of nemo_U.h5) and class field (vo of nemo_V.h5) give the rows of fromArrays
+    with the decoded arrays, bit for bit, in the step order 2, 0, 1, 1"""
+    from nemoflux_amd.field import Field
+    from nemoflux_amd.fluxplot import readTargets
+    files = _h5_files()
+    tr = readTargets(H5_LINES)[0]
+    ff = _quiet(Field, files['tFile'], files['uFile'], files['vFile'], tr)
+    ff.setTracer((files['uFile'], 'uo'), reference=0.01)
+    ff.setClassTracer((files['vFile'], 'vo'))
+    ff.setClassEdges(H5_EDGES)
+    blon, blat, db, u, v, ufill, vfill = _h5_arrays()
+    fa = _field(blon, blat, db, u, v, tr, fill_value=ufill)
+    fa.setTracer(u.copy(), fill_value=ufill, reference=0.01)
+    fa.setClassTracer(v.copy(), fill_value=vfill)
+    fa.setClassEdges(H5_EDGES)
+    for t in (2, 0, 1, 1):
+        got = _trows(ff, t)
+        assert numpy.array_equal(got, _trows(fa, t)), t
+        assert (numpy.abs(got).max(axis=1) > 0).sum() >= 4
+        prof = _tprof(ff, t)
+        assert numpy.array_equal(prof, _tprof(fa, t)), t
+        assert numpy.array_equal(_rows(ff.computeClassTransport(t)), _rows(fa.computeClassTransport(t))), t
+        row = _tracer_row(fa, t)
+        assert numpy.allclose(got.sum(axis=0), row, rtol=1e-12, atol=1e-12 * numpy.abs(got).sum())
+        assert numpy.allclose(prof.sum(axis=0), row, rtol=1e-12, atol=1e-12 * numpy.abs(prof).sum())
+
+
+def test_out_tensors_are_checked_by_both_new_calls():
+    """computeTracerProfile and computeClassTracerTransport write (rows, row_length) doubles through the pointer of `out`:
+    each refuses a float32, a mis-shaped, a host and a non-contiguous tensor and accepts the right one"""
+    import torch
+    u = _case('float64')[3]
+    f = _field(*_args('float64', True), **_kw(False))
+    f.setTracer(_on(_carried(u.shape, u.dtype, 41), True), fill_value=CFILL, missing_value=CMISSING, reference=REF)
+    f.setClassTracer(_on(_level_tau(u.shape, u.dtype), True))
+    f.setClassEdges(LEVEL_EDGES)
+    calls = [(NZ, lambda out: f.computeTracerProfile(1, out=out)),
+             (LEVEL_EDGES.size + 2, lambda out: f.computeClassTracerTransport(1, out=out))]
+    for nrows, call in calls:
+        want = _rows(call(None))
+        assert want.shape == (nrows, f._rowlen) and numpy.abs(want).max() > 0
+        for shape, dtype in (((nrows, f._rowlen), torch.float32), ((nrows + 1, f._rowlen), torch.float64),
+                             ((nrows, f._rowlen + 1), torch.float64), ((nrows * f._rowlen,), torch.float64)):
+            with pytest.raises(RuntimeError, match='out must be'):
+                call(torch.zeros(shape, dtype=dtype, device='cuda'))
+        with pytest.raises(RuntimeError, match='out must be'):
+            call(torch.zeros((nrows, f._rowlen), dtype=torch.float64))                      # not on the GPU
+        with pytest.raises(RuntimeError, match='out must be'):
+            call(torch.zeros((f._rowlen, nrows), dtype=torch.float64, device='cuda').t())   # not contiguous
+        out = torch.full((nrows, f._rowlen), numpy.nan, dtype=torch.float64, device='cuda')
+        assert numpy.array_equal(_rows(call(out)), want)
+        assert numpy.array_equal(out.cpu().numpy(), want)
+
+
+def test_host_class_tracer_stages_its_owned_levels_like_hbm():
+    """a host-resident class tracer is staged into a buffer of its own, the owned levels only: whole steps, a slab range
+    inside a step and whole steps again on one handle give the rows of the HBM-resident field, for both dtypes"""
+    from nemoflux_amd._lib import lib, check
+    cut = (NZ + 2, 2 * NZ - 1)           # levels 2 .. NZ - 2 of step 1
+    for real in ('float32', 'float64'):
+        u = _case(real)[3]
+        sig, tau = _class_field(u.shape, u.dtype, 43), _carried(u.shape, u.dtype, 44)
+        rows = []
+        for resident in (False, True):
+            f = _field(*_args(real, resident), **_kw(False))
+            f.setTracer(_on(tau, resident), fill_value=CFILL, missing_value=CMISSING)
+            f.setClassTracer(_on(sig, resident), fill_value=TFILL, missing_value=TMISSING)
+            f.setClassEdges(SMALL_EDGES)
+            whole = _trows(f, 1)
+            check(lib.nf_field_set_slab_range(ctypes.byref(f._h), *cut))
+            part = _trows(f, 1)
+            check(lib.nf_field_set_slab_range(ctypes.byref(f._h), 0, NT * NZ))
+            assert numpy.array_equal(_trows(f, 1), whole)
+            assert numpy.abs(part).max() > 0 and not numpy.array_equal(part, whole)
+            rows.append((whole, part))
+        assert numpy.array_equal(rows[0][0], rows[1][0]) and numpy.array_equal(rows[0][1], rows[1][1]), real
+
+
+def _read_csv(path):
+    with open(path) as fh:
+        text = fh.read().splitlines()
+    return text[0], text[1], [ln.split(',') for ln in text[2:]]
+
+
+def test_fluxplot_levels_is_the_field_profile(tmp_path):
+    from nemoflux_amd import fluxplot
+    from nemoflux_amd.field import Field
+    files = _h5_files()
+    lines = fluxplot.readTargets(H5_LINES)[0]
+    for tracer in ('', 'uo'):
+        out = str(tmp_path / f'levels_{tracer}.csv')
+        kw = dict(tracer='uo', tracerFile=files['uFile'], tracerRef=0.01, tracerScale=2.5) if tracer else {}
+        _quiet(fluxplot.main, lonLatPoints=H5_LINES, output=out, sverdrup=True, levels=True, **kw, **files)
+        title, header, body = _read_csv(out)
+        assert title == ('# transport of uo per level [uo x Sv x 2.5]' if tracer else '# water flow per level [Sv]')
+        assert header == 'time,ztop,zbot,line0,line1'
+        ff = _quiet(Field, files['tFile'], files['uFile'], files['vFile'], lines, True)
+        if tracer:
+            ff.setTracer((files['uFile'], 'uo'), reference=0.01)
+        assert len(body) == ff.nt * ff.nz
+        for t in range(ff.nt):
+            want = (ff.computeTracerProfile(t)[0] * 2.5) if tracer else ff.computeFluxProfile(t)[0]
+            for z in range(ff.nz):
+                ln = body[t * ff.nz + z]
+                assert (float(ln[1]), float(ln[2])) == tuple(float(x) for x in ff.bounds_depth[z])
+                assert numpy.allclose([float(x) for x in ln[3:]], want[z], rtol=1e-14, atol=1e-300)
+        assert numpy.abs(want).max() > 0
+
+
+def test_fluxplot_carry_is_the_field_table(tmp_path):
+    from nemoflux_amd import fluxplot
+    from nemoflux_amd.field import Field
+    files = _h5_files()
+    out = str(tmp_path / 'carry.csv')
+    _quiet(fluxplot.main, lonLatPoints=H5_LINES, output=out, sverdrup=True, tracer='vo', tracerFile=files['vFile'],
+           classes=','.join(str(e) for e in H5_EDGES), carry='uo', carryFile=files['uFile'], carryRef=0.01, carryScale=2.5,
+           **files)
+    title, header, body = _read_csv(out)
+    assert title == '# transport of uo by vo class [uo x Sv x 2.5]'
+    assert header == 'time,lower,upper,line0,line1'
+    nrow = len(H5_EDGES) + 2
+    ff = _quiet(Field, files['tFile'], files['uFile'], files['vFile'], fluxplot.readTargets(H5_LINES)[0], True)
+    ff.setTracer((files['uFile'], 'uo'), reference=0.01)
+    ff.setClassTracer((files['vFile'], 'vo'))
+    ff.setClassEdges(H5_EDGES)
+    assert len(body) == ff.nt * nrow
+    bounds = [(-numpy.inf, H5_EDGES[0])] + list(zip(H5_EDGES[:-1], H5_EDGES[1:])) + [(H5_EDGES[-1], numpy.inf)]
+    for t in range(ff.nt):
+        want = ff.computeClassTracerTransport(t)[0] * 2.5
+        for k in range(nrow):
+            ln = body[t * nrow + k]
+            lo, hi = float(ln[1]), float(ln[2])
+            if k < nrow - 1:
+                assert (lo, hi) == bounds[k]
+            else:
+                assert numpy.isnan(lo) and numpy.isnan(hi)
+            assert numpy.allclose([float(x) for x in ln[3:]], want[k], rtol=1e-14, atol=1e-300)
+    assert numpy.abs(want).max() > 0
