@@ -82,6 +82,17 @@ int main(void)
     const double flux2 = row[nseg + tid];
     printf("level 2: %d segments, flux = %.12f (max |edge flux| %.6g)\n", nseg, flux2, maxabs);
 
+    /* per-cell layer thicknesses (e3u, e3v at the indices of uo, vo): half the nominal layer everywhere halves the flux;
+     * NULL goes back to `thickness` */
+    static double e3[NY][NX];
+    for (int j = 0; j < NY; ++j)
+        for (int i = 0; i < NX; ++i) e3[j][i] = 0.5;
+    CHECK(nf_field_set_cell_thickness(&fld, e3, e3, 1, NF_F64, 0, NAN));
+    CHECK(nf_field_compute_flux(&fld, 0, row));
+    const double flux_half = row[nseg + tid];
+    CHECK(nf_field_set_cell_thickness(&fld, NULL, NULL, 0, NF_F64, 0, NAN));
+    printf("level 2 with e3u = e3v = 0.5: flux = %.12f\n", flux_half);
+
     /* ---- Level 1: mint's call sequence on the host array */
     Grid_t *grid = NULL;
     PolylineIntegral_t *pli = NULL;
@@ -144,7 +155,7 @@ int main(void)
     CHECK(mnt_grid_del(&grid));
     CHECK(nf_field_del(&fld));
     free(row);
-    const int ok = fabs(flux2 - 360.0) < 1e-9 && fabs(flux1 - 360.0) < 1e-9 && rc == NF_ERR_ARG && ncells == NY * NX &&
+    const int ok = fabs(flux2 - 360.0) < 1e-9 && fabs(flux1 - 360.0) < 1e-9 && fabs(flux_half - 180.0) < 1e-9 && rc == NF_ERR_ARG && ncells == NY * NX &&
                    decoded == 1.0f && status == 0 && nranks == 1 && myrank == 0 && reduced[0] == 1.5 && reduced[2] == 360.0;
     printf(ok ? "C client OK\n" : "C client FAILED\n");
     return ok ? 0 : 2;

@@ -328,6 +328,31 @@ int nf_field_set_class_tracer_missing_value(nf_field **self, double missing_valu
  * resident planes, |.| arrays, running max, last row, tracer planes or a captured pass. */
 int nf_field_compute_class_tracer_transport(nf_field **self, long tIndex, double *rows_host);        /* (nedges+2, row_length) */
 int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, double *rows_dev);   /* HBM, field's stream */
+/* Per-cell layer thicknesses (partial steps, z* / variable-volume runs): the model's e3u / e3v, or thkcello on the U and V
+ * grids, in place of the one number per level of nf_field_set_thickness.  e3u sits on the index of uo (the east face of cell
+ * (j, i)), e3v on the index of vo: no interpolation, no neighbour.  Definition, with th_z read at the face:
+ *   fixth(x) = 0 if x is NaN or one of the thickness's own two markers (compared in its dtype), else (double)x
+ *   accU(c) = fma(fixth(e3u[t',z,c]), fixed(uo[t,z,c]), accU(c)), accV(c) likewise with e3v and vo, z ascending over the
+ *   owned levels; t' = t for a time-varying thickness (nt_th == nt), 0 for a static one (nt_th == 1).
+ * The arc lengths and signs, the Sverdrup scale, the south and west copies, the |.| arrays, the running max and the transect
+ * reduction are those of the volume rows.  The tracer rows take fma(fixth(e3u), fixed(u) * tf, accU); level z's row of
+ * nf_field_compute_profile takes, per slot, the thickness at the slot's own face (east e3u[c], north e3v[c], south e3v of the
+ * south cell, west e3u of the west cell), so it stays the volume row of a field whose e3u, e3v are zero on every other level.
+ * Bit for bit: e3u == e3v == thickness[z] everywhere gives the rows, the six resident planes, the running max, the profile and
+ * the tracer rows of the field without a cell thickness; nf_field_compute_all_async rows equal the per-step rows.
+ * Untouched: nf_field_set_thickness stays required (it fixes nz) and is the thickness of every form again once the cell
+ * thickness is cleared; with none set every call computes what it computed before.
+ * Shape (nt_th, nz, ny, nx), x fastest, nt_th == 1 or nt, in the dtype of uo / vo -- else NF_ERR_ARG, the message naming both
+ * dtypes or both step counts; set_uv and set_thickness first, else NF_ERR_STATE.  on_device = 1: HBM pointers, used in place.
+ * on_device = 0: a time-varying host array is staged one step at a time, owned levels only, into buffers of its own; a
+ * static one is uploaded once, at the call (set_bounds first).  e3u == NULL goes back to the per-level thickness and forgets
+ * the markers.  Setting or clearing invalidates a captured pass; the all-steps-in-one-launch form of small grids is not used
+ * while one is set.  Refused while one is set (NF_ERR_STATE, the message saying how to clear it): the forms that do not take
+ * per-cell thicknesses yet -- nf_field_compute_tracer_profile*, nf_field_compute_class_transport* and
+ * nf_field_compute_class_tracer_transport*. */
+int nf_field_set_cell_thickness(nf_field **self, const void *e3u, const void *e3v, long nt_th, int dtype, int on_device,
+                                double fill_value);
+int nf_field_set_cell_thickness_missing_value(nf_field **self, double missing_value);   /* NaN = none */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

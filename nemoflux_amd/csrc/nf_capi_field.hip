@@ -130,6 +130,16 @@ struct nf_field {
     double sig_fill = std::numeric_limits<double>::quiet_NaN();
     double sig_fill2 = std::numeric_limits<double>::quiet_NaN();
     DevArray<char> stage_sig;   // host-resident class tracer: the owned levels of one step, sized in bytes like stage_tau
+    // per-cell layer thicknesses (nf_field_set_cell_thickness): e3u / e3v of (e3_nt, nz, ny, nx), e3_nt == 1 (static) or nt, in
+    // the dtype of uo / vo; nullptr: the per-level thickness above.  A static host array is uploaded once into e3?_static
+    // and counts as resident from then on; a time-varying host array is staged per step, owned levels only.  Setting or
+    // clearing them changes `version`.
+    const void *e3u = nullptr, *e3v = nullptr;
+    long e3_nt = 0;
+    int e3_dtype = NF_F64, e3_on_device = 1;
+    double e3_fill = std::numeric_limits<double>::quiet_NaN();
+    double e3_fill2 = std::numeric_limits<double>::quiet_NaN();   // nf_field_set_cell_thickness_missing_value
+    DevArray<char> e3u_static, e3v_static, stage_e3u, stage_e3v;
     // tracer profile (nf_field_compute_tracer_profile): the run sums of one chunk (ws.nrec * tracer_profile_chunk(dtype))
     DevArray<double> tprof_scratch;
     // class transport (nf_field_set_class_edges): the edges on the host, uploaded by the next compute after a change; the run
@@ -216,14 +226,34 @@ static int field_reserve_events(nf_field *f, size_t n)
     return NF_OK;
 }
 
+// The flux launch of a step: K1, or with per-cell thicknesses (ct) the kernel of nf_cellthick.hip into the signed planes a.iV
+// points at, followed -- unless the step is signed-only -- by the expansion into the other four, as in K1's split store form
+static int field_flux_kernels(nf_field *f, FluxArgs &a, const CellThick *ct)
+{
+    if (!ct) return launch_flux(a, f->stream);
+    CellThickArgs c;
+    c.in = StepInput{a.u, a.v, a.dtype, a.ncell, a.ny, a.nx, a.z0, a.z1, a.thickness, a.arcE, a.arcN, a.fill, a.fill2, a.scale,
+                     a.sverdrup};
+    c.th = *ct;
+    c.planes = a.iV + a.ncell;
+    c.maxbits = a.maxbits;
+    NF_TRY(launch_cellthick_flux(c, f->stream));
+    if (a.signed_only) return NF_OK;
+    if (a.mid_event) {
+        NF_HIP(hipEventRecord(a.mid_event, f->stream));
+        if (a.mid_recorded) *a.mid_recorded = true;
+    }
+    return launch_expand_planes(a.iV, a.absU, a.ncell, a.ny, a.nx, f->stream);
+}
+
 // one flux launch (and, in the default step, the expansion behind it) on the field's stream; with timing on, bracketed by
 // events
-static int field_launch_flux(nf_field *f, FluxArgs &a)
+static int field_launch_flux(nf_field *f, FluxArgs &a, const CellThick *ct = nullptr)
 {
-    if (!f->timing) return launch_flux(a, f->stream);
+    if (!f->timing) return field_flux_kernels(f, a, ct);
     if (f->ev_used >= kMaxTimedLaunches) {   // nobody reads the timing: keep computing, stop recording
         ++f->ev_dropped;
-        return launch_flux(a, f->stream);
+        return field_flux_kernels(f, a, ct);
     }
     NF_TRY(field_reserve_events(f, f->ev_used + 1));   // no-op when nf_field_timing reserved enough
     const size_t k = f->ev_used++;
@@ -231,7 +261,7 @@ static int field_launch_flux(nf_field *f, FluxArgs &a)
     a.mid_event = f->ev[k].mid;
     a.mid_recorded = &mid;
     NF_HIP(hipEventRecord(f->ev[k].e0, f->stream));
-    const int rc = launch_flux(a, f->stream);
+    const int rc = field_flux_kernels(f, a, ct);
     a.mid_event = nullptr;
     a.mid_recorded = nullptr;
     f->ev[k].has_mid = mid;
@@ -347,6 +377,31 @@ static int field_step_input(nf_field *f, long t, Levels lv, StepInput *in)
     return NF_OK;
 }
 
+// the per-cell thicknesses that go with step t (none set: th->e3u stays nullptr): a static array is its one step, a
+// host-resident time-varying one is staged like uo / vo
+static int field_cell_thick(nf_field *f, long t, Levels lv, CellThick *th)
+{
+    *th = CellThick{};
+    if (!f->e3u) return NF_OK;
+    NF_REQUIRE(f->e3_dtype == f->uv_dtype, NF_ERR_ARG, "compute: the cell thickness's dtype differs from the dtype of uo/vo");
+    NF_REQUIRE(f->e3_nt == 1 || f->e3_nt == f->nt, NF_ERR_ARG, "compute: the cell thickness's nt differs from the nt of uo/vo");
+    const long tt = f->e3_nt == 1 ? 0 : t;
+    NF_TRY(field_stage(f, f->e3u, f->e3_on_device, tt, lv, &f->stage_e3u, &th->e3u));
+    NF_TRY(field_stage(f, f->e3v, f->e3_on_device, tt, lv, &f->stage_e3v, &th->e3v));
+    th->fill = f->e3_fill;
+    th->fill2 = f->e3_fill2;
+    return NF_OK;
+}
+
+// the forms that do not take per-cell thicknesses yet: refused while one is set
+static int field_no_cell_thick(const nf_field *f, const char *what)
+{
+    NF_REQUIRE(!f->e3u, NF_ERR_STATE,
+               std::string(what) + ": this form does not take per-cell thicknesses yet and a cell thickness is set; "
+                                   "nf_field_set_cell_thickness(NULL) clears it");
+    return NF_OK;
+}
+
 // K1's arguments for a step: FluxArgs begins with the fields of StepInput, in the same order; its outputs are the caller's
 static FluxArgs flux_args(const StepInput &in)
 {
@@ -399,6 +454,8 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     }
     StepInput in;
     NF_TRY(field_step_input(f, t, lv, &in));
+    CellThick ct;
+    NF_TRY(field_cell_thick(f, t, lv, &ct));
     FluxArgs a = flux_args(in);
     a.iV = f->geo.iV.get();
     // uv2 holds planes 1 and 2 only: the signed-only kernel stores to iV + ncell and iV + 2 * ncell, nothing below
@@ -413,10 +470,11 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     // the C4 size; the rows are bit-identical (test_slab_sharding_sums_to_full).  nf_tuning_set("partial_step_planes", 1) keeps the
     // six-plane epilogue on partial steps (the before / after measurement of profiles/r04_rank_emulation.txt).
     const bool partial = (lv.z0 > 0 || lv.z1 < (int)f->nz) && !g_partial_full;
-    a.signed_only = (f->compact || partial || form.inner) && flux_supports_signed_only(a);
+    // (the cell-thickness kernel stores the signed planes in every form, one cell per lane included)
+    a.signed_only = (f->compact || partial || form.inner) && (ct.e3u || flux_supports_signed_only(a));
     NF_REQUIRE(!form.to_uv2 || a.signed_only, NF_ERR_STATE, "compute: a step into the second planes must be signed-only");
     if (!form.to_uv2) f->derived_stale = a.signed_only != 0;
-    NF_TRY(field_launch_flux(f, a));
+    NF_TRY(field_launch_flux(f, a, ct.e3u ? &ct : nullptr));
     if (reduce) {
         NF_TRY(field_integral(f, f->geo.iV.get(), f->scratch.get(), row_dev));
         NF_TRY(field_timed_k3_end(f));
@@ -476,6 +534,8 @@ static int field_profile_async(nf_field *f, long t, double *prof_dev, bool trace
     if (tracer) {
         NF_TRY(field_tracer_input(f, t, lv, &a));
         a.ref = f->tau_ref;
+    } else {
+        NF_TRY(field_cell_thick(f, t, lv, &a.th));
     }
     a.tr = field_transects(f);
     a.scratch = scratch.get();
@@ -496,6 +556,7 @@ static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
     TracerArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
     NF_TRY(field_tracer_input(f, t, lv, &a));
+    NF_TRY(field_cell_thick(f, t, lv, &a.th));
     NF_TRY(f->geo.tr_planes.reserve((size_t)f->ncell * 2));
     a.ref = f->tau_ref;
     a.planes = f->geo.tr_planes.get();
@@ -585,7 +646,8 @@ static bool field_can_batch(const nf_field *f)
     // launch-bound grids only: from about a million cells on, one launch per step (with the one-field form of the flux
     // kernel for its few wavefronts) is as fast or faster -- 1440 x 1021: 700 vs 733 us per 4-step pass at float32, 1166 vs
     // 1144 at float64; 2160 x 1080: 1035 vs 1187 and 1863 vs 1928 (tools/size_sweep.py, profiles/r04_size_sweep.txt)
-    return g_batch_steps && f->uv_on_device && f->nt >= 2 && f->nt < 65536 && f->nt * f->ncell <= batch_cell_steps() &&
+    // (the all-steps-in-one-launch form exists for K1 only: off while a cell thickness is set)
+    return g_batch_steps && !f->e3u && f->uv_on_device && f->nt >= 2 && f->nt < 65536 && f->nt * f->ncell <= batch_cell_steps() &&
            f->ncell <= (1l << 20) && f->weights_built;
 }
 
@@ -1038,8 +1100,8 @@ try {
     if (field_can_batch(f)) return field_all_steps_batched(f, rows_dev);
     NF_TRY(field_prepare_pass(f));   // allocations stay out of a graph capture
     // Replay a captured graph of the whole pass when nothing changed since it was captured.  Capture needs a real
-    // (non-null) stream, resident fields, and no per-launch timing events.
-    const bool can_graph = g_use_graph && f->stream != nullptr && f->uv_on_device && !f->timing;
+    // (non-null) stream, resident fields (a cell thickness included), and no per-launch timing events.
+    const bool can_graph = g_use_graph && f->stream != nullptr && f->uv_on_device && (!f->e3u || f->e3_on_device) && !f->timing;
     if (can_graph && f->graph_exec && f->graph_rows == rows_dev && f->graph_version == field_pass_version(f)) {
         NF_HIP(hipGraphLaunch(f->graph_exec, f->stream));
         return NF_OK;
@@ -1185,6 +1247,7 @@ try {
     NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_transport: null argument");
     nf_field *f = *self;
     NF_TRY(field_class_ready(f, "nf_field_compute_class_transport"));
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport"));
     NF_NEED_DEVICE();
     const size_t n = (f->class_edges.size() + 2) * (size_t)field_row_length(f);
     if (n == 0) return NF_OK;
@@ -1197,6 +1260,7 @@ try {
     NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_transport_async: null argument");
     nf_field *f = *self;
     NF_TRY(field_class_ready(f, "nf_field_compute_class_transport_async"));
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport_async"));
     NF_NEED_DEVICE();
     return field_class_step_async(f, tIndex, rows_dev);
 }
@@ -1207,6 +1271,7 @@ try {
     NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_tracer_profile: null argument");
     nf_field *f = *self;
     NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_profile: set_tracer first");
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_tracer_profile"));
     NF_TRY(field_ready(f, "compute_tracer_profile", true));
     NF_NEED_DEVICE();
     const size_t n = (size_t)f->nz * field_row_length(f);
@@ -1220,6 +1285,7 @@ try {
     NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_tracer_profile_async: null argument");
     nf_field *f = *self;
     NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_profile_async: set_tracer first");
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_tracer_profile_async"));
     NF_TRY(field_ready(f, "compute_tracer_profile", true));
     NF_NEED_DEVICE();
     return field_profile_async(f, tIndex, prof_dev, true);
@@ -1266,11 +1332,78 @@ try {
 }
 NF_API_CATCH
 
+int nf_field_set_cell_thickness(nf_field **self, const void *e3u, const void *e3v, long nt_th, int dtype, int on_device,
+                                double fill_value)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_cell_thickness: null field");
+    nf_field *f = *self;
+    if (!e3u) {   // back to the per-level thickness
+        f->e3u = f->e3v = nullptr;
+        f->e3_nt = 0;
+        f->e3_fill = f->e3_fill2 = std::numeric_limits<double>::quiet_NaN();
+        f->e3u_static.reset(), f->e3v_static.reset(), f->stage_e3u.reset(), f->stage_e3v.reset();
+        ++f->version;
+        return NF_OK;
+    }
+    NF_REQUIRE(e3v, NF_ERR_ARG, "nf_field_set_cell_thickness: e3v is null (both arrays or neither)");
+    NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_cell_thickness: dtype must be NF_F64/NF_F32");
+    NF_REQUIRE(f->u && f->v, NF_ERR_STATE, "nf_field_set_cell_thickness: set_uv and set_thickness first");
+    char buf[200];
+    if (dtype != f->uv_dtype) {
+        snprintf(buf, sizeof buf, "nf_field_set_cell_thickness: the cell thickness's dtype is %s, uo/vo are %s",
+                 dtype == NF_F32 ? "float32" : "float64", f->uv_dtype == NF_F32 ? "float32" : "float64");
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    if (nt_th != 1 && nt_th != f->nt) {
+        snprintf(buf, sizeof buf, "nf_field_set_cell_thickness: the cell thickness has nt = %ld time steps, need 1 (static) or "
+                 "the %ld of uo/vo", nt_th, f->nt);
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    NF_REQUIRE(f->thick.get(), NF_ERR_STATE, "nf_field_set_cell_thickness: set_thickness first (it fixes nz)");
+    const bool upload = !on_device && nt_th == 1;   // a static host array: uploaded once, here
+    if (upload) {
+        NF_REQUIRE(f->ncell > 0, NF_ERR_STATE, "nf_field_set_cell_thickness: set_bounds first");
+        NF_NEED_DEVICE();
+        const size_t bytes = (size_t)f->nz * f->ncell * elem_size(dtype);
+        DevArray<char> du, dv;
+        NF_TRY(du.alloc(bytes));
+        NF_TRY(dv.alloc(bytes));
+        NF_HIP(hipMemcpy(du.get(), e3u, bytes, hipMemcpyHostToDevice));
+        NF_HIP(hipMemcpy(dv.get(), e3v, bytes, hipMemcpyHostToDevice));
+        NF_HIP(hipStreamSynchronize(f->stream));   // kernels in flight may still read the arrays these replace
+        f->e3u_static = std::move(du);
+        f->e3v_static = std::move(dv);
+        e3u = f->e3u_static.get();
+        e3v = f->e3v_static.get();
+    } else {
+        f->e3u_static.reset(), f->e3v_static.reset();
+    }
+    f->e3u = e3u;
+    f->e3v = e3v;
+    f->e3_nt = nt_th;
+    f->e3_dtype = dtype;
+    f->e3_on_device = (on_device || upload) ? 1 : 0;
+    f->e3_fill = fill_value;
+    ++f->version;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_cell_thickness_missing_value(nf_field **self, double missing_value)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_cell_thickness_missing_value: null field");
+    (*self)->e3_fill2 = missing_value;
+    ++(*self)->version;
+    return NF_OK;
+}
+NF_API_CATCH
+
 int nf_field_compute_class_tracer_transport(nf_field **self, long tIndex, double *rows_host)
 try {
     NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_tracer_transport: null argument");
     nf_field *f = *self;
     NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport"));
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_tracer_transport"));
     NF_NEED_DEVICE();
     const size_t n = (f->class_edges.size() + 2) * (size_t)field_row_length(f);
     if (n == 0) return NF_OK;
@@ -1283,6 +1416,7 @@ try {
     NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_tracer_transport_async: null argument");
     nf_field *f = *self;
     NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport_async"));
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_tracer_transport_async"));
     NF_NEED_DEVICE();
     return field_class_step_async(f, tIndex, rows_dev, true);
 }

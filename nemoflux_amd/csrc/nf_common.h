@@ -345,7 +345,32 @@ struct StepInput {
 // With a carried tracer (tau != nullptr; nf_field_compute_tracer_profile) every term is multiplied by tr_face of the tracer at
 // its own face, as one level of the tracer transport: 4 + 5 gathers per level, kTracerProfileChunk levels at a time (float64)
 // or kTracerProfileChunkF32 (float32: half the registers per gathered value): tracer_profile_chunk(dtype), measured.
+// Per-cell layer thicknesses (nf_field_set_cell_thickness): e3u at the index of uo (the east face of the cell), e3v at the
+// index of vo, both (nz, ncell) of the field dtype at the base of the step that is read.  e3u == nullptr: the per-level
+// thickness of StepInput.  A thickness that is NaN or one of the two markers (compared in the field dtype) counts as 0.
+struct CellThick {
+    const void *e3u = nullptr, *e3v = nullptr;
+    double fill = __builtin_nan(""), fill2 = __builtin_nan("");   // NaN = none
+};
+// the same for a kernel of dtype T; thick_fixed is fixth() of the definition
+template <typename T>
+struct ThickIn {
+    const T *e3u, *e3v;
+    T m1, m2;
+};
+template <typename T>
+inline ThickIn<T> thick_in(const CellThick &c) { return ThickIn<T>{(const T *)c.e3u, (const T *)c.e3v, (T)c.fill, (T)c.fill2}; }
+template <typename T>
+__device__ inline double thick_fixed(T x, T m1, T m2)
+{
+    return (x != x || x == m1 || x == m2) ? 0.0 : (double)x;
+}
+
 constexpr int kProfileChunk = 8;
+// the volume profile with cell thicknesses: 4 + 4 gathers per level.  Four levels, the 32 gathers per lane that the scalar form
+// has in flight: 95 (float64) / 64 (float32) VGPRs, 5 / 8 waves per SIMD, no scratch (the scalar form: 93 / 66, 5 / 7); eight
+// levels take 159 / 98 VGPRs and 3 / 4 waves (-Rpass-analysis=kernel-resource-usage)
+constexpr int kCellThickProfileChunk = 4;
 constexpr int kTracerProfileChunk = 4;
 constexpr int kTracerProfileChunkF32 = 8;
 inline int tracer_profile_chunk(int dtype) { return dtype == NF_F32 ? kTracerProfileChunkF32 : kTracerProfileChunk; }
@@ -359,6 +384,7 @@ struct ProfileArgs {
     double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
     double ref = 0.0;
     int wrap_x = 1;
+    CellThick th;                // volume rows only (tau == nullptr): every slot's term takes the thickness at its own face
 };
 int launch_profile(const ProfileArgs &a, hipStream_t s);
 
@@ -372,8 +398,21 @@ struct TracerArgs {
     double ref = 0.0;         // reference value subtracted from every face value
     int wrap_x = 1;           // 1: the east face of column nx-1 takes column 0 as its neighbour
     double *planes = nullptr; // [2][ncell]: eU_tau, eV_tau
+    CellThick th;             // e3u set: fma(fixth(e3u), fixed(u) * tfE, accU), two more aligned streams
 };
 int launch_tracer_flux(const TracerArgs &a, hipStream_t s);
+
+// The volume step with cell thicknesses (nf_cellthick.hip): K1's vertical integral with the thickness read at the face,
+//   accU = fma(fixth(e3u[z, c]), fixed(uo[z, c]), accU), accV likewise with e3v and vo, z ascending over [z0, z1),
+// then K1's edge terms.  Writes the two signed planes [eU | eV] at `planes` and raises the running max, as the signed-only
+// form of K1 does; launch_expand_planes derives the other four.  in.thickness is not read.
+struct CellThickArgs {
+    StepInput in;
+    CellThick th;
+    double *planes = nullptr;             // [2][ncell]: eU, eV
+    unsigned long long *maxbits = nullptr;
+};
+int launch_cellthick_flux(const CellThickArgs &a, hipStream_t s);
 
 // K1's masking of uo / vo outside K1 (profile, class and tracer kernels): NaN or one of the two markers -> 0.  `two`: the second
 // marker counts (uv_two_markers: a number that differs from the first; NaN never compares equal, so a kernel without the flag

@@ -12,6 +12,8 @@
 // results are bitwise reproducible.
 //
 // Output row: [ per-segment sums (nseg) | per-transect sums (ntransect) ].
+#include <type_traits>
+
 #include "nf_common.h"
 
 namespace nf {
@@ -115,15 +117,31 @@ __device__ inline LevelUV<T> load_level_uv(const T *__restrict__ u, const T *__r
 // The carried-tracer form multiplies every masked velocity by the tracer at the slot's own face (FaceTf: east face of c, north
 // face of c, north face of cs, east face of cw): fma(th, fixed(x) * tf, 0) * arc, one level of k_tracer_flux's accumulation.
 struct FaceTf { double e, n, s, w; };
+// The thickness of each slot's term: the level's one number in all four (slot_th), or with per-cell thicknesses the value at
+// the slot's own face -- east e3u[c], north e3v[c], south e3v[cs], west e3u[cw] -- masked by thick_fixed (level_th).
+struct SlotTh { double e, n, s, w; };
+__device__ inline SlotTh slot_th(double th) { return SlotTh{th, th, th, th}; }
+template <typename T>
+__device__ inline LevelUV<T> load_level_e3(const ThickIn<T> &ct, long o, long c, const Neighbours &nb)
+{
+    return load_level_uv(ct.e3u, ct.e3v, o, c, nb);
+}
+template <typename T>
+__device__ inline SlotTh level_th(const LevelUV<T> &e3, const ThickIn<T> &ct)
+{
+    return SlotTh{thick_fixed<T>(e3.uc, ct.m1, ct.m2), thick_fixed<T>(e3.vc, ct.m1, ct.m2), thick_fixed<T>(e3.vs, ct.m1, ct.m2),
+                  thick_fixed<T>(e3.uw, ct.m1, ct.m2)};
+}
 template <typename T, bool TR>
-__device__ inline Slots level_slots_tf(double th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2, bool two, double scale,
+__device__ inline Slots level_slots_tf(const SlotTh &th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2, bool two, double scale,
                                        int sverdrup, bool south, const FaceTf &tf)
 {
-    auto term = [&](T x, double a, double f) {
+    auto term = [&](double th, T x, double a, double f) {
         const double xf = uv_fixed<T>(x, fill, fill2, two);
         return fma(th, TR ? xf * f : xf, 0.0) * a;
     };
-    Slots d{+term(x.uc, arc.Ec, tf.e), -term(x.vc, arc.Nc, tf.n), -term(x.vs, arc.Ns, tf.s), +term(x.uw, arc.Ew, tf.w)};
+    Slots d{+term(th.e, x.uc, arc.Ec, tf.e), -term(th.n, x.vc, arc.Nc, tf.n), -term(th.s, x.vs, arc.Ns, tf.s),
+            +term(th.w, x.uw, arc.Ew, tf.w)};
     if (sverdrup) d = Slots{d.e * scale, d.n * scale, d.s * scale, d.w * scale};
     if (!south) d.s = 0.0;
     return d;
@@ -132,7 +150,7 @@ template <typename T>
 __device__ inline Slots level_slots(double th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2, bool two, double scale,
                                     int sverdrup, bool south)
 {
-    return level_slots_tf<T, false>(th, x, arc, fill, fill2, two, scale, sverdrup, south, FaceTf{});
+    return level_slots_tf<T, false>(slot_th(th), x, arc, fill, fill2, two, scale, sverdrup, south, FaceTf{});
 }
 
 // The neighbour rule with the east and north cells that the faces of a tracer need (ce, cn: c itself where there is none).
@@ -177,6 +195,15 @@ template <typename T>
 __device__ inline TauIn<T> tau_in() { return TauIn<T>{}; }
 template <typename T>
 __device__ inline TauIn<T> tau_in(const TauIn<T> &ti) { return ti; }
+// ... and, for the profile, a volume form with per-cell thicknesses (one ThickIn): the other kind of argument is absent
+template <typename T>
+__device__ inline TauIn<T> tau_in(const ThickIn<T> &) { return TauIn<T>{}; }
+template <typename T>
+__device__ inline ThickIn<T> thick_arg() { return ThickIn<T>{}; }
+template <typename T>
+__device__ inline ThickIn<T> thick_arg(const TauIn<T> &) { return ThickIn<T>{}; }
+template <typename T>
+__device__ inline ThickIn<T> thick_arg(const ThickIn<T> &ct) { return ct; }
 // tr_face at the four slots' faces.  Row 0 has no south face: cs = c there and level_slots_tf discards the slot.
 template <typename T>
 __device__ inline FaceTf level_tf(const LevelTau<T> &t, const ClassNeighbours &nb, const TauIn<T> &ti)
@@ -386,7 +413,8 @@ static int check_raw_step(const char *what, const StepInput &in, const Transects
 // 4 x LZ gathers of a lane (4 + 5 with a carried tracer, TR) are all in flight together; then level_slots_tf and weighted_sum
 // per level and one seg_scan<LZ>.  runsum: (levels of the launch) x n doubles, level-major.
 // The volume form takes no trailing argument, the carried-tracer form (row z = the tracer transport of level z alone) one
-// TauIn<T>: TI is empty or TauIn<T>.
+// TauIn<T>: TI is empty or TauIn<T>.  The volume form with per-cell thicknesses takes one ThickIn<T> instead: four more
+// gathers per level, each slot's term with the thickness at its own face (level_th).
 template <typename T, int LZ, typename... TI>
 __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
                                                             const int *__restrict__ seg, long n, const T *__restrict__ u,
@@ -397,8 +425,10 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
                                                             double scale, int sverdrup, double *__restrict__ runsum,
                                                             TI... tracer)
 {
-    constexpr bool TR = sizeof...(TI) > 0;
+    constexpr bool TR = (std::is_same<TI, TauIn<T>>::value || ...);
+    constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
     const TauIn<T> ti = tau_in<T>(tracer...);
+    const ThickIn<T> ct = thick_arg<T>(tracer...);
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
     double val[LZ];
 #pragma unroll
@@ -411,10 +441,12 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
         LevelUV<T> x[LZ];
         LevelTau<T> tt[TR ? LZ : 1];
+        LevelUV<T> e3[CT ? LZ : 1];
 #pragma unroll
         for (int l = 0; l < LZ; ++l)
             if (l < nlev) {   // nlev is launch-uniform
                 x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);
+                if constexpr (CT) e3[l] = load_level_e3(ct, (long)(z0 + l) * ncell, r.c, nb);
                 if constexpr (TR) tt[l] = load_level_tau(ti.tau, (long)(z0 + l) * ncell, r.c, nb);
             }
 #pragma unroll
@@ -422,8 +454,12 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
             if (l < nlev) {
                 FaceTf tf{};
                 if constexpr (TR) tf = level_tf(tt[l], nb, ti);
-                val[l] = weighted_sum(r, level_slots_tf<T, TR>(thickness[z0 + l], x[l], arc, fill, fill2, two, scale, sverdrup,
-                                                               nb.south, tf));
+                SlotTh th;
+                if constexpr (CT)
+                    th = level_th(e3[l], ct);
+                else
+                    th = slot_th(thickness[z0 + l]);
+                val[l] = weighted_sum(r, level_slots_tf<T, TR>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, tf));
             }
     }
     if (seg_scan(val, key, k, n)) {
@@ -434,10 +470,13 @@ __global__ __launch_bounds__(kBlock) void k_profile_segscan(const int *__restric
 }
 
 
-template <typename T, bool TR>
+// FORM: 0 = volume, 1 = carried tracer, 2 = volume with per-cell thicknesses
+template <typename T, int FORM>
 static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 {
-    constexpr int chunk = !TR ? kProfileChunk : sizeof(T) == 4 ? kTracerProfileChunkF32 : kTracerProfileChunk;
+    constexpr bool TR = FORM == 1;
+    constexpr int chunk = FORM == 2 ? kCellThickProfileChunk
+                                    : !TR ? kProfileChunk : sizeof(T) == 4 ? kTracerProfileChunkF32 : kTracerProfileChunk;
     const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
     const long row_length = a.tr.row_length();
@@ -451,6 +490,11 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
                                    (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2,
                                    (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, a.scratch,
                                    TauIn<T>{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0});
+            else if constexpr (FORM == 2)
+                hipLaunchKernelGGL((k_profile_segscan<T, chunk, ThickIn<T>>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
+                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
+                                   (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2,
+                                   (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, a.scratch, thick_in<T>(a.th));
             else
                 hipLaunchKernelGGL((k_profile_segscan<T, chunk>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
                                    ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
@@ -466,11 +510,17 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 
 int launch_profile(const ProfileArgs &a, hipStream_t s)
 {
-    const bool tr = a.tau != nullptr;
-    NF_TRY(check_raw_step("profile", a.in, a.tr, a.scratch_len, tr ? tracer_profile_chunk(a.in.dtype) : kProfileChunk));
+    const bool tr = a.tau != nullptr, ct = a.th.e3u != nullptr;
+    NF_REQUIRE(!(tr && ct), NF_ERR_STATE, "profile: the tracer profile does not take per-cell thicknesses");
+    NF_REQUIRE(!ct || a.th.e3v, NF_ERR_ARG, "profile: null argument");
+    NF_TRY(check_raw_step("profile", a.in, a.tr, a.scratch_len,
+                          tr ? tracer_profile_chunk(a.in.dtype) : ct ? kCellThickProfileChunk : kProfileChunk));
     if (a.tr.row_length() == 0) return NF_OK;
-    if (a.in.dtype == NF_F64) return tr ? launch_profile_t<double, true>(a, s) : launch_profile_t<double, false>(a, s);
-    if (a.in.dtype == NF_F32) return tr ? launch_profile_t<float, true>(a, s) : launch_profile_t<float, false>(a, s);
+    const int form = tr ? 1 : ct ? 2 : 0;
+    if (a.in.dtype == NF_F64)
+        return form == 1 ? launch_profile_t<double, 1>(a, s) : form == 2 ? launch_profile_t<double, 2>(a, s) : launch_profile_t<double, 0>(a, s);
+    if (a.in.dtype == NF_F32)
+        return form == 1 ? launch_profile_t<float, 1>(a, s) : form == 2 ? launch_profile_t<float, 2>(a, s) : launch_profile_t<float, 0>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
 }
 
@@ -556,7 +606,7 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
                 if (l < nlev) {
                     FaceTf tf{};
                     if constexpr (CARRY) tf = level_tf(TWO ? tt[l] : LevelTau<T>{tc[l], te[l], tn[l], tw[l], ts[l]}, nb, ti);
-                    const Slots d = level_slots_tf<T, CARRY>(thickness[z + l], x[l], arc, fill, fill2, two, scale, sverdrup,
+                    const Slots d = level_slots_tf<T, CARRY>(slot_th(thickness[z + l]), x[l], arc, fill, fill2, two, scale, sverdrup,
                                                              nb.south, tf);
                     double f;
                     bool h;

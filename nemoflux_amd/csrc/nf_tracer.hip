@@ -15,6 +15,10 @@
 // a wavefront loads it itself, and the lane that holds a row's last column loads the row's first cell for the wrap.
 //
 // Algorithmic bytes per (t,z,j,i): 3*sizeof(T) read + (16 arc + 16 planes)/nz.
+//
+// Cell-thickness form (nf_field_set_cell_thickness; trailing kernel argument ThickIn<T>): th_z becomes the thickness read at
+// the face, accU = fma(fixth(e3u[z, c]), fixed(u) * tfE, accU) and accV with e3v -- two more aligned non-temporal streams,
+// 5*sizeof(T) per (t,z,j,i).  The form without the argument is the kernel as it was, instruction for instruction.
 #include "nf_common.h"
 
 namespace nf {
@@ -53,15 +57,22 @@ __device__ inline TrLanes<T, VEC> tr_load(const T *p)
 
 // 256 threads, one chunk of VEC cells per lane: lane c0 = (tile * 256 + tid) * VEC.  ncell % VEC == 0 and nx >= VEC (the
 // launcher picks VEC = 1 otherwise), so a lane's cells hold at most one row end.  NAL: nx % VEC == 0, the north stream is
-// 16-byte aligned too.
-template <typename T, int VEC, int UZ, bool NAL>
+// 16-byte aligned too.  TH: empty (per-level thickness) or one ThickIn<T>.
+template <typename T>
+__device__ inline ThickIn<T> tr_thick() { return ThickIn<T>{}; }
+template <typename T>
+__device__ inline ThickIn<T> tr_thick(const ThickIn<T> &th) { return th; }
+
+template <typename T, int VEC, int UZ, bool NAL, typename... TH>
 __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, const T *__restrict__ v,
                                                      const T *__restrict__ tau, long ncell, unsigned nx, int z0, int z1,
                                                      const double *__restrict__ thickness, const double *__restrict__ arcE,
                                                      const double *__restrict__ arcN, T fill, T fill2, T tfill, T tfill2,
                                                      double ref, int wrap_x, double scale, int sverdrup,
-                                                     double *__restrict__ planes, unsigned ntiles)
+                                                     double *__restrict__ planes, unsigned ntiles, TH... thick)
 {
+    constexpr bool CT = sizeof...(TH) > 0;
+    const ThickIn<T> ct = tr_thick<T>(thick...);
     const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
     if (tile >= ntiles) return;   // workgroup-uniform
     const int lane = threadIdx.x & (kWave - 1);
@@ -86,9 +97,12 @@ __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, co
     const T *pu = u + (long)z0 * ncell + cs;
     const T *pv = v + (long)z0 * ncell + cs;
     const T *pt = tau + (long)z0 * ncell + cs;
+    const T *pe = CT ? ct.e3u + (long)z0 * ncell + cs : nullptr;
+    const T *pf = CT ? ct.e3v + (long)z0 * ncell + cs : nullptr;
     for (int z = z0; z < z1; z += UZ) {
         const int nlev = z1 - z < UZ ? z1 - z : UZ;
         TrLanes<T, VEC> lu[UZ], lv[UZ], lt[UZ], ln[UZ];
+        TrLanes<T, VEC> le[CT ? UZ : 1], lf[CT ? UZ : 1];
         T nx1[UZ], wv[UZ];
 #pragma unroll
         for (int r = 0; r < UZ; ++r)
@@ -98,9 +112,17 @@ __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, co
                     lu[r] = tr_load<T, VEC, true>(pu + o);
                     lv[r] = tr_load<T, VEC, true>(pv + o);
                     lt[r] = tr_load<T, VEC, false>(pt + o);
+                    if constexpr (CT) {
+                        le[r] = tr_load<T, VEC, true>(pe + o);
+                        lf[r] = tr_load<T, VEC, true>(pf + o);
+                    }
                 } else {
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) lu[r].x[k] = lv[r].x[k] = lt[r].x[k] = T(0);
+                    if constexpr (CT) {
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) le[r].x[k] = lf[r].x[k] = T(0);
+                    }
                 }
                 if (north_all) {
                     ln[r] = tr_load<T, VEC, false, NAL>(pt + o + nx);
@@ -125,13 +147,22 @@ __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, co
                     const bool has_e = k != kend || wrap_x;
                     const double tfE = tr_face<T>(a, be, has_e, tfill, tfill2, ref);
                     const double tfN = tr_face<T>(a, ln[r].x[k], has_n[k], tfill, tfill2, ref);
-                    accU[k] = fma(th, uv_fixed<T>(lu[r].x[k], fill, fill2) * tfE, accU[k]);
-                    accV[k] = fma(th, uv_fixed<T>(lv[r].x[k], fill, fill2) * tfN, accV[k]);
+                    if constexpr (CT) {
+                        accU[k] = fma(thick_fixed<T>(le[r].x[k], ct.m1, ct.m2), uv_fixed<T>(lu[r].x[k], fill, fill2) * tfE, accU[k]);
+                        accV[k] = fma(thick_fixed<T>(lf[r].x[k], ct.m1, ct.m2), uv_fixed<T>(lv[r].x[k], fill, fill2) * tfN, accV[k]);
+                    } else {
+                        accU[k] = fma(th, uv_fixed<T>(lu[r].x[k], fill, fill2) * tfE, accU[k]);
+                        accV[k] = fma(th, uv_fixed<T>(lv[r].x[k], fill, fill2) * tfN, accV[k]);
+                    }
                 }
             }
         pu += (long)UZ * ncell;
         pv += (long)UZ * ncell;
         pt += (long)UZ * ncell;
+        if constexpr (CT) {
+            pe += (long)UZ * ncell;
+            pf += (long)UZ * ncell;
+        }
     }
     if (!on) return;
     // edge terms in K1's order (field.py:195-196, 225-228)
@@ -162,6 +193,9 @@ namespace {
 // levels per batch: four 16-byte streams per level.  Four levels: 110 VGPRs, 4 waves per SIMD, no scratch
 // (-Rpass-analysis=kernel-resource-usage); five levels take 133 VGPRs and 3 waves
 constexpr int kTracerLevels = 4;
+// the cell-thickness form has six 16-byte streams per level.  Three levels: 114 (float64) / 127 (float32) VGPRs, 4 waves per
+// SIMD, no scratch; four levels take 145 / 155 VGPRs and 3 waves, two 84 / 99 and 5 / 4 waves with a third fewer loads in flight
+constexpr int kTracerLevelsCellThick = 3;
 
 template <typename T, int VEC, bool NAL>
 int launch_tracer_t(const TracerArgs &a, hipStream_t s)
@@ -170,10 +204,16 @@ int launch_tracer_t(const TracerArgs &a, hipStream_t s)
     const long per_tile = 256l * VEC;
     const unsigned ntiles = (unsigned)((in.ncell + per_tile - 1) / per_tile);
     const unsigned grid = xcd_grid(ntiles);
-    hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevels, NAL>), dim3(grid), dim3(256), 0, s, (const T *)in.u,
-                       (const T *)in.v, (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
-                       in.arcN, (T)in.fill, (T)in.fill2, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0, in.scale,
-                       in.sverdrup, a.planes, ntiles);
+    if (a.th.e3u)
+        hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevelsCellThick, NAL, ThickIn<T>>), dim3(grid), dim3(256), 0, s,
+                           (const T *)in.u, (const T *)in.v, (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                           in.thickness, in.arcE, in.arcN, (T)in.fill, (T)in.fill2, (T)a.tfill, (T)a.tfill2, a.ref,
+                           a.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.planes, ntiles, thick_in<T>(a.th));
+    else
+        hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevels, NAL>), dim3(grid), dim3(256), 0, s, (const T *)in.u,
+                           (const T *)in.v, (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
+                           in.arcN, (T)in.fill, (T)in.fill2, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0, in.scale,
+                           in.sverdrup, a.planes, ntiles);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
@@ -182,7 +222,8 @@ template <typename T, int VEC>
 int launch_tracer_v(const TracerArgs &a, hipStream_t s)
 {
     const StepInput &in = a.in;
-    const bool al16 = ((uintptr_t)in.u % 16 == 0) && ((uintptr_t)in.v % 16 == 0) && ((uintptr_t)a.tau % 16 == 0);
+    const bool al16 = ((uintptr_t)in.u % 16 == 0) && ((uintptr_t)in.v % 16 == 0) && ((uintptr_t)a.tau % 16 == 0) &&
+                      ((uintptr_t)a.th.e3u % 16 == 0) && ((uintptr_t)a.th.e3v % 16 == 0);
     if (al16 && in.ncell % VEC == 0 && in.nx >= VEC)
         return in.nx % VEC == 0 ? launch_tracer_t<T, VEC, true>(a, s) : launch_tracer_t<T, VEC, false>(a, s);
     return launch_tracer_t<T, 1, true>(a, s);   // odd sizes / unaligned fields: one cell per lane
@@ -195,7 +236,7 @@ int launch_tracer_flux(const TracerArgs &a, hipStream_t s)
     NF_REQUIRE(in.ncell > 0 && in.nx > 0 && in.ncell == in.ny * in.nx && in.ncell < (1l << 31), NF_ERR_ARG,
                "tracer flux: bad grid sizes");
     NF_REQUIRE(in.z1 > in.z0 && in.z0 >= 0, NF_ERR_ARG, "tracer flux: empty z range");
-    NF_REQUIRE(in.u && in.v && a.tau && a.planes && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+    NF_REQUIRE(in.u && in.v && a.tau && a.planes && in.thickness && in.arcE && in.arcN && (!a.th.e3u || a.th.e3v), NF_ERR_ARG,
                "tracer flux: null argument");
     if (in.dtype == NF_F64) return launch_tracer_v<double, 2>(a, s);
     if (in.dtype == NF_F32) return launch_tracer_v<float, 4>(a, s);

@@ -38,6 +38,14 @@ def _native(a):
     return a if a.dtype.isnative else a.astype(a.dtype.newbyteorder('='))
 
 
+def _native_dtype(a):
+    """numpy dtype, in native byte order, of a host array, a file variable, a DeviceArray or a torch tensor"""
+    dt = a.dtype
+    if isinstance(dt, numpy.dtype):
+        return dt.newbyteorder('=')
+    return numpy.dtype(str(dt).replace('torch.', ''))
+
+
 def _geometry_only(bounds_lon, bounds_lat):
     """Run the geometry kernel alone: {'points': (ncell,4,3), 'arcLengths': (ncell,4), 'box': 4 floats}."""
     h = ctypes.c_void_p()
@@ -249,7 +257,8 @@ class Field(object):
         else:
             uv_dev = 1
         if self._lazy is None:
-            check(lib.nf_field_set_uv(ctypes.byref(self._h), pu, pv, self.nt, _dtype_code(uo), uv_dev, float(fill_value)))
+            self._uv_code = _dtype_code(uo)
+            check(lib.nf_field_set_uv(ctypes.byref(self._h), pu, pv, self.nt, self._uv_code, uv_dev, float(fill_value)))
         if missing_value == missing_value:   # a second marker (CF missing_value that differs from _FillValue)
             check(lib.nf_field_set_missing_value(ctypes.byref(self._h), float(missing_value)))
         check(lib.nf_field_set_sverdrup(ctypes.byref(self._h), 1 if sverdrup else 0))
@@ -446,6 +455,7 @@ class Field(object):
             # on this one: the blocking C call below releases the GIL
             nxt = self._stager.next_after(tIndex)
             self._stager.prefetch(nxt % self.nt if prefetch_next is None else (nxt if nxt < self.nt else -1))
+        self._stage_cell_thickness(tIndex)
 
     def _compute(self, tIndex, readback=None, prefetch_next=None):
         self._stage(tIndex, prefetch_next)
@@ -506,9 +516,10 @@ class Field(object):
         totals and (nt, nseg) per-segment sums.  `out`: optional torch CUDA tensor (nt, row_length) to
         receive the raw rows in HBM (for the RCCL reduce of nemoflux_amd.dist)."""
         import torch
-        if out is not None or self._lazy is None:
+        lazy = self._lazy is not None or self._cell_thickness_lazy()
+        if out is not None or not lazy:
             out = self._rows_out(out, self.nt)
-        if self._lazy is not None:
+        if lazy:
             # file-backed: one step on the GPU, the next one inflating into the other pinned slot (no wrap-around prefetch
             # after the last step)
             rows = numpy.array([self._compute(t, readback=False, prefetch_next=True).copy() for t in range(self.nt)])
@@ -616,6 +627,109 @@ class Field(object):
         self._class_tracer = self._tracer_slot(tracer, fill_value, missing_value, lib.nf_field_set_class_tracer,
                                                lib.nf_field_set_class_tracer_missing_value)
 
+    # ------------------------------------------------------------------------------------------
+    def setCellThickness(self, e3u, e3v, fill_value=None, missing_value=None):
+        """Per-cell layer thicknesses (partial steps, z* / variable-volume runs) in place of the one number per level of
+        deptht_bounds: e3u at the U points (the index of uo), e3v at the V points (the index of vo) -- the model's e3u / e3v,
+        or thkcello on the U and V grids.  Shape (nz, ny, nx) or (1, nz, ny, nx): static; (nt, nz, ny, nx): one per time step.
+        Each of e3u, e3v is a host array, a torch CUDA tensor or a DeviceArray (used in place), or a (path, name) pair read
+        with nemoflux_amd.io, its CF markers and scale / offset decoded as for uo: a time-varying pair one step at a time
+        into pinned buffers, a static one once.  A static host array of another float dtype is cast to the dtype of uo / vo
+        (a float64 mesh_mask thickness beside float32 velocities is rounded to float32); a device array or a time-varying
+        array of another dtype raises.  fill_value / missing_value: the thickness's own missing markers (a file's when not
+        given); a thickness that is NaN or a marker counts as 0.
+        computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux and computeTracerAll then integrate with
+        these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
+        set.  setCellThickness(None, None) goes back to deptht_bounds."""
+        self._e3 = None
+        self._row_valid = False
+        if e3u is None or e3v is None:
+            if e3u is not None or e3v is not None:
+                raise RuntimeError('ERROR: setCellThickness needs both e3u and e3v, or None for both')
+            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), None, None, 0, NF_F64, 0, numpy.nan))
+            return
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        markers, arrs = [], []
+        for e3, which in ((e3u, 'e3u'), (e3v, 'e3v')):
+            if isinstance(e3, tuple) and len(e3) == 2 and isinstance(e3[1], str):
+                path, name = e3
+                var, _, d = open_uvfile(path, name, with_all=True)
+                for m in d['_markers_' + name]:
+                    if m not in markers:
+                        markers.append(m)
+                e3 = var
+            shape = tuple(int(x) for x in e3.shape)
+            nt_th = self.getSizes(shape)[0] if len(shape) in (3, 4) else -1
+            if len(shape) not in (3, 4) or self.getSizes(shape)[1:] != (self.nz, self.ny, self.nx) or nt_th not in (1, self.nt):
+                raise RuntimeError(f'ERROR: {which} has shape {shape}; need (nz, ny, nx) = {(self.nz, self.ny, self.nx)}, '
+                                   f'(1, nz, ny, nx) or (nt, nz, ny, nx) = {(self.nt, self.nz, self.ny, self.nx)}')
+            if hasattr(e3, 'read_step') and nt_th == 1:
+                e3 = e3.read_step(0)       # a static file variable: read once
+            arrs.append((e3, nt_th))
+        if arrs[0][1] != arrs[1][1]:
+            raise RuntimeError(f'ERROR: e3u has {arrs[0][1]} time step(s) and e3v {arrs[1][1]}: both static or both per time step')
+        nt_th = arrs[0][1]
+        if fill_value is None:
+            fill_value = markers[0] if markers else None
+        if missing_value is None:
+            missing_value = markers[1] if len(markers) > 1 else None
+        if len(markers) > 2:
+            raise RuntimeError(f'ERROR: e3u / e3v carry {len(markers)} different _FillValue / missing_value markers '
+                               f'({markers}); the engine masks at most two')
+        slot = dict(lazy=None, step=-1, nt=nt_th, fill=numpy.nan if fill_value is None else float(fill_value), keep=[])
+        ptrs, on_dev, lazy = [], None, []
+        for (e3, _), which in zip(arrs, ('e3u', 'e3v')):
+            dt = numpy.dtype(_native_dtype(e3))
+            ptr = _lib.device_pointer(e3)
+            is_lazy = hasattr(e3, 'read_step')
+            if dt != uv_dtype:
+                if ptr is not None or is_lazy or nt_th != 1 or dt.kind != 'f':
+                    raise RuntimeError(f'ERROR: {which} is {dt.name}, uo/vo are {uv_dtype.name}: only a static host array of '
+                                       f'another float dtype is cast')
+                e3 = numpy.asarray(e3).astype(uv_dtype)
+            dev = ptr is not None
+            if on_dev is not None and dev != on_dev:
+                raise RuntimeError('ERROR: e3u and e3v must both be host arrays or both be device arrays')
+            on_dev = dev
+            lazy.append(is_lazy)
+            if is_lazy:
+                buf = self._host_array((self.nz, self.ny, self.nx), uv_dtype)
+                slot['keep'].append(buf)
+                ptrs.append(buf)
+            elif not dev:
+                e3 = _native(e3)
+                ptrs.append(e3.ctypes.data)
+            else:
+                ptrs.append(ptr)
+            slot['keep'].append(e3)     # a borrowed buffer must outlive the handle
+        if lazy[0] != lazy[1]:
+            raise RuntimeError('ERROR: e3u and e3v must both be read from files one step at a time, or neither')
+        if lazy[0]:
+            slot['lazy'] = (arrs[0][0], arrs[1][0])
+            slot['buf'] = tuple(ptrs)
+        else:
+            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), ptrs[0], ptrs[1], nt_th, self._uv_code,
+                                                  1 if on_dev else 0, slot['fill']))
+        check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), numpy.nan if missing_value is None
+                                                            else float(missing_value)))
+        self._e3 = slot
+
+    def _cell_thickness_lazy(self):
+        e3 = getattr(self, '_e3', None)
+        return e3 is not None and e3['lazy'] is not None
+
+    def _stage_cell_thickness(self, tIndex):
+        """make step tIndex of a file-backed, time-varying cell thickness the one the engine reads"""
+        e3 = getattr(self, '_e3', None)
+        if e3 is not None and e3['lazy'] is not None and e3['step'] != tIndex:
+            bu, bv = e3['buf']
+            e3['lazy'][0].read_step(tIndex, out=bu)
+            e3['lazy'][1].read_step(tIndex, out=bv)
+            off = tIndex * bu.nbytes     # a virtual (nt, nz, ny, nx) base that the engine only dereferences at step tIndex
+            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), bu.ctypes.data - off, bv.ctypes.data - off, self.nt,
+                                                  self._uv_code, 0, e3['fill']))
+            e3['step'] = tIndex
+
     def computeTracerFlux(self, tIndex):
         """Tracer transport of time step tIndex across the transects (setTracer first): (ntransect,) totals and (nseg,)
         per-segment sums in tracer x flux units (x rho0 * c_p for a heat transport in W, and x 1e6 in Sverdrup mode).  Levels
@@ -632,7 +746,8 @@ class Field(object):
         """Tracer transport of all nt steps: (nt, ntransect) totals and (nt, nseg) per-segment sums.  `out`: optional torch
         CUDA tensor (nt, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
         import torch
-        lazy = self._lazy is not None or (getattr(self, '_tracer', None) or {}).get('lazy') is not None
+        lazy = (self._lazy is not None or (getattr(self, '_tracer', None) or {}).get('lazy') is not None or
+                self._cell_thickness_lazy())
         if out is not None or not lazy:
             out = self._rows_out(out, self.nt)
         if lazy:
@@ -740,7 +855,9 @@ class Field(object):
     def depthBandFlux(self, profile, ztop, zbot):
         """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile or
         computeTracerProfile (totals or segments, levels first): level z contributes profile[z] * overlap([ztop, zbot], layer z) / thickness[z], exact
-        because a level's flux is linear in its thickness; layers of zero thickness contribute nothing."""
+        because a level's flux is linear in its thickness; layers of zero thickness contribute nothing.  With a cell
+        thickness set (setCellThickness) the levels are still selected, and cut, by the nominal deptht_bounds: a level
+        inside the band enters whole with its per-cell thicknesses, a level cut by ztop or zbot with the nominal fraction."""
         ztop, zbot = float(ztop), float(zbot)
         if not ztop <= zbot:
             raise ValueError(f'depthBandFlux: need ztop <= zbot, got {ztop}, {zbot}')

@@ -14,6 +14,8 @@ only with --show): the table is always printed or written as CSV, which is what 
                                   (water flow by sigma0 class: one CSV line per time step and class)
     ... --tracer sigma0 --tracer-file S.nc --classes 26,27,28 --carry thetao --carry-scale 4.1e-3   (heat by sigma0 class)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
+    ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
+                                  (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
 """
 import argparse
 import glob
@@ -52,26 +54,34 @@ def readTargets(lonLatPoints='', iFiles=''):
     return lonLatZPoints, names
 
 
-def fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup=False):
-    """(nt, ntransect) total fluxes and the Field (one batched GPU pass over every time step)."""
-    # only the totals are wanted: no read-back, and only the signed edge fluxes stay resident (compact mode)
+def _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness=None):
+    """the Field of a series: only totals are wanted, so no read-back, and only the signed edge fluxes stay resident (compact
+    mode); cellThickness: ((path, name) of e3u, (path, name) of e3v) for Field.setCellThickness, or None"""
     fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    if cellThickness is not None:
+        fld.setCellThickness(*cellThickness)
+    return fld
+
+
+def fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup=False, cellThickness=None):
+    """(nt, ntransect) total fluxes and the Field (one batched GPU pass over every time step)."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     totals, _ = fld.computeAll()
     return totals, fld
 
 
-def bandSeries(tFile, uFile, vFile, lonLatZPoints, ztop, zbot, sverdrup=False):
+def bandSeries(tFile, uFile, vFile, lonLatZPoints, ztop, zbot, sverdrup=False, cellThickness=None):
     """(nt, ntransect) fluxes inside the depth band [ztop, zbot] and the Field: one depth-resolved step per time step."""
-    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     totals = numpy.array([fld.depthBandFlux(fld.computeFluxProfile(t, prefetch_next=True)[0], ztop, zbot)
                           for t in range(fld.nt)]).reshape(fld.nt, len(lonLatZPoints))
     return totals, fld
 
 
-def tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False):
+def tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None):
     """(nt, ntransect) tracer transports (Field.computeTracerAll) of the variable `tracer` of tracerFile (default: the T
     file) and the Field."""
-    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
     totals, _ = fld.computeTracerAll()
     return totals, fld
@@ -99,10 +109,10 @@ def carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracer
     return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
 
 
-def levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tracerRef=0.0, sverdrup=False):
+def levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None):
     """(nt, nz, ntransect) water flow of every level (Field.computeFluxProfile) or, with `tracer`, the transport of that
     variable of tracerFile (default: the T file) of every level (Field.computeTracerProfile), and the Field."""
-    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     if tracer:
         fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
     profile = fld.computeTracerProfile if tracer else fld.computeFluxProfile
@@ -170,6 +180,21 @@ def checkLevelsArgs(levels=False, zrange='', classes='', show=False):
         raise RuntimeError('ERROR: --levels and --show cannot be combined: the level table is written as CSV only')
 
 
+def checkCellThicknessArgs(cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', classes='', carry='', levels=False,
+                           tracer=''):
+    """the --cell-thickness options of the command line: refused combinations raise RuntimeError"""
+    if not cellThickness:
+        if e3u or e3v or e3FileU or e3FileV:
+            raise RuntimeError('ERROR: --e3u / --e3v / --e3-file-u / --e3-file-v need --cell-thickness')
+        return
+    if classes or carry:
+        raise RuntimeError('ERROR: --cell-thickness cannot be combined with --classes / --carry: the class transports do not '
+                           'take per-cell thicknesses yet')
+    if levels and tracer:
+        raise RuntimeError('ERROR: --cell-thickness cannot be combined with --levels --tracer: the tracer transport per level '
+                           'does not take per-cell thicknesses yet (--levels alone, or --tracer alone, does)')
+
+
 def _emit(text, output):
     if output:
         with open(output, 'w') as f:
@@ -207,7 +232,8 @@ def parseZRange(zrange):
 
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
-         carryRef=0.0, carryScale=1.0):
+         carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV=''):
+    checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, carry, levels, tracer)
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
     checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, zrange)
     checkLevelsArgs(levels, zrange, classes, show)
@@ -215,8 +241,9 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
+    ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
     if levels:
-        totals, fld = levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup)
+        totals, fld = levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
         what = 'water flow'
         if tracer:
             totals = totals * float(tracerScale)
@@ -247,12 +274,12 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         _emit(title + '\n'.join(lines) + '\n', output)
         return totals
     if tracer:
-        totals, fld = tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup)
+        totals, fld = tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
         totals = totals * float(tracerScale)
     elif zrange:
-        totals, fld = bandSeries(tFile, uFile, vFile, lonLatZPoints, *parseZRange(zrange), sverdrup=sverdrup)
+        totals, fld = bandSeries(tFile, uFile, vFile, lonLatZPoints, *parseZRange(zrange), sverdrup=sverdrup, cellThickness=ct)
     else:
-        totals, fld = fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup)
+        totals, fld = fluxSeries(tFile, uFile, vFile, lonLatZPoints, sverdrup, ct)
     timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
     title, what = 'Water flow', 'water flow'
     if tracer:
@@ -316,4 +343,11 @@ if __name__ == '__main__':
     ap.add_argument('--levels', action='store_true',
                     help='one CSV line per time step and level (time,ztop,zbot,...): the water flow of each level, or with '
                          '--tracer NAME the transport of NAME of each level (--tracer-ref, --tracer-scale apply)')
+    ap.add_argument('--cell-thickness', dest='cellThickness', action='store_true',
+                    help='integrate with per-cell layer thicknesses (partial steps, z*) read from the U and V files instead of '
+                         'deptht_bounds; with the plain series, --zrange, --levels (without --tracer) and --tracer NAME')
+    ap.add_argument('--e3u', default='', metavar='NAME', help='with --cell-thickness: the thickness at U points (default e3u)')
+    ap.add_argument('--e3v', default='', metavar='NAME', help='with --cell-thickness: the thickness at V points (default e3v)')
+    ap.add_argument('--e3-file-u', dest='e3FileU', default='', metavar='FILE', help='read --e3u from FILE instead of the U file')
+    ap.add_argument('--e3-file-v', dest='e3FileV', default='', metavar='FILE', help='read --e3v from FILE instead of the V file')
     main(**vars(ap.parse_args()))
