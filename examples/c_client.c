@@ -93,6 +93,18 @@ int main(void)
     CHECK(nf_field_set_cell_thickness(&fld, NULL, NULL, 0, NF_F64, 0, NAN));
     printf("level 2 with e3u = e3v = 0.5: flux = %.12f\n", flux_half);
 
+    /* section area and area-weighted tracer per level, rows (2, nz, row_length) = A, T: with a tracer of 3 everywhere and the
+     * reference 1, T / A = 2 on the one level (the mean tracer of the throughflow / overturning / gyre split) */
+    static double tracer[NY][NX];
+    for (int j = 0; j < NY; ++j)
+        for (int i = 0; i < NX; ++i) tracer[j][i] = 3.0;
+    double *area = (double *)calloc((size_t)2 * rowlen, sizeof(double));
+    CHECK(nf_field_set_tracer(&fld, tracer, 1, NF_F64, 0, NAN));
+    CHECK(nf_field_set_tracer_reference(&fld, 1.0));
+    CHECK(nf_field_compute_area_profile(&fld, 0, area));
+    printf("section area %.6f, mean tracer above the reference %.3f\n", area[nseg + tid], area[rowlen + nseg + tid] / area[nseg + tid]);
+    free(area);
+
     /* ---- Level 1: mint's call sequence on the host array */
     Grid_t *grid = NULL;
     PolylineIntegral_t *pli = NULL;

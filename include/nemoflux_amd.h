@@ -309,6 +309,32 @@ int nf_field_compute_class_transport_async(nf_field **self, long tIndex, double 
  * rank does not own get exact zeros; the sum over z is the tracer row up to rounding. */
 int nf_field_compute_tracer_profile(nf_field **self, long tIndex, double *prof_host);        /* synchronous, host */
 int nf_field_compute_tracer_profile_async(nf_field **self, long tIndex, double *prof_dev);   /* HBM, on the field's stream */
+/* Section area and area-weighted tracer, level by level: what splits a tracer transport into the part carried by the net flow
+ * through the section (throughflow), by the vertical overturning and by horizontal correlations (gyre).  Records, slots,
+ * faces and the neighbour rule are those of nf_field_compute_profile and the tracer block: east slot = east face of c, north
+ * slot = north face of c, west slot = east face of the west cell (periodic copy in column 0), south slot = north face of the
+ * south cell (nothing on row 0).  For step t, level z and a record's slot q with weight w_q, a the cell the face belongs to:
+ * the face COUNTS when (1) its velocity -- uo[t,z,a] for east and west slots, vo[t,z,a] for north and south slots -- is
+ * present: not NaN and not one of the uo/vo markers (the comparison of fixed()); (2) the face value x of the tracer of
+ * nf_field_set_tracer exists (its markers and wrap_x apply) and is finite; (3) the slot is not the south slot of row 0.  Then
+ *   area term    alpha = |w_q| * (th_q * arc_q)      (0 when the face does not count)
+ *   tracer term  beta  = alpha * (x - ref)
+ * arc_q = arcE[a] or arcN[a] (positive); th_q = thickness[z], or with a cell thickness set fixth(e3u[t',z,a]) / fixth(e3v[t',z,a])
+ * as in the cell-thickness profile (a thickness of 0 or a marker removes the face); ref the tracer reference.  NO Sverdrup
+ * scale: only ratios of these rows are used.  rows (2, nz, row_length): A(z) = sum of alpha, then T(z) = sum of beta, each row
+ * [segments | transects], the transect columns the sums of their segments; slots are added south, east, north, west, then the
+ * fixed tree of the transect reduction: no atomics, bitwise reproducible.  Levels this rank does not own are exact zeros.  For
+ * a line that cuts cells obliquely A is the staircase area (zonal plus meridional extent): a weight for the mean, not a
+ * geometric length.  tau == ref + 1 (ref an integer) gives T == A bit for bit; the rows do not depend on the values of uo / vo,
+ * only on where they are present.
+ * Decomposition (host, float64, AFTER any all-reduce over ranks: it is not linear), per column, with V(z) the rows of
+ * nf_field_compute_profile and H the row of nf_field_compute_tracer_flux:
+ *   m(z) = T(z) / A(z) (0 where A(z) = 0),  M = sum_z T / sum_z A (0 where the sum is 0)
+ *   throughflow = (sum_z V(z)) * M,  overturning = sum_z V(z) * (m(z) - M),  gyre = H - throughflow - overturning.
+ * Compute before set_tracer: NF_ERR_STATE.  Host-resident uo / vo, tracer and time-varying cell thickness are staged per
+ * step.  The calls change neither the resident planes, |.| arrays, running max, last row, tracer planes nor a captured pass. */
+int nf_field_compute_area_profile(nf_field **self, long tIndex, double *rows_host);       /* (2, nz, row_length): A, T */
+int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *rows_dev);  /* HBM, field's stream */
 /* Class tracer: a second, optional tracer at T-points (potential density sigma) that gives the faces their class value
  * instead of the tracer of nf_field_set_tracer, which is then only carried (heat by density class).  Same (nt,nz,ny,nx) and
  * dtype as uo/vo (else NF_ERR_ARG, the message naming both; set_uv first: NF_ERR_STATE); host (staged per step into a buffer

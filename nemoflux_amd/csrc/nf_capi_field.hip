@@ -18,6 +18,7 @@ static int g_batch_steps = 1;
 //   "pass_k3_pairs"        1 = the per-step pass reduces its whole steps two at a time: one gather launch reads the record
 //                          stream once for both steps; 0 = one reduction per step (default 1)
 //   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
+//   "area_chunk"           levels per launch of the area profile: 2 or 4 (float64), 4 or 8 (float32); 0 = the measured default
 static long g_batch_cellsteps = 32l << 20;
 static int g_partial_full = 0;
 static int g_use_graph = 1;
@@ -60,6 +61,7 @@ int field_tuning_set(const char *name, int value)
         g_class_window = value;
         return NF_OK;
     }
+    if (!strcmp(name, "area_chunk")) return area_chunk_set(value);
     return -1;
 }
 }  // namespace nf
@@ -142,6 +144,8 @@ struct nf_field {
     DevArray<char> e3u_static, e3v_static, stage_e3u, stage_e3v;
     // tracer profile (nf_field_compute_tracer_profile): the run sums of one chunk (ws.nrec * tracer_profile_chunk(dtype))
     DevArray<double> tprof_scratch;
+    // area profile (nf_field_compute_area_profile): the run sums of one chunk, two values per level (ws.nrec * 2 * area_chunk)
+    DevArray<double> area_scratch;
     // class transport (nf_field_set_class_edges): the edges on the host, uploaded by the next compute after a change; the run
     // sums of one window of rows (ws.nrec * window, allocated on first use, dropped with the weights)
     std::vector<double> class_edges;
@@ -542,6 +546,31 @@ static int field_profile_async(nf_field *f, long t, double *prof_dev, bool trace
     a.scratch_len = scratch.size();
     a.prof = prof_dev;
     return launch_profile(a, f->stream);
+}
+
+// Section area and area-weighted tracer of step t on the field's stream: rows_dev (2, nz, row_length) = A, T, written whole.
+// Owned levels only, exact zeros elsewhere.  Reads the raw fields, the tracer, the cell thickness when one is set and the
+// records; the resident planes, |.| arrays, running max, last row, tracer planes, version and a captured pass stay as they are.
+static int field_area_async(nf_field *f, long t, double *rows_dev)
+{
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_area_profile", t, 1, rows_dev, 2 * (size_t)f->nz, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    const size_t rowlen = field_row_length(f);
+    if (lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in both blocks
+        NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * 2 * (size_t)f->nz, f->stream));
+    NF_TRY(f->area_scratch.reserve((size_t)f->ws.nrec * 2 * area_chunk_now(f->uv_dtype)));
+    AreaArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_tracer_input(f, t, lv, &a));
+    NF_TRY(field_cell_thick(f, t, lv, &a.th));
+    a.ref = f->tau_ref;
+    a.tr = field_transects(f);
+    a.scratch = f->area_scratch.get();
+    a.scratch_len = f->area_scratch.size();
+    a.rows = rows_dev;
+    a.nz = f->nz;
+    return launch_area_profile(a, f->stream);
 }
 
 // Tracer transport of step t on the field's stream: K1tau into geo.tr_planes, then K3 over them into row_dev
@@ -970,6 +999,7 @@ try {
     f->weights_built = false;
     f->prof_scratch.reset();
     f->tprof_scratch.reset();
+    f->area_scratch.reset();
     f->class_scratch.reset();
     const int bw = build_weights(f->geo.xy.get(), f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
                                  f->skip_unsupported, f->overlap_warn, nullptr, f->nx);
@@ -1289,6 +1319,30 @@ try {
     NF_TRY(field_ready(f, "compute_tracer_profile", true));
     NF_NEED_DEVICE();
     return field_profile_async(f, tIndex, prof_dev, true);
+}
+NF_API_CATCH
+
+int nf_field_compute_area_profile(nf_field **self, long tIndex, double *rows_host)
+try {
+    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_area_profile: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_area_profile: set_tracer first");
+    NF_NEED_DEVICE();
+    NF_TRY(field_ready(f, "compute_area_profile", true));
+    const size_t n = 2 * (size_t)f->nz * field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_area_async(f, tIndex, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *rows_dev)
+try {
+    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_area_profile_async: null argument");
+    nf_field *f = *self;
+    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_area_profile_async: set_tracer first");
+    NF_NEED_DEVICE();
+    NF_TRY(field_ready(f, "compute_area_profile", true));
+    return field_area_async(f, tIndex, rows_dev);
 }
 NF_API_CATCH
 

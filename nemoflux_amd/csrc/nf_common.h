@@ -388,6 +388,30 @@ struct ProfileArgs {
 };
 int launch_profile(const ProfileArgs &a, hipStream_t s);
 
+// Section area and area-weighted tracer per level (nf_field_compute_area_profile; DESIGN.md section 4, "Throughflow,
+// overturning and gyre parts"): rows (2, nz, row_length) = A, T; the kernels write rows [z0, z1) of both.  The carried tracer is
+// required; th.e3u set: every slot's term takes the thickness at its own face.  Levels go area_chunk(dtype) at a time (measured;
+// the "area_chunk" knob picks the other candidate): scratch holds 2 * chunk * ws.nrec run sums.
+constexpr int kAreaChunk = 4;
+constexpr int kAreaChunkF32 = 8;
+inline int area_chunk(int dtype) { return dtype == NF_F32 ? kAreaChunkF32 : kAreaChunk; }
+int area_chunk_set(int levels);     // 0 = area_chunk(dtype); 2 or 4 (float64), 4 or 8 (float32)
+int area_chunk_now(int dtype);
+struct AreaArgs {
+    StepInput in;                // scale and sverdrup are not read
+    Transects tr;
+    double *scratch = nullptr;
+    size_t scratch_len = 0;
+    double *rows = nullptr;
+    long nz = 0;
+    const void *tau = nullptr;   // the carried tracer of the time step, (nz, ncell) of the field dtype
+    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
+    double ref = 0.0;
+    int wrap_x = 1;
+    CellThick th;
+};
+int launch_area_profile(const AreaArgs &a, hipStream_t s);
+
 // Tracer transport (nf_field_compute_tracer_flux, nf_tracer.hip): K1's vertical integral with every level's velocity
 // multiplied by the tracer interpolated to the face, tf = 0.5 (a + b) - ref (DESIGN.md section 4 has the face rule).  Writes
 // the two signed planes [eU_tau | eV_tau] of one time step, nothing else; K3 (planes = 2) reduces them.

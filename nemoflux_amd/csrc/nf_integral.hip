@@ -524,6 +524,151 @@ int launch_profile(const ProfileArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "profile: dtype must be NF_F64 or NF_F32");
 }
 
+// ---- section area and area-weighted tracer: two values per level, no velocity in them --------------------------------
+// The rows that split a tracer transport into throughflow, overturning and gyre parts (nf_field_compute_area_profile): per
+// level and slot  alpha = |w| * (th * arc)  where the face counts -- its velocity is present (uv_present: uv_fixed's
+// comparison), the carried tracer has a finite face value x (tr_face_raw) and the slot is not row 0's south slot -- else 0, and
+// beta = alpha * (x - ref).  No Sverdrup scale.  A lane owns one record and up to LZ levels, as in k_profile_segscan: the 4 + 5
+// gathers per level (4 + 4 + 5 with per-cell thicknesses, one trailing ThickIn<T>) of the whole chunk are issued before the
+// first is used, the four slots are added in weighted_sum's order, and the 2 * LZ sums go through ONE seg_scan.
+// runsum: 2 * LZ rows of n doubles, level-major: rows [0, LZ) the areas, rows [LZ, 2 LZ) the tracer sums.
+template <typename T>
+__device__ inline bool uv_present(T x, T fill, T fill2, bool two)
+{
+    return !(x != x || x == fill || (two && x == fill2));
+}
+template <typename T>
+__device__ inline void area_terms(const Record &r, const SlotTh &th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2,
+                                  bool two, const LevelTau<T> &t, const ClassNeighbours &nb, const TauIn<T> &ti, double *area,
+                                  double *tsum)
+{
+    double bs, be, bn, bw;
+    auto term = [&](bool slot, double w, double th, T vel, double a, T ta, T tb, bool has_b, double *beta) {
+        double f;
+        const bool has = tr_face_raw<T>(ta, tb, has_b, ti.m1, ti.m2, &f);
+        const bool counts = slot && has && __builtin_isfinite(f) && uv_present<T>(vel, fill, fill2, two);
+        const double al = counts ? __builtin_fabs(w) * (th * a) : 0.0;
+        *beta = counts ? al * (f - ti.ref) : 0.0;
+        return al;
+    };
+    const double as = term(nb.south, r.wa.x, th.s, x.vs, arc.Ns, t.s, t.c, true, &bs);
+    const double ae = term(true, r.wa.y, th.e, x.uc, arc.Ec, t.c, t.e, nb.has_e, &be);
+    const double an = term(true, r.wb.x, th.n, x.vc, arc.Nc, t.c, t.n, nb.has_n, &bn);
+    const double aw = term(true, r.wb.y, th.w, x.uw, arc.Ew, t.w, t.c, nb.has_w, &bw);
+    *area = ((as + ae) + an) + aw;
+    *tsum = ((bs + be) + bn) + bw;
+}
+
+template <typename T, int LZ, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_area_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                         const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                         const T *__restrict__ v, long ncell, unsigned nx, int z0, int nlev,
+                                                         const double *__restrict__ thickness,
+                                                         const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                         T fill, T fill2, int two, TauIn<T> ti, double *__restrict__ runsum,
+                                                         TI... thick)
+{
+    constexpr bool CT = sizeof...(TI) > 0;
+    const ThickIn<T> ct = thick_arg<T>(thick...);
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    double val[2 * LZ];
+#pragma unroll
+    for (int l = 0; l < 2 * LZ; ++l) val[l] = 0.0;
+    int key = -1;
+    if (k < n) {
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, ti.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        LevelUV<T> x[LZ];
+        LevelTau<T> tt[LZ];
+        LevelUV<T> e3[CT ? LZ : 1];
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {   // nlev is launch-uniform
+                x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);
+                if constexpr (CT) e3[l] = load_level_e3(ct, (long)(z0 + l) * ncell, r.c, nb);
+                tt[l] = load_level_tau(ti.tau, (long)(z0 + l) * ncell, r.c, nb);
+            }
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {
+                SlotTh th;
+                if constexpr (CT)
+                    th = level_th(e3[l], ct);
+                else
+                    th = slot_th(thickness[z0 + l]);
+                area_terms<T>(r, th, x[l], arc, fill, fill2, two, tt[l], nb, ti, &val[l], &val[LZ + l]);
+            }
+    }
+    if (seg_scan(val, key, k, n)) {
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {
+                runsum[(long)l * n + k] = val[l];
+                runsum[(long)(LZ + l) * n + k] = val[LZ + l];
+            }
+    }
+}
+
+// "area_chunk" tuning knob: the levels per chunk, one of the instantiated candidates of the dtype; 0 = area_chunk(dtype)
+static int g_area_chunk = 0;
+int area_chunk_set(int levels)
+{
+    if (levels != 0 && levels != 2 && levels != 4 && levels != 8) return -1;
+    g_area_chunk = levels;
+    return NF_OK;
+}
+int area_chunk_now(int dtype) { return g_area_chunk ? g_area_chunk : area_chunk(dtype); }
+
+template <typename T, int LZ>
+static int launch_area_t(const AreaArgs &a, hipStream_t s)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    const TauIn<T> ti{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0};
+    double *tsum = a.scratch + (size_t)LZ * ws.nrec;   // the second half of the run sums
+    for (int zc = in.z0; zc < in.z1; zc += LZ) {
+        const int nlev = in.z1 - zc < LZ ? in.z1 - zc : LZ;
+        if (ws.nrec > 0) {
+            if (a.th.e3u)
+                hipLaunchKernelGGL((k_area_segscan<T, LZ, ThickIn<T>>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
+                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
+                                   (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2,
+                                   (int)uv_two_markers(fill, fill2), ti, a.scratch, thick_in<T>(a.th));
+            else
+                hipLaunchKernelGGL((k_area_segscan<T, LZ>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(),
+                                   ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, zc, nlev,
+                                   in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), ti, a.scratch);
+        }
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)zc * row_length, row_length, (unsigned)nlev,
+                        s);
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, tsum, a.rows + (a.nz + zc) * row_length, row_length, (unsigned)nlev,
+                        s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+int launch_area_profile(const AreaArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    const int chunk = area_chunk_now(in.dtype);
+    NF_REQUIRE(in.u && in.v && a.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "area profile: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "area profile: null argument");
+    NF_REQUIRE(in.z1 <= a.nz, NF_ERR_ARG, "area profile: bad arguments");
+    NF_TRY(check_raw_step("area profile", in, a.tr, a.scratch_len, 2 * (size_t)chunk));
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (in.dtype == NF_F64 && chunk == 2) return launch_area_t<double, 2>(a, s);
+    if (in.dtype == NF_F64 && chunk == 4) return launch_area_t<double, 4>(a, s);
+    if (in.dtype == NF_F32 && chunk == 4) return launch_area_t<float, 4>(a, s);
+    if (in.dtype == NF_F32 && chunk == 8) return launch_area_t<float, 8>(a, s);
+    NF_REQUIRE(in.dtype == NF_F64 || in.dtype == NF_F32, NF_ERR_ARG, "area profile: dtype must be NF_F64 or NF_F32");
+    NF_REQUIRE(false, NF_ERR_ARG, "area profile: the area_chunk knob names a chunk that is not built for this dtype");
+}
+
 // ---- volume transport in tracer classes: level_slots, each term sent to the row of its face's class -------------------
 // One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are
 // level_slots' times their weights; each is added, in slot order (south, east, north, west), to the lane's accumulator of the

@@ -784,6 +784,62 @@ class Field(object):
             check(lib.nf_field_compute_tracer_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return self._split_rows(rows)
 
+    def computeAreaProfile(self, tIndex, out=None, prefetch_next=None):
+        """Section area and area-weighted tracer of time step tIndex, level by level (setTracer first): the pair
+        (area, tracerArea), each split like computeFluxProfile into (nz, ntransect) totals and (nz, nseg) per-segment sums.
+        area[z] = sum of |w| * th * arc over the faces of level z that count (velocity present, tracer face value finite),
+        tracerArea[z] = the same sum with every term times (tracer face value - reference); th is thickness[z], or the cell
+        thickness at the face when one is set.  No Sverdrup scale: only ratios of these rows are used (overturningGyre).  For
+        a line that cuts cells obliquely the area is the staircase area (zonal plus meridional extent): a weight for the
+        mean, not a geometric length.  Levels this rank does not own (slab_range) are zeros.  Leaves the resident edge fluxes,
+        the running max, the row of the last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64
+        torch CUDA tensor (2, nz, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        shape = (2, self.nz, self._row_width)
+        if out is not None:
+            import torch
+            if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
+                raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
+            check(lib.nf_field_compute_area_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros(shape, numpy.float64)
+            check(lib.nf_field_compute_area_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        return self._split_rows(rows[0]), self._split_rows(rows[1])
+
+    @staticmethod
+    def overturningGyre(volumeProfile, areaRows, tracerRow):
+        """Split a tracer transport into its throughflow, overturning and gyre parts.  Host only, float64, on rows that have
+        been summed over all ranks first (the step is not linear).  volumeProfile: V (nz, n) of computeFluxProfile;
+        areaRows: the pair (A, T), each (nz, n), of computeAreaProfile; tracerRow: H (n,) of computeTracerFlux -- totals or
+        segments alike.  Per column, with m(z) = T(z) / A(z) (0 where A(z) = 0) and M = sum_z T / sum_z A (0 where the sum is 0):
+            throughflow = (sum_z V(z)) * M,   overturning = sum_z V(z) * (m(z) - M),   gyre = H - throughflow - overturning.
+        Returns a dict of 'total' (= H), 'throughflow', 'overturning', 'gyre', each (n,), and 'mean' = m, (nz, n)."""
+        V = numpy.asarray(volumeProfile, dtype=numpy.float64)
+        A, T = (numpy.asarray(x, dtype=numpy.float64) for x in areaRows)
+        H = numpy.asarray(tracerRow, dtype=numpy.float64)
+        if V.ndim != 2 or A.shape != V.shape or T.shape != V.shape or H.shape != V.shape[1:]:
+            raise ValueError(f'overturningGyre: need V, A, T of one shape (nz, n) and H of shape (n,), got {V.shape}, {A.shape}, '
+                             f'{T.shape}, {H.shape}')
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            m = numpy.where(A != 0.0, T / A, 0.0)
+            sA, sT = A.sum(axis=0), T.sum(axis=0)
+            M = numpy.where(sA != 0.0, sT / sA, 0.0)
+        through = V.sum(axis=0) * M
+        over = (V * (m - M)).sum(axis=0)
+        return dict(total=H, throughflow=through, overturning=over, gyre=H - through - over, mean=m)
+
+    def decomposeTracerTransport(self, tIndex):
+        """The tracer transport of time step tIndex (setTracer first) and its throughflow, overturning and gyre parts, for
+        the transect totals: computeFluxProfile, computeAreaProfile and computeTracerFlux, then overturningGyre.  On one rank
+        only; sharded runs reduce the rows first (docs/MULTIGPU.md)."""
+        V = self.computeFluxProfile(tIndex)[0]
+        (A, _), (T, _) = self.computeAreaProfile(tIndex)
+        H = self.computeTracerFlux(tIndex)[0]
+        return self.overturningGyre(V, (A, T), H)
+
     def computeClassTracerTransport(self, tIndex, out=None, prefetch_next=None):
         """Transport of the tracer of setTracer (reference subtracted) of time step tIndex, binned by the class of each U / V
         face (setTracer and setClassEdges first): (nedges+2, ntransect) totals and (nedges+2, nseg) per-segment sums, rows as in

@@ -14,6 +14,7 @@ only with --show): the table is always printed or written as CSV, which is what 
                                   (water flow by sigma0 class: one CSV line per time step and class)
     ... --tracer sigma0 --tracer-file S.nc --classes 26,27,28 --carry thetao --carry-scale 4.1e-3   (heat by sigma0 class)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
+    ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
 """
@@ -118,6 +119,33 @@ def levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tr
     profile = fld.computeTracerProfile if tracer else fld.computeFluxProfile
     totals = numpy.array([profile(t, prefetch_next=True)[0] for t in range(fld.nt)])
     return totals.reshape(fld.nt, fld.nz, len(lonLatZPoints)), fld
+
+
+PARTS = ('total', 'throughflow', 'overturning', 'gyre')
+
+
+def decomposeSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None):
+    """(nt, 4, ntransect) transport of the variable `tracer` of tracerFile (default: the T file) and its throughflow,
+    overturning and gyre parts (PARTS; Field.decomposeTracerTransport per time step), and the Field."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    totals = numpy.zeros((fld.nt, len(PARTS), len(lonLatZPoints)))
+    for t in range(fld.nt):
+        d = fld.decomposeTracerTransport(t)
+        totals[t] = [d[k] for k in PARTS]
+    return totals, fld
+
+
+def checkDecomposeArgs(decompose=False, tracer='', classes='', levels=False, zrange='', show=False):
+    """the --decompose option of the command line: refused combinations raise RuntimeError"""
+    if not decompose:
+        return
+    if not tracer:
+        raise RuntimeError('ERROR: --decompose needs --tracer NAME (the tracer whose transport is split)')
+    for on, opt in ((classes, '--classes'), (levels, '--levels'), (zrange, '--zrange'), (show, '--show')):
+        if on:
+            raise RuntimeError(f'ERROR: --decompose and {opt} cannot be combined: --decompose writes the total, throughflow, '
+                               f'overturning and gyre parts of the full-depth transport of --tracer as CSV only')
 
 
 def parseClasses(classes):
@@ -232,7 +260,8 @@ def parseZRange(zrange):
 
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
-         carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV=''):
+         carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False):
+    checkDecomposeArgs(decompose, tracer, classes, levels, zrange, show)
     checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, carry, levels, tracer)
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
     checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, zrange)
@@ -242,6 +271,16 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
     ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    if decompose:
+        totals, fld = decomposeSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
+        totals = totals * float(tracerScale)
+        unit = f'{tracer} x {unit}' + (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '')
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        lines = ['time,part,' + ','.join(names)]
+        lines += [f'{timeVals[t]},{part},' + ','.join(f'{x:.15g}' for x in totals[t, k])
+                  for t in range(fld.nt) for k, part in enumerate(PARTS)]
+        _emit(f'# transport of {tracer} and its parts [{unit}]\n' + '\n'.join(lines) + '\n', output)
+        return totals
     if levels:
         totals, fld = levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
         what = 'water flow'
@@ -343,6 +382,9 @@ if __name__ == '__main__':
     ap.add_argument('--levels', action='store_true',
                     help='one CSV line per time step and level (time,ztop,zbot,...): the water flow of each level, or with '
                          '--tracer NAME the transport of NAME of each level (--tracer-ref, --tracer-scale apply)')
+    ap.add_argument('--decompose', action='store_true',
+                    help='with --tracer NAME: one CSV line per time step and part (time,part,...): the transport of NAME and its '
+                         'throughflow, overturning and gyre parts (--tracer-ref, --tracer-scale, -s and --cell-thickness apply)')
     ap.add_argument('--cell-thickness', dest='cellThickness', action='store_true',
                     help='integrate with per-cell layer thicknesses (partial steps, z*) read from the U and V files instead of '
                          'deptht_bounds; with the plain series, --zrange, --levels (without --tracer) and --tracer NAME')
