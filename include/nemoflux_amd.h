@@ -467,6 +467,28 @@ int nf_inflater_run(nf_inflater **self, const void *comp_host, size_t comp_bytes
                     const long long *chunk_dims, const long long *slab_dims, const long long *origin, void *out_dev,
                     void *hip_stream, int *status_host);
 
+/* ------------------------------------------------------------------ time means (nf_timemean.hip) */
+/* The time mean of nsteps arrays of n values each, step t at src_dev + t * stride_elems elements of dtype (HBM).  Per value
+ * i, the steps visited strictly in ascending order:
+ *     s = +0.0, c = 0                  (first = 0: the s, c that the previous call left in acc_dev / cnt_dev)
+ *     x = src[t * stride_elems + i];   x present:  s = s + (double)x, c += 1
+ * Present: not NaN and equal to neither marker, each marker cast to dtype and compared in dtype (fill, missing: NaN = none);
+ * +-inf is present.  No other arithmetic, no reassociation: a series split over several calls (first on the first one only,
+ * last on the last one only) gives the bits of one call, whatever the launch shape.
+ * last = 0: acc_dev[i] = s, cnt_dev[i] = c for the next call.  last = 1: acc_dev[i] becomes the mean,
+ *     NF_MEAN_OVER_STEPS    s / total_steps   (the velocity rule: a missing velocity counts as 0, as in every flux kernel)
+ *     NF_MEAN_OVER_PRESENT  s / c             (the tracer rule)
+ * and fill_out where c == 0, under both rules; total_steps is read by that call only.
+ * cnt_dev may be NULL when first && last (nothing is carried: nsteps * n * sizeof(dtype) bytes in, 8 n bytes out).
+ * NF_ERR_ARG, decided before a device is needed: NULL acc_dev / src_dev, nsteps < 1, n == 0, stride_elems < n with
+ * nsteps > 1, a bad dtype or rule, last with NF_MEAN_OVER_STEPS and total_steps < 1, NULL cnt_dev without first && last.
+ * Asynchronous on hip_stream. */
+#define NF_MEAN_OVER_STEPS 0
+#define NF_MEAN_OVER_PRESENT 1
+int nf_time_mean(double *acc_dev, unsigned *cnt_dev, const void *src_dev, long nsteps, long long stride_elems, size_t n,
+                 int dtype, double fill, double missing, int first, int last, int rule, long total_steps, double fill_out,
+                 void *hip_stream);
+
 /* ------------------------------------------------------------------ synthetic data (datagen.py) */
 /* Stream functions offered on device (no eval on the GPU): psi = g(z,t) * h(x,y)
  *   0 "x"                                                    README.md:26

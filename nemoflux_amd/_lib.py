@@ -165,7 +165,11 @@ _sig('nf_inflater_upload', [_pp, ctypes.c_void_p, ctypes.c_size_t])
 _sig('nf_inflater_upload_ranges', [_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_size_t])
 _sig('nf_inflater_run', [_pp, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
                          ctypes.c_int, c_ll_p, c_ll_p, c_ll_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p])
-_sig('nf_datagen_bounds', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long] + [ctypes.c_double] * 6 +
+NF_MEAN_OVER_STEPS, NF_MEAN_OVER_PRESENT = 0, 1
+_sig('nf_time_mean', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_longlong,   # HBM addresses
+                      ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                      ctypes.c_long, ctypes.c_double, ctypes.c_void_p])
+_sig('nf_datagen_bounds',[ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long] + [ctypes.c_double] * 6 +
      [ctypes.c_int, ctypes.c_void_p])
 _sig('nf_datagen_uv', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_long] * 6 + [ctypes.c_double] * 6 +
      [ctypes.c_int, ctypes.c_int, ctypes.c_void_p])

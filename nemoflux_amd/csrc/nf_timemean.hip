@@ -1,0 +1,219 @@
+// nf_timemean.hip -- the time mean of a series of arrays (nf_time_mean, Field.timeMean): one streaming, bandwidth-bound pass
+// over nsteps arrays of n values each.
+//
+// Definition, per value i, the steps visited strictly in ascending order:
+//   s = +0.0, c = 0                      (or the s, c a previous call left in acc / cnt)
+//   x = src[t * stride + i];             x present:  s = s + (double)x,  c += 1
+// "Present" is the engine's rule (uv_fixed / tr_present of nf_common.h): not NaN and equal to neither marker, each marker cast
+// to the array's dtype and compared in that dtype; +-inf is present.  There is no other arithmetic and no reassociation: s is
+// the left-to-right float64 sum whatever the launch shape or the grouping of the steps into calls, so a series split over
+// several calls gives the bits of one call and a numpy loop reproduces them.  The last call finishes in place:
+//   NF_MEAN_OVER_STEPS    s / total_steps   (velocities: a missing one counts as 0, as in every flux kernel)
+//   NF_MEAN_OVER_PRESENT  s / c             (tracers)
+// and fill_out where c == 0 under both rules.
+//
+// Access pattern.  A lane owns 16 consecutive bytes of the value axis (2 doubles or 4 floats) and walks the steps with stride
+// `stride`; the loads of a batch of steps -- one aligned, read-once (non-temporal) 16-byte load per step -- are issued before
+// the first add, the adds of the batch then run in step order.  acc leaves in 16-byte stores.  When some step is not 16-byte
+// aligned (an odd n with stride = n, an odd base pointer) the same code runs with one value per lane: the same bits.  All
+// offsets are 64-bit (step 5 of a 3600 x 1800 x 75 series starts beyond 2^31 elements).
+//
+// Algorithmic bytes of a first && last call: nsteps * n * sizeof(T) read + 8 n written; a carried call adds 12 n each way.
+#include "nf_capi.h"
+
+namespace nf {
+
+namespace {
+
+typedef double tm_dvec2 __attribute__((ext_vector_type(2)));
+typedef float tm_fvec4 __attribute__((ext_vector_type(4)));
+typedef unsigned tm_uvec2 __attribute__((ext_vector_type(2)));
+typedef unsigned tm_uvec4 __attribute__((ext_vector_type(4)));
+template <typename T, int VEC> struct tm_vec;
+template <> struct tm_vec<double, 2> { using type = tm_dvec2; };
+template <> struct tm_vec<float, 4> { using type = tm_fvec4; };
+template <> struct tm_vec<double, 1> { using type = double; };
+template <> struct tm_vec<float, 1> { using type = float; };
+template <> struct tm_vec<unsigned, 2> { using type = tm_uvec2; };
+template <> struct tm_vec<unsigned, 4> { using type = tm_uvec4; };
+template <> struct tm_vec<unsigned, 1> { using type = unsigned; };
+
+template <typename T, int VEC> struct TmLanes {
+    T x[VEC];
+};
+
+// VEC consecutive values at p (aligned to VEC * sizeof(T) when VEC > 1); NT: read once
+template <typename T, int VEC, bool NT>
+__device__ inline TmLanes<T, VEC> tm_load(const T *p)
+{
+    using V = typename tm_vec<T, VEC>::type;
+    TmLanes<T, VEC> r;
+    V v = NT ? __builtin_nontemporal_load(reinterpret_cast<const V *>(p)) : *reinterpret_cast<const V *>(p);
+    __builtin_memcpy(&r, &v, sizeof(V));
+    return r;
+}
+template <typename T, int VEC>
+__device__ inline void tm_store(T *p, const TmLanes<T, VEC> &r)
+{
+    using V = typename tm_vec<T, VEC>::type;
+    V v;
+    __builtin_memcpy(&v, &r, sizeof(V));
+    __builtin_nontemporal_store(v, reinterpret_cast<V *>(p));
+}
+
+struct TmFinish {
+    int first, last, rule;
+    double total_steps, fill_out;
+};
+
+// the VEC values that begin at i0: US steps' loads in flight, the adds in step order
+template <typename T, int VEC, int US>
+__device__ inline void tm_lane(double *acc, unsigned *cnt, const T *src, long nsteps, long long stride, size_t i0, T m1, T m2,
+                               const TmFinish &f)
+{
+    double s[VEC];
+    unsigned c[VEC];
+    if (f.first) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) s[k] = 0.0, c[k] = 0u;
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; k += 2) {   // 16 bytes of acc at a time
+            constexpr int W = VEC > 1 ? 2 : 1;
+            const TmLanes<double, W> a = tm_load<double, W, false>(acc + i0 + k);
+#pragma unroll
+            for (int q = 0; q < W; ++q) s[k + q] = a.x[q];
+        }
+        const TmLanes<unsigned, VEC> n0 = tm_load<unsigned, VEC, false>(cnt + i0);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) c[k] = n0.x[k];
+    }
+    const T *p = src + i0;
+    for (long t = 0; t < nsteps; t += US) {
+        const int nb = nsteps - t < US ? (int)(nsteps - t) : US;   // wave-uniform
+        TmLanes<T, VEC> x[US];
+#pragma unroll
+        for (int r = 0; r < US; ++r)
+            if (r < nb) x[r] = tm_load<T, VEC, true>(p + (long long)r * stride);
+#pragma unroll
+        for (int r = 0; r < US; ++r)
+            if (r < nb) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const bool here = tr_present<T>(x[r].x[k], m1, m2);
+                    s[k] = here ? s[k] + (double)x[r].x[k] : s[k];
+                    c[k] += here ? 1u : 0u;
+                }
+            }
+        p += (long long)US * stride;
+    }
+    if (f.last) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k)
+            s[k] = c[k] == 0u ? f.fill_out : (f.rule == NF_MEAN_OVER_STEPS ? s[k] / f.total_steps : s[k] / (double)c[k]);
+    } else {
+        TmLanes<unsigned, VEC> n1;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) n1.x[k] = c[k];
+        tm_store<unsigned, VEC>(cnt + i0, n1);
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; k += 2) {
+        constexpr int W = VEC > 1 ? 2 : 1;
+        TmLanes<double, W> a;
+#pragma unroll
+        for (int q = 0; q < W; ++q) a.x[q] = s[k + q];
+        tm_store<double, W>(acc + i0 + k, a);
+    }
+}
+
+}  // namespace
+
+// 256 threads, VEC values per lane, one tile of 256 * VEC values per block: i0 = (tile * 256 + tid) * VEC.  The tiles are dealt
+// in K1's XCD bands (xcd_tile: every XCD streams one contiguous band of every step); the grid is xcd_grid(ntiles), tiles
+// >= ntiles exit.  The one lane that holds fewer than VEC values (n is no multiple of VEC) takes them one at a time.
+template <typename T, int VEC, int US>
+__global__ __launch_bounds__(256) void k_time_mean(double *acc, unsigned *cnt, const T *__restrict__ src, long nsteps,
+                                                   long long stride, size_t n, unsigned ntiles, T m1, T m2, TmFinish f)
+{
+    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
+    const size_t i0 = ((size_t)tile * 256 + threadIdx.x) * VEC;
+    if (tile >= ntiles || i0 >= n) return;
+    if (VEC == 1 || n - i0 >= (size_t)VEC) {
+        tm_lane<T, VEC, US>(acc, cnt, src, nsteps, stride, i0, m1, m2, f);
+        return;
+    }
+    for (size_t i = i0; i < n; ++i) tm_lane<T, 1, US>(acc, cnt, src, nsteps, stride, i, m1, m2, f);
+}
+
+namespace {
+
+// Steps in flight per lane, one 16-byte load each (4 VGPRs): 44 VGPRs at float64, 52 at float32, 8 waves per SIMD, no
+// scratch (-Rpass-analysis=kernel-resource-usage).  Measured at the bench shape while this was written and not kept
+// (profiles/timemean_timing.txt): 4 or 12 steps in flight (within 1 %), two tiles per lane with all
+// their loads in flight (within 1 % at float64, -4 to +6 % at float32), a capped grid whose blocks walk the tiles (5 to 10 %
+// slower), plain instead of non-temporal loads or stores (no difference); the XCD bands are worth 6 % at float32, nothing
+// at float64.
+constexpr int kTimeMeanSteps = 8;
+
+struct TimeMeanArgs {
+    double *acc;
+    unsigned *cnt;
+    const void *src;
+    long nsteps;
+    long long stride;
+    size_t n;
+    double fill, missing;
+    TmFinish f;
+};
+
+template <typename T, int VEC>
+int launch_time_mean_v(const TimeMeanArgs &a, hipStream_t s)
+{
+    const size_t per_block = 256u * (size_t)VEC;
+    const size_t ntiles = (a.n + per_block - 1) / per_block;
+    NF_REQUIRE(ntiles <= 0x7ffffff0u, NF_ERR_ARG, "nf_time_mean: n is too large for one launch");
+    hipLaunchKernelGGL((k_time_mean<T, VEC, kTimeMeanSteps>), dim3(xcd_grid((unsigned)ntiles)), dim3(256), 0, s, a.acc, a.cnt,
+                       (const T *)a.src, a.nsteps, a.stride, a.n, (unsigned)ntiles, (T)a.fill, (T)a.missing, a.f);
+    NF_HIP(hipGetLastError());
+    return NF_OK;
+}
+
+template <typename T, int VEC>
+int launch_time_mean_t(const TimeMeanArgs &a, hipStream_t s)
+{
+    // every step, acc and cnt 16-byte aligned at every lane's first value: else one value per lane
+    bool al16 = (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.acc % 16 == 0 && (uintptr_t)a.cnt % 16 == 0;
+    if (a.nsteps > 1) al16 = al16 && (a.stride * (long long)sizeof(T)) % 16 == 0;
+    return al16 ? launch_time_mean_v<T, VEC>(a, s) : launch_time_mean_v<T, 1>(a, s);
+}
+
+}  // namespace
+
+}  // namespace nf
+
+using namespace nf;
+
+extern "C" int nf_time_mean(double *acc_dev, unsigned *cnt_dev, const void *src_dev, long nsteps, long long stride_elems,
+                            size_t n, int dtype, double fill, double missing, int first, int last, int rule, long total_steps,
+                            double fill_out, void *hip_stream)
+try {
+    NF_REQUIRE(acc_dev && src_dev, NF_ERR_ARG, "nf_time_mean: null acc_dev or src_dev");
+    NF_REQUIRE(nsteps >= 1, NF_ERR_ARG, "nf_time_mean: nsteps must be at least 1");
+    NF_REQUIRE(n > 0, NF_ERR_ARG, "nf_time_mean: n must not be 0");
+    NF_REQUIRE(nsteps == 1 || (stride_elems >= 0 && (unsigned long long)stride_elems >= n), NF_ERR_ARG,
+               "nf_time_mean: stride_elems must be at least n when there is more than one step");
+    NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_time_mean: dtype must be NF_F64 or NF_F32");
+    NF_REQUIRE(rule == NF_MEAN_OVER_STEPS || rule == NF_MEAN_OVER_PRESENT, NF_ERR_ARG,
+               "nf_time_mean: rule must be NF_MEAN_OVER_STEPS or NF_MEAN_OVER_PRESENT");
+    NF_REQUIRE(!(last && rule == NF_MEAN_OVER_STEPS) || total_steps >= 1, NF_ERR_ARG,
+               "nf_time_mean: total_steps must be at least 1 for the last call of NF_MEAN_OVER_STEPS");
+    NF_REQUIRE(cnt_dev || (first && last), NF_ERR_ARG,
+               "nf_time_mean: cnt_dev may be null only when first && last (nothing is carried)");
+    NF_NEED_DEVICE();
+    const TimeMeanArgs a{acc_dev, cnt_dev, src_dev, nsteps, stride_elems, n, fill, missing,
+                         TmFinish{first ? 1 : 0, last ? 1 : 0, rule, (double)total_steps, fill_out}};
+    hipStream_t s = (hipStream_t)hip_stream;
+    return dtype == NF_F64 ? launch_time_mean_t<double, 2>(a, s) : launch_time_mean_t<float, 4>(a, s);
+}
+NF_API_CATCH

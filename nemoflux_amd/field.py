@@ -197,6 +197,10 @@ class Field(object):
         self.sverdrup = sverdrup
         self.periodX = periodX
         self._readback = readback
+        # what timeMean needs to build the Field of the mean state the way this one was built
+        self._uv_markers = (float(fill_value), float(missing_value))
+        self._build_kw = dict(periodX=periodX, numCellsPerBucket=numCellsPerBucket, readback=readback, compact=compact,
+                              unsupportedCells=unsupportedCells, overlappingCells=overlappingCells)
         self._h = ctypes.c_void_p()
         check(lib.nf_field_new(ctypes.byref(self._h)))
         if stream is not None:
@@ -256,6 +260,7 @@ class Field(object):
             pu, pv, uv_dev = uo.ctypes.data, vo.ctypes.data, 0
         else:
             uv_dev = 1
+        self._uv = (uo, vo)
         if self._lazy is None:
             self._uv_code = _dtype_code(uo)
             check(lib.nf_field_set_uv(ctypes.byref(self._h), pu, pv, self.nt, self._uv_code, uv_dev, float(fill_value)))
@@ -559,6 +564,7 @@ class Field(object):
                                          lib.nf_field_set_tracer_missing_value)
         check(lib.nf_field_set_tracer_reference(ctypes.byref(self._h), float(reference)))
         check(lib.nf_field_set_tracer_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
+        self._tracer_reference, self._tracer_wrapX = float(reference), bool(wrapX)
 
     def _tracer_slot(self, tracer, fill_value, missing_value, set_tracer, set_missing):
         """Hand a tracer at T-points to one of the engine's two tracer slots (set_tracer / set_missing: the slot's C calls) and
@@ -581,7 +587,8 @@ class Field(object):
             raise RuntimeError(f'ERROR: the tracer has shape {shape}; uo/vo have (nt, nz, ny, nx) = '
                                f'{(self.nt, self.nz, self.ny, self.nx)}')
         slot = dict(lazy=None, step=-1, set=set_tracer, code=_dtype_code(tracer),
-                    fill=numpy.nan if fill_value is None else float(fill_value))
+                    fill=numpy.nan if fill_value is None else float(fill_value),
+                    missing=numpy.nan if missing_value is None else float(missing_value))
         ptr = _lib.device_pointer(tracer)
         on_dev = 1
         if hasattr(tracer, 'read_step'):
@@ -676,7 +683,8 @@ class Field(object):
         if len(markers) > 2:
             raise RuntimeError(f'ERROR: e3u / e3v carry {len(markers)} different _FillValue / missing_value markers '
                                f'({markers}); the engine masks at most two')
-        slot = dict(lazy=None, step=-1, nt=nt_th, fill=numpy.nan if fill_value is None else float(fill_value), keep=[])
+        slot = dict(lazy=None, step=-1, nt=nt_th, fill=numpy.nan if fill_value is None else float(fill_value),
+                    missing=numpy.nan if missing_value is None else float(missing_value), keep=[], arrays=[])
         ptrs, on_dev, lazy = [], None, []
         for (e3, _), which in zip(arrs, ('e3u', 'e3v')):
             dt = numpy.dtype(_native_dtype(e3))
@@ -702,6 +710,7 @@ class Field(object):
             else:
                 ptrs.append(ptr)
             slot['keep'].append(e3)     # a borrowed buffer must outlive the handle
+            slot['arrays'].append(e3)
         if lazy[0] != lazy[1]:
             raise RuntimeError('ERROR: e3u and e3v must both be read from files one step at a time, or neither')
         if lazy[0]:
@@ -839,6 +848,130 @@ class Field(object):
         (A, _), (T, _) = self.computeAreaProfile(tIndex)
         H = self.computeTracerFlux(tIndex)[0]
         return self.overturningGyre(V, (A, T), H)
+
+    # ------------------------------------------------------------------------------------------
+    _MEAN_STAGE_BYTES = 256 << 20     # host arrays go to the GPU in groups of steps of at most this many bytes
+
+    def _step_range(self, steps):
+        t0, t1 = (0, self.nt) if steps is None else (int(steps[0]), int(steps[1]))
+        if not 0 <= t0 < t1 <= self.nt:
+            raise RuntimeError(f'ERROR: steps must be None or a half-open (t0, t1) with 0 <= t0 < t1 <= {self.nt}, got {steps}')
+        return t0, t1
+
+    def _time_mean_array(self, a, markers, rule, t0, t1):
+        """The mean over the steps [t0, t1) of a (nt, nz, ny, nx) array in any of its three homes (HBM, host, file-backed), by
+        nf_time_mean: a float64 torch CUDA tensor (1, nz, ny, nx) and its fill -- the first marker as the dtype of `a` holds it,
+        NaN without one -- which stands where the value is missing at every step."""
+        import torch
+        dt = numpy.dtype(_native_dtype(a))
+        code = NF_F32 if dt == numpy.float32 else NF_F64
+        marks = [float(m) for m in markers if m == m]
+        with numpy.errstate(over='ignore'):
+            fill_out = float(dt.type(marks[0])) if marks else numpy.nan
+        fill, missing = (marks + [numpy.nan, numpy.nan])[:2]
+        n = self.nz * self.ny * self.nx
+        acc = torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda')
+
+        def run(ptr, nsteps, first, last, cnt=None):
+            check(lib.nf_time_mean(acc.data_ptr(), None if cnt is None else cnt.data_ptr(), ptr, nsteps, n, n, code, fill, missing,
+                                   1 if first else 0, 1 if last else 0, rule, t1 - t0, fill_out, None))
+
+        ptr = _lib.device_pointer(a)
+        if ptr is not None:       # HBM: one pass, nothing carried
+            run(ptr + t0 * n * dt.itemsize, t1 - t0, True, True)
+        else:
+            cnt = torch.empty(n, dtype=torch.int32, device='cuda')
+            lazy = hasattr(a, 'read_step')
+            if lazy:              # file-backed: one step at a time through one pinned buffer
+                group, buf = 1, self._host_array((self.nz, self.ny, self.nx), dt)
+            else:
+                group, host = max(1, self._MEAN_STAGE_BYTES // (n * dt.itemsize)), _native(a).reshape(self.nt, n)
+            stage = _lib.DeviceBuffer(min(group, t1 - t0) * n * dt.itemsize)
+            for t in range(t0, t1, group):
+                k = min(group, t1 - t)
+                if lazy:
+                    a.read_step(t, out=buf)
+                check(lib.nf_memcpy_h2d(stage.ptr, buf.ctypes.data if lazy else host[t:t + k].ctypes.data, k * n * dt.itemsize))
+                run(stage.ptr, k, t == t0, t + k == t1, cnt)
+                check(lib.nf_synchronize())     # the staging buffer is written again by the next group
+            stage.free()
+        check(lib.nf_synchronize())
+        return acc, fill_out
+
+    def timeMean(self, steps=None):
+        """The mean state of the steps [t0, t1) (steps=None: all of them) as a new Field with nt = 1 and float64 fields in HBM,
+        built through fromArrays from the same bounds, deptht_bounds, transects, sverdrup, periodX and cell policies: every
+        diagnostic of the engine works on it unchanged.  uo / vo: sum over the steps of the present values / number of steps
+        (a missing velocity counts as 0, as in every flux kernel, so the volume flux of the mean state is the mean of the
+        volume fluxes); a value missing at every step is the new Field's fill, the source's first marker as its dtype holds it
+        (NaN without one).  A tracer of setTracer / setClassTracer: the mean of its present values, set on the new Field with
+        the same reference and wrapX; the class edges are carried over.  A static cell thickness is carried over as float64;
+        a time-varying one, and a sharded Field (slab_range), raise.  The sums are float64, left to right in step order
+        (nf_time_mean), wherever the arrays live: HBM (one pass), host (uploaded in groups of steps) or files (one step at a
+        time).  Nothing of this Field changes."""
+        if self.slab_range is not None:
+            raise RuntimeError('ERROR: timeMean: the mean state of a sharded Field (slab_range) is not defined here; build the '
+                               'Field without slab_range')
+        e3 = getattr(self, '_e3', None)
+        if e3 is not None and e3['nt'] != 1:
+            raise RuntimeError('ERROR: timeMean: the mean state of a time-varying cell thickness is not defined here (it would '
+                               'need thickness-weighted means); set a static thickness or none')
+        t0, t1 = self._step_range(steps)
+        u, fill = self._time_mean_array(self._uv[0], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
+        v, _ = self._time_mean_array(self._uv[1], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
+        mean = Field.fromArrays(self._bounds[0], self._bounds[1], self.bounds_depth, u, v, self._polylines, self.sverdrup,
+                                fill_value=fill, **self._build_kw)
+
+        def none_if_nan(x):
+            return None if x != x else x
+
+        tr = getattr(self, '_tracer', None)
+        if tr is not None:
+            tau, tfill = self._time_mean_array(tr['keep'], (tr['fill'], tr['missing']), _lib.NF_MEAN_OVER_PRESENT, t0, t1)
+            mean.setTracer(tau, fill_value=none_if_nan(tfill), reference=self._tracer_reference, wrapX=self._tracer_wrapX)
+        ct = getattr(self, '_class_tracer', None)
+        if ct is not None:
+            sig, sfill = self._time_mean_array(ct['keep'], (ct['fill'], ct['missing']), _lib.NF_MEAN_OVER_PRESENT, t0, t1)
+            mean.setClassTracer(sig, fill_value=none_if_nan(sfill))
+        if getattr(self, '_class_edges', None) is not None:
+            mean.setClassEdges(self._class_edges)
+        if e3 is not None:
+            dt = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+            with numpy.errstate(over='ignore'):
+                marks = [none_if_nan(float(dt.type(m))) if m == m else None for m in (e3['fill'], e3['missing'])]
+            mean.setCellThickness(*[self._as_float64(x) for x in e3['arrays']], fill_value=marks[0], missing_value=marks[1])
+        return mean
+
+    @staticmethod
+    def _as_float64(a):
+        """a static thickness as float64, where it lives"""
+        import torch
+        if isinstance(a, torch.Tensor):
+            return a.to(torch.float64)
+        if isinstance(a, _lib.DeviceArray):
+            if a.dtype == numpy.float64:
+                return a
+            host = numpy.empty(a.shape, a.dtype)
+            check(lib.nf_memcpy_d2h(host.ctypes.data, a.ptr, host.nbytes))
+            a = host
+        return numpy.ascontiguousarray(a, dtype=numpy.float64)
+
+    def meanEddyTracerTransport(self, steps=None):
+        """The mean tracer transport of the steps [t0, t1) (steps=None: all; setTracer first) split in time, for the transect
+        totals: 'total' = the float64 mean over the steps of the computeTracerFlux totals; 'mean' = computeTracerFlux(0) of
+        timeMean(steps), the transport of the mean tracer by the mean flow; 'eddy' = total - mean, the part <u' tau'> carried
+        by the correlation of the fluctuations; 'meanField' = that Field, for its profile, class and decomposition calls."""
+        if getattr(self, '_tracer', None) is None:
+            raise RuntimeError('ERROR: call setTracer first')
+        t0, t1 = self._step_range(steps)
+        if (t0, t1) == (0, self.nt):
+            rows = self.computeTracerAll()[0]
+        else:
+            rows = numpy.array([self.computeTracerFlux(t)[0] for t in range(t0, t1)])
+        total = numpy.asarray(rows, dtype=numpy.float64).sum(axis=0) / float(t1 - t0)
+        meanField = self.timeMean(steps)
+        mean = numpy.array(meanField.computeTracerFlux(0)[0], dtype=numpy.float64)
+        return dict(total=total, mean=mean, eddy=total - mean, meanField=meanField)
 
     def computeClassTracerTransport(self, tIndex, out=None, prefetch_next=None):
         """Transport of the tracer of setTracer (reference subtracted) of time step tIndex, binned by the class of each U / V

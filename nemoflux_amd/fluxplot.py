@@ -15,6 +15,7 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --tracer sigma0 --tracer-file S.nc --classes 26,27,28 --carry thetao --carry-scale 4.1e-3   (heat by sigma0 class)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
+    ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
 """
@@ -134,6 +135,32 @@ def decomposeSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', t
         d = fld.decomposeTracerTransport(t)
         totals[t] = [d[k] for k in PARTS]
     return totals, fld
+
+
+EDDY_PARTS = ('total', 'mean', 'eddy')
+
+
+def eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None):
+    """(3, ntransect): the mean over all time steps of the transport of the variable `tracer` of tracerFile (default: the T
+    file), the transport of the time-mean tracer by the time-mean flow, and their difference, the eddy part (EDDY_PARTS;
+    Field.meanEddyTracerTransport), and the Field."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    d = fld.meanEddyTracerTransport()
+    return numpy.array([d[k] for k in EDDY_PARTS]).reshape(len(EDDY_PARTS), len(lonLatZPoints)), fld
+
+
+def checkEddyArgs(eddy=False, tracer='', classes='', levels=False, zrange='', show=False, decompose=False):
+    """the --eddy option of the command line: refused combinations raise RuntimeError"""
+    if not eddy:
+        return
+    if not tracer:
+        raise RuntimeError('ERROR: --eddy needs --tracer NAME (the tracer whose mean transport is split in time)')
+    for on, opt in ((classes, '--classes'), (levels, '--levels'), (zrange, '--zrange'), (show, '--show'),
+                    (decompose, '--decompose')):
+        if on:
+            raise RuntimeError(f'ERROR: --eddy and {opt} cannot be combined: --eddy writes the time-mean transport of --tracer, '
+                               f'its mean-flow part and its eddy part as CSV only')
 
 
 def checkDecomposeArgs(decompose=False, tracer='', classes='', levels=False, zrange='', show=False):
@@ -260,7 +287,9 @@ def parseZRange(zrange):
 
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
-         carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False):
+         carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
+         eddy=False):
+    checkEddyArgs(eddy, tracer, classes, levels, zrange, show, decompose)
     checkDecomposeArgs(decompose, tracer, classes, levels, zrange, show)
     checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, carry, levels, tracer)
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
@@ -271,6 +300,15 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
     ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    if eddy:
+        totals, fld = eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
+        totals = totals * float(tracerScale)
+        unit = f'{tracer} x {unit}' + (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '')
+        lines = ['part,' + ','.join(names)]
+        lines += [f'{part},' + ','.join(f'{x:.15g}' for x in totals[k]) for k, part in enumerate(EDDY_PARTS)]
+        _emit(f'# mean transport of {tracer} over {fld.nt} time steps, its mean-flow and eddy parts [{unit}]\n' +
+              '\n'.join(lines) + '\n', output)
+        return totals
     if decompose:
         totals, fld = decomposeSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
         totals = totals * float(tracerScale)
@@ -385,6 +423,10 @@ if __name__ == '__main__':
     ap.add_argument('--decompose', action='store_true',
                     help='with --tracer NAME: one CSV line per time step and part (time,part,...): the transport of NAME and its '
                          'throughflow, overturning and gyre parts (--tracer-ref, --tracer-scale, -s and --cell-thickness apply)')
+    ap.add_argument('--eddy', action='store_true',
+                    help='with --tracer NAME: one CSV line per part (part,...): the mean over all time steps of the transport of '
+                         'NAME, the transport of the time-mean NAME by the time-mean flow, and the eddy part, their difference '
+                         '(--tracer-ref, --tracer-scale, -s apply)')
     ap.add_argument('--cell-thickness', dest='cellThickness', action='store_true',
                     help='integrate with per-cell layer thicknesses (partial steps, z*) read from the U and V files instead of '
                          'deptht_bounds; with the plain series, --zrange, --levels (without --tracer) and --tracer NAME')
