@@ -375,7 +375,14 @@ int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, 
  * the markers.  Setting or clearing invalidates a captured pass; the all-steps-in-one-launch form of small grids is not used
  * while one is set.  Refused while one is set (NF_ERR_STATE, the message saying how to clear it): the forms that do not take
  * per-cell thicknesses yet -- nf_field_compute_tracer_profile*, nf_field_compute_class_transport* and
- * nf_field_compute_class_tracer_transport*. */
+ * nf_field_compute_class_tracer_transport*.
+ * A static host array that the handle uploaded belongs to the (nz, ny, nx) in force at that call.  After an
+ * nf_field_set_bounds or nf_field_set_thickness that changes that shape (the shapes are compared, not the byte counts; a
+ * call that leaves the shape as it was keeps the upload valid) every compute that would read the thickness returns
+ * NF_ERR_STATE, the message naming nf_field_set_cell_thickness, and launches nothing, until nf_field_set_cell_thickness is
+ * called again, with arrays of the new shape or with NULL.  Borrowed arrays -- uo / vo, the tracer, the class tracer, an HBM
+ * or time-varying cell thickness -- carry no shape in their calls: the caller must set them again after a change of the grid
+ * or of the levels. */
 int nf_field_set_cell_thickness(nf_field **self, const void *e3u, const void *e3v, long nt_th, int dtype, int on_device,
                                 double fill_value);
 int nf_field_set_cell_thickness_missing_value(nf_field **self, double missing_value);   /* NaN = none */

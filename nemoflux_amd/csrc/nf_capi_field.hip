@@ -142,6 +142,8 @@ struct nf_field {
     double e3_fill = std::numeric_limits<double>::quiet_NaN();
     double e3_fill2 = std::numeric_limits<double>::quiet_NaN();   // nf_field_set_cell_thickness_missing_value
     DevArray<char> e3u_static, e3v_static, stage_e3u, stage_e3v;
+    // the (nz, ny, nx) in force when e3?_static were uploaded: the upload belongs to that shape (field_cell_thick_current)
+    long e3_static_nz = 0, e3_static_ny = 0, e3_static_nx = 0;
     // tracer profile (nf_field_compute_tracer_profile): the run sums of one chunk (ws.nrec * tracer_profile_chunk(dtype))
     DevArray<double> tprof_scratch;
     // area profile (nf_field_compute_area_profile): the run sums of one chunk, two values per level (ws.nrec * 2 * area_chunk)
@@ -297,13 +299,29 @@ static int field_ensure_derived(nf_field *f)
 static Transects field_transects(const nf_field *f) { return Transects{&f->ws, f->tr_off_dev.get(), (int)f->polylines.size()}; }
 static int field_row_length(const nf_field *f) { return (int)field_transects(f).row_length(); }
 
+// A static host cell thickness that the handle uploaded has the shape of the upload, not of the field: after a set_bounds or
+// set_thickness that changed (nz, ny, nx) nothing may read it (the kernels take its pointer without a size).  The shapes are
+// compared, not the byte counts: 2 x 100 and 4 x 50 cells are as many bytes.
+static int field_cell_thick_current(const nf_field *f, const char *what)
+{
+    if (!f->e3u || !f->e3u_static.get()) return NF_OK;
+    if (f->e3_static_nz == f->nz && f->e3_static_ny == f->ny && f->e3_static_nx == f->nx) return NF_OK;
+    char buf[320];
+    snprintf(buf, sizeof buf,
+             ": the static cell thickness was uploaded for (nz, ny, nx) = (%ld, %ld, %ld) and the field is now (%ld, %ld, %ld); "
+             "call nf_field_set_cell_thickness again with arrays of the new shape, or clear it with NULL",
+             f->e3_static_nz, f->e3_static_ny, f->e3_static_nx, f->nz, f->ny, f->nx);
+    NF_REQUIRE(false, NF_ERR_STATE, std::string(what) + buf);
+    return NF_OK;
+}
+
 // the state every per-step computation needs; `what` prefixes the message ("compute", "compute_profile", ...)
 static int field_ready(const nf_field *f, const char *what, bool weights)
 {
     NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
                std::string(what) + ": set_bounds, set_thickness and set_uv first");
     NF_REQUIRE(!weights || f->weights_built, NF_ERR_STATE, std::string(what) + ": build_weights first");
-    return NF_OK;
+    return field_cell_thick_current(f, what);
 }
 
 // the end of the slabs [s_begin, s_end) of the nt * nz that this rank owns (set_slab_range; s_end < 0: up to the last one)
@@ -711,16 +729,29 @@ static int field_prepare_pass(nf_field *f)
 // every time step of a pass, one after the other.  A rank of a multi-GPU run owns a contiguous range of steps (slab
 // sharding): the rows of all the others are zeroed with two memsets instead of one per step (at 8 ranks that is 84 tiny
 // launches per pass saved), and only the owned steps are walked.
-static int field_all_steps_direct(nf_field *f, double *rows_dev)
+// the rows of the steps before and after this rank's own: exact zeros
+static int field_zero_unowned_rows(nf_field *f, double *rows_dev)
 {
     const int rowlen = field_row_length(f);
     const PassSteps p = field_pass_steps(f);
-    if (rowlen > 0) {
-        if (p.ta > 0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)p.ta, f->stream));
-        if (p.tb < f->nt)
-            NF_HIP(hipMemsetAsync(rows_dev + (size_t)p.tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nt - p.tb),
-                                  f->stream));
-    }
+    if (rowlen <= 0) return NF_OK;
+    if (p.ta > 0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)p.ta, f->stream));
+    if (p.tb < f->nt)
+        NF_HIP(hipMemsetAsync(rows_dev + (size_t)p.tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nt - p.tb), f->stream));
+    return NF_OK;
+}
+
+// zero_rows = false: the caller zeroes the other ranks' rows itself -- a captured pass, whose memsets stay out of the graph.
+// Observed once (tests/test_gpu_reuse_products.py, seed 14): with the memsets as nodes of the graph, a replay that followed a
+// flux call and other allocations of the process left other bytes than zeros in the row of a step that is not owned.  Nothing
+// else in the library writes such a row, but the cause is not established -- whether the replayed memset node or something
+// else -- so this is a workaround: the memsets are issued on the stream before every launch of the graph.  Their cost (at
+// most two small stream memsets per pass of a sharded rank, none for a rank that owns every step) was not measured on its own.
+static int field_all_steps_direct(nf_field *f, double *rows_dev, bool zero_rows = true)
+{
+    const int rowlen = field_row_length(f);
+    const PassSteps p = field_pass_steps(f);
+    if (zero_rows) NF_TRY(field_zero_unowned_rows(f, rows_dev));
     const bool pairs = field_pass_pairs(f) && rowlen > 0;
     // an odd number of whole steps leaves one of them single: the first, so that the last pair ends on the last whole step
     // and every pair's second step lands in the resident planes
@@ -1127,12 +1158,14 @@ try {
     NF_NEED_DEVICE();
     nf_field *f = *self;
     NF_REQUIRE(f->weights_built, NF_ERR_STATE, "nf_field_compute_all_async: build_weights first");
+    NF_TRY(field_cell_thick_current(f, "nf_field_compute_all_async"));   // before a capture, and for a rank that owns no step
     if (field_can_batch(f)) return field_all_steps_batched(f, rows_dev);
     NF_TRY(field_prepare_pass(f));   // allocations stay out of a graph capture
     // Replay a captured graph of the whole pass when nothing changed since it was captured.  Capture needs a real
     // (non-null) stream, resident fields (a cell thickness included), and no per-launch timing events.
     const bool can_graph = g_use_graph && f->stream != nullptr && f->uv_on_device && (!f->e3u || f->e3_on_device) && !f->timing;
     if (can_graph && f->graph_exec && f->graph_rows == rows_dev && f->graph_version == field_pass_version(f)) {
+        NF_TRY(field_zero_unowned_rows(f, rows_dev));
         NF_HIP(hipGraphLaunch(f->graph_exec, f->stream));
         return NF_OK;
     }
@@ -1140,13 +1173,14 @@ try {
         field_drop_graph(f);
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int rc = field_all_steps_direct(f, rows_dev);
+            const int rc = field_all_steps_direct(f, rows_dev, false);
             hipError_t e = hipStreamEndCapture(f->stream, &graph);
             if (rc == NF_OK && e == hipSuccess && graph &&
                 hipGraphInstantiate(&f->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                 (void)hipGraphDestroy(graph);
                 f->graph_rows = rows_dev;
                 f->graph_version = field_pass_version(f);
+                NF_TRY(field_zero_unowned_rows(f, rows_dev));
                 NF_HIP(hipGraphLaunch(f->graph_exec, f->stream));
                 return NF_OK;
             }
@@ -1427,6 +1461,7 @@ try {
         NF_HIP(hipStreamSynchronize(f->stream));   // kernels in flight may still read the arrays these replace
         f->e3u_static = std::move(du);
         f->e3v_static = std::move(dv);
+        f->e3_static_nz = f->nz, f->e3_static_ny = f->ny, f->e3_static_nx = f->nx;
         e3u = f->e3u_static.get();
         e3v = f->e3v_static.get();
     } else {
