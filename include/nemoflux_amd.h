@@ -299,6 +299,26 @@ int nf_field_compute_tracer_all_async(nf_field **self, double *rows_dev);       
 int nf_field_set_class_edges(nf_field **self, const double *edges, int nedges);
 int nf_field_compute_class_transport(nf_field **self, long tIndex, double *rows_host);        /* (nedges+2, row_length) */
 int nf_field_compute_class_transport_async(nf_field **self, long tIndex, double *rows_dev);   /* HBM, field's stream */
+/* Transport in JOINT classes of two tracers (theta and S, sigma and theta: the volumetric T-S census of a section; its
+ * cumulative sum along one axis is the thermohaline streamfunction).  Axis A is the tracer of nf_field_set_tracer with the
+ * edges edges_a, axis B the class tracer of nf_field_set_class_tracer with the edges edges_b; both tracers are required.  A
+ * face has the 1-D row ra of A's raw face value among edges_a and rb of B's among edges_b, each as defined above (no value
+ * or NaN: na + 1 / nb + 1); its term goes to the joint row ra * (nb + 2) + rb.  One time step gives (na + 2) * (nb + 2) rows
+ * of row_length doubles, written whole, exact zeros where nothing falls.  carry = 0: the per-level volume terms of
+ * nf_field_compute_class_transport; carry = 1: every term times tf of the tracer A at its own face, reference subtracted, as in
+ * nf_field_compute_class_tracer_transport.  The accumulation order and the summation tree are those of the 1-D forms: the rows
+ * are bitwise reproducible, do not depend on the tuning knobs "joint_window" (1 .. 32 rows per pass, default 32) and
+ * "joint_skip" (0 / 1), and an axis with a single occupied class gives the 1-D rows of the other axis bit for bit.  The fields
+ * are gathered once per call into a term table that the handle owns: 40 bytes x records x owned levels of HBM, allocated on
+ * first use, dropped with the weights; when it cannot be allocated the call fails with NF_ERR_HIP and names the size.
+ * Each edge set: 2 <= n <= 1025, finite, strictly increasing, and (na + 2) * (nb + 2) <= 16384 (else NF_ERR_ARG naming the
+ * count); two NULLs clear the edges.  This state is separate from nf_field_set_class_edges: the 1-D forms do not see it.
+ * Owned levels only (set_slab_range).  Compute before set_tracer, set_class_tracer or set_joint_class_edges: NF_ERR_STATE;
+ * with a cell thickness set: NF_ERR_STATE, as the 1-D class forms.  The calls change nothing else: not the resident planes,
+ * the running max, the last row, the tracer planes, the 1-D class rows or a captured pass. */
+int nf_field_set_joint_class_edges(nf_field **self, const double *edges_a, int na, const double *edges_b, int nb);
+int nf_field_compute_joint_class_transport(nf_field **self, long tIndex, int carry, double *rows_host);
+int nf_field_compute_joint_class_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev);   /* HBM */
 /* Depth- and class-resolved tracer transports: the two forms above with the tracer of nf_field_set_tracer carried by the flow.
  * Every per-level term fma(th_z, fixed(x), 0) * arc of nf_field_compute_profile becomes fma(th_z, fixed(x) * tf, 0) * arc, tf
  * the face value of the tracer block (markers, reference and wrap_x included) at the slot's own face: east slot = east face

@@ -127,6 +127,9 @@ _sig('nf_field_compute_tracer_all_async', [_pp, ctypes.c_void_p])
 _sig('nf_field_set_class_edges', [_pp, c_double_p, ctypes.c_int])
 _sig('nf_field_compute_class_transport', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_class_transport_async', [_pp, ctypes.c_long, ctypes.c_void_p])
+_sig('nf_field_set_joint_class_edges', [_pp, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int])
+_sig('nf_field_compute_joint_class_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
+_sig('nf_field_compute_joint_class_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_compute_tracer_profile', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_tracer_profile_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_compute_area_profile', [_pp, ctypes.c_long, c_double_p])

@@ -19,12 +19,17 @@ static int g_batch_steps = 1;
 //                          stream once for both steps; 0 = one reduction per step (default 1)
 //   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
 //   "area_chunk"           levels per launch of the area profile: 2 or 4 (float64), 4 or 8 (float32); 0 = the measured default
+//   "joint_window"         rows of the joint class transport per pass over its term table, 1 .. 32 (default 32)
+//   "joint_skip"           1 = a block of the joint binning whose records have no term in the window does not read the table
+//                          (default 1: docs/EXPERIMENTS.md); the rows are the same bits either way
 static long g_batch_cellsteps = 32l << 20;
 static int g_partial_full = 0;
 static int g_use_graph = 1;
 static int g_inner_signed = 1;
 static int g_k3_pairs = 1;
 static int g_class_window = 32;
+static int g_joint_window = 32;
+static int g_joint_skip = 1;
 static long g_knob_version = 0;   // bumped by every knob of this file: a captured pass bakes them in
 
 namespace nf {
@@ -59,6 +64,16 @@ int field_tuning_set(const char *name, int value)
     if (!strcmp(name, "class_window")) {
         if (!(value >= 1 && value <= kClassWindowMax)) return -1;
         g_class_window = value;
+        return NF_OK;
+    }
+    if (!strcmp(name, "joint_window")) {
+        if (!(value >= 1 && value <= kClassWindowMax)) return -1;
+        g_joint_window = value;
+        return NF_OK;
+    }
+    if (!strcmp(name, "joint_skip")) {
+        if (!(value == 0 || value == 1)) return -1;
+        g_joint_skip = value;
         return NF_OK;
     }
     if (!strcmp(name, "area_chunk")) return area_chunk_set(value);
@@ -154,6 +169,18 @@ struct nf_field {
     bool class_edges_stale = false;
     DevArray<double> class_edges_dev;
     DevArray<double> class_scratch;
+    // joint class transport (nf_field_set_joint_class_edges): state of its own, the 1-D forms do not see it.  The edges of
+    // axis A then axis B on the host, uploaded by the next compute after a change.  The term table (40 bytes per record and
+    // owned level), the block flags and the run sums of one window are allocated on first use, grown when the records, the
+    // owned levels or the rows ask for more -- their layout is taken from the call's own sizes, never from an earlier one's
+    // -- and dropped with the weights.
+    std::vector<double> joint_edges;
+    int joint_na = 0, joint_nb = 0;
+    bool joint_edges_stale = false;
+    DevArray<double> joint_edges_dev;
+    DevArray<char> joint_table;
+    DevArray<unsigned> joint_flags;
+    DevArray<double> joint_scratch;
     Grid_t grid_view;
     // timing
     bool timing = false;
@@ -666,6 +693,76 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool ca
     return launch_class_transport(a, f->stream);
 }
 
+// the calls of the joint class transport need both tracers and the joint edges: checked before a device is needed
+static int field_joint_ready(const nf_field *f, const char *what)
+{
+    NF_REQUIRE(f->tau, NF_ERR_STATE, std::string(what) + ": set_tracer first");
+    NF_REQUIRE(f->sig, NF_ERR_STATE, std::string(what) + ": set_class_tracer first");
+    NF_REQUIRE(!f->joint_edges.empty(), NF_ERR_STATE, std::string(what) + ": set_joint_class_edges first");
+    NF_TRY(field_ready(f, what, true));
+    return field_no_cell_thick(f, what);
+}
+
+static size_t field_joint_rows(const nf_field *f) { return (size_t)(f->joint_na + 2) * (size_t)(f->joint_nb + 2); }
+
+// Transport of step t in joint classes of the tracer (axis A) and the class tracer (axis B) on the field's stream: rows_dev
+// ((na + 2) * (nb + 2), row_length), written whole.  Owned levels only, exact zeros for a step this rank does not touch.
+// Reads the raw fields, both tracers and the records; the resident planes, |.| arrays, running max, last row, tracer planes,
+// 1-D class rows, version and a captured pass stay as they are.  carry: the transport of the tracer instead of the volume.
+static int field_joint_step_async(nf_field *f, long t, bool carry, double *rows_dev)
+{
+    const size_t nrows = field_joint_rows(f);
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_joint_class_transport", t, 2, rows_dev, nrows, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    if (f->joint_edges_stale) {
+        // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
+        NF_TRY(f->joint_edges_dev.reserve(2 * (size_t)kMaxClassEdges));
+        NF_HIP(hipMemcpyAsync(f->joint_edges_dev.get(), f->joint_edges.data(), sizeof(double) * f->joint_edges.size(),
+                              hipMemcpyHostToDevice, f->stream));
+        NF_HIP(hipStreamSynchronize(f->stream));
+        f->joint_edges_stale = false;
+    }
+    const int window = g_joint_window;
+    const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
+    const size_t table_bytes = kJointEntryBytes * nrec * (size_t)(lv.z1 - lv.z0);
+    if (f->joint_table.size() == 0 || f->joint_table.size() < table_bytes) {
+        // 11.6 GB on the bench workload: a failure names the size, and nothing falls back to another path
+        if (f->joint_table.alloc(table_bytes) != NF_OK) {
+            char buf[256];
+            snprintf(buf, sizeof buf,
+                     "compute_joint_class_transport: cannot allocate the term table of %zu bytes (40 bytes x %zu records x %d "
+                     "owned levels)",
+                     table_bytes, nrec, lv.z1 - lv.z0);
+            NF_REQUIRE(false, NF_ERR_HIP, buf);
+        }
+    }
+    NF_TRY(f->joint_flags.reserve(blocks * (size_t)joint_flag_words((int)nrows, window)));
+    NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
+    JointArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_tracer_input(f, t, lv, &a));
+    NF_TRY(field_stage(f, f->sig, f->sig_on_device, t, lv, &f->stage_sig, &a.sig));
+    a.sfill = f->sig_fill;
+    a.sfill2 = f->sig_fill2;
+    a.ref = f->tau_ref;
+    a.carry = carry ? 1 : 0;
+    a.edges = f->joint_edges_dev.get();
+    a.na = f->joint_na;
+    a.nb = f->joint_nb;
+    a.window = window;
+    a.skip = g_joint_skip;
+    a.tr = field_transects(f);
+    a.table = f->joint_table.get();
+    a.table_len = f->joint_table.size();
+    a.flags = f->joint_flags.get();
+    a.flags_len = f->joint_flags.size();
+    a.scratch = f->joint_scratch.get();
+    a.scratch_len = f->joint_scratch.size();
+    a.rows = rows_dev;
+    return launch_joint_class_transport(a, f->stream);
+}
+
 // steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
 // step, as after two single steps), then ONE reduction of both; rows t and t+1 are contiguous in rows_dev.  last: t+1 is the
 // last owned step of the pass, which stores what it stores on its own.
@@ -1032,6 +1129,9 @@ try {
     f->tprof_scratch.reset();
     f->area_scratch.reset();
     f->class_scratch.reset();
+    f->joint_table.reset();
+    f->joint_flags.reset();
+    f->joint_scratch.reset();
     const int bw = build_weights(f->geo.xy.get(), f->ncell, segs.data(), cc.data(), (int)cc.size(), periodX, &f->ws, f->stream,
                                  f->skip_unsupported, f->overlap_warn, nullptr, f->nx);
     if (bw != NF_OK) {
@@ -1327,6 +1427,73 @@ try {
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport_async"));
     NF_NEED_DEVICE();
     return field_class_step_async(f, tIndex, rows_dev);
+}
+NF_API_CATCH
+
+// one edge set of nf_field_set_joint_class_edges: the rules of nf_field_set_class_edges
+static int joint_edges_check(const char *axis, const double *edges, int n)
+{
+    const std::string w = std::string("nf_field_set_joint_class_edges: axis ") + axis + ": ";
+    if (!(n >= 2 && n <= kMaxClassEdges)) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "need 2 <= nedges <= %d, got %d", kMaxClassEdges, n);
+        NF_REQUIRE(false, NF_ERR_ARG, w + buf);
+    }
+    for (int k = 0; k < n; ++k) {
+        NF_REQUIRE(std::isfinite(edges[k]), NF_ERR_ARG, w + "every edge must be a finite number");
+        NF_REQUIRE(k == 0 || edges[k] > edges[k - 1], NF_ERR_ARG, w + "the edges must be strictly increasing");
+    }
+    return NF_OK;
+}
+
+int nf_field_set_joint_class_edges(nf_field **self, const double *edges_a, int na, const double *edges_b, int nb)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_joint_class_edges: null field");
+    nf_field *f = *self;
+    if (!edges_a && !edges_b) {   // no joint classes
+        f->joint_edges.clear();
+        f->joint_na = f->joint_nb = 0;
+        return NF_OK;
+    }
+    NF_REQUIRE(edges_a && edges_b, NF_ERR_ARG, "nf_field_set_joint_class_edges: null argument");
+    NF_TRY(joint_edges_check("A", edges_a, na));
+    NF_TRY(joint_edges_check("B", edges_b, nb));
+    if ((na + 2) * (nb + 2) > kMaxJointRows) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "nf_field_set_joint_class_edges: (na + 2) * (nb + 2) = %d joint rows, at most %d are supported",
+                 (na + 2) * (nb + 2), kMaxJointRows);
+        NF_REQUIRE(false, NF_ERR_ARG, buf);
+    }
+    f->joint_edges.assign(edges_a, edges_a + na);
+    f->joint_edges.insert(f->joint_edges.end(), edges_b, edges_b + nb);
+    f->joint_na = na;
+    f->joint_nb = nb;
+    f->joint_edges_stale = true;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_joint_class_transport(nf_field **self, long tIndex, int carry, double *rows_host)
+try {
+    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_joint_class_transport: null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_joint_class_transport: carry must be 0 or 1");
+    nf_field *f = *self;
+    NF_TRY(field_joint_ready(f, "nf_field_compute_joint_class_transport"));
+    NF_NEED_DEVICE();
+    const size_t n = field_joint_rows(f) * (size_t)field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_joint_step_async(f, tIndex, carry != 0, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_joint_class_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
+try {
+    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_joint_class_transport_async: null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_joint_class_transport_async: carry must be 0 or 1");
+    nf_field *f = *self;
+    NF_TRY(field_joint_ready(f, "nf_field_compute_joint_class_transport_async"));
+    NF_NEED_DEVICE();
+    return field_joint_step_async(f, tIndex, carry != 0, rows_dev);
 }
 NF_API_CATCH
 

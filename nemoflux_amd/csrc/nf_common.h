@@ -501,6 +501,41 @@ struct ClassArgs {
 };
 int launch_class_transport(const ClassArgs &a, hipStream_t s);
 
+// Transport in JOINT classes of two tracers (nf_field_compute_joint_class_transport, nf_integral.hip): axis A is the tracer
+// (edges ea, na), axis B the class tracer (edges eb, nb); joint row ra * (nb + 2) + rb, ra / rb the 1-D rows of the face's
+// raw value of A / B.  Stage 1 gathers once and writes, per (record, owned level), the four weighted slot terms and their
+// four joint rows to the term table; stage 2 bins the table `window` rows at a time.  The table, per owned level zi:
+//   terms + (zi * 2 + 0) * nrec: dvec2 (south, east) per record;  terms + (zi * 2 + 1) * nrec: dvec2 (north, west);
+//   rows + zi * nrec: 4 x uint16 per record (south, east, north, west; kJointNoRow: the slot contributes nothing)
+// -- 40 bytes per (record, level), a wave's loads 64 consecutive 16- or 8-byte elements.  flags: one bit per (block of
+// kBlock records, window), words_per_block 32-bit words a block; a clear bit: no term of the block has a row in the window.
+constexpr int kMaxJointRows = 16384;
+constexpr unsigned kJointNoRow = 0xFFFFu;
+constexpr size_t kJointEntryBytes = 40;
+struct JointArgs {
+    StepInput in;
+    const void *tau = nullptr, *sig = nullptr;   // A and B at the base of the time step: (nz, ncell) of the field dtype
+    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");   // A's markers
+    double sfill = __builtin_nan(""), sfill2 = __builtin_nan("");   // B's markers
+    double ref = 0.0;            // A's reference (carried form)
+    int wrap_x = 1;
+    int carry = 0;               // 1: every term times tr_face of A at its own face
+    const double *edges = nullptr;   // device: ea (na doubles) followed by eb (nb doubles)
+    int na = 0, nb = 0;
+    int window = 0;              // rows per pass over the table, 1 .. kClassWindowMax
+    int skip = 1;                // 1: a stage-2 block whose flag is clear does not read the table
+    Transects tr;
+    char *table = nullptr;       // kJointEntryBytes * nrec * (z1 - z0) bytes
+    size_t table_len = 0;
+    unsigned *flags = nullptr;   // blocks * words_per_block words
+    size_t flags_len = 0;
+    double *scratch = nullptr;   // nrec * window run sums
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // ((na + 2) * (nb + 2), row_length)
+};
+inline int joint_flag_words(int nrows, int window) { return ((nrows + window - 1) / window + 31) / 32; }
+int launch_joint_class_transport(const JointArgs &a, hipStream_t s);
+
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q
 int launch_find_points(const double *xy, long ncell, long row_length, LocatorBoxes *keep, const double *targets_dev, long npts,

@@ -850,4 +850,204 @@ int launch_class_transport(const ClassArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "class transport: dtype must be NF_F64 or NF_F32");
 }
 
+// ---- transport in joint classes of two tracers: gather once (k_joint_terms), bin many times (k_joint_bin) -------------
+// The terms and the accumulation are k_class_segscan's: per owned level (z ascending) the four slot terms of level_slots_tf
+// times their weights, each added in slot order (south, east, north, west) to the lane's accumulator of its row, then
+// seg_scan_step per row with the one set of flags.  What differs is the row -- ra * (nb + 2) + rb from the faces' raw values
+// of A and of B -- and that there may be thousands of rows: a window-by-window pass over the FIELDS would repeat the 14
+// gathers per level for every window, so stage 1 issues them once and leaves the products and their rows in a table (layout:
+// JointArgs), which stage 2 streams once per window with contiguous, full-sector loads.  -ffp-contract=off: a stored product
+// added later has the bits of the product added at once, hence the 1-D class rows bit for bit where one axis has one class.
+constexpr int kJointLevels = 4;        // levels whose 14 gathers (stage 1) or table loads (stage 2) are issued together
+typedef unsigned short usvec4 __attribute__((ext_vector_type(4)));
+
+// Stage 1.  LDS: ea (na doubles), eb (nbe doubles), then the block's window bitmap (nwords words), filled with LDS OR -- the
+// outcome does not depend on the order -- and stored with one vector store per word.
+template <typename T, bool CARRY>
+__global__ __launch_bounds__(kBlock) void k_joint_terms(const int *__restrict__ cell, const double *__restrict__ w4, long n,
+                                                        const T *__restrict__ u, const T *__restrict__ v,
+                                                        const T *__restrict__ sig, long ncell, unsigned nx, int z0, int z1,
+                                                        const double *__restrict__ thickness,
+                                                        const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                        T fill, T fill2, int two, TauIn<T> ta, T sfill, T sfill2, double scale,
+                                                        int sverdrup, const double *__restrict__ edges, int na, int nbe,
+                                                        int topa, int topb, int window, int nwords,
+                                                        dvec2 *__restrict__ terms, usvec4 *__restrict__ rows,
+                                                        unsigned *__restrict__ flags)
+{
+    extern __shared__ double joint_lds[];
+    const double *ea = joint_lds, *eb = joint_lds + na;
+    unsigned *bits = reinterpret_cast<unsigned *>(joint_lds + na + nbe);
+    for (int q = threadIdx.x; q < na + nbe; q += kBlock) joint_lds[q] = edges[q];
+    for (int q = threadIdx.x; q < nwords; q += kBlock) bits[q] = 0u;
+    __syncthreads();
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    if (k < n) {
+        const Record r = load_record(cell, w4, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, ta.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        // the joint row of the face (a0, a1) of A and (b0, b1) of B; its window is marked in the bitmap
+        auto joint_row = [&](T a0, T a1, T b0, T b1, bool has) {
+            double f;
+            bool h = tr_face_raw<T>(a0, a1, has, ta.m1, ta.m2, &f);
+            const int ra = class_row(h, f, ea, na, topa);
+            h = tr_face_raw<T>(b0, b1, has, sfill, sfill2, &f);
+            const int row = ra * (nbe + 2) + class_row(h, f, eb, nbe, topb);
+            const int w = row / window;
+            const unsigned m = 1u << (w & 31);
+            if (!(bits[w >> 5] & m)) atomicOr(&bits[w >> 5], m);   // the read only spares the OR: a stale 0 sets the bit again
+            return (unsigned short)row;
+        };
+        for (int z = z0; z < z1; z += kJointLevels) {
+            const int nlev = z1 - z < kJointLevels ? z1 - z : kJointLevels;
+            LevelUV<T> x[kJointLevels];
+            LevelTau<T> A[kJointLevels], B[kJointLevels];
+#pragma unroll
+            for (int l = 0; l < kJointLevels; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    A[l] = load_level_tau(ta.tau, o, r.c, nb);
+                    B[l] = load_level_tau(sig, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < kJointLevels; ++l)
+                if (l < nlev) {
+                    FaceTf tf{};
+                    if constexpr (CARRY) tf = level_tf(A[l], nb, ta);
+                    const Slots d = level_slots_tf<T, CARRY>(slot_th(thickness[z + l]), x[l], arc, fill, fill2, two, scale, sverdrup,
+                                                             nb.south, tf);
+                    usvec4 jr;
+                    jr.x = nb.south ? joint_row(A[l].s, A[l].c, B[l].s, B[l].c, true) : (unsigned short)kJointNoRow;
+                    jr.y = joint_row(A[l].c, A[l].e, B[l].c, B[l].e, nb.has_e);
+                    jr.z = joint_row(A[l].c, A[l].n, B[l].c, B[l].n, nb.has_n);
+                    jr.w = joint_row(A[l].w, A[l].c, B[l].w, B[l].c, nb.has_w);
+                    const long zi = z + l - z0;
+                    __builtin_nontemporal_store(dvec2{r.wa.x * d.s, r.wa.y * d.e}, terms + (2 * zi) * n + k);
+                    __builtin_nontemporal_store(dvec2{r.wb.x * d.n, r.wb.y * d.w}, terms + (2 * zi + 1) * n + k);
+                    __builtin_nontemporal_store(jr, rows + zi * n + k);
+                }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < nwords; q += kBlock) flags[(long)blockIdx.x * nwords + q] = bits[q];
+}
+
+// Stage 2 for the window [r0, r0 + nwin) of joint rows, window number `win`.  A lane reads its own table entries, z ascending:
+// the rows of kJointLevels levels first, then the terms of the levels that have a row in the window, all in flight before
+// the first add.  LDS: nwin x kBlock accumulators, k_class_segscan's layout.  skip: a block whose flag is clear adds nothing,
+// so it does not read the table; its run sums are the +0.0 that the scan of untouched accumulators gives either way.
+__global__ __launch_bounds__(kBlock) void k_joint_bin(const int *__restrict__ seg, long n, int nlev,
+                                                      const dvec2 *__restrict__ terms, const usvec4 *__restrict__ rows,
+                                                      const unsigned *__restrict__ flags, int nwords, int win, int skip, int r0,
+                                                      int nwin, double *__restrict__ runsum)
+{
+    extern __shared__ double joint_acc[];
+    double *acc = joint_acc + threadIdx.x;   // acc[q * kBlock]: this lane's row r0 + q; no lane touches another's
+    for (int q = 0; q < nwin; ++q) acc[q * kBlock] = 0.0;
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    const bool live = !skip || ((flags[(long)blockIdx.x * nwords + (win >> 5)] >> (win & 31)) & 1u);
+    int key = -1;
+    if (k < n) {
+        key = load_key(seg, k);
+        if (live) {
+            auto in_window = [&](unsigned short row) { return (unsigned)row - (unsigned)r0 < (unsigned)nwin; };
+            auto add = [&](unsigned short row, double x) {
+                if (in_window(row)) acc[((unsigned)row - (unsigned)r0) * kBlock] += x;
+            };
+            for (int z = 0; z < nlev; z += kJointLevels) {
+                usvec4 jr[kJointLevels];
+                dvec2 se[kJointLevels], nw[kJointLevels];
+                bool hit[kJointLevels];
+#pragma unroll
+                for (int l = 0; l < kJointLevels; ++l)
+                    if (z + l < nlev) jr[l] = __builtin_nontemporal_load(rows + (long)(z + l) * n + k);
+#pragma unroll
+                for (int l = 0; l < kJointLevels; ++l) {
+                    hit[l] = z + l < nlev && (in_window(jr[l].x) || in_window(jr[l].y) || in_window(jr[l].z) || in_window(jr[l].w));
+                    if (hit[l]) {
+                        se[l] = __builtin_nontemporal_load(terms + (2l * (z + l)) * n + k);
+                        nw[l] = __builtin_nontemporal_load(terms + (2l * (z + l) + 1) * n + k);
+                    }
+                }
+#pragma unroll
+                for (int l = 0; l < kJointLevels; ++l)
+                    if (hit[l]) {
+                        add(jr[l].x, se[l].x);
+                        add(jr[l].y, se[l].y);
+                        add(jr[l].z, nw[l].x);
+                        add(jr[l].w, nw[l].y);
+                    }
+            }
+        }
+    }
+    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
+#pragma unroll
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
+        if (seg_scan_take(key, lane, o)) take |= 1u << b;
+    const bool store = seg_run_end(key, lane, k, n);
+    for (int q = 0; q < nwin; ++q) {
+        double val[1] = {k < n ? acc[q * kBlock] : 0.0};
+#pragma unroll
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
+        if (store) runsum[(long)q * n + k] = val[0];
+    }
+}
+
+template <typename T, bool CARRY>
+static int launch_joint_t(const JointArgs &a, hipStream_t s)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
+    const int nrows = (a.na + 2) * (a.nb + 2), nlev = in.z1 - in.z0;
+    const int nwords = joint_flag_words(nrows, a.window);
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    int topa = 1, topb = 1;
+    while (2 * topa <= a.na) topa *= 2;
+    while (2 * topb <= a.nb) topb *= 2;
+    dvec2 *terms = reinterpret_cast<dvec2 *>(a.table);
+    usvec4 *rows = reinterpret_cast<usvec4 *>(a.table + sizeof(dvec2) * 2 * (size_t)ws.nrec * nlev);
+    if (ws.nrec > 0) {
+        const size_t lds = sizeof(double) * (size_t)(a.na + a.nb) + sizeof(unsigned) * (size_t)nwords;
+        hipLaunchKernelGGL((k_joint_terms<T, CARRY>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(), ws.nrec,
+                           (const T *)in.u, (const T *)in.v, (const T *)a.sig, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness,
+                           in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2),
+                           TauIn<T>{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0}, (T)a.sfill, (T)a.sfill2,
+                           in.scale, in.sverdrup, a.edges, a.na, a.nb, topa, topb, a.window, nwords, terms, rows, a.flags);
+        NF_HIP(hipGetLastError());
+    }
+    for (int r0 = 0, win = 0; r0 < nrows; r0 += a.window, ++win) {
+        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
+        if (ws.nrec > 0)
+            hipLaunchKernelGGL(k_joint_bin, record_grid(ws), dim3(kBlock), sizeof(double) * (size_t)nwin * kBlock, s, ws.seg.get(),
+                               ws.nrec, nlev, terms, rows, a.flags, nwords, win, a.skip ? 1 : 0, r0, nwin, a.scratch);
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length, (unsigned)nwin, s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+int launch_joint_class_transport(const JointArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    const auto edges_ok = [](int n) { return n >= 2 && n <= kMaxClassEdges; };
+    NF_REQUIRE(edges_ok(a.na) && edges_ok(a.nb) && a.edges && (a.na + 2) * (a.nb + 2) <= kMaxJointRows, NF_ERR_ARG,
+               "joint class transport: bad class edges");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "joint class transport: bad window");
+    NF_TRY(check_raw_step("joint class transport", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.tau && a.sig && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+               "joint class transport: null argument");
+    if (a.tr.row_length() == 0) return NF_OK;
+    const size_t nrec = (size_t)a.tr.ws->nrec, blocks = (nrec + kBlock - 1) / kBlock;
+    NF_REQUIRE(nrec == 0 || (a.table && a.table_len >= kJointEntryBytes * nrec * (size_t)(in.z1 - in.z0)), NF_ERR_ARG,
+               "joint class transport: the term table is too small");
+    NF_REQUIRE(nrec == 0 || (a.flags && a.flags_len >= blocks * (size_t)joint_flag_words((a.na + 2) * (a.nb + 2), a.window)),
+               NF_ERR_ARG, "joint class transport: the flag array is too small");
+    if (in.dtype == NF_F64) return a.carry ? launch_joint_t<double, true>(a, s) : launch_joint_t<double, false>(a, s);
+    if (in.dtype == NF_F32) return a.carry ? launch_joint_t<float, true>(a, s) : launch_joint_t<float, false>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "joint class transport: dtype must be NF_F64 or NF_F32");
+}
+
 }  // namespace nf

@@ -935,6 +935,8 @@ class Field(object):
             mean.setClassTracer(sig, fill_value=none_if_nan(sfill))
         if getattr(self, '_class_edges', None) is not None:
             mean.setClassEdges(self._class_edges)
+        if getattr(self, '_joint_edges', None) is not None:
+            mean.setJointClassEdges(*self._joint_edges)
         if e3 is not None:
             dt = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
             with numpy.errstate(over='ignore'):
@@ -1040,6 +1042,66 @@ class Field(object):
         if R.ndim < 1 or R.shape[0] < 4:
             raise ValueError(f'classStreamfunction: need the nedges + 2 >= 4 rows of computeClassTransport, got shape {R.shape}')
         return numpy.cumsum(R[:R.shape[0] - 2], axis=0)
+
+    def setJointClassEdges(self, edgesA, edgesB):
+        """Class edges of the two axes of computeJointClassTransport: edgesA for the tracer of setTracer, edgesB for the tracer
+        of setClassTracer, each finite, strictly increasing, 2 <= n <= 1025, with (nA + 2) * (nB + 2) <= 16384 joint rows.
+        They are kept apart from setClassEdges: the 1-D class calls do not see them.  (None, None) clears them."""
+        if edgesA is None and edgesB is None:
+            check(lib.nf_field_set_joint_class_edges(ctypes.byref(self._h), None, 0, None, 0))
+            self._joint_edges = None
+            return
+        if edgesA is None or edgesB is None:
+            raise RuntimeError('ERROR: setJointClassEdges needs both edge sets (or None for both)')
+        ea = numpy.array(edgesA, dtype=numpy.float64).reshape(-1)
+        eb = numpy.array(edgesB, dtype=numpy.float64).reshape(-1)
+        check(lib.nf_field_set_joint_class_edges(ctypes.byref(self._h), _lib.dptr(ea), int(ea.size), _lib.dptr(eb), int(eb.size)))
+        self._joint_edges = (ea, eb)
+
+    def computeJointClassTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Transport of time step tIndex in joint classes of two tracers (setTracer: axis A, setClassTracer: axis B,
+        setJointClassEdges first): totals (nA+2, nB+2, ntransect) and per-segment sums (nA+2, nB+2, nseg) -- the volumetric
+        T-S census of the sections.  Entry [ra, rb] holds the terms of the faces whose value of A lies in row ra of edgesA and
+        whose value of B lies in row rb of edgesB, rows as in computeClassTransport (the last one of an axis: faces without a
+        value of that tracer).  carry=False: the volume terms of computeClassTransport; carry=True: the transport of the
+        tracer A (reference subtracted), the terms of computeClassTracerTransport.  Summed over rb the rows are those of the
+        1-D call binned by A, summed over ra those binned by B (up to rounding).  Levels this rank does not own (slab_range)
+        contribute nothing.  Leaves everything else as it is.  `out`: optional contiguous float64 torch CUDA tensor
+        ((nA+2)*(nB+2), row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_joint_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setJointClassEdges first')
+        na, nb = edges[0].size + 2, edges[1].size + 2
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        carry = 1 if carry else 0
+        if out is not None:
+            out = self._rows_out(out, na * nb)
+            check(lib.nf_field_compute_joint_class_transport_async(ctypes.byref(self._h), tIndex, carry,
+                                                                   ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((na * nb, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_joint_class_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        tot, seg = self._split_rows(rows)
+        return tot.reshape((na, nb) + tot.shape[1:]), seg.reshape((na, nb) + seg.shape[1:])
+
+    @staticmethod
+    def jointClassStreamfunction(rows, axis=0):
+        """Streamfunction in the space of two tracers from the rows of computeJointClassTransport (totals or segments, the two
+        class axes first): the cumulative sum along class axis `axis` (0: A, 1: B) over its rows 0 .. n-1 -- the `>= last
+        edge` row and the no-value row of that axis are left out, as in classStreamfunction; the other axis is kept whole.
+        Host only."""
+        R = numpy.asarray(rows, dtype=numpy.float64)
+        if axis not in (0, 1):
+            raise ValueError(f'jointClassStreamfunction: axis must be 0 or 1, got {axis!r}')
+        if R.ndim < 2 or R.shape[0] < 4 or R.shape[1] < 4:
+            raise ValueError('jointClassStreamfunction: need the (nA + 2, nB + 2, ...) rows of computeJointClassTransport, '
+                             f'got shape {R.shape}')
+        keep = [slice(None)] * R.ndim
+        keep[axis] = slice(0, R.shape[axis] - 2)
+        return numpy.cumsum(R[tuple(keep)], axis=axis)
 
     def depthBandFlux(self, profile, ztop, zbot):
         """Flux between the depths ztop < zbot (the units of deptht_bounds) from a profile of computeFluxProfile or

@@ -111,6 +111,19 @@ def carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracer
     return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
 
 
+def jointClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracer2, edges2, tracerFile='', tracer2File='',
+                     sverdrup=False):
+    """(nt, nA+2, nB+2, ntransect) water flow in joint classes of the variable `tracer` of tracerFile (edges) and the variable
+    `tracer2` of tracer2File (edges2; default for both files: the T file), one Field.computeJointClassTransport per time
+    step, and the Field."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    fld.setTracer((tracerFile or tFile, tracer))
+    fld.setClassTracer((tracer2File or tFile, tracer2))
+    fld.setJointClassEdges(edges, edges2)
+    totals = numpy.array([fld.computeJointClassTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, len(edges) + 2, len(edges2) + 2, len(lonLatZPoints)), fld
+
+
 def levelSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None):
     """(nt, nz, ntransect) water flow of every level (Field.computeFluxProfile) or, with `tracer`, the transport of that
     variable of tracerFile (default: the T file) of every level (Field.computeTracerProfile), and the Field."""
@@ -203,6 +216,32 @@ def checkClassArgs(classes='', tracer='', tracerRef=0.0, tracerScale=1.0, zrange
     parseClasses(classes)
 
 
+def checkJointClassArgs(classes2='', tracer2='', tracer2File='', tracer='', classes='', carry='', levels=False, zrange='',
+                        show=False, eddy=False, decompose=False):
+    """the --tracer2 / --classes2 options of the command line (the water flow in joint classes of two tracers): refused
+    combinations raise RuntimeError"""
+    if not classes2:
+        if tracer2 or tracer2File:
+            raise RuntimeError('ERROR: --tracer2 / --tracer2-file need --classes2 F0,...,FM (the class edges of the second '
+                               'tracer)')
+        return
+    if not (tracer2 and tracer and classes):
+        raise RuntimeError('ERROR: --classes2 needs --tracer2 NAME together with --tracer NAME and --classes E0,...,EN (the two '
+                           'class fields and their edges)')
+    for on, opt in ((carry, '--carry'), (levels, '--levels'), (zrange, '--zrange'), (show, '--show'), (eddy, '--eddy'),
+                    (decompose, '--decompose')):
+        if on:
+            raise RuntimeError(f'ERROR: --classes2 and {opt} cannot be combined: --classes2 writes the water flow in joint '
+                               f'classes of --tracer and --tracer2 as CSV only')
+    try:
+        edges2 = parseClasses(classes2)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace('--classes', '--classes2'))
+    n = (len(parseClasses(classes)) + 2) * (len(edges2) + 2)
+    if n > 16384:
+        raise RuntimeError(f'ERROR: --classes and --classes2 give {n} joint classes; at most 16384 are supported')
+
+
 def checkCarryArgs(carry='', carryFile='', carryRef=0.0, carryScale=1.0, classes='', tracer='', levels=False):
     """the --carry options of the command line (the transport of a second tracer by class): refused combinations raise
     RuntimeError"""
@@ -288,7 +327,8 @@ def parseZRange(zrange):
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
-         eddy=False):
+         eddy=False, tracer2='', tracer2File='', classes2=''):
+    checkJointClassArgs(classes2, tracer2, tracer2File, tracer, classes, carry, levels, zrange, show, eddy, decompose)
     checkEddyArgs(eddy, tracer, classes, levels, zrange, show, decompose)
     checkDecomposeArgs(decompose, tracer, classes, levels, zrange, show)
     checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, carry, levels, tracer)
@@ -331,6 +371,21 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         lines += [f'{timeVals[t]},{fld.bounds_depth[z, 0]:.15g},{fld.bounds_depth[z, 1]:.15g},' +
                   ','.join(f'{x:.15g}' for x in totals[t, z]) for t in range(fld.nt) for z in range(fld.nz)]
         _emit(f'# {what} per level [{unit}]\n' + '\n'.join(lines) + '\n', output)
+        return totals
+    if classes2:
+        edges, edges2 = parseClasses(classes), parseClasses(classes2)
+        totals, fld = jointClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracer2, edges2, tracerFile,
+                                       tracer2File, sverdrup)
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+
+        def bounds_of(e):
+            return [(-numpy.inf, e[0])] + list(zip(e[:-1], e[1:])) + [(e[-1], numpy.inf), (numpy.nan, numpy.nan)]
+
+        lines = ['time,lower,upper,lower2,upper2,' + ','.join(names)]
+        lines += [f'{timeVals[t]},{lo:.15g},{hi:.15g},{lo2:.15g},{hi2:.15g},' + ','.join(f'{x:.15g}' for x in totals[t, ka, kb])
+                  for t in range(fld.nt) for ka, (lo, hi) in enumerate(bounds_of(edges))
+                  for kb, (lo2, hi2) in enumerate(bounds_of(edges2))]
+        _emit(f'# water flow by {tracer} class and {tracer2} class [{unit}]\n' + '\n'.join(lines) + '\n', output)
         return totals
     if classes:
         edges = parseClasses(classes)
@@ -409,6 +464,12 @@ if __name__ == '__main__':
     ap.add_argument('--classes', default='', metavar='E0,E1,...,EN',
                     help='water flow binned by the class of --tracer NAME (e.g. sigma0): one CSV line per time step and '
                          'class [-inf,E0), [E0,E1), ..., [EN,inf), and a last one (nan,nan) for faces without a value')
+    ap.add_argument('--tracer2', default='', metavar='NAME',
+                    help='with --classes2: the second class field (e.g. so beside --tracer thetao); NAME is read from the T file')
+    ap.add_argument('--tracer2-file', dest='tracer2File', default='', metavar='FILE', help='read --tracer2 from FILE instead')
+    ap.add_argument('--classes2', default='', metavar='F0,F1,...,FM',
+                    help='with --tracer NAME --classes E0,...,EN and --tracer2 NAME: the water flow in joint classes of the two '
+                         'tracers (a T-S census): one CSV line per time step and pair of classes')
     ap.add_argument('--carry', default='', metavar='NAME',
                     help='with --classes: the transport of tracer NAME (e.g. heat: thetao) by class of --tracer, in place of '
                          'the water flow; NAME is read from the T file')

@@ -1,0 +1,596 @@
+"""Transport in joint classes of two tracers (Field.setJointClassEdges / computeJointClassTransport,
+nf_field_compute_joint_class_transport*): every per-level term of the class forms goes to the joint row of its face's classes
+of A (the tracer) and of B (the class tracer).  Anchored bit for bit to the 1-D class rows where one axis has a single class,
+checked against the long-double restatement of tests/joint_class_reference.py (markers differing per array, values on
+edges, +-inf, wrap on and off), for its marginals and its sum, for the same bits under every window, with the block skip on
+and off, from host and HBM inputs; sharding, unchanged state, the cell-thickness refusal, timeMean, the re-use of one handle
+through more records, more levels, new edges and another dtype (the term table's re-size path), and fluxplot --classes2.
+
+Grids 72 x 36 and 73 x 37, 7 levels, 3 steps, three transects (one across the periodic seam): 265 to 325 records, two blocks
+of 256.  Edge sets 3 x 5, 2 x 2 and 33 x 9: 35, 16 and 385 joint rows, none a multiple of the window of 32 (385: 13 windows)."""
+import contextlib
+import ctypes
+import io
+
+import numpy
+import pytest
+
+from conftest import transect_xyz
+from joint_class_reference import JointClassReference
+from resolved_reference import array_values
+
+pytestmark = pytest.mark.gpu
+
+PSI_ZT = "(1+10*z)*(t+1)*(cos(2*pi*y/360) + sin(2*pi*x/360))"
+T_TRI = "(-100,-80),(100,-80),(0,80),(-100,-80)"
+T_OPEN = "(-100,-80),(100,-80),(0,80)"
+T_SEAM = "(150,-30),(179.5,-20),(179.9,10),(175,40)"     # crosses the periodic seam: east faces of the last column
+GRIDS = [(72, 36), (73, 37)]
+NZ, NT = 7, 3
+FILL, MISSING = 1.e20, -999.                 # markers of uo / vo
+AFILL, AMISSING = -32768., 12345.            # markers of A
+BFILL, BMISSING = 9999., -7777.              # markers of B
+REF = 3.25
+BAR = 1e-12
+WIDE = numpy.array([-1e300, 1e300])          # one class for every finite value: row 1
+EDGE_SETS = {'3x5': (numpy.array([8., 15., 22.]), numpy.array([33., 34., 35., 36., 37.])),
+             '2x2': (numpy.array([10., 20.]), numpy.array([34., 36.])),
+             '33x9': (numpy.linspace(2., 28., 33), numpy.linspace(32.5, 37.5, 9))}
+
+
+def _quiet(fn, *a, **kw):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return fn(*a, **kw)
+
+
+_CASES = {}
+
+
+def _case(real, grid, fill=True):
+    """host bounds, deptht_bounds, u, v (nt, nz, ny, nx) of the PSI_ZT case on this grid; with `fill`, land blocks marked by
+    _FillValue, NaN and a second missing value"""
+    key = (real, grid, fill)
+    if key not in _CASES:
+        from nemoflux_amd.datagen import DataGen
+        nx, ny = grid
+        dg = DataGen(real=real)
+        dg.setSizes(nx, ny, NZ, NT)
+        dg.setBoundingBox(-180., 180., -90., 90., 0., 1.)
+        dg.build()
+        dg.applyStreamFunction(PSI_ZT)
+        dg.computeUVFromPotential()
+        u, v = dg.u.cpu().numpy().copy(), dg.v.cpu().numpy().copy()
+        v[:, :, -1, :] = 0                     # datagen's pole row is 1e13-sized garbage
+        if fill:
+            dt = u.dtype.type
+            u[:, 3:, 4:9, 10:20] = dt(FILL)
+            v[:, 3:, 4:9, 10:20] = numpy.nan
+            u[:, :2, 20:24, 30:40] = dt(MISSING)
+            v[:, 5:, 20:24, 30:40] = dt(MISSING)
+        _CASES[key] = (dg.bounds_lon.cpu().numpy(), dg.bounds_lat.cpu().numpy(), dg.deptht_bounds, u, v)
+    return _CASES[key]
+
+
+def tracers(real, grid, plain=False, inf_a=False):
+    """A = a function of latitude and level (and step), B = a function of longitude and level (and step), so that a transect
+    walks through the (A, B) plane and the levels move its path: the joint bins fill.  A spans more than the edges 2 .. 28 of
+    EDGE_SETS, B more than 32.5 .. 37.5.  Unless `plain`: pairs of rows / columns that sit exactly on an edge, +-inf beside
+    -+inf in B (in A too with inf_a: the volume form only, carried it makes the terms infinite), and blocks where A, B or
+    both are missing, each array with its own two markers and NaN."""
+    nx, ny = grid
+    dt = numpy.dtype(real).type
+    lat = (numpy.arange(ny) + 0.5) * (180. / ny) - 90.
+    lon = (numpy.arange(nx) + 0.5) * (360. / nx) - 180.
+    z = numpy.arange(NZ)[None, :, None, None]
+    t = numpy.arange(NT)[:, None, None, None]
+    A = 15. + 14.5 * numpy.sin(numpy.radians(lat)[None, None, :, None] * 1.7 + 0.9 * z + 0.4 * t) + 0. * lon[None, None, None, :]
+    B = 35. + 3. * numpy.cos(numpy.radians(lon)[None, None, None, :] * 2. + 0.75 * z - 0.5 * t) + 0. * lat[None, None, :, None]
+    A, B = A.astype(dt), B.astype(dt)
+    if plain:
+        return A, B
+    eA, eB = EDGE_SETS['33x9']
+    A[:, :, 5:7, :] = dt(eA[3])                # the faces inside these two rows lie exactly on an edge of A
+    A[:, :, 24:26, :] = dt(eA[20])
+    B[:, :, :, 30:32] = dt(eB[2])              # ... these two columns on an edge of B
+    B[:, :, :, 50:52] = dt(eB[6])
+    B[:, :, 8:10, 44] = numpy.array([numpy.inf, -numpy.inf], dt)[None, None, :]     # a north face whose mean is NaN
+    B[:, :, 27, 21:23] = numpy.array([-numpy.inf, numpy.inf], dt)[None, None, :]    # an east face
+    if inf_a:
+        A[:, :, 12:14, 50] = numpy.array([numpy.inf, -numpy.inf], dt)[None, None, :]
+        A[:, :, 22, 6:8] = numpy.array([-numpy.inf, numpy.inf], dt)[None, None, :]
+    A[:, :, 10:16, 20:30] = dt(AFILL)          # A missing, B present
+    A[:, 2:, 30:33, 0:6] = dt(AMISSING)
+    A[:, :3, 28, 60:] = numpy.nan
+    B[:, :, 20:26, 40:50] = dt(BMISSING)       # B missing, A present
+    B[:, 4:, 2:6, 12:18] = dt(BFILL)
+    B[:, :, 14:17, -2:] = numpy.nan            # at the seam
+    A[:, :, 16:20, 23:29] = dt(AMISSING)       # neither
+    B[:, :, 16:20, 23:29] = numpy.nan
+    A[:, :, 3, 40:44] = dt(BFILL)              # the other array's markers are values
+    B[:, :, 30, 10:14] = dt(AMISSING)
+    return A, B
+
+
+def _on(a, resident):
+    import torch
+    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
+
+
+LINES = (T_OPEN, T_TRI, T_SEAM)
+
+
+def _field(real, grid, resident=True, fill=True, sverdrup=False, **kw):
+    from nemoflux_amd.field import Field
+    blon, blat, db, u, v = _case(real, grid, fill)
+    kw.update(sverdrup=sverdrup, readback=False)
+    if fill:
+        kw.update(fill_value=FILL, missing_value=MISSING)
+    return _quiet(Field.fromArrays, blon, blat, db, _on(u, resident), _on(v, resident), [transect_xyz(s) for s in LINES], **kw)
+
+
+def _set(f, A, B, resident=True, markers=True, reference=REF, wrap=True):
+    mk = (lambda a, b: dict(fill_value=a, missing_value=b)) if markers else (lambda a, b: {})
+    f.setTracer(_on(A, resident), reference=reference, wrapX=wrap, **mk(AFILL, AMISSING))
+    f.setClassTracer(_on(B, resident), **mk(BFILL, BMISSING))
+
+
+def _rows(pair):
+    """[segments | transects] rows of a (totals, segments) pair, the class axes kept"""
+    tot, seg = pair
+    return numpy.concatenate([seg, tot], axis=-1)
+
+
+def _joint(f, t, carry=False, out=None):
+    return _rows(f.computeJointClassTransport(t, carry=carry, out=out))
+
+
+def _one_d(f, t, carry):
+    return _rows(f.computeClassTracerTransport(t) if carry else f.computeClassTransport(t))
+
+
+def _same_bits(a, b):
+    a, b = numpy.ascontiguousarray(a, numpy.float64), numpy.ascontiguousarray(b, numpy.float64)
+    return a.shape == b.shape and numpy.array_equal(a.view(numpy.uint64), b.view(numpy.uint64))
+
+
+def _plus_zero(a):
+    return not numpy.ascontiguousarray(a, numpy.float64).view(numpy.uint64).any()
+
+
+@contextlib.contextmanager
+def _knob(name, value, default):
+    from nemoflux_amd._lib import lib, check
+    check(lib.nf_tuning_set(name, int(value)))
+    try:
+        yield
+    finally:
+        check(lib.nf_tuning_set(name, default))
+
+
+def _window(w):
+    return _knob(b'joint_window', w, 32)
+
+
+def _skip(on):
+    return _knob(b'joint_skip', on, 1)
+
+
+# ---- 1. bit-for-bit anchors -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+@pytest.mark.parametrize('fill', [True, False], ids=['markers', 'nomarkers'])
+@pytest.mark.parametrize('sverdrup', [False, True], ids=['m2', 'sv'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_one_class_on_an_axis_gives_the_one_dimensional_rows_bit_for_bit(real, sverdrup, fill, resident):
+    """A and B present everywhere.  eB = (-1e300, 1e300): joint[:, 1] is the 1-D form binned by A, every other row +0.0;
+    eA = (-1e300, 1e300): joint[1, :] is the 1-D form binned by B; volume and carried"""
+    grid = GRIDS[sverdrup]
+    A, B = tracers(real, grid, plain=True)
+    eA, eB = EDGE_SETS['33x9'] if fill else EDGE_SETS['3x5']
+    f = _field(real, grid, resident, fill, sverdrup)
+    for t in (2, 0):
+        for carry in (False, True):
+            _set(f, A, B, resident, markers=False)
+            f.setJointClassEdges(eA, WIDE)
+            ja = _joint(f, t, carry)
+            f.setJointClassEdges(WIDE, eB)
+            jb = _joint(f, t, carry)
+            assert ja.shape == (eA.size + 2, 4, f._rowlen) and jb.shape == (4, eB.size + 2, f._rowlen)
+            f.setClassEdges(eB)
+            by_b = _one_d(f, t, carry)               # binned by the class tracer B; carried: A
+            f.setClassTracer(None)
+            f.setClassEdges(eA)
+            by_a = _one_d(f, t, carry)               # binned by A
+            assert numpy.abs(by_a).max() > 0 and numpy.abs(by_b).max() > 0
+            assert (numpy.abs(by_a).max(axis=1) > 0).sum() >= eA.size // 2
+            assert _same_bits(ja[:, 1], by_a), (t, carry)
+            assert _same_bits(jb[1, :], by_b), (t, carry)
+            assert _plus_zero(ja[:, [0, 2, 3]]) and _plus_zero(jb[[0, 2, 3], :]), (t, carry)
+
+
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_the_same_tracer_on_both_axes_fills_the_diagonal_only(real):
+    grid = GRIDS[1]
+    A, _ = tracers(real, grid, plain=True)
+    eA = EDGE_SETS['33x9'][0]
+    f = _field(real, grid)
+    _set(f, A, A, markers=False)
+    f.setJointClassEdges(eA, eA)            # 35 x 35 = 1225 rows
+    for carry in (False, True):
+        j = _joint(f, 1, carry)
+        f.setClassTracer(None)
+        f.setClassEdges(eA)
+        one = _one_d(f, 1, carry)
+        _set(f, A, A, markers=False)
+        k = numpy.arange(eA.size + 2)
+        assert _same_bits(j[k, k], one), carry
+        off = j.copy()
+        off[k, k] = 0.0
+        assert _plus_zero(off), carry
+        assert numpy.abs(one).max() > 0
+
+
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_a_tracer_of_reference_plus_one_carries_the_volume(real):
+    grid = GRIDS[0]
+    _, B = tracers(real, grid, plain=True)
+    A = numpy.full(B.shape, REF + 1., B.dtype)
+    f = _field(real, grid, sverdrup=True)
+    _set(f, A, B, markers=False)
+    f.setJointClassEdges(*EDGE_SETS['3x5'])
+    vol = _joint(f, 2, False)
+    assert numpy.abs(vol).max() > 0
+    assert _same_bits(_joint(f, 2, True), vol)
+
+
+# ---- 2, 3. the restatement, the marginals, the sum ------------------------------------------------------------------------
+def reference_for(f, grid, wrap, sverdrup, markers=True):
+    ce, w, sg = f.getWeights()
+    return JointClassReference(ce, w, sg, f.arcLengths, f.thickness, f._tr_off, grid[0], grid[1], uv_markers=(FILL, MISSING),
+                               tracer_markers=(AFILL, AMISSING) if markers else (),
+                               class_markers=(BFILL, BMISSING) if markers else (), reference=REF, wrap=wrap, sverdrup=sverdrup)
+
+
+def occupancy(mag, na, nb):
+    """(every A row carries terms, every B row does, the share of the joint rows that do) from the restatement's mag"""
+    m = mag.reshape(na + 2, nb + 2, -1).max(axis=2) > 0
+    return m.any(axis=1).all(), m.any(axis=0).all(), m.mean()
+
+
+WORST = {}
+
+
+@pytest.mark.parametrize('edges', sorted(EDGE_SETS))
+@pytest.mark.parametrize('wrap', [True, False], ids=['wrap', 'nowrap'])
+@pytest.mark.parametrize('carry', [False, True], ids=['volume', 'carried'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_against_the_restatement_with_marginals_and_sum(real, carry, wrap, edges):
+    """every value within 1e-12 x sum |terms| of the long-double restatement, no row, segment or transect left out; the
+    marginals over each axis are the 1-D rows and the sum of all rows is the computeFlux / computeTracerFlux row, to the
+    same bar.  The restatement's own mag says that the inputs fill the rows: every A row, every B row, half the joint rows."""
+    grid = GRIDS[wrap]
+    sverdrup = edges == '3x5'
+    A, B = tracers(real, grid, inf_a=not carry)
+    a = dict(zip(('uo', 'vo'), _case(real, grid)[3:]), tracer=A, **{'class': B})
+    eA, eB = EDGE_SETS[edges]
+    f = _field(real, grid, sverdrup=sverdrup)
+    _set(f, A, B, wrap=wrap)
+    f.setJointClassEdges(eA, eB)
+    ref = reference_for(f, grid, wrap, sverdrup)
+    worst = 0.0
+    for t in range(NT):
+        both = ref.joint(array_values(a, t), eA, eB)
+        want, mag = both['tracer' if carry else 'volume']
+        # the inputs fill the rows: judged on the volume terms -- carried, a face without a value of A has the factor 0, so
+        # the no-value row of A is empty by definition; every other row of A must carry tracer terms too
+        a_rows, b_rows, share = occupancy(both['volume'][1], eA.size, eB.size)
+        assert a_rows and b_rows and share >= 0.5, (t, a_rows, b_rows, share)
+        if carry:
+            m = mag.reshape(eA.size + 2, eB.size + 2, -1).max(axis=2) > 0
+            assert m[:-1].any(axis=1).all() and m[:-1].any(axis=0).all() and m.mean() >= 0.5 and not m[-1].any(), t
+        got = _joint(f, t, carry)
+        assert got.shape == (eA.size + 2, eB.size + 2, f._rowlen)
+        got2 = got.reshape(want.shape)
+        assert numpy.isfinite(got2).all()
+        err = numpy.abs(got2 - want)
+        worst = max(worst, (err / numpy.maximum(mag, 1e-300)).max())
+        assert numpy.all(err <= BAR * mag), (t, (err / numpy.maximum(mag, 1e-300)).max())
+        assert _plus_zero(got2[mag == 0]), 'exact zeros where nothing falls'
+        # marginals: over rb the 1-D rows binned by A, over ra those binned by B
+        mag3 = mag.reshape(got.shape)
+        f.setClassEdges(eB)
+        by_b = _one_d(f, t, carry)
+        f.setClassTracer(None)
+        f.setClassEdges(eA)
+        by_a = _one_d(f, t, carry)
+        f.setClassTracer(_on(B, True), fill_value=BFILL, missing_value=BMISSING)
+        assert numpy.all(numpy.abs(got.sum(axis=1) - by_a) <= BAR * mag3.sum(axis=1)), t
+        assert numpy.all(numpy.abs(got.sum(axis=0) - by_b) <= BAR * mag3.sum(axis=0)), t
+        full = _rows(f.computeTracerFlux(t)) if carry else _volume_row(f, t)
+        assert numpy.all(numpy.abs(got.sum(axis=(0, 1)) - full) <= BAR * mag3.sum(axis=(0, 1))), t
+    WORST[real, carry, wrap, edges] = worst
+    print(f'joint classes {real} carry={carry} wrap={wrap} {edges}: worst |err| / sum|terms| = {worst:.3g}')
+
+
+def _volume_row(f, t):
+    f.computeFlux(t)
+    return numpy.array(f._row[:f._rowlen])
+
+
+# ---- 4. the same bits under every variation -------------------------------------------------------------------------------
+@pytest.mark.parametrize('carry', [False, True], ids=['volume', 'carried'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_same_bits_for_every_window_skip_home_and_form(real, carry):
+    import torch
+    grid = GRIDS[1]
+    A, B = tracers(real, grid)
+    eA, eB = EDGE_SETS['33x9']
+    got = {}
+    for resident in (True, False):
+        f = _field(real, grid, resident)
+        _set(f, A, B, resident)
+        f.setJointClassEdges(eA, eB)
+        want = _joint(f, 1, carry)
+        assert _same_bits(_joint(f, 1, carry), want)             # a repeated call
+        got[resident] = want
+        for w in (1, 5, 32) if resident else (5,):
+            for skip in (0, 1):
+                with _window(w), _skip(skip):
+                    assert _same_bits(_joint(f, 1, carry), want), (resident, w, skip)
+        out = torch.full((want.shape[0] * want.shape[1], f._rowlen), numpy.nan, dtype=torch.float64, device='cuda')
+        assert _same_bits(_joint(f, 1, carry, out=out), want)
+        assert _same_bits(out.cpu().numpy().reshape(want.shape), want)
+    assert _same_bits(got[True], got[False])
+    assert (numpy.abs(want).max(axis=2) > 0).mean() > 0.4
+    for shape, dtype in (((385, f._rowlen), torch.float32), ((384, f._rowlen), torch.float64), ((35, 11, f._rowlen), torch.float64)):
+        with pytest.raises(RuntimeError, match='out must be'):
+            f.computeJointClassTransport(1, out=torch.zeros(shape, dtype=dtype, device='cuda'))
+
+
+# ---- 5. sharding ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('carry', [False, True], ids=['volume', 'carried'])
+def test_three_slab_ranges_add_up(carry):
+    import torch
+    from nemoflux_amd.dist import slab_range
+    real, grid, world = 'float64', GRIDS[0], 3
+    A, B = tracers(real, grid)
+    eA, eB = EDGE_SETS['3x5']
+    a = dict(zip(('uo', 'vo'), _case(real, grid)[3:]), tracer=A, **{'class': B})
+    full = _field(real, grid)
+    _set(full, A, B)
+    full.setJointClassEdges(eA, eB)
+    ref = reference_for(full, grid, True, False)
+    want = numpy.array([_joint(full, t, carry) for t in range(NT)])
+    acc = numpy.zeros_like(want)
+    empty = 0
+    for r in range(world + 1):
+        # the last one owns nothing at all: a rank without levels
+        sr = slab_range(NT, NZ, r, world) if r < world else (NT * NZ, NT * NZ)
+        part = _field(real, grid, slab_range=sr)
+        _set(part, A, B)
+        part.setJointClassEdges(eA, eB)
+        for t in range(NT):
+            out = torch.full((35, part._rowlen), numpy.nan, dtype=torch.float64, device='cuda')
+            rows = _joint(part, t, carry, out=out)
+            assert _same_bits(rows, _joint(part, t, carry))
+            if min(sr[1], (t + 1) * NZ) <= max(sr[0], t * NZ):
+                assert _plus_zero(rows), (r, t)
+                empty += 1
+            acc[t] += rows
+    assert empty >= NT + 2
+    for t in range(NT):
+        mag = ref.joint(array_values(a, t), eA, eB)['tracer' if carry else 'volume'][1].reshape(want[t].shape)
+        assert numpy.all(numpy.abs(acc[t] - want[t]) <= BAR * mag), t
+    assert numpy.abs(want).max() > 0
+
+
+# ---- 6. state --------------------------------------------------------------------------------------------------------------
+def _resident(f):
+    from nemoflux_amd import _lib
+    from nemoflux_amd._lib import lib, check
+    n = f.ny * f.nx
+    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
+    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
+    return iV, eU, eV, mx.value
+
+
+@pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
+def test_joint_calls_leave_everything_else_alone(resident):
+    """between joint calls the 1-D class rows (volume and carried), the volume row, the planes and running max of read_step
+    and the tracer row are those of a field that never saw a joint call, bit for bit"""
+    real, grid = 'float64', GRIDS[1]
+    A, B = tracers(real, grid)
+    a, b = _field(real, grid, resident), _field(real, grid, resident)
+    for f in (a, b):
+        _set(f, A, B, resident)
+        f.setClassEdges(EDGE_SETS['3x5'][1])
+    a.setJointClassEdges(*EDGE_SETS['33x9'])
+    j0 = _joint(a, 1)
+    for step in ('flux1', 'class0', 'carried2', 'tracer0', 'read', 'all', 'flux2', 'read', 'tracer2', 'class1'):
+        _joint(a, 2, carry=step in ('read', 'all'))
+        t = int(step[-1]) if step[-1].isdigit() else 0
+        if step == 'all':
+            assert all(_same_bits(x, y) for x, y in zip(a.computeAll(), b.computeAll()))
+        elif step == 'read':
+            for x, y in zip(_resident(a), _resident(b)):
+                assert _same_bits(x, y)
+        elif step.startswith('tracer'):
+            assert _same_bits(_rows(a.computeTracerFlux(t)), _rows(b.computeTracerFlux(t)))
+        elif step.startswith('class') or step.startswith('carried'):
+            assert _same_bits(_one_d(a, t, step.startswith('carried')), _one_d(b, t, step.startswith('carried')))
+        else:
+            assert a.computeFlux(t) == b.computeFlux(t)
+            _joint(a, 0, True)
+            assert _same_bits(numpy.array(a._row[:a._rowlen]), numpy.array(b._row[:b._rowlen]))
+    for x, y in zip(_resident(a), _resident(b)):
+        assert _same_bits(x, y)
+    assert _same_bits(_joint(a, 1), j0)
+
+
+def test_a_cell_thickness_is_refused_as_by_the_sibling_forms():
+    real, grid = 'float64', GRIDS[0]
+    A, B = tracers(real, grid)
+    f = _field(real, grid)
+    _set(f, A, B)
+    f.setClassEdges(EDGE_SETS['3x5'][0])
+    f.setJointClassEdges(*EDGE_SETS['3x5'])
+    want = [_joint(f, 0, carry) for carry in (False, True)]
+    e3 = numpy.full((NZ,) + grid[::-1], 0.1)
+    f.setCellThickness(_on(e3, True), _on(e3, True))
+    with pytest.raises(RuntimeError) as sibling:
+        f.computeClassTransport(0)
+    words = str(sibling.value)[str(sibling.value).index(': this form does not take per-cell thicknesses yet'):]
+    for carry in (False, True):
+        with pytest.raises(RuntimeError) as e:
+            f.computeJointClassTransport(0, carry=carry)
+        assert 'nf_field_compute_joint_class_transport' in str(e.value) and str(e.value).endswith(words), str(e.value)
+    f.setCellThickness(None, None)
+    for carry in (False, True):
+        assert _same_bits(_joint(f, 0, carry), want[carry])
+
+
+def test_the_time_mean_state_carries_the_joint_edges():
+    real, grid = 'float64', GRIDS[0]
+    A, B = tracers(real, grid)
+    f = _field(real, grid)
+    _set(f, A, B)
+    eA, eB = EDGE_SETS['3x5']
+    f.setJointClassEdges(eA, eB)
+    mean = _quiet(f.timeMean)
+    assert all(numpy.array_equal(x, y) for x, y in zip(mean._joint_edges, (eA, eB)))
+    got = _joint(mean, 0)
+    assert got.shape == (5, 7, f._rowlen) and numpy.abs(got).max() > 0
+    # ... and they are the edges in force: a fresh Field on the mean state with the same edges gives the same bits
+    mean.setJointClassEdges(eA, eB)
+    assert _same_bits(_joint(mean, 0), got)
+    mean.setJointClassEdges(eA[:2], eB)
+    assert _joint(mean, 0).shape == (4, 7, f._rowlen)
+    # without joint edges there is nothing to carry
+    g = _field(real, grid)
+    _set(g, A, B)
+    with pytest.raises(RuntimeError, match='setJointClassEdges first'):
+        _quiet(g.timeMean).computeJointClassTransport(0)
+
+
+# ---- 7. one handle through more records, more levels, new edges, another dtype ---------------------------------------------
+def test_handle_reuse_equals_a_fresh_handle():
+    """the term table, the block flags and the run sums are sized by the records, the owned levels and the rows: after each
+    change the re-used handle gives the bits of a fresh one"""
+    from test_gpu_reuse import TRANSECTS, Handle, grid_bounds, velocities
+    dp = ctypes.POINTER(ctypes.c_double)
+    ny, nx = 24, 40
+    rng = numpy.random.default_rng(31)
+
+    class State:
+        lines = [TRANSECTS[2]]
+        thick = numpy.linspace(0.5, 1.5, 3)
+        edges = (numpy.array([3., 5.]), numpy.array([4., 5., 6.]))
+        dtype = numpy.float64
+
+    def fields(nz, dtype):
+        u, v = velocities(rng, 2, nz, ny, nx, dtype, 1e20)
+        A = (5. + 2. * rng.standard_normal(u.shape)).astype(dtype)
+        B = (5. + 1. * rng.standard_normal(u.shape)).astype(dtype)
+        A[:, :, 3:6, 5:9] = numpy.nan
+        return u, v, A, B
+
+    def apply(h, s, what):
+        import torch
+        code = 1 if s.dtype == numpy.float32 else 0
+        if what in ('all', 'bounds'):
+            h.set_bounds(ny, nx, numpy.float64, True)
+        if what in ('all', 'thick'):
+            h.set_thickness(s.thick)
+        if what in ('all', 'thick', 'fields'):
+            u, v, A, B = s.arrays
+            h.set_uv(u, v, True, 1e20)
+            tA, tB = torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda()
+            torch.cuda.synchronize()
+            h.keep['tracers', len(h.keep)] = (tA, tB)
+            h.call('set_tracer', tA.data_ptr(), A.shape[0], code, 1, float('nan'))
+            h.call('set_class_tracer', tB.data_ptr(), B.shape[0], code, 1, float('nan'))
+        if what in ('all', 'lines'):
+            for line in (s.lines if what == 'all' else s.lines[-1:]):
+                h.add_transect(line)
+            h.call('build_weights', 128, 360.)
+        if what in ('all', 'edges'):
+            ea, eb = s.edges
+            h.call('set_joint_class_edges', ea.ctypes.data_as(dp), ea.size, eb.ctypes.data_as(dp), eb.size)
+
+    def rows(h, s):
+        n = (s.edges[0].size + 2) * (s.edges[1].size + 2)
+        out = []
+        for carry in (0, 1):
+            for t in (1, 0):
+                r = numpy.full((n, h.rowlen()), numpy.nan)
+                h.call('compute_joint_class_transport', t, carry, r.ctypes.data_as(dp))
+                out.append(r)
+        return numpy.array(out)
+
+    s = State()
+    s.arrays = fields(s.thick.size, s.dtype)
+    h = Handle()
+    apply(h, s, 'all')
+    first = rows(h, s)
+    assert numpy.abs(first).max() > 0
+    steps = [('lines', lambda: s.lines.append(TRANSECTS[3] + [(170., 60.), (-60., 75.), (-175., -70.)])),   # more records
+             ('thick', lambda: setattr(s, 'thick', numpy.linspace(0.25, 2., 7))),                              # more levels
+             ('edges', lambda: setattr(s, 'edges', (numpy.linspace(1., 9., 33), numpy.linspace(3., 7., 9)))),    # 385 rows
+             ('fields', lambda: setattr(s, 'dtype', numpy.float32))]                                             # dtype
+    for what, change in steps:
+        change()
+        if what in ('thick', 'fields'):
+            s.arrays = fields(s.thick.size, s.dtype)
+        apply(h, s, what)
+        got = rows(h, s)
+        fresh = Handle()
+        apply(fresh, s, 'all')
+        want = rows(fresh, s)
+        assert numpy.isfinite(got).all() and numpy.abs(got).max() > 0, what
+        assert _same_bits(got, want), what
+    assert h.rowlen() > 4 and got.shape[1] == 385
+
+
+# ---- 8. fluxplot ----------------------------------------------------------------------------------------------------------
+def test_fluxplot_classes2_is_the_library_table(tmp_path):
+    from nemoflux_amd import fluxplot
+    from nemoflux_amd.field import Field
+    real, grid = 'float32', GRIDS[0]
+    blon, blat, db, u, v = _case(real, grid)
+    A, B = tracers(real, grid)
+    paths = {k: str(tmp_path / f'{k}.npz') for k in 'TUVS'}
+    fv = lambda name, a, b: {f'_FillValue_{name}': numpy.array(a), f'_missing_value_{name}': numpy.array(b)}   # noqa: E731
+    numpy.savez(paths['T'], bounds_lon=blon, bounds_lat=blat, deptht_bounds=db, thetao=A, **fv('thetao', AFILL, AMISSING))
+    numpy.savez(paths['S'], so=B, **fv('so', BFILL, BMISSING))
+    numpy.savez(paths['U'], uo=u, **fv('uo', FILL, MISSING))
+    numpy.savez(paths['V'], vo=v, **fv('vo', FILL, MISSING))
+    eA, eB = EDGE_SETS['3x5']
+    lines = '[' + T_OPEN + '],[' + T_SEAM + ']'
+    out = str(tmp_path / 'joint.csv')
+    kw = dict(tFile=paths['T'], uFile=paths['U'], vFile=paths['V'])
+    totals = _quiet(fluxplot.main, lonLatPoints=lines, output=out, sverdrup=True, tracer='thetao', tracer2='so',
+                    tracer2File=paths['S'], classes=','.join(str(e) for e in eA), classes2=','.join(str(e) for e in eB), **kw)
+    with open(out) as fh:
+        text = fh.read().splitlines()
+    assert text[0] == '# water flow by thetao class and so class [Sv]'
+    assert text[1] == 'time,lower,upper,lower2,upper2,line0,line1'
+    body = [ln.split(',') for ln in text[2:]]
+    na, nb = eA.size + 2, eB.size + 2
+    ff = _quiet(Field, paths['T'], paths['U'], paths['V'], fluxplot.readTargets(lines)[0], True)
+    ff.setTracer((paths['T'], 'thetao'))
+    ff.setClassTracer((paths['S'], 'so'))
+    ff.setJointClassEdges(eA, eB)
+    assert len(body) == ff.nt * na * nb and totals.shape == (ff.nt, na, nb, 2)
+    bounds = lambda e: [(-numpy.inf, e[0])] + list(zip(e[:-1], e[1:])) + [(e[-1], numpy.inf)]   # noqa: E731
+    for t in range(ff.nt):
+        want = ff.computeJointClassTransport(t)[0]
+        assert _same_bits(totals[t], want)
+        for ka in range(na):
+            for kb in range(nb):
+                ln = body[(t * na + ka) * nb + kb]
+                for k, e, lo, hi in ((ka, eA, ln[1], ln[2]), (kb, eB, ln[3], ln[4])):
+                    if k < e.size + 1:
+                        assert (float(lo), float(hi)) == bounds(e)[k]
+                    else:
+                        assert numpy.isnan(float(lo)) and numpy.isnan(float(hi))
+                assert numpy.allclose([float(x) for x in ln[5:]], want[ka, kb], rtol=1e-14, atol=1e-300)
+    assert (numpy.abs(want).max(axis=2) > 0).sum() > 10
