@@ -355,6 +355,29 @@ int nf_field_compute_tracer_profile_async(nf_field **self, long tIndex, double *
  * step.  The calls change neither the resident planes, |.| arrays, running max, last row, tracer planes nor a captured pass. */
 int nf_field_compute_area_profile(nf_field **self, long tIndex, double *rows_host);       /* (2, nz, row_length): A, T */
 int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *rows_dev);  /* HBM, field's stream */
+/* Gross transports, level by level: how much goes through the section in the direction nf_field_compute counts positive and
+ * how much comes back -- the inflow and the outflow of a strait, a recirculation -- where every other row is their net.
+ * Records, slots, faces and the neighbour rule are those of nf_field_compute_profile.  For step t, level z and a record's slot
+ * with weight w:
+ *   water term    q = w * d,  d the slot's value of the profile: +fma(th, fixed(uo), 0) * arcE for the east and west slots,
+ *                 -fma(th, fixed(vo), 0) * arcN for the north and south slots, times 6.371 in Sverdrup mode, 0 for the south slot
+ *                 of row 0; th = thickness[z], or with a cell thickness set fixth(e3u) / fixth(e3v) at the slot's own face
+ *   carried term  c = q (carry = 0), or the slot's term of the tracer profile (carry = 1): the same with fixed(.) * tf, tf the
+ *                 face value of the tracer of nf_field_set_tracer minus its reference, 0 for a face without a value
+ *   P(z) = sum of c over the slots with q > 0,   N(z) = sum of c over the slots with q < 0;   q == 0: in neither.
+ * The carried form is split by the direction of the WATER, not by the sign of its own term: P is what the flow carries forward,
+ * N what it carries back.  P + N is the row of nf_field_compute_profile (carry = 0) or nf_field_compute_tracer_profile
+ * (carry = 1) up to rounding; with carry = 0, P >= 0 >= N and P - N is the sum of |terms|.  carry = 1 takes a cell thickness
+ * too (the tracer profile does not yet).  rows (2, nz, row_length): P then N, each row [segments | transects].  A lane adds its
+ * four slots south, east, north, west into +0.0 for P and for N alike (a slot that belongs to the other part as +0.0), then the
+ * fixed tree of the transect reduction follows: no atomics, bitwise reproducible, and an order that does not depend on the
+ * signs -- negating uo and vo gives P' == -N and N' == -P bit for bit, tau == ref + 1 gives the carry = 0 rows bit for bit.
+ * Levels this rank does not own are exact zeros.  carry other than 0 or 1: NF_ERR_ARG; carry = 1 before set_tracer:
+ * NF_ERR_STATE.  Host-resident uo / vo, tracer and time-varying cell thickness are staged per step.  The calls change neither
+ * the resident planes, |.| arrays, running max, last row, tracer planes nor a captured pass.  Mean tracer of the inflow:
+ * P(carry = 1) / P(carry = 0) + ref, where the tracer is present wherever the velocity is. */
+int nf_field_compute_gross_profile(nf_field **self, long tIndex, int carry, double *rows_host);       /* (2, nz, row_length): P, N */
+int nf_field_compute_gross_profile_async(nf_field **self, long tIndex, int carry, double *rows_dev);  /* HBM, field's stream */
 /* Class tracer: a second, optional tracer at T-points (potential density sigma) that gives the faces their class value
  * instead of the tracer of nf_field_set_tracer, which is then only carried (heat by density class).  Same (nt,nz,ny,nx) and
  * dtype as uo/vo (else NF_ERR_ARG, the message naming both; set_uv first: NF_ERR_STATE); host (staged per step into a buffer

@@ -19,6 +19,7 @@ static int g_batch_steps = 1;
 //                          stream once for both steps; 0 = one reduction per step (default 1)
 //   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
 //   "area_chunk"           levels per launch of the area profile: 2 or 4 (float64), 4 or 8 (float32); 0 = the measured default
+//   "gross_chunk"          levels per launch of the gross profile: 2, 4 or 8 (float64), 4 or 8 (float32); 0 = the measured default
 //   "joint_window"         rows of the joint class transport per pass over its term table, 1 .. 32 (default 32)
 //   "joint_skip"           1 = a block of the joint binning whose records have no term in the window does not read the table
 //                          (default 1: docs/EXPERIMENTS.md); the rows are the same bits either way
@@ -77,6 +78,7 @@ int field_tuning_set(const char *name, int value)
         return NF_OK;
     }
     if (!strcmp(name, "area_chunk")) return area_chunk_set(value);
+    if (!strcmp(name, "gross_chunk")) return gross_chunk_set(value);
     return -1;
 }
 }  // namespace nf
@@ -163,6 +165,8 @@ struct nf_field {
     DevArray<double> tprof_scratch;
     // area profile (nf_field_compute_area_profile): the run sums of one chunk, two values per level (ws.nrec * 2 * area_chunk)
     DevArray<double> area_scratch;
+    // gross profile (nf_field_compute_gross_profile): the run sums of one chunk, two values per level (ws.nrec * 2 * gross_chunk)
+    DevArray<double> gross_scratch;
     // class transport (nf_field_set_class_edges): the edges on the host, uploaded by the next compute after a change; the run
     // sums of one window of rows (ws.nrec * window, allocated on first use, dropped with the weights)
     std::vector<double> class_edges;
@@ -616,6 +620,32 @@ static int field_area_async(nf_field *f, long t, double *rows_dev)
     a.rows = rows_dev;
     a.nz = f->nz;
     return launch_area_profile(a, f->stream);
+}
+
+// Gross transports of step t on the field's stream: rows_dev (2, nz, row_length) = P, N, written whole.  carry: the terms of the
+// tracer profile instead of those of the volume profile, split by the direction of the water all the same.  Owned levels only,
+// exact zeros elsewhere.  Reads the raw fields, the tracer (carry), the cell thickness when one is set and the records; the
+// resident planes, |.| arrays, running max, last row, tracer planes, version and a captured pass stay as they are.
+static int field_gross_async(nf_field *f, long t, bool carry, double *rows_dev)
+{
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_gross_profile", t, carry ? 1 : 0, rows_dev, 2 * (size_t)f->nz, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    const size_t rowlen = field_row_length(f);
+    if (lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in both blocks
+        NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * 2 * (size_t)f->nz, f->stream));
+    NF_TRY(f->gross_scratch.reserve((size_t)f->ws.nrec * 2 * gross_chunk_now(f->uv_dtype, carry, f->e3u != nullptr)));
+    GrossArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    if (carry) NF_TRY(field_tracer_input(f, t, lv, &a));
+    NF_TRY(field_cell_thick(f, t, lv, &a.th));
+    a.ref = f->tau_ref;
+    a.tr = field_transects(f);
+    a.scratch = f->gross_scratch.get();
+    a.scratch_len = f->gross_scratch.size();
+    a.rows = rows_dev;
+    a.nz = f->nz;
+    return launch_gross_profile(a, f->stream);
 }
 
 // Tracer transport of step t on the field's stream: K1tau into geo.tr_planes, then K3 over them into row_dev
@@ -1128,6 +1158,7 @@ try {
     f->prof_scratch.reset();
     f->tprof_scratch.reset();
     f->area_scratch.reset();
+    f->gross_scratch.reset();
     f->class_scratch.reset();
     f->joint_table.reset();
     f->joint_flags.reset();
@@ -1544,6 +1575,38 @@ try {
     NF_NEED_DEVICE();
     NF_TRY(field_ready(f, "compute_area_profile", true));
     return field_area_async(f, tIndex, rows_dev);
+}
+NF_API_CATCH
+
+// the checks of the two gross calls that need no device: arguments, then the tracer of the carried form
+static int field_gross_args(nf_field **self, int carry, const void *rows, const char *what)
+{
+    const std::string w(what);
+    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
+    NF_REQUIRE(!carry || (*self)->tau, NF_ERR_STATE, w + ": set_tracer first");
+    return NF_OK;
+}
+
+int nf_field_compute_gross_profile(nf_field **self, long tIndex, int carry, double *rows_host)
+try {
+    NF_TRY(field_gross_args(self, carry, rows_host, "nf_field_compute_gross_profile"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    NF_TRY(field_ready(f, "compute_gross_profile", true));
+    const size_t n = 2 * (size_t)f->nz * field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_gross_async(f, tIndex, carry != 0, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_gross_profile_async(nf_field **self, long tIndex, int carry, double *rows_dev)
+try {
+    NF_TRY(field_gross_args(self, carry, rows_dev, "nf_field_compute_gross_profile_async"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    NF_TRY(field_ready(f, "compute_gross_profile", true));
+    return field_gross_async(f, tIndex, carry != 0, rows_dev);
 }
 NF_API_CATCH
 

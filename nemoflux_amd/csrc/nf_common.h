@@ -412,6 +412,37 @@ struct AreaArgs {
 };
 int launch_area_profile(const AreaArgs &a, hipStream_t s);
 
+// Gross transports per level (nf_field_compute_gross_profile; DESIGN.md section 4, "Gross transports"): rows
+// (2, nz, row_length) = P, N, the terms of the profile row split by the direction of the water at their own slot; the kernels
+// write rows [z0, z1) of both.  tau set: the carried form (the terms of the tracer profile, split by the sign of the volume
+// term); th.e3u set: every slot's term takes the thickness at its own face -- the two combine.  Levels go
+// gross_chunk(dtype, carried, cell) at a time (the "gross_chunk" knob picks another candidate): scratch holds
+// 2 * chunk * ws.nrec run sums.  Measured (profiles/gross_timing.txt): float32 is fastest with 8 levels in all four forms;
+// float64 with 8 in the plain volume form only and with 4 wherever more than four gathers per level are in flight.  Every
+// candidate is free of scratch (-Rpass-analysis=kernel-resource-usage; DESIGN.md has the registers).
+constexpr int kGrossChunk = 8;
+constexpr int kGrossChunkWideF64 = 4;
+inline int gross_chunk(int dtype, bool carried, bool cell)
+{
+    return dtype == NF_F64 && (carried || cell) ? kGrossChunkWideF64 : kGrossChunk;
+}
+int gross_chunk_set(int levels);    // 0 = gross_chunk(dtype, carried, cell); 2, 4 or 8 (float64), 4 or 8 (float32)
+int gross_chunk_now(int dtype, bool carried, bool cell);
+struct GrossArgs {
+    StepInput in;
+    Transects tr;
+    double *scratch = nullptr;
+    size_t scratch_len = 0;
+    double *rows = nullptr;
+    long nz = 0;
+    const void *tau = nullptr;   // the carried tracer of the time step, (nz, ncell) of the field dtype; nullptr: volume form
+    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
+    double ref = 0.0;
+    int wrap_x = 1;
+    CellThick th;
+};
+int launch_gross_profile(const GrossArgs &a, hipStream_t s);
+
 // Tracer transport (nf_field_compute_tracer_flux, nf_tracer.hip): K1's vertical integral with every level's velocity
 // multiplied by the tracer interpolated to the face, tf = 0.5 (a + b) - ref (DESIGN.md section 4 has the face rule).  Writes
 // the two signed planes [eU_tau | eV_tau] of one time step, nothing else; K3 (planes = 2) reduces them.

@@ -669,6 +669,160 @@ int launch_area_profile(const AreaArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "area profile: the area_chunk knob names a chunk that is not built for this dtype");
 }
 
+// ---- gross transports: the terms of a profile row, split by the direction of the water at their own slot ----------------
+// The rows of nf_field_compute_gross_profile: per level and slot  q = w * d  with d of level_slots_tf<T, false> (the water) and
+// the carried term  c = q  (volume form) or  c = w * d  with d of level_slots_tf<T, true> (carried form: TauIn<T> among the
+// trailing arguments);  P = the sum of c over the slots with q > 0, N = over those with q < 0, a slot with q == 0 in neither.
+// A lane owns one record and up to LZ levels, as in k_area_segscan: the 4 gathers per level (+ 5 with a carried tracer, + 4 with
+// per-cell thicknesses, ThickIn<T> among the trailing arguments) of the whole chunk are issued before the first is used.  Both
+// parts take all four slots in weighted_sum's order into +0.0, a slot that is not theirs as +0.0: the order of the additions
+// does not depend on the signs, which is why negating uo / vo swaps and negates the parts bit for bit.  The 2 * LZ sums go
+// through ONE seg_scan.  runsum: 2 * LZ rows of n doubles, level-major: rows [0, LZ) P, rows [LZ, 2 LZ) N.
+template <typename T>
+__device__ inline TauIn<T> tau_in(const TauIn<T> &ti, const ThickIn<T> &) { return ti; }
+template <typename T>
+__device__ inline ThickIn<T> thick_arg(const TauIn<T> &, const ThickIn<T> &ct) { return ct; }
+
+// q, c: the water and carried terms of the four slots (weights applied), as Slots
+__device__ inline Slots weighted_slots(const Record &r, const Slots &d)
+{
+    Slots t;
+    t.s = r.wa.x * d.s, t.e = r.wa.y * d.e, t.n = r.wb.x * d.n, t.w = r.wb.y * d.w;
+    return t;
+}
+__device__ inline void gross_terms(const Slots &q, const Slots &c, double *pos, double *neg)
+{
+    *pos = (((0.0 + (q.s > 0.0 ? c.s : 0.0)) + (q.e > 0.0 ? c.e : 0.0)) + (q.n > 0.0 ? c.n : 0.0)) + (q.w > 0.0 ? c.w : 0.0);
+    *neg = (((0.0 + (q.s < 0.0 ? c.s : 0.0)) + (q.e < 0.0 ? c.e : 0.0)) + (q.n < 0.0 ? c.n : 0.0)) + (q.w < 0.0 ? c.w : 0.0);
+}
+
+template <typename T, int LZ, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_gross_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                          const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                          const T *__restrict__ v, long ncell, unsigned nx, int z0, int nlev,
+                                                          const double *__restrict__ thickness,
+                                                          const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                          T fill, T fill2, int two, double scale, int sverdrup,
+                                                          double *__restrict__ runsum, TI... extra)
+{
+    constexpr bool TR = (std::is_same<TI, TauIn<T>>::value || ...);
+    constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
+    const TauIn<T> ti = tau_in<T>(extra...);
+    const ThickIn<T> ct = thick_arg<T>(extra...);
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    double val[2 * LZ];
+#pragma unroll
+    for (int l = 0; l < 2 * LZ; ++l) val[l] = 0.0;
+    int key = -1;
+    if (k < n) {
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const auto nb = step_neighbours<TR>(r.c, nx, ncell, ti.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        LevelUV<T> x[LZ];
+        LevelTau<T> tt[TR ? LZ : 1];
+        LevelUV<T> e3[CT ? LZ : 1];
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {   // nlev is launch-uniform
+                x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);
+                if constexpr (CT) e3[l] = load_level_e3(ct, (long)(z0 + l) * ncell, r.c, nb);
+                if constexpr (TR) tt[l] = load_level_tau(ti.tau, (long)(z0 + l) * ncell, r.c, nb);
+            }
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {
+                SlotTh th;
+                if constexpr (CT)
+                    th = level_th(e3[l], ct);
+                else
+                    th = slot_th(thickness[z0 + l]);
+                const Slots q = weighted_slots(
+                    r, level_slots_tf<T, false>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, FaceTf{}));
+                Slots c = q;
+                if constexpr (TR)
+                    c = weighted_slots(r, level_slots_tf<T, true>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south,
+                                                                  level_tf(tt[l], nb, ti)));
+                gross_terms(q, c, &val[l], &val[LZ + l]);
+            }
+    }
+    if (seg_scan(val, key, k, n)) {
+#pragma unroll
+        for (int l = 0; l < LZ; ++l)
+            if (l < nlev) {
+                runsum[(long)l * n + k] = val[l];
+                runsum[(long)(LZ + l) * n + k] = val[LZ + l];
+            }
+    }
+}
+
+// "gross_chunk" tuning knob: the levels per chunk, one of the instantiated candidates of the dtype; 0 = gross_chunk(dtype,
+// carried, cell)
+static int g_gross_chunk = 0;
+int gross_chunk_set(int levels)
+{
+    if (levels != 0 && levels != 2 && levels != 4 && levels != 8) return -1;
+    g_gross_chunk = levels;
+    return NF_OK;
+}
+int gross_chunk_now(int dtype, bool carried, bool cell)
+{
+    return g_gross_chunk ? g_gross_chunk : gross_chunk(dtype, carried, cell);
+}
+
+template <typename T, int LZ, typename... TI>
+static int launch_gross_t(const GrossArgs &a, hipStream_t s, TI... extra)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    double *nsum = a.scratch + (size_t)LZ * ws.nrec;   // the second half of the run sums
+    for (int zc = in.z0; zc < in.z1; zc += LZ) {
+        const int nlev = in.z1 - zc < LZ ? in.z1 - zc : LZ;
+        if (ws.nrec > 0)
+            hipLaunchKernelGGL((k_gross_segscan<T, LZ, TI...>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(),
+                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, zc, nlev,
+                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale,
+                               in.sverdrup, a.scratch, extra...);
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)zc * row_length, row_length, (unsigned)nlev,
+                        s);
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, nsum, a.rows + (a.nz + zc) * row_length, row_length, (unsigned)nlev,
+                        s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+// the four forms of one dtype and chunk: volume or carried tracer, each with the scalar or the per-cell thicknesses
+template <typename T, int LZ>
+static int launch_gross_form(const GrossArgs &a, hipStream_t s)
+{
+    const TauIn<T> ti{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0};
+    if (a.tau && a.th.e3u) return launch_gross_t<T, LZ>(a, s, ti, thick_in<T>(a.th));
+    if (a.tau) return launch_gross_t<T, LZ>(a, s, ti);
+    if (a.th.e3u) return launch_gross_t<T, LZ>(a, s, thick_in<T>(a.th));
+    return launch_gross_t<T, LZ>(a, s);
+}
+
+int launch_gross_profile(const GrossArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    const int chunk = gross_chunk_now(in.dtype, a.tau != nullptr, a.th.e3u != nullptr);
+    NF_REQUIRE(in.u && in.v && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "gross profile: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "gross profile: null argument");
+    NF_REQUIRE(in.z1 <= a.nz, NF_ERR_ARG, "gross profile: bad arguments");
+    NF_TRY(check_raw_step("gross profile", in, a.tr, a.scratch_len, 2 * (size_t)chunk));
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (in.dtype == NF_F64 && chunk == 2) return launch_gross_form<double, 2>(a, s);
+    if (in.dtype == NF_F64 && chunk == 4) return launch_gross_form<double, 4>(a, s);
+    if (in.dtype == NF_F64 && chunk == 8) return launch_gross_form<double, 8>(a, s);
+    if (in.dtype == NF_F32 && chunk == 4) return launch_gross_form<float, 4>(a, s);
+    if (in.dtype == NF_F32 && chunk == 8) return launch_gross_form<float, 8>(a, s);
+    NF_REQUIRE(in.dtype == NF_F64 || in.dtype == NF_F32, NF_ERR_ARG, "gross profile: dtype must be NF_F64 or NF_F32");
+    NF_REQUIRE(false, NF_ERR_ARG, "gross profile: the gross_chunk knob names a chunk that is not built for this dtype");
+}
+
 // ---- volume transport in tracer classes: level_slots, each term sent to the row of its face's class -------------------
 // One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are
 // level_slots' times their weights; each is added, in slot order (south, east, north, west), to the lane's accumulator of the

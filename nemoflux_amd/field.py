@@ -645,8 +645,8 @@ class Field(object):
         (a float64 mesh_mask thickness beside float32 velocities is rounded to float32); a device array or a time-varying
         array of another dtype raises.  fill_value / missing_value: the thickness's own missing markers (a file's when not
         given); a thickness that is NaN or a marker counts as 0.
-        computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux and computeTracerAll then integrate with
-        these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
+        computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux, computeTracerAll, computeAreaProfile and
+        computeGrossProfile (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
         set.  setCellThickness(None, None) goes back to deptht_bounds."""
         self._e3 = None
         self._row_valid = False
@@ -817,6 +817,65 @@ class Field(object):
             rows = numpy.zeros(shape, numpy.float64)
             check(lib.nf_field_compute_area_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return self._split_rows(rows[0]), self._split_rows(rows[1])
+
+    def computeGrossProfile(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Gross transports of time step tIndex, level by level: (totals, segments) of shape (2, nz, ntransect) and
+        (2, nz, nseg), part 0 = P, what goes through the section in the direction computeFlux counts positive, part 1 = N,
+        what comes back (<= 0 in the volume form).  Every term of the computeFluxProfile row goes to P where it is > 0 and to N
+        where it is < 0, per weight entry, slot and level; P + N is that row up to rounding.  carry=True (setTracer first): the
+        terms of computeTracerProfile instead, split by the direction of the water at their slot, not by their own sign -- P is
+        what the flow carries forward, N what it carries back; this form takes a cell thickness (setCellThickness) too.
+        Levels this rank does not own (slab_range) are zeros.  Leaves the resident edge fluxes, the running max, the row of the
+        last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
+        (2 * nz, row_length), P's rows then N's, that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        self._stage(tIndex, prefetch_next)
+        if carry:
+            self._stage_tracer(tIndex)
+        if out is not None:
+            out = self._rows_out(out, 2 * self.nz)
+            check(lib.nf_field_compute_gross_profile_async(ctypes.byref(self._h), tIndex, 1 if carry else 0,
+                                                           ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((2 * self.nz, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_gross_profile(ctypes.byref(self._h), tIndex, 1 if carry else 0, _lib.dptr(rows)))
+        return self._split_rows(rows.reshape(2, self.nz, self._row_width))
+
+    @staticmethod
+    def grossTransport(parts, ztop=None, zbot=None, bounds_depth=None):
+        """Depth sum of both parts of computeGrossProfile: parts (2, nz, n), totals or segments alike, gives (2, n) = P, N.
+        With ztop < zbot (the units of deptht_bounds) the sum over that depth band instead, level z entering with
+        overlap([ztop, zbot], layer z) / thickness[z] as in depthBandFlux; bounds_depth (nz, 2) is then needed (a Field's
+        bounds_depth)."""
+        P = numpy.asarray(parts, dtype=numpy.float64)
+        if P.ndim < 2 or P.shape[0] != 2:
+            raise ValueError(f'grossTransport: the parts must have shape (2, nz, ...), got {P.shape}')
+        if ztop is None and zbot is None:
+            return P.sum(axis=1)
+        if ztop is None or zbot is None or bounds_depth is None:
+            raise ValueError('grossTransport: a depth band needs ztop, zbot and bounds_depth')
+        ztop, zbot = float(ztop), float(zbot)
+        if not ztop <= zbot:
+            raise ValueError(f'grossTransport: need ztop <= zbot, got {ztop}, {zbot}')
+        if numpy.shape(bounds_depth) != (P.shape[1], 2):
+            raise ValueError(f'grossTransport: bounds_depth must have shape {(P.shape[1], 2)}, got {numpy.shape(bounds_depth)}')
+        return numpy.stack([_band_sum(P[0], bounds_depth, ztop, zbot), _band_sum(P[1], bounds_depth, ztop, zbot)])
+
+    @staticmethod
+    def transportWeightedTracer(volumeParts, carriedParts, reference=0.0):
+        """Transport-weighted mean tracer of the inflow and of the outflow: carried / volume + reference per direction, from
+        the volume parts and the carried parts (computeGrossProfile with carry=False and carry=True, or their grossTransport
+        sums) of one shape (2, ...); `reference`: the reference of setTracer, which the carried parts have subtracted.  NaN
+        where the volume part is 0.  It ASSUMES that the tracer is present wherever the velocity is: a face with a velocity
+        and no tracer value adds to the volume part and nothing to the carried part, and pulls the mean towards the
+        reference."""
+        V = numpy.asarray(volumeParts, dtype=numpy.float64)
+        C = numpy.asarray(carriedParts, dtype=numpy.float64)
+        if V.shape != C.shape or V.shape[:1] != (2,):
+            raise ValueError(f'transportWeightedTracer: need two arrays of one shape (2, ...), got {V.shape}, {C.shape}')
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(V != 0.0, C / V + float(reference), numpy.nan)
 
     @staticmethod
     def overturningGyre(volumeProfile, areaRows, tracerRow):

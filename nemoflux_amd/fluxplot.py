@@ -16,6 +16,7 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
+    ... --gross [--tracer thetao] [--zrange 0,700] (inflow, outflow and net of every transect; what they carry, their mean thetao)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
 """
@@ -161,6 +162,43 @@ def eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracer
     fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
     d = fld.meanEddyTracerTransport()
     return numpy.array([d[k] for k in EDDY_PARTS]).reshape(len(EDDY_PARTS), len(lonLatZPoints)), fld
+
+
+GROSS_COLUMNS = ('inflow', 'outflow', 'net')
+GROSS_TRACER_COLUMNS = ('carried_in', 'carried_out', 'mean_in', 'mean_out')
+
+
+def grossSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, zrange=None,
+                sverdrup=False, cellThickness=None):
+    """(nt, ntransect, 3) inflow, outflow and net water flow of every transect (GROSS_COLUMNS: Field.computeGrossProfile, summed
+    over the depth or the band zrange = (ztop, zbot) by Field.grossTransport; net = inflow + outflow) and the Field.  With
+    `tracer` (nt, ntransect, 7): also what the inflow and the outflow carry of that variable of tracerFile (default: the T
+    file), times tracerScale, and the transport-weighted mean tracer of each (GROSS_TRACER_COLUMNS;
+    Field.transportWeightedTracer, NaN where nothing flows that way)."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    if tracer:
+        fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    band = dict(ztop=zrange[0], zbot=zrange[1], bounds_depth=fld.bounds_depth) if zrange else {}
+    totals = numpy.zeros((fld.nt, len(lonLatZPoints), 7 if tracer else 3))
+    for t in range(fld.nt):
+        vol = fld.grossTransport(fld.computeGrossProfile(t, prefetch_next=not tracer)[0], **band)
+        totals[t, :, 0], totals[t, :, 1], totals[t, :, 2] = vol[0], vol[1], vol[0] + vol[1]
+        if tracer:
+            car = fld.grossTransport(fld.computeGrossProfile(t, carry=True, prefetch_next=True)[0], **band)
+            mean = fld.transportWeightedTracer(vol, car, tracerRef)
+            totals[t, :, 3], totals[t, :, 4] = car[0] * float(tracerScale), car[1] * float(tracerScale)
+            totals[t, :, 5], totals[t, :, 6] = mean[0], mean[1]
+    return totals, fld
+
+
+def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
+    """the --gross option of the command line: refused combinations raise RuntimeError"""
+    if not gross:
+        return
+    for on, opt in ((classes, '--classes'), (levels, '--levels'), (decompose, '--decompose'), (eddy, '--eddy'), (show, '--show')):
+        if on:
+            raise RuntimeError(f'ERROR: --gross and {opt} cannot be combined: --gross writes the inflow, the outflow and the net '
+                               f'transport of every transect (with --tracer what they carry, and their mean tracer) as CSV only')
 
 
 def checkEddyArgs(eddy=False, tracer='', classes='', levels=False, zrange='', show=False, decompose=False):
@@ -327,19 +365,36 @@ def parseZRange(zrange):
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
-         eddy=False, tracer2='', tracer2File='', classes2=''):
+         eddy=False, tracer2='', tracer2File='', classes2='', gross=False):
+    checkGrossArgs(gross, classes, levels, decompose, eddy, show)
     checkJointClassArgs(classes2, tracer2, tracer2File, tracer, classes, carry, levels, zrange, show, eddy, decompose)
     checkEddyArgs(eddy, tracer, classes, levels, zrange, show, decompose)
     checkDecomposeArgs(decompose, tracer, classes, levels, zrange, show)
     checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, carry, levels, tracer)
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
-    checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, zrange)
+    checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '' if gross else zrange)   # --gross sums its parts over a band
     checkLevelsArgs(levels, zrange, classes, show)
     checkCarryArgs(carry, carryFile, carryRef, carryScale, classes, tracer, levels)
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
     ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    if gross:
+        totals, fld = grossSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), float(tracerScale),
+                                  parseZRange(zrange) if zrange else None, sverdrup, ct)
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        cols = GROSS_COLUMNS + (GROSS_TRACER_COLUMNS if tracer else ())
+        title = f'# gross water flow [{unit}]'
+        if tracer:
+            title += (f', what it carries of {tracer} [{tracer} x {unit}' +
+                      (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '') + f'] and its mean {tracer}')
+        if zrange:
+            title += f' between the depths {zrange}'
+        lines = ['time,transect,' + ','.join(cols)]
+        lines += [f'{timeVals[t]},{name},' + ','.join(f'{x:.15g}' for x in totals[t, p])
+                  for t in range(fld.nt) for p, name in enumerate(names)]
+        _emit(title + '\n' + '\n'.join(lines) + '\n', output)
+        return totals
     if eddy:
         totals, fld = eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
         totals = totals * float(tracerScale)
@@ -484,6 +539,11 @@ if __name__ == '__main__':
     ap.add_argument('--decompose', action='store_true',
                     help='with --tracer NAME: one CSV line per time step and part (time,part,...): the transport of NAME and its '
                          'throughflow, overturning and gyre parts (--tracer-ref, --tracer-scale, -s and --cell-thickness apply)')
+    ap.add_argument('--gross', action='store_true',
+                    help='one CSV line per time step and transect (time,transect,inflow,outflow,net): the water that crosses in '
+                         'the positive direction, the water that comes back, and their sum; with --tracer NAME also what the two '
+                         'carry of NAME and the transport-weighted mean NAME of each (--zrange, --cell-thickness, --tracer-ref, '
+                         '--tracer-scale and -s apply)')
     ap.add_argument('--eddy', action='store_true',
                     help='with --tracer NAME: one CSV line per part (part,...): the mean over all time steps of the transport of '
                          'NAME, the transport of the time-mean NAME by the time-mean flow, and the eddy part, their difference '
