@@ -538,6 +538,30 @@ int nf_inflater_run(nf_inflater **self, const void *comp_host, size_t comp_bytes
 int nf_time_mean(double *acc_dev, unsigned *cnt_dev, const void *src_dev, long nsteps, long long stride_elems, size_t n,
                  int dtype, double fill, double missing, int first, int last, int rule, long total_steps, double fill_out,
                  void *hip_stream);
+/* The thickness-weighted time mean of a velocity series and the mean of the cell thickness at its points (z*, variable-volume
+ * output): nsteps arrays of n values each of both, step t at src_dev + t * src_stride_elems and thk_dev + t * thk_stride_elems
+ * elements of dtype (HBM).  Per value i, the steps visited strictly in ascending order:
+ *     sF = +0.0, sH = +0.0, c = 0              (first = 0: what the previous call left in accf_dev / acch_dev / cnt_dev)
+ *     h = fixth(thk[t * thk_stride_elems + i]) fixth as in nf_field_set_cell_thickness: NaN or one of the thickness's two
+ *                                              markers (thk_fill, thk_missing, compared in dtype) -> 0, else (double)
+ *     sH = sH + h                              at every step
+ *     x = src[t * src_stride_elems + i];       x present (nf_time_mean's rule with fill, missing):
+ *                                              sF = sF + (h * (double)x), c += 1     the product rounded, then added: no fma
+ * No other arithmetic, no reassociation: a series split over several calls gives the bits of one call, whatever the launch
+ * shape, as for nf_time_mean.
+ * last = 0: accf_dev[i] = sF, acch_dev[i] = sH, cnt_dev[i] = c for the next call.  last = 1:
+ *     accf_dev[i] = c == 0 ? fill_out : (sH == 0 ? +0.0 : sF / sH)     the weighted mean velocity
+ *     acch_dev[i] = sH / total_steps                                   the mean thickness
+ * so that (mean thickness) x (mean velocity) is the mean of thickness x velocity, face by face, up to rounding; a velocity
+ * missing at every step stays missing, water that is never there (sH == 0) gives velocity 0 and thickness 0.
+ * cnt_dev may be NULL when first && last (nothing is carried: 2 * nsteps * n * sizeof(dtype) bytes in, 16 n bytes out).
+ * NF_ERR_ARG, decided before a device is needed: NULL accf_dev / acch_dev / src_dev / thk_dev, nsteps < 1, n == 0, either
+ * stride < n with nsteps > 1, a bad dtype, last with total_steps < 1, NULL cnt_dev without first && last.
+ * Asynchronous on hip_stream. */
+int nf_time_mean_weighted(double *accf_dev, double *acch_dev, unsigned *cnt_dev, const void *src_dev, long long src_stride_elems,
+                          const void *thk_dev, long long thk_stride_elems, long nsteps, size_t n, int dtype, double fill,
+                          double missing, double thk_fill, double thk_missing, int first, int last, long total_steps,
+                          double fill_out, void *hip_stream);
 
 /* ------------------------------------------------------------------ synthetic data (datagen.py) */
 /* Stream functions offered on device (no eval on the GPU): psi = g(z,t) * h(x,y)

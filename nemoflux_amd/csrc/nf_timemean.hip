@@ -19,6 +19,18 @@
 // offsets are 64-bit (step 5 of a 3600 x 1800 x 75 series starts beyond 2^31 elements).
 //
 // Algorithmic bytes of a first && last call: nsteps * n * sizeof(T) read + 8 n written; a carried call adds 12 n each way.
+//
+// The thickness-weighted mean (nf_time_mean_weighted, Field.timeMean(thicknessWeighted=True)) reads two series at once, a
+// velocity and the cell thickness at its points.  Per value i, the steps visited strictly in ascending order:
+//   sF = +0.0, sH = +0.0, c = 0          (or what the previous call left in accf / acch / cnt)
+//   h = fixth(thk[t * thk_stride + i])   thick_fixed of nf_common.h: NaN or one of the thickness's two markers -> 0
+//   sH = sH + h                          at every step
+//   x = src[t * src_stride + i];         x present (the rule above, src's own markers):  sF = sF + (h * (double)x),  c += 1
+// The product is rounded, then added (-ffp-contract=off: no fma).  The last call finishes in place:
+//   accf = c == 0 ? fill_out : (sH == 0 ? +0.0 : sF / sH)      the weighted mean velocity
+//   acch = sH / total_steps                                    the mean thickness
+// so that acch * accf is the mean volume flux per unit width, face by face.  Same access pattern with two loads per step and
+// lane; 2 * nsteps * n * sizeof(T) read + 16 n written by a first && last call, a carried call adds 20 n each way.
 #include "nf_capi.h"
 
 namespace nf {
@@ -127,6 +139,97 @@ __device__ inline void tm_lane(double *acc, unsigned *cnt, const T *src, long ns
     }
 }
 
+// VEC float64 sums at p, 16 bytes at a time
+template <int VEC>
+__device__ inline void tm_load_sums(double (&s)[VEC], const double *p)
+{
+#pragma unroll
+    for (int k = 0; k < VEC; k += 2) {
+        constexpr int W = VEC > 1 ? 2 : 1;
+        const TmLanes<double, W> a = tm_load<double, W, false>(p + k);
+#pragma unroll
+        for (int q = 0; q < W; ++q) s[k + q] = a.x[q];
+    }
+}
+template <int VEC>
+__device__ inline void tm_store_sums(double *p, const double (&s)[VEC])
+{
+#pragma unroll
+    for (int k = 0; k < VEC; k += 2) {
+        constexpr int W = VEC > 1 ? 2 : 1;
+        TmLanes<double, W> a;
+#pragma unroll
+        for (int q = 0; q < W; ++q) a.x[q] = s[k + q];
+        tm_store<double, W>(p + k, a);
+    }
+}
+
+template <typename T> struct TmwSeries {
+    const T *src, *thk;
+    long long src_stride, thk_stride;
+    T m1, m2, h1, h2;     // the markers of src, of thk
+};
+
+// the weighted form of tm_lane: the VEC values that begin at i0, two loads per step, US steps' loads in flight, the adds in
+// step order.  f.rule is not read.
+template <typename T, int VEC, int US>
+__device__ inline void tmw_lane(double *accf, double *acch, unsigned *cnt, const TmwSeries<T> &in, long nsteps, size_t i0,
+                                const TmFinish &f)
+{
+    double sF[VEC], sH[VEC];
+    unsigned c[VEC];
+    if (f.first) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) sF[k] = 0.0, sH[k] = 0.0, c[k] = 0u;
+    } else {
+        tm_load_sums<VEC>(sF, accf + i0);
+        tm_load_sums<VEC>(sH, acch + i0);
+        const TmLanes<unsigned, VEC> n0 = tm_load<unsigned, VEC, false>(cnt + i0);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) c[k] = n0.x[k];
+    }
+    const T *p = in.src + i0, *q = in.thk + i0;
+    for (long t = 0; t < nsteps; t += US) {
+        const int nb = nsteps - t < US ? (int)(nsteps - t) : US;   // wave-uniform
+        TmLanes<T, VEC> x[US], h[US];
+#pragma unroll
+        for (int r = 0; r < US; ++r)
+            if (r < nb) {
+                x[r] = tm_load<T, VEC, true>(p + (long long)r * in.src_stride);
+                h[r] = tm_load<T, VEC, true>(q + (long long)r * in.thk_stride);
+            }
+#pragma unroll
+        for (int r = 0; r < US; ++r)
+            if (r < nb) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const double hh = thick_fixed<T>(h[r].x[k], in.h1, in.h2);
+                    sH[k] = sH[k] + hh;
+                    const bool here = tr_present<T>(x[r].x[k], in.m1, in.m2);
+                    const double prod = hh * (double)x[r].x[k];     // rounded, then added: no fma (-ffp-contract=off)
+                    sF[k] = here ? sF[k] + prod : sF[k];
+                    c[k] += here ? 1u : 0u;
+                }
+            }
+        p += (long long)US * in.src_stride;
+        q += (long long)US * in.thk_stride;
+    }
+    if (f.last) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            sF[k] = c[k] == 0u ? f.fill_out : (sH[k] == 0.0 ? 0.0 : sF[k] / sH[k]);
+            sH[k] = sH[k] / f.total_steps;
+        }
+    } else {
+        TmLanes<unsigned, VEC> n1;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) n1.x[k] = c[k];
+        tm_store<unsigned, VEC>(cnt + i0, n1);
+    }
+    tm_store_sums<VEC>(accf + i0, sF);
+    tm_store_sums<VEC>(acch + i0, sH);
+}
+
 }  // namespace
 
 // 256 threads, VEC values per lane, one tile of 256 * VEC values per block: i0 = (tile * 256 + tid) * VEC.  The tiles are dealt
@@ -144,6 +247,21 @@ __global__ __launch_bounds__(256) void k_time_mean(double *acc, unsigned *cnt, c
         return;
     }
     for (size_t i = i0; i < n; ++i) tm_lane<T, 1, US>(acc, cnt, src, nsteps, stride, i, m1, m2, f);
+}
+
+// the same launch shape for the thickness-weighted mean: two series in, accf and acch out
+template <typename T, int VEC, int US>
+__global__ __launch_bounds__(256) void k_time_mean_weighted(double *accf, double *acch, unsigned *cnt, TmwSeries<T> in,
+                                                            long nsteps, size_t n, unsigned ntiles, TmFinish f)
+{
+    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
+    const size_t i0 = ((size_t)tile * 256 + threadIdx.x) * VEC;
+    if (tile >= ntiles || i0 >= n) return;
+    if (VEC == 1 || n - i0 >= (size_t)VEC) {
+        tmw_lane<T, VEC, US>(accf, acch, cnt, in, nsteps, i0, f);
+        return;
+    }
+    for (size_t i = i0; i < n; ++i) tmw_lane<T, 1, US>(accf, acch, cnt, in, nsteps, i, f);
 }
 
 namespace {
@@ -188,6 +306,51 @@ int launch_time_mean_t(const TimeMeanArgs &a, hipStream_t s)
     return al16 ? launch_time_mean_v<T, VEC>(a, s) : launch_time_mean_v<T, 1>(a, s);
 }
 
+// Steps in flight per lane of the weighted form, two 16-byte loads each (8 VGPRs), so 4 steps keep the 128 bytes per lane in
+// flight that k_time_mean has with 8.  VGPRs at float64 / float32 and waves per SIMD, none with scratch
+// (-Rpass-analysis=kernel-resource-usage): 2 steps 35 / 50, 8 / 8 waves; 4 steps 54 / 64, 7 (102 SGPRs) / 8 waves; 8 steps
+// 81 / 95, 5 / 5 waves.  Measured at the bench shape, two series of 3600 x 1800 x 75 x 12, each build in a process of its own
+// beside nf_time_mean on one of the series (profiles/weighted_mean_timing.txt): 4 steps 16.44 ms at
+// float64 and 9.44 ms at float32, 0.97 and 0.98 of nf_time_mean's fraction of the HBM peak in that process; 2 steps 17.24
+// and 9.75 ms (1.02, 0.93); 8 steps 16.92 and 10.00 ms (0.93, 0.91).
+constexpr int kTimeMeanWeightedSteps = 4;
+
+struct TimeMeanWeightedArgs {
+    double *accf, *acch;
+    unsigned *cnt;
+    const void *src, *thk;
+    long long src_stride, thk_stride;
+    long nsteps;
+    size_t n;
+    double fill, missing, thk_fill, thk_missing;
+    TmFinish f;
+};
+
+template <typename T, int VEC>
+int launch_time_mean_weighted_v(const TimeMeanWeightedArgs &a, hipStream_t s)
+{
+    const size_t per_block = 256u * (size_t)VEC;
+    const size_t ntiles = (a.n + per_block - 1) / per_block;
+    NF_REQUIRE(ntiles <= 0x7ffffff0u, NF_ERR_ARG, "nf_time_mean_weighted: n is too large for one launch");
+    const TmwSeries<T> in{(const T *)a.src, (const T *)a.thk, a.src_stride, a.thk_stride,
+                          (T)a.fill, (T)a.missing, (T)a.thk_fill, (T)a.thk_missing};
+    hipLaunchKernelGGL((k_time_mean_weighted<T, VEC, kTimeMeanWeightedSteps>), dim3(xcd_grid((unsigned)ntiles)), dim3(256), 0, s,
+                       a.accf, a.acch, a.cnt, in, a.nsteps, a.n, (unsigned)ntiles, a.f);
+    NF_HIP(hipGetLastError());
+    return NF_OK;
+}
+
+template <typename T, int VEC>
+int launch_time_mean_weighted_t(const TimeMeanWeightedArgs &a, hipStream_t s)
+{
+    // every step of both series, accf, acch and cnt 16-byte aligned at every lane's first value: else one value per lane
+    bool al16 = (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.thk % 16 == 0 && (uintptr_t)a.accf % 16 == 0 &&
+                (uintptr_t)a.acch % 16 == 0 && (uintptr_t)a.cnt % 16 == 0;
+    if (a.nsteps > 1)
+        al16 = al16 && (a.src_stride * (long long)sizeof(T)) % 16 == 0 && (a.thk_stride * (long long)sizeof(T)) % 16 == 0;
+    return al16 ? launch_time_mean_weighted_v<T, VEC>(a, s) : launch_time_mean_weighted_v<T, 1>(a, s);
+}
+
 }  // namespace
 
 }  // namespace nf
@@ -215,5 +378,31 @@ try {
                          TmFinish{first ? 1 : 0, last ? 1 : 0, rule, (double)total_steps, fill_out}};
     hipStream_t s = (hipStream_t)hip_stream;
     return dtype == NF_F64 ? launch_time_mean_t<double, 2>(a, s) : launch_time_mean_t<float, 4>(a, s);
+}
+NF_API_CATCH
+
+extern "C" int nf_time_mean_weighted(double *accf_dev, double *acch_dev, unsigned *cnt_dev, const void *src_dev,
+                                     long long src_stride_elems, const void *thk_dev, long long thk_stride_elems, long nsteps,
+                                     size_t n, int dtype, double fill, double missing, double thk_fill, double thk_missing,
+                                     int first, int last, long total_steps, double fill_out, void *hip_stream)
+try {
+    NF_REQUIRE(accf_dev && acch_dev && src_dev && thk_dev, NF_ERR_ARG,
+               "nf_time_mean_weighted: null accf_dev, acch_dev, src_dev or thk_dev");
+    NF_REQUIRE(nsteps >= 1, NF_ERR_ARG, "nf_time_mean_weighted: nsteps must be at least 1");
+    NF_REQUIRE(n > 0, NF_ERR_ARG, "nf_time_mean_weighted: n must not be 0");
+    NF_REQUIRE(nsteps == 1 || (src_stride_elems >= 0 && (unsigned long long)src_stride_elems >= n), NF_ERR_ARG,
+               "nf_time_mean_weighted: src_stride_elems must be at least n when there is more than one step");
+    NF_REQUIRE(nsteps == 1 || (thk_stride_elems >= 0 && (unsigned long long)thk_stride_elems >= n), NF_ERR_ARG,
+               "nf_time_mean_weighted: thk_stride_elems must be at least n when there is more than one step");
+    NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_time_mean_weighted: dtype must be NF_F64 or NF_F32");
+    NF_REQUIRE(!last || total_steps >= 1, NF_ERR_ARG, "nf_time_mean_weighted: total_steps must be at least 1 for the last call");
+    NF_REQUIRE(cnt_dev || (first && last), NF_ERR_ARG,
+               "nf_time_mean_weighted: cnt_dev may be null only when first && last (nothing is carried)");
+    NF_NEED_DEVICE();
+    const TimeMeanWeightedArgs a{accf_dev, acch_dev, cnt_dev, src_dev, thk_dev, src_stride_elems, thk_stride_elems, nsteps, n,
+                                 fill, missing, thk_fill, thk_missing,
+                                 TmFinish{first ? 1 : 0, last ? 1 : 0, NF_MEAN_OVER_STEPS, (double)total_steps, fill_out}};
+    hipStream_t s = (hipStream_t)hip_stream;
+    return dtype == NF_F64 ? launch_time_mean_weighted_t<double, 2>(a, s) : launch_time_mean_weighted_t<float, 4>(a, s);
 }
 NF_API_CATCH

@@ -647,7 +647,9 @@ class Field(object):
         given); a thickness that is NaN or a marker counts as 0.
         computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux, computeTracerAll, computeAreaProfile and
         computeGrossProfile (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
-        set.  setCellThickness(None, None) goes back to deptht_bounds."""
+        set.  timeMean and meanEddyTracerTransport carry a static thickness over to the mean state and take a time-varying one
+        with thicknessWeighted=True (thickness-weighted mean velocities, mean thicknesses).  setCellThickness(None, None) goes
+        back to deptht_bounds."""
         self._e3 = None
         self._row_valid = False
         if e3u is None or e3v is None:
@@ -957,7 +959,63 @@ class Field(object):
         check(lib.nf_synchronize())
         return acc, fill_out
 
-    def timeMean(self, steps=None):
+    def _time_mean_weighted_arrays(self, a, markers, thk, thk_markers, t0, t1):
+        """The thickness-weighted mean over the steps [t0, t1) of the (nt, nz, ny, nx) velocity `a` and the mean of the
+        thickness `thk` at its points, by nf_time_mean_weighted; each of the two in any of the three homes (HBM, host,
+        file-backed), which the bits do not depend on.  Returns two float64 torch CUDA tensors (1, nz, ny, nx) and the fill of
+        the first (as in _time_mean_array)."""
+        import torch
+        dt = numpy.dtype(_native_dtype(a))
+        if numpy.dtype(_native_dtype(thk)) != dt:
+            raise RuntimeError(f'ERROR: timeMean: the cell thickness is {numpy.dtype(_native_dtype(thk)).name}, uo/vo are {dt.name}')
+        code, size = (NF_F32 if dt == numpy.float32 else NF_F64), dt.itemsize
+        marks = [float(m) for m in markers if m == m]
+        with numpy.errstate(over='ignore'):
+            fill_out = float(dt.type(marks[0])) if marks else numpy.nan
+        fill, missing = (marks + [numpy.nan, numpy.nan])[:2]
+        n = self.nz * self.ny * self.nx
+        accf, acch = (torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda') for _ in range(2))
+
+        def run(pa, ph, nsteps, first, last, cnt=None):
+            check(lib.nf_time_mean_weighted(accf.data_ptr(), acch.data_ptr(), None if cnt is None else cnt.data_ptr(), pa, n, ph, n,
+                                            nsteps, n, code, fill, missing, float(thk_markers[0]), float(thk_markers[1]),
+                                            1 if first else 0, 1 if last else 0, t1 - t0, fill_out, None))
+
+        series = (a, thk)
+        ptrs = [_lib.device_pointer(x) for x in series]
+        if ptrs[0] is not None and ptrs[1] is not None:       # both in HBM: one pass, nothing carried
+            run(ptrs[0] + t0 * n * size, ptrs[1] + t0 * n * size, t1 - t0, True, True)
+        else:
+            cnt = torch.empty(n, dtype=torch.int32, device='cuda')
+            staged = [p is None for p in ptrs]
+            lazy = [hasattr(x, 'read_step') for x in series]
+            # file-backed: one step at a time through a pinned buffer; host arrays: groups of steps, the staging buffers of
+            # the two series together within _MEAN_STAGE_BYTES
+            group = 1 if any(lazy) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
+            bufs = [self._host_array((self.nz, self.ny, self.nx), dt) if z else None for z in lazy]
+            hosts = [_native(x).reshape(self.nt, n) if st and not z else None for x, st, z in zip(series, staged, lazy)]
+            stage = [_lib.DeviceBuffer(min(group, t1 - t0) * n * size) if st else None for st in staged]
+            for t in range(t0, t1, group):
+                k = min(group, t1 - t)
+                cur = []
+                for j in range(2):
+                    if not staged[j]:
+                        cur.append(ptrs[j] + t * n * size)
+                        continue
+                    if lazy[j]:
+                        series[j].read_step(t, out=bufs[j])
+                    check(lib.nf_memcpy_h2d(stage[j].ptr, bufs[j].ctypes.data if lazy[j] else hosts[j][t:t + k].ctypes.data,
+                                            k * n * size))
+                    cur.append(stage[j].ptr)
+                run(cur[0], cur[1], k, t == t0, t + k == t1, cnt)
+                check(lib.nf_synchronize())     # the staging buffers are written again by the next group
+            for b in stage:
+                if b is not None:
+                    b.free()
+        check(lib.nf_synchronize())
+        return accf, acch, fill_out
+
+    def timeMean(self, steps=None, thicknessWeighted=False):
         """The mean state of the steps [t0, t1) (steps=None: all of them) as a new Field with nt = 1 and float64 fields in HBM,
         built through fromArrays from the same bounds, deptht_bounds, transects, sverdrup, periodX and cell policies: every
         diagnostic of the engine works on it unchanged.  uo / vo: sum over the steps of the present values / number of steps
@@ -965,19 +1023,35 @@ class Field(object):
         volume fluxes); a value missing at every step is the new Field's fill, the source's first marker as its dtype holds it
         (NaN without one).  A tracer of setTracer / setClassTracer: the mean of its present values, set on the new Field with
         the same reference and wrapX; the class edges are carried over.  A static cell thickness is carried over as float64;
-        a time-varying one, and a sharded Field (slab_range), raise.  The sums are float64, left to right in step order
-        (nf_time_mean), wherever the arrays live: HBM (one pass), host (uploaded in groups of steps) or files (one step at a
-        time).  Nothing of this Field changes."""
+        a sharded Field (slab_range) raises, and so does a time-varying cell thickness unless thicknessWeighted=True.  The sums
+        are float64, left to right in step order (nf_time_mean), wherever the arrays live: HBM (one pass), host (uploaded in
+        groups of steps) or files (one step at a time).  Nothing of this Field changes.
+        thicknessWeighted=True (setCellThickness first): the mean state of z* / variable-volume output.  With a time-varying
+        thickness the velocities are the thickness-weighted means <e3u uo> / <e3u>, <e3v vo> / <e3v> (nf_time_mean_weighted:
+        a missing velocity adds nothing to the numerator, a thickness that is NaN or a marker counts as 0, a velocity missing
+        at every step is the fill, 0 where the thickness sums to 0), and the new Field gets the mean thicknesses <e3u>, <e3v>
+        as a static float64 cell thickness in HBM: (mean thickness) x (mean velocity) is the mean volume flux face by face,
+        so the volume flux of the mean state is again the mean of the volume fluxes.  The tracers keep the plain mean of
+        their present values (there is no e3t to weight them with).  With a static thickness the weights cancel: the result
+        of timeMean(steps), bit for bit."""
         if self.slab_range is not None:
             raise RuntimeError('ERROR: timeMean: the mean state of a sharded Field (slab_range) is not defined here; build the '
                                'Field without slab_range')
         e3 = getattr(self, '_e3', None)
-        if e3 is not None and e3['nt'] != 1:
+        if thicknessWeighted and e3 is None:
+            raise RuntimeError('ERROR: timeMean: thicknessWeighted=True needs a cell thickness; call setCellThickness first')
+        weighted = bool(thicknessWeighted) and e3['nt'] != 1
+        if e3 is not None and e3['nt'] != 1 and not weighted:
             raise RuntimeError('ERROR: timeMean: the mean state of a time-varying cell thickness is not defined here (it would '
                                'need thickness-weighted means); set a static thickness or none')
         t0, t1 = self._step_range(steps)
-        u, fill = self._time_mean_array(self._uv[0], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
-        v, _ = self._time_mean_array(self._uv[1], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
+        if weighted:
+            thk_markers = (e3['fill'], e3['missing'])
+            u, hu, fill = self._time_mean_weighted_arrays(self._uv[0], self._uv_markers, e3['arrays'][0], thk_markers, t0, t1)
+            v, hv, _ = self._time_mean_weighted_arrays(self._uv[1], self._uv_markers, e3['arrays'][1], thk_markers, t0, t1)
+        else:
+            u, fill = self._time_mean_array(self._uv[0], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
+            v, _ = self._time_mean_array(self._uv[1], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
         mean = Field.fromArrays(self._bounds[0], self._bounds[1], self.bounds_depth, u, v, self._polylines, self.sverdrup,
                                 fill_value=fill, **self._build_kw)
 
@@ -996,7 +1070,9 @@ class Field(object):
             mean.setClassEdges(self._class_edges)
         if getattr(self, '_joint_edges', None) is not None:
             mean.setJointClassEdges(*self._joint_edges)
-        if e3 is not None:
+        if weighted:
+            mean.setCellThickness(hu, hv)       # the mean thicknesses: static, float64, in HBM, no markers
+        elif e3 is not None:
             dt = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
             with numpy.errstate(over='ignore'):
                 marks = [none_if_nan(float(dt.type(m))) if m == m else None for m in (e3['fill'], e3['missing'])]
@@ -1017,11 +1093,16 @@ class Field(object):
             a = host
         return numpy.ascontiguousarray(a, dtype=numpy.float64)
 
-    def meanEddyTracerTransport(self, steps=None):
+    def meanEddyTracerTransport(self, steps=None, thicknessWeighted=False):
         """The mean tracer transport of the steps [t0, t1) (steps=None: all; setTracer first) split in time, for the transect
         totals: 'total' = the float64 mean over the steps of the computeTracerFlux totals; 'mean' = computeTracerFlux(0) of
         timeMean(steps), the transport of the mean tracer by the mean flow; 'eddy' = total - mean, the part <u' tau'> carried
-        by the correlation of the fluctuations; 'meanField' = that Field, for its profile, class and decomposition calls."""
+        by the correlation of the fluctuations; 'meanField' = that Field, for its profile, class and decomposition calls.
+        thicknessWeighted=True (a time-varying cell thickness: z* / variable-volume output) is passed on to timeMean: 'total'
+        is computed with the thickness of every step as before, 'mean' is the transport of the time-mean tracer by the
+        time-mean VOLUME FLUX (mean thickness x thickness-weighted mean velocity), and 'eddy' is everything else -- the
+        correlation of the tracer with the volume flux, which includes the tracer-thickness covariance, because there is no
+        e3t to weight the tracer mean with."""
         if getattr(self, '_tracer', None) is None:
             raise RuntimeError('ERROR: call setTracer first')
         t0, t1 = self._step_range(steps)
@@ -1030,7 +1111,7 @@ class Field(object):
         else:
             rows = numpy.array([self.computeTracerFlux(t)[0] for t in range(t0, t1)])
         total = numpy.asarray(rows, dtype=numpy.float64).sum(axis=0) / float(t1 - t0)
-        meanField = self.timeMean(steps)
+        meanField = self.timeMean(steps, thicknessWeighted)
         mean = numpy.array(meanField.computeTracerFlux(0)[0], dtype=numpy.float64)
         return dict(total=total, mean=mean, eddy=total - mean, meanField=meanField)
 

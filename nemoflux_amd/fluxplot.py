@@ -16,6 +16,7 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
+    ... --tracer thetao --eddy --cell-thickness --thickness-weighted   (the same for z* output: thickness-weighted mean flow)
     ... --gross [--tracer thetao] [--zrange 0,700] (inflow, outflow and net of every transect; what they carry, their mean thetao)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
@@ -154,13 +155,15 @@ def decomposeSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', t
 EDDY_PARTS = ('total', 'mean', 'eddy')
 
 
-def eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None):
+def eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None,
+               thicknessWeighted=False):
     """(3, ntransect): the mean over all time steps of the transport of the variable `tracer` of tracerFile (default: the T
     file), the transport of the time-mean tracer by the time-mean flow, and their difference, the eddy part (EDDY_PARTS;
-    Field.meanEddyTracerTransport), and the Field."""
+    Field.meanEddyTracerTransport), and the Field.  thicknessWeighted: the mean flow of a time-varying cell thickness, the
+    mean thickness times the thickness-weighted mean velocity."""
     fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
-    d = fld.meanEddyTracerTransport()
+    d = fld.meanEddyTracerTransport(thicknessWeighted=thicknessWeighted)
     return numpy.array([d[k] for k in EDDY_PARTS]).reshape(len(EDDY_PARTS), len(lonLatZPoints)), fld
 
 
@@ -212,6 +215,13 @@ def checkEddyArgs(eddy=False, tracer='', classes='', levels=False, zrange='', sh
         if on:
             raise RuntimeError(f'ERROR: --eddy and {opt} cannot be combined: --eddy writes the time-mean transport of --tracer, '
                                f'its mean-flow part and its eddy part as CSV only')
+
+
+def checkThicknessWeightedArgs(thicknessWeighted=False, eddy=False, cellThickness=False):
+    """the --thickness-weighted option of the command line: refused combinations raise RuntimeError"""
+    if thicknessWeighted and not (eddy and cellThickness):
+        raise RuntimeError('ERROR: --thickness-weighted needs --eddy and --cell-thickness: it splits the mean transport of '
+                           '--tracer with the thickness-weighted mean flow of time-varying layer thicknesses (z*)')
 
 
 def checkDecomposeArgs(decompose=False, tracer='', classes='', levels=False, zrange='', show=False):
@@ -365,7 +375,8 @@ def parseZRange(zrange):
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
-         eddy=False, tracer2='', tracer2File='', classes2='', gross=False):
+         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False):
+    checkThicknessWeightedArgs(thicknessWeighted, eddy, cellThickness)
     checkGrossArgs(gross, classes, levels, decompose, eddy, show)
     checkJointClassArgs(classes2, tracer2, tracer2File, tracer, classes, carry, levels, zrange, show, eddy, decompose)
     checkEddyArgs(eddy, tracer, classes, levels, zrange, show, decompose)
@@ -396,7 +407,8 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         _emit(title + '\n' + '\n'.join(lines) + '\n', output)
         return totals
     if eddy:
-        totals, fld = eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct)
+        totals, fld = eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct,
+                                 thicknessWeighted)
         totals = totals * float(tracerScale)
         unit = f'{tracer} x {unit}' + (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '')
         lines = ['part,' + ','.join(names)]
@@ -551,6 +563,10 @@ if __name__ == '__main__':
     ap.add_argument('--cell-thickness', dest='cellThickness', action='store_true',
                     help='integrate with per-cell layer thicknesses (partial steps, z*) read from the U and V files instead of '
                          'deptht_bounds; with the plain series, --zrange, --levels (without --tracer) and --tracer NAME')
+    ap.add_argument('--thickness-weighted', dest='thicknessWeighted', action='store_true',
+                    help='with --eddy and --cell-thickness, for thicknesses that change with time (z*, variable volume): the '
+                         'mean flow is the mean thickness times the thickness-weighted mean velocity, so that it carries the '
+                         'mean volume transport')
     ap.add_argument('--e3u', default='', metavar='NAME', help='with --cell-thickness: the thickness at U points (default e3u)')
     ap.add_argument('--e3v', default='', metavar='NAME', help='with --cell-thickness: the thickness at V points (default e3v)')
     ap.add_argument('--e3-file-u', dest='e3FileU', default='', metavar='FILE', help='read --e3u from FILE instead of the U file')
