@@ -84,9 +84,40 @@ int field_tuning_set(const char *name, int value)
 }  // namespace nf
 
 // =============================================================================================== Level 2
+// One input series of a Field: an (nt, nz, ny, nx) array of the dtype of uo / vo that lives in HBM or on the host (a file-backed
+// one arrives as a host array, one step at a time), or a pair that differs only in the pointer: uo / vo, e3u / e3v.  A tracer
+// uses p[0] and stage[0] alone.
+struct Series {
+    const void *p[2] = {nullptr, nullptr};
+    long nt = 0;
+    int dtype = NF_F64, on_device = 1;
+    double fill = std::numeric_limits<double>::quiet_NaN();
+    double fill2 = std::numeric_limits<double>::quiet_NaN();   // the second marker (missing_value)
+    // host-resident arrays: the owned levels of one step (field_stage).  Sized with the element size of uo / vo for every
+    // series; they only grow and survive a re-set of their series.
+    DevArray<char> stage[2];
+};
+
+// Class edges on the host, uploaded by the next compute after a change
+struct EdgeSet {
+    std::vector<double> host;
+    bool stale = false;
+    DevArray<double> dev;   // `cap` doubles
+    int upload(size_t cap, hipStream_t s)
+    {
+        if (!stale) return NF_OK;
+        // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
+        NF_TRY(dev.reserve(cap));
+        NF_HIP(hipMemcpyAsync(dev.get(), host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, s));
+        NF_HIP(hipStreamSynchronize(s));
+        stale = false;
+        return NF_OK;
+    }
+};
+
 struct nf_field {
     hipStream_t stream = nullptr;
-    long ny = 0, nx = 0, ncell = 0, nz = 0, nt = 0;
+    long ny = 0, nx = 0, ncell = 0, nz = 0;
     // everything sized by the grid: allocated by set_bounds (and on demand after it), dropped together by field_free_geometry
     struct Geometry {
         DevArray<double> xy, arc4, arcE, arcN;
@@ -105,12 +136,8 @@ struct nf_field {
     } geo;
     double box[4] = {0, 0, 0, 0};
     DevArray<double> thick;
-    // velocity fields
-    const void *u = nullptr, *v = nullptr;
-    int uv_dtype = NF_F64, uv_on_device = 1;
-    double fill = std::numeric_limits<double>::quiet_NaN();
-    double fill2 = std::numeric_limits<double>::quiet_NaN();   // nf_field_set_missing_value
-    DevArray<char> stage_u, stage_v;   // host-resident fields: the slabs of one step, grown to the largest step staged
+    // velocity fields uo / vo (nf_field_set_uv, nf_field_set_missing_value): their nt and dtype are the Field's
+    Series uv;
     int sverdrup = 0;
     long s_begin = 0, s_end = -1;
     // compact resident mode (nf_field_set_compact): the flux kernel stores only eU and eV; the neighbour-copy planes and
@@ -133,32 +160,18 @@ struct nf_field {
     DevArray<double> row;   // the result of a synchronous call (field_sync): a row, or the (nz, row_length) block of a profile
     // tracer at T-points (nf_field_set_tracer*): same (nt, nz, ny, nx) and dtype as uo / vo; none of its setters changes
     // `version`, and nothing of it enters a captured pass
-    const void *tau = nullptr;
-    long tau_nt = 0;
-    int tau_dtype = NF_F64, tau_on_device = 1;
-    double tau_fill = std::numeric_limits<double>::quiet_NaN();
-    double tau_fill2 = std::numeric_limits<double>::quiet_NaN();
+    Series tau;
     double tau_ref = 0.0;
     int tau_wrap = 1;
-    DevArray<char> stage_tau;   // host-resident tracer: the owned levels of one step
     // class tracer at T-points (nf_field_set_class_tracer*): the field whose classes the class calls bin by; nullptr: the
     // tracer above.  No reference; the wrap rule is the tracer's.  Its setters change neither `version` nor a captured pass.
-    const void *sig = nullptr;
-    long sig_nt = 0;
-    int sig_dtype = NF_F64, sig_on_device = 1;
-    double sig_fill = std::numeric_limits<double>::quiet_NaN();
-    double sig_fill2 = std::numeric_limits<double>::quiet_NaN();
-    DevArray<char> stage_sig;   // host-resident class tracer: the owned levels of one step, sized in bytes like stage_tau
-    // per-cell layer thicknesses (nf_field_set_cell_thickness): e3u / e3v of (e3_nt, nz, ny, nx), e3_nt == 1 (static) or nt, in
+    Series sig;
+    // per-cell layer thicknesses (nf_field_set_cell_thickness): e3u / e3v of (e3.nt, nz, ny, nx), e3.nt == 1 (static) or nt, in
     // the dtype of uo / vo; nullptr: the per-level thickness above.  A static host array is uploaded once into e3?_static
     // and counts as resident from then on; a time-varying host array is staged per step, owned levels only.  Setting or
     // clearing them changes `version`.
-    const void *e3u = nullptr, *e3v = nullptr;
-    long e3_nt = 0;
-    int e3_dtype = NF_F64, e3_on_device = 1;
-    double e3_fill = std::numeric_limits<double>::quiet_NaN();
-    double e3_fill2 = std::numeric_limits<double>::quiet_NaN();   // nf_field_set_cell_thickness_missing_value
-    DevArray<char> e3u_static, e3v_static, stage_e3u, stage_e3v;
+    Series e3;
+    DevArray<char> e3u_static, e3v_static;
     // the (nz, ny, nx) in force when e3?_static were uploaded: the upload belongs to that shape (field_cell_thick_current)
     long e3_static_nz = 0, e3_static_ny = 0, e3_static_nx = 0;
     // tracer profile (nf_field_compute_tracer_profile): the run sums of one chunk (ws.nrec * tracer_profile_chunk(dtype))
@@ -167,21 +180,17 @@ struct nf_field {
     DevArray<double> area_scratch;
     // gross profile (nf_field_compute_gross_profile): the run sums of one chunk, two values per level (ws.nrec * 2 * gross_chunk)
     DevArray<double> gross_scratch;
-    // class transport (nf_field_set_class_edges): the edges on the host, uploaded by the next compute after a change; the run
-    // sums of one window of rows (ws.nrec * window, allocated on first use, dropped with the weights)
-    std::vector<double> class_edges;
-    bool class_edges_stale = false;
-    DevArray<double> class_edges_dev;
+    // class transport (nf_field_set_class_edges): the edges; the run sums of one window of rows (ws.nrec * window, allocated on
+    // first use, dropped with the weights)
+    EdgeSet class_edges;
     DevArray<double> class_scratch;
     // joint class transport (nf_field_set_joint_class_edges): state of its own, the 1-D forms do not see it.  The edges of
-    // axis A then axis B on the host, uploaded by the next compute after a change.  The term table (40 bytes per record and
+    // axis A then axis B in one set.  The term table (40 bytes per record and
     // owned level), the block flags and the run sums of one window are allocated on first use, grown when the records, the
     // owned levels or the rows ask for more -- their layout is taken from the call's own sizes, never from an earlier one's
     // -- and dropped with the weights.
-    std::vector<double> joint_edges;
+    EdgeSet joint_edges;
     int joint_na = 0, joint_nb = 0;
-    bool joint_edges_stale = false;
-    DevArray<double> joint_edges_dev;
     DevArray<char> joint_table;
     DevArray<unsigned> joint_flags;
     DevArray<double> joint_scratch;
@@ -335,7 +344,7 @@ static int field_row_length(const nf_field *f) { return (int)field_transects(f).
 // compared, not the byte counts: 2 x 100 and 4 x 50 cells are as many bytes.
 static int field_cell_thick_current(const nf_field *f, const char *what)
 {
-    if (!f->e3u || !f->e3u_static.get()) return NF_OK;
+    if (!f->e3.p[0] || !f->e3u_static.get()) return NF_OK;
     if (f->e3_static_nz == f->nz && f->e3_static_ny == f->ny && f->e3_static_nx == f->nx) return NF_OK;
     char buf[320];
     snprintf(buf, sizeof buf,
@@ -349,7 +358,7 @@ static int field_cell_thick_current(const nf_field *f, const char *what)
 // the state every per-step computation needs; `what` prefixes the message ("compute", "compute_profile", ...)
 static int field_ready(const nf_field *f, const char *what, bool weights)
 {
-    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->u && f->v, NF_ERR_STATE,
+    NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->uv.p[0] && f->uv.p[1], NF_ERR_STATE,
                std::string(what) + ": set_bounds, set_thickness and set_uv first");
     NF_REQUIRE(!weights || f->weights_built, NF_ERR_STATE, std::string(what) + ": build_weights first");
     return field_cell_thick_current(f, what);
@@ -358,7 +367,7 @@ static int field_ready(const nf_field *f, const char *what, bool weights)
 // the end of the slabs [s_begin, s_end) of the nt * nz that this rank owns (set_slab_range; s_end < 0: up to the last one)
 static long field_slab_end(const nf_field *f)
 {
-    const long total = f->nt * f->nz;
+    const long total = f->uv.nt * f->nz;
     return f->s_end < 0 ? total : std::min(f->s_end, total);
 }
 
@@ -394,14 +403,15 @@ static PassSteps field_pass_steps(const nf_field *f)
 
 // Step t of a (nt, nz, ncell) array of the field dtype as the kernels read it: a device-resident array in place, a
 // host-resident one staged into `buf` -- the owned levels only, at their place in one step (PCIe-inclusive path)
-static int field_stage(nf_field *f, const void *src, int on_device, long t, Levels lv, DevArray<char> *buf, const void **out)
+static int field_stage(nf_field *f, Series &s, int which, long t, Levels lv, const void **out)
 {
-    const size_t es = elem_size(f->uv_dtype), step_bytes = (size_t)f->nz * f->ncell * es;
-    const char *base = (const char *)src + (size_t)t * step_bytes;
-    if (on_device) {
+    const size_t es = elem_size(f->uv.dtype), step_bytes = (size_t)f->nz * f->ncell * es;
+    const char *base = (const char *)s.p[which] + (size_t)t * step_bytes;
+    if (s.on_device) {
         *out = base;
         return NF_OK;
     }
+    DevArray<char> *buf = &s.stage[which];
     NF_TRY(buf->reserve(step_bytes));
     const size_t off = (size_t)lv.z0 * f->ncell * es, len = (size_t)(lv.z1 - lv.z0) * f->ncell * es;
     NF_HIP(hipMemcpyAsync(buf->get() + off, base + off, len, hipMemcpyHostToDevice, f->stream));
@@ -412,9 +422,9 @@ static int field_stage(nf_field *f, const void *src, int on_device, long t, Leve
 // what the per-step kernels read of step t: uo / vo (staged when host-resident), the grid and the levels lv
 static int field_step_input(nf_field *f, long t, Levels lv, StepInput *in)
 {
-    NF_TRY(field_stage(f, f->u, f->uv_on_device, t, lv, &f->stage_u, &in->u));
-    NF_TRY(field_stage(f, f->v, f->uv_on_device, t, lv, &f->stage_v, &in->v));
-    in->dtype = f->uv_dtype;
+    NF_TRY(field_stage(f, f->uv, 0, t, lv, &in->u));
+    NF_TRY(field_stage(f, f->uv, 1, t, lv, &in->v));
+    in->dtype = f->uv.dtype;
     in->ncell = f->ncell;
     in->ny = f->ny;
     in->nx = f->nx;
@@ -423,10 +433,32 @@ static int field_step_input(nf_field *f, long t, Levels lv, StepInput *in)
     in->thickness = f->thick.get();
     in->arcE = f->geo.arcE.get();
     in->arcN = f->geo.arcN.get();
-    in->fill = f->fill;
-    in->fill2 = f->fill2;
+    in->fill = f->uv.fill;
+    in->fill2 = f->uv.fill2;
     in->scale = kEarthRadiusSv / 1.e6;   // field.py:226
     in->sverdrup = f->sverdrup;
+    return NF_OK;
+}
+
+// The "matches uo/vo" rule of a series that is read beside them: their dtype, and their nt (kStaticOk: or one step).  w
+// prefixes the message and `noun` names the series.  The setters word some of it in their own way: kNameDtypes, kCountSteps.
+enum : int { kStaticOk = 1, kNameDtypes = 2, kCountSteps = 4 };
+static int field_matches_uv(const nf_field *f, int dtype, long nt, const std::string &w, const char *noun, int how = 0)
+{
+    const std::string the = w + ": the " + noun;
+    char buf[160];
+    if (dtype != f->uv.dtype) {
+        if (!(how & kNameDtypes)) NF_REQUIRE(false, NF_ERR_ARG, the + "'s dtype differs from the dtype of uo/vo");
+        snprintf(buf, sizeof buf, "'s dtype is %s, uo/vo are %s", dtype == NF_F32 ? "float32" : "float64",
+                 f->uv.dtype == NF_F32 ? "float32" : "float64");
+        NF_REQUIRE(false, NF_ERR_ARG, the + buf);
+    }
+    if (nt != f->uv.nt && !((how & kStaticOk) && nt == 1)) {
+        if (!(how & kCountSteps)) NF_REQUIRE(false, NF_ERR_ARG, the + "'s nt differs from the nt of uo/vo");
+        snprintf(buf, sizeof buf, (how & kStaticOk) ? " has nt = %ld time steps, need 1 (static) or the %ld of uo/vo"
+                                                    : " has nt = %ld time steps, uo/vo have %ld", nt, f->uv.nt);
+        NF_REQUIRE(false, NF_ERR_ARG, the + buf);
+    }
     return NF_OK;
 }
 
@@ -435,21 +467,20 @@ static int field_step_input(nf_field *f, long t, Levels lv, StepInput *in)
 static int field_cell_thick(nf_field *f, long t, Levels lv, CellThick *th)
 {
     *th = CellThick{};
-    if (!f->e3u) return NF_OK;
-    NF_REQUIRE(f->e3_dtype == f->uv_dtype, NF_ERR_ARG, "compute: the cell thickness's dtype differs from the dtype of uo/vo");
-    NF_REQUIRE(f->e3_nt == 1 || f->e3_nt == f->nt, NF_ERR_ARG, "compute: the cell thickness's nt differs from the nt of uo/vo");
-    const long tt = f->e3_nt == 1 ? 0 : t;
-    NF_TRY(field_stage(f, f->e3u, f->e3_on_device, tt, lv, &f->stage_e3u, &th->e3u));
-    NF_TRY(field_stage(f, f->e3v, f->e3_on_device, tt, lv, &f->stage_e3v, &th->e3v));
-    th->fill = f->e3_fill;
-    th->fill2 = f->e3_fill2;
+    if (!f->e3.p[0]) return NF_OK;
+    NF_TRY(field_matches_uv(f, f->e3.dtype, f->e3.nt, "compute", "cell thickness", kStaticOk));
+    const long tt = f->e3.nt == 1 ? 0 : t;
+    NF_TRY(field_stage(f, f->e3, 0, tt, lv, &th->e3u));
+    NF_TRY(field_stage(f, f->e3, 1, tt, lv, &th->e3v));
+    th->fill = f->e3.fill;
+    th->fill2 = f->e3.fill2;
     return NF_OK;
 }
 
 // the forms that do not take per-cell thicknesses yet: refused while one is set
 static int field_no_cell_thick(const nf_field *f, const char *what)
 {
-    NF_REQUIRE(!f->e3u, NF_ERR_STATE,
+    NF_REQUIRE(!f->e3.p[0], NF_ERR_STATE,
                std::string(what) + ": this form does not take per-cell thicknesses yet and a cell thickness is set; "
                                    "nf_field_set_cell_thickness(NULL) clears it");
     return NF_OK;
@@ -499,7 +530,7 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     const int rowlen = field_row_length(f);
     const bool reduce = row_dev && rowlen > 0 && !form.to_uv2;
     NF_TRY(field_ready(f, "compute", reduce));
-    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, "compute: time index out of range");
+    NF_REQUIRE(t >= 0 && t < f->uv.nt, NF_ERR_ARG, "compute: time index out of range");
     const Levels lv = field_levels(f, t);
     if (lv.z1 <= lv.z0) {  // this rank owns no slab of step t: contributes zeros
         if (row_dev && rowlen > 0) NF_HIP(hipMemsetAsync(row_dev, 0, sizeof(double) * rowlen, f->stream));
@@ -541,27 +572,25 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
 static int field_raw_step_begin(nf_field *f, const char *what, long t, int tracer, double *rows_dev, size_t nrows, Levels *lv)
 {
     const std::string w(what);
-    NF_REQUIRE(t >= 0 && t < f->nt, NF_ERR_ARG, w + ": time index out of range");
-    NF_REQUIRE(!tracer || f->tau_dtype == f->uv_dtype, NF_ERR_ARG, w + ": the tracer's dtype differs from the dtype of uo/vo");
-    NF_REQUIRE(!tracer || f->tau_nt == f->nt, NF_ERR_ARG, w + ": the tracer's nt differs from the nt of uo/vo");
-    if (tracer == 2 && f->sig) {   // a call that reads the class field
-        NF_REQUIRE(f->sig_dtype == f->uv_dtype, NF_ERR_ARG, w + ": the class tracer's dtype differs from the dtype of uo/vo");
-        NF_REQUIRE(f->sig_nt == f->nt, NF_ERR_ARG, w + ": the class tracer's nt differs from the nt of uo/vo");
-    }
+    NF_REQUIRE(t >= 0 && t < f->uv.nt, NF_ERR_ARG, w + ": time index out of range");
+    if (tracer) NF_TRY(field_matches_uv(f, f->tau.dtype, f->tau.nt, w, "tracer"));
+    if (tracer == 2 && f->sig.p[0])   // a call that reads the class field
+        NF_TRY(field_matches_uv(f, f->sig.dtype, f->sig.nt, w, "class tracer"));
     const size_t rowlen = field_row_length(f);
     *lv = rowlen > 0 ? field_levels(f, t) : Levels{};
     if (rowlen > 0 && lv->z1 <= lv->z0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * nrows, f->stream));
     return NF_OK;
 }
 
-// the tracer of step t (staged when host-resident), its markers and wrap rule: the members TracerArgs and ClassArgs share
-template <typename Args>
-static int field_tracer_input(nf_field *f, long t, Levels lv, Args *a)
+// Step t of the tracer or the class tracer (staged when host-resident) with its markers.  The reference is the tracer's -- the
+// class tracer has none -- and the wrap rule is the tracer's for both.
+static int field_tracer_input(nf_field *f, Series &s, long t, Levels lv, TracerIn *in)
 {
-    NF_TRY(field_stage(f, f->tau, f->tau_on_device, t, lv, &f->stage_tau, &a->tau));
-    a->tfill = f->tau_fill;
-    a->tfill2 = f->tau_fill2;
-    a->wrap_x = f->tau_wrap;
+    NF_TRY(field_stage(f, s, 0, t, lv, &in->tau));
+    in->fill = s.fill;
+    in->fill2 = s.fill2;
+    in->ref = &s == &f->tau ? f->tau_ref : 0.0;
+    in->wrap_x = f->tau_wrap;
     return NF_OK;
 }
 
@@ -581,12 +610,11 @@ static int field_profile_async(nf_field *f, long t, double *prof_dev, bool trace
         NF_HIP(hipMemsetAsync(prof_dev + (size_t)lv.z1 * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nz - lv.z1),
                               f->stream));
     DevArray<double> &scratch = tracer ? f->tprof_scratch : f->prof_scratch;
-    NF_TRY(scratch.reserve((size_t)f->ws.nrec * (tracer ? tracer_profile_chunk(f->uv_dtype) : kProfileChunk)));
+    NF_TRY(scratch.reserve((size_t)f->ws.nrec * (tracer ? tracer_profile_chunk(f->uv.dtype) : kProfileChunk)));
     ProfileArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
     if (tracer) {
-        NF_TRY(field_tracer_input(f, t, lv, &a));
-        a.ref = f->tau_ref;
+        NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
     } else {
         NF_TRY(field_cell_thick(f, t, lv, &a.th));
     }
@@ -608,12 +636,11 @@ static int field_area_async(nf_field *f, long t, double *rows_dev)
     const size_t rowlen = field_row_length(f);
     if (lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in both blocks
         NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * 2 * (size_t)f->nz, f->stream));
-    NF_TRY(f->area_scratch.reserve((size_t)f->ws.nrec * 2 * area_chunk_now(f->uv_dtype)));
+    NF_TRY(f->area_scratch.reserve((size_t)f->ws.nrec * 2 * area_chunk_now(f->uv.dtype)));
     AreaArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, t, lv, &a));
+    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
-    a.ref = f->tau_ref;
     a.tr = field_transects(f);
     a.scratch = f->area_scratch.get();
     a.scratch_len = f->area_scratch.size();
@@ -634,12 +661,11 @@ static int field_gross_async(nf_field *f, long t, bool carry, double *rows_dev)
     const size_t rowlen = field_row_length(f);
     if (lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in both blocks
         NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * 2 * (size_t)f->nz, f->stream));
-    NF_TRY(f->gross_scratch.reserve((size_t)f->ws.nrec * 2 * gross_chunk_now(f->uv_dtype, carry, f->e3u != nullptr)));
+    NF_TRY(f->gross_scratch.reserve((size_t)f->ws.nrec * 2 * gross_chunk_now(f->uv.dtype, carry, f->e3.p[0] != nullptr)));
     GrossArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    if (carry) NF_TRY(field_tracer_input(f, t, lv, &a));
+    if (carry) NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
-    a.ref = f->tau_ref;
     a.tr = field_transects(f);
     a.scratch = f->gross_scratch.get();
     a.scratch_len = f->gross_scratch.size();
@@ -659,10 +685,9 @@ static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
     if (lv.z1 <= lv.z0) return NF_OK;
     TracerArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, t, lv, &a));
+    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
     NF_TRY(f->geo.tr_planes.reserve((size_t)f->ncell * 2));
-    a.ref = f->tau_ref;
     a.planes = f->geo.tr_planes.get();
     NF_TRY(launch_tracer_flux(a, f->stream));
     // K3 reads the two signed members of [4][ncell] planes at +ncell and +2 ncell: the tracer planes sit at +ncell
@@ -672,8 +697,8 @@ static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
 // the calls of the class transport need a tracer and class edges: checked before a device is needed
 static int field_class_ready(const nf_field *f, const char *what)
 {
-    NF_REQUIRE(f->tau, NF_ERR_STATE, std::string(what) + ": set_tracer first");
-    NF_REQUIRE(!f->class_edges.empty(), NF_ERR_STATE, std::string(what) + ": set_class_edges first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, std::string(what) + ": set_tracer first");
+    NF_REQUIRE(!f->class_edges.host.empty(), NF_ERR_STATE, std::string(what) + ": set_class_edges first");
     return field_ready(f, what, true);
 }
 
@@ -684,36 +709,20 @@ static int field_class_ready(const nf_field *f, const char *what)
 // of the volume (nf_field_compute_class_tracer_transport).
 static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool carry = false)
 {
-    const int nedges = (int)f->class_edges.size();
+    const int nedges = (int)f->class_edges.host.size();
     Levels lv;
     NF_TRY(field_raw_step_begin(f, carry ? "compute_class_tracer_transport" : "compute_class_transport", t, 2, rows_dev,
                                 (size_t)nedges + 2, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
-    if (f->class_edges_stale) {
-        // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
-        NF_TRY(f->class_edges_dev.reserve((size_t)kMaxClassEdges));
-        NF_HIP(hipMemcpyAsync(f->class_edges_dev.get(), f->class_edges.data(), sizeof(double) * nedges, hipMemcpyHostToDevice,
-                              f->stream));
-        NF_HIP(hipStreamSynchronize(f->stream));
-        f->class_edges_stale = false;
-    }
+    NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
     const int window = g_class_window;
     NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
     ClassArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, t, lv, &a));
-    if (carry) {   // the tracer is carried ...
-        a.carry = a.tau;
-        a.cfill = a.tfill;
-        a.cfill2 = a.tfill2;
-        a.ref = f->tau_ref;
-    }
-    if (f->sig) {   // ... and binned by the class tracer
-        NF_TRY(field_stage(f, f->sig, f->sig_on_device, t, lv, &f->stage_sig, &a.tau));
-        a.tfill = f->sig_fill;
-        a.tfill2 = f->sig_fill2;
-    }
-    a.edges = f->class_edges_dev.get();
+    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.cls));
+    if (carry) a.carry = a.cls;                                                    // the tracer is carried ...
+    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.cls));   // ... and binned by the class tracer
+    a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
     a.window = window;
     a.tr = field_transects(f);
@@ -726,9 +735,9 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool ca
 // the calls of the joint class transport need both tracers and the joint edges: checked before a device is needed
 static int field_joint_ready(const nf_field *f, const char *what)
 {
-    NF_REQUIRE(f->tau, NF_ERR_STATE, std::string(what) + ": set_tracer first");
-    NF_REQUIRE(f->sig, NF_ERR_STATE, std::string(what) + ": set_class_tracer first");
-    NF_REQUIRE(!f->joint_edges.empty(), NF_ERR_STATE, std::string(what) + ": set_joint_class_edges first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, std::string(what) + ": set_tracer first");
+    NF_REQUIRE(f->sig.p[0], NF_ERR_STATE, std::string(what) + ": set_class_tracer first");
+    NF_REQUIRE(!f->joint_edges.host.empty(), NF_ERR_STATE, std::string(what) + ": set_joint_class_edges first");
     NF_TRY(field_ready(f, what, true));
     return field_no_cell_thick(f, what);
 }
@@ -745,14 +754,7 @@ static int field_joint_step_async(nf_field *f, long t, bool carry, double *rows_
     Levels lv;
     NF_TRY(field_raw_step_begin(f, "compute_joint_class_transport", t, 2, rows_dev, nrows, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
-    if (f->joint_edges_stale) {
-        // the host copy may change again before an asynchronous copy from pageable memory has read it: wait for this one
-        NF_TRY(f->joint_edges_dev.reserve(2 * (size_t)kMaxClassEdges));
-        NF_HIP(hipMemcpyAsync(f->joint_edges_dev.get(), f->joint_edges.data(), sizeof(double) * f->joint_edges.size(),
-                              hipMemcpyHostToDevice, f->stream));
-        NF_HIP(hipStreamSynchronize(f->stream));
-        f->joint_edges_stale = false;
-    }
+    NF_TRY(f->joint_edges.upload(2 * (size_t)kMaxClassEdges, f->stream));
     const int window = g_joint_window;
     const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
     const size_t table_bytes = kJointEntryBytes * nrec * (size_t)(lv.z1 - lv.z0);
@@ -771,13 +773,10 @@ static int field_joint_step_async(nf_field *f, long t, bool carry, double *rows_
     NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
     JointArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, t, lv, &a));
-    NF_TRY(field_stage(f, f->sig, f->sig_on_device, t, lv, &f->stage_sig, &a.sig));
-    a.sfill = f->sig_fill;
-    a.sfill2 = f->sig_fill2;
-    a.ref = f->tau_ref;
+    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.ta));
+    NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.tb));
     a.carry = carry ? 1 : 0;
-    a.edges = f->joint_edges_dev.get();
+    a.edges = f->joint_edges.dev.get();
     a.na = f->joint_na;
     a.nb = f->joint_nb;
     a.window = window;
@@ -821,8 +820,8 @@ static bool field_can_batch(const nf_field *f)
     // kernel for its few wavefronts) is as fast or faster -- 1440 x 1021: 700 vs 733 us per 4-step pass at float32, 1166 vs
     // 1144 at float64; 2160 x 1080: 1035 vs 1187 and 1863 vs 1928 (tools/size_sweep.py, profiles/r04_size_sweep.txt)
     // (the all-steps-in-one-launch form exists for K1 only: off while a cell thickness is set)
-    return g_batch_steps && !f->e3u && f->uv_on_device && f->nt >= 2 && f->nt < 65536 && f->nt * f->ncell <= batch_cell_steps() &&
-           f->ncell <= (1l << 20) && f->weights_built;
+    return g_batch_steps && !f->e3.p[0] && f->uv.on_device && f->uv.nt >= 2 && f->uv.nt < 65536 &&
+           f->uv.nt * f->ncell <= batch_cell_steps() && f->ncell <= (1l << 20) && f->weights_built;
 }
 
 // the per-step pass reduces its whole steps in pairs: needs the record form of K3 (the unique-edge entries have no pair
@@ -832,13 +831,13 @@ static bool field_pass_pairs(const nf_field *f)
     if (!g_k3_pairs || integral_uses_edges() || !f->geo.uv2.get() || !f->weights_built) return false;
     // every step starts 16-byte aligned when the first one does: resident fields with a step size that is a multiple of
     // 16 bytes, or steps staged into the (allocation-aligned) staging buffers
-    const size_t step_bytes = (size_t)f->nz * f->ncell * elem_size(f->uv_dtype);
+    const size_t step_bytes = (size_t)f->nz * f->ncell * elem_size(f->uv.dtype);
     FluxArgs a{};
-    a.u = f->uv_on_device ? f->u : nullptr;
-    a.v = f->uv_on_device ? f->v : nullptr;
-    a.dtype = f->uv_dtype;
+    a.u = f->uv.on_device ? f->uv.p[0] : nullptr;
+    a.v = f->uv.on_device ? f->uv.p[1] : nullptr;
+    a.dtype = f->uv.dtype;
     a.ncell = f->ncell;
-    return flux_supports_signed_only(a) && (!f->uv_on_device || step_bytes % 16 == 0);
+    return flux_supports_signed_only(a) && (!f->uv.on_device || step_bytes % 16 == 0);
 }
 
 // device memory a per-step pass may need, allocated before the pass is launched or captured: the second signed planes of
@@ -863,8 +862,9 @@ static int field_zero_unowned_rows(nf_field *f, double *rows_dev)
     const PassSteps p = field_pass_steps(f);
     if (rowlen <= 0) return NF_OK;
     if (p.ta > 0) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * (size_t)p.ta, f->stream));
-    if (p.tb < f->nt)
-        NF_HIP(hipMemsetAsync(rows_dev + (size_t)p.tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->nt - p.tb), f->stream));
+    if (p.tb < f->uv.nt)
+        NF_HIP(hipMemsetAsync(rows_dev + (size_t)p.tb * rowlen, 0, sizeof(double) * rowlen * (size_t)(f->uv.nt - p.tb),
+                              f->stream));
     return NF_OK;
 }
 
@@ -903,19 +903,19 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
     const int rowlen = field_row_length(f);
     const size_t n = (size_t)f->ncell;
     nf_field::Geometry &g = f->geo;
-    if (g.batch_steps != f->nt) {
-        NF_TRY(g.iVb.alloc(n * 4 * f->nt));
-        NF_TRY(g.absb.alloc(n * 2 * f->nt));
-        NF_TRY(g.zr.alloc((size_t)2 * f->nt));
+    if (g.batch_steps != f->uv.nt) {
+        NF_TRY(g.iVb.alloc(n * 4 * f->uv.nt));
+        NF_TRY(g.absb.alloc(n * 2 * f->uv.nt));
+        NF_TRY(g.zr.alloc((size_t)2 * f->uv.nt));
         // south slots of row 0 are never written (field.py:219): every step's planes start as zeros
-        NF_HIP(hipMemsetAsync(g.iVb.get(), 0, sizeof(double) * n * 4 * f->nt, f->stream));
-        g.batch_steps = f->nt;
+        NF_HIP(hipMemsetAsync(g.iVb.get(), 0, sizeof(double) * n * 4 * f->uv.nt, f->stream));
+        g.batch_steps = f->uv.nt;
         g.batch_version = -1;
     }
     if (g.batch_version != f->version) {  // scratch follows the weight set, z ranges follow the slab ownership
-        NF_TRY(g.scratchb.alloc((size_t)std::max(f->ws.nrec, f->ws.nent) * f->nt));
-        std::vector<int> zr((size_t)2 * f->nt);
-        for (long t = 0; t < f->nt; ++t) {
+        NF_TRY(g.scratchb.alloc((size_t)std::max(f->ws.nrec, f->ws.nent) * f->uv.nt));
+        std::vector<int> zr((size_t)2 * f->uv.nt);
+        for (long t = 0; t < f->uv.nt; ++t) {
             const Levels lv = field_levels(f, t);
             zr[2 * t] = lv.z0;
             zr[2 * t + 1] = lv.z1;
@@ -930,18 +930,18 @@ static int field_all_steps_batched(nf_field *f, double *rows_dev)
     a.absU = g.absb.get();
     a.absV = g.absb.get() + f->ncell;
     a.maxbits = g.maxbits.get();
-    a.batch.nsteps = (int)f->nt;
+    a.batch.nsteps = (int)f->uv.nt;
     a.batch.in_stride = f->nz * f->ncell;
     a.batch.zr = g.zr.get();
     NF_TRY(field_launch_flux(f, a));
     if (rowlen > 0) {
-        NF_TRY(field_integral(f, g.iVb.get(), g.scratchb.get(), rows_dev, (int)f->nt, (long)(4 * n), rowlen));
+        NF_TRY(field_integral(f, g.iVb.get(), g.scratchb.get(), rows_dev, (int)f->uv.nt, (long)(4 * n), rowlen));
         NF_TRY(field_timed_k3_end(f));
     }
     // the resident single-step arrays keep their meaning: they hold the LAST step (what read_step returns)
-    NF_HIP(hipMemcpyAsync(g.iV.get(), g.iVb.get() + (size_t)(f->nt - 1) * 4 * n, sizeof(double) * 4 * n,
+    NF_HIP(hipMemcpyAsync(g.iV.get(), g.iVb.get() + (size_t)(f->uv.nt - 1) * 4 * n, sizeof(double) * 4 * n,
                           hipMemcpyDeviceToDevice, f->stream));
-    NF_HIP(hipMemcpyAsync(g.abs.get(), g.absb.get() + (size_t)(f->nt - 1) * 2 * n, sizeof(double) * 2 * n,
+    NF_HIP(hipMemcpyAsync(g.abs.get(), g.absb.get() + (size_t)(f->uv.nt - 1) * 2 * n, sizeof(double) * 2 * n,
                           hipMemcpyDeviceToDevice, f->stream));
     f->derived_stale = false;
     return NF_OK;
@@ -1051,12 +1051,12 @@ try {
     NF_REQUIRE(nt > 0, NF_ERR_ARG, "nf_field_set_uv: nt must be positive");
     NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_uv: dtype must be NF_F64/NF_F32");
     nf_field *f = *self;
-    f->u = u;
-    f->v = v;
-    f->nt = nt;
-    f->uv_dtype = dtype;
-    f->uv_on_device = on_device;
-    f->fill = fill_value;
+    f->uv.p[0] = u;
+    f->uv.p[1] = v;
+    f->uv.nt = nt;
+    f->uv.dtype = dtype;
+    f->uv.on_device = on_device;
+    f->uv.fill = fill_value;
     ++f->version;
     return NF_OK;
 }
@@ -1065,7 +1065,7 @@ NF_API_CATCH
 int nf_field_set_missing_value(nf_field **self, double missing_value)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_missing_value: null field");
-    (*self)->fill2 = missing_value;
+    (*self)->uv.fill2 = missing_value;
     ++(*self)->version;
     return NF_OK;
 }
@@ -1294,7 +1294,8 @@ try {
     NF_TRY(field_prepare_pass(f));   // allocations stay out of a graph capture
     // Replay a captured graph of the whole pass when nothing changed since it was captured.  Capture needs a real
     // (non-null) stream, resident fields (a cell thickness included), and no per-launch timing events.
-    const bool can_graph = g_use_graph && f->stream != nullptr && f->uv_on_device && (!f->e3u || f->e3_on_device) && !f->timing;
+    const bool can_graph =
+        g_use_graph && f->stream != nullptr && f->uv.on_device && (!f->e3.p[0] || f->e3.on_device) && !f->timing;
     if (can_graph && f->graph_exec && f->graph_rows == rows_dev && f->graph_version == field_pass_version(f)) {
         NF_TRY(field_zero_unowned_rows(f, rows_dev));
         NF_HIP(hipGraphLaunch(f->graph_exec, f->stream));
@@ -1353,18 +1354,13 @@ try {
     NF_REQUIRE(self && *self && tracer, NF_ERR_ARG, "nf_field_set_tracer: null argument");
     NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_tracer: dtype must be NF_F64/NF_F32");
     nf_field *f = *self;
-    NF_REQUIRE(f->u && f->v, NF_ERR_STATE, "nf_field_set_tracer: set_uv first");
-    NF_REQUIRE(dtype == f->uv_dtype, NF_ERR_ARG, "nf_field_set_tracer: the tracer's dtype differs from the dtype of uo/vo");
-    if (nt != f->nt) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "nf_field_set_tracer: the tracer has nt = %ld time steps, uo/vo have %ld", nt, f->nt);
-        NF_REQUIRE(false, NF_ERR_ARG, buf);
-    }
-    f->tau = tracer;
-    f->tau_nt = nt;
-    f->tau_dtype = dtype;
-    f->tau_on_device = on_device ? 1 : 0;
-    f->tau_fill = fill_value;
+    NF_REQUIRE(f->uv.p[0] && f->uv.p[1], NF_ERR_STATE, "nf_field_set_tracer: set_uv first");
+    NF_TRY(field_matches_uv(f, dtype, nt, "nf_field_set_tracer", "tracer", kCountSteps));
+    f->tau.p[0] = tracer;
+    f->tau.nt = nt;
+    f->tau.dtype = dtype;
+    f->tau.on_device = on_device ? 1 : 0;
+    f->tau.fill = fill_value;
     return NF_OK;
 }
 NF_API_CATCH
@@ -1372,7 +1368,7 @@ NF_API_CATCH
 int nf_field_set_tracer_missing_value(nf_field **self, double missing_value)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_tracer_missing_value: null field");
-    (*self)->tau_fill2 = missing_value;
+    (*self)->tau.fill2 = missing_value;
     return NF_OK;
 }
 NF_API_CATCH
@@ -1399,7 +1395,7 @@ int nf_field_compute_tracer_flux(nf_field **self, long tIndex, double *row_host)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_compute_tracer_flux: null field");
     nf_field *f = *self;
-    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_flux: set_tracer first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_flux: set_tracer first");
     NF_NEED_DEVICE();
     return field_sync(f, field_row_length(f), row_host, [&](double *row) { return field_tracer_step_async(f, tIndex, row); });
 }
@@ -1409,30 +1405,36 @@ int nf_field_compute_tracer_all_async(nf_field **self, double *rows_dev)
 try {
     NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_tracer_all_async: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_all_async: set_tracer first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_all_async: set_tracer first");
     NF_NEED_DEVICE();
     const int rowlen = field_row_length(f);
-    for (long t = 0; t < f->nt; ++t) NF_TRY(field_tracer_step_async(f, t, rows_dev + (size_t)t * rowlen));
+    for (long t = 0; t < f->uv.nt; ++t) NF_TRY(field_tracer_step_async(f, t, rows_dev + (size_t)t * rowlen));
     return NF_OK;
 }
 NF_API_CATCH
 
+// the rules of one set of class edges; w prefixes the messages
+static int class_edges_check(const std::string &w, const double *edges, int n)
+{
+    if (!(n >= 2 && n <= kMaxClassEdges)) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "need 2 <= nedges <= %d, got %d", kMaxClassEdges, n);
+        NF_REQUIRE(false, NF_ERR_ARG, w + buf);
+    }
+    for (int k = 0; k < n; ++k) {
+        NF_REQUIRE(std::isfinite(edges[k]), NF_ERR_ARG, w + "every edge must be a finite number");
+        NF_REQUIRE(k == 0 || edges[k] > edges[k - 1], NF_ERR_ARG, w + "the edges must be strictly increasing");
+    }
+    return NF_OK;
+}
+
 int nf_field_set_class_edges(nf_field **self, const double *edges, int nedges)
 try {
     NF_REQUIRE(self && *self && edges, NF_ERR_ARG, "nf_field_set_class_edges: null argument");
-    if (!(nedges >= 2 && nedges <= kMaxClassEdges)) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "nf_field_set_class_edges: need 2 <= nedges <= %d, got %d", kMaxClassEdges, nedges);
-        NF_REQUIRE(false, NF_ERR_ARG, buf);
-    }
-    for (int k = 0; k < nedges; ++k) {
-        NF_REQUIRE(std::isfinite(edges[k]), NF_ERR_ARG, "nf_field_set_class_edges: every edge must be a finite number");
-        NF_REQUIRE(k == 0 || edges[k] > edges[k - 1], NF_ERR_ARG,
-                   "nf_field_set_class_edges: the edges must be strictly increasing");
-    }
+    NF_TRY(class_edges_check("nf_field_set_class_edges: ", edges, nedges));
     nf_field *f = *self;
-    f->class_edges.assign(edges, edges + nedges);
-    f->class_edges_stale = true;
+    f->class_edges.host.assign(edges, edges + nedges);
+    f->class_edges.stale = true;
     return NF_OK;
 }
 NF_API_CATCH
@@ -1444,7 +1446,7 @@ try {
     NF_TRY(field_class_ready(f, "nf_field_compute_class_transport"));
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport"));
     NF_NEED_DEVICE();
-    const size_t n = (f->class_edges.size() + 2) * (size_t)field_row_length(f);
+    const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
     if (n == 0) return NF_OK;
     return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows); });
 }
@@ -1461,45 +1463,29 @@ try {
 }
 NF_API_CATCH
 
-// one edge set of nf_field_set_joint_class_edges: the rules of nf_field_set_class_edges
-static int joint_edges_check(const char *axis, const double *edges, int n)
-{
-    const std::string w = std::string("nf_field_set_joint_class_edges: axis ") + axis + ": ";
-    if (!(n >= 2 && n <= kMaxClassEdges)) {
-        char buf[96];
-        snprintf(buf, sizeof buf, "need 2 <= nedges <= %d, got %d", kMaxClassEdges, n);
-        NF_REQUIRE(false, NF_ERR_ARG, w + buf);
-    }
-    for (int k = 0; k < n; ++k) {
-        NF_REQUIRE(std::isfinite(edges[k]), NF_ERR_ARG, w + "every edge must be a finite number");
-        NF_REQUIRE(k == 0 || edges[k] > edges[k - 1], NF_ERR_ARG, w + "the edges must be strictly increasing");
-    }
-    return NF_OK;
-}
-
 int nf_field_set_joint_class_edges(nf_field **self, const double *edges_a, int na, const double *edges_b, int nb)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_joint_class_edges: null field");
     nf_field *f = *self;
     if (!edges_a && !edges_b) {   // no joint classes
-        f->joint_edges.clear();
+        f->joint_edges.host.clear();
         f->joint_na = f->joint_nb = 0;
         return NF_OK;
     }
     NF_REQUIRE(edges_a && edges_b, NF_ERR_ARG, "nf_field_set_joint_class_edges: null argument");
-    NF_TRY(joint_edges_check("A", edges_a, na));
-    NF_TRY(joint_edges_check("B", edges_b, nb));
+    NF_TRY(class_edges_check("nf_field_set_joint_class_edges: axis A: ", edges_a, na));
+    NF_TRY(class_edges_check("nf_field_set_joint_class_edges: axis B: ", edges_b, nb));
     if ((na + 2) * (nb + 2) > kMaxJointRows) {
         char buf[200];
         snprintf(buf, sizeof buf, "nf_field_set_joint_class_edges: (na + 2) * (nb + 2) = %d joint rows, at most %d are supported",
                  (na + 2) * (nb + 2), kMaxJointRows);
         NF_REQUIRE(false, NF_ERR_ARG, buf);
     }
-    f->joint_edges.assign(edges_a, edges_a + na);
-    f->joint_edges.insert(f->joint_edges.end(), edges_b, edges_b + nb);
+    f->joint_edges.host.assign(edges_a, edges_a + na);
+    f->joint_edges.host.insert(f->joint_edges.host.end(), edges_b, edges_b + nb);
     f->joint_na = na;
     f->joint_nb = nb;
-    f->joint_edges_stale = true;
+    f->joint_edges.stale = true;
     return NF_OK;
 }
 NF_API_CATCH
@@ -1532,7 +1518,7 @@ int nf_field_compute_tracer_profile(nf_field **self, long tIndex, double *prof_h
 try {
     NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_tracer_profile: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_profile: set_tracer first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_profile: set_tracer first");
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_tracer_profile"));
     NF_TRY(field_ready(f, "compute_tracer_profile", true));
     NF_NEED_DEVICE();
@@ -1546,7 +1532,7 @@ int nf_field_compute_tracer_profile_async(nf_field **self, long tIndex, double *
 try {
     NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_tracer_profile_async: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_tracer_profile_async: set_tracer first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_profile_async: set_tracer first");
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_tracer_profile_async"));
     NF_TRY(field_ready(f, "compute_tracer_profile", true));
     NF_NEED_DEVICE();
@@ -1558,7 +1544,7 @@ int nf_field_compute_area_profile(nf_field **self, long tIndex, double *rows_hos
 try {
     NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_area_profile: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_area_profile: set_tracer first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_area_profile: set_tracer first");
     NF_NEED_DEVICE();
     NF_TRY(field_ready(f, "compute_area_profile", true));
     const size_t n = 2 * (size_t)f->nz * field_row_length(f);
@@ -1571,7 +1557,7 @@ int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *ro
 try {
     NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_area_profile_async: null argument");
     nf_field *f = *self;
-    NF_REQUIRE(f->tau, NF_ERR_STATE, "nf_field_compute_area_profile_async: set_tracer first");
+    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_area_profile_async: set_tracer first");
     NF_NEED_DEVICE();
     NF_TRY(field_ready(f, "compute_area_profile", true));
     return field_area_async(f, tIndex, rows_dev);
@@ -1584,7 +1570,7 @@ static int field_gross_args(nf_field **self, int carry, const void *rows, const 
     const std::string w(what);
     NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
     NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
-    NF_REQUIRE(!carry || (*self)->tau, NF_ERR_STATE, w + ": set_tracer first");
+    NF_REQUIRE(!carry || (*self)->tau.p[0], NF_ERR_STATE, w + ": set_tracer first");
     return NF_OK;
 }
 
@@ -1615,29 +1601,19 @@ try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_class_tracer: null field");
     nf_field *f = *self;
     if (!tracer) {   // back to "the class field is the carried tracer"
-        f->sig = nullptr;
-        f->sig_nt = 0;
-        f->sig_fill = f->sig_fill2 = std::numeric_limits<double>::quiet_NaN();
+        f->sig.p[0] = nullptr;
+        f->sig.nt = 0;
+        f->sig.fill = f->sig.fill2 = std::numeric_limits<double>::quiet_NaN();
         return NF_OK;
     }
     NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_class_tracer: dtype must be NF_F64/NF_F32");
-    NF_REQUIRE(f->u && f->v, NF_ERR_STATE, "nf_field_set_class_tracer: set_uv first");
-    if (dtype != f->uv_dtype) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "nf_field_set_class_tracer: the class tracer's dtype is %s, uo/vo are %s",
-                 dtype == NF_F32 ? "float32" : "float64", f->uv_dtype == NF_F32 ? "float32" : "float64");
-        NF_REQUIRE(false, NF_ERR_ARG, buf);
-    }
-    if (nt != f->nt) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "nf_field_set_class_tracer: the class tracer has nt = %ld time steps, uo/vo have %ld", nt, f->nt);
-        NF_REQUIRE(false, NF_ERR_ARG, buf);
-    }
-    f->sig = tracer;
-    f->sig_nt = nt;
-    f->sig_dtype = dtype;
-    f->sig_on_device = on_device ? 1 : 0;
-    f->sig_fill = fill_value;
+    NF_REQUIRE(f->uv.p[0] && f->uv.p[1], NF_ERR_STATE, "nf_field_set_class_tracer: set_uv first");
+    NF_TRY(field_matches_uv(f, dtype, nt, "nf_field_set_class_tracer", "class tracer", kNameDtypes | kCountSteps));
+    f->sig.p[0] = tracer;
+    f->sig.nt = nt;
+    f->sig.dtype = dtype;
+    f->sig.on_device = on_device ? 1 : 0;
+    f->sig.fill = fill_value;
     return NF_OK;
 }
 NF_API_CATCH
@@ -1645,7 +1621,7 @@ NF_API_CATCH
 int nf_field_set_class_tracer_missing_value(nf_field **self, double missing_value)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_class_tracer_missing_value: null field");
-    (*self)->sig_fill2 = missing_value;
+    (*self)->sig.fill2 = missing_value;
     return NF_OK;
 }
 NF_API_CATCH
@@ -1656,27 +1632,18 @@ try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_cell_thickness: null field");
     nf_field *f = *self;
     if (!e3u) {   // back to the per-level thickness
-        f->e3u = f->e3v = nullptr;
-        f->e3_nt = 0;
-        f->e3_fill = f->e3_fill2 = std::numeric_limits<double>::quiet_NaN();
-        f->e3u_static.reset(), f->e3v_static.reset(), f->stage_e3u.reset(), f->stage_e3v.reset();
+        f->e3.p[0] = f->e3.p[1] = nullptr;
+        f->e3.nt = 0;
+        f->e3.fill = f->e3.fill2 = std::numeric_limits<double>::quiet_NaN();
+        f->e3u_static.reset(), f->e3v_static.reset(), f->e3.stage[0].reset(), f->e3.stage[1].reset();
         ++f->version;
         return NF_OK;
     }
     NF_REQUIRE(e3v, NF_ERR_ARG, "nf_field_set_cell_thickness: e3v is null (both arrays or neither)");
     NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_cell_thickness: dtype must be NF_F64/NF_F32");
-    NF_REQUIRE(f->u && f->v, NF_ERR_STATE, "nf_field_set_cell_thickness: set_uv and set_thickness first");
-    char buf[200];
-    if (dtype != f->uv_dtype) {
-        snprintf(buf, sizeof buf, "nf_field_set_cell_thickness: the cell thickness's dtype is %s, uo/vo are %s",
-                 dtype == NF_F32 ? "float32" : "float64", f->uv_dtype == NF_F32 ? "float32" : "float64");
-        NF_REQUIRE(false, NF_ERR_ARG, buf);
-    }
-    if (nt_th != 1 && nt_th != f->nt) {
-        snprintf(buf, sizeof buf, "nf_field_set_cell_thickness: the cell thickness has nt = %ld time steps, need 1 (static) or "
-                 "the %ld of uo/vo", nt_th, f->nt);
-        NF_REQUIRE(false, NF_ERR_ARG, buf);
-    }
+    NF_REQUIRE(f->uv.p[0] && f->uv.p[1], NF_ERR_STATE, "nf_field_set_cell_thickness: set_uv and set_thickness first");
+    NF_TRY(field_matches_uv(f, dtype, nt_th, "nf_field_set_cell_thickness", "cell thickness",
+                            kStaticOk | kNameDtypes | kCountSteps));
     NF_REQUIRE(f->thick.get(), NF_ERR_STATE, "nf_field_set_cell_thickness: set_thickness first (it fixes nz)");
     const bool upload = !on_device && nt_th == 1;   // a static host array: uploaded once, here
     if (upload) {
@@ -1697,12 +1664,12 @@ try {
     } else {
         f->e3u_static.reset(), f->e3v_static.reset();
     }
-    f->e3u = e3u;
-    f->e3v = e3v;
-    f->e3_nt = nt_th;
-    f->e3_dtype = dtype;
-    f->e3_on_device = (on_device || upload) ? 1 : 0;
-    f->e3_fill = fill_value;
+    f->e3.p[0] = e3u;
+    f->e3.p[1] = e3v;
+    f->e3.nt = nt_th;
+    f->e3.dtype = dtype;
+    f->e3.on_device = (on_device || upload) ? 1 : 0;
+    f->e3.fill = fill_value;
     ++f->version;
     return NF_OK;
 }
@@ -1711,7 +1678,7 @@ NF_API_CATCH
 int nf_field_set_cell_thickness_missing_value(nf_field **self, double missing_value)
 try {
     NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_cell_thickness_missing_value: null field");
-    (*self)->e3_fill2 = missing_value;
+    (*self)->e3.fill2 = missing_value;
     ++(*self)->version;
     return NF_OK;
 }
@@ -1724,7 +1691,7 @@ try {
     NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport"));
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_tracer_transport"));
     NF_NEED_DEVICE();
-    const size_t n = (f->class_edges.size() + 2) * (size_t)field_row_length(f);
+    const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
     if (n == 0) return NF_OK;
     return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows, true); });
 }

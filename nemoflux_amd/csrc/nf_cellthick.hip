@@ -13,36 +13,9 @@
 // launch_expand_planes derives the south / west copies and the |.| planes behind it.
 //
 // Algorithmic bytes per (t,z,j,i): 4*sizeof(T) read + (16 arc + 16 planes)/nz.
-#include "nf_common.h"
+#include "nf_lanes.h"
 
 namespace nf {
-
-namespace {
-
-typedef double ct_dvec2 __attribute__((ext_vector_type(2)));
-typedef float ct_fvec4 __attribute__((ext_vector_type(4)));
-template <typename T, int VEC> struct ct_vec;
-template <> struct ct_vec<double, 2> { using type = ct_dvec2; };
-template <> struct ct_vec<float, 4> { using type = ct_fvec4; };
-template <> struct ct_vec<double, 1> { using type = double; };
-template <> struct ct_vec<float, 1> { using type = float; };
-
-template <typename T, int VEC> struct CtLanes {
-    T x[VEC];
-};
-
-// VEC consecutive values at p (16-byte aligned when VEC > 1), read once: non-temporal
-template <typename T, int VEC>
-__device__ inline CtLanes<T, VEC> ct_load(const T *p)
-{
-    using V = typename ct_vec<T, VEC>::type;
-    CtLanes<T, VEC> r;
-    V v = __builtin_nontemporal_load(reinterpret_cast<const V *>(p));
-    __builtin_memcpy(&r, &v, sizeof(V));
-    return r;
-}
-
-}  // namespace
 
 // 256 threads, one chunk of VEC cells per lane: c0 = (tile * 256 + tid) * VEC; ncell % VEC == 0 (the launcher picks VEC = 1
 // otherwise), so a lane's cells are all there or all absent
@@ -65,15 +38,15 @@ __global__ __launch_bounds__(256) void k_cellthick_flux(const T *__restrict__ u,
         const T *pu = u + o0, *pv = v + o0, *pe = e3u + o0, *pf = e3v + o0;
         for (int z = z0; z < z1; z += UZ) {
             const int nlev = z1 - z < UZ ? z1 - z : UZ;   // wave-uniform
-            CtLanes<T, VEC> lu[UZ], lv[UZ], le[UZ], lf[UZ];
+            Lanes<T, VEC> lu[UZ], lv[UZ], le[UZ], lf[UZ];
 #pragma unroll
             for (int r = 0; r < UZ; ++r)
                 if (r < nlev) {
                     const long o = (long)r * ncell;
-                    lu[r] = ct_load<T, VEC>(pu + o);
-                    le[r] = ct_load<T, VEC>(pe + o);
-                    lv[r] = ct_load<T, VEC>(pv + o);
-                    lf[r] = ct_load<T, VEC>(pf + o);
+                    lu[r] = lane_load<T, VEC, true>(pu + o);
+                    le[r] = lane_load<T, VEC, true>(pe + o);
+                    lv[r] = lane_load<T, VEC, true>(pv + o);
+                    lf[r] = lane_load<T, VEC, true>(pf + o);
                 }
 #pragma unroll
             for (int r = 0; r < UZ; ++r)
@@ -106,9 +79,9 @@ __global__ __launch_bounds__(256) void k_cellthick_flux(const T *__restrict__ u,
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; k += 2) {
-                const ct_dvec2 a = {eU[k], eU[k + 1 < VEC ? k + 1 : k]}, b = {eV[k], eV[k + 1 < VEC ? k + 1 : k]};
-                __builtin_nontemporal_store(a, reinterpret_cast<ct_dvec2 *>(pU + k));
-                __builtin_nontemporal_store(b, reinterpret_cast<ct_dvec2 *>(pV + k));
+                const dvec2 a = {eU[k], eU[k + 1 < VEC ? k + 1 : k]}, b = {eV[k], eV[k + 1 < VEC ? k + 1 : k]};
+                __builtin_nontemporal_store(a, reinterpret_cast<dvec2 *>(pU + k));
+                __builtin_nontemporal_store(b, reinterpret_cast<dvec2 *>(pV + k));
             }
         }
     }
@@ -147,9 +120,7 @@ int launch_cellthick_t(const CellThickArgs &a, hipStream_t s)
 template <typename T, int VEC>
 int launch_cellthick_v(const CellThickArgs &a, hipStream_t s)
 {
-    bool al16 = true;
-    for (const void *p : {a.in.u, a.in.v, a.th.e3u, a.th.e3v}) al16 = al16 && (uintptr_t)p % 16 == 0;
-    if (al16 && a.in.ncell % VEC == 0) return launch_cellthick_t<T, VEC>(a, s);
+    if (lanes_aligned16({a.in.u, a.in.v, a.th.e3u, a.th.e3v}) && a.in.ncell % VEC == 0) return launch_cellthick_t<T, VEC>(a, s);
     return launch_cellthick_t<T, 1>(a, s);   // odd sizes / unaligned arrays: one cell per lane
 }
 }  // namespace

@@ -342,7 +342,7 @@ struct StepInput {
 // Depth-resolved rows (nf_field_compute_profile): the per-level form of the record path of K3, reading the raw fields of
 // one time step.  prof: (nz, row_length) doubles; the kernels write rows [z0, z1) only.  Levels are processed
 // kProfileChunk at a time: scratch holds the run sums of one chunk, ws.nrec * kProfileChunk doubles.
-// With a carried tracer (tau != nullptr; nf_field_compute_tracer_profile) every term is multiplied by tr_face of the tracer at
+// With a carried tracer (t.tau != nullptr; nf_field_compute_tracer_profile) every term is multiplied by tr_face of the tracer at
 // its own face, as one level of the tracer transport: 4 + 5 gathers per level, kTracerProfileChunk levels at a time (float64)
 // or kTracerProfileChunkF32 (float32: half the registers per gathered value): tracer_profile_chunk(dtype), measured.
 // Per-cell layer thicknesses (nf_field_set_cell_thickness): e3u at the index of uo (the east face of the cell), e3v at the
@@ -366,6 +366,15 @@ __device__ inline double thick_fixed(T x, T m1, T m2)
     return (x != x || x == m1 || x == m2) ? 0.0 : (double)x;
 }
 
+// A tracer at T-points as the kernels of a Field read one time step of it (nf_field_set_tracer*, nf_field_set_class_tracer*):
+// the tracer transport, the carried forms of the profiles, the class field and the two axes of the joint classes.
+struct TracerIn {
+    const void *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
+    double fill = __builtin_nan(""), fill2 = __builtin_nan("");   // the tracer's own _FillValue / missing_value; NaN = none
+    double ref = 0.0;            // reference value subtracted from every face value
+    int wrap_x = 1;              // 1: the east face of column nx-1 takes column 0 as its neighbour
+};
+
 constexpr int kProfileChunk = 8;
 // the volume profile with cell thicknesses: 4 + 4 gathers per level.  Four levels, the 32 gathers per lane that the scalar form
 // has in flight: 95 (float64) / 64 (float32) VGPRs, 5 / 8 waves per SIMD, no scratch (the scalar form: 93 / 66, 5 / 7); eight
@@ -380,11 +389,8 @@ struct ProfileArgs {
     double *scratch = nullptr;
     size_t scratch_len = 0;
     double *prof = nullptr;
-    const void *tau = nullptr;   // the carried tracer of the time step, (nz, ncell) of the field dtype; nullptr: volume rows
-    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
-    double ref = 0.0;
-    int wrap_x = 1;
-    CellThick th;                // volume rows only (tau == nullptr): every slot's term takes the thickness at its own face
+    TracerIn t;                  // the carried tracer; t.tau == nullptr: volume rows
+    CellThick th;                // volume rows only (t.tau == nullptr): every slot's term takes the thickness at its own face
 };
 int launch_profile(const ProfileArgs &a, hipStream_t s);
 
@@ -404,10 +410,7 @@ struct AreaArgs {
     size_t scratch_len = 0;
     double *rows = nullptr;
     long nz = 0;
-    const void *tau = nullptr;   // the carried tracer of the time step, (nz, ncell) of the field dtype
-    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
-    double ref = 0.0;
-    int wrap_x = 1;
+    TracerIn t;                  // the carried tracer
     CellThick th;
 };
 int launch_area_profile(const AreaArgs &a, hipStream_t s);
@@ -435,10 +438,7 @@ struct GrossArgs {
     size_t scratch_len = 0;
     double *rows = nullptr;
     long nz = 0;
-    const void *tau = nullptr;   // the carried tracer of the time step, (nz, ncell) of the field dtype; nullptr: volume form
-    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
-    double ref = 0.0;
-    int wrap_x = 1;
+    TracerIn t;                  // the carried tracer; t.tau == nullptr: volume form
     CellThick th;
 };
 int launch_gross_profile(const GrossArgs &a, hipStream_t s);
@@ -448,10 +448,7 @@ int launch_gross_profile(const GrossArgs &a, hipStream_t s);
 // the two signed planes [eU_tau | eV_tau] of one time step, nothing else; K3 (planes = 2) reduces them.
 struct TracerArgs {
     StepInput in;
-    const void *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
-    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");   // the tracer's own _FillValue / missing_value
-    double ref = 0.0;         // reference value subtracted from every face value
-    int wrap_x = 1;           // 1: the east face of column nx-1 takes column 0 as its neighbour
+    TracerIn t;
     double *planes = nullptr; // [2][ncell]: eU_tau, eV_tau
     CellThick th;             // e3u set: fma(fixth(e3u), fixed(u) * tfE, accU), two more aligned streams
 };
@@ -513,9 +510,7 @@ constexpr int kMaxClassEdges = 1025;
 constexpr int kClassWindowMax = 32;
 struct ClassArgs {
     StepInput in;
-    const void *tau = nullptr;   // base of the time step: (nz, ncell) of the field dtype
-    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");
-    int wrap_x = 1;
+    TracerIn cls;                // the class field; its wrap_x is the rule of every face, its ref is not read
     const double *edges = nullptr;   // device, nedges
     int nedges = 0;
     int window = 0;              // rows per pass over the fields, 1 .. kClassWindowMax
@@ -524,11 +519,9 @@ struct ClassArgs {
     size_t scratch_len = 0;
     double *rows = nullptr;      // (nedges + 2, row_length)
     // tracer transport in classes (nf_field_compute_class_tracer_transport): every term times tr_face of the carried tracer
-    // at its own face.  nullptr: volume transport.  The carried tracer may be the class field itself (carry == tau with the
-    // same markers: one set of gathers) or another array; it shares wrap_x with the class field.
-    const void *carry = nullptr;
-    double cfill = __builtin_nan(""), cfill2 = __builtin_nan("");
-    double ref = 0.0;
+    // at its own face.  carry.tau == nullptr: volume transport.  The carried tracer may be the class field itself (the same
+    // array with the same markers: one set of gathers) or another array; its wrap_x is not read.
+    TracerIn carry;
 };
 int launch_class_transport(const ClassArgs &a, hipStream_t s);
 
@@ -545,11 +538,7 @@ constexpr unsigned kJointNoRow = 0xFFFFu;
 constexpr size_t kJointEntryBytes = 40;
 struct JointArgs {
     StepInput in;
-    const void *tau = nullptr, *sig = nullptr;   // A and B at the base of the time step: (nz, ncell) of the field dtype
-    double tfill = __builtin_nan(""), tfill2 = __builtin_nan("");   // A's markers
-    double sfill = __builtin_nan(""), sfill2 = __builtin_nan("");   // B's markers
-    double ref = 0.0;            // A's reference (carried form)
-    int wrap_x = 1;
+    TracerIn ta, tb;             // A (its ref: the carried form; its wrap_x: the rule of every face) and B (markers only)
     int carry = 0;               // 1: every term times tr_face of A at its own face
     const double *edges = nullptr;   // device: ea (na doubles) followed by eb (nb doubles)
     int na = 0, nb = 0;

@@ -190,6 +190,8 @@ struct TauIn {
     double ref;
     int wrap_x;
 };
+template <typename T>
+inline TauIn<T> tau_of(const TracerIn &t) { return TauIn<T>{(const T *)t.tau, (T)t.fill, (T)t.fill2, t.ref, t.wrap_x ? 1 : 0}; }
 // the trailing arguments of a kernel that has a volume form (none) and a carried-tracer form (one TauIn)
 template <typename T>
 __device__ inline TauIn<T> tau_in() { return TauIn<T>{}; }
@@ -489,7 +491,7 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
                                    ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
                                    (unsigned)in.nx, zc, nlev, in.thickness, in.arcE, in.arcN, fill, fill2,
                                    (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, a.scratch,
-                                   TauIn<T>{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0});
+                                   tau_of<T>(a.t));
             else if constexpr (FORM == 2)
                 hipLaunchKernelGGL((k_profile_segscan<T, chunk, ThickIn<T>>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(),
                                    ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell,
@@ -510,7 +512,7 @@ static int launch_profile_t(const ProfileArgs &a, hipStream_t s)
 
 int launch_profile(const ProfileArgs &a, hipStream_t s)
 {
-    const bool tr = a.tau != nullptr, ct = a.th.e3u != nullptr;
+    const bool tr = a.t.tau != nullptr, ct = a.th.e3u != nullptr;
     NF_REQUIRE(!(tr && ct), NF_ERR_STATE, "profile: the tracer profile does not take per-cell thicknesses");
     NF_REQUIRE(!ct || a.th.e3v, NF_ERR_ARG, "profile: null argument");
     NF_TRY(check_raw_step("profile", a.in, a.tr, a.scratch_len,
@@ -628,7 +630,7 @@ static int launch_area_t(const AreaArgs &a, hipStream_t s)
     const StepInput &in = a.in;
     const long row_length = a.tr.row_length();
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    const TauIn<T> ti{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0};
+    const TauIn<T> ti = tau_of<T>(a.t);
     double *tsum = a.scratch + (size_t)LZ * ws.nrec;   // the second half of the run sums
     for (int zc = in.z0; zc < in.z1; zc += LZ) {
         const int nlev = in.z1 - zc < LZ ? in.z1 - zc : LZ;
@@ -656,7 +658,7 @@ int launch_area_profile(const AreaArgs &a, hipStream_t s)
 {
     const StepInput &in = a.in;
     const int chunk = area_chunk_now(in.dtype);
-    NF_REQUIRE(in.u && in.v && a.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "area profile: null argument");
+    NF_REQUIRE(in.u && in.v && a.t.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "area profile: null argument");
     NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "area profile: null argument");
     NF_REQUIRE(in.z1 <= a.nz, NF_ERR_ARG, "area profile: bad arguments");
     NF_TRY(check_raw_step("area profile", in, a.tr, a.scratch_len, 2 * (size_t)chunk));
@@ -798,9 +800,9 @@ static int launch_gross_t(const GrossArgs &a, hipStream_t s, TI... extra)
 template <typename T, int LZ>
 static int launch_gross_form(const GrossArgs &a, hipStream_t s)
 {
-    const TauIn<T> ti{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0};
-    if (a.tau && a.th.e3u) return launch_gross_t<T, LZ>(a, s, ti, thick_in<T>(a.th));
-    if (a.tau) return launch_gross_t<T, LZ>(a, s, ti);
+    const TauIn<T> ti = tau_of<T>(a.t);
+    if (a.t.tau && a.th.e3u) return launch_gross_t<T, LZ>(a, s, ti, thick_in<T>(a.th));
+    if (a.t.tau) return launch_gross_t<T, LZ>(a, s, ti);
     if (a.th.e3u) return launch_gross_t<T, LZ>(a, s, thick_in<T>(a.th));
     return launch_gross_t<T, LZ>(a, s);
 }
@@ -808,7 +810,7 @@ static int launch_gross_form(const GrossArgs &a, hipStream_t s)
 int launch_gross_profile(const GrossArgs &a, hipStream_t s)
 {
     const StepInput &in = a.in;
-    const int chunk = gross_chunk_now(in.dtype, a.tau != nullptr, a.th.e3u != nullptr);
+    const int chunk = gross_chunk_now(in.dtype, a.t.tau != nullptr, a.th.e3u != nullptr);
     NF_REQUIRE(in.u && in.v && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "gross profile: null argument");
     NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "gross profile: null argument");
     NF_REQUIRE(in.z1 <= a.nz, NF_ERR_ARG, "gross profile: bad arguments");
@@ -959,20 +961,21 @@ static int launch_class_t(const ClassArgs &a, hipStream_t s)
                     NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T, false>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL((k_class_segscan<T, false>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
-                                   ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.tau, in.ncell,
+                                   ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau, in.ncell,
                                    (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
-                                   (int)uv_two_markers(fill, fill2), (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale,
+                                   (int)uv_two_markers(fill, fill2), (T)a.cls.fill, (T)a.cls.fill2, a.cls.wrap_x ? 1 : 0, in.scale,
                                    in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch);
             } else {
                 if (lds > 65536)
                     NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T, FORM == 2, TauIn<T>>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL((k_class_segscan<T, FORM == 2, TauIn<T>>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(),
-                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.tau,
+                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau,
                                    in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
-                                   (int)uv_two_markers(fill, fill2), (T)a.tfill, (T)a.tfill2, a.wrap_x ? 1 : 0, in.scale,
+                                   (int)uv_two_markers(fill, fill2), (T)a.cls.fill, (T)a.cls.fill2, a.cls.wrap_x ? 1 : 0, in.scale,
                                    in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch,
-                                   TauIn<T>{(const T *)a.carry, (T)a.cfill, (T)a.cfill2, a.ref, a.wrap_x ? 1 : 0});
+                                   TauIn<T>{(const T *)a.carry.tau, (T)a.carry.fill, (T)a.carry.fill2, a.carry.ref,
+                                            a.cls.wrap_x ? 1 : 0});
             }
         }
         launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
@@ -985,8 +988,8 @@ static int launch_class_t(const ClassArgs &a, hipStream_t s)
 template <typename T>
 static int launch_class_form(const ClassArgs &a, hipStream_t s)
 {
-    if (!a.carry) return launch_class_t<T, 0>(a, s);
-    const bool one = a.carry == a.tau && same_bits(a.cfill, a.tfill) && same_bits(a.cfill2, a.tfill2);
+    if (!a.carry.tau) return launch_class_t<T, 0>(a, s);
+    const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
     return one ? launch_class_t<T, 1>(a, s) : launch_class_t<T, 2>(a, s);
 }
 
@@ -996,7 +999,7 @@ int launch_class_transport(const ClassArgs &a, hipStream_t s)
     NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "class transport: bad class edges");
     NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "class transport: bad window");
     NF_TRY(check_raw_step("class transport", in, a.tr, a.scratch_len, (size_t)a.window));
-    NF_REQUIRE(in.u && in.v && a.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+    NF_REQUIRE(in.u && in.v && a.cls.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
                "class transport: null argument");
     if (a.tr.row_length() == 0) return NF_OK;
     if (in.dtype == NF_F64) return launch_class_form<double>(a, s);
@@ -1166,10 +1169,10 @@ static int launch_joint_t(const JointArgs &a, hipStream_t s)
     if (ws.nrec > 0) {
         const size_t lds = sizeof(double) * (size_t)(a.na + a.nb) + sizeof(unsigned) * (size_t)nwords;
         hipLaunchKernelGGL((k_joint_terms<T, CARRY>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(), ws.nrec,
-                           (const T *)in.u, (const T *)in.v, (const T *)a.sig, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness,
-                           in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2),
-                           TauIn<T>{(const T *)a.tau, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0}, (T)a.sfill, (T)a.sfill2,
-                           in.scale, in.sverdrup, a.edges, a.na, a.nb, topa, topb, a.window, nwords, terms, rows, a.flags);
+                           (const T *)in.u, (const T *)in.v, (const T *)a.tb.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                           in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), tau_of<T>(a.ta),
+                           (T)a.tb.fill, (T)a.tb.fill2, in.scale, in.sverdrup, a.edges, a.na, a.nb, topa, topb, a.window, nwords,
+                           terms, rows, a.flags);
         NF_HIP(hipGetLastError());
     }
     for (int r0 = 0, win = 0; r0 < nrows; r0 += a.window, ++win) {
@@ -1191,7 +1194,7 @@ int launch_joint_class_transport(const JointArgs &a, hipStream_t s)
                "joint class transport: bad class edges");
     NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "joint class transport: bad window");
     NF_TRY(check_raw_step("joint class transport", in, a.tr, a.scratch_len, (size_t)a.window));
-    NF_REQUIRE(in.u && in.v && a.tau && a.sig && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+    NF_REQUIRE(in.u && in.v && a.ta.tau && a.tb.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
                "joint class transport: null argument");
     if (a.tr.row_length() == 0) return NF_OK;
     const size_t nrec = (size_t)a.tr.ws->nrec, blocks = (nrec + kBlock - 1) / kBlock;

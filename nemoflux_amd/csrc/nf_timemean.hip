@@ -32,53 +32,45 @@
 // so that acch * accf is the mean volume flux per unit width, face by face.  Same access pattern with two loads per step and
 // lane; 2 * nsteps * n * sizeof(T) read + 16 n written by a first && last call, a carried call adds 20 n each way.
 #include "nf_capi.h"
+#include "nf_lanes.h"
 
 namespace nf {
 
 namespace {
-
-typedef double tm_dvec2 __attribute__((ext_vector_type(2)));
-typedef float tm_fvec4 __attribute__((ext_vector_type(4)));
-typedef unsigned tm_uvec2 __attribute__((ext_vector_type(2)));
-typedef unsigned tm_uvec4 __attribute__((ext_vector_type(4)));
-template <typename T, int VEC> struct tm_vec;
-template <> struct tm_vec<double, 2> { using type = tm_dvec2; };
-template <> struct tm_vec<float, 4> { using type = tm_fvec4; };
-template <> struct tm_vec<double, 1> { using type = double; };
-template <> struct tm_vec<float, 1> { using type = float; };
-template <> struct tm_vec<unsigned, 2> { using type = tm_uvec2; };
-template <> struct tm_vec<unsigned, 4> { using type = tm_uvec4; };
-template <> struct tm_vec<unsigned, 1> { using type = unsigned; };
-
-template <typename T, int VEC> struct TmLanes {
-    T x[VEC];
-};
-
-// VEC consecutive values at p (aligned to VEC * sizeof(T) when VEC > 1); NT: read once
-template <typename T, int VEC, bool NT>
-__device__ inline TmLanes<T, VEC> tm_load(const T *p)
-{
-    using V = typename tm_vec<T, VEC>::type;
-    TmLanes<T, VEC> r;
-    V v = NT ? __builtin_nontemporal_load(reinterpret_cast<const V *>(p)) : *reinterpret_cast<const V *>(p);
-    __builtin_memcpy(&r, &v, sizeof(V));
-    return r;
-}
-template <typename T, int VEC>
-__device__ inline void tm_store(T *p, const TmLanes<T, VEC> &r)
-{
-    using V = typename tm_vec<T, VEC>::type;
-    V v;
-    __builtin_memcpy(&v, &r, sizeof(V));
-    __builtin_nontemporal_store(v, reinterpret_cast<V *>(p));
-}
 
 struct TmFinish {
     int first, last, rule;
     double total_steps, fill_out;
 };
 
-// the VEC values that begin at i0: US steps' loads in flight, the adds in step order
+// VEC float64 sums at p, 16 bytes at a time
+template <int VEC>
+__device__ inline void tm_load_sums(double (&s)[VEC], const double *p)
+{
+#pragma unroll
+    for (int k = 0; k < VEC; k += 2) {
+        constexpr int W = VEC > 1 ? 2 : 1;
+        const Lanes<double, W> a = lane_load<double, W, false>(p + k);
+#pragma unroll
+        for (int q = 0; q < W; ++q) s[k + q] = a.x[q];
+    }
+}
+template <int VEC>
+__device__ inline void tm_store_sums(double *p, const double (&s)[VEC])
+{
+#pragma unroll
+    for (int k = 0; k < VEC; k += 2) {
+        constexpr int W = VEC > 1 ? 2 : 1;
+        Lanes<double, W> a;
+#pragma unroll
+        for (int q = 0; q < W; ++q) a.x[q] = s[k + q];
+        lane_store<double, W>(p + k, a);
+    }
+}
+
+// the VEC values that begin at i0: US steps' loads in flight, the adds in step order.  acc is read and written here as
+// tm_load_sums / tm_store_sums do it, written out: through the two helpers the compiler allocates and schedules
+// k_time_mean<float, 4, 8> differently (612 of its 951 instructions, one more of them), and the kernels stay as measured.
 template <typename T, int VEC, int US>
 __device__ inline void tm_lane(double *acc, unsigned *cnt, const T *src, long nsteps, long long stride, size_t i0, T m1, T m2,
                                const TmFinish &f)
@@ -92,21 +84,21 @@ __device__ inline void tm_lane(double *acc, unsigned *cnt, const T *src, long ns
 #pragma unroll
         for (int k = 0; k < VEC; k += 2) {   // 16 bytes of acc at a time
             constexpr int W = VEC > 1 ? 2 : 1;
-            const TmLanes<double, W> a = tm_load<double, W, false>(acc + i0 + k);
+            const Lanes<double, W> a = lane_load<double, W, false>(acc + i0 + k);
 #pragma unroll
             for (int q = 0; q < W; ++q) s[k + q] = a.x[q];
         }
-        const TmLanes<unsigned, VEC> n0 = tm_load<unsigned, VEC, false>(cnt + i0);
+        const Lanes<unsigned, VEC> n0 = lane_load<unsigned, VEC, false>(cnt + i0);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) c[k] = n0.x[k];
     }
     const T *p = src + i0;
     for (long t = 0; t < nsteps; t += US) {
         const int nb = nsteps - t < US ? (int)(nsteps - t) : US;   // wave-uniform
-        TmLanes<T, VEC> x[US];
+        Lanes<T, VEC> x[US];
 #pragma unroll
         for (int r = 0; r < US; ++r)
-            if (r < nb) x[r] = tm_load<T, VEC, true>(p + (long long)r * stride);
+            if (r < nb) x[r] = lane_load<T, VEC, true>(p + (long long)r * stride);
 #pragma unroll
         for (int r = 0; r < US; ++r)
             if (r < nb) {
@@ -124,43 +116,18 @@ __device__ inline void tm_lane(double *acc, unsigned *cnt, const T *src, long ns
         for (int k = 0; k < VEC; ++k)
             s[k] = c[k] == 0u ? f.fill_out : (f.rule == NF_MEAN_OVER_STEPS ? s[k] / f.total_steps : s[k] / (double)c[k]);
     } else {
-        TmLanes<unsigned, VEC> n1;
+        Lanes<unsigned, VEC> n1;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) n1.x[k] = c[k];
-        tm_store<unsigned, VEC>(cnt + i0, n1);
+        lane_store<unsigned, VEC>(cnt + i0, n1);
     }
 #pragma unroll
     for (int k = 0; k < VEC; k += 2) {
         constexpr int W = VEC > 1 ? 2 : 1;
-        TmLanes<double, W> a;
+        Lanes<double, W> a;
 #pragma unroll
         for (int q = 0; q < W; ++q) a.x[q] = s[k + q];
-        tm_store<double, W>(acc + i0 + k, a);
-    }
-}
-
-// VEC float64 sums at p, 16 bytes at a time
-template <int VEC>
-__device__ inline void tm_load_sums(double (&s)[VEC], const double *p)
-{
-#pragma unroll
-    for (int k = 0; k < VEC; k += 2) {
-        constexpr int W = VEC > 1 ? 2 : 1;
-        const TmLanes<double, W> a = tm_load<double, W, false>(p + k);
-#pragma unroll
-        for (int q = 0; q < W; ++q) s[k + q] = a.x[q];
-    }
-}
-template <int VEC>
-__device__ inline void tm_store_sums(double *p, const double (&s)[VEC])
-{
-#pragma unroll
-    for (int k = 0; k < VEC; k += 2) {
-        constexpr int W = VEC > 1 ? 2 : 1;
-        TmLanes<double, W> a;
-#pragma unroll
-        for (int q = 0; q < W; ++q) a.x[q] = s[k + q];
-        tm_store<double, W>(p + k, a);
+        lane_store<double, W>(acc + i0 + k, a);
     }
 }
 
@@ -184,19 +151,19 @@ __device__ inline void tmw_lane(double *accf, double *acch, unsigned *cnt, const
     } else {
         tm_load_sums<VEC>(sF, accf + i0);
         tm_load_sums<VEC>(sH, acch + i0);
-        const TmLanes<unsigned, VEC> n0 = tm_load<unsigned, VEC, false>(cnt + i0);
+        const Lanes<unsigned, VEC> n0 = lane_load<unsigned, VEC, false>(cnt + i0);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) c[k] = n0.x[k];
     }
     const T *p = in.src + i0, *q = in.thk + i0;
     for (long t = 0; t < nsteps; t += US) {
         const int nb = nsteps - t < US ? (int)(nsteps - t) : US;   // wave-uniform
-        TmLanes<T, VEC> x[US], h[US];
+        Lanes<T, VEC> x[US], h[US];
 #pragma unroll
         for (int r = 0; r < US; ++r)
             if (r < nb) {
-                x[r] = tm_load<T, VEC, true>(p + (long long)r * in.src_stride);
-                h[r] = tm_load<T, VEC, true>(q + (long long)r * in.thk_stride);
+                x[r] = lane_load<T, VEC, true>(p + (long long)r * in.src_stride);
+                h[r] = lane_load<T, VEC, true>(q + (long long)r * in.thk_stride);
             }
 #pragma unroll
         for (int r = 0; r < US; ++r)
@@ -221,10 +188,10 @@ __device__ inline void tmw_lane(double *accf, double *acch, unsigned *cnt, const
             sH[k] = sH[k] / f.total_steps;
         }
     } else {
-        TmLanes<unsigned, VEC> n1;
+        Lanes<unsigned, VEC> n1;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) n1.x[k] = c[k];
-        tm_store<unsigned, VEC>(cnt + i0, n1);
+        lane_store<unsigned, VEC>(cnt + i0, n1);
     }
     tm_store_sums<VEC>(accf + i0, sF);
     tm_store_sums<VEC>(acch + i0, sH);
@@ -274,6 +241,16 @@ namespace {
 // at float64.
 constexpr int kTimeMeanSteps = 8;
 
+// one tile of 256 * VEC values per block: the number of tiles of n values, refused when one launch cannot hold them
+template <int VEC>
+int tm_tiles(size_t n, const char *what, unsigned *ntiles)
+{
+    const size_t per_block = 256u * (size_t)VEC, tiles = (n + per_block - 1) / per_block;
+    NF_REQUIRE(tiles <= 0x7ffffff0u, NF_ERR_ARG, std::string(what) + ": n is too large for one launch");
+    *ntiles = (unsigned)tiles;
+    return NF_OK;
+}
+
 struct TimeMeanArgs {
     double *acc;
     unsigned *cnt;
@@ -288,11 +265,10 @@ struct TimeMeanArgs {
 template <typename T, int VEC>
 int launch_time_mean_v(const TimeMeanArgs &a, hipStream_t s)
 {
-    const size_t per_block = 256u * (size_t)VEC;
-    const size_t ntiles = (a.n + per_block - 1) / per_block;
-    NF_REQUIRE(ntiles <= 0x7ffffff0u, NF_ERR_ARG, "nf_time_mean: n is too large for one launch");
-    hipLaunchKernelGGL((k_time_mean<T, VEC, kTimeMeanSteps>), dim3(xcd_grid((unsigned)ntiles)), dim3(256), 0, s, a.acc, a.cnt,
-                       (const T *)a.src, a.nsteps, a.stride, a.n, (unsigned)ntiles, (T)a.fill, (T)a.missing, a.f);
+    unsigned ntiles;
+    NF_TRY(tm_tiles<VEC>(a.n, "nf_time_mean", &ntiles));
+    hipLaunchKernelGGL((k_time_mean<T, VEC, kTimeMeanSteps>), dim3(xcd_grid(ntiles)), dim3(256), 0, s, a.acc, a.cnt,
+                       (const T *)a.src, a.nsteps, a.stride, a.n, ntiles, (T)a.fill, (T)a.missing, a.f);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
@@ -301,8 +277,7 @@ template <typename T, int VEC>
 int launch_time_mean_t(const TimeMeanArgs &a, hipStream_t s)
 {
     // every step, acc and cnt 16-byte aligned at every lane's first value: else one value per lane
-    bool al16 = (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.acc % 16 == 0 && (uintptr_t)a.cnt % 16 == 0;
-    if (a.nsteps > 1) al16 = al16 && (a.stride * (long long)sizeof(T)) % 16 == 0;
+    const bool al16 = lanes_aligned16({a.src, a.acc, a.cnt}, a.nsteps, {a.stride * (long long)sizeof(T)});
     return al16 ? launch_time_mean_v<T, VEC>(a, s) : launch_time_mean_v<T, 1>(a, s);
 }
 
@@ -329,13 +304,12 @@ struct TimeMeanWeightedArgs {
 template <typename T, int VEC>
 int launch_time_mean_weighted_v(const TimeMeanWeightedArgs &a, hipStream_t s)
 {
-    const size_t per_block = 256u * (size_t)VEC;
-    const size_t ntiles = (a.n + per_block - 1) / per_block;
-    NF_REQUIRE(ntiles <= 0x7ffffff0u, NF_ERR_ARG, "nf_time_mean_weighted: n is too large for one launch");
+    unsigned ntiles;
+    NF_TRY(tm_tiles<VEC>(a.n, "nf_time_mean_weighted", &ntiles));
     const TmwSeries<T> in{(const T *)a.src, (const T *)a.thk, a.src_stride, a.thk_stride,
                           (T)a.fill, (T)a.missing, (T)a.thk_fill, (T)a.thk_missing};
-    hipLaunchKernelGGL((k_time_mean_weighted<T, VEC, kTimeMeanWeightedSteps>), dim3(xcd_grid((unsigned)ntiles)), dim3(256), 0, s,
-                       a.accf, a.acch, a.cnt, in, a.nsteps, a.n, (unsigned)ntiles, a.f);
+    hipLaunchKernelGGL((k_time_mean_weighted<T, VEC, kTimeMeanWeightedSteps>), dim3(xcd_grid(ntiles)), dim3(256), 0, s, a.accf,
+                       a.acch, a.cnt, in, a.nsteps, a.n, ntiles, a.f);
     NF_HIP(hipGetLastError());
     return NF_OK;
 }
@@ -344,10 +318,8 @@ template <typename T, int VEC>
 int launch_time_mean_weighted_t(const TimeMeanWeightedArgs &a, hipStream_t s)
 {
     // every step of both series, accf, acch and cnt 16-byte aligned at every lane's first value: else one value per lane
-    bool al16 = (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.thk % 16 == 0 && (uintptr_t)a.accf % 16 == 0 &&
-                (uintptr_t)a.acch % 16 == 0 && (uintptr_t)a.cnt % 16 == 0;
-    if (a.nsteps > 1)
-        al16 = al16 && (a.src_stride * (long long)sizeof(T)) % 16 == 0 && (a.thk_stride * (long long)sizeof(T)) % 16 == 0;
+    const bool al16 = lanes_aligned16({a.src, a.thk, a.accf, a.acch, a.cnt}, a.nsteps,
+                                      {a.src_stride * (long long)sizeof(T), a.thk_stride * (long long)sizeof(T)});
     return al16 ? launch_time_mean_weighted_v<T, VEC>(a, s) : launch_time_mean_weighted_v<T, 1>(a, s);
 }
 

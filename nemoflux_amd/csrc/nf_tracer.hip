@@ -19,41 +19,9 @@
 // Cell-thickness form (nf_field_set_cell_thickness; trailing kernel argument ThickIn<T>): th_z becomes the thickness read at
 // the face, accU = fma(fixth(e3u[z, c]), fixed(u) * tfE, accU) and accV with e3v -- two more aligned non-temporal streams,
 // 5*sizeof(T) per (t,z,j,i).  The form without the argument is the kernel as it was, instruction for instruction.
-#include "nf_common.h"
+#include "nf_lanes.h"
 
 namespace nf {
-
-namespace {
-
-typedef double tr_dvec2 __attribute__((ext_vector_type(2)));
-typedef float tr_fvec4 __attribute__((ext_vector_type(4)));
-template <typename T, int VEC> struct tr_vec;
-template <> struct tr_vec<double, 2> { using type = tr_dvec2; };
-template <> struct tr_vec<float, 4> { using type = tr_fvec4; };
-template <> struct tr_vec<double, 1> { using type = double; };
-template <> struct tr_vec<float, 1> { using type = float; };
-
-template <typename T, int VEC> struct TrLanes {
-    T x[VEC];
-};
-
-// VEC consecutive values at p (16-byte aligned when ALIGNED)
-template <typename T, int VEC, bool NT, bool ALIGNED = true>
-__device__ inline TrLanes<T, VEC> tr_load(const T *p)
-{
-    TrLanes<T, VEC> r;
-    if (ALIGNED) {
-        using V = typename tr_vec<T, VEC>::type;
-        V v = NT ? __builtin_nontemporal_load(reinterpret_cast<const V *>(p)) : *reinterpret_cast<const V *>(p);
-        __builtin_memcpy(&r, &v, sizeof(V));
-    } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) r.x[k] = p[k];
-    }
-    return r;
-}
-
-}  // namespace
 
 // 256 threads, one chunk of VEC cells per lane: lane c0 = (tile * 256 + tid) * VEC.  ncell % VEC == 0 and nx >= VEC (the
 // launcher picks VEC = 1 otherwise), so a lane's cells hold at most one row end.  NAL: nx % VEC == 0, the north stream is
@@ -101,20 +69,20 @@ __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, co
     const T *pf = CT ? ct.e3v + (long)z0 * ncell + cs : nullptr;
     for (int z = z0; z < z1; z += UZ) {
         const int nlev = z1 - z < UZ ? z1 - z : UZ;
-        TrLanes<T, VEC> lu[UZ], lv[UZ], lt[UZ], ln[UZ];
-        TrLanes<T, VEC> le[CT ? UZ : 1], lf[CT ? UZ : 1];
+        Lanes<T, VEC> lu[UZ], lv[UZ], lt[UZ], ln[UZ];
+        Lanes<T, VEC> le[CT ? UZ : 1], lf[CT ? UZ : 1];
         T nx1[UZ], wv[UZ];
 #pragma unroll
         for (int r = 0; r < UZ; ++r)
             if (r < nlev) {
                 const long o = (long)r * ncell;
                 if (on) {
-                    lu[r] = tr_load<T, VEC, true>(pu + o);
-                    lv[r] = tr_load<T, VEC, true>(pv + o);
-                    lt[r] = tr_load<T, VEC, false>(pt + o);
+                    lu[r] = lane_load<T, VEC, true>(pu + o);
+                    lv[r] = lane_load<T, VEC, true>(pv + o);
+                    lt[r] = lane_load<T, VEC, false>(pt + o);
                     if constexpr (CT) {
-                        le[r] = tr_load<T, VEC, true>(pe + o);
-                        lf[r] = tr_load<T, VEC, true>(pf + o);
+                        le[r] = lane_load<T, VEC, true>(pe + o);
+                        lf[r] = lane_load<T, VEC, true>(pf + o);
                     }
                 } else {
 #pragma unroll
@@ -125,7 +93,7 @@ __global__ __launch_bounds__(256) void k_tracer_flux(const T *__restrict__ u, co
                     }
                 }
                 if (north_all) {
-                    ln[r] = tr_load<T, VEC, false, NAL>(pt + o + nx);
+                    ln[r] = lane_load<T, VEC, false, NAL>(pt + o + nx);
                 } else {
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) ln[r].x[k] = has_n[k] ? pt[o + nx + k] : T(0);
@@ -206,13 +174,13 @@ int launch_tracer_t(const TracerArgs &a, hipStream_t s)
     const unsigned grid = xcd_grid(ntiles);
     if (a.th.e3u)
         hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevelsCellThick, NAL, ThickIn<T>>), dim3(grid), dim3(256), 0, s,
-                           (const T *)in.u, (const T *)in.v, (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1,
-                           in.thickness, in.arcE, in.arcN, (T)in.fill, (T)in.fill2, (T)a.tfill, (T)a.tfill2, a.ref,
-                           a.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.planes, ntiles, thick_in<T>(a.th));
+                           (const T *)in.u, (const T *)in.v, (const T *)a.t.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                           in.thickness, in.arcE, in.arcN, (T)in.fill, (T)in.fill2, (T)a.t.fill, (T)a.t.fill2, a.t.ref,
+                           a.t.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.planes, ntiles, thick_in<T>(a.th));
     else
         hipLaunchKernelGGL((k_tracer_flux<T, VEC, kTracerLevels, NAL>), dim3(grid), dim3(256), 0, s, (const T *)in.u,
-                           (const T *)in.v, (const T *)a.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
-                           in.arcN, (T)in.fill, (T)in.fill2, (T)a.tfill, (T)a.tfill2, a.ref, a.wrap_x ? 1 : 0, in.scale,
+                           (const T *)in.v, (const T *)a.t.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
+                           in.arcN, (T)in.fill, (T)in.fill2, (T)a.t.fill, (T)a.t.fill2, a.t.ref, a.t.wrap_x ? 1 : 0, in.scale,
                            in.sverdrup, a.planes, ntiles);
     NF_HIP(hipGetLastError());
     return NF_OK;
@@ -222,9 +190,7 @@ template <typename T, int VEC>
 int launch_tracer_v(const TracerArgs &a, hipStream_t s)
 {
     const StepInput &in = a.in;
-    const bool al16 = ((uintptr_t)in.u % 16 == 0) && ((uintptr_t)in.v % 16 == 0) && ((uintptr_t)a.tau % 16 == 0) &&
-                      ((uintptr_t)a.th.e3u % 16 == 0) && ((uintptr_t)a.th.e3v % 16 == 0);
-    if (al16 && in.ncell % VEC == 0 && in.nx >= VEC)
+    if (lanes_aligned16({in.u, in.v, a.t.tau, a.th.e3u, a.th.e3v}) && in.ncell % VEC == 0 && in.nx >= VEC)
         return in.nx % VEC == 0 ? launch_tracer_t<T, VEC, true>(a, s) : launch_tracer_t<T, VEC, false>(a, s);
     return launch_tracer_t<T, 1, true>(a, s);   // odd sizes / unaligned fields: one cell per lane
 }
@@ -236,7 +202,7 @@ int launch_tracer_flux(const TracerArgs &a, hipStream_t s)
     NF_REQUIRE(in.ncell > 0 && in.nx > 0 && in.ncell == in.ny * in.nx && in.ncell < (1l << 31), NF_ERR_ARG,
                "tracer flux: bad grid sizes");
     NF_REQUIRE(in.z1 > in.z0 && in.z0 >= 0, NF_ERR_ARG, "tracer flux: empty z range");
-    NF_REQUIRE(in.u && in.v && a.tau && a.planes && in.thickness && in.arcE && in.arcN && (!a.th.e3u || a.th.e3v), NF_ERR_ARG,
+    NF_REQUIRE(in.u && in.v && a.t.tau && a.planes && in.thickness && in.arcE && in.arcN && (!a.th.e3u || a.th.e3v), NF_ERR_ARG,
                "tracer flux: null argument");
     if (in.dtype == NF_F64) return launch_tracer_v<double, 2>(a, s);
     if (in.dtype == NF_F32) return launch_tracer_v<float, 4>(a, s);

@@ -594,8 +594,8 @@ class Field(object):
         if hasattr(tracer, 'read_step'):
             # file-backed: step t is read into one pinned host buffer and handed over as a host-resident tracer through a
             # virtual (nt, nz, ny, nx) base that the engine only dereferences at step t (as _stage does for uo / vo)
-            slot['lazy'] = tracer
-            slot['buf'] = self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('='))
+            slot['lazy'] = (tracer,)
+            slot['buf'] = (self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('=')),)
             ptr = None
         elif ptr is None:
             tracer = _native(tracer)
@@ -607,11 +607,14 @@ class Field(object):
         return slot
 
     def _stage_slot(self, slot, tIndex):
-        """make step tIndex of a file-backed tracer slot the one the engine reads (no-op for in-memory / HBM tracers)"""
+        """make step tIndex of a file-backed slot -- a tracer, or the e3u / e3v pair of a time-varying cell thickness -- the one
+        the engine reads (no-op for in-memory / HBM arrays)"""
         if slot is not None and slot['lazy'] is not None and slot['step'] != tIndex:
-            buf = slot['buf']
-            slot['lazy'].read_step(tIndex, out=buf)
-            check(slot['set'](ctypes.byref(self._h), buf.ctypes.data - tIndex * buf.nbytes, self.nt, slot['code'], 0,
+            for src, buf in zip(slot['lazy'], slot['buf']):
+                src.read_step(tIndex, out=buf)
+            # a virtual (nt, nz, ny, nx) base that the engine only dereferences at step tIndex
+            off = tIndex * slot['buf'][0].nbytes
+            check(slot['set'](ctypes.byref(self._h), *[buf.ctypes.data - off for buf in slot['buf']], self.nt, slot['code'], 0,
                               slot['fill']))
             slot['step'] = tIndex
 
@@ -685,7 +688,8 @@ class Field(object):
         if len(markers) > 2:
             raise RuntimeError(f'ERROR: e3u / e3v carry {len(markers)} different _FillValue / missing_value markers '
                                f'({markers}); the engine masks at most two')
-        slot = dict(lazy=None, step=-1, nt=nt_th, fill=numpy.nan if fill_value is None else float(fill_value),
+        slot = dict(lazy=None, step=-1, set=lib.nf_field_set_cell_thickness, code=self._uv_code, nt=nt_th,
+                    fill=numpy.nan if fill_value is None else float(fill_value),
                     missing=numpy.nan if missing_value is None else float(missing_value), keep=[], arrays=[])
         ptrs, on_dev, lazy = [], None, []
         for (e3, _), which in zip(arrs, ('e3u', 'e3v')):
@@ -731,15 +735,7 @@ class Field(object):
 
     def _stage_cell_thickness(self, tIndex):
         """make step tIndex of a file-backed, time-varying cell thickness the one the engine reads"""
-        e3 = getattr(self, '_e3', None)
-        if e3 is not None and e3['lazy'] is not None and e3['step'] != tIndex:
-            bu, bv = e3['buf']
-            e3['lazy'][0].read_step(tIndex, out=bu)
-            e3['lazy'][1].read_step(tIndex, out=bv)
-            off = tIndex * bu.nbytes     # a virtual (nt, nz, ny, nx) base that the engine only dereferences at step tIndex
-            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), bu.ctypes.data - off, bv.ctypes.data - off, self.nt,
-                                                  self._uv_code, 0, e3['fill']))
-            e3['step'] = tIndex
+        self._stage_slot(getattr(self, '_e3', None), tIndex)
 
     def computeTracerFlux(self, tIndex):
         """Tracer transport of time step tIndex across the transects (setTracer first): (ntransect,) totals and (nseg,)
@@ -919,78 +915,36 @@ class Field(object):
             raise RuntimeError(f'ERROR: steps must be None or a half-open (t0, t1) with 0 <= t0 < t1 <= {self.nt}, got {steps}')
         return t0, t1
 
-    def _time_mean_array(self, a, markers, rule, t0, t1):
-        """The mean over the steps [t0, t1) of a (nt, nz, ny, nx) array in any of its three homes (HBM, host, file-backed), by
-        nf_time_mean: a float64 torch CUDA tensor (1, nz, ny, nx) and its fill -- the first marker as the dtype of `a` holds it,
-        NaN without one -- which stands where the value is missing at every step."""
+    def _time_mean_walk(self, series, markers, t0, t1, nacc, kernel):
+        """The steps [t0, t1) of a list of (nt, nz, ny, nx) arrays of one dtype, each in any of its three homes (HBM, host,
+        file-backed), through one of the time-mean kernels into `nacc` float64 torch CUDA tensors (1, nz, ny, nx).
+        kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total_steps, fill_out) makes the C call for nsteps
+        steps that begin at the HBM addresses ptrs (one per series); fill / missing: `markers` without NaN.  Returns the
+        tensors and fill_out -- the first marker as the dtype of the arrays holds it, NaN without one -- which stands where
+        the value is missing at every step.  The bits do not depend on the homes or on the grouping of the steps."""
         import torch
-        dt = numpy.dtype(_native_dtype(a))
-        code = NF_F32 if dt == numpy.float32 else NF_F64
-        marks = [float(m) for m in markers if m == m]
-        with numpy.errstate(over='ignore'):
-            fill_out = float(dt.type(marks[0])) if marks else numpy.nan
-        fill, missing = (marks + [numpy.nan, numpy.nan])[:2]
-        n = self.nz * self.ny * self.nx
-        acc = torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda')
-
-        def run(ptr, nsteps, first, last, cnt=None):
-            check(lib.nf_time_mean(acc.data_ptr(), None if cnt is None else cnt.data_ptr(), ptr, nsteps, n, n, code, fill, missing,
-                                   1 if first else 0, 1 if last else 0, rule, t1 - t0, fill_out, None))
-
-        ptr = _lib.device_pointer(a)
-        if ptr is not None:       # HBM: one pass, nothing carried
-            run(ptr + t0 * n * dt.itemsize, t1 - t0, True, True)
-        else:
-            cnt = torch.empty(n, dtype=torch.int32, device='cuda')
-            lazy = hasattr(a, 'read_step')
-            if lazy:              # file-backed: one step at a time through one pinned buffer
-                group, buf = 1, self._host_array((self.nz, self.ny, self.nx), dt)
-            else:
-                group, host = max(1, self._MEAN_STAGE_BYTES // (n * dt.itemsize)), _native(a).reshape(self.nt, n)
-            stage = _lib.DeviceBuffer(min(group, t1 - t0) * n * dt.itemsize)
-            for t in range(t0, t1, group):
-                k = min(group, t1 - t)
-                if lazy:
-                    a.read_step(t, out=buf)
-                check(lib.nf_memcpy_h2d(stage.ptr, buf.ctypes.data if lazy else host[t:t + k].ctypes.data, k * n * dt.itemsize))
-                run(stage.ptr, k, t == t0, t + k == t1, cnt)
-                check(lib.nf_synchronize())     # the staging buffer is written again by the next group
-            stage.free()
-        check(lib.nf_synchronize())
-        return acc, fill_out
-
-    def _time_mean_weighted_arrays(self, a, markers, thk, thk_markers, t0, t1):
-        """The thickness-weighted mean over the steps [t0, t1) of the (nt, nz, ny, nx) velocity `a` and the mean of the
-        thickness `thk` at its points, by nf_time_mean_weighted; each of the two in any of the three homes (HBM, host,
-        file-backed), which the bits do not depend on.  Returns two float64 torch CUDA tensors (1, nz, ny, nx) and the fill of
-        the first (as in _time_mean_array)."""
-        import torch
-        dt = numpy.dtype(_native_dtype(a))
-        if numpy.dtype(_native_dtype(thk)) != dt:
-            raise RuntimeError(f'ERROR: timeMean: the cell thickness is {numpy.dtype(_native_dtype(thk)).name}, uo/vo are {dt.name}')
+        dt = numpy.dtype(_native_dtype(series[0]))
         code, size = (NF_F32 if dt == numpy.float32 else NF_F64), dt.itemsize
         marks = [float(m) for m in markers if m == m]
         with numpy.errstate(over='ignore'):
             fill_out = float(dt.type(marks[0])) if marks else numpy.nan
         fill, missing = (marks + [numpy.nan, numpy.nan])[:2]
         n = self.nz * self.ny * self.nx
-        accf, acch = (torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda') for _ in range(2))
+        accs = [torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda') for _ in range(nacc)]
 
-        def run(pa, ph, nsteps, first, last, cnt=None):
-            check(lib.nf_time_mean_weighted(accf.data_ptr(), acch.data_ptr(), None if cnt is None else cnt.data_ptr(), pa, n, ph, n,
-                                            nsteps, n, code, fill, missing, float(thk_markers[0]), float(thk_markers[1]),
-                                            1 if first else 0, 1 if last else 0, t1 - t0, fill_out, None))
+        def run(cur, nsteps, first, last, cnt=None):
+            kernel([x.data_ptr() for x in accs], None if cnt is None else cnt.data_ptr(), cur, nsteps, n, code, fill, missing,
+                   1 if first else 0, 1 if last else 0, t1 - t0, fill_out)
 
-        series = (a, thk)
         ptrs = [_lib.device_pointer(x) for x in series]
-        if ptrs[0] is not None and ptrs[1] is not None:       # both in HBM: one pass, nothing carried
-            run(ptrs[0] + t0 * n * size, ptrs[1] + t0 * n * size, t1 - t0, True, True)
+        staged = [p is None for p in ptrs]
+        if not any(staged):       # all in HBM: one pass, nothing carried
+            run([p + t0 * n * size for p in ptrs], t1 - t0, True, True)
         else:
             cnt = torch.empty(n, dtype=torch.int32, device='cuda')
-            staged = [p is None for p in ptrs]
             lazy = [hasattr(x, 'read_step') for x in series]
             # file-backed: one step at a time through a pinned buffer; host arrays: groups of steps, the staging buffers of
-            # the two series together within _MEAN_STAGE_BYTES
+            # all the series together within _MEAN_STAGE_BYTES
             group = 1 if any(lazy) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
             bufs = [self._host_array((self.nz, self.ny, self.nx), dt) if z else None for z in lazy]
             hosts = [_native(x).reshape(self.nt, n) if st and not z else None for x, st, z in zip(series, staged, lazy)]
@@ -998,7 +952,7 @@ class Field(object):
             for t in range(t0, t1, group):
                 k = min(group, t1 - t)
                 cur = []
-                for j in range(2):
+                for j in range(len(series)):
                     if not staged[j]:
                         cur.append(ptrs[j] + t * n * size)
                         continue
@@ -1007,12 +961,37 @@ class Field(object):
                     check(lib.nf_memcpy_h2d(stage[j].ptr, bufs[j].ctypes.data if lazy[j] else hosts[j][t:t + k].ctypes.data,
                                             k * n * size))
                     cur.append(stage[j].ptr)
-                run(cur[0], cur[1], k, t == t0, t + k == t1, cnt)
+                run(cur, k, t == t0, t + k == t1, cnt)
                 check(lib.nf_synchronize())     # the staging buffers are written again by the next group
             for b in stage:
                 if b is not None:
                     b.free()
         check(lib.nf_synchronize())
+        return accs, fill_out
+
+    def _time_mean_array(self, a, markers, rule, t0, t1):
+        """The mean over the steps [t0, t1) of a (nt, nz, ny, nx) array in any of its three homes, by nf_time_mean: a float64
+        torch CUDA tensor (1, nz, ny, nx) and its fill (_time_mean_walk)."""
+        def kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total, fill_out):
+            check(lib.nf_time_mean(accs[0], cnt, ptrs[0], nsteps, n, n, code, fill, missing, first, last, rule, total, fill_out,
+                                   None))
+
+        (acc,), fill_out = self._time_mean_walk([a], markers, t0, t1, 1, kernel)
+        return acc, fill_out
+
+    def _time_mean_weighted_arrays(self, a, markers, thk, thk_markers, t0, t1):
+        """The thickness-weighted mean over the steps [t0, t1) of the (nt, nz, ny, nx) velocity `a` and the mean of the
+        thickness `thk` at its points, by nf_time_mean_weighted; each of the two in any of the three homes.  Returns two
+        float64 torch CUDA tensors (1, nz, ny, nx) and the fill of the first (_time_mean_walk)."""
+        dt = numpy.dtype(_native_dtype(a))
+        if numpy.dtype(_native_dtype(thk)) != dt:
+            raise RuntimeError(f'ERROR: timeMean: the cell thickness is {numpy.dtype(_native_dtype(thk)).name}, uo/vo are {dt.name}')
+
+        def kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total, fill_out):
+            check(lib.nf_time_mean_weighted(accs[0], accs[1], cnt, ptrs[0], n, ptrs[1], n, nsteps, n, code, fill, missing,
+                                            float(thk_markers[0]), float(thk_markers[1]), first, last, total, fill_out, None))
+
+        (accf, acch), fill_out = self._time_mean_walk([a, thk], markers, t0, t1, 2, kernel)
         return accf, acch, fill_out
 
     def timeMean(self, steps=None, thicknessWeighted=False):

@@ -19,7 +19,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def asm_of(commit, tmp, src):
     d = os.path.join(tmp, 'worktree' if commit == '.' else commit.replace('/', '_'))
-    for rel in ('nemoflux_amd/csrc/' + src, 'nemoflux_amd/csrc/nf_common.h', 'include/nemoflux_amd.h'):
+    csrc = 'nemoflux_amd/csrc/'
+    # every header of csrc/ that exists at the commit being built
+    names = os.listdir(os.path.join(ROOT, csrc)) if commit == '.' else subprocess.check_output(
+        ['git', '-C', ROOT, 'ls-tree', '--name-only', f'{commit}:{csrc[:-1]}'], text=True).split()
+    for rel in [csrc + src, 'include/nemoflux_amd.h'] + [csrc + h for h in sorted(names) if h.endswith('.h')]:
         os.makedirs(os.path.dirname(os.path.join(d, rel)), exist_ok=True)
         with open(os.path.join(d, rel), 'wb') as f:
             f.write(open(os.path.join(ROOT, rel), 'rb').read() if commit == '.' else
