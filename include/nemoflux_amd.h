@@ -378,6 +378,32 @@ int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *ro
  * P(carry = 1) / P(carry = 0) + ref, where the tracer is present wherever the velocity is. */
 int nf_field_compute_gross_profile(nf_field **self, long tIndex, int carry, double *rows_host);       /* (2, nz, row_length): P, N */
 int nf_field_compute_gross_profile_async(nf_field **self, long tIndex, int carry, double *rows_dev);  /* HBM, field's stream */
+/* Gross transports in tracer classes: the inflow and the outflow of every class -- the dense overflow against the light water
+ * above it, the two layers of a strait, a recirculating limb that the net class transport hides.  Needs nf_field_set_tracer
+ * and nf_field_set_class_edges (else NF_ERR_STATE, as nf_field_compute_class_transport).  One time step t over the owned
+ * levels; for every weight record and every slot i, in the order south, east, north, west:
+ *   d_i  the slot's water term of nf_field_compute_gross_profile: the masked velocity, the arc, the Sverdrup scale, and the
+ *        thickness thickness[z] or, with a cell thickness set, fixth(e3u) / fixth(e3v) at the slot's own face; 0 for the south
+ *        slot of row 0
+ *   q_i = w_i * d_i
+ *   c_i = q_i (carry = 0), or w_i * d_i^tau (carry = 1), d^tau the slot's term of the tracer profile: fixed(.) * tf, tf the face
+ *        value of the tracer of nf_field_set_tracer minus its reference, 0 for a face without a value
+ *   r_i  the class row of the slot's face, 0 .. n+1 as in nf_field_compute_class_transport (n+1: no class value), from the raw
+ *        face value of the class field: the class tracer when one is set, else the tracer; wrap_x is the tracer's
+ *   P[r_i] += c_i where q_i > 0,   N[r_i] += c_i where q_i < 0;   q_i == 0: in neither.
+ * A lane's accumulator of a row starts at +0.0 and takes its terms with z ascending and the slots in order; then the fixed tree
+ * of the transect reduction follows: no atomics, bitwise reproducible.  rows (2, n + 2, row_length): P then N, each row
+ * [segments | transects], written whole; a step this rank does not touch gives exact zeros.  Unlike the net class forms these
+ * calls TAKE a cell thickness: P + N is the class transport (carry = 0) or the class tracer transport (carry = 1) up to
+ * rounding, and the only route to them under partial steps or z* thicknesses.  Negating uo and vo gives P' == -N, N' == -P;
+ * a class field equal to the level index with edges at the half-integers gives the rows of nf_field_compute_gross_profile,
+ * both bit for bit.  With carry = 0, P >= 0 >= N.  The terms go through the term table of the joint class transport (40 bytes
+ * x records x owned levels, allocated on first use, an error that names the size when it cannot be; the joint_window and
+ * joint_skip knobs apply).  carry other than 0 or 1: NF_ERR_ARG.  Host-resident uo / vo, tracers and time-varying cell
+ * thickness are staged per step.  The calls change neither the resident planes, |.| arrays, running max, last row, tracer
+ * planes, class or joint state nor a captured pass. */
+int nf_field_compute_gross_class_transport(nf_field **self, long tIndex, int carry, double *rows_host);       /* (2, n+2, row_length): P, N */
+int nf_field_compute_gross_class_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev);  /* HBM, field's stream */
 /* Class tracer: a second, optional tracer at T-points (potential density sigma) that gives the faces their class value
  * instead of the tracer of nf_field_set_tracer, which is then only carried (heat by density class).  Same (nt,nz,ny,nx) and
  * dtype as uo/vo (else NF_ERR_ARG, the message naming both; set_uv first: NF_ERR_STATE); host (staged per step into a buffer

@@ -556,6 +556,33 @@ struct JointArgs {
 inline int joint_flag_words(int nrows, int window) { return ((nrows + window - 1) / window + 31) / 32; }
 int launch_joint_class_transport(const JointArgs &a, hipStream_t s);
 
+// Gross (inflow / outflow) transports in tracer classes (nf_field_compute_gross_class_transport, nf_integral.hip): the terms of
+// the gross profile -- volume form, or carried form with carry.tau set -- sent to the class row of their own face instead of
+// their level: rows (2, nedges + 2, row_length) = P, N, row part * (nedges + 2) + r of JointArgs' term table and window bitmap
+// (layout above), binned by the joint classes' stage 2.  th.e3u set: every slot's term takes the thickness at its own face.
+// Stage 1 issues the gathers of kGrossClassLevels levels together, the joint classes' batch: no instantiation uses scratch
+// memory (-Rpass-analysis=kernel-resource-usage; DESIGN.md has the registers and what two levels gave for the widest form).
+constexpr int kGrossClassLevels = 4;
+struct GrossClassArgs {
+    StepInput in;
+    TracerIn cls;                // the class field; its wrap_x is the rule of every face, its ref is not read
+    TracerIn carry;              // the carried tracer (the class field itself, or another array); tau == nullptr: volume form
+    CellThick th;
+    const double *edges = nullptr;   // device, nedges
+    int nedges = 0;
+    int window = 0;              // rows per pass over the table, 1 .. kClassWindowMax
+    int skip = 1;                // 1: a stage-2 block whose flag is clear does not read the table
+    Transects tr;
+    char *table = nullptr;       // kJointEntryBytes * nrec * (z1 - z0) bytes
+    size_t table_len = 0;
+    unsigned *flags = nullptr;   // blocks * joint_flag_words(2 * (nedges + 2), window) words
+    size_t flags_len = 0;
+    double *scratch = nullptr;   // nrec * window run sums
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // (2 * (nedges + 2), row_length)
+};
+int launch_gross_class_transport(const GrossClassArgs &a, hipStream_t s);
+
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q
 int launch_find_points(const double *xy, long ncell, long row_length, LocatorBoxes *keep, const double *targets_dev, long npts,

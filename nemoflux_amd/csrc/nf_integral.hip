@@ -1020,6 +1020,13 @@ typedef unsigned short usvec4 __attribute__((ext_vector_type(4)));
 
 // Stage 1.  LDS: ea (na doubles), eb (nbe doubles), then the block's window bitmap (nwords words), filled with LDS OR -- the
 // outcome does not depend on the order -- and stored with one vector store per word.
+// joint_mark_window: a term with row `row` was written, so the block's bit of that row's window is set.
+__device__ inline void joint_mark_window(unsigned *bits, int row, int window)
+{
+    const int w = row / window;
+    const unsigned m = 1u << (w & 31);
+    if (!(bits[w >> 5] & m)) atomicOr(&bits[w >> 5], m);   // the read only spares the OR: a stale 0 sets the bit again
+}
 template <typename T, bool CARRY>
 __global__ __launch_bounds__(kBlock) void k_joint_terms(const int *__restrict__ cell, const double *__restrict__ w4, long n,
                                                         const T *__restrict__ u, const T *__restrict__ v,
@@ -1050,9 +1057,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_terms(const int *__restrict__ 
             const int ra = class_row(h, f, ea, na, topa);
             h = tr_face_raw<T>(b0, b1, has, sfill, sfill2, &f);
             const int row = ra * (nbe + 2) + class_row(h, f, eb, nbe, topb);
-            const int w = row / window;
-            const unsigned m = 1u << (w & 31);
-            if (!(bits[w >> 5] & m)) atomicOr(&bits[w >> 5], m);   // the read only spares the OR: a stale 0 sets the bit again
+            joint_mark_window(bits, row, window);
             return (unsigned short)row;
         };
         for (int z = z0; z < z1; z += kJointLevels) {
@@ -1152,12 +1157,29 @@ __global__ __launch_bounds__(kBlock) void k_joint_bin(const int *__restrict__ se
     }
 }
 
+// stage 2 over all `nrows` rows of a term table of `nlev` levels, `window` rows per pass, each pass finalized into its rows of
+// `out` (nrows, row_length): shared by the joint classes and the gross class transport
+static int launch_joint_bins(const Transects &tr, int nrows, int nlev, int window, int skip, const dvec2 *terms,
+                             const usvec4 *rows, const unsigned *flags, int nwords, double *scratch, double *out, hipStream_t s)
+{
+    const WeightSet &ws = *tr.ws;
+    const long row_length = tr.row_length();
+    for (int r0 = 0, win = 0; r0 < nrows; r0 += window, ++win) {
+        const int nwin = nrows - r0 < window ? nrows - r0 : window;
+        if (ws.nrec > 0)
+            hipLaunchKernelGGL(k_joint_bin, record_grid(ws), dim3(kBlock), sizeof(double) * (size_t)nwin * kBlock, s, ws.seg.get(),
+                               ws.nrec, nlev, terms, rows, flags, nwords, win, skip ? 1 : 0, r0, nwin, scratch);
+        launch_finalize(tr, ws.seg_start.get(), ws.nrec, scratch, out + (long)r0 * row_length, row_length, (unsigned)nwin, s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
 template <typename T, bool CARRY>
 static int launch_joint_t(const JointArgs &a, hipStream_t s)
 {
     const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
-    const long row_length = a.tr.row_length();
     const int nrows = (a.na + 2) * (a.nb + 2), nlev = in.z1 - in.z0;
     const int nwords = joint_flag_words(nrows, a.window);
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
@@ -1175,15 +1197,7 @@ static int launch_joint_t(const JointArgs &a, hipStream_t s)
                            terms, rows, a.flags);
         NF_HIP(hipGetLastError());
     }
-    for (int r0 = 0, win = 0; r0 < nrows; r0 += a.window, ++win) {
-        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
-        if (ws.nrec > 0)
-            hipLaunchKernelGGL(k_joint_bin, record_grid(ws), dim3(kBlock), sizeof(double) * (size_t)nwin * kBlock, s, ws.seg.get(),
-                               ws.nrec, nlev, terms, rows, a.flags, nwords, win, a.skip ? 1 : 0, r0, nwin, a.scratch);
-        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length, (unsigned)nwin, s);
-        NF_HIP(hipGetLastError());
-    }
-    return NF_OK;
+    return launch_joint_bins(a.tr, nrows, nlev, a.window, a.skip, terms, rows, a.flags, nwords, a.scratch, a.rows, s);
 }
 
 int launch_joint_class_transport(const JointArgs &a, hipStream_t s)
@@ -1205,6 +1219,154 @@ int launch_joint_class_transport(const JointArgs &a, hipStream_t s)
     if (in.dtype == NF_F64) return a.carry ? launch_joint_t<double, true>(a, s) : launch_joint_t<double, false>(a, s);
     if (in.dtype == NF_F32) return a.carry ? launch_joint_t<float, true>(a, s) : launch_joint_t<float, false>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "joint class transport: dtype must be NF_F64 or NF_F32");
+}
+
+// ---- gross (inflow / outflow) transports in tracer classes: k_gross_class_terms, then k_joint_bin ---------------------
+// Where the gross profile and the class transport cross: per (record, owned level, slot) the water term q = w * d of
+// k_gross_segscan, the carried term c (= q in the volume form, w * d^tau in the carried form) and the class row r of the slot's
+// face, k_class_segscan's; c goes to row r of P where q > 0 and to row r of N where q < 0 -- row part * (nedges + 2) + r of the
+// term table, part 0 = P, 1 = N -- and a slot with q == 0 (row 0's south slot among them) to kJointNoRow.  The table and the
+// window bitmap are JointArgs', so stage 2 is k_joint_bin as it stands: a lane's accumulator of a row starts at +0.0 and takes
+// its terms z ascending, slots in order.  The widest form gathers 4 + 4 + 5 + 5 values per level, once.
+// FORM: 0 = volume, 1 = carried tracer that is the class field (one set of 5 gathers), 2 = carried tracer and a class field of
+// its own.  TI: empty or ThickIn<T>, the per-cell thicknesses.  LZ: the levels whose gathers are issued together.
+// LDS: the edges (nedges doubles), then the block's window bitmap (nwords words).
+template <typename T, int FORM, int LZ, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_gross_class_terms(const int *__restrict__ cell, const double *__restrict__ w4, long n,
+                                                              const T *__restrict__ u, const T *__restrict__ v, long ncell,
+                                                              unsigned nx, int z0, int z1, const double *__restrict__ thickness,
+                                                              const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                              T fill, T fill2, int two, TauIn<T> cls, TauIn<T> carry, double scale,
+                                                              int sverdrup, const double *__restrict__ edges, int nedges, int top,
+                                                              int window, int nwords, dvec2 *__restrict__ terms,
+                                                              usvec4 *__restrict__ rows, unsigned *__restrict__ flags, TI... extra)
+{
+    constexpr bool CT = sizeof...(TI) > 0;
+    const ThickIn<T> ct = thick_arg<T>(extra...);
+    extern __shared__ double gross_class_lds[];
+    const double *e = gross_class_lds;
+    unsigned *bits = reinterpret_cast<unsigned *>(gross_class_lds + nedges);
+    for (int q = threadIdx.x; q < nedges; q += kBlock) gross_class_lds[q] = edges[q];
+    for (int q = threadIdx.x; q < nwords; q += kBlock) bits[q] = 0u;
+    __syncthreads();
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    if (k < n) {
+        const Record r = load_record(cell, w4, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, cls.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        // the row of a slot with water term q whose face has the class values (a0, a1); its window is marked in the bitmap
+        auto gross_row = [&](double q, T a0, T a1, bool has) {
+            if (!(q > 0.0) && !(q < 0.0)) return (unsigned short)kJointNoRow;
+            double f;
+            const bool h = tr_face_raw<T>(a0, a1, has, cls.m1, cls.m2, &f);
+            const int row = (q < 0.0 ? nedges + 2 : 0) + class_row(h, f, e, nedges, top);
+            joint_mark_window(bits, row, window);
+            return (unsigned short)row;
+        };
+        for (int z = z0; z < z1; z += LZ) {
+            const int nlev = z1 - z < LZ ? z1 - z : LZ;
+            LevelUV<T> x[LZ];
+            LevelUV<T> e3[CT ? LZ : 1];
+            LevelTau<T> S[LZ];                    // the class field
+            LevelTau<T> A[FORM == 2 ? LZ : 1];    // the carried tracer, when it is another array
+#pragma unroll
+            for (int l = 0; l < LZ; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
+                    S[l] = load_level_tau(cls.tau, o, r.c, nb);
+                    if constexpr (FORM == 2) A[l] = load_level_tau(carry.tau, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < LZ; ++l)
+                if (l < nlev) {
+                    SlotTh th;
+                    if constexpr (CT)
+                        th = level_th(e3[l], ct);
+                    else
+                        th = slot_th(thickness[z + l]);
+                    const Slots q = weighted_slots(
+                        r, level_slots_tf<T, false>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, FaceTf{}));
+                    Slots c = q;
+                    if constexpr (FORM != 0)
+                        c = weighted_slots(r, level_slots_tf<T, true>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south,
+                                                                      level_tf(FORM == 2 ? A[l] : S[l], nb, carry)));
+                    usvec4 jr;
+                    jr.x = nb.south ? gross_row(q.s, S[l].s, S[l].c, true) : (unsigned short)kJointNoRow;
+                    jr.y = gross_row(q.e, S[l].c, S[l].e, nb.has_e);
+                    jr.z = gross_row(q.n, S[l].c, S[l].n, nb.has_n);
+                    jr.w = gross_row(q.w, S[l].w, S[l].c, nb.has_w);
+                    const long zi = z + l - z0;
+                    __builtin_nontemporal_store(dvec2{c.s, c.e}, terms + (2 * zi) * n + k);
+                    __builtin_nontemporal_store(dvec2{c.n, c.w}, terms + (2 * zi + 1) * n + k);
+                    __builtin_nontemporal_store(jr, rows + zi * n + k);
+                }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < nwords; q += kBlock) flags[(long)blockIdx.x * nwords + q] = bits[q];
+}
+
+template <typename T, int FORM, typename... TI>
+static int launch_gross_class_t(const GrossClassArgs &a, hipStream_t s, TI... extra)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const int nrows = 2 * (a.nedges + 2), nlev = in.z1 - in.z0;
+    const int nwords = joint_flag_words(nrows, a.window);
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    int top = 1;
+    while (2 * top <= a.nedges) top *= 2;
+    dvec2 *terms = reinterpret_cast<dvec2 *>(a.table);
+    usvec4 *rows = reinterpret_cast<usvec4 *>(a.table + sizeof(dvec2) * 2 * (size_t)ws.nrec * nlev);
+    if (ws.nrec > 0) {
+        const size_t lds = sizeof(double) * (size_t)a.nedges + sizeof(unsigned) * (size_t)nwords;
+        TauIn<T> carry = tau_of<T>(a.carry);
+        carry.wrap_x = a.cls.wrap_x ? 1 : 0;
+        hipLaunchKernelGGL((k_gross_class_terms<T, FORM, kGrossClassLevels, TI...>), record_grid(ws), dim3(kBlock), lds, s,
+                           ws.cell.get(), ws.w4.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0,
+                           in.z1, in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), tau_of<T>(a.cls),
+                           carry, in.scale, in.sverdrup, a.edges, a.nedges, top, a.window, nwords, terms, rows, a.flags, extra...);
+        NF_HIP(hipGetLastError());
+    }
+    return launch_joint_bins(a.tr, nrows, nlev, a.window, a.skip, terms, rows, a.flags, nwords, a.scratch, a.rows, s);
+}
+
+// the three forms of one dtype, each with the scalar or the per-cell thicknesses
+template <typename T, int FORM>
+static int launch_gross_class_th(const GrossClassArgs &a, hipStream_t s)
+{
+    if (a.th.e3u) return launch_gross_class_t<T, FORM>(a, s, thick_in<T>(a.th));
+    return launch_gross_class_t<T, FORM>(a, s);
+}
+template <typename T>
+static int launch_gross_class_form(const GrossClassArgs &a, hipStream_t s)
+{
+    if (!a.carry.tau) return launch_gross_class_th<T, 0>(a, s);
+    const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
+    return one ? launch_gross_class_th<T, 1>(a, s) : launch_gross_class_th<T, 2>(a, s);
+}
+
+int launch_gross_class_transport(const GrossClassArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "gross class transport: bad class edges");
+    static_assert(2 * (kMaxClassEdges + 2) <= kMaxJointRows && 2 * (kMaxClassEdges + 2) < (int)kJointNoRow, "rows fit the table");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "gross class transport: bad window");
+    NF_TRY(check_raw_step("gross class transport", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.cls.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+               "gross class transport: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "gross class transport: null argument");
+    if (a.tr.row_length() == 0) return NF_OK;
+    const size_t nrec = (size_t)a.tr.ws->nrec, blocks = (nrec + kBlock - 1) / kBlock;
+    NF_REQUIRE(nrec == 0 || (a.table && a.table_len >= kJointEntryBytes * nrec * (size_t)(in.z1 - in.z0)), NF_ERR_ARG,
+               "gross class transport: the term table is too small");
+    NF_REQUIRE(nrec == 0 || (a.flags && a.flags_len >= blocks * (size_t)joint_flag_words(2 * (a.nedges + 2), a.window)),
+               NF_ERR_ARG, "gross class transport: the flag array is too small");
+    if (in.dtype == NF_F64) return launch_gross_class_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_gross_class_form<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "gross class transport: dtype must be NF_F64 or NF_F32");
 }
 
 }  // namespace nf

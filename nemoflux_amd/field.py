@@ -649,7 +649,7 @@ class Field(object):
         array of another dtype raises.  fill_value / missing_value: the thickness's own missing markers (a file's when not
         given); a thickness that is NaN or a marker counts as 0.
         computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux, computeTracerAll, computeAreaProfile and
-        computeGrossProfile (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
+        computeGrossProfile and computeGrossClassTransport (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
         set.  timeMean and meanEddyTracerTransport carry a static thickness over to the mean state and take a time-varying one
         with thicknessWeighted=True (thickness-weighted mean velocities, mean thicknesses).  setCellThickness(None, None) goes
         back to deptht_bounds."""
@@ -842,7 +842,8 @@ class Field(object):
 
     @staticmethod
     def grossTransport(parts, ztop=None, zbot=None, bounds_depth=None):
-        """Depth sum of both parts of computeGrossProfile: parts (2, nz, n), totals or segments alike, gives (2, n) = P, N.
+        """Depth sum of both parts of computeGrossProfile: parts (2, nz, n), totals or segments alike, gives (2, n) = P, N
+        (of the parts of computeGrossClassTransport, (2, nedges+2, n): the sum over the classes, without a band).
         With ztop < zbot (the units of deptht_bounds) the sum over that depth band instead, level z entering with
         overlap([ztop, zbot], layer z) / thickness[z] as in depthBandFlux; bounds_depth (nz, 2) is then needed (a Field's
         bounds_depth)."""
@@ -863,8 +864,8 @@ class Field(object):
     @staticmethod
     def transportWeightedTracer(volumeParts, carriedParts, reference=0.0):
         """Transport-weighted mean tracer of the inflow and of the outflow: carried / volume + reference per direction, from
-        the volume parts and the carried parts (computeGrossProfile with carry=False and carry=True, or their grossTransport
-        sums) of one shape (2, ...); `reference`: the reference of setTracer, which the carried parts have subtracted.  NaN
+        the volume parts and the carried parts (computeGrossProfile or computeGrossClassTransport with carry=False and
+        carry=True, or their grossTransport sums) of one shape (2, ...); `reference`: the reference of setTracer, which the carried parts have subtracted.  NaN
         where the volume part is 0.  It ASSUMES that the tracer is present wherever the velocity is: a face with a velocity
         and no tracer value adds to the volume part and nothing to the carried part, and pulls the mean towards the
         reference."""
@@ -1152,9 +1153,43 @@ class Field(object):
             check(lib.nf_field_compute_class_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return self._split_rows(rows)
 
+    def computeGrossClassTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Gross transports of time step tIndex in tracer classes (setTracer and setClassEdges first): (totals, segments) of
+        shape (2, nedges+2, ntransect) and (2, nedges+2, nseg), part 0 = P, the inflow of every class (what goes through the
+        section in the direction computeFlux counts positive), part 1 = N, its outflow (<= 0 in the volume form); rows and
+        class field as in computeClassTransport.  Every term of computeGrossProfile goes to the row of its own face's class
+        instead of its level: to P where the water term of its slot is > 0, to N where it is < 0.  carry=True: the terms of
+        computeClassTracerTransport instead, split by the direction of the water at their slot.  Unlike computeClassTransport
+        and computeClassTracerTransport this call takes a cell thickness (setCellThickness), so P + N is the class transport
+        under partial steps and z* thicknesses -- on the Field of timeMean(thicknessWeighted=True) too; without one P + N is
+        their rows up to rounding.  The parts go as they are into grossTransport (the sum over the classes),
+        transportWeightedTracer (the mean tracer of a class's inflow) and classStreamfunction(P + N).  Levels this rank does
+        not own (slab_range) contribute nothing.  Leaves the resident edge fluxes, the running max, the row of the last
+        computeFlux and the tracer, class and joint rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
+        (2 * (nedges+2), row_length), P's rows then N's, that receives the raw rows in HBM (for
+        nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_class_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setClassEdges first')
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        nrows = edges.size + 2
+        carry = 1 if carry else 0
+        if out is not None:
+            out = self._rows_out(out, 2 * nrows)
+            check(lib.nf_field_compute_gross_class_transport_async(ctypes.byref(self._h), tIndex, carry,
+                                                                   ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_gross_class_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        return self._split_rows(rows.reshape(2, nrows, self._row_width))
+
     @staticmethod
     def classStreamfunction(rows):
-        """Overturning streamfunction in class space from the rows of computeClassTransport or computeClassTracerTransport
+        """Overturning streamfunction in class space from the rows of computeClassTransport or computeClassTracerTransport,
+        or from P + N of computeGrossClassTransport (the one form that takes a cell thickness)
         (totals or segments, classes first): psi[k] = rows[0] + ... + rows[k], k = 0 .. nedges-1, the transport of the faces whose class value is below
         e[k].  Host only."""
         R = numpy.asarray(rows, dtype=numpy.float64)

@@ -18,6 +18,8 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
     ... --tracer thetao --eddy --cell-thickness --thickness-weighted   (the same for z* output: thickness-weighted mean flow)
     ... --gross [--tracer thetao] [--zrange 0,700] (inflow, outflow and net of every transect; what they carry, their mean thetao)
+    ... --tracer sigma0 --tracer-file S.nc --gross-classes 26,27,28 [--carry thetao] [--cell-thickness]
+                                  (inflow, outflow and net of every sigma0 class: one CSV line per time step, transect and class)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
 """
@@ -192,6 +194,45 @@ def grossSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tr
             totals[t, :, 3], totals[t, :, 4] = car[0] * float(tracerScale), car[1] * float(tracerScale)
             totals[t, :, 5], totals[t, :, 6] = mean[0], mean[1]
     return totals, fld
+
+
+def grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', carry='', carryFile='', carryRef=0.0,
+                     sverdrup=False, cellThickness=None):
+    """(nt, 2, nedges+2, ntransect) inflow and outflow of every class of the variable `tracer` of tracerFile (default: the T
+    file), one Field.computeGrossClassTransport per time step, and the Field.  With `carry`: what they carry of that variable
+    of carryFile (reference carryRef) instead of the water."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    if carry:
+        fld.setTracer((carryFile or tFile, carry), reference=carryRef)
+        fld.setClassTracer((tracerFile or tFile, tracer))
+    else:
+        fld.setTracer((tracerFile or tFile, tracer))
+    fld.setClassEdges(edges)
+    totals = numpy.array([fld.computeGrossClassTransport(t, carry=bool(carry), prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, 2, len(edges) + 2, len(lonLatZPoints)), fld
+
+
+def checkGrossClassArgs(grossClasses='', tracer='', tracerRef=0.0, tracerScale=1.0, classes='', classes2='', gross=False,
+                        levels=False, zrange='', decompose=False, eddy=False, show=False):
+    """the --gross-classes option of the command line (inflow and outflow of every tracer class): refused combinations raise
+    RuntimeError"""
+    if not grossClasses:
+        return
+    if not tracer:
+        raise RuntimeError('ERROR: --gross-classes needs --tracer NAME (the class field, e.g. sigma0 or thetao)')
+    for on, opt in ((classes, '--classes'), (classes2, '--classes2'), (gross, '--gross'), (levels, '--levels'),
+                    (zrange, '--zrange'), (decompose, '--decompose'), (eddy, '--eddy'), (show, '--show')):
+        if on:
+            raise RuntimeError(f'ERROR: --gross-classes and {opt} cannot be combined: --gross-classes writes the inflow, the '
+                               f'outflow and the net transport of every class of --tracer (with --carry NAME: of NAME) as CSV '
+                               f'only')
+    if float(tracerRef) != 0.0 or float(tracerScale) != 1.0:
+        raise RuntimeError('ERROR: --gross-classes bins by the raw tracer: --tracer-ref / --tracer-scale do not apply '
+                           '(--carry-ref / --carry-scale do, with --carry NAME)')
+    try:
+        parseClasses(grossClasses)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace('--classes', '--gross-classes'))
 
 
 def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
@@ -375,21 +416,41 @@ def parseZRange(zrange):
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
-         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False):
+         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses=''):
+    checkGrossClassArgs(grossClasses, tracer, tracerRef, tracerScale, classes, classes2, gross, levels, zrange, decompose, eddy,
+                        show)
     checkThicknessWeightedArgs(thicknessWeighted, eddy, cellThickness)
     checkGrossArgs(gross, classes, levels, decompose, eddy, show)
     checkJointClassArgs(classes2, tracer2, tracer2File, tracer, classes, carry, levels, zrange, show, eddy, decompose)
     checkEddyArgs(eddy, tracer, classes, levels, zrange, show, decompose)
     checkDecomposeArgs(decompose, tracer, classes, levels, zrange, show)
-    checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, carry, levels, tracer)
+    # --gross-classes takes --carry and --cell-thickness together: its form of the class transports has per-cell thicknesses
+    checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, '' if grossClasses else carry, levels, tracer)
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
     checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '' if gross else zrange)   # --gross sums its parts over a band
     checkLevelsArgs(levels, zrange, classes, show)
-    checkCarryArgs(carry, carryFile, carryRef, carryScale, classes, tracer, levels)
+    checkCarryArgs(carry, carryFile, carryRef, carryScale, classes or grossClasses, tracer, levels)
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
     ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    if grossClasses:
+        edges = parseClasses(grossClasses)
+        totals, fld = grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
+                                       float(carryRef), sverdrup, ct)
+        title = f'# gross water flow by {tracer} class [{unit}]'
+        if carry:
+            totals = totals * float(carryScale)
+            title = (f'# gross transport of {carry} by {tracer} class [{carry} x {unit}' +
+                     (f' x {float(carryScale):g}' if float(carryScale) != 1.0 else '') + ']')
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
+        lines = ['time,transect,lower,upper,' + ','.join(GROSS_COLUMNS)]
+        lines += [f'{timeVals[t]},{name},{lo:.15g},{hi:.15g},' +
+                  ','.join(f'{x:.15g}' for x in (totals[t, 0, k, p], totals[t, 1, k, p], totals[t, 0, k, p] + totals[t, 1, k, p]))
+                  for t in range(fld.nt) for p, name in enumerate(names) for k, (lo, hi) in enumerate(bounds)]
+        _emit(title + '\n' + '\n'.join(lines) + '\n', output)
+        return totals
     if gross:
         totals, fld = grossSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), float(tracerScale),
                                   parseZRange(zrange) if zrange else None, sverdrup, ct)
@@ -556,6 +617,11 @@ if __name__ == '__main__':
                          'the positive direction, the water that comes back, and their sum; with --tracer NAME also what the two '
                          'carry of NAME and the transport-weighted mean NAME of each (--zrange, --cell-thickness, --tracer-ref, '
                          '--tracer-scale and -s apply)')
+    ap.add_argument('--gross-classes', dest='grossClasses', default='', metavar='E0,E1,...,EN',
+                    help='with --tracer NAME (the class field): one CSV line per time step, transect and class '
+                         '(time,transect,lower,upper,inflow,outflow,net): the water of that class that crosses in the positive '
+                         'direction, the water that comes back, and their sum; with --carry NAME what the two carry of NAME '
+                         '(--carry-ref, --carry-scale, --cell-thickness and -s apply)')
     ap.add_argument('--eddy', action='store_true',
                     help='with --tracer NAME: one CSV line per part (part,...): the mean over all time steps of the transport of '
                          'NAME, the transport of the time-mean NAME by the time-mean flow, and the eddy part, their difference '
