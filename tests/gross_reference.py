@@ -1,34 +1,22 @@
-"""A sparse float64 / long-double reference of the gross transports of one time step (nf_field_compute_gross_profile), for any
-grid size: the definition of include/nemoflux_amd.h restated in numpy over the cells the weight entries touch.  It uses the
-entry / face bookkeeping and the summation of tests/resolved_reference.py, through tests/cellthick_reference.py, and shares no
-code with the product.
+"""The reference of the gross transports of one time step (nf_field_compute_gross_profile), for any grid size.  Entries, faces,
+the volume and tracer terms (th scalar or read at the face) and the summation are those of tests/resolved_reference.py; its
+own is the split by the sign of the water term.  Per level z and entry
 
-Per level z and entry (cell c, slot, weight w, segment), with `a` the cell whose face the slot is (east, north: c; west: the
-west cell; south: the south cell; the south entries of row 0 are dropped):
-
-    water term    q = w * ((th * fixed(vel)) * arc)         vel = uo[t, z, a], arc = +arcE[a] for the east and west slots,
-                                                            vel = vo[t, z, a], arc = -arcN[a] for the north and south slots
-    carried term  c = q                                     (volume form)
-                  c = w * ((th * (fixed(vel) * tf)) * arc)  (carried form; tf = the tracer's face value - reference, 0 for a
-                                                            face without a value)
-
-each times 6.371 in Sverdrup mode; th = thickness[z], or fixth(e3u[t', z, a]) / fixth(e3v[t', z, a]) with cell thicknesses.
+    water term    q = the volume term
+    carried term  c = q (volume form), or the tracer term (carried form)
 
     P[z] = sum of c over the entries with q > 0,    N[z] = sum of c over the entries with q < 0;    q == 0: in neither.
 
-Terms are formed in float64 and summed in long double per (level, segment), the transect columns from the segments; `mag` is
-the sum of |c| over the same entries.  The sign of q is the product of the signs of its factors unless the product underflows:
-min_abs_q, the smallest non-zero |q| met, says how far the inputs are from that.
+Terms are summed per (level, segment), the transect columns from the segments; `mag` is the sum of |c| over the same entries.
+The sign of q is the product of the signs of its factors unless the product underflows: min_abs_q, the smallest non-zero |q|
+met, says how far the inputs are from that.
 
 gross_velocities / gross_thickness: the inputs of the tests, made so that no |q| comes near underflow -- velocities of
 magnitude in [0.01, 1] with either sign, exactly 0, or missing; thicknesses in [0.2, 3], exactly 0, or missing.
 """
-import concurrent.futures
-
 import numpy
 
-from cellthick_reference import CellThickReference, array_values  # noqa: F401  (array_values: for the callers)
-from resolved_reference import ACC, _face, _group_sums, _present
+from resolved_reference import ACC, ResolvedReference, _present, _term_sums, array_values  # noqa: F401  (for the callers)
 
 FILL, MISSING = 1.e20, -999.             # uo / vo
 THFILL, THMISSING = -1.e30, 9.e9         # e3u / e3v
@@ -83,64 +71,33 @@ def inputs_are_safe(u, v, e3=(), markers=(FILL, MISSING), thick_markers=(THFILL,
     return ok
 
 
-class GrossReference(CellThickReference):
-    """CellThickReference with the rows of the gross profile.  cell_thickness=True: the thickness is read at the face
-    ('e3u', 'e3v' of the callback, markers thick_markers); otherwise `thickness` (nz,) is used."""
+class GrossReference(ResolvedReference):
+    """ResolvedReference with the rows of the gross profile."""
 
-    def __init__(self, *a, cell_thickness=False, **kw):
-        super().__init__(*a, **kw)
-        self.cell_thickness = bool(cell_thickness)
+    def _gross_terms(self, values, z, tracer):
+        """per entry: q, the carried terms [q] or [q, tracer term], and the smallest non-zero |q| (inf: every q is 0)"""
+        dv, dt = self._factors(values, z, tracer)[:2]
+        q = self._entries(dv)
+        return q, [q, self._entries(dt)] if tracer else [q], float(numpy.abs(q[q != 0]).min(initial=numpy.inf))
 
-    def gross_step(self, values, tracer=True, threads=1):
-        """values(name, z, cells) -> the raw values of 'uo', 'vo' (and 'tracer' with tracer=True, 'e3u', 'e3v' with
-        cell_thickness) of level z at the flat cell indices `cells`, in the array's dtype.  Returns {'volume': (want, mag),
-        'carried': (want, mag) (tracer=True), 'min_abs_q': float}; want and mag have shape (2, nz, row_length): P then N, rows
-        [segments | transects]; mag is the sum of |c| of the entries of the value.  min_abs_q: the smallest non-zero |q|,
-        inf when every q is 0."""
-        nz, nseg = self.nz, self.nseg
-        forms = ('volume', 'carried') if tracer else ('volume',)
-        prof = {nm: numpy.zeros((2, nz, nseg, 2), ACC) for nm in forms}   # last axis: the sum, the sum of |terms|
-        min_q = [numpy.inf] * nz
-
-        def level(z):
-            uo, vo = values('uo', z, self.cells), values('vo', z, self.cells)
-            fu = numpy.where(_present(uo, self.uv_markers), uo.astype(numpy.float64), 0.0)
-            fv = numpy.where(_present(vo, self.uv_markers), vo.astype(numpy.float64), 0.0)
-            vel = numpy.where(self.f_is_u, fu[self.ia], fv[self.ia])
-            if self.cell_thickness:
-                e3u, e3v = values('e3u', z, self.cells), values('e3v', z, self.cells)
-                tu = numpy.where(_present(e3u, self.thick_markers), e3u.astype(numpy.float64), 0.0)
-                tv = numpy.where(_present(e3v, self.thick_markers), e3v.astype(numpy.float64), 0.0)
-                th = numpy.where(self.f_is_u, tu[self.ia], tv[self.ia])
-            else:
-                th = self.thickness[z]
-            d = {'volume': (th * vel) * self.f_arc}
-            if tracer:
-                tau = values('tracer', z, self.cells)
-                has_t, xt = _face(tau[self.ia], tau[self.ib], self.f_has_b, self.tracer_markers)
-                with numpy.errstate(invalid='ignore'):
-                    tf = numpy.where(has_t, numpy.where(has_t, xt, 0.0) - self.reference, 0.0)
-                d['carried'] = (th * (vel * tf)) * self.f_arc
-            if self.scale is not None:
-                d = {nm: x * self.scale for nm, x in d.items()}
-            q = self.w * d['volume'][self.face_of]                        # per entry
-            nonzero = numpy.abs(q[q != 0])
-            if nonzero.size:
-                min_q[z] = float(nonzero.min())
-            for nm in forms:
-                c = q if nm == 'volume' else self.w * d[nm][self.face_of]
-                for part, sel in enumerate((q > 0, q < 0)):
-                    t = numpy.where(sel, c, 0.0)
-                    out = numpy.zeros((self.seg_starts.size, 2), ACC)
-                    out[:, 0], out[:, 1] = _group_sums(t, self.seg_starts), _group_sums(numpy.abs(t), self.seg_starts)
-                    prof[nm][part, z][self.useg] = out
-
-        if threads > 1:
-            with concurrent.futures.ThreadPoolExecutor(threads) as pool:
-                list(pool.map(level, range(nz)))
-        else:
-            for z in range(nz):
-                level(z)
-        res = {nm: (self._with_totals(prof[nm][..., 0]), self._with_totals(prof[nm][..., 1])) for nm in forms}
+    def _gross_result(self, acc, min_q):
+        """acc: (2, ..., nseg, 2 forms), last axis: per form the sum, the sum of |terms|"""
+        res = {nm: self._pair(acc, 2 * k) for k, nm in enumerate(('volume', 'carried')[:acc.shape[-1] // 2])}
         res['min_abs_q'] = min(min_q)
         return res
+
+    def gross_step(self, values, tracer=True, threads=1):
+        """values(name, z, cells): as in ResolvedReference.step, 'uo', 'vo' (and 'tracer' with tracer=True, 'e3u', 'e3v' with
+        cell_thickness).  Returns {'volume': (want, mag), 'carried': (want, mag) (tracer=True), 'min_abs_q': float}; want and
+        mag have shape (2, nz, row_length): P then N, rows [segments | transects]; mag is the sum of |c| of the entries of
+        the value.  min_abs_q: the smallest non-zero |q|, inf when every q is 0."""
+        prof = numpy.zeros((2, self.nz, self.nseg, 4 if tracer else 2), ACC)
+        min_q = [numpy.inf] * self.nz
+
+        def level(z):
+            q, cs, min_q[z] = self._gross_terms(values, z, tracer)
+            for part, sel in enumerate((q > 0, q < 0)):
+                prof[part, z][self.useg] = _term_sums([numpy.where(sel, c, 0.0) for c in cs], self.seg_starts)
+
+        self._each_level(level, threads)
+        return self._gross_result(prof, min_q)

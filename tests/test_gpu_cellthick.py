@@ -8,9 +8,7 @@ Grids 72 x 36 x 7 x 3 and 73 x 37 x 7 x 3 (odd: the one-cell-per-lane kernels), 
 
 Measured on an MI355X: worst |err| / sum |terms| against the definition 2.7e-16 (bar 1e-12), sharded sums 3.3e-16, closed form
 2.6e-16 relative at float64 (bar 1e-12) and 7.0e-9 at float32 (bar 1e-6: the velocities' own float32 rounding)."""
-import contextlib
 import ctypes
-import io
 import os
 
 import numpy
@@ -18,6 +16,7 @@ import pytest
 
 from conftest import transect_xyz
 from cellthick_reference import CellThickReference, array_values
+from gpu_helpers import _field, _on, _quiet, _rows
 
 pytestmark = pytest.mark.gpu
 
@@ -35,16 +34,6 @@ BAR = 1e-12
 # thicknesses that float32 holds exactly, and bounds whose differences are those numbers exactly (sums of dyadic fractions)
 TH = numpy.array([0.125, 0.25, 0.5, 0.375, 0.75, 1.0, 0.625])
 DB = numpy.stack([numpy.concatenate([[0.], numpy.cumsum(TH)[:-1]]), numpy.cumsum(TH)], axis=1)
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
 
 
 _CASES = {}
@@ -74,11 +63,6 @@ def _case(real, grid=GRIDS[0], psi=PSI_ZT, fill=True):
     return _CASES[key]
 
 
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
-
-
 LINES = [T_OPEN, T_TRI, T_SEAM]
 
 
@@ -93,11 +77,6 @@ def _make(real, grid, resident, u=None, v=None, **kw):
 
 def _row(f):
     return numpy.array(f._row[:f._rowlen])
-
-
-def _rows(pair):
-    tot, seg = pair
-    return numpy.concatenate([seg, tot], axis=-1)
 
 
 def _resident(f):

@@ -4,14 +4,13 @@ level index), checked for conservation against the volume row, against a float64
 wrap, values on the edges, +-inf), against K1 + K3 on class-masked uo / vo; determinism, sharding, unchanged state,
 file-backed inputs and fluxplot --classes."""
 import contextlib
-import ctypes
-import io
 import os
 
 import numpy
 import pytest
 
 from conftest import GOLDEN, transect_xyz
+from gpu_helpers import _field, _on, _quiet, _resident, _rows
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +24,6 @@ TFILL, TMISSING = -32768., 12345.
 R_SV = 6371000.0 / 1.e6
 EPS = numpy.finfo(numpy.float64).eps
 LEVEL_EDGES = numpy.arange(NZ + 1) - 0.5          # -0.5, 0.5, ..., NZ - 0.5
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
 
 
 _CASES = {}
@@ -64,11 +53,6 @@ def _case(real, fill=True):
     return _CASES[key]
 
 
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
-
-
 def _args(real, resident, fill=True):
     blon, blat, db, u, v = _case(real, fill)
     return (blon, blat, db, _on(u, resident), _on(v, resident),
@@ -80,12 +64,6 @@ def _kw(sverdrup, fill=True, **kw):
     if fill:
         kw.update(fill_value=FILL, missing_value=MISSING)
     return kw
-
-
-def _rows(pair):
-    """[segments | transects] rows of a (totals, segments) pair"""
-    tot, seg = pair
-    return numpy.concatenate([seg, tot], axis=-1)
 
 
 def _class_rows(f, t, out=None):
@@ -325,15 +303,6 @@ def test_class_masked_volume_rows_are_the_class_rows():
         ut.copy_(torch.from_numpy(u))
         vt.copy_(torch.from_numpy(v))
         assert numpy.abs(got[:edges.size + 1]).max() > 0
-
-
-def _resident(f):
-    from nemoflux_amd import _lib
-    from nemoflux_amd._lib import lib, check
-    n = f.ny * f.nx
-    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
-    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
-    return iV, eU, eV, mx.value
 
 
 @pytest.mark.parametrize('real', ['float64', 'float32'])

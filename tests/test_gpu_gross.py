@@ -18,9 +18,10 @@ import numpy
 import pytest
 
 from conftest import transect_xyz
+from gpu_helpers import _field, _on, _quiet, _rows
 from gross_reference import MIN_ABS_Q, GrossReference, array_values, gross_thickness, gross_velocities
-from test_gpu_cellthick import (BAR, FILL, MISSING, T_OPEN, T_SEAM, T_TRI, TFILL, THFILL, THMISSING, TMISSING, _case, _field, _on,
-                                _quiet, _resident, _row, _rows)
+from test_gpu_cellthick import (BAR, FILL, MISSING, T_OPEN, T_SEAM, T_TRI, TFILL, THFILL, THMISSING, TMISSING, _case, _resident,
+                                _row)
 from test_gpu_tracer_resolved import H5_LINES, _h5_arrays, _h5_files, _read_csv
 from test_gross_cpu import GPU_E3_SEED, GPU_GRIDS as GRIDS, GPU_NT as NT, GPU_NZ as NZ, GPU_UV_SEED
 

@@ -21,12 +21,13 @@ import numpy
 import pytest
 
 from conftest import transect_xyz
+from gpu_helpers import _field, _on, _quiet, _rows, _same_bits
 from gross_class_reference import GrossClassReference
 from gross_reference import MIN_ABS_Q, array_values, gross_thickness, gross_velocities
-from test_gpu_cellthick import (BAR, FILL, MISSING, T_OPEN, T_SEAM, T_TRI, TFILL, THFILL, THMISSING, TMISSING, _case, _field, _on,
-                                _quiet, _resident, _row, _rows)
+from test_gpu_cellthick import (BAR, FILL, MISSING, T_OPEN, T_SEAM, T_TRI, TFILL, THFILL, THMISSING, TMISSING, _case, _resident,
+                                _row)
 from test_gpu_gross import DB, GRIDS, NT, NZ, REF, TH, _gross, _make as _make_gross, _set_thickness, _tau, _uv
-from test_gpu_joint_classes import _same_bits, _skip, _window
+from test_gpu_joint_classes import _skip, _window
 
 pytestmark = pytest.mark.gpu
 

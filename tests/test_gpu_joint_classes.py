@@ -8,14 +8,13 @@ through more records, more levels, new edges and another dtype (the term table's
 
 Grids 72 x 36 and 73 x 37, 7 levels, 3 steps, three transects (one across the periodic seam): 265 to 325 records, two blocks
 of 256.  Edge sets 3 x 5, 2 x 2 and 33 x 9: 35, 16 and 385 joint rows, none a multiple of the window of 32 (385: 13 windows)."""
-import contextlib
 import ctypes
-import io
 
 import numpy
 import pytest
 
 from conftest import transect_xyz
+from gpu_helpers import _knob, _on, _quiet, _resident, _rows, _same_bits
 from joint_class_reference import JointClassReference
 from resolved_reference import array_values
 
@@ -36,11 +35,6 @@ WIDE = numpy.array([-1e300, 1e300])          # one class for every finite value:
 EDGE_SETS = {'3x5': (numpy.array([8., 15., 22.]), numpy.array([33., 34., 35., 36., 37.])),
              '2x2': (numpy.array([10., 20.]), numpy.array([34., 36.])),
              '33x9': (numpy.linspace(2., 28., 33), numpy.linspace(32.5, 37.5, 9))}
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
 
 
 _CASES = {}
@@ -111,11 +105,6 @@ def tracers(real, grid, plain=False, inf_a=False):
     return A, B
 
 
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
-
-
 LINES = (T_OPEN, T_TRI, T_SEAM)
 
 
@@ -134,12 +123,6 @@ def _set(f, A, B, resident=True, markers=True, reference=REF, wrap=True):
     f.setClassTracer(_on(B, resident), **mk(BFILL, BMISSING))
 
 
-def _rows(pair):
-    """[segments | transects] rows of a (totals, segments) pair, the class axes kept"""
-    tot, seg = pair
-    return numpy.concatenate([seg, tot], axis=-1)
-
-
 def _joint(f, t, carry=False, out=None):
     return _rows(f.computeJointClassTransport(t, carry=carry, out=out))
 
@@ -148,23 +131,8 @@ def _one_d(f, t, carry):
     return _rows(f.computeClassTracerTransport(t) if carry else f.computeClassTransport(t))
 
 
-def _same_bits(a, b):
-    a, b = numpy.ascontiguousarray(a, numpy.float64), numpy.ascontiguousarray(b, numpy.float64)
-    return a.shape == b.shape and numpy.array_equal(a.view(numpy.uint64), b.view(numpy.uint64))
-
-
 def _plus_zero(a):
     return not numpy.ascontiguousarray(a, numpy.float64).view(numpy.uint64).any()
-
-
-@contextlib.contextmanager
-def _knob(name, value, default):
-    from nemoflux_amd._lib import lib, check
-    check(lib.nf_tuning_set(name, int(value)))
-    try:
-        yield
-    finally:
-        check(lib.nf_tuning_set(name, default))
 
 
 def _window(w):
@@ -384,15 +352,6 @@ def test_three_slab_ranges_add_up(carry):
 
 
 # ---- 6. state --------------------------------------------------------------------------------------------------------------
-def _resident(f):
-    from nemoflux_amd import _lib
-    from nemoflux_amd._lib import lib, check
-    n = f.ny * f.nx
-    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
-    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
-    return iV, eU, eV, mx.value
-
-
 @pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
 def test_joint_calls_leave_everything_else_alone(resident):
     """between joint calls the 1-D class rows (volume and carried), the volume row, the planes and running max of read_step

@@ -3,15 +3,13 @@ level z alone carries.  Anchored bit for bit to computeFlux of a field whose onl
 full-depth rows, the CPU oracle run on one level and the closed form of fluxexact; computing a profile changes nothing
 else; sharded ranks add up to the single-rank profile; file-backed fields, depth bands and fluxplot --zrange."""
 import ast
-import contextlib
-import ctypes
-import io
 import os
 
 import numpy
 import pytest
 
 from conftest import GOLDEN, case_box, load_golden, transect_xyz
+from gpu_helpers import _field, _quiet, _resident
 
 pytestmark = pytest.mark.gpu
 
@@ -20,16 +18,6 @@ T_TRI = "(-100,-80),(100,-80),(0,80),(-100,-80)"
 T_OPEN = "(-100,-80),(100,-80),(0,80)"
 NX, NY, NZ, NT = 72, 36, 7, 3
 FILL, MISSING = 1.e20, -999.
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
 
 
 _CASES = {}
@@ -179,15 +167,6 @@ def test_profile_levels_against_the_closed_form(name, cases):
                 phiB = _expr.evaluate(code, x=xy[-1, 0], y=xy[-1, 1], z=zhalf[k], t=t, nt=nt)
                 exact = float((phiB - phiA) * thickness[k])
                 assert abs(tot[k, i] - exact) <= 1e-13 * max(amp, abs(exact)), (t, n, k)
-
-
-def _resident(f):
-    from nemoflux_amd import _lib
-    from nemoflux_amd._lib import lib, check
-    n = f.ny * f.nx
-    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
-    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
-    return iV, eU, eV, mx.value
 
 
 @pytest.mark.parametrize('compact', [False, True])

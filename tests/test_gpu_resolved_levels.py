@@ -15,9 +15,10 @@ import pytest
 
 import bench
 import test_gpu_tracer_resolved as base
+from gpu_helpers import _field, _rows
 from resolved_reference import ResolvedReference, array_values
-from test_gpu_tracer_resolved import (CFILL, CMISSING, FILL, MISSING, TFILL, TMISSING, REF, EPS, _carried, _class_field, _field,
-                                      _rows, _tprof, _tracer_row, _trows, _window)
+from test_gpu_tracer_resolved import (CFILL, CMISSING, FILL, MISSING, TFILL, TMISSING, REF, EPS, _carried, _class_field, _tprof,
+                                      _tracer_row, _trows, _window)
 
 pytestmark = pytest.mark.gpu
 

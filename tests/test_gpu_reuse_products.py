@@ -33,7 +33,6 @@ import pytest
 import reuse_model
 from reuse_model import NF_ERR_STATE, Model, run_sequence
 from test_gpu_reuse import TRANSECTS, Handle, same_bits
-from resolved_reference import ResolvedReference
 from section_reference import SectionReference, array_values
 
 pytestmark = pytest.mark.gpu
@@ -257,10 +256,7 @@ def anchor(h, model):
                            cell_thickness=with_ct, reference=model.tracer_ref, wrap=bool(model.tracer_wrap),
                            sverdrup=bool(model.sverdrup), **markers)
     values = array_values(arrays, t)
-    if with_ct:
-        want = ref.step(values)
-    else:
-        want = ResolvedReference.step(ref, values, edge_sets=[model.edges])
+    want = ref.step(values, edge_sets=() if with_ct else [model.edges])
     want.update(ref.area_step(values))
 
     def rows(kind, form='sync'):

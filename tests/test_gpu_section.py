@@ -16,9 +16,10 @@ import numpy
 import pytest
 
 from conftest import transect_xyz
+from gpu_helpers import _field, _on, _quiet, _rows
 from section_reference import SectionReference, array_values
 from test_gpu_cellthick import (BAR, DB, FILL, GRIDS, LINES, MISSING, NT, NZ, TFILL, TH, THFILL, THMISSING, TMISSING, _broadcast,
-                                _case, _field, _make, _on, _quiet, _random_thickness, _resident, _row, _rows)
+                                _case, _make, _random_thickness, _resident, _row)
 from test_gpu_tracer_resolved import H5_LINES, _h5_arrays, _h5_files, _read_csv
 from test_section_cpu import ZONAL, zonal_line_area
 

@@ -10,9 +10,10 @@ import contextlib
 import numpy
 import pytest
 
+from gpu_helpers import _rows
 from section_reference import SectionReference, array_values
 from test_gpu_resolved_levels import (CFILL, CMISSING, FILL, MISSING, NT, NX, NY, NZ, REF, TFILL, THREADS, TMISSING, _data, _make,
-                                      _on, _rows)
+                                      _on)
 
 pytestmark = pytest.mark.gpu
 

@@ -9,14 +9,13 @@ Grids 72 x 36 x 7 x 3 and 73 x 37 x 7 x 3 (odd: every other step of an array is 
 
 Measured on an MI355X: worst |err| / sum |terms| against the resolved reference 2.7e-16 (bar 1e-12); the anchors' worst error
 1.7e-4 of their bar; 48 tests in 5 s."""
-import contextlib
 import ctypes
-import io
 
 import numpy
 import pytest
 
 from conftest import transect_xyz, write_classic_triple
+from gpu_helpers import _field, _on, _quiet, _rows
 from resolved_reference import ResolvedReference, array_values
 import timemean_reference as tmr
 
@@ -34,26 +33,6 @@ BAR = 1e-12
 TH = numpy.array([0.125, 0.25, 0.5, 0.375, 0.75, 1.0, 0.625])
 DB = numpy.stack([numpy.concatenate([[0.], numpy.cumsum(TH)[:-1]]), numpy.cumsum(TH)], axis=1)
 NF_F64, NF_F32 = 0, 1
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
-
-
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
-
-
-def _rows(pair):
-    tot, seg = pair
-    return numpy.concatenate([seg, tot], axis=-1)
 
 
 def _row(f):

@@ -3,15 +3,13 @@ the integral of u * tau_face, tau at T-points interpolated to the U / V faces.  
 (tau == ref + 1, tau == 2**k), checked against a float64 numpy restatement of the definition (face rule, markers, wrap, last
 row) on odd grids, against the depth profiles for a tracer that depends on z only; computing tracer rows changes nothing
 else; sharded ranks add up; file-backed tracers; fluxplot --tracer."""
-import contextlib
-import ctypes
-import io
 import os
 
 import numpy
 import pytest
 
 from conftest import GOLDEN, transect_xyz
+from gpu_helpers import _field, _on, _quiet, _resident
 
 pytestmark = pytest.mark.gpu
 
@@ -24,16 +22,6 @@ NX, NY, NZ, NT = 72, 36, 7, 3
 FILL, MISSING = 1.e20, -999.
 TFILL, TMISSING = -32768., 12345.        # the tracer's own markers (not those of uo / vo)
 R_SV = 6371000.0 / 1.e6
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
 
 
 _CASES = {}
@@ -61,11 +49,6 @@ def _case(real, fill=True):
             v[:, 5:, 20:24, 30:40] = dt(MISSING)
         _CASES[key] = (dg.bounds_lon.cpu().numpy(), dg.bounds_lat.cpu().numpy(), dg.deptht_bounds, u, v)
     return _CASES[key]
-
-
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
 
 
 def _args(real, resident, fill=True):
@@ -278,15 +261,6 @@ def test_level_tracer_is_the_weighted_profile(real, resident):
         bound = 1e-13 * (numpy.abs((c - ref)[:, None] * prof).sum(axis=0) + numpy.abs(want).max())
         got = _tracer_row(f, t)
         assert numpy.all(numpy.abs(got - want) <= bound), t
-
-
-def _resident(f):
-    from nemoflux_amd import _lib
-    from nemoflux_amd._lib import lib, check
-    n = f.ny * f.nx
-    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
-    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
-    return iV, eU, eV, mx.value
 
 
 @pytest.mark.parametrize('compact', [False, True])

@@ -6,13 +6,13 @@ to stated bounds against a float64 numpy restatement of the definitions on odd g
 row and against K1tau + K3 on class-masked uo / vo; unchanged state, sharding, file-backed inputs, `out=` and fluxplot."""
 import contextlib
 import ctypes
-import io
 import os
 
 import numpy
 import pytest
 
 from conftest import GOLDEN, transect_xyz
+from gpu_helpers import _field, _on, _quiet, _resident, _rows
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +30,6 @@ EPS = numpy.finfo(numpy.float64).eps
 LEVEL_EDGES = numpy.arange(NZ + 1) - 0.5          # -0.5, 0.5, ..., NZ - 0.5
 SMALL_EDGES = numpy.array([0., 5., 8., 10., 12., 15., 20.])
 DEFAULT_WINDOW = 32     # nf_tuning_set("class_window") default
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
 
 
 _CASES = {}
@@ -72,11 +62,6 @@ def _case(real, fill=True):
 LINES = [T_OPEN, T_TRI, T_SEAM]
 
 
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
-
-
 def _args(real, resident, fill=True, db=None):
     blon, blat, db0, u, v = _case(real, fill)
     return (blon, blat, db0 if db is None else db, _on(u, resident), _on(v, resident), [transect_xyz(s) for s in LINES])
@@ -87,12 +72,6 @@ def _kw(sverdrup, fill=True, **kw):
     if fill:
         kw.update(fill_value=FILL, missing_value=MISSING)
     return kw
-
-
-def _rows(pair):
-    """[segments | transects] rows of a (totals, segments) pair"""
-    tot, seg = pair
-    return numpy.concatenate([seg, tot], axis=-1)
 
 
 def _tprof(f, t, out=None):
@@ -433,15 +412,6 @@ def test_class_masked_tracer_rows_are_the_class_rows():
 
 
 # ---- state and plumbing -----------------------------------------------------------------------------------------------------
-def _resident(f):
-    from nemoflux_amd import _lib
-    from nemoflux_amd._lib import lib, check
-    n = f.ny * f.nx
-    iV, eU, eV, mx = numpy.zeros((n, 4)), numpy.zeros(n), numpy.zeros(n), ctypes.c_double()
-    check(lib.nf_field_read_step(ctypes.byref(f._h), _lib.dptr(iV), _lib.dptr(eU), _lib.dptr(eV), ctypes.byref(mx)))
-    return iV, eU, eV, mx.value
-
-
 @pytest.mark.parametrize('compact', [False, True])
 @pytest.mark.parametrize('resident', [True, False], ids=['hbm', 'host'])
 def test_new_calls_leave_everything_else_alone(compact, resident):

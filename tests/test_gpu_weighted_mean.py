@@ -13,15 +13,14 @@ velocities and thicknesses of this file: 0 x inf is NaN here as in every flux ke
 
 Measured on an MI355X: the anchors' worst error 2.4e-4 of their bar (volume and profile rows) and 4.3e-5 (the eddy part of a
 constant tracer); the eddy part that the plain means leave is 8.6e8 x the bar or more; 52 tests in 3.5 s."""
-import contextlib
 import ctypes
-import io
 
 import numpy
 import pytest
 
 from conftest import transect_xyz, write_classic_triple
 from cellthick_reference import CellThickReference, array_values
+from gpu_helpers import _field, _on, _quiet, _rows
 import timemean_reference as tmr
 import weighted_mean_reference as wmr
 
@@ -42,26 +41,6 @@ TH2 = numpy.array([0.125, 0.25, 0.5, 0.25, 1.0, 2.0, 0.5])       # powers of two
 DB2 = numpy.stack([numpy.concatenate([[0.], numpy.cumsum(TH2)[:-1]]), numpy.cumsum(TH2)], axis=1)
 NF_F64, NF_F32 = 0, 1
 US = 4                                   # kTimeMeanWeightedSteps of nf_timemean.hip: the steps a lane has in flight
-
-
-def _quiet(fn, *a, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **kw)
-
-
-def _field(*a, **kw):
-    from nemoflux_amd.field import Field
-    return _quiet(Field.fromArrays, *a, **kw)
-
-
-def _on(a, resident):
-    import torch
-    return torch.from_numpy(numpy.ascontiguousarray(a)).cuda() if resident else numpy.ascontiguousarray(a)
-
-
-def _rows(pair):
-    tot, seg = pair
-    return numpy.concatenate([seg, tot], axis=-1)
 
 
 def _row(f):
