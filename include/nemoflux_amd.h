@@ -589,6 +589,24 @@ int nf_time_mean_weighted(double *accf_dev, double *acch_dev, unsigned *cnt_dev,
                           double missing, double thk_fill, double thk_missing, int first, int last, long total_steps,
                           double fill_out, void *hip_stream);
 
+/* Potential density anomaly sigma_pref(theta, S) = rho(S, T_pref, pref) - 1000 in kg m-3 by the UNESCO EOS-80 equation of state,
+ * value by value over n values of dtype in HBM (nf_eos.hip): theta_dev potential temperature in degC referenced to the surface,
+ * salt_dev practical salinity, pref_dbar the reference pressure in dbar, uniform over the call.  pref_dbar == 0: T_pref = theta
+ * and rho is the one-atmosphere equation (sigma0).  pref_dbar > 0: T_pref is theta moved adiabatically from 0 to pref_dbar by the
+ * Fofonoff-Millard Runge-Kutta step over Bryden's lapse rate, rho the one-atmosphere density over 1 - P / K with the secant bulk
+ * modulus K (sigma2, sigma4).  All arithmetic is float64 in the operation order written in nf_eos.hip, without fused
+ * multiply-adds; float32 inputs are widened first, the result is rounded once to dtype.  TEOS-10 (conservative temperature,
+ * absolute salinity) is not covered.
+ * A value is present when it is not NaN and equals neither of its array's two markers (theta_fill, theta_missing; salt_fill,
+ * salt_missing; NaN = none), each cast to dtype and compared in dtype.  Where theta or S is missing out_dev gets fill_out (cast to
+ * dtype).  A negative S gives NaN.  3 * n * sizeof(dtype) bytes move.  n == 0 is a no-op.
+ * NF_ERR_ARG, decided before a device is needed: a bad dtype, pref_dbar negative or not finite, and with n > 0 a NULL pointer or
+ * an out_dev that overlaps theta_dev or salt_dev without being equal to it (in place over either input is allowed).
+ * Asynchronous on hip_stream. */
+int nf_sigma_eos80(void *out_dev, const void *theta_dev, const void *salt_dev, size_t n, int dtype, double pref_dbar,
+                   double theta_fill, double theta_missing, double salt_fill, double salt_missing, double fill_out,
+                   void *hip_stream);
+
 /* ------------------------------------------------------------------ synthetic data (datagen.py) */
 /* Stream functions offered on device (no eval on the GPU): psi = g(z,t) * h(x,y)
  *   0 "x"                                                    README.md:26

@@ -179,6 +179,8 @@ _sig('nf_time_mean', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.
 _sig('nf_time_mean_weighted', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                ctypes.c_void_p, ctypes.c_longlong, ctypes.c_long, ctypes.c_size_t, ctypes.c_int] +
      [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_double, ctypes.c_void_p])
+_sig('nf_sigma_eos80', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] +   # HBM addresses
+     [ctypes.c_double] * 6 + [ctypes.c_void_p])
 _sig('nf_datagen_bounds',[ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long] + [ctypes.c_double] * 6 +
      [ctypes.c_int, ctypes.c_void_p])
 _sig('nf_datagen_uv', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_long] * 6 + [ctypes.c_double] * 6 +

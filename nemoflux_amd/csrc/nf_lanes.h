@@ -1,5 +1,5 @@
 // nf_lanes.h -- the lane loader of the streaming kernels that are built like K1 (nf_tracer.hip, nf_cellthick.hip,
-// nf_timemean.hip; internal).  A lane owns VEC consecutive values -- 16 bytes: 2 doubles, 4 floats or 4 counts -- or one value
+// nf_timemean.hip, nf_eos.hip; internal).  A lane owns VEC consecutive values -- 16 bytes: 2 doubles, 4 floats or 4 counts -- or one value
 // where some array is not 16-byte aligned.  K1 keeps its own copy: nf_flux.hip is fingerprinted by the benchmark.
 #pragma once
 #include "nf_common.h"
@@ -8,7 +8,7 @@
 
 namespace nf {
 
-namespace {   // as in the three files that include this: nothing here has a name outside its translation unit
+namespace {   // as in the files that include this: nothing here has a name outside its translation unit
 
 typedef double dvec2 __attribute__((ext_vector_type(2)));   // clang vectors: accepted by the non-temporal builtins
 typedef float fvec4 __attribute__((ext_vector_type(4)));

@@ -197,6 +197,7 @@ class Field(object):
         self.sverdrup = sverdrup
         self.periodX = periodX
         self._readback = readback
+        self._stream = stream
         # what timeMean needs to build the Field of the mean state the way this one was built
         self._uv_markers = (float(fill_value), float(missing_value))
         self._build_kw = dict(periodX=periodX, numCellsPerBucket=numCellsPerBucket, readback=readback, compact=compact,
@@ -556,7 +557,9 @@ class Field(object):
         """A tracer at T-points (potential temperature, salinity) for computeTracerFlux / computeTracerAll: the same
         (nt, nz, ny, nx) and dtype as uo / vo.  `tracer`: a host array (staged one time step at a time), a torch CUDA tensor
         or a DeviceArray (used in place), or a (path, name) pair read with nemoflux_amd.io one time step at a time, its CF
-        markers and scale / offset decoded as for uo.  fill_value / missing_value: the tracer's own missing markers (a file's
+        markers and scale / offset decoded as for uo; or a nemoflux_amd.eos.Sigma(thetao, so, pref): potential density computed
+        from temperature and salinity on the GPU, one time step at a time (it carries its own markers).  fill_value /
+        missing_value: the tracer's own missing markers (a file's
         _FillValue / missing_value when not given; NaN always counts as missing).  reference: subtracted from every face value
         (theta_ref of a heat transport).  wrapX: the east face of the last column takes the first column as its neighbour
         (the periodic rule of the volume rows)."""
@@ -569,7 +572,13 @@ class Field(object):
     def _tracer_slot(self, tracer, fill_value, missing_value, set_tracer, set_missing):
         """Hand a tracer at T-points to one of the engine's two tracer slots (set_tracer / set_missing: the slot's C calls) and
         return what staging it needs: host arrays and device arrays are set once; a (path, name) pair is opened with its CF
-        markers and read one time step at a time into one pinned host buffer by _stage_slot."""
+        markers and read one time step at a time into one pinned host buffer by _stage_slot; a Sigma is computed one time step
+        at a time into one device buffer by _stage_slot."""
+        from .eos import Sigma
+        if isinstance(tracer, Sigma):
+            if fill_value is not None or missing_value is not None:
+                raise RuntimeError('ERROR: a Sigma carries the markers of thetao and so itself; give them to Sigma(...)')
+            return self._sigma_slot(tracer, set_tracer, set_missing)
         if isinstance(tracer, tuple) and len(tracer) == 2 and isinstance(tracer[1], str):
             path, name = tracer
             var, _, d = open_uvfile(path, name, with_all=True)
@@ -606,10 +615,72 @@ class Field(object):
         check(set_missing(ctypes.byref(self._h), numpy.nan if missing_value is None else float(missing_value)))
         return slot
 
+    def _sigma_slot(self, sigma, set_tracer, set_missing):
+        """The slot of a derived tracer (nemoflux_amd.eos.Sigma): thetao and so each stay where they are -- device arrays are
+        read in place by offset, host arrays and file variables go one time step at a time through a pinned buffer of their
+        own into a device buffer -- and _stage_slot has nf_sigma_eos80 write step t into one (nz, ny, nx) device buffer of the
+        dtype of uo / vo, which the engine reads as a device-resident tracer whose fill is NaN."""
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        if self.getSizes(sigma.shape) != (self.nt, self.nz, self.ny, self.nx):
+            raise RuntimeError(f'ERROR: thetao and so of the Sigma have shape {sigma.shape}; uo/vo have (nt, nz, ny, nx) = '
+                               f'{(self.nt, self.nz, self.ny, self.nx)}')
+        if sigma.dtype != uv_dtype:
+            raise RuntimeError(f'ERROR: thetao and so of the Sigma are {sigma.dtype.name}, uo/vo are {uv_dtype.name}')
+        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
+        inputs = []
+        for src, (fill, missing) in zip(sigma.sources, sigma.markers):
+            ptr = _lib.device_pointer(src)
+            one = dict(ptr=ptr, fill=numpy.nan if fill is None else fill, missing=numpy.nan if missing is None else missing,
+                       keep=src)     # a borrowed buffer must outlive the handle
+            if ptr is None:
+                one['file'] = hasattr(src, 'read_step')
+                one['host'] = None if one['file'] else _native(src).reshape(self.nt, self.nz, self.ny, self.nx)
+                one['pinned'] = self._host_array((self.nz, self.ny, self.nx), uv_dtype)
+                one['dev'] = _lib.DeviceBuffer(nbytes)
+            inputs.append(one)
+        slot = dict(lazy=tuple(sigma.sources), step=-1, set=set_tracer, code=self._uv_code, fill=numpy.nan, missing=numpy.nan,
+                    keep=sigma, sigma=dict(pref=sigma.pref, inputs=inputs, out=_lib.DeviceBuffer(nbytes), nbytes=nbytes))
+        check(set_missing(ctypes.byref(self._h), numpy.nan))
+        return slot
+
+    def _stage_sigma(self, slot, tIndex):
+        """step tIndex of a Sigma slot: thetao and so of that step on the device, nf_sigma_eos80 into the slot's buffer on the
+        Field's stream, and the buffer handed over through a virtual (nt, nz, ny, nx) base"""
+        sg = slot['sigma']
+        off = tIndex * sg['nbytes']
+        ptrs = []
+        for one in sg['inputs']:
+            if one['ptr'] is not None:
+                ptrs.append(one['ptr'] + off)
+                continue
+            if one['file']:
+                one['keep'].read_step(tIndex, out=one['pinned'])
+            else:
+                numpy.copyto(one['pinned'], one['host'][tIndex])
+            check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, sg['nbytes']))
+            ptrs.append(one['dev'].ptr)
+        th, so = sg['inputs']
+        check(lib.nf_sigma_eos80(sg['out'].ptr, ptrs[0], ptrs[1], self.nz * self.ny * self.nx, slot['code'], sg['pref'],
+                                 th['fill'], th['missing'], so['fill'], so['missing'], numpy.nan, self._stream))
+        if any(one['ptr'] is None for one in sg['inputs']):
+            check(lib.nf_synchronize())     # the staging buffers are written again by the next step
+        check(slot['set'](ctypes.byref(self._h), sg['out'].ptr - off, self.nt, slot['code'], 1, numpy.nan))
+        slot['step'] = tIndex
+
+    def _sigma_refused(self, what):
+        for slot in (getattr(self, '_tracer', None), getattr(self, '_class_tracer', None)):
+            if slot is not None and slot.get('sigma') is not None:
+                raise RuntimeError(f'ERROR: {what}: this Field holds a Sigma (potential density computed from thetao and so); '
+                                   f'the mean of sigma and sigma of the means are different quantities and neither is chosen '
+                                   f'here: set a plain tracer')
+
     def _stage_slot(self, slot, tIndex):
         """make step tIndex of a file-backed slot -- a tracer, or the e3u / e3v pair of a time-varying cell thickness -- the one
         the engine reads (no-op for in-memory / HBM arrays)"""
-        if slot is not None and slot['lazy'] is not None and slot['step'] != tIndex:
+        if slot is not None and slot.get('sigma') is not None:
+            if slot['step'] != tIndex:
+                self._stage_sigma(slot, tIndex)
+        elif slot is not None and slot['lazy'] is not None and slot['step'] != tIndex:
             for src, buf in zip(slot['lazy'], slot['buf']):
                 src.read_step(tIndex, out=buf)
             # a virtual (nt, nz, ny, nx) base that the engine only dereferences at step tIndex
@@ -1003,7 +1074,8 @@ class Field(object):
         volume fluxes); a value missing at every step is the new Field's fill, the source's first marker as its dtype holds it
         (NaN without one).  A tracer of setTracer / setClassTracer: the mean of its present values, set on the new Field with
         the same reference and wrapX; the class edges are carried over.  A static cell thickness is carried over as float64;
-        a sharded Field (slab_range) raises, and so does a time-varying cell thickness unless thicknessWeighted=True.  The sums
+        a sharded Field (slab_range) raises, and so does a time-varying cell thickness unless thicknessWeighted=True;
+        a Field that holds a Sigma (nemoflux_amd.eos) raises too.  The sums
         are float64, left to right in step order (nf_time_mean), wherever the arrays live: HBM (one pass), host (uploaded in
         groups of steps) or files (one step at a time).  Nothing of this Field changes.
         thicknessWeighted=True (setCellThickness first): the mean state of z* / variable-volume output.  With a time-varying
@@ -1014,6 +1086,7 @@ class Field(object):
         so the volume flux of the mean state is again the mean of the volume fluxes.  The tracers keep the plain mean of
         their present values (there is no e3t to weight them with).  With a static thickness the weights cancel: the result
         of timeMean(steps), bit for bit."""
+        self._sigma_refused('timeMean')
         if self.slab_range is not None:
             raise RuntimeError('ERROR: timeMean: the mean state of a sharded Field (slab_range) is not defined here; build the '
                                'Field without slab_range')
@@ -1083,6 +1156,7 @@ class Field(object):
         time-mean VOLUME FLUX (mean thickness x thickness-weighted mean velocity), and 'eddy' is everything else -- the
         correlation of the tracer with the volume flux, which includes the tracer-thickness covariance, because there is no
         e3t to weight the tracer mean with."""
+        self._sigma_refused('meanEddyTracerTransport')
         if getattr(self, '_tracer', None) is None:
             raise RuntimeError('ERROR: call setTracer first')
         t0, t1 = self._step_range(steps)

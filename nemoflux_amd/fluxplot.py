@@ -13,6 +13,8 @@ only with --show): the table is always printed or written as CSV, which is what 
     python -m nemoflux_amd.fluxplot -t T.nc -u U.nc -v V.nc -l "..." -s --tracer sigma0 --tracer-file S.nc --classes 26,27,28
                                   (water flow by sigma0 class: one CSV line per time step and class)
     ... --tracer sigma0 --tracer-file S.nc --classes 26,27,28 --carry thetao --carry-scale 4.1e-3   (heat by sigma0 class)
+    ... --sigma thetao,so[,PREF] --classes 26,27,28   (the same by sigma_PREF computed from thetao and so on the GPU: EOS-80,
+                                  PREF in dbar, default 0; in place of --tracer for --classes, --gross-classes, --carry, --classes2)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
@@ -93,35 +95,64 @@ def tracerSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', trac
     return totals, fld
 
 
-def classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', sverdrup=False):
-    """(nt, nedges+2, ntransect) water flow by class of the variable `tracer` of tracerFile (default: the T file), one
-    Field.computeClassTransport per time step, and the Field."""
+def parseSigma(sigma):
+    """'THETA,SALT[,PREF]' -> (theta name, salt name, pref in dbar): the variables of --sigma and its reference pressure"""
+    parts = [x.strip() for x in sigma.split(',')]
+    if len(parts) not in (2, 3) or not parts[0] or not parts[1]:
+        raise RuntimeError(f'ERROR: --sigma must be THETA,SALT[,PREF] (two variable names and a pressure in dbar), got {sigma!r}')
+    try:
+        pref = float(parts[2]) if len(parts) == 3 else 0.0
+    except ValueError:
+        raise RuntimeError(f'ERROR: --sigma must be THETA,SALT[,PREF] with a number PREF, got {sigma!r}')
+    if not (pref >= 0.0 and numpy.isfinite(pref)):
+        raise RuntimeError(f'ERROR: --sigma needs a finite PREF >= 0 (dbar), got {sigma!r}')
+    return parts[0], parts[1], pref
+
+
+def sigmaName(pref):
+    """what the tables call the class field of --sigma: sigma0, sigma2, sigma4 (PREF in 1000 dbar)"""
+    return f'sigma{pref / 1000.0:g}'
+
+
+def _classField(tFile, tracer, tracerFile, sigma):
+    """the class field for setTracer / setClassTracer: the variable `tracer` of tracerFile (default: the T file), or with
+    sigma = (theta name, salt name, pref) the potential density of those two variables of that file"""
+    path = tracerFile or tFile
+    if sigma is None:
+        return (path, tracer)
+    from .eos import Sigma
+    return Sigma((path, sigma[0]), (path, sigma[1]), pref=sigma[2])
+
+
+def classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', sverdrup=False, sigma=None):
+    """(nt, nedges+2, ntransect) water flow by class of the variable `tracer` of tracerFile (default: the T file; sigma: see
+    _classField), one Field.computeClassTransport per time step, and the Field."""
     fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
-    fld.setTracer((tracerFile or tFile, tracer))
+    fld.setTracer(_classField(tFile, tracer, tracerFile, sigma))
     fld.setClassEdges(edges)
     totals = numpy.array([fld.computeClassTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
     return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
 
 
 def carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracerFile='', carryFile='', carryRef=0.0,
-                sverdrup=False):
+                sverdrup=False, sigma=None):
     """(nt, nedges+2, ntransect) transport of the variable `carry` of carryFile by class of the variable `tracer` of
     tracerFile (default for both: the T file), one Field.computeClassTracerTransport per time step, and the Field."""
     fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
     fld.setTracer((carryFile or tFile, carry), reference=carryRef)
-    fld.setClassTracer((tracerFile or tFile, tracer))
+    fld.setClassTracer(_classField(tFile, tracer, tracerFile, sigma))
     fld.setClassEdges(edges)
     totals = numpy.array([fld.computeClassTracerTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
     return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
 
 
 def jointClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracer2, edges2, tracerFile='', tracer2File='',
-                     sverdrup=False):
+                     sverdrup=False, sigma=None):
     """(nt, nA+2, nB+2, ntransect) water flow in joint classes of the variable `tracer` of tracerFile (edges) and the variable
     `tracer2` of tracer2File (edges2; default for both files: the T file), one Field.computeJointClassTransport per time
     step, and the Field."""
     fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
-    fld.setTracer((tracerFile or tFile, tracer))
+    fld.setTracer(_classField(tFile, tracer, tracerFile, sigma))
     fld.setClassTracer((tracer2File or tFile, tracer2))
     fld.setJointClassEdges(edges, edges2)
     totals = numpy.array([fld.computeJointClassTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
@@ -197,16 +228,16 @@ def grossSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tr
 
 
 def grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', carry='', carryFile='', carryRef=0.0,
-                     sverdrup=False, cellThickness=None):
+                     sverdrup=False, cellThickness=None, sigma=None):
     """(nt, 2, nedges+2, ntransect) inflow and outflow of every class of the variable `tracer` of tracerFile (default: the T
     file), one Field.computeGrossClassTransport per time step, and the Field.  With `carry`: what they carry of that variable
     of carryFile (reference carryRef) instead of the water."""
     fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     if carry:
         fld.setTracer((carryFile or tFile, carry), reference=carryRef)
-        fld.setClassTracer((tracerFile or tFile, tracer))
+        fld.setClassTracer(_classField(tFile, tracer, tracerFile, sigma))
     else:
-        fld.setTracer((tracerFile or tFile, tracer))
+        fld.setTracer(_classField(tFile, tracer, tracerFile, sigma))
     fld.setClassEdges(edges)
     totals = numpy.array([fld.computeGrossClassTransport(t, carry=bool(carry), prefetch_next=True)[0] for t in range(fld.nt)])
     return totals.reshape(fld.nt, 2, len(edges) + 2, len(lonLatZPoints)), fld
@@ -416,7 +447,18 @@ def parseZRange(zrange):
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
-         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses=''):
+         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma=''):
+    sig = None
+    if sigma:
+        # the class field computed from two variables: in the tables it goes by the name sigmaName gives it
+        if tracer:
+            raise RuntimeError('ERROR: --sigma and --tracer cannot be combined: --sigma THETA,SALT[,PREF] is the class field in '
+                               'place of --tracer NAME')
+        if not (classes or grossClasses or classes2):
+            raise RuntimeError('ERROR: --sigma needs --classes, --gross-classes or --classes2: it is the class field of the '
+                               'class transports (with --carry NAME too)')
+        sig = parseSigma(sigma)
+        tracer = sigmaName(sig[2])
     checkGrossClassArgs(grossClasses, tracer, tracerRef, tracerScale, classes, classes2, gross, levels, zrange, decompose, eddy,
                         show)
     checkThicknessWeightedArgs(thicknessWeighted, eddy, cellThickness)
@@ -437,7 +479,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     if grossClasses:
         edges = parseClasses(grossClasses)
         totals, fld = grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
-                                       float(carryRef), sverdrup, ct)
+                                       float(carryRef), sverdrup, ct, sig)
         title = f'# gross water flow by {tracer} class [{unit}]'
         if carry:
             totals = totals * float(carryScale)
@@ -503,7 +545,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     if classes2:
         edges, edges2 = parseClasses(classes), parseClasses(classes2)
         totals, fld = jointClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracer2, edges2, tracerFile,
-                                       tracer2File, sverdrup)
+                                       tracer2File, sverdrup, sig)
         timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
 
         def bounds_of(e):
@@ -519,12 +561,12 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         edges = parseClasses(classes)
         if carry:
             totals, fld = carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracerFile, carryFile,
-                                      float(carryRef), sverdrup)
+                                      float(carryRef), sverdrup, sig)
             totals = totals * float(carryScale)
             title = (f'# transport of {carry} by {tracer} class [{carry} x {unit}' +
                      (f' x {float(carryScale):g}' if float(carryScale) != 1.0 else '') + ']\n')
         else:
-            totals, fld = classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, sverdrup)
+            totals, fld = classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, sverdrup, sig)
             title = f'# water flow by {tracer} class [{unit}]\n'
         timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
         bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
@@ -589,6 +631,11 @@ if __name__ == '__main__':
                     help='reference value subtracted from the tracer (theta_ref of a heat transport across an open section)')
     ap.add_argument('--tracer-scale', dest='tracerScale', type=float, default=1.0, metavar='S',
                     help='multiply the tracer transport by S (with -s: 1e6 * rho0 * c_p * 1e-15 = 4.1e-3 turns Sv degC into PW)')
+    ap.add_argument('--sigma', default='', metavar='THETA,SALT[,PREF]',
+                    help='in place of --tracer NAME as the class field of --classes, --gross-classes, --carry and --classes2: '
+                         'the potential density sigma_PREF (EOS-80; PREF in dbar, default 0) of potential temperature THETA and '
+                         'practical salinity SALT, computed on the GPU one time step at a time; the two are read from the T '
+                         'file, or from --tracer-file')
     ap.add_argument('--classes', default='', metavar='E0,E1,...,EN',
                     help='water flow binned by the class of --tracer NAME (e.g. sigma0): one CSV line per time step and '
                          'class [-inf,E0), [E0,E1), ..., [EN,inf), and a last one (nan,nan) for faces without a value')
