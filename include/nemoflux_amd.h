@@ -404,6 +404,32 @@ int nf_field_compute_gross_profile_async(nf_field **self, long tIndex, int carry
  * planes, class or joint state nor a captured pass. */
 int nf_field_compute_gross_class_transport(nf_field **self, long tIndex, int carry, double *rows_host);       /* (2, n+2, row_length): P, N */
 int nf_field_compute_gross_class_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev);  /* HBM, field's stream */
+/* Section area in tracer classes: the area of the section that every class occupies, and the area-weighted tracer in it --
+ * the pseudo-depth axis of an overturning streamfunction in density space, the mean theta of a sigma class, and the A and T rows
+ * that split the transport of a tracer into throughflow, overturning and gyre parts in class space instead of by level.  Needs
+ * nf_field_set_tracer and nf_field_set_class_edges (else NF_ERR_STATE, as nf_field_compute_class_transport).  One time step t
+ * over the owned levels; for every weight record and every slot i, in the order south, east, north, west:
+ *   alpha_i, beta_i  the slot's area term and tracer term of nf_field_compute_area_profile: alpha = |w_i| * (th_i * arc_i) where
+ *        the face counts -- its velocity is present, the tracer of nf_field_set_tracer has a finite face value x, the slot is
+ *        not the south slot of row 0 -- and beta = alpha * (x - ref); th_i = thickness[z] or, with a cell thickness set,
+ *        fixth(e3u) / fixth(e3v) at the slot's own face.  NO Sverdrup scale
+ *   r_i  the class row of the slot's face, 0 .. n+1 as in nf_field_compute_class_transport (n+1: no class value), from the raw
+ *        face value of the class field: the class tracer when one is set, else the tracer; wrap_x is the tracer's
+ *   A[r_i] += alpha_i,   B[r_i] += beta_i   where the face counts; a face that does not count is in neither.
+ * A lane's accumulator of a row starts at +0.0 and takes its terms with z ascending and the slots in order; then the fixed tree
+ * of the transect reduction follows: no atomics, bitwise reproducible.  rows (2, n + 2, row_length): A then B, each row
+ * [segments | transects], written whole; a step this rank does not touch gives exact zeros.  A >= 0.  Without a class tracer
+ * row n+1 is empty: a face counts only where the tracer, which is then the class field, has a value.  The sum of A (of B) over
+ * the classes is the sum over z of the A (the T) of nf_field_compute_area_profile up to rounding; a class field equal to the
+ * level index with edges at the half-integers gives those rows bit for bit, and tau == ref + 1 (ref an integer) gives B == A bit
+ * for bit.  The rows do not depend on the values of uo / vo, only on where they are present.  The terms go through the term
+ * table of the joint class transport with TWO entries per record and owned level, the alphas and the betas (80 bytes x records
+ * x owned levels, allocated on first use, an error that names the size when it cannot be; the joint_window and joint_skip knobs
+ * apply, and the rows are the same bits for every setting).  Host-resident uo / vo, tracers and time-varying cell thickness are
+ * staged per step.  The calls change neither the resident planes, |.| arrays, running max, last row, tracer planes, class or
+ * joint state nor a captured pass. */
+int nf_field_compute_class_area(nf_field **self, long tIndex, double *rows_host);       /* (2, n+2, row_length): A, B */
+int nf_field_compute_class_area_async(nf_field **self, long tIndex, double *rows_dev);  /* HBM, field's stream */
 /* Class tracer: a second, optional tracer at T-points (potential density sigma) that gives the faces their class value
  * instead of the tracer of nf_field_set_tracer, which is then only carried (heat by density class).  Same (nt,nz,ny,nx) and
  * dtype as uo/vo (else NF_ERR_ARG, the message naming both; set_uv first: NF_ERR_STATE); host (staged per step into a buffer

@@ -138,6 +138,8 @@ _sig('nf_field_compute_gross_profile', [_pp, ctypes.c_long, ctypes.c_int, c_doub
 _sig('nf_field_compute_gross_profile_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_compute_gross_class_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
 _sig('nf_field_compute_gross_class_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
+_sig('nf_field_compute_class_area', [_pp, ctypes.c_long, c_double_p])
+_sig('nf_field_compute_class_area_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_set_class_tracer', [_pp, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double])
 _sig('nf_field_set_class_tracer_missing_value', [_pp, ctypes.c_double])
 _sig('nf_field_set_cell_thickness', [_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int,

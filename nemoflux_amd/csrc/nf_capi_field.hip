@@ -20,8 +20,8 @@ static int g_batch_steps = 1;
 //   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
 //   "area_chunk"           levels per launch of the area profile: 2 or 4 (float64), 4 or 8 (float32); 0 = the measured default
 //   "gross_chunk"          levels per launch of the gross profile: 2, 4 or 8 (float64), 4 or 8 (float32); 0 = the measured default
-//   "joint_window"         rows of the joint class transport (and of the gross class transport) per pass over the term table,
-//                          1 .. 32 (default 32)
+//   "joint_window"         rows of the joint class transport (and of the gross class transport and the class area) per pass
+//                          over the term table, 1 .. 32 (default 32)
 //   "joint_skip"           1 = a block of the joint binning whose records have no term in the window does not read the table
 //                          (default 1: docs/EXPERIMENTS.md); the rows are the same bits either way
 static long g_batch_cellsteps = 32l << 20;
@@ -189,8 +189,9 @@ struct nf_field {
     // axis A then axis B in one set.  The term table (40 bytes per record and
     // owned level), the block flags and the run sums of one window are allocated on first use, grown when the records, the
     // owned levels or the rows ask for more -- their layout is taken from the call's own sizes, never from an earlier one's
-    // -- and dropped with the weights.  The gross class transport (nf_field_compute_gross_class_transport) uses the same three
-    // buffers with the 1-D class edges: each call sizes them for itself.
+    // -- and dropped with the weights.  The gross class transport (nf_field_compute_gross_class_transport) and the class area
+    // (nf_field_compute_class_area, two table entries per record and owned level) use the same three buffers with the 1-D
+    // class edges: each call sizes them for itself.
     EdgeSet joint_edges;
     int joint_na = 0, joint_nb = 0;
     DevArray<char> joint_table;
@@ -843,6 +844,56 @@ static int field_gross_class_async(nf_field *f, long t, bool carry, double *rows
     a.scratch_len = f->joint_scratch.size();
     a.rows = rows_dev;
     return launch_gross_class_transport(a, f->stream);
+}
+
+// Section area (A) and area-weighted tracer (B) of step t in the classes of the class field on the field's stream: rows_dev
+// (2, nedges + 2, row_length) = A, B, written whole.  Owned levels only, exact zeros for a step this rank does not touch.  The
+// class field is the class tracer when one is set, else the tracer, which is the carried one either way.  It takes a cell
+// thickness, as the area profile does.  The term table, flags and run sums are the joint class transport's buffers, grown to the
+// larger need: the table takes two entries per (record, owned level) here.  Reads the raw fields, the tracers, the cell
+// thickness when one is set and the records; the resident planes, |.| arrays, running max, last row, tracer planes, class and
+// joint rows, version and a captured pass stay as they are.
+static int field_class_area_async(nf_field *f, long t, double *rows_dev)
+{
+    const int nedges = (int)f->class_edges.host.size();
+    const size_t nrows = 2 * ((size_t)nedges + 2);
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_class_area", t, 2, rows_dev, nrows, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
+    const int window = g_joint_window;
+    const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
+    const size_t table_bytes = kClassAreaEntryBytes * nrec * (size_t)(lv.z1 - lv.z0);
+    if (f->joint_table.size() == 0 || f->joint_table.size() < table_bytes) {
+        if (f->joint_table.alloc(table_bytes) != NF_OK) {
+            char buf[256];
+            snprintf(buf, sizeof buf,
+                     "compute_class_area: cannot allocate the term table of %zu bytes (80 bytes x %zu records x %d owned levels)",
+                     table_bytes, nrec, lv.z1 - lv.z0);
+            NF_REQUIRE(false, NF_ERR_HIP, buf);
+        }
+    }
+    NF_TRY(f->joint_flags.reserve(blocks * (size_t)joint_flag_words((int)nrows, window)));
+    NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
+    ClassAreaArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.carry));
+    a.cls = a.carry;                                                               // the tracer is carried ...
+    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.cls));   // ... and binned by the class tracer when one is set
+    NF_TRY(field_cell_thick(f, t, lv, &a.th));
+    a.edges = f->class_edges.dev.get();
+    a.nedges = nedges;
+    a.window = window;
+    a.skip = g_joint_skip;
+    a.tr = field_transects(f);
+    a.table = f->joint_table.get();
+    a.table_len = f->joint_table.size();
+    a.flags = f->joint_flags.get();
+    a.flags_len = f->joint_flags.size();
+    a.scratch = f->joint_scratch.get();
+    a.scratch_len = f->joint_scratch.size();
+    a.rows = rows_dev;
+    return launch_class_area(a, f->stream);
 }
 
 // steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
@@ -1675,6 +1726,33 @@ try {
     nf_field *f = *self;
     NF_NEED_DEVICE();
     return field_gross_class_async(f, tIndex, carry != 0, rows_dev);
+}
+NF_API_CATCH
+
+// the checks of the two class area calls that need no device: arguments, then the tracer and the class edges
+static int field_class_area_args(nf_field **self, const void *rows, const char *what)
+{
+    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, std::string(what) + ": null argument");
+    return field_class_ready(*self, what);
+}
+
+int nf_field_compute_class_area(nf_field **self, long tIndex, double *rows_host)
+try {
+    NF_TRY(field_class_area_args(self, rows_host, "nf_field_compute_class_area"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    const size_t n = 2 * (f->class_edges.host.size() + 2) * field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_area_async(f, tIndex, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_class_area_async(nf_field **self, long tIndex, double *rows_dev)
+try {
+    NF_TRY(field_class_area_args(self, rows_dev, "nf_field_compute_class_area_async"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    return field_class_area_async(f, tIndex, rows_dev);
 }
 NF_API_CATCH
 

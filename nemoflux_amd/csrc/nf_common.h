@@ -583,6 +583,36 @@ struct GrossClassArgs {
 };
 int launch_gross_class_transport(const GrossClassArgs &a, hipStream_t s);
 
+// Section area and area-weighted tracer in tracer classes (nf_field_compute_class_area, nf_integral.hip): the alpha and beta of
+// the area profile sent to the class row of their own face instead of their level: rows (2, nedges + 2, row_length) = A, B, row
+// part * (nedges + 2) + r of JointArgs' window bitmap, binned by the joint classes' stage 2.  A table entry holds one term per
+// slot and a (record, level) has two, so the table takes TWO entries per (record, owned level) in JointArgs' layout over
+// 2 * (z1 - z0) "levels": entries [0, z1 - z0) the alphas, [z1 - z0, 2 (z1 - z0)) the betas -- 80 bytes per (record, level),
+// one round of gathers (DESIGN.md section 4 has the choice).  carry: the tracer of the area profile, required; cls: the class
+// field, the same array or another.  th.e3u set: every slot's term takes the thickness at its own face.  scale and sverdrup of
+// StepInput are not read.  Stage 1 issues the gathers of kClassAreaLevels levels together, the gross class batch.
+constexpr int kClassAreaLevels = kGrossClassLevels;
+constexpr size_t kClassAreaEntryBytes = 2 * kJointEntryBytes;
+struct ClassAreaArgs {
+    StepInput in;
+    TracerIn cls;                // the class field; its wrap_x is the rule of every face, its ref is not read
+    TracerIn carry;              // the carried tracer (the class field itself, or another array)
+    CellThick th;
+    const double *edges = nullptr;   // device, nedges
+    int nedges = 0;
+    int window = 0;              // rows per pass over the table, 1 .. kClassWindowMax
+    int skip = 1;                // 1: a stage-2 block whose flag is clear does not read the table
+    Transects tr;
+    char *table = nullptr;       // kClassAreaEntryBytes * nrec * (z1 - z0) bytes
+    size_t table_len = 0;
+    unsigned *flags = nullptr;   // blocks * joint_flag_words(2 * (nedges + 2), window) words
+    size_t flags_len = 0;
+    double *scratch = nullptr;   // nrec * window run sums
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // (2 * (nedges + 2), row_length)
+};
+int launch_class_area(const ClassAreaArgs &a, hipStream_t s);
+
 // VectorInterp (field.py:90-95,119-120)
 // targets_dev: caller order (n,3); sorted_dev: the same points sorted by y; order_dev: caller index of sorted point q
 int launch_find_points(const double *xy, long ncell, long row_length, LocatorBoxes *keep, const double *targets_dev, long npts,

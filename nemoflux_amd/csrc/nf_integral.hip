@@ -560,6 +560,20 @@ __device__ inline void area_terms(const Record &r, const SlotTh &th, const Level
     *area = ((as + ae) + an) + aw;
     *tsum = ((bs + be) + bn) + bw;
 }
+// One slot's term of area_terms on its own, for the kernel that sends every slot to a row of its own (k_class_area_terms): the
+// same expressions, so the same bits.  Returns whether the face counts; *face: the raw face value of the carried tracer (a
+// value only where the face counts).
+template <typename T>
+__device__ inline bool area_slot(bool slot, double w, double th, T vel, double a, T ta, T tb, bool has_b, T fill, T fill2, bool two,
+                                 const TauIn<T> &ti, double *alpha, double *beta, double *face)
+{
+    const bool has = tr_face_raw<T>(ta, tb, has_b, ti.m1, ti.m2, face);
+    const bool counts = slot && has && __builtin_isfinite(*face) && uv_present<T>(vel, fill, fill2, two);
+    const double al = counts ? __builtin_fabs(w) * (th * a) : 0.0;
+    *alpha = al;
+    *beta = counts ? al * (*face - ti.ref) : 0.0;
+    return counts;
+}
 
 template <typename T, int LZ, typename... TI>
 __global__ __launch_bounds__(kBlock) void k_area_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
@@ -1367,6 +1381,163 @@ int launch_gross_class_transport(const GrossClassArgs &a, hipStream_t s)
     if (in.dtype == NF_F64) return launch_gross_class_form<double>(a, s);
     if (in.dtype == NF_F32) return launch_gross_class_form<float>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "gross class transport: dtype must be NF_F64 or NF_F32");
+}
+
+// ---- section area in tracer classes: k_class_area_terms, then k_joint_bin ---------------------------------------------
+// Where the area profile and the class transport cross: per (record, owned level, slot) the alpha and beta of area_terms
+// (area_slot) and the class row r of the slot's face, k_class_segscan's, from the class field -- the carried tracer itself
+// (TWO = false: one set of 5 gathers, the face value that makes the face count is its class value) or a class field of its own
+// (TWO = true: a counted face without a class value goes to row nedges + 1).  alpha goes to row r of part 0 (A), beta to row
+// (nedges + 2) + r of part 1 (B); a slot that does not count (row 0's south slot among them) to kJointNoRow in both.  A table
+// entry of JointArgs' layout holds ONE term per slot, so a (record, level) takes two: entry zi of the nlev owned levels holds
+// the alphas, entry nlev + zi the betas, and stage 2 is k_joint_bin as it stands over 2 * nlev "levels" -- a lane's accumulator
+// of a row starts at +0.0 and takes its terms z ascending, slots in order, because a row of A meets only the first nlev entries
+// and a row of B only the last.  The velocities are gathered for their presence alone; the widest form gathers 4 + 4 + 5 + 5
+// values per level, once.  TI: empty or ThickIn<T>, the per-cell thicknesses.  LZ: the levels whose gathers are issued together.
+// LDS: the edges (nedges doubles), then the block's window bitmap (nwords words).
+template <typename T, bool TWO, int LZ, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_class_area_terms(const int *__restrict__ cell, const double *__restrict__ w4, long n,
+                                                             const T *__restrict__ u, const T *__restrict__ v, long ncell,
+                                                             unsigned nx, int z0, int z1, const double *__restrict__ thickness,
+                                                             const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                             T fill, T fill2, int two, TauIn<T> cls, TauIn<T> carry,
+                                                             const double *__restrict__ edges, int nedges, int top, int window,
+                                                             int nwords, dvec2 *__restrict__ terms, usvec4 *__restrict__ rows,
+                                                             unsigned *__restrict__ flags, TI... extra)
+{
+    constexpr bool CT = sizeof...(TI) > 0;
+    const ThickIn<T> ct = thick_arg<T>(extra...);
+    extern __shared__ double class_area_lds[];
+    const double *e = class_area_lds;
+    unsigned *bits = reinterpret_cast<unsigned *>(class_area_lds + nedges);
+    for (int q = threadIdx.x; q < nedges; q += kBlock) class_area_lds[q] = edges[q];
+    for (int q = threadIdx.x; q < nwords; q += kBlock) bits[q] = 0u;
+    __syncthreads();
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    if (k < n) {
+        const Record r = load_record(cell, w4, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, carry.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        const long ztot = z1 - z0;
+        // one slot: its alpha and beta and its row in A, kJointNoRow where the face does not count (its row in B: part_b);
+        // both windows are marked in the bitmap.  (s0, s1): the face's values of the class field, (t0, t1) of the carried tracer
+        auto slot = [&](bool on, double w, double th, T vel, double a, T s0, T s1, T t0, T t1, bool has_b, double *al,
+                        double *be) {
+            double f;
+            if (!area_slot<T>(on, w, th, vel, a, t0, t1, has_b, fill, fill2, two, carry, al, be, &f))
+                return (unsigned short)kJointNoRow;
+            bool h = true;
+            if constexpr (TWO) h = tr_face_raw<T>(s0, s1, has_b, cls.m1, cls.m2, &f);
+            const int row = class_row(h, f, e, nedges, top);
+            joint_mark_window(bits, row, window);
+            joint_mark_window(bits, nedges + 2 + row, window);
+            return (unsigned short)row;
+        };
+        auto part_b = [&](unsigned short row) {
+            return row == (unsigned short)kJointNoRow ? row : (unsigned short)(nedges + 2 + row);
+        };
+        for (int z = z0; z < z1; z += LZ) {
+            const int nlev = z1 - z < LZ ? z1 - z : LZ;
+            LevelUV<T> x[LZ];
+            LevelUV<T> e3[CT ? LZ : 1];
+            LevelTau<T> A[LZ];                // the carried tracer
+            LevelTau<T> S[TWO ? LZ : 1];      // the class field, when it is another array
+#pragma unroll
+            for (int l = 0; l < LZ; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
+                    A[l] = load_level_tau(carry.tau, o, r.c, nb);
+                    if constexpr (TWO) S[l] = load_level_tau(cls.tau, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < LZ; ++l)
+                if (l < nlev) {
+                    SlotTh th;
+                    if constexpr (CT)
+                        th = level_th(e3[l], ct);
+                    else
+                        th = slot_th(thickness[z + l]);
+                    const LevelTau<T> &C = TWO ? S[l] : A[l];
+                    Slots al, be;
+                    usvec4 ja, jb;
+                    ja.x = slot(nb.south, r.wa.x, th.s, x[l].vs, arc.Ns, C.s, C.c, A[l].s, A[l].c, true, &al.s, &be.s);
+                    ja.y = slot(true, r.wa.y, th.e, x[l].uc, arc.Ec, C.c, C.e, A[l].c, A[l].e, nb.has_e, &al.e, &be.e);
+                    ja.z = slot(true, r.wb.x, th.n, x[l].vc, arc.Nc, C.c, C.n, A[l].c, A[l].n, nb.has_n, &al.n, &be.n);
+                    ja.w = slot(true, r.wb.y, th.w, x[l].uw, arc.Ew, C.w, C.c, A[l].w, A[l].c, nb.has_w, &al.w, &be.w);
+                    jb.x = part_b(ja.x), jb.y = part_b(ja.y), jb.z = part_b(ja.z), jb.w = part_b(ja.w);
+                    const long za = z + l - z0, zb = ztot + za;
+                    __builtin_nontemporal_store(dvec2{al.s, al.e}, terms + (2 * za) * n + k);
+                    __builtin_nontemporal_store(dvec2{al.n, al.w}, terms + (2 * za + 1) * n + k);
+                    __builtin_nontemporal_store(ja, rows + za * n + k);
+                    __builtin_nontemporal_store(dvec2{be.s, be.e}, terms + (2 * zb) * n + k);
+                    __builtin_nontemporal_store(dvec2{be.n, be.w}, terms + (2 * zb + 1) * n + k);
+                    __builtin_nontemporal_store(jb, rows + zb * n + k);
+                }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < nwords; q += kBlock) flags[(long)blockIdx.x * nwords + q] = bits[q];
+}
+
+template <typename T, bool TWO, typename... TI>
+static int launch_class_area_t(const ClassAreaArgs &a, hipStream_t s, TI... extra)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const int nrows = 2 * (a.nedges + 2), nent = 2 * (in.z1 - in.z0);   // two table entries per owned level
+    const int nwords = joint_flag_words(nrows, a.window);
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    int top = 1;
+    while (2 * top <= a.nedges) top *= 2;
+    dvec2 *terms = reinterpret_cast<dvec2 *>(a.table);
+    usvec4 *rows = reinterpret_cast<usvec4 *>(a.table + sizeof(dvec2) * 2 * (size_t)ws.nrec * nent);
+    if (ws.nrec > 0) {
+        const size_t lds = sizeof(double) * (size_t)a.nedges + sizeof(unsigned) * (size_t)nwords;
+        TauIn<T> carry = tau_of<T>(a.carry);
+        carry.wrap_x = a.cls.wrap_x ? 1 : 0;
+        hipLaunchKernelGGL((k_class_area_terms<T, TWO, kClassAreaLevels, TI...>), record_grid(ws), dim3(kBlock), lds, s,
+                           ws.cell.get(), ws.w4.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0,
+                           in.z1, in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), tau_of<T>(a.cls),
+                           carry, a.edges, a.nedges, top, a.window, nwords, terms, rows, a.flags, extra...);
+        NF_HIP(hipGetLastError());
+    }
+    return launch_joint_bins(a.tr, nrows, nent, a.window, a.skip, terms, rows, a.flags, nwords, a.scratch, a.rows, s);
+}
+
+// the two forms of one dtype, each with the scalar or the per-cell thicknesses
+template <typename T, bool TWO>
+static int launch_class_area_th(const ClassAreaArgs &a, hipStream_t s)
+{
+    if (a.th.e3u) return launch_class_area_t<T, TWO>(a, s, thick_in<T>(a.th));
+    return launch_class_area_t<T, TWO>(a, s);
+}
+template <typename T>
+static int launch_class_area_form(const ClassAreaArgs &a, hipStream_t s)
+{
+    const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
+    return one ? launch_class_area_th<T, false>(a, s) : launch_class_area_th<T, true>(a, s);
+}
+
+int launch_class_area(const ClassAreaArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "class area: bad class edges");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "class area: bad window");
+    NF_TRY(check_raw_step("class area", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.cls.tau && a.carry.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+               "class area: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "class area: null argument");
+    if (a.tr.row_length() == 0) return NF_OK;
+    const size_t nrec = (size_t)a.tr.ws->nrec, blocks = (nrec + kBlock - 1) / kBlock;
+    NF_REQUIRE(nrec == 0 || (a.table && a.table_len >= kClassAreaEntryBytes * nrec * (size_t)(in.z1 - in.z0)), NF_ERR_ARG,
+               "class area: the term table is too small");
+    NF_REQUIRE(nrec == 0 || (a.flags && a.flags_len >= blocks * (size_t)joint_flag_words(2 * (a.nedges + 2), a.window)),
+               NF_ERR_ARG, "class area: the flag array is too small");
+    if (in.dtype == NF_F64) return launch_class_area_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_class_area_form<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "class area: dtype must be NF_F64 or NF_F32");
 }
 
 }  // namespace nf

@@ -719,7 +719,7 @@ class Field(object):
         (a float64 mesh_mask thickness beside float32 velocities is rounded to float32); a device array or a time-varying
         array of another dtype raises.  fill_value / missing_value: the thickness's own missing markers (a file's when not
         given); a thickness that is NaN or a marker counts as 0.
-        computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux, computeTracerAll, computeAreaProfile and
+        computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux, computeTracerAll, computeAreaProfile, computeClassArea and
         computeGrossProfile and computeGrossClassTransport (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
         set.  timeMean and meanEddyTracerTransport carry a static thickness over to the mean state and take a time-varying one
         with thicknessWeighted=True (thickness-weighted mean velocities, mean thicknesses).  setCellThickness(None, None) goes
@@ -952,7 +952,8 @@ class Field(object):
         """Split a tracer transport into its throughflow, overturning and gyre parts.  Host only, float64, on rows that have
         been summed over all ranks first (the step is not linear).  volumeProfile: V (nz, n) of computeFluxProfile;
         areaRows: the pair (A, T), each (nz, n), of computeAreaProfile; tracerRow: H (n,) of computeTracerFlux -- totals or
-        segments alike.  Per column, with m(z) = T(z) / A(z) (0 where A(z) = 0) and M = sum_z T / sum_z A (0 where the sum is 0):
+        segments alike; the rows may be classes instead of levels: V of computeClassTransport, (A, B) of computeClassArea
+        (decomposeTracerTransportByClass).  Per column, with m(z) = T(z) / A(z) (0 where A(z) = 0) and M = sum_z T / sum_z A (0 where the sum is 0):
             throughflow = (sum_z V(z)) * M,   overturning = sum_z V(z) * (m(z) - M),   gyre = H - throughflow - overturning.
         Returns a dict of 'total' (= H), 'throughflow', 'overturning', 'gyre', each (n,), and 'mean' = m, (nz, n)."""
         V = numpy.asarray(volumeProfile, dtype=numpy.float64)
@@ -1259,6 +1260,101 @@ class Field(object):
             rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
             check(lib.nf_field_compute_gross_class_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
         return self._split_rows(rows.reshape(2, nrows, self._row_width))
+
+    def computeClassArea(self, tIndex, out=None, prefetch_next=None):
+        """Section area of time step tIndex in tracer classes (setTracer and setClassEdges first): (totals, segments) of shape
+        (2, nedges+2, ntransect) and (2, nedges+2, nseg), part 0 = A, the area of the section that every class occupies,
+        part 1 = B, the area-weighted tracer of setTracer (reference subtracted) in it; rows and class field as in
+        computeClassTransport.  Every term of computeAreaProfile -- |w| * th * arc over the faces that count (velocity present,
+        tracer face value finite), and the same times (tracer face value - reference) -- goes to the row of its own face's
+        class instead of its level, so the rows add up over the classes to the depth sums of computeAreaProfile (up to
+        rounding).  th is thickness[z], or the cell thickness at the face when one is set (setCellThickness).  No Sverdrup
+        scale.  With a class field of its own (setClassTracer, or a Sigma) row nedges+1 holds the counted faces without a
+        class value; without one it is empty.  A goes into classInterfaceDepth (the depth axis of classStreamfunction), the
+        pair into classMeanTracer (the mean theta of a sigma class) and into overturningGyre
+        (decomposeTracerTransportByClass).  Levels this rank does not own (slab_range) contribute nothing.  Leaves the
+        resident edge fluxes, the running max, the row of the last computeFlux and the tracer, class and joint rows as they
+        are.  `out`: optional contiguous float64 torch CUDA tensor (2 * (nedges+2), row_length), A's rows then B's, that
+        receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_class_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setClassEdges first')
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        nrows = edges.size + 2
+        if out is not None:
+            out = self._rows_out(out, 2 * nrows)
+            check(lib.nf_field_compute_class_area_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_class_area(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        return self._split_rows(rows.reshape(2, nrows, self._row_width))
+
+    @staticmethod
+    def classMeanTracer(areaParts, reference=0.0):
+        """Area-weighted mean tracer of every class: B / A + reference from the parts (2, ...) = A, B of computeClassArea
+        (totals or segments alike); `reference`: the reference of setTracer, which B has subtracted.  NaN where A is 0."""
+        P = numpy.asarray(areaParts, dtype=numpy.float64)
+        if P.ndim < 1 or P.shape[0] != 2:
+            raise ValueError(f'classMeanTracer: the parts must have shape (2, ...), got {P.shape}')
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(P[0] != 0.0, P[1] / P[0] + float(reference), numpy.nan)
+
+    @staticmethod
+    def classInterfaceDepth(classArea, areaProfile, bounds_depth):
+        """Pseudo-depth of the class interfaces: the depth axis that classStreamfunction is drawn against.  Host only,
+        float64, on rows that have been summed over all ranks first (the step is not linear).  classArea: A (nedges+2, n) of
+        computeClassArea; areaProfile: A(z) (nz, n) of computeAreaProfile; bounds_depth (nz, 2), top then bottom of every
+        level (a Field's bounds_depth) -- totals or segments alike.  Per column and edge k, with
+            phi_k = (A[0] + ... + A[k]) / (A[0] + ... + A[nedges])      (the row of the faces without a class value left out)
+        the result is the depth d above which the section has that fraction of its area: G(d) / G(inf) = phi_k, G the
+        piecewise-linear area above d, level z filling linearly between its two bounds; where G is flat, the shallowest such
+        d.  Returns (nedges, n), non-decreasing in k; NaN where either total is 0."""
+        C = numpy.asarray(classArea, dtype=numpy.float64)
+        Z = numpy.asarray(areaProfile, dtype=numpy.float64)
+        bd = numpy.asarray(bounds_depth, dtype=numpy.float64)
+        if C.ndim != 2 or C.shape[0] < 4 or Z.ndim != 2 or Z.shape[1] != C.shape[1] or bd.shape != (Z.shape[0], 2):
+            raise ValueError(f'classInterfaceDepth: need classArea (nedges+2, n) with nedges >= 2, areaProfile (nz, n) and '
+                             f'bounds_depth (nz, 2), got {C.shape}, {Z.shape}, {bd.shape}')
+        top, bot = bd[:, 0], bd[:, 1]
+        if not numpy.all(bot > top):
+            raise ValueError('classInterfaceDepth: every level needs bounds_depth[z, 0] < bounds_depth[z, 1]')
+        nedges, n = C.shape[0] - 2, C.shape[1]
+        cum = numpy.cumsum(C[:nedges + 1], axis=0)             # cum[k] = A[0] + ... + A[k]; cum[nedges]: the class total
+        b = numpy.unique(bd)                                   # the depths at which G changes slope
+        G = numpy.zeros((b.size, n))                           # G at those depths, the levels added z ascending
+        for z in range(Z.shape[0]):
+            G += numpy.clip((b - top[z]) / (bot[z] - top[z]), 0.0, 1.0)[:, None] * Z[z][None, :]
+        depth = numpy.full((nedges, n), numpy.nan)
+        for c in range(n):
+            if not (cum[nedges, c] > 0.0 and G[-1, c] > 0.0):
+                continue
+            g = (cum[:nedges, c] / cum[nedges, c]) * G[-1, c]
+            i = numpy.minimum(numpy.searchsorted(G[:, c], g, side='left'), b.size - 1)   # the first depth with G >= g
+            lo = numpy.maximum(i - 1, 0)
+            rise = G[i, c] - G[lo, c]
+            with numpy.errstate(divide='ignore', invalid='ignore'):
+                f = numpy.where(rise > 0.0, (g - G[lo, c]) / rise, 1.0)
+            depth[:, c] = numpy.where(i > 0, b[lo] + f * (b[i] - b[lo]), b[0])
+        return depth
+
+    def decomposeTracerTransportByClass(self, tIndex):
+        """The tracer transport of time step tIndex and its throughflow, overturning and gyre parts with the classes of the
+        class field in the place of the levels (setTracer and setClassEdges first), for the transect totals: the overturning
+        part is what the diapycnal circulation carries, the gyre part what is carried along the classes.  overturningGyre
+        with V = the class transport rows (P + N of computeGrossClassTransport when a cell thickness is set, else
+        computeClassTransport), (A, B) of computeClassArea and H of computeTracerFlux; 'mean' is then (nedges+2, ntransect).
+        On one rank only; sharded runs reduce the rows first (docs/MULTIGPU.md)."""
+        if getattr(self, '_e3', None) is not None:
+            P = self.computeGrossClassTransport(tIndex)[0]
+            V = P[0] + P[1]
+        else:
+            V = self.computeClassTransport(tIndex)[0]
+        AB = self.computeClassArea(tIndex)[0]
+        H = self.computeTracerFlux(tIndex)[0]
+        return self.overturningGyre(V, (AB[0], AB[1]), H)
 
     @staticmethod
     def classStreamfunction(rows):

@@ -22,6 +22,9 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --gross [--tracer thetao] [--zrange 0,700] (inflow, outflow and net of every transect; what they carry, their mean thetao)
     ... --tracer sigma0 --tracer-file S.nc --gross-classes 26,27,28 [--carry thetao] [--cell-thickness]
                                   (inflow, outflow and net of every sigma0 class: one CSV line per time step, transect and class)
+    ... --tracer sigma0 --tracer-file S.nc --class-area 26,27,28 [--carry thetao] [--cell-thickness]
+                                  (section area, mean carried tracer and interface depth of every sigma0 class: one CSV line
+                                  per time step, transect and class; --sigma thetao,so in place of --tracer works too)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
 """
@@ -266,6 +269,57 @@ def checkGrossClassArgs(grossClasses='', tracer='', tracerRef=0.0, tracerScale=1
         raise RuntimeError(str(e).replace('--classes', '--gross-classes'))
 
 
+CLASS_AREA_COLUMNS = ('area', 'mean', 'depth')
+
+
+def classAreaSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', carry='', carryFile='', carryRef=0.0,
+                    cellThickness=None, sigma=None):
+    """(nt, 3, nedges+2, ntransect), CLASS_AREA_COLUMNS: the section area that every class of the variable `tracer` of
+    tracerFile (default: the T file) occupies, the area-weighted mean of the carried tracer in it -- `carry` of carryFile
+    (reference carryRef), else the class field itself -- and the pseudo-depth of the class's upper edge (NaN for the two last
+    rows, which have none), and the Field: Field.computeClassArea and Field.computeAreaProfile per time step, then
+    Field.classMeanTracer and Field.classInterfaceDepth on the transect totals."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, False, cellThickness)
+    if carry:
+        fld.setTracer((carryFile or tFile, carry), reference=carryRef)
+        fld.setClassTracer(_classField(tFile, tracer, tracerFile, sigma))
+    else:
+        fld.setTracer(_classField(tFile, tracer, tracerFile, sigma))
+    fld.setClassEdges(edges)
+    totals = numpy.full((fld.nt, 3, len(edges) + 2, len(lonLatZPoints)), numpy.nan)
+    for t in range(fld.nt):
+        parts = fld.computeClassArea(t)[0]
+        byLevel = fld.computeAreaProfile(t, prefetch_next=True)[0][0]
+        totals[t, 0] = parts[0]
+        totals[t, 1] = fld.classMeanTracer(parts, carryRef if carry else 0.0)
+        totals[t, 2, :len(edges)] = fld.classInterfaceDepth(parts[0], byLevel, fld.bounds_depth)
+    return totals, fld
+
+
+def checkClassAreaArgs(classArea='', tracer='', tracerRef=0.0, tracerScale=1.0, carryScale=1.0, classes='', classes2='',
+                       gross=False, grossClasses='', levels=False, zrange='', decompose=False, eddy=False, show=False):
+    """the --class-area option of the command line (section area, mean tracer and interface depth of every tracer class):
+    refused combinations raise RuntimeError"""
+    if not classArea:
+        return
+    if not tracer:
+        raise RuntimeError('ERROR: --class-area needs --tracer NAME or --sigma THETA,SALT[,PREF] (the class field, e.g. sigma0)')
+    for on, opt in ((classes, '--classes'), (classes2, '--classes2'), (gross, '--gross'), (grossClasses, '--gross-classes'),
+                    (levels, '--levels'), (zrange, '--zrange'), (decompose, '--decompose'), (eddy, '--eddy'), (show, '--show')):
+        if on:
+            raise RuntimeError(f'ERROR: --class-area and {opt} cannot be combined: --class-area writes the section area, the mean '
+                               f'carried tracer and the interface depth of every class of --tracer as CSV only')
+    if float(tracerRef) != 0.0 or float(tracerScale) != 1.0:
+        raise RuntimeError('ERROR: --class-area bins by the raw tracer: --tracer-ref / --tracer-scale do not apply '
+                           '(--carry-ref does, with --carry NAME)')
+    if float(carryScale) != 1.0:
+        raise RuntimeError('ERROR: --class-area writes the mean of --carry NAME, not a transport: --carry-scale does not apply')
+    try:
+        parseClasses(classArea)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace('--classes', '--class-area'))
+
+
 def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
     """the --gross option of the command line: refused combinations raise RuntimeError"""
     if not gross:
@@ -447,35 +501,51 @@ def parseZRange(zrange):
 def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, output='', show=False, zrange='',
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
-         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma=''):
+         eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
+         classArea=''):
     sig = None
     if sigma:
         # the class field computed from two variables: in the tables it goes by the name sigmaName gives it
         if tracer:
             raise RuntimeError('ERROR: --sigma and --tracer cannot be combined: --sigma THETA,SALT[,PREF] is the class field in '
                                'place of --tracer NAME')
-        if not (classes or grossClasses or classes2):
-            raise RuntimeError('ERROR: --sigma needs --classes, --gross-classes or --classes2: it is the class field of the '
-                               'class transports (with --carry NAME too)')
+        if not (classes or grossClasses or classes2 or classArea):
+            raise RuntimeError('ERROR: --sigma needs --classes, --gross-classes or --classes2 (or --class-area): it is the class '
+                               'field of the class transports (with --carry NAME too)')
         sig = parseSigma(sigma)
         tracer = sigmaName(sig[2])
     checkGrossClassArgs(grossClasses, tracer, tracerRef, tracerScale, classes, classes2, gross, levels, zrange, decompose, eddy,
                         show)
+    checkClassAreaArgs(classArea, tracer, tracerRef, tracerScale, carryScale, classes, classes2, gross, grossClasses, levels,
+                       zrange, decompose, eddy, show)
     checkThicknessWeightedArgs(thicknessWeighted, eddy, cellThickness)
     checkGrossArgs(gross, classes, levels, decompose, eddy, show)
     checkJointClassArgs(classes2, tracer2, tracer2File, tracer, classes, carry, levels, zrange, show, eddy, decompose)
     checkEddyArgs(eddy, tracer, classes, levels, zrange, show, decompose)
     checkDecomposeArgs(decompose, tracer, classes, levels, zrange, show)
-    # --gross-classes takes --carry and --cell-thickness together: its form of the class transports has per-cell thicknesses
-    checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, '' if grossClasses else carry, levels, tracer)
+    # --gross-classes and --class-area take --carry and --cell-thickness together: their forms have per-cell thicknesses
+    checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, classes, '' if grossClasses or classArea else carry, levels,
+                           tracer)
     checkClassArgs(classes, tracer, tracerRef, tracerScale, zrange, show)
     checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '' if gross else zrange)   # --gross sums its parts over a band
     checkLevelsArgs(levels, zrange, classes, show)
-    checkCarryArgs(carry, carryFile, carryRef, carryScale, classes or grossClasses, tracer, levels)
+    checkCarryArgs(carry, carryFile, carryRef, carryScale, classes or grossClasses or classArea, tracer, levels)
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
     ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    if classArea:
+        edges = parseClasses(classArea)
+        totals, fld = classAreaSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
+                                      float(carryRef), ct, sig)
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
+        lines = ['time,transect,lower,upper,' + ','.join(CLASS_AREA_COLUMNS)]
+        lines += [f'{timeVals[t]},{name},{lo:.15g},{hi:.15g},' + ','.join(f'{x:.15g}' for x in totals[t, :, k, p])
+                  for t in range(fld.nt) for p, name in enumerate(names) for k, (lo, hi) in enumerate(bounds)]
+        _emit(f'# section area by {tracer} class [A m], mean {carry or tracer} of the class and depth of its upper edge\n' +
+              '\n'.join(lines) + '\n', output)
+        return totals
     if grossClasses:
         edges = parseClasses(grossClasses)
         totals, fld = grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
@@ -669,6 +739,12 @@ if __name__ == '__main__':
                          '(time,transect,lower,upper,inflow,outflow,net): the water of that class that crosses in the positive '
                          'direction, the water that comes back, and their sum; with --carry NAME what the two carry of NAME '
                          '(--carry-ref, --carry-scale, --cell-thickness and -s apply)')
+    ap.add_argument('--class-area', dest='classArea', default='', metavar='E0,E1,...,EN',
+                    help='with --tracer NAME or --sigma (the class field): one CSV line per time step, transect and class '
+                         '(time,transect,lower,upper,area,mean,depth): the section area that the class occupies, the '
+                         'area-weighted mean of the class field in it -- with --carry NAME of NAME (--carry-ref applies) -- and '
+                         'the pseudo-depth of the upper edge of the class, the depth axis of an overturning streamfunction in '
+                         'class space (--cell-thickness applies; -s does not: an area has no Sverdrup scale)')
     ap.add_argument('--eddy', action='store_true',
                     help='with --tracer NAME: one CSV line per part (part,...): the mean over all time steps of the transport of '
                          'NAME, the transport of the time-mean NAME by the time-mean flow, and the eddy part, their difference '
