@@ -378,6 +378,33 @@ int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *ro
  * P(carry = 1) / P(carry = 0) + ref, where the tracer is present wherever the velocity is. */
 int nf_field_compute_gross_profile(nf_field **self, long tIndex, int carry, double *rows_host);       /* (2, nz, row_length): P, N */
 int nf_field_compute_gross_profile_async(nf_field **self, long tIndex, int carry, double *rows_dev);  /* HBM, field's stream */
+/* Crossings: the integrand of every other row.  A crossing is one record of the weights: the piece of one target segment inside
+ * one grid cell.  nf_field_num_crossings gives their number ncross = nf_field_num_weights / 4; nf_field_get_crossings gives, in
+ * record order (by segment, then along the segment), the global segment, the cell and the piece's parameters 0 <= ta < tb <= 1
+ * on its own target segment (also for a piece found through a periodic image).  Identical duplicates (halo columns, a north-fold
+ * row) keep their separate records with the same [ta, tb] and half the weight each.  Both calls need built weights (after
+ * nf_field_add_transect without nf_field_build_weights: NF_ERR_STATE, like the compute calls); nf_field_get_crossings is a
+ * blocking readback meant to be called once per weight build.
+ * nf_field_compute_crossings gives, for step t, every level z and every crossing k, out[(p * nz + z) * ncross + k]:
+ *   carry = 0, planes (q, g):  q = the sum over the record's four slots of w * d, d the slot's value of nf_field_compute_profile
+ *                              (see nf_field_compute_gross_profile's water term); g = the sum of |w| * (th * arc) over the slots
+ *                              whose velocity is present (not NaN, not a marker), without the south slot of row 0: the section
+ *                              area of the piece, no tracer condition
+ *   carry = 1, planes (q, c, a, b):  q as above; c = the record's term of nf_field_compute_tracer_profile (every slot's d with
+ *                              fixed(.) * tf); a, b = the record's terms of nf_field_compute_area_profile (A and T)
+ * th = thickness[z], or with a cell thickness set fixth(e3u) / fixth(e3v) at the slot's own face, in both forms.  q and c take
+ * the Sverdrup scale when it is on; g, a and b never do.  The four slots are added south, east, north, west, ((s + e) + n) + w,
+ * with the expressions of the profile kernels: the sum of a plane over the records of a target segment is that segment's column
+ * of nf_field_compute_profile (q), nf_field_compute_tracer_profile or P + N of nf_field_compute_gross_profile(carry = 1) (c),
+ * nf_field_compute_area_profile (a, b) up to the rounding of the sum, and bit for bit where the segment has one record.  There
+ * is no reduction at all, so sharded ranks' planes add up exactly.  Levels this rank does not own are exact zeros.  carry other
+ * than 0 or 1: NF_ERR_ARG; carry = 1 before set_tracer: NF_ERR_STATE.  Host-resident uo / vo, tracer and time-varying cell
+ * thickness are staged per step.  The calls change neither the resident planes, |.| arrays, running max, last row, tracer
+ * planes, class / joint rows nor a captured pass. */
+int nf_field_num_crossings(nf_field **self, size_t *n);   /* = num_weights / 4 */
+int nf_field_get_crossings(nf_field **self, int *seg_global, int64_t *cell, double *ta, double *tb);
+int nf_field_compute_crossings(nf_field **self, long tIndex, int carry, double *out_host);       /* (carry ? 4 : 2, nz, ncross) */
+int nf_field_compute_crossings_async(nf_field **self, long tIndex, int carry, double *out_dev);  /* HBM, field's stream */
 /* Gross transports in tracer classes: the inflow and the outflow of every class -- the dense overflow against the light water
  * above it, the two layers of a strait, a recirculating limb that the net class transport hides.  Needs nf_field_set_tracer
  * and nf_field_set_class_edges (else NF_ERR_STATE, as nf_field_compute_class_transport).  One time step t over the owned

@@ -136,6 +136,10 @@ _sig('nf_field_compute_area_profile', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_area_profile_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_compute_gross_profile', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
 _sig('nf_field_compute_gross_profile_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
+_sig('nf_field_num_crossings', [_pp, ctypes.POINTER(ctypes.c_size_t)])
+_sig('nf_field_get_crossings', [_pp, c_int_p, c_int64_p, c_double_p, c_double_p])
+_sig('nf_field_compute_crossings', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
+_sig('nf_field_compute_crossings_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_compute_gross_class_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
 _sig('nf_field_compute_gross_class_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_compute_class_area', [_pp, ctypes.c_long, c_double_p])

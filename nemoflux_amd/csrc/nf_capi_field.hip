@@ -20,6 +20,7 @@ static int g_batch_steps = 1;
 //   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
 //   "area_chunk"           levels per launch of the area profile: 2 or 4 (float64), 4 or 8 (float32); 0 = the measured default
 //   "gross_chunk"          levels per launch of the gross profile: 2, 4 or 8 (float64), 4 or 8 (float32); 0 = the measured default
+//   "crossing_chunk"       levels per launch of the crossings: 2, 4 or 8; 0 = the measured default of the form (the same bits either way)
 //   "joint_window"         rows of the joint class transport (and of the gross class transport and the class area) per pass
 //                          over the term table, 1 .. 32 (default 32)
 //   "joint_skip"           1 = a block of the joint binning whose records have no term in the window does not read the table
@@ -80,6 +81,7 @@ int field_tuning_set(const char *name, int value)
     }
     if (!strcmp(name, "area_chunk")) return area_chunk_set(value);
     if (!strcmp(name, "gross_chunk")) return gross_chunk_set(value);
+    if (!strcmp(name, "crossing_chunk")) return crossing_chunk_set(value);
     return -1;
 }
 }  // namespace nf
@@ -181,6 +183,9 @@ struct nf_field {
     DevArray<double> area_scratch;
     // gross profile (nf_field_compute_gross_profile): the run sums of one chunk, two values per level (ws.nrec * 2 * gross_chunk)
     DevArray<double> gross_scratch;
+    // crossings (nf_field_compute_crossings): the planes of a synchronous call, (2 or 4) * nz * ws.nrec doubles, sized on demand
+    // as `row` is and dropped with the weights
+    DevArray<double> crossings;
     // class transport (nf_field_set_class_edges): the edges; the run sums of one window of rows (ws.nrec * window, allocated on
     // first use, dropped with the weights)
     EdgeSet class_edges;
@@ -675,6 +680,30 @@ static int field_gross_async(nf_field *f, long t, bool carry, double *rows_dev)
     a.rows = rows_dev;
     a.nz = f->nz;
     return launch_gross_profile(a, f->stream);
+}
+
+// Crossings of step t on the field's stream: out_dev (carry ? 4 : 2, nz, ws.nrec), written whole: the planes q, g (volume
+// form) or q, c, a, b (carried form) per record and level, no reduction.  Owned levels only, exact zeros elsewhere.  Reads the
+// raw fields, the tracer (carry), the cell thickness when one is set and the records; the resident planes, |.| arrays, running
+// max, last row, tracer planes, class / joint rows, version and a captured pass stay as they are.
+static int field_crossings_async(nf_field *f, long t, bool carry, double *out_dev)
+{
+    NF_REQUIRE(t >= 0 && t < f->uv.nt, NF_ERR_ARG, "compute_crossings: time index out of range");
+    if (carry) NF_TRY(field_matches_uv(f, f->tau.dtype, f->tau.nt, "compute_crossings", "tracer"));
+    const size_t nrec = (size_t)f->ws.nrec, nplanes = carry ? 4 : 2;
+    if (nrec == 0) return NF_OK;
+    const Levels lv = field_levels(f, t);
+    if (lv.z1 <= lv.z0 || lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in every plane
+        NF_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * nplanes * (size_t)f->nz * nrec, f->stream));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    CrossingArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    if (carry) NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
+    NF_TRY(field_cell_thick(f, t, lv, &a.th));
+    a.ws = &f->ws;
+    a.out = out_dev;
+    a.nz = f->nz;
+    return launch_crossing_terms(a, f->stream);
 }
 
 // Tracer transport of step t on the field's stream: K1tau into geo.tr_planes, then K3 over them into row_dev
@@ -1263,6 +1292,7 @@ try {
     f->tprof_scratch.reset();
     f->area_scratch.reset();
     f->gross_scratch.reset();
+    f->crossings.reset();
     f->class_scratch.reset();
     f->joint_table.reset();
     f->joint_flags.reset();
@@ -1697,6 +1727,60 @@ try {
     NF_NEED_DEVICE();
     NF_TRY(field_ready(f, "compute_gross_profile", true));
     return field_gross_async(f, tIndex, carry != 0, rows_dev);
+}
+NF_API_CATCH
+
+int nf_field_num_crossings(nf_field **self, size_t *n)
+try {
+    NF_REQUIRE(self && *self && n, NF_ERR_ARG, "nf_field_num_crossings: null argument");
+    NF_REQUIRE((*self)->weights_built, NF_ERR_STATE, "nf_field_num_crossings: build_weights first");
+    *n = (size_t)(*self)->ws.nrec;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_get_crossings(nf_field **self, int *seg_global, int64_t *cell, double *ta, double *tb)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_get_crossings: null field");
+    NF_REQUIRE((*self)->weights_built, NF_ERR_STATE, "nf_field_get_crossings: build_weights first");
+    // a one-off readback: three blocking copies, the cells widened on the host
+    const WeightSet &ws = (*self)->ws;
+    const size_t n = (size_t)ws.nrec;
+    if (n == 0) return NF_OK;
+    NF_REQUIRE(seg_global && cell && ta && tb, NF_ERR_ARG, "nf_field_get_crossings: null argument");
+    NF_NEED_DEVICE();
+    std::vector<int> c(n);
+    std::vector<double> tab(2 * n);
+    NF_HIP(hipMemcpy(seg_global, ws.seg.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    NF_HIP(hipMemcpy(c.data(), ws.cell.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    NF_HIP(hipMemcpy(tab.data(), ws.tab.get(), sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n; ++k) cell[k] = c[k], ta[k] = tab[2 * k], tb[k] = tab[2 * k + 1];
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_crossings(nf_field **self, long tIndex, int carry, double *out_host)
+try {
+    NF_TRY(field_gross_args(self, carry, out_host, "nf_field_compute_crossings"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    NF_TRY(field_ready(f, "compute_crossings", true));
+    const size_t n = (carry ? 4 : 2) * (size_t)f->nz * (size_t)f->ws.nrec;
+    NF_TRY(f->crossings.reserve(n > 0 ? n : 1));
+    NF_TRY(field_crossings_async(f, tIndex, carry != 0, f->crossings.get()));
+    if (n > 0) NF_HIP(hipMemcpyAsync(out_host, f->crossings.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
+    NF_HIP(hipStreamSynchronize(f->stream));
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_compute_crossings_async(nf_field **self, long tIndex, int carry, double *out_dev)
+try {
+    NF_TRY(field_gross_args(self, carry, out_dev, "nf_field_compute_crossings_async"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    NF_TRY(field_ready(f, "compute_crossings", true));
+    return field_crossings_async(f, tIndex, carry != 0, out_dev);
 }
 NF_API_CATCH
 

@@ -242,6 +242,7 @@ struct WeightSet {  // device-resident result: one record per (target segment, c
     DevArray<int> cell;        // cell id of the record
     DevArray<double> w4;       // 4 edge weights per record (S,E,N,W), multiplicity applied
     DevArray<int> seg;         // global segment id of the record
+    DevArray<double> tab;      // (ta, tb) per record: the piece's parameters on its own target segment (the crossings)
     int nseg = 0;              // total target segments
     DevArray<int> seg_start;   // (nseg+1) CSR over records
     // host: fraction of every target segment that lies inside cells of the grid (sum of coef*(tb-ta) over its records);
@@ -442,6 +443,33 @@ struct GrossArgs {
     CellThick th;
 };
 int launch_gross_profile(const GrossArgs &a, hipStream_t s);
+
+// Crossings (nf_field_compute_crossings; DESIGN.md section 4, "Crossings"): the per-record, per-level values that the profile
+// kernels fold away, stored without any scan.  out: (planes, nz, ws.nrec) doubles, out[(p * nz + z) * nrec + k]; the kernel
+// writes levels [z0, z1) of every plane.  Volume form (t.tau == nullptr): planes q, g = the terms of the flux profile and the
+// section area |w| * (th * arc) of the slots whose velocity is present (no tracer condition).  Carried form: planes q, c, a, b =
+// the terms of the flux profile, of the tracer profile, and the two of the area profile.  th.e3u set: every slot's term takes the
+// thickness at its own face, in both forms.  Levels go crossing_chunk(dtype, carried, cell) at a time.  Measured
+// (profiles/crossings_timing.txt): float32 is fastest with 8 levels in all four forms, float64 with 8 in the plain volume form
+// only and with 4 wherever more than four gathers per level are in flight -- the gross profile's rule.  The "crossing_chunk"
+// knob picks another candidate; there is no cross-lane arithmetic, so every candidate gives the same bits).  No scratch.
+constexpr int kCrossingChunk = 8;
+constexpr int kCrossingChunkWideF64 = 4;
+inline int crossing_chunk(int dtype, bool carried, bool cell)
+{
+    return dtype == NF_F64 && (carried || cell) ? kCrossingChunkWideF64 : kCrossingChunk;
+}
+int crossing_chunk_set(int levels);   // 0 = crossing_chunk(dtype, carried, cell); 2, 4 or 8
+int crossing_chunk_now(int dtype, bool carried, bool cell);
+struct CrossingArgs {
+    StepInput in;
+    const WeightSet *ws = nullptr;
+    double *out = nullptr;
+    long nz = 0;
+    TracerIn t;                  // the carried tracer; t.tau == nullptr: volume form
+    CellThick th;
+};
+int launch_crossing_terms(const CrossingArgs &a, hipStream_t s);
 
 // Tracer transport (nf_field_compute_tracer_flux, nf_tracer.hip): K1's vertical integral with every level's velocity
 // multiplied by the tracer interpolated to the face, tf = 0.5 (a + b) - ref (DESIGN.md section 4 has the face rule).  Writes

@@ -839,6 +839,145 @@ int launch_gross_profile(const GrossArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "gross profile: the gross_chunk knob names a chunk that is not built for this dtype");
 }
 
+// ---- crossings: the per-record, per-level values of the profile kernels, stored without a scan ------------------------------
+// The planes of nf_field_compute_crossings.  A lane owns one record and up to LZ levels, as in k_area_segscan: the 4 gathers per
+// level (+ 5 in the carried form, + 4 with per-cell thicknesses, one trailing ThickIn<T>) of the whole chunk are issued before
+// the first is used.  Then, with the expressions of the profile kernels and hence their bits:
+//   q  weighted_sum of level_slots_tf<T, false>          -- the record's term of k_profile_segscan's volume row
+//   g  ((gs + ge) + gn) + gw, g_slot = |w| * (th * arc) where the slot's velocity is present (uv_present) and the slot is not
+//      row 0's south slot, else 0                          -- volume form only: area_terms without its tracer condition
+//   c  weighted_sum of level_slots_tf<T, true>           -- the record's term of the tracer profile / of P + N of the carried
+//                                                             gross profile
+//   a, b  area_terms' *area, *tsum                         -- the record's terms of k_area_segscan
+// No Sverdrup scale in g, a, b.  Nothing crosses lanes: out[(p * nz + z) * n + k], consecutive lanes store consecutive doubles,
+// every value is written once and not read again here (non-temporal).  `out` points at level z0 of plane 0.
+template <typename T>
+__device__ inline double present_area(const Record &r, const SlotTh &th, const LevelUV<T> &x, const Arcs &arc, T fill, T fill2,
+                                      bool two, bool south)
+{
+    auto term = [&](bool slot, double w, double h, T vel, double a) {
+        return slot && uv_present<T>(vel, fill, fill2, two) ? __builtin_fabs(w) * (h * a) : 0.0;
+    };
+    const double gs = term(south, r.wa.x, th.s, x.vs, arc.Ns);
+    const double ge = term(true, r.wa.y, th.e, x.uc, arc.Ec);
+    const double gn = term(true, r.wb.x, th.n, x.vc, arc.Nc);
+    const double gw = term(true, r.wb.y, th.w, x.uw, arc.Ew);
+    return ((gs + ge) + gn) + gw;
+}
+
+template <typename T, int LZ, bool CARRY, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_crossing_terms(const int *__restrict__ cell, const double *__restrict__ w4, long n,
+                                                           const T *__restrict__ u, const T *__restrict__ v, long ncell,
+                                                           unsigned nx, int z0, int nlev, const double *__restrict__ thickness,
+                                                           const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                           T fill, T fill2, int two, double scale, int sverdrup, TauIn<T> ti,
+                                                           double *__restrict__ out, long plane, TI... thick)
+{
+    constexpr bool CT = sizeof...(TI) > 0;
+    const ThickIn<T> ct = thick_arg<T>(thick...);
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const Record r = load_record(cell, w4, k);
+    const auto nb = step_neighbours<CARRY>(r.c, nx, ncell, ti.wrap_x);
+    const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+    LevelUV<T> x[LZ];
+    LevelTau<T> tt[CARRY ? LZ : 1];
+    LevelUV<T> e3[CT ? LZ : 1];
+#pragma unroll
+    for (int l = 0; l < LZ; ++l)
+        if (l < nlev) {   // nlev is launch-uniform
+            x[l] = load_level_uv(u, v, (long)(z0 + l) * ncell, r.c, nb);
+            if constexpr (CT) e3[l] = load_level_e3(ct, (long)(z0 + l) * ncell, r.c, nb);
+            if constexpr (CARRY) tt[l] = load_level_tau(ti.tau, (long)(z0 + l) * ncell, r.c, nb);
+        }
+#pragma unroll
+    for (int l = 0; l < LZ; ++l)
+        if (l < nlev) {
+            SlotTh th;
+            if constexpr (CT)
+                th = level_th(e3[l], ct);
+            else
+                th = slot_th(thickness[z0 + l]);
+            double *o = out + (long)l * n + k;
+            const double q =
+                weighted_sum(r, level_slots_tf<T, false>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, FaceTf{}));
+            __builtin_nontemporal_store(q, o);
+            if constexpr (CARRY) {
+                const double c = weighted_sum(r, level_slots_tf<T, true>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south,
+                                                                         level_tf(tt[l], nb, ti)));
+                double area, tsum;
+                area_terms<T>(r, th, x[l], arc, fill, fill2, two, tt[l], nb, ti, &area, &tsum);
+                __builtin_nontemporal_store(c, o + plane);
+                __builtin_nontemporal_store(area, o + 2 * plane);
+                __builtin_nontemporal_store(tsum, o + 3 * plane);
+            } else {
+                __builtin_nontemporal_store(present_area<T>(r, th, x[l], arc, fill, fill2, two, nb.south), o + plane);
+            }
+        }
+}
+
+// "crossing_chunk" tuning knob: the levels per chunk, one of the instantiated candidates; 0 = crossing_chunk(dtype, carried,
+// cell)
+static int g_crossing_chunk = 0;
+int crossing_chunk_set(int levels)
+{
+    if (levels != 0 && levels != 2 && levels != 4 && levels != 8) return -1;
+    g_crossing_chunk = levels;
+    return NF_OK;
+}
+int crossing_chunk_now(int dtype, bool carried, bool cell)
+{
+    return g_crossing_chunk ? g_crossing_chunk : crossing_chunk(dtype, carried, cell);
+}
+
+template <typename T, int LZ, bool CARRY, typename... TI>
+static int launch_crossing_t(const CrossingArgs &a, hipStream_t s, TI... thick)
+{
+    const WeightSet &ws = *a.ws;
+    const StepInput &in = a.in;
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    const long plane = a.nz * ws.nrec;
+    for (int zc = in.z0; zc < in.z1; zc += LZ) {
+        const int nlev = in.z1 - zc < LZ ? in.z1 - zc : LZ;
+        hipLaunchKernelGGL((k_crossing_terms<T, LZ, CARRY, TI...>), record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(),
+                           ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, zc, nlev, in.thickness, in.arcE,
+                           in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, tau_of<T>(a.t),
+                           a.out + (long)zc * ws.nrec, plane, thick...);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+// the four forms of one dtype and chunk: volume or carried, each with the scalar or the per-cell thicknesses
+template <typename T, int LZ>
+static int launch_crossing_form(const CrossingArgs &a, hipStream_t s)
+{
+    if (a.t.tau && a.th.e3u) return launch_crossing_t<T, LZ, true>(a, s, thick_in<T>(a.th));
+    if (a.t.tau) return launch_crossing_t<T, LZ, true>(a, s);
+    if (a.th.e3u) return launch_crossing_t<T, LZ, false>(a, s, thick_in<T>(a.th));
+    return launch_crossing_t<T, LZ, false>(a, s);
+}
+
+int launch_crossing_terms(const CrossingArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    const int chunk = crossing_chunk_now(in.dtype, a.t.tau != nullptr, a.th.e3u != nullptr);
+    NF_REQUIRE(a.ws && in.u && in.v && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "crossings: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "crossings: null argument");
+    NF_REQUIRE(in.ncell > 0 && in.nx > 0 && in.ncell % in.nx == 0 && in.ncell < (1l << 31), NF_ERR_ARG, "crossings: bad grid sizes");
+    NF_REQUIRE(in.z0 >= 0 && in.z1 >= in.z0 && in.z1 <= a.nz, NF_ERR_ARG, "crossings: bad arguments");
+    if (a.ws->nrec == 0) return NF_OK;
+    NF_REQUIRE(a.out, NF_ERR_ARG, "crossings: null argument");
+    NF_REQUIRE(in.dtype == NF_F64 || in.dtype == NF_F32, NF_ERR_ARG, "crossings: dtype must be NF_F64 or NF_F32");
+    if (in.dtype == NF_F64 && chunk == 2) return launch_crossing_form<double, 2>(a, s);
+    if (in.dtype == NF_F64 && chunk == 4) return launch_crossing_form<double, 4>(a, s);
+    if (in.dtype == NF_F64 && chunk == 8) return launch_crossing_form<double, 8>(a, s);
+    if (in.dtype == NF_F32 && chunk == 2) return launch_crossing_form<float, 2>(a, s);
+    if (in.dtype == NF_F32 && chunk == 4) return launch_crossing_form<float, 4>(a, s);
+    if (in.dtype == NF_F32 && chunk == 8) return launch_crossing_form<float, 8>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "crossings: the crossing_chunk knob names a chunk that is not built");
+}
+
 // ---- volume transport in tracer classes: level_slots, each term sent to the row of its face's class -------------------
 // One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are
 // level_slots' times their weights; each is added, in slot order (south, east, north, west), to the lane's accumulator of the

@@ -376,7 +376,8 @@ __global__ __launch_bounds__(kBlock) void k_expand(const unsigned long long *__r
                                                    const double *__restrict__ segs, const int *__restrict__ seg_cc, int nshift,
                                                    double periodX, unsigned long long *__restrict__ err,
                                                    int *__restrict__ cell_out, double *__restrict__ w4_out,
-                                                   int *__restrict__ seg_out, double *__restrict__ len_out)
+                                                   int *__restrict__ seg_out, double *__restrict__ len_out,
+                                                   double2 *__restrict__ tab_out)
 {
     long i = (long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= nrec) return;
@@ -416,6 +417,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(const unsigned long long *__r
     cell_out[i] = (int)c;
     seg_out[i] = (int)s;
     len_out[i] = coef * (tb - ta);   // the piece of the target segment this record accounts for
+    tab_out[i] = make_double2(ta, tb);   // where the piece lies on its own target segment (a periodic image's too)
 }
 
 // coverage of every target segment: sum of coef * (tb - ta) over its records = the fraction of the segment that lies in
@@ -752,12 +754,13 @@ int build_weights(const double *xy, long ncell, const double *segs_host, const i
     NF_TRY(out->cell.alloc((size_t)nrec));
     NF_TRY(out->w4.alloc(4 * (size_t)nrec));
     NF_TRY(out->seg.alloc((size_t)nrec));
+    NF_TRY(out->tab.alloc(2 * (size_t)nrec));
     double *d_len = nullptr, *d_cov = nullptr;
     NF_HIP(level[0].take(&d_len, (size_t)nrec));
     NF_HIP(misc.take(&d_cov, (size_t)(nseg + 1)));
     hipLaunchKernelGGL(k_expand, dim3(nb_rec), dim3(kBlock), 0, s, (const unsigned long long *)k_out, (const unsigned *)v_tie, nrec,
                        rec, xy, period, (const double *)d_segs, (const int *)d_cc, nshift, periodX, d_err, out->cell.get(), out->w4.get(),
-                       out->seg.get(), d_len);
+                       out->seg.get(), d_len, reinterpret_cast<double2 *>(out->tab.get()));
     if (nseg > 0) {
         hipLaunchKernelGGL(k_seg_coverage, dim3((unsigned)(((long)nseg * kWave + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                            (const double *)d_len, (const int *)rstart, nseg, d_cov);

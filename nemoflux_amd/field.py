@@ -83,6 +83,36 @@ def _band_sum(P, bounds_depth, ztop, zbot):
     return acc
 
 
+def _arc_length(lon0, lat0, lon1, lat1):
+    """great-circle distance on the unit sphere between points given in degrees: the units of Field.arcLengths (the angle
+    between the two position vectors, as the cell edges' lengths are formed)"""
+    d = numpy.pi / 180.
+    lo0, la0, lo1, la1 = (numpy.asarray(x, dtype=numpy.float64) * d for x in (lon0, lat0, lon1, lat1))
+    dot = numpy.cos(la0) * numpy.cos(la1) * numpy.cos(lo1 - lo0) + numpy.sin(la0) * numpy.sin(la1)
+    return numpy.fabs(numpy.arccos(numpy.clip(dot, -1., 1.)))
+
+
+class Crossings(object):
+    """The crossings of a Field's transects (Field.getCrossings), in record order: one per (target segment, crossed cell), by
+    segment and then along the segment.  Arrays of length ncross unless said otherwise:
+    segment (global id), transect, offsets (ntransect + 1: the crossings of transect p are offsets[p]:offsets[p + 1]), cell,
+    j, i, ta, tb (the piece's parameters on its own target segment), lon0, lat0, lon1, lat1 (the piece's ends: the segment's end
+    points interpolated linearly in the planar lon-lat space the weights are built in), s0, s1 (distance along the transect
+    to the piece's ends, in the units of arcLengths: the great-circle length of the earlier segments plus the fraction ta / tb
+    of this one's)."""
+    _names = ('segment', 'transect', 'offsets', 'cell', 'j', 'i', 'ta', 'tb', 'lon0', 'lat0', 'lon1', 'lat1', 's0', 's1')
+
+    def __init__(self, **kw):
+        for n in self._names:
+            setattr(self, n, kw[n])
+
+    def __len__(self):
+        return int(self.segment.size)
+
+    def asdict(self):
+        return {n: getattr(self, n) for n in self._names}
+
+
 class _TimeObj(object):
     """timeobj.TimeObj stand-in that tolerates a missing time axis."""
 
@@ -910,6 +940,127 @@ class Field(object):
             rows = numpy.zeros((2 * self.nz, self._row_width), numpy.float64)
             check(lib.nf_field_compute_gross_profile(ctypes.byref(self._h), tIndex, 1 if carry else 0, _lib.dptr(rows)))
         return self._split_rows(rows.reshape(2, self.nz, self._row_width))
+
+    def getCrossings(self):
+        """The crossings of the batched transect set: a Crossings object (see there), in the record order of getWeights() --
+        crossing k is entries 4k .. 4k + 3.  Identical duplicates (halo columns, a north-fold row) keep their separate records
+        with the same [ta, tb] and half the weight each; a crossing found through a periodic image has ta, tb in the parameter
+        of its own target segment, so its lon0 .. lon1 lie on the line as the caller gave it."""
+        n = ctypes.c_size_t()
+        check(lib.nf_field_num_crossings(ctypes.byref(self._h), ctypes.byref(n)))
+        n = n.value
+        seg, cell = numpy.zeros(n, numpy.int32), numpy.zeros(n, numpy.int64)
+        ta, tb = numpy.zeros(n, numpy.float64), numpy.zeros(n, numpy.float64)
+        if n:
+            check(lib.nf_field_get_crossings(ctypes.byref(self._h), seg.ctypes.data_as(_lib.c_int_p),
+                                             cell.ctypes.data_as(_lib.c_int64_p), _lib.dptr(ta), _lib.dptr(tb)))
+        off = numpy.asarray(self._tr_off, dtype=numpy.int64)
+        transect = numpy.searchsorted(off, seg, side='right') - 1
+        # per global segment: its end points and the distance along its transect at which it begins
+        p0 = numpy.concatenate([p[:-1, :2] for p in self._polylines] + [numpy.zeros((0, 2))])
+        p1 = numpy.concatenate([p[1:, :2] for p in self._polylines] + [numpy.zeros((0, 2))])
+        length = _arc_length(p0[:, 0], p0[:, 1], p1[:, 0], p1[:, 1])
+        start = numpy.zeros(self._nseg, numpy.float64)
+        for q in range(len(self.plis)):
+            a, b = off[q], off[q + 1]
+            start[a:b] = numpy.concatenate([[0.], numpy.cumsum(length[a:b])[:-1]]) if b > a else []
+        d = p1[seg] - p0[seg]
+        return Crossings(segment=seg, transect=transect.astype(numpy.int32), offsets=numpy.searchsorted(seg, off, side='left'),
+                         cell=cell, j=cell // self.nx, i=cell % self.nx, ta=ta, tb=tb,
+                         lon0=p0[seg, 0] + ta * d[:, 0], lat0=p0[seg, 1] + ta * d[:, 1],
+                         lon1=p0[seg, 0] + tb * d[:, 0], lat1=p0[seg, 1] + tb * d[:, 1],
+                         s0=start[seg] + ta * length[seg], s1=start[seg] + tb * length[seg])
+
+    def computeCrossings(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """The integrand of every other product, for time step tIndex: per level and crossing (getCrossings: the piece of one
+        target segment inside one grid cell) what flows through the piece, its section area and the tracer on it.  Returns
+        (2, nz, ncross) = q, g, or with carry=True (setTracer first) (4, nz, ncross) = q, c, a, b:
+            q  the volume transport through the piece: the crossing's terms of computeFluxProfile (Sverdrup scale when on)
+            g  its section area |w| * th * arc over the faces whose velocity is present -- no tracer condition, no scale
+            c  the tracer transport through the piece: its terms of computeTracerProfile (of P + N of
+               computeGrossProfile(carry=True) with a cell thickness)
+            a, b  its terms of computeAreaProfile: the area of the faces that count and that area times (tracer - reference)
+        Both forms take a cell thickness (setCellThickness).  The sum of a plane over a segment's crossings is that segment's
+        column of the product named, up to rounding (bit for bit where the segment has one crossing).  Nothing is reduced, so
+        the planes of sharded ranks add up exactly; levels this rank does not own (slab_range) are zeros.  Leaves the resident
+        edge fluxes, the running max, the row of the last computeFlux and the tracer rows as they are.  `out`: optional
+        contiguous float64 torch CUDA tensor of the result's shape that receives the planes in HBM."""
+        tIndex = int(tIndex)
+        if carry not in (False, True, 0, 1):
+            raise RuntimeError(f'ERROR: carry must be False or True, got {carry!r}')
+        self._stage(tIndex, prefetch_next)
+        if carry:
+            self._stage_tracer(tIndex)
+        n = ctypes.c_size_t()
+        check(lib.nf_field_num_crossings(ctypes.byref(self._h), ctypes.byref(n)))
+        shape = (4 if carry else 2, self.nz, n.value)
+        if out is not None:
+            import torch
+            if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
+                raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
+            if n.value:
+                check(lib.nf_field_compute_crossings_async(ctypes.byref(self._h), tIndex, 1 if carry else 0,
+                                                           ctypes.c_void_p(out.data_ptr())))
+            return out.cpu().numpy()
+        planes = numpy.zeros(shape, numpy.float64)
+        if n.value:
+            check(lib.nf_field_compute_crossings(ctypes.byref(self._h), tIndex, 1 if carry else 0, _lib.dptr(planes)))
+        return planes
+
+    @staticmethod
+    def _crossing_area(parts):
+        P = numpy.asarray(parts, dtype=numpy.float64)
+        if P.ndim != 3 or P.shape[0] not in (2, 4):
+            raise ValueError(f'the planes of computeCrossings have shape (2 or 4, nz, ncross), got {P.shape}')
+        return P, P[1] if P.shape[0] == 2 else P[2]
+
+    @staticmethod
+    def crossingVelocity(parts):
+        """Mean normal velocity through every piece and level: q / g of the volume form, q / a of the carried form (the area of
+        the faces that also have a tracer value), (nz, ncross); NaN where the area is 0.  In the units of uo / vo without the Sverdrup scale;
+        with it q carries the factor 6.371 (Earth radius / 1e6) and the areas never do, so the ratio is 6.371 times the
+        velocity: divide by 6.371 for m/s."""
+        P, area = Field._crossing_area(parts)
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(area != 0.0, P[0] / area, numpy.nan)
+
+    @staticmethod
+    def crossingTracer(parts, reference=0.0):
+        """Mean tracer on every piece and level, from the carried form's planes: reference + b / a, (nz, ncross); NaN where
+        a == 0.  `reference`: the reference of setTracer, which b has subtracted."""
+        P = numpy.asarray(parts, dtype=numpy.float64)
+        if P.ndim != 3 or P.shape[0] != 4:
+            raise ValueError(f'crossingTracer needs the planes of computeCrossings(carry=True), (4, nz, ncross), got {P.shape}')
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(P[2] != 0.0, float(reference) + P[3] / P[2], numpy.nan)
+
+    @staticmethod
+    def cumulativeTransport(parts, crossings, ztop=None, zbot=None, bounds_depth=None):
+        """Cumulative volume transport along every transect, (ncross,): per transect the running sum, in record order, of q
+        summed over depth -- or over the depth band [ztop, zbot] as in depthBandFlux (bounds_depth (nz, 2) is then needed).
+        The last value of a transect is its computeFlux up to rounding.  parts: the planes of either form of
+        computeCrossings; crossings: getCrossings()."""
+        P, _ = Field._crossing_area(parts)
+        q = P[0]
+        if q.shape[1] != len(crossings):
+            raise ValueError(f'cumulativeTransport: {q.shape[1]} columns for {len(crossings)} crossings')
+        if ztop is None and zbot is None:
+            col = q.sum(axis=0)
+        else:
+            if ztop is None or zbot is None or bounds_depth is None:
+                raise ValueError('cumulativeTransport: a depth band needs ztop, zbot and bounds_depth')
+            ztop, zbot = float(ztop), float(zbot)
+            if not ztop <= zbot:
+                raise ValueError(f'cumulativeTransport: need ztop <= zbot, got {ztop}, {zbot}')
+            if numpy.shape(bounds_depth) != (q.shape[0], 2):
+                raise ValueError(f'cumulativeTransport: bounds_depth must have shape {(q.shape[0], 2)}, got '
+                                 f'{numpy.shape(bounds_depth)}')
+            col = _band_sum(q, bounds_depth, ztop, zbot)
+        out = numpy.zeros(col.shape, numpy.float64)
+        off = numpy.asarray(crossings.offsets)
+        for p in range(off.size - 1):
+            out[off[p]:off[p + 1]] = numpy.cumsum(col[off[p]:off[p + 1]])
+        return out
 
     @staticmethod
     def grossTransport(parts, ztop=None, zbot=None, bounds_depth=None):

@@ -320,6 +320,50 @@ def checkClassAreaArgs(classArea='', tracer='', tracerRef=0.0, tracerScale=1.0, 
         raise RuntimeError(str(e).replace('--classes', '--class-area'))
 
 
+CROSSINGS_MAX_BYTES = 2 << 30
+
+
+def crossingsSeries(tFile, uFile, vFile, lonLatZPoints, path, tracer='', tracerFile='', tracerRef=0.0, zrange=None,
+                    sverdrup=False, cellThickness=None, sigma=None):
+    """--crossings FILE.npz: for every time step the planes of Field.computeCrossings -- (nt, 2, nz, ncross) = q, g, or with a
+    tracer (a variable, or sigma = (theta, salt, pref)) (nt, 4, nz, ncross) = q, c, a, b -- the cumulative transport along
+    every transect (nt, ncross), over the depth or the band zrange = (ztop, zbot), and the arrays of Field.getCrossings(),
+    written to `path` with numpy.savez.  Returns (planes, cumulative, Field).  Refused when the planes would exceed 2 GiB: the
+    file is for sections, not for batches of basin-wide transects."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    carried = bool(tracer) or sigma is not None
+    if carried:
+        fld.setTracer(_classField(tFile, tracer, tracerFile, sigma), reference=tracerRef)
+    cr = fld.getCrossings()
+    nplanes = 4 if carried else 2
+    nbytes = 8 * fld.nt * nplanes * fld.nz * len(cr)
+    if nbytes > CROSSINGS_MAX_BYTES:
+        raise RuntimeError(f'ERROR: --crossings would write {nbytes / 2.**30:.1f} GiB ({fld.nt} steps x {nplanes} planes x {fld.nz} '
+                           f'levels x {len(cr)} crossings x 8 bytes), more than 2 GiB: it is meant for sections -- give fewer or '
+                           f'shorter transects')
+    planes = numpy.zeros((fld.nt, nplanes, fld.nz, len(cr)))
+    cumulative = numpy.zeros((fld.nt, len(cr)))
+    band = dict(ztop=zrange[0], zbot=zrange[1], bounds_depth=fld.bounds_depth) if zrange else {}
+    for t in range(fld.nt):
+        planes[t] = fld.computeCrossings(t, carry=carried, prefetch_next=True)
+        cumulative[t] = fld.cumulativeTransport(planes[t], cr, **band)
+    numpy.savez(path, planes=planes, plane_names=numpy.array(['q', 'c', 'a', 'b'] if carried else ['q', 'g']),
+                cumulative=cumulative, bounds_depth=numpy.asarray(fld.bounds_depth), reference=float(tracerRef),
+                sverdrup=bool(sverdrup), **cr.asdict())
+    return planes, cumulative, fld
+
+
+def checkCrossingsArgs(crossings='', **others):
+    """the --crossings option of the command line: it writes its own file and combines with --tracer / --sigma, --tracer-ref,
+    --zrange, --cell-thickness and -s alone; refused combinations raise RuntimeError"""
+    if not crossings:
+        return
+    for opt, on in others.items():
+        if on:
+            raise RuntimeError(f'ERROR: --crossings and {opt} cannot be combined: --crossings writes the per-crossing planes of '
+                               f'every time step to its own file')
+
+
 def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
     """the --gross option of the command line: refused combinations raise RuntimeError"""
     if not gross:
@@ -502,8 +546,22 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
-         classArea=''):
+         classArea='', crossings=''):
     sig = None
+    if crossings:
+        checkCrossingsArgs(crossings, **{'--classes': classes, '--classes2': classes2, '--gross-classes': grossClasses,
+                                         '--class-area': classArea, '--gross': gross, '--levels': levels, '--decompose': decompose,
+                                         '--eddy': eddy, '--show': show, '--carry': carry, '--tracer2': tracer2,
+                                         '--thickness-weighted': thicknessWeighted,
+                                         '--tracer together with --sigma': bool(tracer and sigma),
+                                         '--tracer-scale': float(tracerScale) != 1.0})
+        checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
+        lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
+        ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+        planes, _, _ = crossingsSeries(tFile, uFile, vFile, lonLatZPoints, crossings, tracer, tracerFile, float(tracerRef),
+                                       parseZRange(zrange) if zrange else None, sverdrup, ct, parseSigma(sigma) if sigma else None)
+        print(f'crossings: planes of shape {planes.shape} written to {crossings}')
+        return planes
     if sigma:
         # the class field computed from two variables: in the tables it goes by the name sigmaName gives it
         if tracer:
@@ -745,6 +803,11 @@ if __name__ == '__main__':
                          'area-weighted mean of the class field in it -- with --carry NAME of NAME (--carry-ref applies) -- and '
                          'the pseudo-depth of the upper edge of the class, the depth axis of an overturning streamfunction in '
                          'class space (--cell-thickness applies; -s does not: an area has no Sverdrup scale)')
+    ap.add_argument('--crossings', default='', metavar='FILE.npz',
+                    help='write the per-crossing planes of every time step to FILE.npz: what flows through the piece of the line '
+                         'inside each grid cell at each level (q) and its section area (g); with --tracer NAME or --sigma the '
+                         'carried form (q, c, a, b).  Also the position of every crossing along the line and the cumulative '
+                         'transport (--zrange: of that band).  With --cell-thickness, -s, --tracer-ref.  Refused above 2 GiB')
     ap.add_argument('--eddy', action='store_true',
                     help='with --tracer NAME: one CSV line per part (part,...): the mean over all time steps of the transport of '
                          'NAME, the transport of the time-mean NAME by the time-mean flow, and the eddy part, their difference '
