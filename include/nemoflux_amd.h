@@ -476,6 +476,27 @@ int nf_field_set_class_tracer_missing_value(nf_field **self, double missing_valu
  * resident planes, |.| arrays, running max, last row, tracer planes or a captured pass. */
 int nf_field_compute_class_tracer_transport(nf_field **self, long tIndex, double *rows_host);        /* (nedges+2, row_length) */
 int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, double *rows_dev);   /* HBM, field's stream */
+/* Conservative (piecewise-linear) remapping of the class transport: the rows of nf_field_compute_class_transport (carry = 0)
+ * or nf_field_compute_class_tracer_transport (carry = 1) with every term t = w * d -- the same term, of one weight slot of one
+ * record at one level z -- spread over the classes instead of going whole to the row of its face.  The class field is taken
+ * to vary linearly between the layer's interfaces: with f_z the class value of the slot's face at level z (as above),
+ *   g_up = 0.5 (f_{z-1} + f_z) when z > 0 and the same face has a class value at level z - 1, else f_z;
+ *   g_dn = 0.5 (f_{z+1} + f_z) when z < nz - 1 and it has one at level z + 1, else f_z;
+ *   lo = min(g_up, g_dn), hi = max(g_up, g_dn); for every row j from row(lo) to row(hi):
+ *   left = lo in row(lo), else e[j-1]; right = hi in row(hi), else e[j]; the row gets t * ((right - left) / (hi - lo)),
+ *   nothing where right == left.
+ * lo == hi: whole to row(lo).  g_up, g_dn or g_dn - g_up not finite: whole to row(f_z), the step rule.  No class value at level
+ * z (or NaN): whole to row n + 1.  The fractions of a term add up to 1 up to rounding, so the rows add up to the rows of the
+ * step rule; a class field that is constant in z gives those rows bit for bit.  Per lane the additions run level-ascending,
+ * then in slot order, then row-ascending; windows and reduction as in the step forms: no atomics, bitwise reproducible,
+ * independent of the window.  Levels z - 1 and z + 1 are levels of the array, not of the owned range: under a slab range the
+ * first and the last owned level read one level this rank does not own, and a host-resident class field is staged with that
+ * one level more on each side (an HBM one is read in place), so sharded ranks' rows add up to the unsharded ones up to
+ * rounding.  Class edges, tracer slots, window knob, scratch, state checks and refusals (NF_ERR_STATE before set_tracer or
+ * set_class_edges and while a cell thickness is set) are those of nf_field_compute_class_tracer_transport; carry other than
+ * 0 or 1: NF_ERR_ARG.  Changes nothing else. */
+int nf_field_compute_class_remap(nf_field **self, long tIndex, int carry, double *rows_host);        /* (nedges+2, row_length) */
+int nf_field_compute_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev);   /* HBM, field's stream */
 /* Per-cell layer thicknesses (partial steps, z* / variable-volume runs): the model's e3u / e3v, or thkcello on the U and V
  * grids, in place of the one number per level of nf_field_set_thickness.  e3u sits on the index of uo (the east face of cell
  * (j, i)), e3v on the index of vo: no interpolation, no neighbour.  Definition, with th_z read at the face:
@@ -496,8 +517,8 @@ int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, 
  * static one is uploaded once, at the call (set_bounds first).  e3u == NULL goes back to the per-level thickness and forgets
  * the markers.  Setting or clearing invalidates a captured pass; the all-steps-in-one-launch form of small grids is not used
  * while one is set.  Refused while one is set (NF_ERR_STATE, the message saying how to clear it): the forms that do not take
- * per-cell thicknesses yet -- nf_field_compute_tracer_profile*, nf_field_compute_class_transport* and
- * nf_field_compute_class_tracer_transport*.
+ * per-cell thicknesses yet -- nf_field_compute_tracer_profile*, nf_field_compute_class_transport*,
+ * nf_field_compute_class_tracer_transport* and nf_field_compute_class_remap*.
  * A static host array that the handle uploaded belongs to the (nz, ny, nx) in force at that call.  After an
  * nf_field_set_bounds or nf_field_set_thickness that changes that shape (the shapes are compared, not the byte counts; a
  * call that leaves the shape as it was keeps the upload valid) every compute that would read the thickness returns

@@ -764,6 +764,35 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool ca
     return launch_class_transport(a, f->stream);
 }
 
+// The class transport of step t by conservative remapping (nf_field_compute_class_remap): field_class_step_async with
+// launch_class_remap.  Its kernel reads the class field one level above and one below the owned ones, so a host-resident class
+// field is staged with that halo level on each side (an HBM one is read in place).
+static int field_class_remap_step_async(nf_field *f, long t, double *rows_dev, bool carry)
+{
+    const int nedges = (int)f->class_edges.host.size();
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_class_remap", t, 2, rows_dev, (size_t)nedges + 2, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
+    const int window = g_class_window;
+    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
+    const Levels halo{std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)};
+    ClassArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : halo, &a.cls));
+    if (carry) a.carry = a.cls;                                                    // the tracer is carried ...
+    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, halo, &a.cls));   // ... and binned by the class tracer
+    a.edges = f->class_edges.dev.get();
+    a.nedges = nedges;
+    a.window = window;
+    a.tr = field_transects(f);
+    a.scratch = f->class_scratch.get();
+    a.scratch_len = f->class_scratch.size();
+    a.rows = rows_dev;
+    a.remap_nz = (int)f->nz;
+    return launch_class_remap(a, f->stream);
+}
+
 // the calls of the joint class transport need both tracers and the joint edges: checked before a device is needed
 static int field_joint_ready(const nf_field *f, const char *what)
 {
@@ -1594,6 +1623,32 @@ try {
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport_async"));
     NF_NEED_DEVICE();
     return field_class_step_async(f, tIndex, rows_dev);
+}
+NF_API_CATCH
+
+int nf_field_compute_class_remap(nf_field **self, long tIndex, int carry, double *rows_host)
+try {
+    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_remap: null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_class_remap: carry must be 0 or 1");
+    nf_field *f = *self;
+    NF_TRY(field_class_ready(f, "nf_field_compute_class_remap"));
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_remap"));
+    NF_NEED_DEVICE();
+    const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_remap_step_async(f, tIndex, rows, carry != 0); });
+}
+NF_API_CATCH
+
+int nf_field_compute_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev)
+try {
+    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_remap_async: null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_class_remap_async: carry must be 0 or 1");
+    nf_field *f = *self;
+    NF_TRY(field_class_ready(f, "nf_field_compute_class_remap_async"));
+    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_remap_async"));
+    NF_NEED_DEVICE();
+    return field_class_remap_step_async(f, tIndex, rows_dev, carry != 0);
 }
 NF_API_CATCH
 

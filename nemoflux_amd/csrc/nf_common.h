@@ -550,8 +550,13 @@ struct ClassArgs {
     // at its own face.  carry.tau == nullptr: volume transport.  The carried tracer may be the class field itself (the same
     // array with the same markers: one set of gathers) or another array; its wrap_x is not read.
     TracerIn carry;
+    // launch_class_remap only: the levels of the arrays -- the class field's levels z0 - 1 and z1 are read where the array has them
+    int remap_nz = 0;
 };
 int launch_class_transport(const ClassArgs &a, hipStream_t s);
+// Conservative remapping of the class transport (nf_field_compute_class_remap, nf_integral.hip): the same rows from the same
+// terms, each spread over the classes between the class field's values at the layer's two interfaces (k_class_remap_segscan)
+int launch_class_remap(const ClassArgs &a, hipStream_t s);
 
 // Transport in JOINT classes of two tracers (nf_field_compute_joint_class_transport, nf_integral.hip): axis A is the tracer
 // (edges ea, na), axis B the class tracer (edges eb, nb); joint row ra * (nb + 2) + rb, ra / rb the 1-D rows of the face's

@@ -1090,6 +1090,121 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
     }
 }
 
+// ---- conservative (piecewise-linear) remapping of the class transport -----------------------------------------------------
+// k_class_segscan with another rule for the row: the class field is taken to vary linearly between the interfaces of a layer,
+// and a term is spread uniformly in class space over the interval between its face's two interface values
+//   g_up = 0.5 (f[z-1] + f[z]) where z > 0 and the face has a value at level z - 1, else f[z];  g_dn likewise with z + 1 < nz;
+// row j gets the share of [lo, hi] = [min, max](g_up, g_dn) that lies in it,  t * ((right - left) / (hi - lo)).  Whole to
+// class_row(f[z]) (the step rule) where g_up, g_dn or their difference is not finite, whole to class_row(lo) where lo == hi,
+// whole to row nedges + 1 without a class value.  Per lane the adds run level-ascending, then in slot order, then
+// row-ascending; a term's row loop is clipped to the window first.  Levels z - 1 and z + 1 are levels of the ARRAY (nz of them),
+// not of the owned range: the first and the last owned level read one halo level each.
+// The class field's five gathers are issued once per level: c[] is a rolling window of levels z - 1 .. z + RL whose first two
+// members come from the batch before.  LDS, scan and stores: k_class_segscan's.
+constexpr int kRemapLevels = 4;        // levels whose 9 gathers are issued together (volume form, one-tracer carry form)
+constexpr int kRemapLevelsTwo = 2;     // ... whose 14 gathers are (carry form with a class field of its own)
+
+template <typename T, bool TWO, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                                const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                                const T *__restrict__ v, const T *__restrict__ tau, long ncell,
+                                                                unsigned nx, int z0, int z1,
+                                                                const double *__restrict__ thickness,
+                                                                const double *__restrict__ arcE,
+                                                                const double *__restrict__ arcN, T fill, T fill2, int two,
+                                                                T tfill, T tfill2, int wrap_x, double scale, int sverdrup,
+                                                                const double *__restrict__ edges, int nedges, int top, int r0,
+                                                                int nwin, double *__restrict__ runsum, int nz, TI... tracer)
+{
+    constexpr bool CARRY = sizeof...(TI) > 0;
+    constexpr int RL = TWO ? kRemapLevelsTwo : kRemapLevels;
+    const TauIn<T> ti = tau_in<T>(tracer...);
+    extern __shared__ double class_lds[];
+    double *e = class_lds;
+    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
+    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
+    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
+    __syncthreads();   // the edges; every lane touches only its own accumulators
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    int key = -1;
+    if (k < n) {   // z0 < z1 <= nz: the launcher's
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        const int rend = r0 + nwin - 1;
+        auto add = [&](int row, double x) {
+            const int q = row - r0;
+            if (q >= 0 && q < nwin) acc[q * kBlock] += x;
+        };
+        // the term t of the face (a, b) at a level whose class values are (a1, b1), with (a0, b0) above and (a2, b2) below
+        auto spread = [&](T a0, T b0, T a1, T b1, T a2, T b2, bool has_b, bool up, bool dn, double t) {
+            double f, fu = 0.0, fd = 0.0;
+            const bool h = tr_face_raw<T>(a1, b1, has_b, tfill, tfill2, &f);
+            if (!h || f != f) return add(nedges + 1, t);
+            const bool hu = up && tr_face_raw<T>(a0, b0, has_b, tfill, tfill2, &fu);
+            const bool hd = dn && tr_face_raw<T>(a2, b2, has_b, tfill, tfill2, &fd);
+            const double gu = hu ? 0.5 * (fu + f) : f, gd = hd ? 0.5 * (fd + f) : f;
+            if (!(__builtin_isfinite(gu) && __builtin_isfinite(gd) && __builtin_isfinite(gd - gu)))
+                return add(class_row(true, f, e, nedges, top), t);
+            const double lo = gu < gd ? gu : gd, hi = gu < gd ? gd : gu;
+            const int jlo = class_row(true, lo, e, nedges, top);
+            if (lo == hi) return add(jlo, t);
+            const int jhi = class_row(true, hi, e, nedges, top);
+            const double width = hi - lo;
+            const int ja = jlo > r0 ? jlo : r0, jb = jhi < rend ? jhi : rend;
+            for (int j = ja; j <= jb; ++j) {
+                const double left = j == jlo ? lo : e[j - 1], right = j == jhi ? hi : e[j];
+                if (right != left) acc[(j - r0) * kBlock] += t * ((right - left) / width);
+            }
+        };
+        LevelTau<T> c[RL + 2];   // the class field of levels z - 1 .. z + RL
+        c[1] = load_level_tau(tau, (long)z0 * ncell, r.c, nb);
+        c[0] = z0 > 0 ? load_level_tau(tau, (long)(z0 - 1) * ncell, r.c, nb) : c[1];
+        for (int z = z0; z < z1; z += RL) {
+            const int nlev = z1 - z < RL ? z1 - z : RL;
+            LevelUV<T> x[RL];
+            LevelTau<T> tt[TWO ? RL : 1];               // the carried tracer, when it is another array
+#pragma unroll
+            for (int l = 0; l < RL; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    c[l + 2] = z + l + 1 < nz ? load_level_tau(tau, o + ncell, r.c, nb) : c[l + 1];
+                    if constexpr (TWO) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < RL; ++l)
+                if (l < nlev) {
+                    const LevelTau<T> &p = c[l], &m = c[l + 1], &q = c[l + 2];
+                    const bool up = z + l > 0, dn = z + l + 1 < nz;
+                    FaceTf tf{};
+                    if constexpr (CARRY) tf = level_tf(TWO ? tt[l] : m, nb, ti);
+                    const Slots d = level_slots_tf<T, CARRY>(slot_th(thickness[z + l]), x[l], arc, fill, fill2, two, scale, sverdrup,
+                                                             nb.south, tf);
+                    if (nb.south) spread(p.s, p.c, m.s, m.c, q.s, q.c, true, up, dn, r.wa.x * d.s);
+                    spread(p.c, p.e, m.c, m.e, q.c, q.e, nb.has_e, up, dn, r.wa.y * d.e);
+                    spread(p.c, p.n, m.c, m.n, q.c, q.n, nb.has_n, up, dn, r.wb.x * d.n);
+                    spread(p.w, p.c, m.w, m.c, q.w, q.c, nb.has_w, up, dn, r.wb.y * d.w);
+                }
+            c[0] = c[RL];
+            c[1] = c[RL + 1];
+        }
+    }
+    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
+#pragma unroll
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
+        if (seg_scan_take(key, lane, o)) take |= 1u << b;
+    const bool store = seg_run_end(key, lane, k, n);
+    for (int r = 0; r < nwin; ++r) {
+        double val[1] = {k < n ? acc[r * kBlock] : 0.0};
+#pragma unroll
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
+        if (store) runsum[(long)r * n + k] = val[0];
+    }
+}
+
 
 // same bits of two doubles (NaN included): the markers of two tracer slots agree
 static bool same_bits(double a, double b) { return __builtin_memcmp(&a, &b, sizeof a) == 0; }
@@ -1158,6 +1273,69 @@ int launch_class_transport(const ClassArgs &a, hipStream_t s)
     if (in.dtype == NF_F64) return launch_class_form<double>(a, s);
     if (in.dtype == NF_F32) return launch_class_form<float>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "class transport: dtype must be NF_F64 or NF_F32");
+}
+
+// the launchers of k_class_remap_segscan: launch_class_t's loop over the windows and launch_class_form's choice of the form
+template <typename T, int FORM>
+static int launch_class_remap_t(const ClassArgs &a, hipStream_t s)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    int top = 1;
+    while (2 * top <= a.nedges) top *= 2;
+    const int nrows = a.nedges + 2;
+    for (int r0 = 0; r0 < nrows; r0 += a.window) {
+        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
+        const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
+        // the kernel of the form with its trailing arguments: the array's levels, then the carried tracer (FORM > 0)
+        auto launch = [&](auto kernel, auto... tail) {
+            if (lds > 65536)
+                NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds));
+            hipLaunchKernelGGL(kernel, record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec,
+                               (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), (T)a.cls.fill,
+                               (T)a.cls.fill2, a.cls.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.edges, a.nedges, top, r0, nwin,
+                               a.scratch, a.remap_nz, tail...);
+            return (int)NF_OK;
+        };
+        if (ws.nrec > 0) {
+            if constexpr (FORM == 0)
+                NF_TRY(launch(&k_class_remap_segscan<T, false>));
+            else
+                NF_TRY(launch(&k_class_remap_segscan<T, FORM == 2, TauIn<T>>,
+                              TauIn<T>{(const T *)a.carry.tau, (T)a.carry.fill, (T)a.carry.fill2, a.carry.ref, a.cls.wrap_x ? 1 : 0}));
+        }
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
+                        (unsigned)nwin, s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+template <typename T>
+static int launch_class_remap_form(const ClassArgs &a, hipStream_t s)
+{
+    if (!a.carry.tau) return launch_class_remap_t<T, 0>(a, s);
+    const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
+    return one ? launch_class_remap_t<T, 1>(a, s) : launch_class_remap_t<T, 2>(a, s);
+}
+
+// a.remap_nz: the levels of the arrays; the checks are launch_class_transport's
+int launch_class_remap(const ClassArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "class remap: bad class edges");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "class remap: bad window");
+    NF_TRY(check_raw_step("class remap", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.cls.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "class remap: null argument");
+    NF_REQUIRE(in.z0 < in.z1 && in.z1 <= a.remap_nz, NF_ERR_ARG, "class remap: bad levels");
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (in.dtype == NF_F64) return launch_class_remap_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_class_remap_form<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "class remap: dtype must be NF_F64 or NF_F32");
 }
 
 // ---- transport in joint classes of two tracers: gather once (k_joint_terms), bin many times (k_joint_bin) -------------

@@ -1379,6 +1379,36 @@ class Field(object):
             check(lib.nf_field_compute_class_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
         return self._split_rows(rows)
 
+    def computeClassRemap(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Class transport of time step tIndex by conservative (piecewise-linear) remapping (setTracer and setClassEdges
+        first): (nedges+2, ntransect) totals and (nedges+2, nseg) per-segment sums, rows, class field and terms as in
+        computeClassTransport (carry=False) or computeClassTracerTransport (carry=True).  Instead of going whole to the class
+        of its face, a level's term is spread uniformly in class space over the interval between the class field's values
+        at the layer's upper and lower interface -- the mean of the face's values at this level and at the level above /
+        below, the level's own value where there is no such level or the face has no value there -- and every class gets the
+        share of the interval that lies in it: xgcm's transform(method='conservative').  With many class edges and few levels
+        the rows are then a smooth function of the class instead of a comb.  The rows add up to those of the step rule; a
+        layer that lies inside one class goes to it whole; a face without a class value goes to row nedges+1; a non-finite
+        interface value falls back to the step rule for that term.  Levels this rank does not own (slab_range) contribute
+        nothing, but the class field is read one level beyond them.  The rows go into classStreamfunction and timeMean
+        Fields as those of the step forms do.  Raises while a cell thickness is set.  Leaves everything else as it is.
+        `out`: as in computeClassTransport."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_class_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setClassEdges first')
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        carry = 1 if carry else 0
+        if out is not None:
+            out = self._rows_out(out, edges.size + 2)
+            check(lib.nf_field_compute_class_remap_async(ctypes.byref(self._h), tIndex, carry, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_class_remap(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        return self._split_rows(rows)
+
     def computeGrossClassTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
         """Gross transports of time step tIndex in tracer classes (setTracer and setClassEdges first): (totals, segments) of
         shape (2, nedges+2, ntransect) and (2, nedges+2, nseg), part 0 = P, the inflow of every class (what goes through the

@@ -15,6 +15,9 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --tracer sigma0 --tracer-file S.nc --classes 26,27,28 --carry thetao --carry-scale 4.1e-3   (heat by sigma0 class)
     ... --sigma thetao,so[,PREF] --classes 26,27,28   (the same by sigma_PREF computed from thetao and so on the GPU: EOS-80,
                                   PREF in dbar, default 0; in place of --tracer for --classes, --gross-classes, --carry, --classes2)
+    ... --sigma thetao,so --classes 26,26.01,...,28 --remap linear [--carry thetao]
+                                  (conservative remapping: every level's transport spread over the classes between the class
+                                  field's values at the layer's two interfaces -- a smooth MOC(sigma) with many class edges)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
@@ -146,6 +149,21 @@ def carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracer
     fld.setClassTracer(_classField(tFile, tracer, tracerFile, sigma))
     fld.setClassEdges(edges)
     totals = numpy.array([fld.computeClassTracerTransport(t, prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
+
+
+def remapSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry='', tracerFile='', carryFile='', carryRef=0.0,
+                sverdrup=False, sigma=None):
+    """(nt, nedges+2, ntransect) rows of classSeries -- or, with `carry`, of carrySeries -- by conservative remapping, one
+    Field.computeClassRemap per time step, and the Field."""
+    fld = Field(tFile, uFile, vFile, lonLatZPoints, sverdrup, readback=False, compact=True)
+    if carry:
+        fld.setTracer((carryFile or tFile, carry), reference=carryRef)
+        fld.setClassTracer(_classField(tFile, tracer, tracerFile, sigma))
+    else:
+        fld.setTracer(_classField(tFile, tracer, tracerFile, sigma))
+    fld.setClassEdges(edges)
+    totals = numpy.array([fld.computeClassRemap(t, carry=bool(carry), prefetch_next=True)[0] for t in range(fld.nt)])
     return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
 
 
@@ -434,6 +452,21 @@ def checkClassArgs(classes='', tracer='', tracerRef=0.0, tracerScale=1.0, zrange
     parseClasses(classes)
 
 
+def checkRemapArgs(remap='', classes='', tracer='', classes2='', levels=False, decompose=False, eddy=False):
+    """the --remap option of the command line (conservative remapping of the class transport of --classes, with or without
+    --carry): refused combinations raise RuntimeError"""
+    if not remap:
+        return
+    if remap != 'linear':
+        raise RuntimeError(f"ERROR: --remap must be 'linear' (piecewise-linear conservative remapping), got {remap!r}")
+    if not (classes and tracer):
+        raise RuntimeError('ERROR: --remap needs --classes E0,...,EN and --tracer NAME or --sigma THETA,SALT[,PREF] (the class '
+                           'field): it spreads the class transport of --classes, or of --classes --carry NAME')
+    for on, opt in ((classes2, '--classes2'), (levels, '--levels'), (decompose, '--decompose'), (eddy, '--eddy')):
+        if on:
+            raise RuntimeError(f'ERROR: --remap and {opt} cannot be combined: --remap applies to the table of --classes')
+
+
 def checkJointClassArgs(classes2='', tracer2='', tracer2File='', tracer='', classes='', carry='', levels=False, zrange='',
                         show=False, eddy=False, decompose=False):
     """the --tracer2 / --classes2 options of the command line (the water flow in joint classes of two tracers): refused
@@ -546,7 +579,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
-         classArea='', crossings=''):
+         classArea='', crossings='', remap=''):
     sig = None
     if crossings:
         checkCrossingsArgs(crossings, **{'--classes': classes, '--classes2': classes2, '--gross-classes': grossClasses,
@@ -554,7 +587,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
                                          '--eddy': eddy, '--show': show, '--carry': carry, '--tracer2': tracer2,
                                          '--thickness-weighted': thicknessWeighted,
                                          '--tracer together with --sigma': bool(tracer and sigma),
-                                         '--tracer-scale': float(tracerScale) != 1.0})
+                                         '--tracer-scale': float(tracerScale) != 1.0, '--remap': remap})
         checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
         ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
@@ -576,6 +609,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
                         show)
     checkClassAreaArgs(classArea, tracer, tracerRef, tracerScale, carryScale, classes, classes2, gross, grossClasses, levels,
                        zrange, decompose, eddy, show)
+    checkRemapArgs(remap, classes, tracer, classes2, levels, decompose, eddy)
     checkThicknessWeightedArgs(thicknessWeighted, eddy, cellThickness)
     checkGrossArgs(gross, classes, levels, decompose, eddy, show)
     checkJointClassArgs(classes2, tracer2, tracer2File, tracer, classes, carry, levels, zrange, show, eddy, decompose)
@@ -687,15 +721,21 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         return totals
     if classes:
         edges = parseClasses(classes)
-        if carry:
+        if remap:
+            totals, fld = remapSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracerFile, carryFile,
+                                      float(carryRef), sverdrup, sig)
+        elif carry:
             totals, fld = carrySeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, carry, tracerFile, carryFile,
                                       float(carryRef), sverdrup, sig)
-            totals = totals * float(carryScale)
-            title = (f'# transport of {carry} by {tracer} class [{carry} x {unit}' +
-                     (f' x {float(carryScale):g}' if float(carryScale) != 1.0 else '') + ']\n')
         else:
             totals, fld = classSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, sverdrup, sig)
-            title = f'# water flow by {tracer} class [{unit}]\n'
+        if carry:
+            totals = totals * float(carryScale)
+            title = (f'# transport of {carry} by {tracer} class [{carry} x {unit}' +
+                     (f' x {float(carryScale):g}' if float(carryScale) != 1.0 else '') + ']')
+        else:
+            title = f'# water flow by {tracer} class [{unit}]'
+        title += ', conservative remapping\n' if remap else '\n'
         timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
         bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
         lines = ['time,lower,upper,' + ','.join(names)]
@@ -767,6 +807,10 @@ if __name__ == '__main__':
     ap.add_argument('--classes', default='', metavar='E0,E1,...,EN',
                     help='water flow binned by the class of --tracer NAME (e.g. sigma0): one CSV line per time step and '
                          'class [-inf,E0), [E0,E1), ..., [EN,inf), and a last one (nan,nan) for faces without a value')
+    ap.add_argument('--remap', default='', metavar='linear',
+                    help='with --classes (and --carry): conservative remapping -- a level\'s transport is spread over the '
+                         'classes between the class field\'s values at the layer\'s upper and lower interface (piecewise-linear '
+                         'in z) instead of going whole to the class of its face: a smooth MOC(sigma) with many class edges')
     ap.add_argument('--tracer2', default='', metavar='NAME',
                     help='with --classes2: the second class field (e.g. so beside --tracer thetao); NAME is read from the T file')
     ap.add_argument('--tracer2-file', dest='tracer2File', default='', metavar='FILE', help='read --tracer2 from FILE instead')
