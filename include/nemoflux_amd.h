@@ -616,6 +616,32 @@ int nf_inflater_run(nf_inflater **self, const void *comp_host, size_t comp_bytes
                     const long long *in_len, int nchunks, long long chunk_bytes, int elem_size, int shuffled,
                     const long long *chunk_dims, const long long *slab_dims, const long long *origin, void *out_dev,
                     void *hip_stream, int *status_host);
+/* The same into a STACK of slabs: out_dev holds slab_dims[0] / stack_nz slabs of (stack_nz, ny, nx) one behind the other
+ * (the variables and time steps of a group, decoded by one launch), origin[3 i] counts levels from the top of the stack.  A
+ * chunk that hangs over in z is cut at the end of the slab it starts in: the levels behind it belong to the next slab.
+ * stack_nz = 0 (what nf_inflater_run passes): one slab.  slab_dims[0] must be a multiple of stack_nz. */
+int nf_inflater_run_stacked(nf_inflater **self, const void *comp_host, size_t comp_bytes, const long long *in_off,
+                            const long long *in_len, int nchunks, long long chunk_bytes, int elem_size, int shuffled,
+                            const long long *chunk_dims, const long long *slab_dims, const long long *origin, void *out_dev,
+                            void *hip_stream, int *status_host, long long stack_nz);
+/* Which placement launch nf_inflater_run takes for a chunk geometry (it asks this very function): BYTES = raw bytes;
+ * PLANES16_F4 / PLANES4_* = shuffled chunks of whole (y, x) planes, 16 or 4 elements per lane; ROWS4_* = other shuffled chunks
+ * whose rows are a multiple of four elements long, 4 per lane; ELEM_* = one element per lane.  Needs no GPU: the tests'
+ * geometry table is checked against it, so that a change of the dispatch cannot drop a launch from the suite unnoticed. */
+enum {
+    NF_PLACE_BYTES = 0,
+    NF_PLACE_PLANES16_F4 = 1,
+    NF_PLACE_PLANES4_F4 = 2,
+    NF_PLACE_PLANES4_F8 = 3,
+    NF_PLACE_ROWS4_F4 = 4,
+    NF_PLACE_ROWS4_F8 = 5,
+    NF_PLACE_ELEM_F4_SHUFFLED = 6,
+    NF_PLACE_ELEM_F4 = 7,
+    NF_PLACE_ELEM_F8_SHUFFLED = 8,
+    NF_PLACE_ELEM_F8 = 9,
+    NF_PLACE_FORMS = 10
+};
+int nf_inflater_place_form(int elem_size, int shuffled, const long long *chunk_dims, const long long *slab_dims, int *form);
 
 /* ------------------------------------------------------------------ time means (nf_timemean.hip) */
 /* The time mean of nsteps arrays of n values each, step t at src_dev + t * stride_elems elements of dtype (HBM).  Per value

@@ -178,8 +178,11 @@ _sig('nf_inflater_share_scratch', [_pp, _pp])
 _sig('nf_inflater_capacity', [c_int_p])
 _sig('nf_inflater_upload', [_pp, ctypes.c_void_p, ctypes.c_size_t])
 _sig('nf_inflater_upload_ranges', [_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_size_t])
+_sig('nf_inflater_place_form', [ctypes.c_int, ctypes.c_int, c_ll_p, c_ll_p, c_int_p])
 _sig('nf_inflater_run', [_pp, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
                          ctypes.c_int, c_ll_p, c_ll_p, c_ll_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p])
+_sig('nf_inflater_run_stacked', [_pp, ctypes.c_void_p, ctypes.c_size_t, c_ll_p, c_ll_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
+                                 ctypes.c_int, c_ll_p, c_ll_p, c_ll_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p, ctypes.c_longlong])
 NF_MEAN_OVER_STEPS, NF_MEAN_OVER_PRESENT = 0, 1
 _sig('nf_time_mean', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_longlong,   # HBM addresses
                       ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,

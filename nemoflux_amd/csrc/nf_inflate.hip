@@ -62,7 +62,11 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t *__restrict__ comp
 // four elements long take the one-element-per-lane form.
 struct SlabGeom {
     unsigned cz, cy, cx, nz, ny, nx;
+    unsigned nzs;       // the slab is a stack of slabs of nzs levels each (nzs == nz: one slab)
 };
+// A chunk that hangs over in z stops at the end of the slab it starts in -- in a stack of slabs (the steps and variables of a
+// group, nf_inflater_run_stacked) the levels behind it belong to the NEXT slab, not to the chunk.
+__device__ inline unsigned chunk_z_end(const SlabGeom &g, unsigned z0) { return (z0 / g.nzs + 1u) * g.nzs; }
 template <int ES, bool SHUFFLED>
 __global__ __launch_bounds__(kBlock) void k_place(const uint8_t *__restrict__ tmp, unsigned chunk_bytes,
                                                   const InflateJob *__restrict__ jobs, int njobs, SlabGeom g,
@@ -72,13 +76,14 @@ __global__ __launch_bounds__(kBlock) void k_place(const uint8_t *__restrict__ tm
     for (int i = blockIdx.y; i < njobs; i += gridDim.y) {
         const InflateJob job = jobs[i];
         const uint8_t *s = tmp + (unsigned long long)i * chunk_bytes;
+        const unsigned zend = chunk_z_end(g, job.z0);
         for (unsigned long long e = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; e < n;
              e += (unsigned long long)gridDim.x * kBlock) {
             const unsigned c = (unsigned)(e % g.cx);
             const unsigned long long r = e / g.cx;
             const unsigned b = (unsigned)(r % g.cy), a = (unsigned)(r / g.cy);
             const unsigned z = job.z0 + a, y = job.y0 + b, x = job.x0 + c;
-            if (z >= g.nz || y >= g.ny || x >= g.nx) continue;
+            if (z >= zend || y >= g.ny || x >= g.nx) continue;
             const unsigned long long o = ((unsigned long long)z * g.ny + y) * g.nx + x;
             if (ES == 1) {
                 dst[o] = s[e];
@@ -115,6 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_place4(const uint8_t *__restrict__ t
     for (int i = blockIdx.y; i < njobs; i += gridDim.y) {
         const InflateJob job = jobs[i];
         const uint32_t *s = reinterpret_cast<const uint32_t *>(tmp + (unsigned long long)i * chunk_bytes);
+        const unsigned zend = chunk_z_end(g, job.z0);
         for (unsigned q = blockIdx.x * kBlock + threadIdx.x; q < nq; q += gridDim.x * kBlock) {
             const unsigned e = 4 * q;
             unsigned x, y, z;
@@ -122,14 +128,14 @@ __global__ __launch_bounds__(kBlock) void k_place4(const uint8_t *__restrict__ t
                 z = job.z0 + e / plane;           // only the bound matters: the level an over-hanging chunk must stop at
                 y = 0;
                 x = 0;
-                if (z >= g.nz) continue;
+                if (z >= zend) continue;
             } else {
                 const unsigned c = e % g.cx, r = e / g.cx;
                 const unsigned b = r % g.cy, a = r / g.cy;
                 z = job.z0 + a;
                 y = job.y0 + b;
                 x = job.x0 + c;
-                if (z >= g.nz || y >= g.ny || x >= g.nx) continue;
+                if (z >= zend || y >= g.ny || x >= g.nx) continue;
             }
             uint32_t w[ES];
 #pragma unroll
@@ -170,9 +176,10 @@ __global__ __launch_bounds__(kBlock) void k_place16(const uint8_t *__restrict__ 
     for (int i = blockIdx.y; i < njobs; i += gridDim.y) {
         const InflateJob job = jobs[i];
         const uint8_t *s = tmp + (unsigned long long)i * chunk_bytes;
+        const unsigned zend = chunk_z_end(g, job.z0);
         for (unsigned q = blockIdx.x * kBlock + threadIdx.x; q < nq; q += gridDim.x * kBlock) {
             const unsigned e = 16 * q;
-            if (job.z0 + e / plane >= g.nz) continue;            // the levels of an over-hanging chunk that lie beyond the slab
+            if (job.z0 + e / plane >= zend) continue;            // the levels of an over-hanging chunk that lie beyond the slab
             uvec4 w[4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) w[p] = __builtin_nontemporal_load(reinterpret_cast<const uvec4 *>(s + (unsigned long long)p * n + e));
@@ -279,19 +286,43 @@ int inflater_upload_ranges(Inflater *h, const unsigned long long *src_addr, cons
     return NF_OK;
 }
 
-int inflater_run(Inflater *h, const void *comp_host, size_t comp_bytes, const long long *in_off, const long long *in_len,
-                 int n, long long chunk_bytes, int elem_size, int shuffled, const long long *chunk_dims,
-                 const long long *slab_dims, const long long *origin, void *out_dev, hipStream_t s, int *status_host)
+// Which placement launch a chunk geometry takes (NF_PLACE_* of include/nemoflux_amd.h): the ONE place where that is decided --
+// inflater_run launches what this returns, nf_inflater_place_form hands it to the tests, whose geometry table has to reach
+// every form.  Host arithmetic only.
+int place_form(int elem_size, int shuffled, const long long *chunk_dims, const long long *slab_dims, int *form)
 {
-    NF_REQUIRE(h && chunk_dims && slab_dims && (n == 0 || (in_off && in_len && origin && out_dev)), NF_ERR_ARG,
-               "inflate: null argument");
-    NF_REQUIRE(n == 0 || comp_host || (h->uploaded == comp_bytes && comp_bytes > 0), NF_ERR_STATE,
-               "inflate: no compressed buffer given and none of that size uploaded (nf_inflater_upload)");
+    NF_REQUIRE(chunk_dims && slab_dims && form, NF_ERR_ARG, "inflate: null argument");
     NF_REQUIRE(elem_size == 1 || elem_size == 4 || elem_size == 8, NF_ERR_ARG, "inflate: element size must be 1, 4 or 8");
     NF_REQUIRE(!(shuffled && elem_size == 1), NF_ERR_ARG, "inflate: single bytes cannot be shuffled");
     for (int k = 0; k < 3; ++k)
         NF_REQUIRE(chunk_dims[k] > 0 && slab_dims[k] > 0 && chunk_dims[k] < (1ll << 31) && slab_dims[k] < (1ll << 31), NF_ERR_ARG,
                    "inflate: bad chunk / slab dimensions");
+    const bool four = shuffled && chunk_dims[2] % 4 == 0;             // four elements per lane (k_place4)
+    // whole (y, x) planes per chunk whose plane size is a multiple of four elements: no index arithmetic at all
+    const bool planes = chunk_dims[1] == slab_dims[1] && chunk_dims[2] == slab_dims[2] && (slab_dims[1] * slab_dims[2]) % 4 == 0;
+    const bool sixteen = elem_size == 4 && four && planes && (slab_dims[1] * slab_dims[2]) % 16 == 0;
+    if (elem_size == 1) *form = NF_PLACE_BYTES;
+    else if (sixteen) *form = NF_PLACE_PLANES16_F4;
+    else if (four && planes) *form = elem_size == 4 ? NF_PLACE_PLANES4_F4 : NF_PLACE_PLANES4_F8;
+    else if (four) *form = elem_size == 4 ? NF_PLACE_ROWS4_F4 : NF_PLACE_ROWS4_F8;
+    else if (elem_size == 4) *form = shuffled ? NF_PLACE_ELEM_F4_SHUFFLED : NF_PLACE_ELEM_F4;
+    else *form = shuffled ? NF_PLACE_ELEM_F8_SHUFFLED : NF_PLACE_ELEM_F8;
+    return NF_OK;
+}
+
+int inflater_run(Inflater *h, const void *comp_host, size_t comp_bytes, const long long *in_off, const long long *in_len,
+                 int n, long long chunk_bytes, int elem_size, int shuffled, const long long *chunk_dims,
+                 const long long *slab_dims, const long long *origin, void *out_dev, hipStream_t s, int *status_host,
+                 long long stack_nz)
+{
+    NF_REQUIRE(h && chunk_dims && slab_dims && (n == 0 || (in_off && in_len && origin && out_dev)), NF_ERR_ARG,
+               "inflate: null argument");
+    NF_REQUIRE(n == 0 || comp_host || (h->uploaded == comp_bytes && comp_bytes > 0), NF_ERR_STATE,
+               "inflate: no compressed buffer given and none of that size uploaded (nf_inflater_upload)");
+    int form = 0;                  // checks element size and dimensions, too
+    NF_TRY_RC(place_form(elem_size, shuffled, chunk_dims, slab_dims, &form));
+    NF_REQUIRE(stack_nz == 0 || (stack_nz > 0 && slab_dims[0] % stack_nz == 0), NF_ERR_ARG,
+               "inflate: the slab is not a whole number of stacked slabs of stack_nz levels");
     NF_REQUIRE(chunk_bytes == chunk_dims[0] * chunk_dims[1] * chunk_dims[2] * elem_size && chunk_bytes < (1ll << 31), NF_ERR_ARG,
                "inflate: chunk_bytes does not match the chunk dimensions (chunks of up to 2 GiB)");
     if (n == 0) return NF_OK;
@@ -336,26 +367,29 @@ int inflater_run(Inflater *h, const void *comp_host, size_t comp_bytes, const lo
     hipLaunchKernelGGL(k_inflate, dim3((unsigned)n), dim3(64), 0, s, h->d_comp.get(), (unsigned long long)comp_pad,
                        d_jobs, n, d_tmp, (unsigned)chunk_bytes, so->d_status.get());
     const SlabGeom g{(unsigned)chunk_dims[0], (unsigned)chunk_dims[1], (unsigned)chunk_dims[2], (unsigned)slab_dims[0],
-                     (unsigned)slab_dims[1], (unsigned)slab_dims[2]};
-    const bool four = shuffled && chunk_dims[2] % 4 == 0;             // four elements per lane (k_place4)
-    // whole (y, x) planes per chunk whose plane size is a multiple of four elements: no index arithmetic at all
-    const bool planes = chunk_dims[1] == slab_dims[1] && chunk_dims[2] == slab_dims[2] && (slab_dims[1] * slab_dims[2]) % 4 == 0;
-    const bool sixteen = elem_size == 4 && four && planes && (slab_dims[1] * slab_dims[2]) % 16 == 0;
-    const long long nelem = chunk_bytes / elem_size / (sixteen ? 16 : four ? 4 : 1);
+                     (unsigned)slab_dims[1], (unsigned)slab_dims[2], (unsigned)(stack_nz ? stack_nz : slab_dims[0])};
+    const int per_lane = form == NF_PLACE_PLANES16_F4 ? 16
+                         : (form == NF_PLACE_PLANES4_F4 || form == NF_PLACE_PLANES4_F8 || form == NF_PLACE_ROWS4_F4 || form == NF_PLACE_ROWS4_F8) ? 4 : 1;
+    const long long nelem = chunk_bytes / elem_size / per_lane;
     unsigned gx = (unsigned)std::min<long long>(4096, (nelem + kBlock - 1) / kBlock);
     if (gx == 0) gx = 1;
     const dim3 grid(gx, (unsigned)std::min(n, 65535)), block(kBlock);  // gridDim.y is capped: the kernels walk the chunks
     uint8_t *dst = (uint8_t *)out_dev;
-    if (elem_size == 1) hipLaunchKernelGGL((k_place<1, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (sixteen) hipLaunchKernelGGL(k_place16, grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (elem_size == 4 && four && planes) hipLaunchKernelGGL((k_place4<4, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (elem_size == 8 && four && planes) hipLaunchKernelGGL((k_place4<8, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (elem_size == 4 && four) hipLaunchKernelGGL((k_place4<4, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (elem_size == 8 && four) hipLaunchKernelGGL((k_place4<8, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (elem_size == 4 && shuffled) hipLaunchKernelGGL((k_place<4, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (elem_size == 4) hipLaunchKernelGGL((k_place<4, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else if (shuffled) hipLaunchKernelGGL((k_place<8, true>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
-    else hipLaunchKernelGGL((k_place<8, false>), grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst);
+#define NF_PLACE_LAUNCH(kernel) hipLaunchKernelGGL(kernel, grid, block, 0, s, d_tmp, (unsigned)chunk_bytes, d_jobs, n, g, dst)
+    switch (form) {
+        case NF_PLACE_BYTES: NF_PLACE_LAUNCH((k_place<1, false>)); break;
+        case NF_PLACE_PLANES16_F4: NF_PLACE_LAUNCH(k_place16); break;
+        case NF_PLACE_PLANES4_F4: NF_PLACE_LAUNCH((k_place4<4, true>)); break;
+        case NF_PLACE_PLANES4_F8: NF_PLACE_LAUNCH((k_place4<8, true>)); break;
+        case NF_PLACE_ROWS4_F4: NF_PLACE_LAUNCH((k_place4<4, false>)); break;
+        case NF_PLACE_ROWS4_F8: NF_PLACE_LAUNCH((k_place4<8, false>)); break;
+        case NF_PLACE_ELEM_F4_SHUFFLED: NF_PLACE_LAUNCH((k_place<4, true>)); break;
+        case NF_PLACE_ELEM_F4: NF_PLACE_LAUNCH((k_place<4, false>)); break;
+        case NF_PLACE_ELEM_F8_SHUFFLED: NF_PLACE_LAUNCH((k_place<8, true>)); break;
+        case NF_PLACE_ELEM_F8: NF_PLACE_LAUNCH((k_place<8, false>)); break;
+        default: NF_REQUIRE(false, NF_ERR_STATE, "inflate: unknown placement form");
+    }
+#undef NF_PLACE_LAUNCH
     NF_HIP(hipGetLastError());
     std::vector<int> status((size_t)n, 0);
     NF_HIP(hipMemcpyAsync(status.data(), so->d_status.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -489,6 +523,11 @@ int nf_inflater_capacity(int *streams)
     return NF_OK;
 }
 
+int nf_inflater_place_form(int elem_size, int shuffled, const long long *chunk_dims, const long long *slab_dims, int *form)
+{
+    return place_form(elem_size, shuffled, chunk_dims, slab_dims, form);
+}
+
 int nf_inflater_del(nf_inflater **self)
 {
     if (self && *self) {
@@ -508,10 +547,10 @@ int nf_inflater_del(nf_inflater **self)
     return NF_OK;
 }
 
-int nf_inflater_run(nf_inflater **self, const void *comp_host, size_t comp_bytes, const long long *in_off,
-                    const long long *in_len, int nchunks, long long chunk_bytes, int elem_size, int shuffled,
-                    const long long *chunk_dims, const long long *slab_dims, const long long *origin, void *out_dev,
-                    void *hip_stream, int *status_host)
+int nf_inflater_run_stacked(nf_inflater **self, const void *comp_host, size_t comp_bytes, const long long *in_off,
+                            const long long *in_len, int nchunks, long long chunk_bytes, int elem_size, int shuffled,
+                            const long long *chunk_dims, const long long *slab_dims, const long long *origin, void *out_dev,
+                            void *hip_stream, int *status_host, long long stack_nz)
 {
     if (!self || !*self) {
         set_error("nf_inflater_run: null handle");
@@ -524,11 +563,21 @@ int nf_inflater_run(nf_inflater **self, const void *comp_host, size_t comp_bytes
     }
     try {
         return inflater_run(reinterpret_cast<Inflater *>(*self), comp_host, comp_bytes, in_off, in_len, nchunks, chunk_bytes,
-                            elem_size, shuffled, chunk_dims, slab_dims, origin, out_dev, (hipStream_t)hip_stream, status_host);
+                            elem_size, shuffled, chunk_dims, slab_dims, origin, out_dev, (hipStream_t)hip_stream, status_host,
+                            stack_nz);
     } catch (...) {
         set_error("nf_inflater_run: out of host memory");
         return NF_ERR_HOST;
     }
+}
+
+int nf_inflater_run(nf_inflater **self, const void *comp_host, size_t comp_bytes, const long long *in_off,
+                    const long long *in_len, int nchunks, long long chunk_bytes, int elem_size, int shuffled,
+                    const long long *chunk_dims, const long long *slab_dims, const long long *origin, void *out_dev,
+                    void *hip_stream, int *status_host)
+{
+    return nf_inflater_run_stacked(self, comp_host, comp_bytes, in_off, in_len, nchunks, chunk_bytes, elem_size, shuffled,
+                                   chunk_dims, slab_dims, origin, out_dev, hip_stream, status_host, 0);
 }
 
 }  // extern "C"

@@ -87,15 +87,24 @@ class ChunkDecoder(object):
     def gather_many(self, items, pinned, total_nz, threads=None, copy=True):
         """items: [(mapped file, device_plan of one slab, z offset of that slab in the group's slab)] -- e.g. uo and vo of
         several time steps, stacked along z into one (total_nz, ny, nx) slab.  The compressed chunks of all of them are
-        copied into `pinned` back to back; slabs of the same chunk geometry are merged into ONE StagedChunks (= one launch,
-        one wavefront per chunk); returns the list of StagedChunks (one per distinct geometry)."""
+        copied into `pinned` back to back; slabs of the same geometry are merged into ONE StagedChunks (= one launch,
+        one wavefront per chunk); returns the list of StagedChunks (one per distinct geometry).  The z offsets are whole
+        multiples of the slabs' own height (plan['stack_nz'] tells the device where one slab ends and the next begins:
+        an edge chunk that hangs over in z must not reach into the slab stacked behind it)."""
         groups = {}
         src_addr, dst_addr, lens = [], [], []
         keep = []
         pos = 0
         for raw, plan, zoff in items:
-            key = (tuple(plan['chunk_dims']), tuple(plan['slab_dims'][1:]), plan['elem_size'], plan['shuffled'])
+            key = (tuple(plan['chunk_dims']), tuple(plan['slab_dims']), plan['elem_size'], plan['shuffled'])
             g = groups.setdefault(key, dict(in_off=[], in_len=[], origin=[], plan=plan))
+            nz = int(plan['slab_dims'][0])
+            if zoff % nz or int(total_nz) % nz:
+                # slabs that do not sit at whole multiples of their own height cannot be told apart on the device: fine as
+                # long as no chunk hangs over in z (nothing is cut then), an error otherwise
+                if nz % int(plan['chunk_dims'][0]):
+                    raise RuntimeError('ERROR: slabs whose chunks hang over in z must be stacked at multiples of their height')
+                g['loose'] = True
             src = numpy.frombuffer(raw, numpy.uint8)
             keep.append(src)
             base = src.ctypes.data
@@ -121,6 +130,8 @@ class ChunkDecoder(object):
         out = []
         for key, g in groups.items():
             plan = dict(g['plan'])
+            if not g.get('loose'):
+                plan['stack_nz'] = int(plan['slab_dims'][0])      # a chunk that hangs over in z stops at the end of ITS slab
             plan['slab_dims'] = (int(total_nz),) + tuple(plan['slab_dims'][1:])
             out.append(StagedChunks(pinned, pos, numpy.array(g['in_off'], numpy.int64), numpy.array(g['in_len'], numpy.int64),
                                     numpy.ascontiguousarray(numpy.array(g['origin'], numpy.int64).reshape(-1, 3)), plan))
@@ -152,26 +163,35 @@ class ChunkDecoder(object):
         ll = _lib.c_ll_p
         cd = numpy.array(plan['chunk_dims'], numpy.int64)
         sd = numpy.array(plan['slab_dims'], numpy.int64)
-        check(lib.nf_inflater_run(ctypes.byref(self._h), None if uploaded else ctypes.c_void_p(staged.pinned.ptr), int(staged.used),
-                                  staged.in_off.ctypes.data_as(ll), staged.in_len.ctypes.data_as(ll), n,
-                                  int(plan['chunk_bytes']), int(plan['elem_size']), int(plan['shuffled']),
-                                  cd.ctypes.data_as(ll), sd.ctypes.data_as(ll), staged.origin.ctypes.data_as(ll),
-                                  ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(stream) if stream else None,
-                                  status.ctypes.data_as(_lib.c_int_p)))
+        # plan['stack_nz'] (gather_many): the slab is a stack of slabs of that many levels, chunks are cut at the end of their own
+        check(lib.nf_inflater_run_stacked(ctypes.byref(self._h), None if uploaded else ctypes.c_void_p(staged.pinned.ptr),
+                                          int(staged.used), staged.in_off.ctypes.data_as(ll), staged.in_len.ctypes.data_as(ll), n,
+                                          int(plan['chunk_bytes']), int(plan['elem_size']), int(plan['shuffled']),
+                                          cd.ctypes.data_as(ll), sd.ctypes.data_as(ll), staged.origin.ctypes.data_as(ll),
+                                          ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(stream) if stream else None,
+                                          status.ctypes.data_as(_lib.c_int_p), int(plan.get('stack_nz', 0))))
         return status[:n]
 
-    def decode_streams(self, streams, out_len, elem_size=1, shuffled=0):
+    def decode_streams(self, streams, out_len, elem_size=1, shuffled=0, align=8):
         """Convenience for tests / tools: inflate a list of zlib streams that all decode to out_len bytes, one per row of a
-        (n, 1, out_len / elem_size) slab; returns the decoded rows (host numpy uint8, shape (n, out_len))."""
+        (n, 1, out_len / elem_size) slab; returns the decoded rows (host numpy uint8, shape (n, out_len)).  align: every
+        stream starts at a multiple of it (8 is what gather_many does); align=1 packs the streams back to back, the last
+        one ending at the last byte of the compressed buffer (the C ABI takes any in_off).  The offsets used are kept in
+        self.last_in_off."""
         n = len(streams)
-        total_in = sum((len(s) + 7) & ~7 for s in streams)
+        align = int(align)
+        if align < 1:
+            raise ValueError('ERROR: align must be at least 1')
+        step = lambda nbytes: -(-nbytes // align) * align
+        total_in = sum(step(len(s)) for s in streams)
         pinned = _Pinned(total_in + 16)
         in_off = numpy.zeros(n, numpy.int64)
         pos = 0
         for i, s in enumerate(streams):
             in_off[i] = pos
             pinned.array[pos:pos + len(s)] = numpy.frombuffer(s, numpy.uint8)
-            pos += (len(s) + 7) & ~7
+            pos += step(len(s))
+        self.last_in_off = in_off
         ne = out_len // elem_size
         plan = dict(chunk_dims=(1, 1, ne), slab_dims=(n, 1, ne), chunk_bytes=out_len, elem_size=elem_size, shuffled=shuffled)
         origin = numpy.zeros((n, 3), numpy.int64)

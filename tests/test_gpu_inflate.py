@@ -167,16 +167,20 @@ def test_far_path_on_the_device():
     """The shipped decoder keeps DEFLATE's whole 32 KiB window in LDS, so its FAR path (a match source that has already been
     flushed to HBM) never runs on a GPU -- it would with a smaller window.  To keep that path trustworthy (round-3 advisor)
     the library is built here with -DNFI_WINDOW=8192 (`make window8k`: one object, seconds; test-only, never loaded by the
-    package) and decodes capacity + 200 streams, a third of them made of matches 9 000 .. 30 000 bytes back, against zlib."""
+    package) and decodes capacity + 200 streams, a third of them made of matches 9 000 .. 30 000 bytes back, against zlib;
+    then the catalogue of tests/deflate_writer.py."""
     import os
     import subprocess
     import sys
     from conftest import ROOT
     subprocess.check_call(['make', '-C', os.path.join(ROOT, 'nemoflux_amd', 'csrc'), 'window8k', '-s'])
     lib = os.path.join(ROOT, 'build', 'window8k', 'libnemoflux_amd_w8k.so')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'check_inflate_window.py')], env=dict(os.environ, NEMOFLUX_AMD_LIB=lib),
-                       capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'check_inflate_window.py'), '--catalogue'],
+                       env=dict(os.environ, NEMOFLUX_AMD_LIB=lib), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and 'bit-identical' in r.stdout and 'libnemoflux_amd_w8k.so' in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+    # ... and the catalogue of legal foreign streams (tests/deflate_writer.py): its distance and copy cases are far here
+    from deflate_writer import foreign_streams
+    assert f'foreign catalogue OK: {len(foreign_streams())} streams' in r.stdout, r.stdout[-1500:]
     cap = int(r.stdout.split('capacity ')[1].split(')')[0])
     assert cap > 2000            # ten streams per CU with the 8 KiB window (the shipped build: 1024)
 

@@ -2,8 +2,9 @@
 host (one "lane", no barriers), against zlib's own streams: every block type (stored, fixed, dynamic), every compression
 level and strategy, all four alignments of the stream's first byte, long-distance matches across the 32 KiB window,
 overlapping copies, byte-shuffled float32 data like the HDF5 chunks of NEMO files, and malformed streams (which must end
-in an error code, never in an out-of-bounds write).  The device build of the same source is checked by
-tests/test_gpu_inflate.py."""
+in an error code, never in an out-of-bounds write), and the legal streams no normal compressor writes
+(tests/deflate_writer.py: the catalogue and random streams, pinned against zlib here).  The device build of the same source
+is checked by tests/test_gpu_inflate.py and tests/test_gpu_inflate_foreign.py."""
 import ctypes
 import os
 import subprocess
@@ -13,6 +14,7 @@ import numpy
 import pytest
 
 from conftest import ROOT
+from deflate_writer import foreign_streams, random_streams
 
 
 @pytest.fixture(scope='module', params=[32768, 8192], ids=['window32k', 'window8k'])
@@ -97,3 +99,34 @@ def test_malformed_streams_end_in_an_error(host_inflate):
     for trial in range(100):                                        # pure noise behind a valid header
         noise = b'\x78\x9c' + rng.integers(0, 256, 2000, dtype=numpy.uint8).tobytes()
         host_inflate(noise, 10000)
+
+
+def test_writer_streams_are_legal_and_hold_what_they_mean():
+    """zlib is the reference of every foreign stream: it must accept each one (a refusal is a bug of the writer) and decode
+    it to the bytes the writer's own token expansion states"""
+    cat = foreign_streams()
+    assert len(cat) >= 50 and len({len(d) for _, d in cat.values()}) <= 4          # a handful of decoded lengths
+    for letter in 'abcdefg':
+        assert any(n.startswith(letter + '_') for n in cat)
+    for name, (stream, data) in cat.items():
+        assert zlib.decompress(stream) == data, name
+    rnd = random_streams(300, 11)
+    assert len(rnd) == 300 and len({s for s, _ in rnd}) == 300
+    for i, (stream, data) in enumerate(rnd):
+        assert zlib.decompress(stream) == data, i
+
+
+def test_host_build_decodes_the_foreign_catalogue(host_inflate):
+    for name, (stream, _) in foreign_streams().items():
+        want = zlib.decompress(stream)
+        for skip in (0, 1, 2, 3):
+            rc, out = host_inflate(stream, len(want), skip)
+            assert rc == 0 and out == want, (name, skip, rc)
+
+
+def test_host_build_decodes_random_foreign_streams(host_inflate):
+    for i, (stream, _) in enumerate(random_streams(300, 11)):
+        want = zlib.decompress(stream)
+        for skip in (0, 1, 2, 3):
+            rc, out = host_inflate(stream, len(want), skip)
+            assert rc == 0 and out == want, (i, skip, rc)

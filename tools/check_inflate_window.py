@@ -1,7 +1,10 @@
 """The device decoder against zlib on streams whose matches reach far back (periods of 9 000 .. 30 000 bytes: beyond an
 8 KiB window, inside DEFLATE's 32 KiB) plus mixed content, more streams than are resident at once.  Run against the
 `make window8k` build (NEMOFLUX_AMD_LIB=build/window8k/libnemoflux_amd_w8k.so) it exercises the decoder's FAR path on the
-device; against the shipped library the same streams stay inside the LDS window."""
+device; against the shipped library the same streams stay inside the LDS window.
+
+--catalogue: also the catalogue of legal foreign streams of tests/deflate_writer.py (every distance symbol, copies across the
+window's edges: those take the far path on purpose with the 8 KiB build); a second line reports it."""
 import os
 import sys
 import zlib
@@ -35,3 +38,14 @@ out = dec.decode_streams(streams, size)
 bad = [i for i in range(n) if not numpy.array_equal(out[i], datas[i])]
 assert not bad, bad[:10]
 print(f'inflate window check OK: {n} streams (capacity {cap}) bit-identical to zlib with {os.environ.get("NEMOFLUX_AMD_LIB", "the shipped library")}')
+if '--catalogue' in sys.argv[1:]:
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from deflate_writer import foreign_streams  # noqa: E402
+    by_size = {}
+    for name, (stream, _) in foreign_streams().items():
+        by_size.setdefault(len(zlib.decompress(stream)), []).append((name, stream))
+    for fsize, group in sorted(by_size.items()):
+        out = dec.decode_streams([s for _, s in group], fsize)
+        bad = [name for i, (name, s) in enumerate(group) if bytes(out[i]) != zlib.decompress(s)]
+        assert not bad, bad
+    print(f'foreign catalogue OK: {sum(len(g) for g in by_size.values())} streams in {len(by_size)} launches bit-identical to zlib')
