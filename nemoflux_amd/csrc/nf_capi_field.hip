@@ -17,6 +17,10 @@ static int g_batch_steps = 1;
 //                          stores on its own (default 1)
 //   "pass_k3_pairs"        1 = the per-step pass reduces its whole steps two at a time: one gather launch reads the record
 //                          stream once for both steps; 0 = one reduction per step (default 1)
+//   "pass_inner_interleaved"  1 = the steps of a pair whose planes no caller can read -- the first step of every pair, and the
+//                          second of every pair but the pass's last -- store ONE interleaved (eU, eV) stream, which the pair
+//                          reduction gathers with three loads per record instead of four; 0 = two planes each, the pass as it
+//                          was without the form; -1 = by the dtype of uo / vo, as measured (default: see g_inner_interleaved)
 //   "class_window"         rows of the class transport per pass over the fields, 1 .. 32 (default 32: DESIGN.md section 4)
 //   "area_chunk"           levels per launch of the area profile: 2 or 4 (float64), 4 or 8 (float32); 0 = the measured default
 //   "gross_chunk"          levels per launch of the gross profile: 2, 4 or 8 (float64), 4 or 8 (float32); 0 = the measured default
@@ -30,6 +34,10 @@ static int g_partial_full = 0;
 static int g_use_graph = 1;
 static int g_inner_signed = 1;
 static int g_k3_pairs = 1;
+// Measured in-process at the headline size (tools/ab_pass.py, profiles/pass_interleaved.txt): float64 -1.2 % per pass, the
+// ranges of nine rounds apart; float32 +0.6 % -- there the flux kernel's four 16-byte stores at a 64-byte lane stride cost it
+// more (+2.8 % per launch) than the reduction gains.  So the default (-1) interleaves float64 passes only.
+static int g_inner_interleaved = -1;
 static int g_class_window = 32;
 static int g_joint_window = 32;
 static int g_joint_skip = 1;
@@ -62,6 +70,11 @@ int field_tuning_set(const char *name, int value)
     }
     if (!strcmp(name, "pass_k3_pairs")) {
         g_k3_pairs = value != 0;
+        return NF_OK;
+    }
+    if (!strcmp(name, "pass_inner_interleaved")) {
+        if (!(value >= -1 && value <= 1)) return -1;
+        g_inner_interleaved = value;
         return NF_OK;
     }
     if (!strcmp(name, "class_window")) {
@@ -129,7 +142,10 @@ struct nf_field {
         DevArray<double> iV;    // [4][ncell]
         DevArray<double> abs;   // [2][ncell]
         DevArray<double> aos;   // (ncell,4) re-pack buffer for read_step, allocated on first use
-        DevArray<double> uv2;   // [2][ncell] eU, eV of the first step of a pair ("pass_k3_pairs"), allocated on first use
+        // the steps of a pair that do not go to the resident planes ("pass_k3_pairs"), 2 * ncell doubles each, allocated on
+        // first use: pair[0] the first step's [eU | eV] planes or ("pass_inner_interleaved") its interleaved stream; pair[1]
+        // the interleaved stream of the second step of a pair that is not the pass's last
+        DevArray<double> pair[2];
         DevArray<double> tr_planes;   // [2][ncell] eU_tau, eV_tau of the last tracer step, allocated on first use
         DevArray<unsigned long long> maxbits;
         // multi-step launches for small grids (compute_all): per-step planes, scratch and z ranges
@@ -527,16 +543,18 @@ struct StepForm {
     // a step of the pass that another step follows: its planes are overwritten before anybody but K3 can read them, so
     // only the two signed planes are stored (the f64 flux kernel in its signed-only form, no f32 expansion)
     bool inner = false;
-    // the step's signed planes go to geo.uv2 instead of the resident planes, and no reduction is launched: the first step
-    // of a pair, reduced together with the next one (field_pair_async)
-    bool to_uv2 = false;
+    // the step's signed values go to `pair_buf` (2 * ncell doubles) instead of the resident planes, and no reduction is
+    // launched: a step of a pair, reduced by field_pair_async.  The handle's resident state (planes, derived_stale) is not touched.
+    double *pair_buf = nullptr;
+    // ... as K1's interleaved stream instead of the two planes [eU | eV]
+    bool interleaved = false;
 };
 
 // one time step on the field's stream; row_dev receives [segments | transects]
 static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form = {})
 {
     const int rowlen = field_row_length(f);
-    const bool reduce = row_dev && rowlen > 0 && !form.to_uv2;
+    const bool reduce = row_dev && rowlen > 0 && !form.pair_buf;
     NF_TRY(field_ready(f, "compute", reduce));
     NF_REQUIRE(t >= 0 && t < f->uv.nt, NF_ERR_ARG, "compute: time index out of range");
     const Levels lv = field_levels(f, t);
@@ -550,8 +568,9 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     NF_TRY(field_cell_thick(f, t, lv, &ct));
     FluxArgs a = flux_args(in);
     a.iV = f->geo.iV.get();
-    // uv2 holds planes 1 and 2 only: the signed-only kernel stores to iV + ncell and iV + 2 * ncell, nothing below
-    if (form.to_uv2) a.iV = f->geo.uv2.get() - f->ncell;
+    // a pair buffer holds planes 1 and 2 only: the signed-only kernel stores to iV + ncell and iV + 2 * ncell, nothing below;
+    // the interleaved form stores its one stream at iV
+    if (form.pair_buf) a.iV = form.interleaved ? form.pair_buf : form.pair_buf - f->ncell;
     a.absU = f->geo.abs.get();
     a.absV = f->geo.abs.get() + f->ncell;
     a.maxbits = f->geo.maxbits.get();
@@ -564,8 +583,11 @@ static int field_step_async(nf_field *f, long t, double *row_dev, StepForm form 
     const bool partial = (lv.z0 > 0 || lv.z1 < (int)f->nz) && !g_partial_full;
     // (the cell-thickness kernel stores the signed planes in every form, one cell per lane included)
     a.signed_only = (f->compact || partial || form.inner) && (ct.e3u || flux_supports_signed_only(a));
-    NF_REQUIRE(!form.to_uv2 || a.signed_only, NF_ERR_STATE, "compute: a step into the second planes must be signed-only");
-    if (!form.to_uv2) f->derived_stale = a.signed_only != 0;
+    NF_REQUIRE(!form.pair_buf || a.signed_only, NF_ERR_STATE, "compute: a step into a pair buffer must be signed-only");
+    NF_REQUIRE(!form.interleaved || (form.pair_buf && !ct.e3u && !partial && flux_supports_interleaved(a)), NF_ERR_STATE,
+               "compute: the interleaved form is a whole step of a pair on K1's two-field kernel");
+    a.interleaved = form.interleaved;
+    if (!form.pair_buf) f->derived_stale = a.signed_only != 0;
     NF_TRY(field_launch_flux(f, a, ct.e3u ? &ct : nullptr));
     if (reduce) {
         NF_TRY(field_integral(f, f->geo.iV.get(), f->scratch.get(), row_dev));
@@ -954,19 +976,28 @@ static int field_class_area_async(nf_field *f, long t, double *rows_dev)
     return launch_class_area(a, f->stream);
 }
 
-// steps t and t+1, both owned whole: flux t into geo.uv2, flux t+1 into the resident planes (which therefore hold the later
+// steps t and t+1, both owned whole: flux t into geo.pair[0], flux t+1 into the resident planes (which therefore hold the later
 // step, as after two single steps), then ONE reduction of both; rows t and t+1 are contiguous in rows_dev.  last: t+1 is the
-// last owned step of the pass, which stores what it stores on its own.
-static int field_pair_async(nf_field *f, long t, double *rows_dev, bool last)
+// last owned step of the pass, which stores what it stores on its own.  interleaved (field_pass_interleaved): the first step
+// is stored as K1's interleaved stream, and so is -- into geo.pair[1] -- the second step of a pair that another pair
+// follows (last_pair = false): the pass's last pair overwrites the resident planes behind it, so nobody can miss them.
+static int field_pair_async(nf_field *f, long t, double *rows_dev, bool last, bool last_pair, bool interleaved)
 {
     const int rowlen = field_row_length(f);
     StepForm first, second;
-    first.inner = first.to_uv2 = true;
+    first.inner = true;
+    first.pair_buf = f->geo.pair[0].get();
+    first.interleaved = interleaved;
     second.inner = g_inner_signed && !last;
+    if (interleaved && second.inner && !last_pair) {
+        second.pair_buf = f->geo.pair[1].get();
+        second.interleaved = true;
+    }
     NF_TRY(field_step_async(f, t, nullptr, first));
     NF_TRY(field_step_async(f, t + 1, nullptr, second));
-    NF_TRY(launch_integral_pair(field_transects(f), f->geo.uv2.get(), f->geo.iV.get() + f->ncell, f->ncell, f->nx,
-                                f->scratch.get(), rows_dev + (size_t)t * rowlen, rowlen, f->stream));
+    const double *uvB = second.pair_buf ? second.pair_buf : f->geo.iV.get() + f->ncell;
+    NF_TRY(launch_integral_pair(field_transects(f), first.pair_buf, uvB, f->ncell, f->nx, f->scratch.get(),
+                                rows_dev + (size_t)t * rowlen, rowlen, f->stream, first.interleaved, second.interleaved));
     NF_TRY(field_timed_k3_end(f));   // the pair's reduction is timed with the second step's launch
     return NF_OK;
 }
@@ -990,7 +1021,7 @@ static bool field_can_batch(const nf_field *f)
 // kernel), the second signed planes (field_prepare_pass) and the signed-only flux kernel for the first step of a pair
 static bool field_pass_pairs(const nf_field *f)
 {
-    if (!g_k3_pairs || integral_uses_edges() || !f->geo.uv2.get() || !f->weights_built) return false;
+    if (!g_k3_pairs || integral_uses_edges() || !f->geo.pair[0].get() || !f->weights_built) return false;
     // every step starts 16-byte aligned when the first one does: resident fields with a step size that is a multiple of
     // 16 bytes, or steps staged into the (allocation-aligned) staging buffers
     const size_t step_bytes = (size_t)f->nz * f->ncell * elem_size(f->uv.dtype);
@@ -1002,15 +1033,30 @@ static bool field_pass_pairs(const nf_field *f)
     return flux_supports_signed_only(a) && (!f->uv.on_device || step_bytes % 16 == 0);
 }
 
-// device memory a per-step pass may need, allocated before the pass is launched or captured: the second signed planes of
-// a pair.  Nothing is allocated for a pass that takes no pairs (knob off, fewer than two whole steps owned, the edge-entry
-// form of K3).
+// ... and stores the steps of its pairs that nobody else reads interleaved ("pass_inner_interleaved"): K1's own kernel in its
+// two-field form only -- not the cell-thickness kernel, not the compact mode, not a launch small enough for the one-field form
+static bool field_pass_interleaved(const nf_field *f)
+{
+    const bool on = g_inner_interleaved < 0 ? f->uv.dtype == NF_F64 : g_inner_interleaved != 0;
+    if (!on || f->compact || f->e3.p[0]) return false;
+    FluxArgs a{};
+    a.u = f->uv.on_device ? f->uv.p[0] : nullptr;
+    a.v = f->uv.on_device ? f->uv.p[1] : nullptr;
+    a.dtype = f->uv.dtype;
+    a.ncell = f->ncell;
+    return flux_supports_interleaved(a);
+}
+
+// device memory a per-step pass may need, allocated before the pass is launched or captured: the buffers of the steps of a
+// pair that do not go to the resident planes.  Nothing is allocated for a pass that takes no pairs (knob off, fewer than two
+// whole steps owned, the edge-entry form of K3), and the second buffer only for a pass of two pairs or more that interleaves.
 static int field_prepare_pass(nf_field *f)
 {
-    if (!g_k3_pairs || integral_uses_edges() || f->geo.uv2.get() || !f->geo.iV.get()) return NF_OK;
+    if (!g_k3_pairs || integral_uses_edges() || !f->geo.iV.get()) return NF_OK;
     const PassSteps p = field_pass_steps(f);
     if (p.wb - p.wa < 2) return NF_OK;
-    NF_TRY(f->geo.uv2.alloc((size_t)f->ncell * 2));
+    if (!f->geo.pair[0].get()) NF_TRY(f->geo.pair[0].alloc((size_t)f->ncell * 2));
+    if (!f->geo.pair[1].get() && p.wb - p.wa >= 4 && field_pass_interleaved(f)) NF_TRY(f->geo.pair[1].alloc((size_t)f->ncell * 2));
     return NF_OK;
 }
 
@@ -1045,10 +1091,12 @@ static int field_all_steps_direct(nf_field *f, double *rows_dev, bool zero_rows 
     // an odd number of whole steps leaves one of them single: the first, so that the last pair ends on the last whole step
     // and every pair's second step lands in the resident planes
     const long pa = pairs ? p.wa + (p.wb - p.wa) % 2 : p.wb;
+    // (a pass of two pairs or more interleaves only with the second buffer that field_prepare_pass gave it)
+    const bool interleaved = pairs && field_pass_interleaved(f) && (p.wb - pa < 4 || f->geo.pair[1].get());
     for (long t = p.ta; t < p.tb;) {
         const bool last = t + 1 == p.tb;
         if (t >= pa && t + 1 < p.wb) {
-            NF_TRY(field_pair_async(f, t, rows_dev, t + 2 == p.tb));
+            NF_TRY(field_pair_async(f, t, rows_dev, t + 2 == p.tb, t + 2 == p.wb, interleaved));
             t += 2;
         } else {
             StepForm form;

@@ -132,7 +132,7 @@ try {
     NF_REQUIRE(name, NF_ERR_ARG, "nf_tuning_set: null name");
     if (!strcmp(name, "batch_cellsteps_m"))
         NF_REQUIRE(value >= 0 && value <= 2047, NF_ERR_ARG, "nf_tuning_set: batch_cellsteps_m must be in [0, 2047]");
-    // batch_steps, batch_cellsteps_m, partial_step_planes, graph, pass_inner_signed, pass_k3_pairs
+    // batch_steps, batch_cellsteps_m, partial_step_planes, graph, pass_inner_signed, pass_k3_pairs, pass_inner_interleaved
     if (field_tuning_set(name, value) == NF_OK) return NF_OK;
     if (!strcmp(name, "edge_weights")) {   // K3 on the engine's planes: 1 = unique-edge entries (built by the next
                                            // nf_field_build_weights), 0 = (cell, 4 weights) records (default)

@@ -174,12 +174,18 @@ struct FluxArgs {
     unsigned long long *maxbits;  // running max as the bits of a non-negative double
     StepBatch batch;
     int signed_only = 0;      // 1: store only planes 1 (eU) and 2 (eV); launch_expand_planes derives the other four
+    // 1 (with signed_only): iV is ONE stream E of 2 * ncell doubles, E[2c] = eU[c], E[2c + 1] = eV[c], and nothing else is
+    // stored (an inner step of a per-step pass, read by the pair form of K3 only); needs flux_supports_interleaved
+    int interleaved = 0;
     // timing: when the default step runs as flux kernel + expansion, mid_event is recorded between the two launches
     hipEvent_t mid_event = nullptr;
     bool *mid_recorded = nullptr;
 };
 int launch_flux(const FluxArgs &a, hipStream_t s);
 bool flux_supports_signed_only(const FluxArgs &a);
+// the interleaved store form: the signed-only form's conditions, and a launch that the two-field kernel takes (the one-field
+// form of small launches has eU and eV in different wavefronts)
+bool flux_supports_interleaved(const FluxArgs &a);
 // planes 0 (south copies), 3 (west copies incl. the periodic wrap) and |eU|, |eV| from planes 1 and 2 (field.py:209-232)
 int launch_expand_planes(double *iV, double *absUV, long ncell, long ny, long nx, hipStream_t s);
 int tuning_set(const char *name, int value);
@@ -324,8 +330,10 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
 // two time steps of the engine's own planes through the (cell, 4 weights) records in ONE gather launch (the record stream is
 // read once for both): uvA -> row, uvB -> row + row_stride, where uvX is a step's eU plane followed by its eV plane.
 // scratch: 2 * ws.nrec doubles.  The same summation tree per step as launch_integral(planes = 2): the same bits.
+// a_interleaved / b_interleaved: that operand is K1's interleaved stream E (FluxArgs::interleaved) instead of two planes; B may
+// be interleaved only when A is.
 int launch_integral_pair(const Transects &tr, const double *uvA, const double *uvB, long ncell, long nx, double *scratch,
-                         double *row, long row_stride, hipStream_t s);
+                         double *row, long row_stride, hipStream_t s, bool a_interleaved = false, bool b_interleaved = false);
 
 // What every per-step kernel of a Field reads of one time step (K1's FluxArgs has the same fields, filled from this): the
 // fields, the grid, the levels [z0, z1) and the masking / unit settings of uo / vo.

@@ -146,12 +146,14 @@ __device__ inline void store_cells(long c0, const double *eU, const double *eV, 
 // remove an ingredient of the kernel to price it, i.e. give WRONG results on purpose) exist only in tuning builds
 // (-DNF_TUNING_BUILD, `make tuning`, tools/ab_flux.py) and are compiled out of the shipped .so.
 constexpr int kFormSignedOnly = 16;    // store only planes 1 (eU) and 2 (eV): split step and compact resident mode
+constexpr int kFormInterleaved = 32;   // signed-only as ONE interleaved (eU, eV) stream at iV, 32 B per lane and cell pair: the
+                                       // inner steps of a per-step pass, which only the pair form of K3 reads
 constexpr int kFormNestedLoads = 128;  // per-level nested load loop instead of the flat one
 constexpr int kFormTwoFills = 256;     // a second value counts as missing (missing_value != _FillValue)
 #ifdef NF_TUNING_BUILD
-constexpr int kDiagNoStores = 1, kDiagNoFix = 2, kDiagNoMax = 4, kDiagNoArc = 8, kDiagInterleaved = 32, kDiagPlainStores = 64;
+constexpr int kDiagNoStores = 1, kDiagNoFix = 2, kDiagNoMax = 4, kDiagNoArc = 8, kDiagPlainStores = 64;
 #else
-constexpr int kDiagNoStores = 0, kDiagNoFix = 0, kDiagNoMax = 0, kDiagNoArc = 0, kDiagInterleaved = 0, kDiagPlainStores = 0;
+constexpr int kDiagNoStores = 0, kDiagNoFix = 0, kDiagNoMax = 0, kDiagNoArc = 0, kDiagPlainStores = 0;
 #endif
 
 // BLOCK threads; every lane owns CH chunks of VEC cells, chunk q at tile_base + q*BLOCK*VEC + tid*VEC, so the
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(BLOCK) void k_flux(const T *__restrict__ u, const T
                                                 unsigned ntiles, int xcd_map, StepBatch sb, T fill2)
 {
 #ifndef NF_TUNING_BUILD
-    static_assert((FORM & ~(kFormSignedOnly | kFormNestedLoads | kFormTwoFills)) == 0, "diagnostic forms exist only in tuning builds");
+    static_assert((FORM & ~(kFormSignedOnly | kFormInterleaved | kFormNestedLoads | kFormTwoFills)) == 0, "diagnostic forms exist only in tuning builds");
 #endif
     const unsigned tile = xcd_map ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
     if (sb.zr) {  // several time steps in one launch (small grids are launch-bound): blockIdx.y is the step
@@ -261,7 +263,7 @@ __global__ __launch_bounds__(BLOCK) void k_flux(const T *__restrict__ u, const T
                     }
                     tmax = fmax(tmax, fmax(fabs(eU[k]), fabs(eV[k])));
                 }
-                if (FORM & kDiagInterleaved) {  // diagnostic: ONE interleaved (eU,eV) stream, 32 B per lane
+                if (FORM & kFormInterleaved) {  // ONE interleaved (eU, eV) stream: iV is E, a 16-byte store per cell
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) store2<true>(iV + 2 * (c0 + k), eU[k], eV[k], true);
                 } else if (FORM & kFormSignedOnly) {  // only the two signed planes (the rest comes from k_expand_planes)
@@ -550,17 +552,31 @@ static int launch_flux_field(const FluxArgs &a, hipStream_t s)
 // Store form of the vector path (nf_tuning_set("flux_variant")): 0 = the per-dtype default, 5 = the other
 // one; same bits either way (tests/test_gpu_configs.py).  Any other number runs the default kernel in the shipped library;
 // the measured alternatives of the load loop exist only in the tuning build (`make tuning`), where the same test checks them.
+// few wavefronts (one time step of a mid-size or small grid): one field per wavefront
+static bool takes_field_form(const FluxArgs &a, int vec)
+{
+    if ((a.batch.zr ? 0 : g_variant) != 0) return false;
+    const long waves = (a.ncell / vec + kWave - 1) / kWave;
+    return g_field_split < 0 ? (!a.batch.zr && waves < kFieldSplitWaves) : g_field_split != 0;
+}
+
 template <typename T, int VEC>
 static int launch_flux_v(const FluxArgs &a, hipStream_t s)
 {
     const int variant = a.batch.zr ? 0 : g_variant;  // the multi-step launch exists for the default kernel only
-    if (variant == 0) {   // few wavefronts (one time step of a mid-size or small grid): one field per wavefront
-        const long waves = (a.ncell / VEC + kWave - 1) / kWave;
-        const bool split = g_field_split < 0 ? (!a.batch.zr && waves < kFieldSplitWaves) : g_field_split != 0;
-        if (split) return launch_flux_field<T, VEC>(a, s);
-    }
     // a second missing value (compared in the file's dtype, like the first): the default kernels with one more compare
     const bool two = (T)a.fill2 == (T)a.fill2 && !((T)a.fill2 == (T)a.fill);
+    if (a.interleaved) {  // an inner step of a per-step pass: the signed-only kernel with the interleaved store
+        if constexpr (VEC > 1) {
+            NF_REQUIRE(a.signed_only && !a.batch.zr && !takes_field_form(a, VEC), NF_ERR_STATE,
+                       "flux: the interleaved form is a signed-only step of the two-field kernel");
+            constexpr int kLevels = sizeof(T) == 8 ? 10 : 8;   // same batches as the signed-only form
+            if (two) return launch_flux_t<T, VEC, kLevels, true, 256, 1, kFormSignedOnly | kFormInterleaved | kFormTwoFills>(a, s);
+            return launch_flux_t<T, VEC, kLevels, true, 256, 1, kFormSignedOnly | kFormInterleaved>(a, s);
+        }
+        NF_REQUIRE(false, NF_ERR_STATE, "flux: the interleaved form needs 16-byte aligned fields and an even cell count");
+    }
+    if (takes_field_form(a, VEC)) return launch_flux_field<T, VEC>(a, s);
     if (a.signed_only) {  // compact resident mode: the caller expands on demand
         NF_REQUIRE(VEC > 1 && !a.batch.zr, NF_ERR_STATE, "flux: the compact mode needs 16-byte aligned fields, an even cell count and one step per launch");
         if (two) return launch_flux_t<T, VEC, (sizeof(T) == 8 ? 10 : 8), true, 256, 1, kFormSignedOnly | kFormTwoFills>(a, s);
@@ -595,7 +611,7 @@ static int launch_flux_v(const FluxArgs &a, hipStream_t s)
         // diagnostic builds (WRONG RESULTS on purpose) that price one ingredient each
         case 21: return launch_flux_t<T, VEC, 10, true, 256, 1, kDiagNoStores>(a, s);     // no stores
         case 28: return launch_flux_t<T, VEC, 10, true, 256, 1, kFormSignedOnly>(a, s);   // only the two signed planes, no expansion
-        case 29: return launch_flux_t<T, VEC, 10, true, 256, 1, kDiagInterleaved>(a, s);  // one interleaved (eU,eV) stream
+        case 29: return launch_flux_t<T, VEC, 10, true, 256, 1, kFormInterleaved>(a, s);  // one interleaved (eU,eV) stream over the planes
         case 45: return launch_flux_ww<T, VEC, 2, 2>(a, s);                        // writer-wave, no stores
         case 6: {  // the nested per-level load loop with the split store form: the defaults before the flat loop
             const int rc = launch_flux_t<T, VEC, (sizeof(T) == 8 ? 10 : 8), true, 256, 1, kFormSignedOnly | kFormNestedLoads>(a, s);
@@ -628,6 +644,11 @@ bool flux_supports_signed_only(const FluxArgs &a)
 {
     const bool al16 = ((uintptr_t)a.u % 16 == 0) && ((uintptr_t)a.v % 16 == 0);
     return al16 && !a.batch.zr && a.ncell % (a.dtype == NF_F32 ? 4 : 2) == 0;
+}
+
+bool flux_supports_interleaved(const FluxArgs &a)
+{
+    return flux_supports_signed_only(a) && !takes_field_form(a, a.dtype == NF_F32 ? 4 : 2);
 }
 
 int launch_flux(const FluxArgs &a, hipStream_t s)

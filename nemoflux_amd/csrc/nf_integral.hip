@@ -65,6 +65,15 @@ __device__ inline Slots signed_plane_slots(const double *__restrict__ eU, long n
     return Slots{eU[c], eV[c], nb.south ? eV[nb.cs] : 0.0, eU[nb.cw]};
 }
 
+// the same slot values from K1's interleaved stream E, E[2c] = eU[c], E[2c + 1] = eV[c]: east and north are ONE 16-byte load,
+// the west value sits in the same 64-byte sector three times out of four, and the south value is in the sector that the
+// record one row below pulls for its own cell -- three loads per record instead of four
+__device__ inline Slots interleaved_slots(const double *__restrict__ E, long c, const Neighbours &nb)
+{
+    const dvec2 ec = reinterpret_cast<const dvec2 *>(E)[c];
+    return Slots{ec.x, ec.y, nb.south ? E[2 * nb.cs + 1] : 0.0, E[2 * nb.cw]};
+}
+
 // The wavefront segmented scan keyed by the segment id (key -1: a lane without a record), 6 shuffle steps.  seg_scan_take: the
 // lane o below is in the same run -- it depends on the keys only, so it is formed once per step for any number of values;
 // seg_scan_step adds the values from o below where it holds; seg_run_end: record k is the last of its run inside the wave.
@@ -254,7 +263,9 @@ __global__ __launch_bounds__(kBlock) void k_gather_segscan(const int *__restrict
 }
 
 // Stage A for TWO time steps of the engine's own planes at once (the per-step pass takes its whole steps in pairs): the record
-// is read once and both steps' sums go through seg_scan side by side.  uvA / uvB: a step's [eU | eV]; runsum: 2 * n doubles.
+// is read once and both steps' sums go through seg_scan side by side.  uvA / uvB: a step's [eU | eV], or (A_IL / B_IL) its
+// interleaved stream; runsum: 2 * n doubles.  <false, false> is the kernel as it was before the interleaved form existed.
+template <bool A_IL, bool B_IL>
 __global__ __launch_bounds__(kBlock) void k_gather_segscan_pair(const int *__restrict__ cell, const double *__restrict__ w4,
                                                                 const int *__restrict__ seg, long n,
                                                                 const double *__restrict__ uvA,
@@ -267,8 +278,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_segscan_pair(const int *__res
     if (k < n) {
         const Record r = load_record(cell, w4, k);
         const Neighbours nb = neighbours(r.c, nx);
-        val[0] = weighted_sum(r, signed_plane_slots(uvA, ncell, r.c, nb));
-        val[1] = weighted_sum(r, signed_plane_slots(uvB, ncell, r.c, nb));
+        val[0] = weighted_sum(r, A_IL ? interleaved_slots(uvA, r.c, nb) : signed_plane_slots(uvA, ncell, r.c, nb));
+        val[1] = weighted_sum(r, B_IL ? interleaved_slots(uvB, r.c, nb) : signed_plane_slots(uvB, ncell, r.c, nb));
         key = load_key(seg, k);
     }
     if (seg_scan(val, key, k, n)) {
@@ -388,12 +399,16 @@ int launch_integral(const WeightSet &ws, const double *data, long ncell, int pla
 }
 
 int launch_integral_pair(const Transects &tr, const double *uvA, const double *uvB, long ncell, long nx, double *scratch,
-                         double *row, long row_stride, hipStream_t s)
+                         double *row, long row_stride, hipStream_t s, bool a_interleaved, bool b_interleaved)
 {
     const WeightSet &ws = *tr.ws;
-    if (ws.nrec > 0)
-        hipLaunchKernelGGL(k_gather_segscan_pair, record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(),
-                           ws.seg.get(), ws.nrec, uvA, uvB, ncell, (unsigned)(nx > 0 ? nx : 1), scratch);
+    NF_REQUIRE(a_interleaved || !b_interleaved, NF_ERR_ARG, "integral: operand B is interleaved only when A is");
+    if (ws.nrec > 0) {
+        auto *kernel = b_interleaved ? k_gather_segscan_pair<true, true>
+                                     : (a_interleaved ? k_gather_segscan_pair<true, false> : k_gather_segscan_pair<false, false>);
+        hipLaunchKernelGGL(kernel, record_grid(ws), dim3(kBlock), 0, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec,
+                           uvA, uvB, ncell, (unsigned)(nx > 0 ? nx : 1), scratch);
+    }
     launch_finalize(tr, ws.seg_start.get(), ws.nrec, scratch, row, row_stride, 2, s);
     NF_HIP(hipGetLastError());
     return NF_OK;

@@ -1,4 +1,8 @@
-"""In-process A/B of WHOLE passes (K1 + K3 for every time step, as bench.py times them) between k_flux variants."""
+"""In-process A/B of WHOLE passes (K1 + K3 for every time step, as bench.py times them) between k_flux variants and knobs.
+The interleaved inner steps against the pass without them, float64 then float32:
+    python tools/ab_pass.py 0:pass_inner_interleaved=0,0:pass_inner_interleaved=1 float64
+Prints, per run, the wall time per time step over 8 rounds (the first is a warm-up), the K1 events per launch and the K3
+events per time step; the rows of every round must equal those of the first."""
 import contextlib, ctypes, io, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy, torch
@@ -27,6 +31,7 @@ rows = torch.zeros((nt, fld._rowlen), dtype=torch.float64, device='cuda')
 ref = None
 res = {k: [] for k in variants}
 k1 = {k: [] for k in variants}
+k3 = {k: [] for k in variants}
 for r in range(9):
     for k in (variants if r % 2 == 0 else variants[::-1]):
         parts = k.split(':')
@@ -44,10 +49,12 @@ for r in range(9):
         if r:
             res[k].append((time.perf_counter() - t0) / 3 / nt * 1e3)
             k1[k].append(kms / nl)
+            k3[k].append(fld.readTransectTiming() / 3 / nt)
         got = rows.cpu().numpy().copy()
         if ref is None:
             ref = got
         assert os.environ.get('AB_NOCHECK') or numpy.array_equal(ref, got), 'variants disagree'
 for k in variants:
     print(f'{k:24s}: median {statistics.median(res[k]):.4f} ms per time step (K1+K3)  min {min(res[k]):.4f} max {max(res[k]):.4f}'
-          f'   K1 events {statistics.median(k1[k]):.4f} ms')
+          f'   K1 events {statistics.median(k1[k]):.4f} ms per launch (min {min(k1[k]):.4f} max {max(k1[k]):.4f})'
+          f'   K3 events {statistics.median(k3[k]):.4f} ms per time step (min {min(k3[k]):.4f} max {max(k3[k]):.4f})')
