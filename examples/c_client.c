@@ -105,6 +105,18 @@ int main(void)
     printf("section area %.6f, mean tracer above the reference %.3f\n", area[nseg + tid], area[rowlen + nseg + tid] / area[nseg + tid]);
     free(area);
 
+    /* transports in true-depth bins, rows (nedges + 2, row_length): with e3u = e3v = 0.5 the one layer lies between the depths
+     * 0 and 0.5 at every face, so the edges 0.25 and 1 cut its flux of 180 in two halves: depth < 0.25 and 0.25 <= depth < 1 */
+    const double depth_edges[2] = {0.25, 1.0};
+    double *bins = (double *)calloc((size_t)4 * rowlen, sizeof(double));
+    CHECK(nf_field_set_cell_thickness(&fld, e3, e3, 1, NF_F64, 0, NAN));
+    CHECK(nf_field_set_depth_edges(&fld, depth_edges, 2, 0.0));
+    CHECK(nf_field_compute_depth_transport(&fld, 0, 0, bins));
+    CHECK(nf_field_set_cell_thickness(&fld, NULL, NULL, 0, NF_F64, 0, NAN));
+    const double above = bins[nseg + tid], below = bins[rowlen + nseg + tid], deeper = bins[2 * rowlen + nseg + tid];
+    printf("depth bins: %.6f above 0.25, %.6f between 0.25 and 1, %.6f below\n", above, below, deeper);
+    free(bins);
+
     /* ---- Level 1: mint's call sequence on the host array */
     Grid_t *grid = NULL;
     PolylineIntegral_t *pli = NULL;
@@ -167,7 +179,8 @@ int main(void)
     CHECK(mnt_grid_del(&grid));
     CHECK(nf_field_del(&fld));
     free(row);
-    const int ok = fabs(flux2 - 360.0) < 1e-9 && fabs(flux1 - 360.0) < 1e-9 && fabs(flux_half - 180.0) < 1e-9 && rc == NF_ERR_ARG && ncells == NY * NX &&
+    const int ok = fabs(flux2 - 360.0) < 1e-9 && fabs(flux1 - 360.0) < 1e-9 && fabs(flux_half - 180.0) < 1e-9 &&
+                   fabs(above - 90.0) < 1e-9 && fabs(below - 90.0) < 1e-9 && deeper == 0.0 && rc == NF_ERR_ARG && ncells == NY * NX &&
                    decoded == 1.0f && status == 0 && nranks == 1 && myrank == 0 && reduced[0] == 1.5 && reduced[2] == 360.0;
     printf(ok ? "C client OK\n" : "C client FAILED\n");
     return ok ? 0 : 2;

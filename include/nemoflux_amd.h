@@ -529,6 +529,38 @@ int nf_field_compute_class_remap_async(nf_field **self, long tIndex, int carry, 
 int nf_field_set_cell_thickness(nf_field **self, const void *e3u, const void *e3v, long nt_th, int dtype, int on_device,
                                 double fill_value);
 int nf_field_set_cell_thickness_missing_value(nf_field **self, double missing_value);   /* NaN = none */
+/* Transports in true-depth bins: the terms of nf_field_compute_profile (carry = 0) or of the tracer profile (carry = 1: every
+ * term times tf of the tracer of nf_field_set_tracer at its own face) binned by the DEPTH of the layer at the term's own face
+ * instead of by its level -- under partial steps, z* and terrain-following coordinates a level is not a depth.
+ * Depth edges e[0] < ... < e[n-1], 2 <= n <= 1025, all finite, and a finite surface value `top` (the depth of the upper
+ * interface of level 0).  They are a set of their own: the class edges and the joint edges are not touched.
+ * For one weight slot of one record (one face) at time step t the interface depths run over ALL levels of the array:
+ *   D_0 = top,   D_{z+1} = D_z + h_z   (one float64 addition per level, z ascending from 0)
+ *   h_z = fixth(e3) at the slot's own face while a cell thickness is set (east e3u[c], north e3v[c], south e3v of the south
+ *         cell, west e3u of the west cell; t' as in nf_field_set_cell_thickness), else thickness[z].
+ * The term t = w * d of the slot at level z -- d as in nf_field_compute_profile: the thickness at the face, the Sverdrup scale
+ * and the south rule included; times tf with carry = 1 -- is spread uniformly in depth over [D_z, D_{z+1}]:
+ *   D_z, D_{z+1} or D_{z+1} - D_z not finite: whole to row n + 1.  Otherwise lo = min, hi = max of the two and
+ *   row(x) = the number of edges <= x;  lo == hi (a zero or missing thickness: the term is +-0): whole to row(lo);  else
+ *   every row j from row(lo) to row(hi) gets t * ((right - left) / (hi - lo)), left = lo in row(lo), else e[j-1];
+ *   right = hi in row(hi), else e[j]; nothing where right == left.
+ * Row 0: depth < e[0]; row k: e[k-1] <= depth < e[k]; row n: depth >= e[n-1]; row n + 1 stays exactly +0.0 unless an
+ * interface depth is not finite.  Per lane the additions run level-ascending, then in slot order (south, east, north, west),
+ * then row-ascending, into accumulators that start at +0.0; windows ("class_window" knob) and reduction as in the class
+ * forms: no atomics, bitwise reproducible, independent of the window.  The fractions of a term add up to 1 up to rounding, so
+ * the rows add up to the sum over z of the profile rows; with the per-level thickness and edges D_1 .. D_{nz-1} rows
+ * 0 .. nz-1 are the profile rows bit for bit.  rows (n + 2, row_length), each row [segments | transects], written whole.
+ * Under a slab range the terms come from the owned levels only (a step this rank does not touch gives exact zeros) but the
+ * running sum still starts at level 0: the thickness of the levels above the owned ones is read too -- in HBM in place; a
+ * host-resident time-varying cell thickness is staged for the levels [0, z1) of the step -- so the ranks' rows add up to the
+ * unsharded ones up to rounding.  Host-resident uo / vo and tracer are staged per step, owned levels only.
+ * NF_ERR_ARG: a null argument, bad edges, a `top` that is not finite, carry other than 0 or 1 -- decided before a device is
+ * needed.  NF_ERR_STATE: compute before set_depth_edges, carry = 1 before set_tracer, and the stale static cell thickness of
+ * nf_field_set_cell_thickness.  The calls change neither the resident planes, |.| arrays, running max, last row, tracer
+ * planes, class or joint state nor a captured pass. */
+int nf_field_set_depth_edges(nf_field **self, const double *edges, int nedges, double top);
+int nf_field_compute_depth_transport(nf_field **self, long tIndex, int carry, double *rows_host);        /* (nedges+2, row_length) */
+int nf_field_compute_depth_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev);   /* HBM, field's stream */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

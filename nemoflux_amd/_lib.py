@@ -153,6 +153,9 @@ _sig('nf_field_compute_class_tracer_transport', [_pp, ctypes.c_long, c_double_p]
 _sig('nf_field_compute_class_tracer_transport_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_compute_class_remap', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
 _sig('nf_field_compute_class_remap_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
+_sig('nf_field_set_depth_edges', [_pp, c_double_p, ctypes.c_int, ctypes.c_double])
+_sig('nf_field_compute_depth_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
+_sig('nf_field_compute_depth_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_read_step', [_pp, c_double_p, c_double_p, c_double_p, c_double_p])
 _sig('nf_field_reset_max', [_pp])
 _sig('nf_field_get_arclengths', [_pp, c_double_p])

@@ -206,6 +206,10 @@ struct nf_field {
     // first use, dropped with the weights)
     EdgeSet class_edges;
     DevArray<double> class_scratch;
+    // transports in depth bins (nf_field_set_depth_edges): edges of their own and the depth of the upper interface of level 0;
+    // the run sums of a window go to class_scratch
+    EdgeSet depth_edges;
+    double depth_top = 0.0;
     // joint class transport (nf_field_set_joint_class_edges): state of its own, the 1-D forms do not see it.  The edges of
     // axis A then axis B in one set.  The term table (40 bytes per record and
     // owned level), the block flags and the run sums of one window are allocated on first use, grown when the records, the
@@ -813,6 +817,35 @@ static int field_class_remap_step_async(nf_field *f, long t, double *rows_dev, b
     a.rows = rows_dev;
     a.remap_nz = (int)f->nz;
     return launch_class_remap(a, f->stream);
+}
+
+// Transports in depth bins of step t on the field's stream (nf_field_compute_depth_transport): rows_dev (nedges + 2,
+// row_length), written whole.  Terms of the owned levels only, exact zeros for a step this rank does not touch; the interface
+// depths are summed from level 0, so a cell thickness is read -- and a host-resident time-varying one staged -- for the levels
+// [0, z1) of the step.  Reads the raw fields, the tracer (carry), the thickness and the records; the resident planes, |.|
+// arrays, running max, last row, tracer planes, class / joint rows, version and a captured pass stay as they are.
+static int field_depth_step_async(nf_field *f, long t, bool carry, double *rows_dev)
+{
+    const int nedges = (int)f->depth_edges.host.size();
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_depth_transport", t, carry ? 1 : 0, rows_dev, (size_t)nedges + 2, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    NF_TRY(f->depth_edges.upload((size_t)kMaxClassEdges, f->stream));
+    const int window = g_class_window;
+    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
+    DepthArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    if (carry) NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
+    NF_TRY(field_cell_thick(f, t, Levels{0, lv.z1}, &a.th));
+    a.edges = f->depth_edges.dev.get();
+    a.nedges = nedges;
+    a.top = f->depth_top;
+    a.window = window;
+    a.tr = field_transects(f);
+    a.scratch = f->class_scratch.get();
+    a.scratch_len = f->class_scratch.size();
+    a.rows = rows_dev;
+    return launch_depth_transport(a, f->stream);
 }
 
 // the calls of the joint class transport need both tracers and the joint edges: checked before a device is needed
@@ -1697,6 +1730,50 @@ try {
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_remap_async"));
     NF_NEED_DEVICE();
     return field_class_remap_step_async(f, tIndex, rows_dev, carry != 0);
+}
+NF_API_CATCH
+
+int nf_field_set_depth_edges(nf_field **self, const double *edges, int nedges, double top)
+try {
+    NF_REQUIRE(self && *self && edges, NF_ERR_ARG, "nf_field_set_depth_edges: null argument");
+    NF_TRY(class_edges_check("nf_field_set_depth_edges: ", edges, nedges));
+    NF_REQUIRE(std::isfinite(top), NF_ERR_ARG, "nf_field_set_depth_edges: top must be a finite number");
+    nf_field *f = *self;
+    f->depth_edges.host.assign(edges, edges + nedges);
+    f->depth_edges.stale = true;
+    f->depth_top = top;
+    return NF_OK;
+}
+NF_API_CATCH
+
+// the checks of the two depth calls that need no device: arguments, then the depth edges and the tracer of the carried form
+static int field_depth_args(nf_field **self, int carry, const void *rows, const char *what)
+{
+    const std::string w(what);
+    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
+    NF_REQUIRE(!(*self)->depth_edges.host.empty(), NF_ERR_STATE, w + ": set_depth_edges first");
+    NF_REQUIRE(!carry || (*self)->tau.p[0], NF_ERR_STATE, w + ": set_tracer first");
+    return field_ready(*self, what, true);
+}
+
+int nf_field_compute_depth_transport(nf_field **self, long tIndex, int carry, double *rows_host)
+try {
+    NF_TRY(field_depth_args(self, carry, rows_host, "nf_field_compute_depth_transport"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    const size_t n = (f->depth_edges.host.size() + 2) * (size_t)field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_depth_step_async(f, tIndex, carry != 0, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_depth_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
+try {
+    NF_TRY(field_depth_args(self, carry, rows_dev, "nf_field_compute_depth_transport_async"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    return field_depth_step_async(f, tIndex, carry != 0, rows_dev);
 }
 NF_API_CATCH
 

@@ -566,6 +566,28 @@ int launch_class_transport(const ClassArgs &a, hipStream_t s);
 // terms, each spread over the classes between the class field's values at the layer's two interfaces (k_class_remap_segscan)
 int launch_class_remap(const ClassArgs &a, hipStream_t s);
 
+// Transports in true-depth bins (nf_field_compute_depth_transport, nf_integral.hip; the contract is in nemoflux_amd.h): rows
+// 0 .. nedges+1 of one time step -- row 0: depth < e[0]; row k: e[k-1] <= depth < e[k]; row nedges: depth >= e[nedges-1];
+// row nedges+1: terms of a face whose interface depth is not finite.  Each per-level term of the profile kernel is spread
+// uniformly in depth over [D_z, D_z+1], the running sum from `top` of the thicknesses of its own face over ALL levels of the
+// array from level 0 on: th.e3u set: fixth(e3) at the slot's face (level_th), read for the levels [0, in.z1) of the step; else
+// in.thickness[z].  Terms come from the owned levels [in.z0, in.z1) only.  t.tau set: the carried form (the terms of the tracer
+// profile); the two combine.  The rows are built `window` at a time: scratch holds ws.nrec * window run sums.
+struct DepthArgs {
+    StepInput in;
+    const double *edges = nullptr;   // device, nedges
+    int nedges = 0;
+    double top = 0.0;            // D_0, the depth of the upper interface of level 0
+    int window = 0;              // rows per pass over the fields, 1 .. kClassWindowMax
+    Transects tr;
+    double *scratch = nullptr;
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // (nedges + 2, row_length)
+    TracerIn t;                  // the carried tracer; t.tau == nullptr: volume form
+    CellThick th;
+};
+int launch_depth_transport(const DepthArgs &a, hipStream_t s);
+
 // Transport in JOINT classes of two tracers (nf_field_compute_joint_class_transport, nf_integral.hip): axis A is the tracer
 // (edges ea, na), axis B the class tracer (edges eb, nb); joint row ra * (nb + 2) + rb, ra / rb the 1-D rows of the face's
 // raw value of A / B.  Stage 1 gathers once and writes, per (record, owned level), the four weighted slot terms and their

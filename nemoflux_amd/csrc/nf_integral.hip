@@ -1353,6 +1353,202 @@ int launch_class_remap(const ClassArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "class remap: dtype must be NF_F64 or NF_F32");
 }
 
+// ---- transports in true-depth bins: the terms of the profile, each spread over the depth of its layer at its own face ------
+// k_class_remap_segscan with the interface values of another rule: the running sum, from `surface` at level 0, of the
+// thicknesses of the slot's own face -- level_th of the gathered e3u / e3v (ThickIn<T> among the trailing arguments: four
+// running depths per lane) or thickness[z] (one) -- one float64 addition per level.  A term of level z is spread uniformly over
+// [D_z, D_z+1]: whole to row nedges + 1 where either or their difference is not finite, whole to class_row(lo) where lo == hi,
+// else row j gets  t * ((right - left) / (hi - lo)),  the remap kernel's share rule.  Per lane the adds run level-ascending,
+// then in slot order, then row-ascending; a term's row loop is clipped to the window first.  The terms are k_gross_segscan's:
+// level_slots_tf with the thickness at the face, times the carried tracer at the face with TauIn<T> among the trailing
+// arguments.  Levels [0, z0) of a partial slab only move the depths: with per-cell thicknesses their four thickness gathers per
+// level are issued kDepthLevels levels at a time, nothing else is read.  Owned levels go kDepthLevels at a time too, all
+// gathers of a batch (4 per level, + 4 with per-cell thicknesses, + 5 with a carried tracer) issued before the first is used.
+// LDS, scan and stores: k_class_segscan's.
+constexpr int kDepthLevels = 4;
+
+// where a term goes: rows jlo .. jhi of [lo, hi], or (jhi < 0) whole to row jlo
+struct DepthSpan {
+    double lo, hi;
+    int jlo, jhi;
+};
+
+template <typename T, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_depth_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                          const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                          const T *__restrict__ v, long ncell, unsigned nx, int z0, int z1,
+                                                          const double *__restrict__ thickness,
+                                                          const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                          T fill, T fill2, int two, double scale, int sverdrup,
+                                                          const double *__restrict__ edges, int nedges, int top, double surface,
+                                                          int r0, int nwin, double *__restrict__ runsum, TI... extra)
+{
+    constexpr bool TR = (std::is_same<TI, TauIn<T>>::value || ...);
+    constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
+    constexpr int DL = kDepthLevels;
+    const TauIn<T> ti = tau_in<T>(extra...);
+    const ThickIn<T> ct = thick_arg<T>(extra...);
+    extern __shared__ double class_lds[];
+    double *e = class_lds;
+    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
+    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
+    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
+    __syncthreads();   // the edges; every lane touches only its own accumulators
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    int key = -1;
+    if (k < n) {   // 0 <= z0 < z1: the launcher's
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const auto nb = step_neighbours<TR>(r.c, nx, ncell, ti.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        const int rend = r0 + nwin - 1;
+        auto span = [&](double a, double b) {
+            if (!(__builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(b - a))) return DepthSpan{0.0, 0.0, nedges + 1, -1};
+            const double lo = a < b ? a : b, hi = a < b ? b : a;
+            const int jlo = class_row(true, lo, e, nedges, top);
+            if (lo == hi) return DepthSpan{lo, hi, jlo, -1};
+            return DepthSpan{lo, hi, jlo, class_row(true, hi, e, nedges, top)};
+        };
+        auto put = [&](const DepthSpan &p, double t) {
+            if (p.jhi < 0) {
+                const int q = p.jlo - r0;
+                if (q >= 0 && q < nwin) acc[q * kBlock] += t;
+                return;
+            }
+            const double width = p.hi - p.lo;
+            const int ja = p.jlo > r0 ? p.jlo : r0, jb = p.jhi < rend ? p.jhi : rend;
+            for (int j = ja; j <= jb; ++j) {
+                const double left = j == p.jlo ? p.lo : e[j - 1], right = j == p.jhi ? p.hi : e[j];
+                if (right != left) acc[(j - r0) * kBlock] += t * ((right - left) / width);
+            }
+        };
+        SlotTh D = slot_th(surface);   // the depth of the upper interface of the next level at the four faces
+        auto below = [](const SlotTh &d, const SlotTh &th) { return SlotTh{d.e + th.e, d.n + th.n, d.s + th.s, d.w + th.w}; };
+        for (int z = 0; z < z0; z += DL) {   // above the owned levels: the depths move, no term
+            const int nlev = z0 - z < DL ? z0 - z : DL;
+            if constexpr (CT) {
+                LevelUV<T> e3[DL];
+#pragma unroll
+                for (int l = 0; l < DL; ++l)
+                    if (l < nlev) e3[l] = load_level_e3(ct, (long)(z + l) * ncell, r.c, nb);
+#pragma unroll
+                for (int l = 0; l < DL; ++l)
+                    if (l < nlev) D = below(D, level_th(e3[l], ct));
+            } else {
+                for (int l = 0; l < nlev; ++l) D = below(D, slot_th(thickness[z + l]));
+            }
+        }
+        for (int z = z0; z < z1; z += DL) {
+            const int nlev = z1 - z < DL ? z1 - z : DL;
+            LevelUV<T> x[DL];
+            LevelTau<T> tt[TR ? DL : 1];
+            LevelUV<T> e3[CT ? DL : 1];
+#pragma unroll
+            for (int l = 0; l < DL; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
+                    if constexpr (TR) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < DL; ++l)
+                if (l < nlev) {
+                    FaceTf tf{};
+                    if constexpr (TR) tf = level_tf(tt[l], nb, ti);
+                    SlotTh th;
+                    if constexpr (CT)
+                        th = level_th(e3[l], ct);
+                    else
+                        th = slot_th(thickness[z + l]);
+                    const Slots d = level_slots_tf<T, TR>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, tf);
+                    const SlotTh Dn = below(D, th);
+                    if constexpr (CT) {
+                        if (nb.south) put(span(D.s, Dn.s), r.wa.x * d.s);
+                        put(span(D.e, Dn.e), r.wa.y * d.e);
+                        put(span(D.n, Dn.n), r.wb.x * d.n);
+                        put(span(D.w, Dn.w), r.wb.y * d.w);
+                    } else {   // one depth for the four faces: one span
+                        const DepthSpan p = span(D.e, Dn.e);
+                        if (nb.south) put(p, r.wa.x * d.s);
+                        put(p, r.wa.y * d.e);
+                        put(p, r.wb.x * d.n);
+                        put(p, r.wb.y * d.w);
+                    }
+                    D = Dn;
+                }
+        }
+    }
+    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
+#pragma unroll
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
+        if (seg_scan_take(key, lane, o)) take |= 1u << b;
+    const bool store = seg_run_end(key, lane, k, n);
+    for (int r = 0; r < nwin; ++r) {
+        double val[1] = {k < n ? acc[r * kBlock] : 0.0};
+#pragma unroll
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
+        if (store) runsum[(long)r * n + k] = val[0];
+    }
+}
+
+// launch_class_remap_t's loop over the windows; the trailing arguments choose the form as in launch_gross_t
+template <typename T, typename... TI>
+static int launch_depth_t(const DepthArgs &a, hipStream_t s, TI... extra)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    int top = 1;
+    while (2 * top <= a.nedges) top *= 2;
+    const int nrows = a.nedges + 2;
+    for (int r0 = 0; r0 < nrows; r0 += a.window) {
+        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
+        const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
+        if (ws.nrec > 0) {
+            if (lds > 65536)
+                NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_depth_segscan<T, TI...>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((k_depth_segscan<T, TI...>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
+                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale,
+                               in.sverdrup, a.edges, a.nedges, top, a.top, r0, nwin, a.scratch, extra...);
+        }
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
+                        (unsigned)nwin, s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+// the four forms of one dtype: volume or carried tracer, each with the scalar or the per-cell thicknesses
+template <typename T>
+static int launch_depth_form(const DepthArgs &a, hipStream_t s)
+{
+    const TauIn<T> ti = tau_of<T>(a.t);
+    if (a.t.tau && a.th.e3u) return launch_depth_t<T>(a, s, ti, thick_in<T>(a.th));
+    if (a.t.tau) return launch_depth_t<T>(a, s, ti);
+    if (a.th.e3u) return launch_depth_t<T>(a, s, thick_in<T>(a.th));
+    return launch_depth_t<T>(a, s);
+}
+
+int launch_depth_transport(const DepthArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "depth transport: bad depth edges");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "depth transport: bad window");
+    NF_TRY(check_raw_step("depth transport", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "depth transport: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "depth transport: null argument");
+    NF_REQUIRE(in.z0 < in.z1, NF_ERR_ARG, "depth transport: bad levels");
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (in.dtype == NF_F64) return launch_depth_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_depth_form<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "depth transport: dtype must be NF_F64 or NF_F32");
+}
+
 // ---- transport in joint classes of two tracers: gather once (k_joint_terms), bin many times (k_joint_bin) -------------
 // The terms and the accumulation are k_class_segscan's: per owned level (z ascending) the four slot terms of level_slots_tf
 // times their weights, each added in slot order (south, east, north, west) to the lane's accumulator of its row, then

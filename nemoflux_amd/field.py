@@ -1225,7 +1225,7 @@ class Field(object):
         (a missing velocity counts as 0, as in every flux kernel, so the volume flux of the mean state is the mean of the
         volume fluxes); a value missing at every step is the new Field's fill, the source's first marker as its dtype holds it
         (NaN without one).  A tracer of setTracer / setClassTracer: the mean of its present values, set on the new Field with
-        the same reference and wrapX; the class edges are carried over.  A static cell thickness is carried over as float64;
+        the same reference and wrapX; the class edges and the depth edges are carried over.  A static cell thickness is carried over as float64;
         a sharded Field (slab_range) raises, and so does a time-varying cell thickness unless thicknessWeighted=True;
         a Field that holds a Sigma (nemoflux_amd.eos) raises too.  The sums
         are float64, left to right in step order (nf_time_mean), wherever the arrays live: HBM (one pass), host (uploaded in
@@ -1275,6 +1275,8 @@ class Field(object):
             mean.setClassEdges(self._class_edges)
         if getattr(self, '_joint_edges', None) is not None:
             mean.setJointClassEdges(*self._joint_edges)
+        if getattr(self, '_depth_edges', None) is not None:
+            mean.setDepthEdges(*self._depth_edges)
         if weighted:
             mean.setCellThickness(hu, hv)       # the mean thicknesses: static, float64, in HBM, no markers
         elif e3 is not None:
@@ -1407,6 +1409,45 @@ class Field(object):
         else:
             rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
             check(lib.nf_field_compute_class_remap(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        return self._split_rows(rows)
+
+    def setDepthEdges(self, edges, top=0.0):
+        """Depth edges e[0] < ... < e[n-1] (2 <= n <= 1025, finite; the units of the thicknesses) for computeDepthTransport,
+        and `top`, the depth of the upper interface of level 0 (finite).  A set of its own: setClassEdges and
+        setJointClassEdges do not see it."""
+        e = numpy.array(edges, dtype=numpy.float64).reshape(-1)
+        check(lib.nf_field_set_depth_edges(ctypes.byref(self._h), _lib.dptr(e), int(e.size), float(top)))
+        self._depth_edges = (e, float(top))
+
+    def computeDepthTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Transport of time step tIndex in true-depth bins (setDepthEdges first): (nedges+2, ntransect) totals and
+        (nedges+2, nseg) per-segment sums.  Row 0: depth < e[0]; row k: e[k-1] <= depth < e[k]; row nedges: depth >=
+        e[nedges-1]; row nedges+1: terms of a face whose interface depth is not finite (exactly +0.0 otherwise).  Every
+        per-level term of computeFluxProfile (carry=True, setTracer first: of computeTracerProfile -- and with a cell
+        thickness, which that call refuses, the same term with the thickness at the face) is spread uniformly in depth over
+        the layer at its own face, [D_z, D_z+1] with D_0 = top and D_z+1 = D_z + h_z: h_z is the cell thickness at the face
+        when one is set (setCellThickness: partial steps, z*, terrain-following levels), else thickness[z]; every bin gets
+        the share of the layer that lies in it.  The rows add up to the sum over z of the profile rows (up to rounding);
+        with the per-level thickness and edges at the level interfaces they are the profile rows bit for bit.  Levels this
+        rank does not own (slab_range) contribute nothing, but the depths are summed from level 0: the thickness is read
+        above the owned levels too.  The rows go into classStreamfunction as they are: the overturning streamfunction in
+        depth.  Leaves everything else as it is.  `out`: as in computeClassTransport."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_depth_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setDepthEdges first')
+        nrows = edges[0].size + 2
+        self._stage(tIndex, prefetch_next)
+        if carry:
+            self._stage_tracer(tIndex)
+        carry = 1 if carry else 0
+        if out is not None:
+            out = self._rows_out(out, nrows)
+            check(lib.nf_field_compute_depth_transport_async(ctypes.byref(self._h), tIndex, carry, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((nrows, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_depth_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
         return self._split_rows(rows)
 
     def computeGrossClassTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
@@ -1542,7 +1583,8 @@ class Field(object):
         """Overturning streamfunction in class space from the rows of computeClassTransport or computeClassTracerTransport,
         or from P + N of computeGrossClassTransport (the one form that takes a cell thickness)
         (totals or segments, classes first): psi[k] = rows[0] + ... + rows[k], k = 0 .. nedges-1, the transport of the faces whose class value is below
-        e[k].  Host only."""
+        e[k].  The rows of computeDepthTransport give the overturning streamfunction in depth, the transport above e[k].
+        Host only."""
         R = numpy.asarray(rows, dtype=numpy.float64)
         if R.ndim < 1 or R.shape[0] < 4:
             raise ValueError(f'classStreamfunction: need the nedges + 2 >= 4 rows of computeClassTransport, got shape {R.shape}')

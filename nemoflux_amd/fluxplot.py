@@ -18,6 +18,9 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --sigma thetao,so --classes 26,26.01,...,28 --remap linear [--carry thetao]
                                   (conservative remapping: every level's transport spread over the classes between the class
                                   field's values at the layer's two interfaces -- a smooth MOC(sigma) with many class edges)
+    ... --depth-bins 0,100,500,1000,6000 [--depth-top 0] [--tracer thetao] [--cell-thickness]
+                                  (water flow, or the transport of thetao, in true-depth bins: a level's transport is spread over
+                                  the bins its layer covers at each face -- with --cell-thickness the depths are sums of e3u / e3v)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
@@ -382,6 +385,39 @@ def checkCrossingsArgs(crossings='', **others):
                                f'every time step to its own file')
 
 
+def depthSeries(tFile, uFile, vFile, lonLatZPoints, edges, top=0.0, tracer='', tracerFile='', tracerRef=0.0, sverdrup=False,
+                cellThickness=None):
+    """(nt, nedges+2, ntransect) water flow -- or, with `tracer`, transport of that variable of tracerFile (default: the T
+    file) -- in the true-depth bins of `edges`, one Field.computeDepthTransport per time step, and the Field.  With
+    cellThickness the depth of a layer is the running sum of the cell thicknesses at its own face."""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    if tracer:
+        fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    fld.setDepthEdges(edges, top)
+    totals = numpy.array([fld.computeDepthTransport(t, carry=bool(tracer), prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, len(edges) + 2, len(lonLatZPoints)), fld
+
+
+def checkDepthBinsArgs(depthBins='', depthTop=0.0, **others):
+    """the --depth-bins option of the command line (transports in true-depth bins): it combines with --depth-top, --tracer
+    (with --tracer-file, --tracer-ref, --tracer-scale), --cell-thickness and -s alone; refused combinations raise
+    RuntimeError"""
+    if not depthBins:
+        if float(depthTop) != 0.0:
+            raise RuntimeError('ERROR: --depth-top needs --depth-bins E0,...,EN')
+        return
+    for opt, on in others.items():
+        if on:
+            raise RuntimeError(f'ERROR: --depth-bins and {opt} cannot be combined: --depth-bins writes the transport in every '
+                               f'depth bin as CSV only')
+    if not numpy.isfinite(float(depthTop)):
+        raise RuntimeError(f'ERROR: --depth-top must be a finite number, got {depthTop!r}')
+    try:
+        parseClasses(depthBins)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace('--classes', '--depth-bins'))
+
+
 def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
     """the --gross option of the command line: refused combinations raise RuntimeError"""
     if not gross:
@@ -579,8 +615,36 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
-         classArea='', crossings='', remap=''):
+         classArea='', crossings='', remap='', depthBins='', depthTop=0.0):
     sig = None
+    checkDepthBinsArgs(depthBins, depthTop, **{'--classes': classes, '--classes2': classes2, '--gross-classes': grossClasses,
+                                               '--class-area': classArea, '--crossings': crossings, '--gross': gross,
+                                               '--levels': levels, '--decompose': decompose, '--eddy': eddy, '--show': show,
+                                               '--carry': carry, '--tracer2': tracer2, '--sigma': sigma, '--zrange': zrange,
+                                               '--thickness-weighted': thicknessWeighted, '--remap': remap})
+    if depthBins:
+        checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
+        checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
+        lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
+        unit = 'Sv' if sverdrup else 'A m^2/s'
+        ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+        edges = parseClasses(depthBins)
+        totals, fld = depthSeries(tFile, uFile, vFile, lonLatZPoints, edges, float(depthTop), tracer, tracerFile,
+                                  float(tracerRef), sverdrup, ct)
+        if tracer:
+            totals = totals * float(tracerScale)
+            title = (f'# transport of {tracer} by depth bin [{tracer} x {unit}' +
+                     (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '') + ']')
+        else:
+            title = f'# water flow by depth bin [{unit}]'
+        title += ', depths from the cell thicknesses\n' if cellThickness else '\n'
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
+        lines = ['time,ztop,zbot,' + ','.join(names)]
+        lines += [f'{timeVals[t]},{lo:.15g},{hi:.15g},' + ','.join(f'{x:.15g}' for x in totals[t, k])
+                  for t in range(fld.nt) for k, (lo, hi) in enumerate(bounds)]
+        _emit(title + '\n'.join(lines) + '\n', output)
+        return totals
     if crossings:
         checkCrossingsArgs(crossings, **{'--classes': classes, '--classes2': classes2, '--gross-classes': grossClasses,
                                          '--class-area': classArea, '--gross': gross, '--levels': levels, '--decompose': decompose,
@@ -811,6 +875,14 @@ if __name__ == '__main__':
                     help='with --classes (and --carry): conservative remapping -- a level\'s transport is spread over the '
                          'classes between the class field\'s values at the layer\'s upper and lower interface (piecewise-linear '
                          'in z) instead of going whole to the class of its face: a smooth MOC(sigma) with many class edges')
+    ap.add_argument('--depth-bins', dest='depthBins', default='', metavar='E0,E1,...,EN',
+                    help='water flow in true-depth bins: one CSV line per time step and bin [-inf,E0), [E0,E1), ..., [EN,inf), '
+                         'and a last one (nan,nan) for layers without a finite depth.  A level\'s transport is spread over the '
+                         'bins that its layer covers at each face; with --cell-thickness the layer depths are the running sum '
+                         'of e3u / e3v at the face (partial steps, z*, s-coordinates).  With --tracer NAME the transport of NAME '
+                         '(--tracer-ref, --tracer-scale apply); -s applies')
+    ap.add_argument('--depth-top', dest='depthTop', type=float, default=0.0, metavar='X',
+                    help='with --depth-bins: the depth of the upper interface of the first level (default 0)')
     ap.add_argument('--tracer2', default='', metavar='NAME',
                     help='with --classes2: the second class field (e.g. so beside --tracer thetao); NAME is read from the T file')
     ap.add_argument('--tracer2-file', dest='tracer2File', default='', metavar='FILE', help='read --tracer2 from FILE instead')
