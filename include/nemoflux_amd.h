@@ -720,6 +720,42 @@ int nf_time_mean_weighted(double *accf_dev, double *acch_dev, unsigned *cnt_dev,
                           const void *thk_dev, long long thk_stride_elems, long nsteps, size_t n, int dtype, double fill,
                           double missing, double thk_fill, double thk_missing, int first, int last, long total_steps,
                           double fill_out, void *hip_stream);
+/* The two means above over selected, weighted steps: a table of nsteps steps, step j at src_dev + step_offsets[j] elements of
+ * dtype (HBM) with the weight weights[j] (step lengths: the months of an annual mean).  step_offsets and weights are HOST
+ * arrays, read before the call returns; weights = NULL: all 1.  The offsets are >= 0, in any order, and may repeat.  Per
+ * value i, the table walked strictly in order j = 0 .. nsteps - 1, everything float64, no fma, no reassociation:
+ *     x = src[step_offsets[j] + i];   x present (nf_time_mean's rule):
+ *                                     s = s + (w_j * (double)x), wp = wp + w_j, c += 1     the product rounded, then added
+ * first = 0: s, wp, c start from acc_dev / wsum_dev / cnt_dev as the previous call left them.  last = 1: acc_dev[i] becomes
+ *     NF_MEAN_OVER_STEPS    s / total_weight
+ *     NF_MEAN_OVER_PRESENT  s / wp
+ * and fill_out where c == 0.  total_weight is the caller's float64 sum of all weights of all calls, added in order; it is
+ * read by the last call only.  Any cut of a table into calls gives the bits of one call.  Unit weights (or NULL) on the offsets
+ * j * stride_elems with total_weight = total_steps give the bits of nf_time_mean (1 * x is exact, wp == c); so do weights
+ * that all equal one power of two.
+ * wsum_dev is read and written under NF_MEAN_OVER_PRESENT only; it may be NULL under NF_MEAN_OVER_STEPS or when first && last,
+ * and so may cnt_dev when first && last.  When any listed step, acc_dev, wsum_dev or cnt_dev is not 16-byte aligned the whole
+ * call takes one value per lane: the same bits.  The table travels as kernel arguments, 16 steps a launch; a longer table is
+ * a chain of launches that carries acc, cnt (and wsum) between them, 12 n (20 n) bytes each way per further launch.
+ * NF_ERR_ARG, decided before a device is needed: NULL acc_dev / src_dev / step_offsets, nsteps < 1, n == 0, a bad dtype or
+ * rule, a negative offset, a weight that is not finite and > 0, last with NF_MEAN_OVER_STEPS and a total_weight that is not
+ * finite and > 0, a NULL cnt_dev or wsum_dev where it is not allowed.  Asynchronous on hip_stream. */
+int nf_time_mean_steps(double *acc_dev, double *wsum_dev, unsigned *cnt_dev, const void *src_dev, const long long *step_offsets,
+                       const double *weights, long nsteps, size_t n, int dtype, double fill, double missing, int first, int last,
+                       int rule, double total_weight, double fill_out, void *hip_stream);
+/* nf_time_mean_weighted over selected, weighted steps: step j of the velocity at src_dev + src_offsets[j], of the thickness
+ * at thk_dev + thk_offsets[j] elements.  Per value i, the table walked strictly in order:
+ *     g = w_j * fixth(thk[thk_offsets[j] + i])    rounded
+ *     sH = sH + g                                 at every step
+ *     x = src[src_offsets[j] + i];  x present:    sF = sF + (g * (double)x), c += 1       the product rounded, then added
+ * last = 1: accf_dev[i] = c == 0 ? fill_out : (sH == 0 ? +0.0 : sF / sH), acch_dev[i] = sH / total_weight.  Everything else
+ * as for nf_time_mean_steps (there is no wsum_dev; a further launch of a chain carries 28 n bytes each way); unit weights on
+ * the offsets j * stride give the bits of nf_time_mean_weighted. */
+int nf_time_mean_weighted_steps(double *accf_dev, double *acch_dev, unsigned *cnt_dev, const void *src_dev,
+                                const long long *src_offsets, const void *thk_dev, const long long *thk_offsets,
+                                const double *weights, long nsteps, size_t n, int dtype, double fill, double missing,
+                                double thk_fill, double thk_missing, int first, int last, double total_weight, double fill_out,
+                                void *hip_stream);
 
 /* Potential density anomaly sigma_pref(theta, S) = rho(S, T_pref, pref) - 1000 in kg m-3 by the UNESCO EOS-80 equation of state,
  * value by value over n values of dtype in HBM (nf_eos.hip): theta_dev potential temperature in degC referenced to the surface,

@@ -193,6 +193,12 @@ _sig('nf_time_mean', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.
 _sig('nf_time_mean_weighted', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                ctypes.c_void_p, ctypes.c_longlong, ctypes.c_long, ctypes.c_size_t, ctypes.c_int] +
      [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_double, ctypes.c_void_p])
+_sig('nf_time_mean_steps', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_double_p,   # host tables
+                            ctypes.c_long, ctypes.c_size_t, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                            ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p])
+_sig('nf_time_mean_weighted_steps', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p,
+                                     c_ll_p, c_double_p, ctypes.c_long, ctypes.c_size_t, ctypes.c_int] + [ctypes.c_double] * 4 +
+     [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p])
 _sig('nf_sigma_eos80', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] +   # HBM addresses
      [ctypes.c_double] * 6 + [ctypes.c_void_p])
 _sig('nf_datagen_bounds',[ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long] + [ctypes.c_double] * 6 +

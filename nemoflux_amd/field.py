@@ -490,7 +490,10 @@ class Field(object):
             # the steps that come next (fluxviz's 't' key, fluxplot's loop) are prepared on a host thread while the GPU works
             # on this one: the blocking C call below releases the GIL
             nxt = self._stager.next_after(tIndex)
-            self._stager.prefetch(nxt % self.nt if prefetch_next is None else (nxt if nxt < self.nt else -1))
+            if prefetch_next is None or isinstance(prefetch_next, bool):
+                self._stager.prefetch(nxt % self.nt if prefetch_next is None else (nxt if nxt < self.nt else -1))
+            else:       # a step index: the next step of a walk over selected steps (meanEddySplit); -1: none
+                self._stager.prefetch(int(prefetch_next))
         self._stage_cell_thickness(tIndex)
 
     def _compute(self, tIndex, readback=None, prefetch_next=None):
@@ -1139,13 +1142,111 @@ class Field(object):
             raise RuntimeError(f'ERROR: steps must be None or a half-open (t0, t1) with 0 <= t0 < t1 <= {self.nt}, got {steps}')
         return t0, t1
 
+    def _step_table(self, what, steps, select, weights):
+        """The steps a time mean visits and their weights: (list of ascending step indices, float64 weights or None for all 1,
+        the float64 sum of the weights added in order).  steps: None or a half-open (t0, t1); select: a strictly ascending
+        sequence of step indices, instead of steps; weights: one positive finite number per visited step, or 'bounds' for the
+        step lengths of the file's time bounds (TimeObj.getStepLengths)."""
+        if select is not None:
+            if steps is not None:
+                raise RuntimeError(f'ERROR: {what}: give steps or select, not both')
+            idx = [int(t) for t in select]
+            if [float(t) for t in idx] != [float(t) for t in select]:
+                raise RuntimeError(f'ERROR: {what}: select must hold whole step indices, got {list(select)}')
+            if not idx or idx[0] < 0 or idx[-1] >= self.nt or any(b <= a for a, b in zip(idx, idx[1:])):
+                raise RuntimeError(f'ERROR: {what}: select must be a strictly ascending sequence of step indices in '
+                                   f'[0, {self.nt}), got {idx}')
+        else:
+            idx = list(range(*self._step_range(steps)))
+        if weights is None:
+            return idx, None, float(len(idx))
+        if isinstance(weights, str):
+            if weights != 'bounds':
+                raise RuntimeError(f"ERROR: {what}: weights must be numbers or 'bounds', got '{weights}'")
+            lengths = getattr(self.timeObj, 'getStepLengths', lambda: None)()
+            if lengths is None or len(lengths) != self.nt:
+                name = getattr(self.timeObj, 'timeVarName', '') or 'none found'
+                raise RuntimeError(f"ERROR: {what}: weights='bounds' needs the bounds of the time variable ({name}): its "
+                                   f'`bounds` attribute must name a (nt, 2) variable of the U file')
+            w = numpy.asarray(lengths, dtype=numpy.float64)[idx]
+        else:
+            w = numpy.array(weights, dtype=numpy.float64).reshape(-1)
+            if w.size != len(idx):
+                raise RuntimeError(f'ERROR: {what}: {w.size} weights for {len(idx)} steps')
+        if not (numpy.isfinite(w).all() and (w > 0).all()):
+            raise RuntimeError(f'ERROR: {what}: every weight must be finite and > 0, got {w.tolist()}')
+        total = numpy.float64(0.0)
+        for x in w:
+            total = total + x
+        return idx, numpy.ascontiguousarray(w), float(total)
+
+    def _time_mean_walk_table(self, series, markers, table, nacc, kernel, carry_wsum):
+        """_time_mean_walk over a table (_step_table) of selected, weighted steps.  kernel(accs, wsum, cnt, ptrs, offsets,
+        weights, nsteps, n, code, fill, missing, first, last, total_weight, fill_out) makes the C call for nsteps table entries:
+        series j's steps at the element offsets offsets[j] (int64) from the HBM address ptrs[j].  HBM: one call on the offsets
+        select * n.  Host: groups of selected steps packed into the staging buffer.  File-backed: one selected step at a time;
+        a step that is not selected is never read.  carry_wsum: the kernel carries a sum of weights (NF_MEAN_OVER_PRESENT)."""
+        import torch
+        idx, w, total = table
+        dt = numpy.dtype(_native_dtype(series[0]))
+        code, size = (NF_F32 if dt == numpy.float32 else NF_F64), dt.itemsize
+        marks = [float(m) for m in markers if m == m]
+        with numpy.errstate(over='ignore'):
+            fill_out = float(dt.type(marks[0])) if marks else numpy.nan
+        fill, missing = (marks + [numpy.nan, numpy.nan])[:2]
+        n = self.nz * self.ny * self.nx
+        accs = [torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda') for _ in range(nacc)]
+        ptrs = [_lib.device_pointer(x) for x in series]
+        staged = [p is None for p in ptrs]
+
+        def run(cur, offsets, j0, k, first, last, wsum=None, cnt=None):
+            offsets = [numpy.ascontiguousarray(o, dtype=numpy.int64) for o in offsets]
+            kernel([x.data_ptr() for x in accs], None if wsum is None else wsum.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                   cur, offsets, None if w is None else w[j0:j0 + k], k, n, code, fill, missing, 1 if first else 0,
+                   1 if last else 0, total, fill_out)
+
+        everywhere = numpy.array(idx, dtype=numpy.int64) * n
+        if not any(staged):       # all in HBM: one pass, nothing carried
+            run(ptrs, [everywhere] * len(series), 0, len(idx), True, True)
+        else:
+            cnt = torch.empty(n, dtype=torch.int32, device='cuda')
+            wsum = torch.empty(n, dtype=torch.float64, device='cuda') if carry_wsum else None
+            lazy = [hasattr(x, 'read_step') for x in series]
+            group = 1 if any(lazy) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
+            bufs = [self._host_array((self.nz, self.ny, self.nx), dt) if z else None for z in lazy]
+            hosts = [_native(x).reshape(self.nt, n) if st and not z else None for x, st, z in zip(series, staged, lazy)]
+            stage = [_lib.DeviceBuffer(min(group, len(idx)) * n * size) if st else None for st in staged]
+            for j0 in range(0, len(idx), group):
+                k = min(group, len(idx) - j0)
+                cur, offsets = [], []
+                for j in range(len(series)):
+                    if not staged[j]:
+                        cur.append(ptrs[j])
+                        offsets.append(everywhere[j0:j0 + k])
+                        continue
+                    for m, t in enumerate(idx[j0:j0 + k]):      # the selected steps of this group, packed
+                        if lazy[j]:
+                            series[j].read_step(t, out=bufs[j])
+                        check(lib.nf_memcpy_h2d(stage[j].ptr + m * n * size,
+                                                bufs[j].ctypes.data if lazy[j] else hosts[j][t:t + 1].ctypes.data, n * size))
+                    cur.append(stage[j].ptr)
+                    offsets.append(numpy.arange(k, dtype=numpy.int64) * n)
+                run(cur, offsets, j0, k, j0 == 0, j0 + k == len(idx), wsum, cnt)
+                check(lib.nf_synchronize())     # the staging buffers are written again by the next group
+            for b in stage:
+                if b is not None:
+                    b.free()
+        check(lib.nf_synchronize())
+        return accs, fill_out
+
     def _time_mean_walk(self, series, markers, t0, t1, nacc, kernel):
         """The steps [t0, t1) of a list of (nt, nz, ny, nx) arrays of one dtype, each in any of its three homes (HBM, host,
         file-backed), through one of the time-mean kernels into `nacc` float64 torch CUDA tensors (1, nz, ny, nx).
         kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total_steps, fill_out) makes the C call for nsteps
         steps that begin at the HBM addresses ptrs (one per series); fill / missing: `markers` without NaN.  Returns the
         tensors and fill_out -- the first marker as the dtype of the arrays holds it, NaN without one -- which stands where
-        the value is missing at every step.  The bits do not depend on the homes or on the grouping of the steps."""
+        the value is missing at every step.  The bits do not depend on the homes or on the grouping of the steps.
+        The selected, weighted form of the walk is _time_mean_walk_table."""
         import torch
         dt = numpy.dtype(_native_dtype(series[0]))
         code, size = (NF_F32 if dt == numpy.float32 else NF_F64), dt.itemsize
@@ -1193,9 +1294,19 @@ class Field(object):
         check(lib.nf_synchronize())
         return accs, fill_out
 
-    def _time_mean_array(self, a, markers, rule, t0, t1):
+    def _time_mean_array(self, a, markers, rule, t0, t1, table=None):
         """The mean over the steps [t0, t1) of a (nt, nz, ny, nx) array in any of its three homes, by nf_time_mean: a float64
-        torch CUDA tensor (1, nz, ny, nx) and its fill (_time_mean_walk)."""
+        torch CUDA tensor (1, nz, ny, nx) and its fill (_time_mean_walk).  table (_step_table) instead of t0, t1: the mean over
+        its selected, weighted steps by nf_time_mean_steps (_time_mean_walk_table)."""
+        if table is not None:
+            def steps_kernel(accs, wsum, cnt, ptrs, offsets, w, nsteps, n, code, fill, missing, first, last, total, fill_out):
+                check(lib.nf_time_mean_steps(accs[0], wsum, cnt, ptrs[0], offsets[0].ctypes.data_as(_lib.c_ll_p),
+                                             None if w is None else _lib.dptr(w), nsteps, n, code, fill, missing, first, last,
+                                             rule, total, fill_out, None))
+
+            (acc,), fill_out = self._time_mean_walk_table([a], markers, table, 1, steps_kernel, rule == _lib.NF_MEAN_OVER_PRESENT)
+            return acc, fill_out
+
         def kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total, fill_out):
             check(lib.nf_time_mean(accs[0], cnt, ptrs[0], nsteps, n, n, code, fill, missing, first, last, rule, total, fill_out,
                                    None))
@@ -1203,13 +1314,24 @@ class Field(object):
         (acc,), fill_out = self._time_mean_walk([a], markers, t0, t1, 1, kernel)
         return acc, fill_out
 
-    def _time_mean_weighted_arrays(self, a, markers, thk, thk_markers, t0, t1):
+    def _time_mean_weighted_arrays(self, a, markers, thk, thk_markers, t0, t1, table=None):
         """The thickness-weighted mean over the steps [t0, t1) of the (nt, nz, ny, nx) velocity `a` and the mean of the
         thickness `thk` at its points, by nf_time_mean_weighted; each of the two in any of the three homes.  Returns two
-        float64 torch CUDA tensors (1, nz, ny, nx) and the fill of the first (_time_mean_walk)."""
+        float64 torch CUDA tensors (1, nz, ny, nx) and the fill of the first (_time_mean_walk).  table (_step_table) instead
+        of t0, t1: over its selected, weighted steps by nf_time_mean_weighted_steps (_time_mean_walk_table)."""
         dt = numpy.dtype(_native_dtype(a))
         if numpy.dtype(_native_dtype(thk)) != dt:
             raise RuntimeError(f'ERROR: timeMean: the cell thickness is {numpy.dtype(_native_dtype(thk)).name}, uo/vo are {dt.name}')
+        if table is not None:
+            def steps_kernel(accs, wsum, cnt, ptrs, offsets, w, nsteps, n, code, fill, missing, first, last, total, fill_out):
+                check(lib.nf_time_mean_weighted_steps(accs[0], accs[1], cnt, ptrs[0], offsets[0].ctypes.data_as(_lib.c_ll_p),
+                                                      ptrs[1], offsets[1].ctypes.data_as(_lib.c_ll_p),
+                                                      None if w is None else _lib.dptr(w), nsteps, n, code, fill, missing,
+                                                      float(thk_markers[0]), float(thk_markers[1]), first, last, total,
+                                                      fill_out, None))
+
+            (accf, acch), fill_out = self._time_mean_walk_table([a, thk], markers, table, 2, steps_kernel, False)
+            return accf, acch, fill_out
 
         def kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total, fill_out):
             check(lib.nf_time_mean_weighted(accs[0], accs[1], cnt, ptrs[0], n, ptrs[1], n, nsteps, n, code, fill, missing,
@@ -1218,7 +1340,7 @@ class Field(object):
         (accf, acch), fill_out = self._time_mean_walk([a, thk], markers, t0, t1, 2, kernel)
         return accf, acch, fill_out
 
-    def timeMean(self, steps=None, thicknessWeighted=False):
+    def timeMean(self, steps=None, thicknessWeighted=False, select=None, weights=None):
         """The mean state of the steps [t0, t1) (steps=None: all of them) as a new Field with nt = 1 and float64 fields in HBM,
         built through fromArrays from the same bounds, deptht_bounds, transects, sverdrup, periodX and cell policies: every
         diagnostic of the engine works on it unchanged.  uo / vo: sum over the steps of the present values / number of steps
@@ -1237,7 +1359,15 @@ class Field(object):
         as a static float64 cell thickness in HBM: (mean thickness) x (mean velocity) is the mean volume flux face by face,
         so the volume flux of the mean state is again the mean of the volume fluxes.  The tracers keep the plain mean of
         their present values (there is no e3t to weight them with).  With a static thickness the weights cancel: the result
-        of timeMean(steps), bit for bit."""
+        of timeMean(steps), bit for bit.
+        select: a strictly ascending sequence of step indices instead of the range `steps` (a season of every year, a
+        climatological month, everything but the spin-up); weights: one positive finite number per visited step, or 'bounds'
+        for the step lengths of the file's time bounds (months of 28 to 31 days).  The sums become sum of w_j x over the visited
+        steps in their order, divided by the sum of all weights (velocities, thicknesses) or of the weights of the present
+        values (tracers): nf_time_mean_steps / nf_time_mean_weighted_steps, one pass over the selected steps in HBM, selected
+        steps packed into the staging buffer from the host, one selected step at a time from files -- a step that is not
+        selected is never read.  select without weights over a range gives timeMean(steps) of that range, bit for bit; with
+        both None the code and the bits are those of before."""
         self._sigma_refused('timeMean')
         if self.slab_range is not None:
             raise RuntimeError('ERROR: timeMean: the mean state of a sharded Field (slab_range) is not defined here; build the '
@@ -1249,14 +1379,18 @@ class Field(object):
         if e3 is not None and e3['nt'] != 1 and not weighted:
             raise RuntimeError('ERROR: timeMean: the mean state of a time-varying cell thickness is not defined here (it would '
                                'need thickness-weighted means); set a static thickness or none')
-        t0, t1 = self._step_range(steps)
+        if select is None and weights is None:
+            (t0, t1), table = self._step_range(steps), None
+        else:
+            t0 = t1 = None
+            table = self._step_table('timeMean', steps, select, weights)
         if weighted:
             thk_markers = (e3['fill'], e3['missing'])
-            u, hu, fill = self._time_mean_weighted_arrays(self._uv[0], self._uv_markers, e3['arrays'][0], thk_markers, t0, t1)
-            v, hv, _ = self._time_mean_weighted_arrays(self._uv[1], self._uv_markers, e3['arrays'][1], thk_markers, t0, t1)
+            u, hu, fill = self._time_mean_weighted_arrays(self._uv[0], self._uv_markers, e3['arrays'][0], thk_markers, t0, t1, table)
+            v, hv, _ = self._time_mean_weighted_arrays(self._uv[1], self._uv_markers, e3['arrays'][1], thk_markers, t0, t1, table)
         else:
-            u, fill = self._time_mean_array(self._uv[0], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
-            v, _ = self._time_mean_array(self._uv[1], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1)
+            u, fill = self._time_mean_array(self._uv[0], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1, table)
+            v, _ = self._time_mean_array(self._uv[1], self._uv_markers, _lib.NF_MEAN_OVER_STEPS, t0, t1, table)
         mean = Field.fromArrays(self._bounds[0], self._bounds[1], self.bounds_depth, u, v, self._polylines, self.sverdrup,
                                 fill_value=fill, **self._build_kw)
 
@@ -1265,11 +1399,11 @@ class Field(object):
 
         tr = getattr(self, '_tracer', None)
         if tr is not None:
-            tau, tfill = self._time_mean_array(tr['keep'], (tr['fill'], tr['missing']), _lib.NF_MEAN_OVER_PRESENT, t0, t1)
+            tau, tfill = self._time_mean_array(tr['keep'], (tr['fill'], tr['missing']), _lib.NF_MEAN_OVER_PRESENT, t0, t1, table)
             mean.setTracer(tau, fill_value=none_if_nan(tfill), reference=self._tracer_reference, wrapX=self._tracer_wrapX)
         ct = getattr(self, '_class_tracer', None)
         if ct is not None:
-            sig, sfill = self._time_mean_array(ct['keep'], (ct['fill'], ct['missing']), _lib.NF_MEAN_OVER_PRESENT, t0, t1)
+            sig, sfill = self._time_mean_array(ct['keep'], (ct['fill'], ct['missing']), _lib.NF_MEAN_OVER_PRESENT, t0, t1, table)
             mean.setClassTracer(sig, fill_value=none_if_nan(sfill))
         if getattr(self, '_class_edges', None) is not None:
             mean.setClassEdges(self._class_edges)
@@ -1300,7 +1434,46 @@ class Field(object):
             a = host
         return numpy.ascontiguousarray(a, dtype=numpy.float64)
 
-    def meanEddyTracerTransport(self, steps=None, thicknessWeighted=False):
+    _SPLIT_METHODS = ('computeTracerFlux', 'computeFluxProfile', 'computeTracerProfile', 'computeClassTransport',
+                      'computeClassTracerTransport', 'computeClassRemap', 'computeDepthTransport', 'computeGrossProfile',
+                      'computeGrossClassTransport')
+
+    def meanEddySplit(self, method, steps=None, select=None, weights=None, thicknessWeighted=False, **kw):
+        """The time mean of one per-step row product split into the part of the mean state and the rest.  method: the name of
+        the product -- computeTracerFlux, computeFluxProfile, computeTracerProfile, computeClassTransport,
+        computeClassTracerTransport, computeClassRemap, computeDepthTransport, computeGrossProfile or
+        computeGrossClassTransport; kw goes to it (carry=).  steps / select / weights choose and weight the steps as in
+        timeMean.  Returns a dict: 'total' = sum of w_j rows_j over the visited steps / sum of w_j, formed on the host in float64
+        step by step in their order; 'mean' = the same product at step 0 of 'meanField' = timeMean(steps, thicknessWeighted,
+        select, weights), the transport by the mean flow of the mean tracer in the classes of the mean class field; 'eddy' =
+        total - mean, what the transients carry (how much of MOC(sigma) is eddy-induced, at which depth and in which class
+        the fluctuations carry the heat).  total, mean and eddy are (totals, segments) pairs shaped as the product returns them.
+        The mean state and the total use the same steps and weights, so the split closes: for a product that is linear in
+        (uo, vo) with everything else constant in time, eddy is rounding.  What the product refuses (a cell thickness, a
+        Sigma) it refuses here with its own words."""
+        if method not in self._SPLIT_METHODS:
+            raise RuntimeError(f'ERROR: meanEddySplit: method must be one of {", ".join(self._SPLIT_METHODS)}, got {method!r}')
+        idx, w, wtotal = self._step_table('meanEddySplit', steps, select, weights)
+        call = getattr(self, method)
+        lookahead = method != 'computeTracerFlux'      # the one product without prefetch_next
+        total = None
+        for j, t in enumerate(idx):
+            if lookahead:
+                rows = call(t, prefetch_next=idx[j + 1] if j + 1 < len(idx) else -1, **kw)
+            else:
+                rows = call(t, **kw)
+            wj = numpy.float64(1.0 if w is None else w[j])
+            terms = [wj * numpy.asarray(r, dtype=numpy.float64) for r in rows]
+            total = terms if total is None else [a + b for a, b in zip(total, terms)]
+        total = tuple(a / numpy.float64(wtotal) for a in total)
+        if select is None and weights is None:
+            meanField = self.timeMean(steps, thicknessWeighted)
+        else:
+            meanField = self.timeMean(steps, thicknessWeighted, select=select, weights=weights)
+        mean = tuple(numpy.array(r, dtype=numpy.float64) for r in getattr(meanField, method)(0, **kw))
+        return dict(total=total, mean=mean, eddy=tuple(a - b for a, b in zip(total, mean)), meanField=meanField)
+
+    def meanEddyTracerTransport(self, steps=None, thicknessWeighted=False, select=None, weights=None):
         """The mean tracer transport of the steps [t0, t1) (steps=None: all; setTracer first) split in time, for the transect
         totals: 'total' = the float64 mean over the steps of the computeTracerFlux totals; 'mean' = computeTracerFlux(0) of
         timeMean(steps), the transport of the mean tracer by the mean flow; 'eddy' = total - mean, the part <u' tau'> carried
@@ -1309,10 +1482,15 @@ class Field(object):
         is computed with the thickness of every step as before, 'mean' is the transport of the time-mean tracer by the
         time-mean VOLUME FLUX (mean thickness x thickness-weighted mean velocity), and 'eddy' is everything else -- the
         correlation of the tracer with the volume flux, which includes the tracer-thickness covariance, because there is no
-        e3t to weight the tracer mean with."""
+        e3t to weight the tracer mean with.
+        select / weights (timeMean): the steps of a strided or irregular selection and their weights (step lengths); this is
+        then meanEddySplit('computeTracerFlux', ...) reduced to the transect totals."""
         self._sigma_refused('meanEddyTracerTransport')
         if getattr(self, '_tracer', None) is None:
             raise RuntimeError('ERROR: call setTracer first')
+        if select is not None or weights is not None:
+            d = self.meanEddySplit('computeTracerFlux', steps, select, weights, thicknessWeighted)
+            return dict(total=d['total'][0], mean=d['mean'][0], eddy=d['eddy'][0], meanField=d['meanField'])
         t0, t1 = self._step_range(steps)
         if (t0, t1) == (0, self.nt):
             rows = self.computeTracerAll()[0]

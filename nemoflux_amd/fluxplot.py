@@ -25,6 +25,7 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
     ... --tracer thetao --eddy --cell-thickness --thickness-weighted   (the same for z* output: thickness-weighted mean flow)
+    ... --tracer thetao --eddy --time-weights bounds --time-select months:12,1,2   (the DJF mean, months weighted by their length)
     ... --gross [--tracer thetao] [--zrange 0,700] (inflow, outflow and net of every transect; what they carry, their mean thetao)
     ... --tracer sigma0 --tracer-file S.nc --gross-classes 26,27,28 [--carry thetao] [--cell-thickness]
                                   (inflow, outflow and net of every sigma0 class: one CSV line per time step, transect and class)
@@ -212,15 +213,62 @@ def decomposeSeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', t
 EDDY_PARTS = ('total', 'mean', 'eddy')
 
 
+def parseTimeWeights(text):
+    """--time-weights: 'bounds' (the step lengths of the file's time bounds) or W0,W1,... (one positive number per visited step)"""
+    if text.strip() == 'bounds':
+        return 'bounds'
+    try:
+        w = [float(x) for x in text.split(',')]
+    except ValueError:
+        raise RuntimeError(f"ERROR: --time-weights must be 'bounds' or W0,W1,... (numbers), got '{text}'")
+    if not w or not all(x > 0 and x < numpy.inf for x in w):
+        raise RuntimeError(f'ERROR: --time-weights: every weight must be finite and > 0, got {text}')
+    return w
+
+
+def parseTimeSelect(text):
+    """--time-select: I0,I1,... (strictly ascending step indices) as a list, or months:M1,M2,... as ('months', [M1, ...])"""
+    months = text.strip().startswith('months:')
+    try:
+        v = [int(x) for x in text.strip()[len('months:') if months else 0:].split(',')]
+    except ValueError:
+        raise RuntimeError(f"ERROR: --time-select must be I0,I1,... or months:M1,M2,... (whole numbers), got '{text}'")
+    if months:
+        if not all(1 <= m <= 12 for m in v):
+            raise RuntimeError(f'ERROR: --time-select months:M1,M2,...: months are 1 to 12, got {text}')
+        return ('months', v)
+    if v[0] < 0 or any(b <= a for a, b in zip(v, v[1:])):
+        raise RuntimeError(f'ERROR: --time-select I0,I1,...: step indices must be >= 0 and strictly ascending, got {text}')
+    return v
+
+
+def selectSteps(fld, timeSelect):
+    """the step indices of a parsed --time-select on a Field: the list itself, or the steps whose month is one of the months"""
+    if not timeSelect or timeSelect[0] != 'months':
+        return timeSelect or None
+    months = getattr(fld.timeObj, 'getMonths', lambda: None)()
+    if not months or any(m is None for m in months):
+        raise RuntimeError('ERROR: --time-select months:... needs a time variable with decodable units in the U file')
+    steps = [t for t, m in enumerate(months) if m in timeSelect[1]]
+    if not steps:
+        raise RuntimeError(f'ERROR: --time-select months:{",".join(str(m) for m in timeSelect[1])} selects no time step')
+    return steps
+
+
 def eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile='', tracerRef=0.0, sverdrup=False, cellThickness=None,
-               thicknessWeighted=False):
+               thicknessWeighted=False, timeWeights=None, timeSelect=None):
     """(3, ntransect): the mean over all time steps of the transport of the variable `tracer` of tracerFile (default: the T
     file), the transport of the time-mean tracer by the time-mean flow, and their difference, the eddy part (EDDY_PARTS;
     Field.meanEddyTracerTransport), and the Field.  thicknessWeighted: the mean flow of a time-varying cell thickness, the
-    mean thickness times the thickness-weighted mean velocity."""
+    mean thickness times the thickness-weighted mean velocity.  timeWeights / timeSelect (parseTimeWeights, parseTimeSelect):
+    the weights and the selection of the steps of the mean; the Field keeps the selected steps in _eddy_steps."""
     fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
-    d = fld.meanEddyTracerTransport(thicknessWeighted=thicknessWeighted)
+    if timeWeights or timeSelect:
+        fld._eddy_steps = selectSteps(fld, timeSelect)
+        d = fld.meanEddyTracerTransport(thicknessWeighted=thicknessWeighted, select=fld._eddy_steps, weights=timeWeights or None)
+    else:
+        d = fld.meanEddyTracerTransport(thicknessWeighted=thicknessWeighted)
     return numpy.array([d[k] for k in EDDY_PARTS]).reshape(len(EDDY_PARTS), len(lonLatZPoints)), fld
 
 
@@ -448,6 +496,19 @@ def checkThicknessWeightedArgs(thicknessWeighted=False, eddy=False, cellThicknes
                            '--tracer with the thickness-weighted mean flow of time-varying layer thicknesses (z*)')
 
 
+def checkTimeMeanArgs(timeWeights='', timeSelect='', eddy=False):
+    """the --time-weights and --time-select options of the command line: they weight and select the steps of the time mean of
+    --eddy and are refused anywhere else; a value that does not parse raises RuntimeError too"""
+    for on, opt in ((timeWeights, '--time-weights'), (timeSelect, '--time-select')):
+        if on and not eddy:
+            raise RuntimeError(f'ERROR: {opt} needs --eddy: it chooses the steps, or their weights, of the time mean that --eddy '
+                               f'splits; no other table is a time mean')
+    if timeWeights:
+        parseTimeWeights(timeWeights)
+    if timeSelect:
+        parseTimeSelect(timeSelect)
+
+
 def checkDecomposeArgs(decompose=False, tracer='', classes='', levels=False, zrange='', show=False):
     """the --decompose option of the command line: refused combinations raise RuntimeError"""
     if not decompose:
@@ -615,8 +676,9 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
-         classArea='', crossings='', remap='', depthBins='', depthTop=0.0):
+         classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect=''):
     sig = None
+    checkTimeMeanArgs(timeWeights, timeSelect, eddy)
     checkDepthBinsArgs(depthBins, depthTop, **{'--classes': classes, '--classes2': classes2, '--gross-classes': grossClasses,
                                                '--class-area': classArea, '--crossings': crossings, '--gross': gross,
                                                '--levels': levels, '--decompose': decompose, '--eddy': eddy, '--show': show,
@@ -737,12 +799,15 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         return totals
     if eddy:
         totals, fld = eddySeries(tFile, uFile, vFile, lonLatZPoints, tracer, tracerFile, float(tracerRef), sverdrup, ct,
-                                 thicknessWeighted)
+                                 thicknessWeighted, parseTimeWeights(timeWeights) if timeWeights else None,
+                                 parseTimeSelect(timeSelect) if timeSelect else None)
+        nsel = len(getattr(fld, '_eddy_steps', None) or range(fld.nt))
         totals = totals * float(tracerScale)
         unit = f'{tracer} x {unit}' + (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '')
         lines = ['part,' + ','.join(names)]
         lines += [f'{part},' + ','.join(f'{x:.15g}' for x in totals[k]) for k, part in enumerate(EDDY_PARTS)]
-        _emit(f'# mean transport of {tracer} over {fld.nt} time steps, its mean-flow and eddy parts [{unit}]\n' +
+        _emit(f'# mean transport of {tracer} over {nsel} time steps' + (', weighted' if timeWeights else '') +
+              f', its mean-flow and eddy parts [{unit}]\n' +
               '\n'.join(lines) + '\n', output)
         return totals
     if decompose:
@@ -928,6 +993,12 @@ if __name__ == '__main__':
                     help='with --tracer NAME: one CSV line per part (part,...): the mean over all time steps of the transport of '
                          'NAME, the transport of the time-mean NAME by the time-mean flow, and the eddy part, their difference '
                          '(--tracer-ref, --tracer-scale, -s apply)')
+    ap.add_argument('--time-weights', dest='timeWeights', default='', metavar='bounds|W0,W1,...',
+                    help="with --eddy: the weights of the steps of the time mean, 'bounds' for the step lengths of the time "
+                         "variable's bounds (months of 28 to 31 days) or one positive number per visited step")
+    ap.add_argument('--time-select', dest='timeSelect', default='', metavar='I0,I1,...|months:M1,M2,...',
+                    help='with --eddy: the steps of the time mean, as ascending step indices or as the months (1-12) to keep '
+                         '(months:12,1,2 is DJF of every year)')
     ap.add_argument('--cell-thickness', dest='cellThickness', action='store_true',
                     help='integrate with per-cell layer thicknesses (partial steps, z*) read from the U and V files instead of '
                          'deptht_bounds; with the plain series, --zrange, --levels (without --tracer) and --tracer NAME')

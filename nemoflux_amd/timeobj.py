@@ -8,6 +8,8 @@ variable (datagen output) get index labels instead of raising (SURVEY.md 8a quir
 import re
 from datetime import date, datetime, timedelta
 
+import numpy
+
 _UNITS = re.compile(r'^\s*(seconds|second|secs|sec|s|minutes|minute|min|hours|hour|hrs|hr|h|days|day|d)\s+since\s+'
                     r'(-?\d+)-(\d+)-(\d+)(?:[ T](\d+):(\d+):(\d+(?:\.\d*)?))?', re.I)
 _SECONDS = {'s': 1., 'm': 60., 'h': 3600., 'd': 86400.}
@@ -25,10 +27,15 @@ def _as_text(v):
 
 class TimeObj(object):
 
-    def __init__(self, values=None, units='', calendar='gregorian', name=''):
+    def __init__(self, values=None, units='', calendar='gregorian', name='', bounds=None):
         self.timeVarName = name
         self.timeVar = [] if values is None else list(values)
         self._dates = None
+        self._bounds = None
+        if bounds is not None:
+            b = numpy.asarray(bounds, dtype=numpy.float64)
+            if b.shape == (len(self.timeVar), 2):
+                self._bounds = b
         if values is not None and units:
             self._dates = [self._decode(float(x), _as_text(units), _as_text(calendar).lower()) for x in self.timeVar]
 
@@ -41,7 +48,9 @@ class TimeObj(object):
                 continue
             a = variables.get('_attrs_' + k, {})
             if _as_text(a.get('standard_name', '')) == 'time' or _as_text(a.get('long_name', '')) == 'Time axis':
-                return cls(v, a.get('units', ''), a.get('calendar', 'gregorian'), k)
+                # CF cell boundaries: the attribute `bounds` names a (nt, 2) variable in the units of the time variable
+                b = variables.get(_as_text(a['bounds']).strip().strip('\x00')) if 'bounds' in a else None
+                return cls(v, a.get('units', ''), a.get('calendar', 'gregorian'), k, bounds=b)
         return cls()
 
     @staticmethod
@@ -79,6 +88,20 @@ class TimeObj(object):
 
     def getSize(self):
         return len(self.timeVar)
+
+    def getStepLengths(self):
+        """The length of every step, bounds[:, 1] - bounds[:, 0] of the time variable's `bounds` variable, float64 in the units
+        of the time variable (the weights of a time mean over steps of unequal length); None without bounds."""
+        if self._bounds is None:
+            return None
+        return self._bounds[:, 1] - self._bounds[:, 0]
+
+    def getMonths(self):
+        """The month (1 .. 12) of every step in the file's own calendar; None where a value does not decode, and for the whole
+        axis without decodable units."""
+        if not self._dates:
+            return None
+        return [d[1] if d else None for d in self._dates]
 
     def getTimeAsDate(self, timeIndex):
         """timeobj.py:24-28 (a datetime.date); the bare index when the file has no decodable time axis."""
