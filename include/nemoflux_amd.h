@@ -561,6 +561,44 @@ int nf_field_set_cell_thickness_missing_value(nf_field **self, double missing_va
 int nf_field_set_depth_edges(nf_field **self, const double *edges, int nedges, double top);
 int nf_field_compute_depth_transport(nf_field **self, long tIndex, int carry, double *rows_host);        /* (nedges+2, row_length) */
 int nf_field_compute_depth_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev);   /* HBM, field's stream */
+/* Transports between surfaces: the depth bins above with edges that are 2-D fields -- the transport inside the mixed layer,
+ * above an isotherm, below an ice-shelf draft, within 200 m of the sea bed (column depth minus 200).
+ * Surfaces.  m surfaces, 1 <= m <= 8, each a field at T-points of shape (nt_s, ny, nx), nt_s = 1 (static) or the nt of uo / vo,
+ * in the dtype of uo / vo: surfaces[k] is the base of surface k.  Values are depths, positive downward, in the units of the
+ * thicknesses, measured from the origin of `top`, the depth of the upper interface of level 0 (finite).  The surfaces have
+ * two missing markers of their own (fill_value, nf_field_set_depth_surfaces_missing_value; NaN = none; NaN always counts as
+ * missing) and a wrap_x of their own (nf_field_set_depth_surfaces_wrap, default 1).  They are a state of their own: the
+ * depth, class and joint edges do not see them; surfaces == NULL clears them.  HBM arrays (on_device = 1) are used in place; a
+ * static host set is uploaded once at the call and then belongs to the (ny, nx) of that moment -- after a set_bounds of another
+ * shape every compute returns NF_ERR_STATE naming nf_field_set_depth_surfaces until it is set again or cleared; a time-varying
+ * host set is staged one step at a time into a buffer of the handle.
+ * Face value of a surface: the class-field rule of nf_field_compute_class_transport -- both cells beside the face have a
+ * value: 0.5 * (a + b) in double; one has: that one; neither: none.  East face of c = (c, c + 1), the periodic copy in the last
+ * column under wrap_x; north face = (c, c + nx); the west slot is the east face of the west cell, the south slot the north
+ * face of the south cell.
+ * Edges of a face.  x_1 .. x_m its face values: if any has no value or is not finite every term of the face goes whole to row
+ * m + 1, at every level.  Otherwise e_1 = x_1, e_k = max(e_{k-1}, x_k): a surface that rises above the one before it is taken
+ * at that one, its layer has zero width there.  The edges of a face are non-decreasing, not strictly increasing.
+ * Terms and spreading.  D_z, the term t = w * d (times tf with carry = 1) and the spread rule are those of
+ * nf_field_compute_depth_transport with the face's own e in place of the global edges: D_0 = top, D_{z+1} = D_z + h_z from
+ * level 0 under a slab range too; row(x) = the number of e_k <= x; a depth or a difference that is not finite: whole to row
+ * m + 1; lo == hi: whole to row(lo); else row j gets t * ((right - left) / (hi - lo)), nothing where right == left.
+ * Rows.  m + 2 rows of row_length, each [segments | transects], written whole: row 0 above surface 1, row k between surfaces
+ * k and k + 1, row m below surface m, row m + 1 the faces without an edge set or with a depth that is not finite (exactly
+ * +0.0 otherwise).  Per lane the additions run level-ascending, then in slot order (south, east, north, west), then
+ * row-ascending, into accumulators that start at +0.0; scan and finalize as in the class forms: no atomics, bitwise
+ * reproducible, independent of the "class_window" knob.  With surfaces that are constant over the grid at e_1 < .. < e_m the
+ * rows are those of nf_field_compute_depth_transport with these edges, bit for bit.
+ * NF_ERR_ARG, decided before a device is needed: a null argument, m outside 1 .. 8, nt_s not 1 or nt, a dtype other than that
+ * of uo / vo (the message names both), a `top` that is not finite, carry other than 0 or 1.  NF_ERR_STATE: the setter before
+ * set_uv, a compute before the setter, carry = 1 before set_tracer.  The calls change neither the resident planes, |.| arrays,
+ * running max, last row, tracer planes, any edge set nor a captured pass. */
+int nf_field_set_depth_surfaces(nf_field **self, const void *const *surfaces, int m, long nt_s, int dtype, int on_device,
+                                double fill_value, double top);
+int nf_field_set_depth_surfaces_missing_value(nf_field **self, double missing_value);   /* NaN = none */
+int nf_field_set_depth_surfaces_wrap(nf_field **self, int wrap_x);
+int nf_field_compute_surface_transport(nf_field **self, long tIndex, int carry, double *rows_host);        /* (m+2, row_length) */
+int nf_field_compute_surface_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev);   /* HBM, field's stream */
 /* Read-back of the resident per-step arrays into caller-owned HOST arrays, in place (fluxviz.py aliases
  * them: fluxviz.py:148,160,168): integratedVelocity (ncell,4), edgeFluxesU/V (ncell) = |flux|; any may be
  * NULL.  max_abs: running max (field.py:234). */

@@ -156,6 +156,12 @@ _sig('nf_field_compute_class_remap_async', [_pp, ctypes.c_long, ctypes.c_int, ct
 _sig('nf_field_set_depth_edges', [_pp, c_double_p, ctypes.c_int, ctypes.c_double])
 _sig('nf_field_compute_depth_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
 _sig('nf_field_compute_depth_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
+_sig('nf_field_set_depth_surfaces', [_pp, c_void_pp, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                     ctypes.c_double])
+_sig('nf_field_set_depth_surfaces_missing_value', [_pp, ctypes.c_double])
+_sig('nf_field_set_depth_surfaces_wrap', [_pp, ctypes.c_int])
+_sig('nf_field_compute_surface_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
+_sig('nf_field_compute_surface_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_read_step', [_pp, c_double_p, c_double_p, c_double_p, c_double_p])
 _sig('nf_field_reset_max', [_pp])
 _sig('nf_field_get_arclengths', [_pp, c_double_p])

@@ -210,6 +210,22 @@ struct nf_field {
     // the run sums of a window go to class_scratch
     EdgeSet depth_edges;
     double depth_top = 0.0;
+    // transports between surfaces (nf_field_set_depth_surfaces): m 2-D fields of (nt, ny, nx), nt == 1 (static) or the nt of
+    // uo / vo, in their dtype; a state of its own that no other product reads.  HBM arrays are used in place, a static host set
+    // is uploaded once into `fixed` (m planes) and counts as resident from then on, a time-varying host set is staged one
+    // step at a time into `stage`.  Its setters change neither `version` nor a captured pass.
+    struct Surfaces {
+        const void *p[kMaxSurfaces] = {};
+        int m = 0;
+        long nt = 0;
+        int dtype = NF_F64, on_device = 1;
+        double fill = std::numeric_limits<double>::quiet_NaN();
+        double fill2 = std::numeric_limits<double>::quiet_NaN();
+        int wrap = 1;
+        double top = 0.0;
+        DevArray<char> fixed, stage;
+        long fixed_ny = 0, fixed_nx = 0;   // the (ny, nx) in force when `fixed` was uploaded (field_surfaces_current)
+    } surf;
     // joint class transport (nf_field_set_joint_class_edges): state of its own, the 1-D forms do not see it.  The edges of
     // axis A then axis B in one set.  The term table (40 bytes per record and
     // owned level), the block flags and the run sums of one window are allocated on first use, grown when the records, the
@@ -383,12 +399,28 @@ static int field_cell_thick_current(const nf_field *f, const char *what)
     return NF_OK;
 }
 
+// The same rule for a static host set of surfaces that the handle uploaded (nf_field_set_depth_surfaces): it has the (ny, nx) of
+// the upload.
+static int field_surfaces_current(const nf_field *f, const char *what)
+{
+    if (!f->surf.m || !f->surf.fixed.get()) return NF_OK;
+    if (f->surf.fixed_ny == f->ny && f->surf.fixed_nx == f->nx) return NF_OK;
+    char buf[320];
+    snprintf(buf, sizeof buf,
+             ": the static depth surfaces were uploaded for (ny, nx) = (%ld, %ld) and the field is now (%ld, %ld); "
+             "call nf_field_set_depth_surfaces again with arrays of the new shape, or clear them with NULL",
+             f->surf.fixed_ny, f->surf.fixed_nx, f->ny, f->nx);
+    NF_REQUIRE(false, NF_ERR_STATE, std::string(what) + buf);
+    return NF_OK;
+}
+
 // the state every per-step computation needs; `what` prefixes the message ("compute", "compute_profile", ...)
 static int field_ready(const nf_field *f, const char *what, bool weights)
 {
     NF_REQUIRE(f->geo.arcE.get() && f->thick.get() && f->uv.p[0] && f->uv.p[1], NF_ERR_STATE,
                std::string(what) + ": set_bounds, set_thickness and set_uv first");
     NF_REQUIRE(!weights || f->weights_built, NF_ERR_STATE, std::string(what) + ": build_weights first");
+    NF_TRY(field_surfaces_current(f, what));
     return field_cell_thick_current(f, what);
 }
 
@@ -846,6 +878,47 @@ static int field_depth_step_async(nf_field *f, long t, bool carry, double *rows_
     a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
     return launch_depth_transport(a, f->stream);
+}
+
+// Transports between the surfaces of step t on the field's stream (nf_field_compute_surface_transport): rows_dev (m + 2,
+// row_length), written whole.  field_depth_step_async with the surfaces in place of the edges: step t' = t of every surface, or
+// 0 of a static set; a host-resident time-varying set is staged, the m planes of the step, into a buffer of the handle.
+static int field_surface_step_async(nf_field *f, long t, bool carry, double *rows_dev)
+{
+    nf_field::Surfaces &sf = f->surf;
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_surface_transport", t, carry ? 1 : 0, rows_dev, (size_t)sf.m + 2, &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    NF_TRY(field_matches_uv(f, sf.dtype, sf.nt, "compute_surface_transport", "depth surfaces", kStaticOk));
+    const int window = g_class_window;
+    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
+    SurfaceArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    if (carry) NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
+    NF_TRY(field_cell_thick(f, t, Levels{0, lv.z1}, &a.th));
+    const size_t plane = (size_t)f->ncell * elem_size(f->uv.dtype);
+    const size_t off = (sf.nt == 1 ? 0 : (size_t)t) * plane;
+    if (!sf.on_device) NF_TRY(sf.stage.reserve(plane * sf.m));
+    for (int q = 0; q < sf.m; ++q) {
+        const char *src = (const char *)sf.p[q] + off;
+        if (!sf.on_device) {
+            char *dst = sf.stage.get() + (size_t)q * plane;
+            NF_HIP(hipMemcpyAsync(dst, src, plane, hipMemcpyHostToDevice, f->stream));
+            src = dst;
+        }
+        a.sf.p[q] = src;
+    }
+    a.sf.m = sf.m;
+    a.sf.fill = sf.fill;
+    a.sf.fill2 = sf.fill2;
+    a.sf.wrap_x = sf.wrap;
+    a.top = sf.top;
+    a.window = window;
+    a.tr = field_transects(f);
+    a.scratch = f->class_scratch.get();
+    a.scratch_len = f->class_scratch.size();
+    a.rows = rows_dev;
+    return launch_surface_transport(a, f->stream);
 }
 
 // the calls of the joint class transport need both tracers and the joint edges: checked before a device is needed
@@ -1774,6 +1847,96 @@ try {
     nf_field *f = *self;
     NF_NEED_DEVICE();
     return field_depth_step_async(f, tIndex, carry != 0, rows_dev);
+}
+NF_API_CATCH
+
+int nf_field_set_depth_surfaces(nf_field **self, const void *const *surfaces, int m, long nt_s, int dtype, int on_device,
+                                double fill_value, double top)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_depth_surfaces: null field");
+    nf_field *f = *self;
+    nf_field::Surfaces &sf = f->surf;
+    if (!surfaces) {   // no surfaces; freeing the handle's buffers waits for the kernels that read them
+        sf = nf_field::Surfaces{};
+        return NF_OK;
+    }
+    NF_REQUIRE(m >= 1 && m <= kMaxSurfaces, NF_ERR_ARG, "nf_field_set_depth_surfaces: need 1 <= m <= 8 surfaces");
+    for (int q = 0; q < m; ++q) NF_REQUIRE(surfaces[q], NF_ERR_ARG, "nf_field_set_depth_surfaces: null argument");
+    NF_REQUIRE(dtype == NF_F64 || dtype == NF_F32, NF_ERR_ARG, "nf_field_set_depth_surfaces: dtype must be NF_F64/NF_F32");
+    NF_REQUIRE(std::isfinite(top), NF_ERR_ARG, "nf_field_set_depth_surfaces: top must be a finite number");
+    NF_REQUIRE(nt_s >= 1, NF_ERR_ARG, "nf_field_set_depth_surfaces: need nt_s = 1 (static) or the nt of uo/vo");
+    NF_REQUIRE(f->uv.p[0] && f->uv.p[1], NF_ERR_STATE, "nf_field_set_depth_surfaces: set_uv first");
+    NF_TRY(field_matches_uv(f, dtype, nt_s, "nf_field_set_depth_surfaces", "depth surfaces",
+                            kStaticOk | kNameDtypes | kCountSteps));
+    const bool upload = !on_device && nt_s == 1;   // a static host set: uploaded once, here
+    DevArray<char> fixed;
+    if (upload) {
+        NF_REQUIRE(f->ncell > 0, NF_ERR_STATE, "nf_field_set_depth_surfaces: set_bounds first");
+        NF_NEED_DEVICE();
+        const size_t plane = (size_t)f->ncell * elem_size(dtype);
+        NF_TRY(fixed.alloc(plane * m));
+        for (int q = 0; q < m; ++q) NF_HIP(hipMemcpy(fixed.get() + (size_t)q * plane, surfaces[q], plane, hipMemcpyHostToDevice));
+        NF_HIP(hipStreamSynchronize(f->stream));   // kernels in flight may still read the arrays these replace
+    }
+    sf.fixed = std::move(fixed);
+    sf.fixed_ny = f->ny, sf.fixed_nx = f->nx;
+    const size_t plane = (size_t)f->ncell * elem_size(dtype);
+    for (int q = 0; q < kMaxSurfaces; ++q)
+        sf.p[q] = q >= m ? nullptr : (upload ? (const void *)(sf.fixed.get() + (size_t)q * plane) : surfaces[q]);
+    sf.m = m;
+    sf.nt = nt_s;
+    sf.dtype = dtype;
+    sf.on_device = (on_device || upload) ? 1 : 0;
+    sf.fill = fill_value;
+    sf.top = top;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_depth_surfaces_missing_value(nf_field **self, double missing_value)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_depth_surfaces_missing_value: null field");
+    (*self)->surf.fill2 = missing_value;
+    return NF_OK;
+}
+NF_API_CATCH
+
+int nf_field_set_depth_surfaces_wrap(nf_field **self, int wrap_x)
+try {
+    NF_REQUIRE(self && *self, NF_ERR_ARG, "nf_field_set_depth_surfaces_wrap: null field");
+    (*self)->surf.wrap = wrap_x ? 1 : 0;
+    return NF_OK;
+}
+NF_API_CATCH
+
+// the checks of the two surface calls that need no device: arguments, then the surfaces and the tracer of the carried form
+static int field_surface_args(nf_field **self, int carry, const void *rows, const char *what)
+{
+    const std::string w(what);
+    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
+    NF_REQUIRE((*self)->surf.m > 0, NF_ERR_STATE, w + ": set_depth_surfaces first");
+    NF_REQUIRE(!carry || (*self)->tau.p[0], NF_ERR_STATE, w + ": set_tracer first");
+    return field_ready(*self, what, true);
+}
+
+int nf_field_compute_surface_transport(nf_field **self, long tIndex, int carry, double *rows_host)
+try {
+    NF_TRY(field_surface_args(self, carry, rows_host, "nf_field_compute_surface_transport"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    const size_t n = ((size_t)f->surf.m + 2) * (size_t)field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_surface_step_async(f, tIndex, carry != 0, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_surface_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
+try {
+    NF_TRY(field_surface_args(self, carry, rows_dev, "nf_field_compute_surface_transport_async"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    return field_surface_step_async(f, tIndex, carry != 0, rows_dev);
 }
 NF_API_CATCH
 

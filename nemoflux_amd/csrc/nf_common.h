@@ -588,6 +588,31 @@ struct DepthArgs {
 };
 int launch_depth_transport(const DepthArgs &a, hipStream_t s);
 
+// Transports between surfaces (nf_field_compute_surface_transport, nf_integral.hip; the contract is in nemoflux_amd.h): the
+// depth bins with the edges of every face taken from m 2-D fields at T-points -- rows 0 .. m + 1 of one time step, row 0 above
+// surface 1, row k between surfaces k and k + 1, row m below surface m, row m + 1 the terms of a face without an edge set or
+// with an interface depth that is not finite.  Terms, interface depths, spreading and the window loop are DepthArgs'.
+constexpr int kMaxSurfaces = 8;
+struct SurfaceSet {
+    const void *p[kMaxSurfaces] = {};   // device: step t' of every surface, (ncell) of the field dtype
+    int m = 0;
+    double fill = __builtin_nan(""), fill2 = __builtin_nan("");   // the surfaces' own markers; NaN = none
+    int wrap_x = 1;              // 1: the east face of column nx-1 takes column 0 as its neighbour
+};
+struct SurfaceArgs {
+    StepInput in;
+    SurfaceSet sf;
+    double top = 0.0;            // D_0, the origin of the surfaces' depths too
+    int window = 0;              // rows per pass over the fields, 1 .. kClassWindowMax
+    Transects tr;
+    double *scratch = nullptr;
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // (m + 2, row_length)
+    TracerIn t;                  // the carried tracer; t.tau == nullptr: volume form
+    CellThick th;
+};
+int launch_surface_transport(const SurfaceArgs &a, hipStream_t s);
+
 // Transport in JOINT classes of two tracers (nf_field_compute_joint_class_transport, nf_integral.hip): axis A is the tracer
 // (edges ea, na), axis B the class tracer (edges eb, nb); joint row ra * (nb + 2) + rb, ra / rb the 1-D rows of the face's
 // raw value of A / B.  Stage 1 gathers once and writes, per (record, owned level), the four weighted slot terms and their

@@ -1549,6 +1549,227 @@ int launch_depth_transport(const DepthArgs &a, hipStream_t s)
     NF_REQUIRE(false, NF_ERR_ARG, "depth transport: dtype must be NF_F64 or NF_F32");
 }
 
+// ---- transports between surfaces: k_depth_segscan with an edge set per face ---------------------------------------------
+// The edges of a face are the face values (tr_face_raw, the surfaces' own markers and wrap rule) of the m surfaces, each raised
+// to the one before it (a running max: non-decreasing); a face where any surface has no finite value has no edge set and sends
+// every term to row m + 1.  A lane gathers the five values c, e, n, w, s of every surface once, before the level loop, and
+// keeps the 4 m edges of its four faces in LDS behind the accumulators, ed[(face * m + k) * kSurfaceBlock + lane]: a wave reads
+// 64 consecutive doubles, no bank conflict, and no dynamic index reaches a register array (it would go to scratch).  row(x), the
+// number of edges <= x, is a linear count over the m <= 8 edges, lo and hi in one pass; with edges that are the same on every
+// face it is class_row of k_depth_segscan, and spans, shares and the order of the additions are that kernel's: the same bits.
+// Both thickness forms carry four spans per level, the edges differ from face to face.  Nothing is shared between waves and
+// there is no barrier, so a workgroup is ONE wave (kSurfaceBlock lanes: the same records in the same waves as a kBlock launch
+// would give them, hence the same scan): LDS is (nwin + 4 m) x 64 doubles a workgroup, 21 KiB at m = 8 with all ten rows in
+// one window, and seven waves fit a CU where one 256-lane workgroup of 84 KiB would leave one wave per SIMD.
+constexpr int kSurfaceBlock = kWave;
+template <typename T>
+struct SurfIn {
+    const T *p[kMaxSurfaces];   // step t' of every surface: (ncell) of the field dtype
+    int m;
+    T m1, m2;
+    int wrap_x;
+};
+
+template <typename T, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_surface_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                            const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                            const T *__restrict__ v, long ncell, unsigned nx, int z0, int z1,
+                                                            const double *__restrict__ thickness,
+                                                            const double *__restrict__ arcE, const double *__restrict__ arcN,
+                                                            T fill, T fill2, int two, double scale, int sverdrup,
+                                                            SurfIn<T> sf, double surface, int r0, int nwin,
+                                                            double *__restrict__ runsum, TI... extra)
+{
+    constexpr bool TR = (std::is_same<TI, TauIn<T>>::value || ...);
+    constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
+    constexpr int DL = kDepthLevels;
+    const TauIn<T> ti = tau_in<T>(extra...);
+    const ThickIn<T> ct = thick_arg<T>(extra...);
+    const int m = sf.m;
+    extern __shared__ double class_lds[];
+    double *acc = class_lds + threadIdx.x;                                 // acc[r * kSurfaceBlock]: this lane's row r
+    double *ed = class_lds + (size_t)nwin * kSurfaceBlock + threadIdx.x;   // ed[(face * m + k) * kSurfaceBlock]: this lane's edges
+    for (int r = 0; r < nwin; ++r) acc[r * kSurfaceBlock] = 0.0;           // every lane touches only its own part of the LDS
+    const long k = (long)blockIdx.x * kSurfaceBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    int key = -1;
+    if (k < n) {   // 0 <= z0 < z1: the launcher's
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const ClassNeighbours nbs = class_neighbours(r.c, nx, ncell, sf.wrap_x);
+        const auto nb = step_neighbours<TR>(r.c, nx, ncell, ti.wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        const int rend = r0 + nwin - 1;
+        // the edge sets of the four faces (slot order: south, east, north, west); ok: every surface has a finite value there
+        bool ok_s = true, ok_e = true, ok_n = true, ok_w = true;
+        {
+            double ps = 0.0, pe = 0.0, pn = 0.0, pw = 0.0;
+            auto edge = [&](int f, int q, bool h, double x, bool &ok, double &prev) {
+                ok = ok && h && __builtin_isfinite(x);
+                prev = (q == 0 || x > prev) ? x : prev;
+                ed[(f * m + q) * kSurfaceBlock] = prev;
+            };
+            for (int q = 0; q < m; ++q) {
+                const LevelTau<T> x = load_level_tau(sf.p[q], 0, r.c, nbs);
+                double f;
+                bool h = tr_face_raw<T>(x.s, x.c, true, sf.m1, sf.m2, &f);
+                edge(0, q, h, f, ok_s, ps);
+                h = tr_face_raw<T>(x.c, x.e, nbs.has_e, sf.m1, sf.m2, &f);
+                edge(1, q, h, f, ok_e, pe);
+                h = tr_face_raw<T>(x.c, x.n, nbs.has_n, sf.m1, sf.m2, &f);
+                edge(2, q, h, f, ok_n, pn);
+                h = tr_face_raw<T>(x.w, x.c, nbs.has_w, sf.m1, sf.m2, &f);
+                edge(3, q, h, f, ok_w, pw);
+            }
+        }
+        auto span = [&](const double *e, bool ok, double a, double b) {
+            if (!(ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(b - a)))
+                return DepthSpan{0.0, 0.0, m + 1, -1};
+            const double lo = a < b ? a : b, hi = a < b ? b : a;
+            int jlo = 0, jhi = 0;
+            for (int q = 0; q < m; ++q) {
+                const double x = e[q * kSurfaceBlock];
+                jlo += x <= lo ? 1 : 0;
+                jhi += x <= hi ? 1 : 0;
+            }
+            return DepthSpan{lo, hi, jlo, lo == hi ? -1 : jhi};
+        };
+        auto put = [&](const double *e, const DepthSpan &p, double t) {
+            if (p.jhi < 0) {
+                const int q = p.jlo - r0;
+                if (q >= 0 && q < nwin) acc[q * kSurfaceBlock] += t;
+                return;
+            }
+            const double width = p.hi - p.lo;
+            const int ja = p.jlo > r0 ? p.jlo : r0, jb = p.jhi < rend ? p.jhi : rend;
+            for (int j = ja; j <= jb; ++j) {
+                const double left = j == p.jlo ? p.lo : e[(j - 1) * kSurfaceBlock], right = j == p.jhi ? p.hi : e[j * kSurfaceBlock];
+                if (right != left) acc[(j - r0) * kSurfaceBlock] += t * ((right - left) / width);
+            }
+        };
+        const double *es = ed, *ee = ed + (size_t)m * kSurfaceBlock, *en = ed + (size_t)2 * m * kSurfaceBlock, *ew = ed + (size_t)3 * m * kSurfaceBlock;
+        SlotTh D = slot_th(surface);   // the depth of the upper interface of the next level at the four faces
+        auto below = [](const SlotTh &d, const SlotTh &th) { return SlotTh{d.e + th.e, d.n + th.n, d.s + th.s, d.w + th.w}; };
+        for (int z = 0; z < z0; z += DL) {   // above the owned levels: the depths move, no term
+            const int nlev = z0 - z < DL ? z0 - z : DL;
+            if constexpr (CT) {
+                LevelUV<T> e3[DL];
+#pragma unroll
+                for (int l = 0; l < DL; ++l)
+                    if (l < nlev) e3[l] = load_level_e3(ct, (long)(z + l) * ncell, r.c, nb);
+#pragma unroll
+                for (int l = 0; l < DL; ++l)
+                    if (l < nlev) D = below(D, level_th(e3[l], ct));
+            } else {
+                for (int l = 0; l < nlev; ++l) D = below(D, slot_th(thickness[z + l]));
+            }
+        }
+        for (int z = z0; z < z1; z += DL) {
+            const int nlev = z1 - z < DL ? z1 - z : DL;
+            LevelUV<T> x[DL];
+            LevelTau<T> tt[TR ? DL : 1];
+            LevelUV<T> e3[CT ? DL : 1];
+#pragma unroll
+            for (int l = 0; l < DL; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
+                    if constexpr (TR) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < DL; ++l)
+                if (l < nlev) {
+                    FaceTf tf{};
+                    if constexpr (TR) tf = level_tf(tt[l], nb, ti);
+                    SlotTh th;
+                    if constexpr (CT)
+                        th = level_th(e3[l], ct);
+                    else
+                        th = slot_th(thickness[z + l]);
+                    const Slots d = level_slots_tf<T, TR>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, tf);
+                    const SlotTh Dn = below(D, th);
+                    if (nb.south) put(es, span(es, ok_s, D.s, Dn.s), r.wa.x * d.s);
+                    put(ee, span(ee, ok_e, D.e, Dn.e), r.wa.y * d.e);
+                    put(en, span(en, ok_n, D.n, Dn.n), r.wb.x * d.n);
+                    put(ew, span(ew, ok_w, D.w, Dn.w), r.wb.y * d.w);
+                    D = Dn;
+                }
+        }
+    }
+    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
+#pragma unroll
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
+        if (seg_scan_take(key, lane, o)) take |= 1u << b;
+    const bool store = seg_run_end(key, lane, k, n);
+    for (int r = 0; r < nwin; ++r) {
+        double val[1] = {k < n ? acc[r * kSurfaceBlock] : 0.0};
+#pragma unroll
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
+        if (store) runsum[(long)r * n + k] = val[0];
+    }
+}
+
+// launch_depth_t's loop over the windows; m + 2 <= 10 rows fit one window of the default size, a smaller one repeats the pass
+template <typename T, typename... TI>
+static int launch_surface_t(const SurfaceArgs &a, hipStream_t s, TI... extra)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const long row_length = a.tr.row_length();
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    SurfIn<T> sf{};
+    for (int q = 0; q < a.sf.m; ++q) sf.p[q] = (const T *)a.sf.p[q];
+    sf.m = a.sf.m;
+    sf.m1 = (T)a.sf.fill;
+    sf.m2 = (T)a.sf.fill2;
+    sf.wrap_x = a.sf.wrap_x ? 1 : 0;
+    const int nrows = a.sf.m + 2;
+    for (int r0 = 0; r0 < nrows; r0 += a.window) {
+        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
+        const size_t lds = sizeof(double) * ((size_t)nwin + 4 * (size_t)a.sf.m) * kSurfaceBlock;   // <= 21 KiB
+        if (ws.nrec > 0) {
+            const dim3 grid((unsigned)((ws.nrec + kSurfaceBlock - 1) / kSurfaceBlock));
+            hipLaunchKernelGGL((k_surface_segscan<T, TI...>), grid, dim3(kSurfaceBlock), lds, s, ws.cell.get(), ws.w4.get(),
+                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale,
+                               in.sverdrup, sf, a.top, r0, nwin, a.scratch, extra...);
+        }
+        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
+                        (unsigned)nwin, s);
+        NF_HIP(hipGetLastError());
+    }
+    return NF_OK;
+}
+
+// the four forms of one dtype: volume or carried tracer, each with the scalar or the per-cell thicknesses
+template <typename T>
+static int launch_surface_form(const SurfaceArgs &a, hipStream_t s)
+{
+    const TauIn<T> ti = tau_of<T>(a.t);
+    if (a.t.tau && a.th.e3u) return launch_surface_t<T>(a, s, ti, thick_in<T>(a.th));
+    if (a.t.tau) return launch_surface_t<T>(a, s, ti);
+    if (a.th.e3u) return launch_surface_t<T>(a, s, thick_in<T>(a.th));
+    return launch_surface_t<T>(a, s);
+}
+
+int launch_surface_transport(const SurfaceArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.sf.m >= 1 && a.sf.m <= kMaxSurfaces, NF_ERR_ARG, "surface transport: bad number of surfaces");
+    for (int q = 0; q < a.sf.m; ++q) NF_REQUIRE(a.sf.p[q], NF_ERR_ARG, "surface transport: null argument");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "surface transport: bad window");
+    NF_TRY(check_raw_step("surface transport", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "surface transport: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "surface transport: null argument");
+    NF_REQUIRE(in.z0 < in.z1, NF_ERR_ARG, "surface transport: bad levels");
+    NF_REQUIRE(__builtin_isfinite(a.top), NF_ERR_ARG, "surface transport: top must be a finite number");
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (in.dtype == NF_F64) return launch_surface_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_surface_form<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "surface transport: dtype must be NF_F64 or NF_F32");
+}
+
 // ---- transport in joint classes of two tracers: gather once (k_joint_terms), bin many times (k_joint_bin) -------------
 // The terms and the accumulation are k_class_segscan's: per owned level (z ascending) the four slot terms of level_slots_tf
 // times their weights, each added in slot order (south, east, north, west) to the lane's accumulator of its row, then

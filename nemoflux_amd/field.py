@@ -1411,6 +1411,7 @@ class Field(object):
             mean.setJointClassEdges(*self._joint_edges)
         if getattr(self, '_depth_edges', None) is not None:
             mean.setDepthEdges(*self._depth_edges)
+        self._mean_surfaces(mean, table, t0, t1)
         if weighted:
             mean.setCellThickness(hu, hv)       # the mean thicknesses: static, float64, in HBM, no markers
         elif e3 is not None:
@@ -1436,13 +1437,13 @@ class Field(object):
 
     _SPLIT_METHODS = ('computeTracerFlux', 'computeFluxProfile', 'computeTracerProfile', 'computeClassTransport',
                       'computeClassTracerTransport', 'computeClassRemap', 'computeDepthTransport', 'computeGrossProfile',
-                      'computeGrossClassTransport')
+                      'computeGrossClassTransport', 'computeSurfaceTransport')
 
     def meanEddySplit(self, method, steps=None, select=None, weights=None, thicknessWeighted=False, **kw):
         """The time mean of one per-step row product split into the part of the mean state and the rest.  method: the name of
         the product -- computeTracerFlux, computeFluxProfile, computeTracerProfile, computeClassTransport,
-        computeClassTracerTransport, computeClassRemap, computeDepthTransport, computeGrossProfile or
-        computeGrossClassTransport; kw goes to it (carry=).  steps / select / weights choose and weight the steps as in
+        computeClassTracerTransport, computeClassRemap, computeDepthTransport, computeGrossProfile,
+        computeGrossClassTransport or computeSurfaceTransport; kw goes to it (carry=).  steps / select / weights choose and weight the steps as in
         timeMean.  Returns a dict: 'total' = sum of w_j rows_j over the visited steps / sum of w_j, formed on the host in float64
         step by step in their order; 'mean' = the same product at step 0 of 'meanField' = timeMean(steps, thicknessWeighted,
         select, weights), the transport by the mean flow of the mean tracer in the classes of the mean class field; 'eddy' =
@@ -1626,6 +1627,176 @@ class Field(object):
         else:
             rows = numpy.zeros((nrows, self._row_width), numpy.float64)
             check(lib.nf_field_compute_depth_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        return self._split_rows(rows)
+
+    def setDepthSurfaces(self, surfaces, top=0.0, fill_value=None, missing_value=None, wrapX=True):
+        """Surfaces that bound the layers of computeSurfaceTransport: a list of 1 to 8 fields at T-points whose values are
+        depths, positive downward, in the units of the thicknesses and measured from the origin of `top`, the depth of the
+        upper interface of level 0 (finite) -- the mixed-layer depth, the depth of an isotherm, an ice-shelf draft, the column
+        depth minus 200.  Each item is a host array of shape (ny, nx), (1, ny, nx) (static) or (nt, ny, nx), a torch CUDA
+        tensor or a DeviceArray of such a shape (used in place), or a (path, name) pair read with nemoflux_amd.io, its CF
+        markers decoded: a time-varying one, one step at a time.  All items are static or all vary in time, and all live on the
+        host (files included) or all on the device.  A host array of another float dtype is cast to the dtype of uo / vo; a
+        device array of another dtype raises.  fill_value / missing_value: the surfaces' own missing markers (the files' when
+        not given; more than two distinct ones over the set raise); NaN always counts as missing.  wrapX: the east face of
+        the last column takes column 0 as its neighbour.  A set of its own: setDepthEdges, setClassEdges and
+        setJointClassEdges do not see it.  setDepthSurfaces(None) clears it."""
+        self._surfaces = None
+        if surfaces is None:
+            check(lib.nf_field_set_depth_surfaces(ctypes.byref(self._h), None, 0, 0, NF_F64, 0, numpy.nan, 0.0))
+            return
+        surfaces = list(surfaces)
+        if not 1 <= len(surfaces) <= 8:
+            raise RuntimeError(f'ERROR: setDepthSurfaces needs a list of 1 to 8 surfaces, got {len(surfaces)}')
+        if not numpy.isfinite(float(top)):
+            raise RuntimeError(f'ERROR: setDepthSurfaces: top must be a finite number, got {top!r}')
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        markers, items, nts, homes = [], [], [], []
+        for k, s in enumerate(surfaces):
+            if isinstance(s, tuple) and len(s) == 2 and isinstance(s[1], str):
+                var, _, d = open_uvfile(s[0], s[1], with_all=True)
+                for m in d['_markers_' + s[1]]:
+                    if m not in markers:
+                        markers.append(m)
+                s = var
+            shape = tuple(int(x) for x in s.shape)
+            nt_s = 1 if len(shape) == 2 else (shape[0] if len(shape) == 3 else -1)
+            if shape[-2:] != (self.ny, self.nx) or nt_s not in (1, self.nt):
+                raise RuntimeError(f'ERROR: surface {k} has shape {shape}; need (ny, nx) = {(self.ny, self.nx)}, (1, ny, nx) or '
+                                   f'(nt, ny, nx) = {(self.nt, self.ny, self.nx)}')
+            if hasattr(s, 'read_step') and (nt_s == 1 or len(shape) == 2):     # a static file variable: read once
+                s = numpy.stack([s.read_step(j) for j in range(shape[0])]) if len(shape) == 2 else s.read_step(0)
+            dt, ptr, lazy = numpy.dtype(_native_dtype(s)), _lib.device_pointer(s), hasattr(s, 'read_step')
+            if ptr is not None and dt != uv_dtype:
+                raise RuntimeError(f'ERROR: surface {k} is {dt.name}, uo/vo are {uv_dtype.name}: only a host array of another '
+                                   f'float dtype is cast')
+            if dt.kind != 'f':
+                raise RuntimeError(f'ERROR: surface {k} is {dt.name}: need a float array')
+            if ptr is None and not lazy:
+                s = _native(numpy.asarray(s, dtype=uv_dtype))
+            items.append(s)
+            nts.append(nt_s)
+            homes.append(ptr is not None)
+        if len(set(nts)) > 1:
+            raise RuntimeError(f'ERROR: setDepthSurfaces: the surfaces have {nts} time steps: all static or all per time step')
+        if len(set(homes)) > 1:
+            raise RuntimeError('ERROR: setDepthSurfaces: the surfaces must all be host arrays (or files) or all be device arrays')
+        for m in (fill_value, missing_value):
+            if m is not None and float(m) == float(m) and float(m) not in markers:
+                markers.append(float(m))
+        if len(markers) > 2:
+            raise RuntimeError(f'ERROR: the surfaces carry {len(markers)} different _FillValue / missing_value markers '
+                               f'({markers}); the engine masks at most two')
+        if fill_value is None:
+            fill_value = markers[0] if markers else None
+        if missing_value is None:
+            missing_value = markers[1] if len(markers) > 1 else None
+        slot = dict(items=items, nt=nts[0], on_dev=homes[0], step=-1, top=float(top), wrapX=bool(wrapX),
+                    fill=numpy.nan if fill_value is None else float(fill_value),
+                    missing=numpy.nan if missing_value is None else float(missing_value),
+                    buf=[self._host_array((self.ny, self.nx), uv_dtype) if hasattr(s, 'read_step') else None for s in items])
+        if not any(b is not None for b in slot['buf']):
+            self._set_surfaces(slot, [_lib.device_pointer(s) if slot['on_dev'] else s.ctypes.data for s in items])
+        check(lib.nf_field_set_depth_surfaces_missing_value(ctypes.byref(self._h), slot['missing']))
+        check(lib.nf_field_set_depth_surfaces_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
+        self._surfaces = slot
+
+    def _set_surfaces(self, slot, ptrs):
+        arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+        check(lib.nf_field_set_depth_surfaces(ctypes.byref(self._h), arr, len(ptrs), slot['nt'], self._uv_code,
+                                              1 if slot['on_dev'] else 0, slot['fill'], slot['top']))
+
+    def _stage_surfaces(self, tIndex):
+        """make step tIndex of the file-backed surfaces the one the engine reads: each into its pinned buffer, handed over
+        through a virtual (nt, ny, nx) base that the engine only dereferences at step tIndex"""
+        slot = self._surfaces
+        if slot['step'] == tIndex or not any(b is not None for b in slot['buf']):
+            return
+        ptrs = []
+        for s, buf in zip(slot['items'], slot['buf']):
+            if buf is None:
+                ptrs.append(s.ctypes.data)
+            else:
+                numpy.copyto(buf, s.read_step(tIndex), casting='same_kind')
+                ptrs.append(buf.ctypes.data - tIndex * buf.nbytes)
+        self._set_surfaces(slot, ptrs)
+        slot['step'] = tIndex
+
+    def _surface_step_host(self, s, t):
+        """step t of one surface as a host array (ny, nx)"""
+        import torch
+        if hasattr(s, 'read_step'):
+            return numpy.asarray(s.read_step(t))
+        if isinstance(s, torch.Tensor):
+            return s.reshape(-1, self.ny, self.nx)[t].cpu().numpy()
+        if isinstance(s, _lib.DeviceArray):
+            host = numpy.empty((self.ny, self.nx), s.dtype)
+            check(lib.nf_memcpy_d2h(host.ctypes.data, s.ptr + t * host.nbytes, host.nbytes))
+            return host
+        return s.reshape(-1, self.ny, self.nx)[t]
+
+    def _mean_surfaces(self, mean, table, t0, t1):
+        """carry the surfaces to the Field of timeMean: a static set as it is (float64, where it lives), a time-varying one
+        as the mean of its present values over the visited steps with their weights -- the tracer rule of timeMean: sum of
+        w_j x over the steps where x is present / the sum of those w_j, float64 in step order; missing at every step: the
+        first marker (NaN without one)"""
+        slot = getattr(self, '_surfaces', None)
+        if slot is None:
+            return
+        dt = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        with numpy.errstate(over='ignore'):
+            marks = [float(dt.type(m)) for m in (slot['fill'], slot['missing']) if m == m]
+        marks = [m for m in marks if m == m]
+        if slot['nt'] == 1:
+            out = [self._as_float64(s) for s in slot['items']]
+        else:
+            idx, w = (list(range(t0, t1)), None) if table is None else table[:2]
+            out = []
+            for s in slot['items']:
+                num, den = numpy.zeros((self.ny, self.nx)), numpy.zeros((self.ny, self.nx))
+                for j, t in enumerate(idx):
+                    x = self._surface_step_host(s, t)
+                    ok = ~numpy.isnan(x)
+                    for m in marks:
+                        ok &= x != x.dtype.type(m)
+                    wj = numpy.float64(1.0 if w is None else w[j])
+                    num += numpy.where(ok, wj * numpy.where(ok, x, 0).astype(numpy.float64), 0.0)
+                    den += numpy.where(ok, wj, 0.0)
+                with numpy.errstate(invalid='ignore', divide='ignore'):
+                    out.append(numpy.where(den > 0, num / den, marks[0] if marks else numpy.nan))
+        mean.setDepthSurfaces(out, top=slot['top'], fill_value=marks[0] if marks else None,
+                              missing_value=marks[1] if len(marks) > 1 else None, wrapX=slot['wrapX'])
+
+    def computeSurfaceTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Transport of time step tIndex between the surfaces of setDepthSurfaces: (m+2, ntransect) totals and (m+2, nseg)
+        per-segment sums.  Row 0: above surface 1; row k: between surfaces k and k+1; row m: below surface m; row m+1: the
+        terms of a face where a surface has no finite value, or whose interface depth is not finite (exactly +0.0
+        otherwise).  The terms, the interface depths of the layers and the spreading are those of computeDepthTransport
+        (carry=True, setTracer first: the tracer's terms; with setCellThickness the depths are sums of the cell thicknesses
+        at the face), but the edges are the face's own: the mean of each surface in the two cells beside the face (the
+        present one when only one has a value), each raised to the surface before it, so that a surface that rises above
+        the one before it bounds a layer of zero width there.  With surfaces that are constant over the grid the rows are
+        those of computeDepthTransport with these edges, bit for bit.  The rows add up to the sum over z of the profile rows
+        (up to rounding) and go into classStreamfunction as they are.  Levels this rank does not own (slab_range)
+        contribute nothing, but the depths are summed from level 0.  Leaves everything else as it is.  `out`: as in
+        computeClassTransport."""
+        tIndex = int(tIndex)
+        slot = getattr(self, '_surfaces', None)
+        if slot is None:
+            raise RuntimeError('ERROR: call setDepthSurfaces first')
+        nrows = len(slot['items']) + 2
+        self._stage(tIndex, prefetch_next)
+        self._stage_surfaces(tIndex)
+        if carry:
+            self._stage_tracer(tIndex)
+        carry = 1 if carry else 0
+        if out is not None:
+            out = self._rows_out(out, nrows)
+            check(lib.nf_field_compute_surface_transport_async(ctypes.byref(self._h), tIndex, carry, ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((nrows, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_surface_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
         return self._split_rows(rows)
 
     def computeGrossClassTransport(self, tIndex, carry=False, out=None, prefetch_next=None):

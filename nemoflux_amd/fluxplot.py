@@ -21,6 +21,9 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --depth-bins 0,100,500,1000,6000 [--depth-top 0] [--tracer thetao] [--cell-thickness]
                                   (water flow, or the transport of thetao, in true-depth bins: a level's transport is spread over
                                   the bins its layer covers at each face -- with --cell-thickness the depths are sums of e3u / e3v)
+    ... --depth-surfaces mldr10_1,iso20 [--surface-file S.nc] [--depth-top 0] [--tracer thetao] [--cell-thickness]
+                                  (water flow, or the transport of thetao, in the layers bounded by 2-D fields: above the first
+                                  surface, between consecutive ones, below the last; a layer that a surface cuts is split)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
@@ -466,6 +469,44 @@ def checkDepthBinsArgs(depthBins='', depthTop=0.0, **others):
         raise RuntimeError(str(e).replace('--classes', '--depth-bins'))
 
 
+def surfaceSeries(tFile, uFile, vFile, lonLatZPoints, names, surfaceFile='', top=0.0, tracer='', tracerFile='', tracerRef=0.0,
+                  sverdrup=False, cellThickness=None):
+    """(nt, m+2, ntransect) water flow -- or, with `tracer`, transport of that variable of tracerFile (default: the T file) --
+    in the layers bounded by the 2-D variables `names` of surfaceFile (default: the T file), one
+    Field.computeSurfaceTransport per time step, and the Field"""
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    if tracer:
+        fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    fld.setDepthSurfaces([(surfaceFile or tFile, n) for n in names], top=top)
+    totals = numpy.array([fld.computeSurfaceTransport(t, carry=bool(tracer), prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, len(names) + 2, len(lonLatZPoints)), fld
+
+
+def parseSurfaces(text):
+    """--depth-surfaces: NAME[,NAME...], 1 to 8 variable names"""
+    names = [x.strip() for x in text.split(',')]
+    if not 1 <= len(names) <= 8 or not all(names):
+        raise RuntimeError(f"ERROR: --depth-surfaces must be NAME[,NAME...] with 1 to 8 variable names, got '{text}'")
+    return names
+
+
+def checkDepthSurfacesArgs(depthSurfaces='', surfaceFile='', depthTop=0.0, **others):
+    """the --depth-surfaces option of the command line (transports between surfaces): it combines with --surface-file,
+    --depth-top, --tracer (with --tracer-file, --tracer-ref, --tracer-scale), --cell-thickness and -s alone; refused
+    combinations raise RuntimeError"""
+    if not depthSurfaces:
+        if surfaceFile:
+            raise RuntimeError('ERROR: --surface-file needs --depth-surfaces NAME[,NAME...]')
+        return
+    for opt, on in others.items():
+        if on:
+            raise RuntimeError(f'ERROR: --depth-surfaces and {opt} cannot be combined: --depth-surfaces writes the transport in '
+                               f'every layer between the surfaces as CSV only')
+    if not numpy.isfinite(float(depthTop)):
+        raise RuntimeError(f'ERROR: --depth-top must be a finite number, got {depthTop!r}')
+    parseSurfaces(depthSurfaces)
+
+
 def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
     """the --gross option of the command line: refused combinations raise RuntimeError"""
     if not gross:
@@ -676,9 +717,39 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          tracer='', tracerFile='', tracerRef=0.0, tracerScale=1.0, classes='', levels=False, carry='', carryFile='',
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
-         classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect=''):
+         classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect='', depthSurfaces='',
+         surfaceFile=''):
     sig = None
     checkTimeMeanArgs(timeWeights, timeSelect, eddy)
+    checkDepthSurfacesArgs(depthSurfaces, surfaceFile, depthTop,
+                           **{'--depth-bins': depthBins, '--classes': classes, '--classes2': classes2,
+                              '--gross-classes': grossClasses, '--class-area': classArea, '--crossings': crossings, '--gross': gross,
+                              '--levels': levels, '--decompose': decompose, '--eddy': eddy, '--show': show, '--carry': carry,
+                              '--tracer2': tracer2, '--sigma': sigma, '--zrange': zrange,
+                              '--thickness-weighted': thicknessWeighted, '--remap': remap})
+    if depthSurfaces:
+        checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
+        checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
+        lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
+        unit = 'Sv' if sverdrup else 'A m^2/s'
+        ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+        surfaces = parseSurfaces(depthSurfaces)
+        totals, fld = surfaceSeries(tFile, uFile, vFile, lonLatZPoints, surfaces, surfaceFile, float(depthTop), tracer, tracerFile,
+                                    float(tracerRef), sverdrup, ct)
+        if tracer:
+            totals = totals * float(tracerScale)
+            title = (f'# transport of {tracer} by layer between surfaces [{tracer} x {unit}' +
+                     (f' x {float(tracerScale):g}' if float(tracerScale) != 1.0 else '') + ']')
+        else:
+            title = f'# water flow by layer between surfaces [{unit}]'
+        title += ', depths from the cell thicknesses\n' if cellThickness else '\n'
+        timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
+        bounds = list(zip(['top'] + surfaces, surfaces + ['bottom'])) + [('nan', 'nan')]
+        lines = ['time,upper,lower,' + ','.join(names)]
+        lines += [f'{timeVals[t]},{lo},{hi},' + ','.join(f'{x:.15g}' for x in totals[t, k])
+                  for t in range(fld.nt) for k, (lo, hi) in enumerate(bounds)]
+        _emit(title + '\n'.join(lines) + '\n', output)
+        return totals
     checkDepthBinsArgs(depthBins, depthTop, **{'--classes': classes, '--classes2': classes2, '--gross-classes': grossClasses,
                                                '--class-area': classArea, '--crossings': crossings, '--gross': gross,
                                                '--levels': levels, '--decompose': decompose, '--eddy': eddy, '--show': show,
@@ -947,7 +1018,16 @@ if __name__ == '__main__':
                          'of e3u / e3v at the face (partial steps, z*, s-coordinates).  With --tracer NAME the transport of NAME '
                          '(--tracer-ref, --tracer-scale apply); -s applies')
     ap.add_argument('--depth-top', dest='depthTop', type=float, default=0.0, metavar='X',
-                    help='with --depth-bins: the depth of the upper interface of the first level (default 0)')
+                    help='with --depth-bins or --depth-surfaces: the depth of the upper interface of the first level (default 0)')
+    ap.add_argument('--depth-surfaces', dest='depthSurfaces', default='', metavar='NAME[,NAME...]',
+                    help='water flow in the layers bounded by 1 to 8 two-dimensional variables at T-points (mixed-layer depth, '
+                         'the depth of an isotherm, column depth minus 200): one CSV line per time step and layer -- above the '
+                         'first surface, between consecutive surfaces, below the last, and a last one (nan,nan) for faces where '
+                         'a surface has no value.  Depths are positive downward from --depth-top; a surface that rises above '
+                         'the one before it is taken at that one.  With --tracer NAME the transport of that variable; with '
+                         '--cell-thickness the layer depths are the running sum of e3u / e3v')
+    ap.add_argument('--surface-file', dest='surfaceFile', default='', metavar='FILE',
+                    help='with --depth-surfaces: the file that holds the surfaces (default: the T file)')
     ap.add_argument('--tracer2', default='', metavar='NAME',
                     help='with --classes2: the second class field (e.g. so beside --tracer thetao); NAME is read from the T file')
     ap.add_argument('--tracer2-file', dest='tracer2File', default='', metavar='FILE', help='read --tracer2 from FILE instead')
