@@ -796,22 +796,25 @@ static int field_class_ready(const nf_field *f, const char *what)
 // Owned levels only, exact zeros for a step this rank does not touch.  Reads the raw fields, the tracer and the records; the
 // resident planes, |.| arrays, running max, last row, tracer planes, version and a captured pass stay as they are.
 // The class field is the class tracer when one is set, else the tracer.  carry = true: the transport of the tracer instead
-// of the volume (nf_field_compute_class_tracer_transport).
-static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool carry = false)
+// of the volume (nf_field_compute_class_tracer_transport).  remap = true: by conservative remapping
+// (nf_field_compute_class_remap, launch_class_remap); its kernel reads the class field one level above and one below the owned
+// ones, so a host-resident class field is staged with that halo level on each side (an HBM one is read in place).
+static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool carry = false, bool remap = false)
 {
     const int nedges = (int)f->class_edges.host.size();
+    const char *what = remap ? "compute_class_remap" : carry ? "compute_class_tracer_transport" : "compute_class_transport";
     Levels lv;
-    NF_TRY(field_raw_step_begin(f, carry ? "compute_class_tracer_transport" : "compute_class_transport", t, 2, rows_dev,
-                                (size_t)nedges + 2, &lv));
+    NF_TRY(field_raw_step_begin(f, what, t, 2, rows_dev, (size_t)nedges + 2, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
     const int window = g_class_window;
     NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
+    const Levels cls_lv = remap ? Levels{std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)} : lv;
     ClassArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.cls));
-    if (carry) a.carry = a.cls;                                                    // the tracer is carried ...
-    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.cls));   // ... and binned by the class tracer
+    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : cls_lv, &a.cls));
+    if (carry) a.carry = a.cls;                                                     // the tracer is carried ...
+    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, cls_lv, &a.cls));   // ... and binned by the class tracer
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
     a.window = window;
@@ -819,36 +822,8 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool ca
     a.scratch = f->class_scratch.get();
     a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
-    return launch_class_transport(a, f->stream);
-}
-
-// The class transport of step t by conservative remapping (nf_field_compute_class_remap): field_class_step_async with
-// launch_class_remap.  Its kernel reads the class field one level above and one below the owned ones, so a host-resident class
-// field is staged with that halo level on each side (an HBM one is read in place).
-static int field_class_remap_step_async(nf_field *f, long t, double *rows_dev, bool carry)
-{
-    const int nedges = (int)f->class_edges.host.size();
-    Levels lv;
-    NF_TRY(field_raw_step_begin(f, "compute_class_remap", t, 2, rows_dev, (size_t)nedges + 2, &lv));
-    if (lv.z1 <= lv.z0) return NF_OK;
-    NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
-    const int window = g_class_window;
-    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
-    const Levels halo{std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)};
-    ClassArgs a;
-    NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : halo, &a.cls));
-    if (carry) a.carry = a.cls;                                                    // the tracer is carried ...
-    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, halo, &a.cls));   // ... and binned by the class tracer
-    a.edges = f->class_edges.dev.get();
-    a.nedges = nedges;
-    a.window = window;
-    a.tr = field_transects(f);
-    a.scratch = f->class_scratch.get();
-    a.scratch_len = f->class_scratch.size();
-    a.rows = rows_dev;
-    a.remap_nz = (int)f->nz;
-    return launch_class_remap(a, f->stream);
+    a.remap_nz = (int)f->nz;   // read by launch_class_remap only
+    return remap ? launch_class_remap(a, f->stream) : launch_class_transport(a, f->stream);
 }
 
 // Transports in depth bins of step t on the field's stream (nf_field_compute_depth_transport): rows_dev (nedges + 2,
@@ -933,6 +908,36 @@ static int field_joint_ready(const nf_field *f, const char *what)
 
 static size_t field_joint_rows(const nf_field *f) { return (size_t)(f->joint_na + 2) * (size_t)(f->joint_nb + 2); }
 
+// The term table, flags and run sums of a product that bins a term table (joint classes, gross classes, class area) into
+// `nrows` rows, with the window and skip knobs, in the arguments *a: the field's joint buffers, grown to the need of entry_bytes
+// per (record, owned level).  11.6 GB on the bench workload: a failure names the size, and nothing falls back to another path.
+template <typename Args>
+static int field_joint_buffers(nf_field *f, const char *what, size_t entry_bytes, const Levels &lv, size_t nrows, Args *a)
+{
+    const int window = g_joint_window;
+    const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
+    const size_t table_bytes = entry_bytes * nrec * (size_t)(lv.z1 - lv.z0);
+    if (f->joint_table.size() == 0 || f->joint_table.size() < table_bytes) {
+        if (f->joint_table.alloc(table_bytes) != NF_OK) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "%s: cannot allocate the term table of %zu bytes (%zu bytes x %zu records x %d owned levels)",
+                     what, table_bytes, entry_bytes, nrec, lv.z1 - lv.z0);
+            NF_REQUIRE(false, NF_ERR_HIP, buf);
+        }
+    }
+    NF_TRY(f->joint_flags.reserve(blocks * (size_t)joint_flag_words((int)nrows, window)));
+    NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
+    a->window = window;
+    a->skip = g_joint_skip;
+    a->table = f->joint_table.get();
+    a->table_len = f->joint_table.size();
+    a->flags = f->joint_flags.get();
+    a->flags_len = f->joint_flags.size();
+    a->scratch = f->joint_scratch.get();
+    a->scratch_len = f->joint_scratch.size();
+    return NF_OK;
+}
+
 // Transport of step t in joint classes of the tracer (axis A) and the class tracer (axis B) on the field's stream: rows_dev
 // ((na + 2) * (nb + 2), row_length), written whole.  Owned levels only, exact zeros for a step this rank does not touch.
 // Reads the raw fields, both tracers and the records; the resident planes, |.| arrays, running max, last row, tracer planes,
@@ -944,23 +949,8 @@ static int field_joint_step_async(nf_field *f, long t, bool carry, double *rows_
     NF_TRY(field_raw_step_begin(f, "compute_joint_class_transport", t, 2, rows_dev, nrows, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->joint_edges.upload(2 * (size_t)kMaxClassEdges, f->stream));
-    const int window = g_joint_window;
-    const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
-    const size_t table_bytes = kJointEntryBytes * nrec * (size_t)(lv.z1 - lv.z0);
-    if (f->joint_table.size() == 0 || f->joint_table.size() < table_bytes) {
-        // 11.6 GB on the bench workload: a failure names the size, and nothing falls back to another path
-        if (f->joint_table.alloc(table_bytes) != NF_OK) {
-            char buf[256];
-            snprintf(buf, sizeof buf,
-                     "compute_joint_class_transport: cannot allocate the term table of %zu bytes (40 bytes x %zu records x %d "
-                     "owned levels)",
-                     table_bytes, nrec, lv.z1 - lv.z0);
-            NF_REQUIRE(false, NF_ERR_HIP, buf);
-        }
-    }
-    NF_TRY(f->joint_flags.reserve(blocks * (size_t)joint_flag_words((int)nrows, window)));
-    NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
     JointArgs a;
+    NF_TRY(field_joint_buffers(f, "compute_joint_class_transport", kJointEntryBytes, lv, nrows, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
     NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.ta));
     NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.tb));
@@ -968,15 +958,7 @@ static int field_joint_step_async(nf_field *f, long t, bool carry, double *rows_
     a.edges = f->joint_edges.dev.get();
     a.na = f->joint_na;
     a.nb = f->joint_nb;
-    a.window = window;
-    a.skip = g_joint_skip;
     a.tr = field_transects(f);
-    a.table = f->joint_table.get();
-    a.table_len = f->joint_table.size();
-    a.flags = f->joint_flags.get();
-    a.flags_len = f->joint_flags.size();
-    a.scratch = f->joint_scratch.get();
-    a.scratch_len = f->joint_scratch.size();
     a.rows = rows_dev;
     return launch_joint_class_transport(a, f->stream);
 }
@@ -996,22 +978,8 @@ static int field_gross_class_async(nf_field *f, long t, bool carry, double *rows
     NF_TRY(field_raw_step_begin(f, "compute_gross_class_transport", t, 2, rows_dev, nrows, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
-    const int window = g_joint_window;
-    const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
-    const size_t table_bytes = kJointEntryBytes * nrec * (size_t)(lv.z1 - lv.z0);
-    if (f->joint_table.size() == 0 || f->joint_table.size() < table_bytes) {
-        if (f->joint_table.alloc(table_bytes) != NF_OK) {
-            char buf[256];
-            snprintf(buf, sizeof buf,
-                     "compute_gross_class_transport: cannot allocate the term table of %zu bytes (40 bytes x %zu records x %d "
-                     "owned levels)",
-                     table_bytes, nrec, lv.z1 - lv.z0);
-            NF_REQUIRE(false, NF_ERR_HIP, buf);
-        }
-    }
-    NF_TRY(f->joint_flags.reserve(blocks * (size_t)joint_flag_words((int)nrows, window)));
-    NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
     GrossClassArgs a;
+    NF_TRY(field_joint_buffers(f, "compute_gross_class_transport", kJointEntryBytes, lv, nrows, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
     NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.cls));
     if (carry) a.carry = a.cls;                                                    // the tracer is carried ...
@@ -1019,15 +987,7 @@ static int field_gross_class_async(nf_field *f, long t, bool carry, double *rows
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
-    a.window = window;
-    a.skip = g_joint_skip;
     a.tr = field_transects(f);
-    a.table = f->joint_table.get();
-    a.table_len = f->joint_table.size();
-    a.flags = f->joint_flags.get();
-    a.flags_len = f->joint_flags.size();
-    a.scratch = f->joint_scratch.get();
-    a.scratch_len = f->joint_scratch.size();
     a.rows = rows_dev;
     return launch_gross_class_transport(a, f->stream);
 }
@@ -1047,21 +1007,8 @@ static int field_class_area_async(nf_field *f, long t, double *rows_dev)
     NF_TRY(field_raw_step_begin(f, "compute_class_area", t, 2, rows_dev, nrows, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
-    const int window = g_joint_window;
-    const size_t nrec = (size_t)f->ws.nrec, blocks = (nrec + kBlock - 1) / kBlock;
-    const size_t table_bytes = kClassAreaEntryBytes * nrec * (size_t)(lv.z1 - lv.z0);
-    if (f->joint_table.size() == 0 || f->joint_table.size() < table_bytes) {
-        if (f->joint_table.alloc(table_bytes) != NF_OK) {
-            char buf[256];
-            snprintf(buf, sizeof buf,
-                     "compute_class_area: cannot allocate the term table of %zu bytes (80 bytes x %zu records x %d owned levels)",
-                     table_bytes, nrec, lv.z1 - lv.z0);
-            NF_REQUIRE(false, NF_ERR_HIP, buf);
-        }
-    }
-    NF_TRY(f->joint_flags.reserve(blocks * (size_t)joint_flag_words((int)nrows, window)));
-    NF_TRY(f->joint_scratch.reserve(nrec * (size_t)window));
     ClassAreaArgs a;
+    NF_TRY(field_joint_buffers(f, "compute_class_area", kClassAreaEntryBytes, lv, nrows, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
     NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.carry));
     a.cls = a.carry;                                                               // the tracer is carried ...
@@ -1069,15 +1016,7 @@ static int field_class_area_async(nf_field *f, long t, double *rows_dev)
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
-    a.window = window;
-    a.skip = g_joint_skip;
     a.tr = field_transects(f);
-    a.table = f->joint_table.get();
-    a.table_len = f->joint_table.size();
-    a.flags = f->joint_flags.get();
-    a.flags_len = f->joint_flags.size();
-    a.scratch = f->joint_scratch.get();
-    a.scratch_len = f->joint_scratch.size();
     a.rows = rows_dev;
     return launch_class_area(a, f->stream);
 }
@@ -1790,7 +1729,7 @@ try {
     NF_NEED_DEVICE();
     const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
     if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_remap_step_async(f, tIndex, rows, carry != 0); });
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows, carry != 0, true); });
 }
 NF_API_CATCH
 
@@ -1802,7 +1741,7 @@ try {
     NF_TRY(field_class_ready(f, "nf_field_compute_class_remap_async"));
     NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_remap_async"));
     NF_NEED_DEVICE();
-    return field_class_remap_step_async(f, tIndex, rows_dev, carry != 0);
+    return field_class_step_async(f, tIndex, rows_dev, carry != 0, true);
 }
 NF_API_CATCH
 

@@ -232,6 +232,155 @@ __device__ inline auto step_neighbours(long c, unsigned nx, long ncell, int wrap
         return neighbours(c, nx);
 }
 
+// ---- the pieces of the windowed-row kernels (class, remap, depth, surface, joint bin) -----------------------------------------
+// A lane keeps one accumulator per row of the window [r0, r0 + nwin) as a column of LDS, acc[q * STRIDE] with acc already
+// offset by the lane (a dynamic row index in registers would go to scratch); STRIDE: the lanes of a workgroup.  The order in
+// which a lane adds to a row, and the scan, are what the rows' bit-for-bit identities rest on: they live here only.
+// window_add: x to row `row` when it lies in the window.
+template <int STRIDE>
+__device__ inline void window_add(double *acc, int row, int r0, int nwin, double x)
+{
+    const int q = row - r0;
+    if (q >= 0 && q < nwin) acc[q * STRIDE] += x;
+}
+
+// window_scan_store: the flags of all six scan steps formed once and kept as bits, then seg_scan_step once per row of the
+// window; the last lane of a run stores row q of the window to runsum[q * n + k].
+template <int STRIDE>
+__device__ inline void window_scan_store(const double *acc, int key, int lane, long k, long n, int nwin, double *__restrict__ runsum)
+{
+    unsigned take = 0;
+#pragma unroll
+    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
+        if (seg_scan_take(key, lane, o)) take |= 1u << b;
+    const bool store = seg_run_end(key, lane, k, n);
+    for (int q = 0; q < nwin; ++q) {
+        double val[1] = {k < n ? acc[q * STRIDE] : 0.0};
+#pragma unroll
+        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
+        if (store) runsum[(long)q * n + k] = val[0];
+    }
+}
+
+// The LDS of a kBlock workgroup with one edge table: the edges (nedges doubles, padded to even), then nwin x kBlock
+// accumulators.  window_lds copies the edges, zeroes the lane's column and returns after the barrier (for the edges: every
+// lane touches only its own accumulators).
+struct WindowLds {
+    const double *e;
+    double *acc;   // acc[q * kBlock]: this lane's row r0 + q
+};
+__device__ inline WindowLds window_lds(const double *__restrict__ edges, int nedges, int nwin)
+{
+    extern __shared__ double class_lds[];
+    double *e = class_lds;
+    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;
+    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
+    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
+    __syncthreads();
+    return WindowLds{e, acc};
+}
+
+// Where a term goes among rows bounded by non-decreasing edges: the rows jlo .. jhi of the interval [lo, hi], or (jhi < 0)
+// whole to row jlo.  make_span: the interval between a and b; whole to row `none` where !ok or a, b or their difference is not
+// finite.  rows(lo, hi): the kernel's row lookup, which returns the span of lo <= hi: whole to the row of lo where lo == hi.
+// (The lookup decides how: class_row looks hi up only where lo < hi, the linear count takes both in one pass.)
+struct RowSpan {
+    double lo, hi;
+    int jlo, jhi;
+};
+template <typename Rows>
+__device__ inline RowSpan make_span(bool ok, double a, double b, int none, Rows rows)
+{
+    if (!(ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(b - a))) return RowSpan{0.0, 0.0, none, -1};
+    const double lo = a < b ? a : b, hi = a < b ? b : a;
+    return rows(lo, hi);
+}
+
+// The share rule: the term t spread uniformly over [lo, hi]; row j gets  t * ((right - left) / (hi - lo))  with [left, right]
+// the part of the interval inside the row, rows ascending, the loop clipped to the window [r0, rend] first.  e[j * ESTRIDE]:
+// the upper edge of row j.  add_span: that, or the whole term to row jlo.  k_depth_segscan's `put` is a written-out copy of
+// add_span<kBlock, 1> (the reason is there): keep the two alike.
+template <int STRIDE, int ESTRIDE>
+__device__ inline void spread_span(double *acc, const double *e, const RowSpan &p, double t, int r0, int rend)
+{
+    const double width = p.hi - p.lo;
+    const int ja = p.jlo > r0 ? p.jlo : r0, jb = p.jhi < rend ? p.jhi : rend;
+    for (int j = ja; j <= jb; ++j) {
+        const double left = j == p.jlo ? p.lo : e[(j - 1) * ESTRIDE], right = j == p.jhi ? p.hi : e[j * ESTRIDE];
+        if (right != left) acc[(j - r0) * STRIDE] += t * ((right - left) / width);
+    }
+}
+template <int STRIDE, int ESTRIDE>
+__device__ inline void add_span(double *acc, const double *e, const RowSpan &p, double t, int r0, int nwin)
+{
+    if (p.jhi < 0) return window_add<STRIDE>(acc, p.jlo, r0, nwin, t);
+    spread_span<STRIDE, ESTRIDE>(acc, e, p, t, r0, r0 + nwin - 1);
+}
+
+// The depth walk of a record: D, the depth of the upper interface of the next level at the four faces, starts at `surface`
+// and grows by the thickness at each slot's own face -- level_th of the gathered e3u / e3v (CT: four running depths per lane)
+// or thickness[z] (one) -- one float64 addition per level.  Levels [0, z0) of a partial slab only move the depths: with
+// per-cell thicknesses their four gathers per level are issued kDepthLevels levels at a time, nothing else is read.  Owned
+// levels go kDepthLevels at a time too, all gathers of a batch (4 per level, + 4 with CT, + 5 with a carried tracer, TR) issued
+// before the first is used; each owned level, z ascending, is handed to  level(D, Dn, d, south):  its upper and lower depths,
+// the four slot terms (k_gross_segscan's: level_slots_tf with the thickness at the face) and whether the south slot exists.
+// The terms come without their weights: the callee forms each product where it adds it, so that the south product exists
+// only under `if (south)` (formed here, ahead of that branch, it costs the surface kernel registers).  The callee adds in
+// slot order: south (if there) r.wa.x * d.s, east r.wa.y * d.e, north r.wb.x * d.n, west r.wb.y * d.w.
+constexpr int kDepthLevels = 4;
+template <typename T, bool TR, bool CT, typename NB, typename F>
+__device__ inline void depth_walk(const Record &r, const NB &nb, const Arcs &arc, const T *__restrict__ u, const T *__restrict__ v,
+                                  long ncell, int z0, int z1, const double *__restrict__ thickness, T fill, T fill2, int two,
+                                  double scale, int sverdrup, const TauIn<T> &ti, const ThickIn<T> &ct, double surface, F level)
+{
+    constexpr int DL = kDepthLevels;
+    SlotTh D = slot_th(surface);
+    auto below = [](const SlotTh &d, const SlotTh &th) { return SlotTh{d.e + th.e, d.n + th.n, d.s + th.s, d.w + th.w}; };
+    for (int z = 0; z < z0; z += DL) {   // above the owned levels: the depths move, no term
+        const int nlev = z0 - z < DL ? z0 - z : DL;
+        if constexpr (CT) {
+            LevelUV<T> e3[DL];
+#pragma unroll
+            for (int l = 0; l < DL; ++l)
+                if (l < nlev) e3[l] = load_level_e3(ct, (long)(z + l) * ncell, r.c, nb);
+#pragma unroll
+            for (int l = 0; l < DL; ++l)
+                if (l < nlev) D = below(D, level_th(e3[l], ct));
+        } else {
+            for (int l = 0; l < nlev; ++l) D = below(D, slot_th(thickness[z + l]));
+        }
+    }
+    for (int z = z0; z < z1; z += DL) {
+        const int nlev = z1 - z < DL ? z1 - z : DL;
+        LevelUV<T> x[DL];
+        LevelTau<T> tt[TR ? DL : 1];
+        LevelUV<T> e3[CT ? DL : 1];
+#pragma unroll
+        for (int l = 0; l < DL; ++l)
+            if (l < nlev) {
+                const long o = (long)(z + l) * ncell;
+                x[l] = load_level_uv(u, v, o, r.c, nb);
+                if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
+                if constexpr (TR) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
+            }
+#pragma unroll
+        for (int l = 0; l < DL; ++l)
+            if (l < nlev) {
+                FaceTf tf{};
+                if constexpr (TR) tf = level_tf(tt[l], nb, ti);
+                SlotTh th;
+                if constexpr (CT)
+                    th = level_th(e3[l], ct);
+                else
+                    th = slot_th(thickness[z + l]);
+                const Slots d = level_slots_tf<T, TR>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, tf);
+                const SlotTh Dn = below(D, th);
+                level(D, Dn, d, nb.south);
+                D = Dn;
+            }
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_gather_segscan(const int *__restrict__ cell,
                                                            const double *__restrict__ w4,
                                                            const int *__restrict__ seg, long n,
@@ -825,15 +974,22 @@ static int launch_gross_t(const GrossArgs &a, hipStream_t s, TI... extra)
     return NF_OK;
 }
 
-// the four forms of one dtype and chunk: volume or carried tracer, each with the scalar or the per-cell thicknesses
+// the four forms of one dtype: volume or carried tracer, each with the scalar or the per-cell thicknesses, as the trailing
+// arguments of launch(...); the gross profile's, the depth bins' and the surface bins'
+template <typename T, typename F>
+static int launch_tracer_thick_form(const TracerIn &t, const CellThick &th, F launch)
+{
+    const TauIn<T> ti = tau_of<T>(t);
+    if (t.tau && th.e3u) return launch(ti, thick_in<T>(th));
+    if (t.tau) return launch(ti);
+    if (th.e3u) return launch(thick_in<T>(th));
+    return launch();
+}
+
 template <typename T, int LZ>
 static int launch_gross_form(const GrossArgs &a, hipStream_t s)
 {
-    const TauIn<T> ti = tau_of<T>(a.t);
-    if (a.t.tau && a.th.e3u) return launch_gross_t<T, LZ>(a, s, ti, thick_in<T>(a.th));
-    if (a.t.tau) return launch_gross_t<T, LZ>(a, s, ti);
-    if (a.th.e3u) return launch_gross_t<T, LZ>(a, s, thick_in<T>(a.th));
-    return launch_gross_t<T, LZ>(a, s);
+    return launch_tracer_thick_form<T>(a.t, a.th, [&](auto... extra) { return launch_gross_t<T, LZ>(a, s, extra...); });
 }
 
 int launch_gross_profile(const GrossArgs &a, hipStream_t s)
@@ -996,13 +1152,11 @@ int launch_crossing_terms(const CrossingArgs &a, hipStream_t s)
 // ---- volume transport in tracer classes: level_slots, each term sent to the row of its face's class -------------------
 // One lane per record, K3's record order and 64-record waves.  Per owned level (z ascending) the four slot terms are
 // level_slots' times their weights; each is added, in slot order (south, east, north, west), to the lane's accumulator of the
-// row that its own face's class value selects, when that row lies in the window [r0, r0 + nwin).  The accumulators are a column
-// of LDS per lane (a dynamic row index in registers would go to scratch).  Then seg_scan_step runs once per row of the
-// window with the one set of flags.  With one class per level (tau = z) a row gets exactly one level's four terms, added as
-// ((0 + t0) + t1) + t2) + t3: weighted_sum's ((t0 + t1) + t2) + t3, bit for bit.
+// row that its own face's class value selects (class_row), when that row lies in the window [r0, r0 + nwin): window_lds,
+// window_add and window_scan_store, the window pieces above.  With one class per level (tau = z) a row gets exactly one
+// level's four terms, added as ((0 + t0) + t1) + t2) + t3: weighted_sum's ((t0 + t1) + t2) + t3, bit for bit.
 //   faces: east(c) = (tau[c], tau[c+1]; column nx-1: tau[c+1-nx] when wrap_x, else none), north(c) = (tau[c], tau[c+nx];
 //   last row: none), the west slot is east(cw), the south slot north(cs).
-// LDS: the edges (nedges doubles, padded to even), then nwin x kBlock accumulators.
 // CARRY: the carried-tracer form, every term times tr_face of the carried tracer at its own face (level_slots_tf).  TWO: the
 // class field and the carried tracer are different arrays (5 more gathers per level); otherwise the one set of values serves
 // both.
@@ -1035,12 +1189,7 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
     constexpr bool CARRY = sizeof...(TI) > 0;
     constexpr int CL = TWO ? kClassLevelsTwo : kClassLevels;
     const TauIn<T> ti = tau_in<T>(tracer...);
-    extern __shared__ double class_lds[];
-    double *e = class_lds;
-    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
-    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
-    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
-    __syncthreads();   // the edges; every lane touches only its own accumulators
+    const WindowLds w = window_lds(edges, nedges, nwin);
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
     int key = -1;
@@ -1049,10 +1198,8 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
         key = load_key(seg, k);
         const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, wrap_x);
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
-        auto add = [&](int row, double x) {
-            const int q = row - r0;
-            if (q >= 0 && q < nwin) acc[q * kBlock] += x;
-        };
+        // x to the row of the face value f (has: the face has one)
+        auto add = [&](bool has, double f, double x) { window_add<kBlock>(w.acc, class_row(has, f, w.e, nedges, top), r0, nwin, x); };
         for (int z = z0; z < z1; z += CL) {
             const int nlev = z1 - z < CL ? z1 - z : CL;
             LevelUV<T> x[CL];
@@ -1081,41 +1228,31 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
                     bool h;
                     if (nb.south) {
                         h = tr_face_raw<T>(ts[l], tc[l], true, tfill, tfill2, &f);
-                        add(class_row(h, f, e, nedges, top), r.wa.x * d.s);
+                        add(h, f, r.wa.x * d.s);
                     }
                     h = tr_face_raw<T>(tc[l], te[l], nb.has_e, tfill, tfill2, &f);
-                    add(class_row(h, f, e, nedges, top), r.wa.y * d.e);
+                    add(h, f, r.wa.y * d.e);
                     h = tr_face_raw<T>(tc[l], tn[l], nb.has_n, tfill, tfill2, &f);
-                    add(class_row(h, f, e, nedges, top), r.wb.x * d.n);
+                    add(h, f, r.wb.x * d.n);
                     h = tr_face_raw<T>(tw[l], tc[l], nb.has_w, tfill, tfill2, &f);
-                    add(class_row(h, f, e, nedges, top), r.wb.y * d.w);
+                    add(h, f, r.wb.y * d.w);
                 }
         }
     }
-    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
-#pragma unroll
-    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
-        if (seg_scan_take(key, lane, o)) take |= 1u << b;
-    const bool store = seg_run_end(key, lane, k, n);
-    for (int r = 0; r < nwin; ++r) {
-        double val[1] = {k < n ? acc[r * kBlock] : 0.0};
-#pragma unroll
-        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
-        if (store) runsum[(long)r * n + k] = val[0];
-    }
+    window_scan_store<kBlock>(w.acc, key, lane, k, n, nwin, runsum);
 }
 
 // ---- conservative (piecewise-linear) remapping of the class transport -----------------------------------------------------
 // k_class_segscan with another rule for the row: the class field is taken to vary linearly between the interfaces of a layer,
 // and a term is spread uniformly in class space over the interval between its face's two interface values
 //   g_up = 0.5 (f[z-1] + f[z]) where z > 0 and the face has a value at level z - 1, else f[z];  g_dn likewise with z + 1 < nz;
-// row j gets the share of [lo, hi] = [min, max](g_up, g_dn) that lies in it,  t * ((right - left) / (hi - lo)).  Whole to
-// class_row(f[z]) (the step rule) where g_up, g_dn or their difference is not finite, whole to class_row(lo) where lo == hi,
-// whole to row nedges + 1 without a class value.  Per lane the adds run level-ascending, then in slot order, then
-// row-ascending; a term's row loop is clipped to the window first.  Levels z - 1 and z + 1 are levels of the ARRAY (nz of them),
-// not of the owned range: the first and the last owned level read one halo level each.
+// row j gets the share of [lo, hi] = [min, max](g_up, g_dn) that lies in it (spread_span).  Whole to class_row(f[z]) (the
+// step rule) where g_up, g_dn or their difference is not finite, whole to class_row(lo) where lo == hi, whole to row
+// nedges + 1 without a class value: these fallbacks are this kernel's own, not make_span's.  Per lane the adds run
+// level-ascending, then in slot order, then row-ascending.  Levels z - 1 and z + 1 are levels of the ARRAY (nz of them), not of
+// the owned range: the first and the last owned level read one halo level each.
 // The class field's five gathers are issued once per level: c[] is a rolling window of levels z - 1 .. z + RL whose first two
-// members come from the batch before.  LDS, scan and stores: k_class_segscan's.
+// members come from the batch before.
 constexpr int kRemapLevels = 4;        // levels whose 9 gathers are issued together (volume form, one-tracer carry form)
 constexpr int kRemapLevelsTwo = 2;     // ... whose 14 gathers are (carry form with a class field of its own)
 
@@ -1134,12 +1271,7 @@ __global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__res
     constexpr bool CARRY = sizeof...(TI) > 0;
     constexpr int RL = TWO ? kRemapLevelsTwo : kRemapLevels;
     const TauIn<T> ti = tau_in<T>(tracer...);
-    extern __shared__ double class_lds[];
-    double *e = class_lds;
-    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
-    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
-    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
-    __syncthreads();   // the edges; every lane touches only its own accumulators
+    const WindowLds w = window_lds(edges, nedges, nwin);
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
     int key = -1;
@@ -1149,10 +1281,8 @@ __global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__res
         const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, wrap_x);
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
         const int rend = r0 + nwin - 1;
-        auto add = [&](int row, double x) {
-            const int q = row - r0;
-            if (q >= 0 && q < nwin) acc[q * kBlock] += x;
-        };
+        auto add = [&](int row, double x) { window_add<kBlock>(w.acc, row, r0, nwin, x); };
+        auto row = [&](double x) { return class_row(true, x, w.e, nedges, top); };
         // the term t of the face (a, b) at a level whose class values are (a1, b1), with (a0, b0) above and (a2, b2) below
         auto spread = [&](T a0, T b0, T a1, T b1, T a2, T b2, bool has_b, bool up, bool dn, double t) {
             double f, fu = 0.0, fd = 0.0;
@@ -1161,18 +1291,11 @@ __global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__res
             const bool hu = up && tr_face_raw<T>(a0, b0, has_b, tfill, tfill2, &fu);
             const bool hd = dn && tr_face_raw<T>(a2, b2, has_b, tfill, tfill2, &fd);
             const double gu = hu ? 0.5 * (fu + f) : f, gd = hd ? 0.5 * (fd + f) : f;
-            if (!(__builtin_isfinite(gu) && __builtin_isfinite(gd) && __builtin_isfinite(gd - gu)))
-                return add(class_row(true, f, e, nedges, top), t);
+            if (!(__builtin_isfinite(gu) && __builtin_isfinite(gd) && __builtin_isfinite(gd - gu))) return add(row(f), t);
             const double lo = gu < gd ? gu : gd, hi = gu < gd ? gd : gu;
-            const int jlo = class_row(true, lo, e, nedges, top);
+            const int jlo = row(lo);
             if (lo == hi) return add(jlo, t);
-            const int jhi = class_row(true, hi, e, nedges, top);
-            const double width = hi - lo;
-            const int ja = jlo > r0 ? jlo : r0, jb = jhi < rend ? jhi : rend;
-            for (int j = ja; j <= jb; ++j) {
-                const double left = j == jlo ? lo : e[j - 1], right = j == jhi ? hi : e[j];
-                if (right != left) acc[(j - r0) * kBlock] += t * ((right - left) / width);
-            }
+            spread_span<kBlock, 1>(w.acc, w.e, RowSpan{lo, hi, jlo, row(hi)}, t, r0, rend);
         };
         LevelTau<T> c[RL + 2];   // the class field of levels z - 1 .. z + RL
         c[1] = load_level_tau(tau, (long)z0 * ncell, r.c, nb);
@@ -1207,73 +1330,83 @@ __global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__res
             c[1] = c[RL + 1];
         }
     }
-    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
-#pragma unroll
-    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
-        if (seg_scan_take(key, lane, o)) take |= 1u << b;
-    const bool store = seg_run_end(key, lane, k, n);
-    for (int r = 0; r < nwin; ++r) {
-        double val[1] = {k < n ? acc[r * kBlock] : 0.0};
-#pragma unroll
-        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
-        if (store) runsum[(long)r * n + k] = val[0];
-    }
+    window_scan_store<kBlock>(w.acc, key, lane, k, n, nwin, runsum);
 }
-
 
 // same bits of two doubles (NaN included): the markers of two tracer slots agree
 static bool same_bits(double a, double b) { return __builtin_memcmp(&a, &b, sizeof a) == 0; }
 
-// FORM: 0 = volume, 1 = carried tracer that is the class field, 2 = carried tracer and a class field of its own
-template <typename T, int FORM>
-static int launch_class_t(const ClassArgs &a, hipStream_t s)
+// ---- the host side of the windowed rows ----
+// class_top: the largest power of two <= nedges, class_row's first step.  class_lds_bytes: window_lds' layout.
+static int class_top(int nedges)
 {
-    const WeightSet &ws = *a.tr.ws;
-    const StepInput &in = a.in;
-    const long row_length = a.tr.row_length();
-    const T fill = (T)in.fill, fill2 = (T)in.fill2;
     int top = 1;
-    while (2 * top <= a.nedges) top *= 2;
-    const int nrows = a.nedges + 2;
-    for (int r0 = 0; r0 < nrows; r0 += a.window) {
-        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
-        const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
-        if (ws.nrec > 0) {
-            if constexpr (FORM == 0) {
-                if (lds > 65536)
-                    NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T, false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_class_segscan<T, false>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
-                                   ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau, in.ncell,
-                                   (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
-                                   (int)uv_two_markers(fill, fill2), (T)a.cls.fill, (T)a.cls.fill2, a.cls.wrap_x ? 1 : 0, in.scale,
-                                   in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch);
-            } else {
-                if (lds > 65536)
-                    NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_class_segscan<T, FORM == 2, TauIn<T>>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_class_segscan<T, FORM == 2, TauIn<T>>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(),
-                                   ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau,
-                                   in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2,
-                                   (int)uv_two_markers(fill, fill2), (T)a.cls.fill, (T)a.cls.fill2, a.cls.wrap_x ? 1 : 0, in.scale,
-                                   in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch,
-                                   TauIn<T>{(const T *)a.carry.tau, (T)a.carry.fill, (T)a.carry.fill2, a.carry.ref,
-                                            a.cls.wrap_x ? 1 : 0});
-            }
-        }
-        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
-                        (unsigned)nwin, s);
+    while (2 * top <= nedges) top *= 2;
+    return top;
+}
+static size_t class_lds_bytes(int nedges, int nwin) { return sizeof(double) * ((size_t)((nedges + 1) & ~1) + (size_t)nwin * kBlock); }
+
+// a launch with `lds` bytes of dynamic LDS: above 64 KiB the kernel's limit is raised first
+template <typename K, typename... A>
+static int launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args)
+{
+    if (lds > 65536)
+        NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return NF_OK;
+}
+
+// The passes over `nrows` rows, `window` rows at a time: pass(r0, nwin, win) launches the kernel that leaves the run sums of
+// rows [r0, r0 + nwin), window number `win`, in `scratch` (not called without records); each pass is finalized into its rows
+// of `rows` (nrows, row_length).
+template <typename F>
+static int for_each_window(const Transects &tr, int nrows, int window, double *scratch, double *rows, hipStream_t s, F pass)
+{
+    const WeightSet &ws = *tr.ws;
+    const long row_length = tr.row_length();
+    for (int r0 = 0, win = 0; r0 < nrows; r0 += window, ++win) {
+        const int nwin = nrows - r0 < window ? nrows - r0 : window;
+        if (ws.nrec > 0) NF_TRY(pass(r0, nwin, win));
+        launch_finalize(tr, ws.seg_start.get(), ws.nrec, scratch, rows + (long)r0 * row_length, row_length, (unsigned)nwin, s);
         NF_HIP(hipGetLastError());
     }
     return NF_OK;
 }
 
-template <typename T>
+// k_class_segscan or (REMAP) k_class_remap_segscan over the windows.  FORM: 0 = volume, 1 = carried tracer that is the class
+// field, 2 = carried tracer and a class field of its own.  The kernel of the form takes trailing arguments of its own: the
+// array's levels (REMAP), then the carried tracer (FORM > 0).
+template <typename T, int FORM, bool REMAP>
+static int launch_class_t(const ClassArgs &a, hipStream_t s)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    const int top = class_top(a.nedges), wrap_x = a.cls.wrap_x ? 1 : 0;
+    // the carried tracer with the class field's wrap rule; empty and not passed in the volume form (FORM == 0)
+    const TauIn<T> carry{(const T *)a.carry.tau, (T)a.carry.fill, (T)a.carry.fill2, a.carry.ref, wrap_x};
+    return for_each_window(a.tr, a.nedges + 2, a.window, a.scratch, a.rows, s, [&](int r0, int nwin, int) {
+        // the arguments that the two kernels share, then `tail` in the kernel's own order: remap_nz first, carry last
+        auto launch = [&](auto kernel, auto... tail) {
+            return launch_lds(kernel, record_grid(ws), dim3(kBlock), class_lds_bytes(a.nedges, nwin), s, ws.cell.get(), ws.w4.get(),
+                              ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau, in.ncell, (unsigned)in.nx,
+                              in.z0, in.z1, in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2),
+                              (T)a.cls.fill, (T)a.cls.fill2, wrap_x, in.scale, in.sverdrup, a.edges, a.nedges, top, r0, nwin,
+                              a.scratch, tail...);
+        };
+        if constexpr (REMAP && FORM == 0) return launch(&k_class_remap_segscan<T, false>, a.remap_nz);
+        if constexpr (REMAP && FORM > 0) return launch(&k_class_remap_segscan<T, FORM == 2, TauIn<T>>, a.remap_nz, carry);
+        if constexpr (!REMAP && FORM == 0) return launch(&k_class_segscan<T, false>);
+        if constexpr (!REMAP && FORM > 0) return launch(&k_class_segscan<T, FORM == 2, TauIn<T>>, carry);
+    });
+}
+
+template <typename T, bool REMAP>
 static int launch_class_form(const ClassArgs &a, hipStream_t s)
 {
-    if (!a.carry.tau) return launch_class_t<T, 0>(a, s);
+    if (!a.carry.tau) return launch_class_t<T, 0, REMAP>(a, s);
     const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
-    return one ? launch_class_t<T, 1>(a, s) : launch_class_t<T, 2>(a, s);
+    return one ? launch_class_t<T, 1, REMAP>(a, s) : launch_class_t<T, 2, REMAP>(a, s);
 }
 
 int launch_class_transport(const ClassArgs &a, hipStream_t s)
@@ -1285,57 +1418,9 @@ int launch_class_transport(const ClassArgs &a, hipStream_t s)
     NF_REQUIRE(in.u && in.v && a.cls.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
                "class transport: null argument");
     if (a.tr.row_length() == 0) return NF_OK;
-    if (in.dtype == NF_F64) return launch_class_form<double>(a, s);
-    if (in.dtype == NF_F32) return launch_class_form<float>(a, s);
+    if (in.dtype == NF_F64) return launch_class_form<double, false>(a, s);
+    if (in.dtype == NF_F32) return launch_class_form<float, false>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "class transport: dtype must be NF_F64 or NF_F32");
-}
-
-// the launchers of k_class_remap_segscan: launch_class_t's loop over the windows and launch_class_form's choice of the form
-template <typename T, int FORM>
-static int launch_class_remap_t(const ClassArgs &a, hipStream_t s)
-{
-    const WeightSet &ws = *a.tr.ws;
-    const StepInput &in = a.in;
-    const long row_length = a.tr.row_length();
-    const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    int top = 1;
-    while (2 * top <= a.nedges) top *= 2;
-    const int nrows = a.nedges + 2;
-    for (int r0 = 0; r0 < nrows; r0 += a.window) {
-        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
-        const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
-        // the kernel of the form with its trailing arguments: the array's levels, then the carried tracer (FORM > 0)
-        auto launch = [&](auto kernel, auto... tail) {
-            if (lds > 65536)
-                NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds));
-            hipLaunchKernelGGL(kernel, record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec,
-                               (const T *)in.u, (const T *)in.v, (const T *)a.cls.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1,
-                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), (T)a.cls.fill,
-                               (T)a.cls.fill2, a.cls.wrap_x ? 1 : 0, in.scale, in.sverdrup, a.edges, a.nedges, top, r0, nwin,
-                               a.scratch, a.remap_nz, tail...);
-            return (int)NF_OK;
-        };
-        if (ws.nrec > 0) {
-            if constexpr (FORM == 0)
-                NF_TRY(launch(&k_class_remap_segscan<T, false>));
-            else
-                NF_TRY(launch(&k_class_remap_segscan<T, FORM == 2, TauIn<T>>,
-                              TauIn<T>{(const T *)a.carry.tau, (T)a.carry.fill, (T)a.carry.fill2, a.carry.ref, a.cls.wrap_x ? 1 : 0}));
-        }
-        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
-                        (unsigned)nwin, s);
-        NF_HIP(hipGetLastError());
-    }
-    return NF_OK;
-}
-
-template <typename T>
-static int launch_class_remap_form(const ClassArgs &a, hipStream_t s)
-{
-    if (!a.carry.tau) return launch_class_remap_t<T, 0>(a, s);
-    const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
-    return one ? launch_class_remap_t<T, 1>(a, s) : launch_class_remap_t<T, 2>(a, s);
 }
 
 // a.remap_nz: the levels of the arrays; the checks are launch_class_transport's
@@ -1348,31 +1433,17 @@ int launch_class_remap(const ClassArgs &a, hipStream_t s)
     NF_REQUIRE(in.u && in.v && a.cls.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG, "class remap: null argument");
     NF_REQUIRE(in.z0 < in.z1 && in.z1 <= a.remap_nz, NF_ERR_ARG, "class remap: bad levels");
     if (a.tr.row_length() == 0) return NF_OK;
-    if (in.dtype == NF_F64) return launch_class_remap_form<double>(a, s);
-    if (in.dtype == NF_F32) return launch_class_remap_form<float>(a, s);
+    if (in.dtype == NF_F64) return launch_class_form<double, true>(a, s);
+    if (in.dtype == NF_F32) return launch_class_form<float, true>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "class remap: dtype must be NF_F64 or NF_F32");
 }
 
 // ---- transports in true-depth bins: the terms of the profile, each spread over the depth of its layer at its own face ------
-// k_class_remap_segscan with the interface values of another rule: the running sum, from `surface` at level 0, of the
-// thicknesses of the slot's own face -- level_th of the gathered e3u / e3v (ThickIn<T> among the trailing arguments: four
-// running depths per lane) or thickness[z] (one) -- one float64 addition per level.  A term of level z is spread uniformly over
-// [D_z, D_z+1]: whole to row nedges + 1 where either or their difference is not finite, whole to class_row(lo) where lo == hi,
-// else row j gets  t * ((right - left) / (hi - lo)),  the remap kernel's share rule.  Per lane the adds run level-ascending,
-// then in slot order, then row-ascending; a term's row loop is clipped to the window first.  The terms are k_gross_segscan's:
-// level_slots_tf with the thickness at the face, times the carried tracer at the face with TauIn<T> among the trailing
-// arguments.  Levels [0, z0) of a partial slab only move the depths: with per-cell thicknesses their four thickness gathers per
-// level are issued kDepthLevels levels at a time, nothing else is read.  Owned levels go kDepthLevels at a time too, all
-// gathers of a batch (4 per level, + 4 with per-cell thicknesses, + 5 with a carried tracer) issued before the first is used.
-// LDS, scan and stores: k_class_segscan's.
-constexpr int kDepthLevels = 4;
-
-// where a term goes: rows jlo .. jhi of [lo, hi], or (jhi < 0) whole to row jlo
-struct DepthSpan {
-    double lo, hi;
-    int jlo, jhi;
-};
-
+// depth_walk's terms and depths, binned by the window pieces: a term of level z goes by add_span's rule (this kernel keeps a
+// written-out copy of it, see `put`) to the span (make_span) of
+// [D_z, D_z+1] at its own face among the depth edges, looked up with class_row; no depth: row nedges + 1.  With per-cell
+// thicknesses (ThickIn<T> among the trailing arguments) there are four spans per level, else one for the four faces; TauIn<T>
+// among the trailing arguments: the carried form.  Per lane the adds run level-ascending, then in slot order, then row-ascending.
 template <typename T, typename... TI>
 __global__ __launch_bounds__(kBlock) void k_depth_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
                                                           const int *__restrict__ seg, long n, const T *__restrict__ u,
@@ -1385,15 +1456,9 @@ __global__ __launch_bounds__(kBlock) void k_depth_segscan(const int *__restrict_
 {
     constexpr bool TR = (std::is_same<TI, TauIn<T>>::value || ...);
     constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
-    constexpr int DL = kDepthLevels;
     const TauIn<T> ti = tau_in<T>(extra...);
     const ThickIn<T> ct = thick_arg<T>(extra...);
-    extern __shared__ double class_lds[];
-    double *e = class_lds;
-    double *acc = class_lds + ((nedges + 1) & ~1) + threadIdx.x;   // acc[r * kBlock]: this lane's row r
-    for (int q = threadIdx.x; q < nedges; q += kBlock) e[q] = edges[q];
-    for (int r = 0; r < nwin; ++r) acc[r * kBlock] = 0.0;
-    __syncthreads();   // the edges; every lane touches only its own accumulators
+    const WindowLds w = window_lds(edges, nedges, nwin);
     const long k = (long)blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
     int key = -1;
@@ -1402,15 +1467,23 @@ __global__ __launch_bounds__(kBlock) void k_depth_segscan(const int *__restrict_
         key = load_key(seg, k);
         const auto nb = step_neighbours<TR>(r.c, nx, ncell, ti.wrap_x);
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
-        const int rend = r0 + nwin - 1;
+        // the span of [a, b] among the edges: class_row; lo == hi: whole to the row of lo, jhi = -1 (k_surface_segscan's span
+        // lambda states the same rule for its own lookup: a change to one is a change to the other)
         auto span = [&](double a, double b) {
-            if (!(__builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(b - a))) return DepthSpan{0.0, 0.0, nedges + 1, -1};
-            const double lo = a < b ? a : b, hi = a < b ? b : a;
-            const int jlo = class_row(true, lo, e, nedges, top);
-            if (lo == hi) return DepthSpan{lo, hi, jlo, -1};
-            return DepthSpan{lo, hi, jlo, class_row(true, hi, e, nedges, top)};
+            return make_span(true, a, b, nedges + 1, [&](double lo, double hi) {
+                const int jlo = class_row(true, lo, w.e, nedges, top);
+                if (lo == hi) return RowSpan{lo, hi, jlo, -1};
+                return RowSpan{lo, hi, jlo, class_row(true, hi, w.e, nedges, top)};
+            });
         };
-        auto put = [&](const DepthSpan &p, double t) {
+        const int rend = r0 + nwin - 1;
+        const double *e = w.e;
+        double *acc = w.acc;
+        // add_span<kBlock, 1>, written out: through the shared function every unrolled share loop of the forms without ThickIn
+        // forms the address of e[j] with a scalar add of its own (13 instructions more a kernel); written out, the kernel is
+        // the one it was before the pieces were shared, up to labels and branch polarity.  The rule is spread_span's,
+        // statement for statement: a change there is a change here.
+        auto put = [&](const RowSpan &p, double t) {
             if (p.jhi < 0) {
                 const int q = p.jlo - r0;
                 if (q >= 0 && q < nwin) acc[q * kBlock] += t;
@@ -1423,115 +1496,45 @@ __global__ __launch_bounds__(kBlock) void k_depth_segscan(const int *__restrict_
                 if (right != left) acc[(j - r0) * kBlock] += t * ((right - left) / width);
             }
         };
-        SlotTh D = slot_th(surface);   // the depth of the upper interface of the next level at the four faces
-        auto below = [](const SlotTh &d, const SlotTh &th) { return SlotTh{d.e + th.e, d.n + th.n, d.s + th.s, d.w + th.w}; };
-        for (int z = 0; z < z0; z += DL) {   // above the owned levels: the depths move, no term
-            const int nlev = z0 - z < DL ? z0 - z : DL;
-            if constexpr (CT) {
-                LevelUV<T> e3[DL];
-#pragma unroll
-                for (int l = 0; l < DL; ++l)
-                    if (l < nlev) e3[l] = load_level_e3(ct, (long)(z + l) * ncell, r.c, nb);
-#pragma unroll
-                for (int l = 0; l < DL; ++l)
-                    if (l < nlev) D = below(D, level_th(e3[l], ct));
-            } else {
-                for (int l = 0; l < nlev; ++l) D = below(D, slot_th(thickness[z + l]));
-            }
-        }
-        for (int z = z0; z < z1; z += DL) {
-            const int nlev = z1 - z < DL ? z1 - z : DL;
-            LevelUV<T> x[DL];
-            LevelTau<T> tt[TR ? DL : 1];
-            LevelUV<T> e3[CT ? DL : 1];
-#pragma unroll
-            for (int l = 0; l < DL; ++l)
-                if (l < nlev) {
-                    const long o = (long)(z + l) * ncell;
-                    x[l] = load_level_uv(u, v, o, r.c, nb);
-                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
-                    if constexpr (TR) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
-                }
-#pragma unroll
-            for (int l = 0; l < DL; ++l)
-                if (l < nlev) {
-                    FaceTf tf{};
-                    if constexpr (TR) tf = level_tf(tt[l], nb, ti);
-                    SlotTh th;
-                    if constexpr (CT)
-                        th = level_th(e3[l], ct);
-                    else
-                        th = slot_th(thickness[z + l]);
-                    const Slots d = level_slots_tf<T, TR>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, tf);
-                    const SlotTh Dn = below(D, th);
-                    if constexpr (CT) {
-                        if (nb.south) put(span(D.s, Dn.s), r.wa.x * d.s);
-                        put(span(D.e, Dn.e), r.wa.y * d.e);
-                        put(span(D.n, Dn.n), r.wb.x * d.n);
-                        put(span(D.w, Dn.w), r.wb.y * d.w);
-                    } else {   // one depth for the four faces: one span
-                        const DepthSpan p = span(D.e, Dn.e);
-                        if (nb.south) put(p, r.wa.x * d.s);
-                        put(p, r.wa.y * d.e);
-                        put(p, r.wb.x * d.n);
-                        put(p, r.wb.y * d.w);
-                    }
-                    D = Dn;
-                }
-        }
+        depth_walk<T, TR, CT>(r, nb, arc, u, v, ncell, z0, z1, thickness, fill, fill2, two, scale, sverdrup, ti, ct, surface,
+                              [&](const SlotTh &D, const SlotTh &Dn, const Slots &d, bool south) {
+                                  if constexpr (CT) {
+                                      if (south) put(span(D.s, Dn.s), r.wa.x * d.s);
+                                      put(span(D.e, Dn.e), r.wa.y * d.e);
+                                      put(span(D.n, Dn.n), r.wb.x * d.n);
+                                      put(span(D.w, Dn.w), r.wb.y * d.w);
+                                  } else {   // one depth for the four faces: one span
+                                      const RowSpan p = span(D.e, Dn.e);
+                                      if (south) put(p, r.wa.x * d.s);
+                                      put(p, r.wa.y * d.e);
+                                      put(p, r.wb.x * d.n);
+                                      put(p, r.wb.y * d.w);
+                                  }
+                              });
     }
-    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
-#pragma unroll
-    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
-        if (seg_scan_take(key, lane, o)) take |= 1u << b;
-    const bool store = seg_run_end(key, lane, k, n);
-    for (int r = 0; r < nwin; ++r) {
-        double val[1] = {k < n ? acc[r * kBlock] : 0.0};
-#pragma unroll
-        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
-        if (store) runsum[(long)r * n + k] = val[0];
-    }
+    window_scan_store<kBlock>(w.acc, key, lane, k, n, nwin, runsum);
 }
 
-// launch_class_remap_t's loop over the windows; the trailing arguments choose the form as in launch_gross_t
+// the trailing arguments choose the form as in launch_gross_t
 template <typename T, typename... TI>
 static int launch_depth_t(const DepthArgs &a, hipStream_t s, TI... extra)
 {
     const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
-    const long row_length = a.tr.row_length();
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    int top = 1;
-    while (2 * top <= a.nedges) top *= 2;
-    const int nrows = a.nedges + 2;
-    for (int r0 = 0; r0 < nrows; r0 += a.window) {
-        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
-        const size_t lds = sizeof(double) * ((size_t)((a.nedges + 1) & ~1) + (size_t)nwin * kBlock);
-        if (ws.nrec > 0) {
-            if (lds > 65536)
-                NF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_depth_segscan<T, TI...>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_depth_segscan<T, TI...>), record_grid(ws), dim3(kBlock), lds, s, ws.cell.get(), ws.w4.get(),
-                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0, in.z1,
-                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale,
-                               in.sverdrup, a.edges, a.nedges, top, a.top, r0, nwin, a.scratch, extra...);
-        }
-        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
-                        (unsigned)nwin, s);
-        NF_HIP(hipGetLastError());
-    }
-    return NF_OK;
+    const int top = class_top(a.nedges);
+    return for_each_window(a.tr, a.nedges + 2, a.window, a.scratch, a.rows, s, [&](int r0, int nwin, int) {
+        return launch_lds(&k_depth_segscan<T, TI...>, record_grid(ws), dim3(kBlock), class_lds_bytes(a.nedges, nwin), s, ws.cell.get(),
+                          ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0, in.z1,
+                          in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, a.edges,
+                          a.nedges, top, a.top, r0, nwin, a.scratch, extra...);
+    });
 }
 
-// the four forms of one dtype: volume or carried tracer, each with the scalar or the per-cell thicknesses
 template <typename T>
 static int launch_depth_form(const DepthArgs &a, hipStream_t s)
 {
-    const TauIn<T> ti = tau_of<T>(a.t);
-    if (a.t.tau && a.th.e3u) return launch_depth_t<T>(a, s, ti, thick_in<T>(a.th));
-    if (a.t.tau) return launch_depth_t<T>(a, s, ti);
-    if (a.th.e3u) return launch_depth_t<T>(a, s, thick_in<T>(a.th));
-    return launch_depth_t<T>(a, s);
+    return launch_tracer_thick_form<T>(a.t, a.th, [&](auto... extra) { return launch_depth_t<T>(a, s, extra...); });
 }
 
 int launch_depth_transport(const DepthArgs &a, hipStream_t s)
@@ -1554,13 +1557,14 @@ int launch_depth_transport(const DepthArgs &a, hipStream_t s)
 // to the one before it (a running max: non-decreasing); a face where any surface has no finite value has no edge set and sends
 // every term to row m + 1.  A lane gathers the five values c, e, n, w, s of every surface once, before the level loop, and
 // keeps the 4 m edges of its four faces in LDS behind the accumulators, ed[(face * m + k) * kSurfaceBlock + lane]: a wave reads
-// 64 consecutive doubles, no bank conflict, and no dynamic index reaches a register array (it would go to scratch).  row(x), the
-// number of edges <= x, is a linear count over the m <= 8 edges, lo and hi in one pass; with edges that are the same on every
-// face it is class_row of k_depth_segscan, and spans, shares and the order of the additions are that kernel's: the same bits.
-// Both thickness forms carry four spans per level, the edges differ from face to face.  Nothing is shared between waves and
-// there is no barrier, so a workgroup is ONE wave (kSurfaceBlock lanes: the same records in the same waves as a kBlock launch
-// would give them, hence the same scan): LDS is (nwin + 4 m) x 64 doubles a workgroup, 21 KiB at m = 8 with all ten rows in
-// one window, and seven waves fit a CU where one 256-lane workgroup of 84 KiB would leave one wave per SIMD.
+// 64 consecutive doubles, no bank conflict, and no dynamic index reaches a register array (it would go to scratch).  The row
+// lookup is a linear count over the m <= 8 edges; with edges that are the same on every face it is class_row of
+// k_depth_segscan, and depth_walk, make_span and add_span are the ones that kernel calls: the same bits.  Both thickness forms
+// carry four spans per level, the edges differ from face to face.  Nothing is shared between waves and there is no barrier, so
+// a workgroup is ONE wave (kSurfaceBlock lanes: the same records in the same waves as a kBlock launch would give them, hence
+// the same scan): LDS is (nwin + 4 m) x 64 doubles a workgroup, 21 KiB at m = 8 with all ten rows in one window, and seven
+// waves fit a CU where one 256-lane workgroup of 84 KiB would leave one wave per SIMD.  __launch_bounds__ stays kBlock although
+// the launch has kSurfaceBlock lanes: the bound is part of how the kernel is compiled, and changing it is a tuning change.
 constexpr int kSurfaceBlock = kWave;
 template <typename T>
 struct SurfIn {
@@ -1582,7 +1586,6 @@ __global__ __launch_bounds__(kBlock) void k_surface_segscan(const int *__restric
 {
     constexpr bool TR = (std::is_same<TI, TauIn<T>>::value || ...);
     constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
-    constexpr int DL = kDepthLevels;
     const TauIn<T> ti = tau_in<T>(extra...);
     const ThickIn<T> ct = thick_arg<T>(extra...);
     const int m = sf.m;
@@ -1599,7 +1602,6 @@ __global__ __launch_bounds__(kBlock) void k_surface_segscan(const int *__restric
         const ClassNeighbours nbs = class_neighbours(r.c, nx, ncell, sf.wrap_x);
         const auto nb = step_neighbours<TR>(r.c, nx, ncell, ti.wrap_x);
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
-        const int rend = r0 + nwin - 1;
         // the edge sets of the four faces (slot order: south, east, north, west); ok: every surface has a finite value there
         bool ok_s = true, ok_e = true, ok_n = true, ok_w = true;
         {
@@ -1622,101 +1624,39 @@ __global__ __launch_bounds__(kBlock) void k_surface_segscan(const int *__restric
                 edge(3, q, h, f, ok_w, pw);
             }
         }
+        // the span of [a, b] among the m edges e of a face: row(x), the number of edges <= x, lo and hi in one pass; lo == hi:
+        // whole to the row of lo, jhi = -1 (k_depth_segscan's span lambda states the same rule for class_row: a change to
+        // one is a change to the other)
         auto span = [&](const double *e, bool ok, double a, double b) {
-            if (!(ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(b - a)))
-                return DepthSpan{0.0, 0.0, m + 1, -1};
-            const double lo = a < b ? a : b, hi = a < b ? b : a;
-            int jlo = 0, jhi = 0;
-            for (int q = 0; q < m; ++q) {
-                const double x = e[q * kSurfaceBlock];
-                jlo += x <= lo ? 1 : 0;
-                jhi += x <= hi ? 1 : 0;
-            }
-            return DepthSpan{lo, hi, jlo, lo == hi ? -1 : jhi};
+            return make_span(ok, a, b, m + 1, [&](double lo, double hi) {
+                int jlo = 0, jhi = 0;
+                for (int q = 0; q < m; ++q) {
+                    const double x = e[q * kSurfaceBlock];
+                    jlo += x <= lo ? 1 : 0;
+                    jhi += x <= hi ? 1 : 0;
+                }
+                return RowSpan{lo, hi, jlo, lo == hi ? -1 : jhi};
+            });
         };
-        auto put = [&](const double *e, const DepthSpan &p, double t) {
-            if (p.jhi < 0) {
-                const int q = p.jlo - r0;
-                if (q >= 0 && q < nwin) acc[q * kSurfaceBlock] += t;
-                return;
-            }
-            const double width = p.hi - p.lo;
-            const int ja = p.jlo > r0 ? p.jlo : r0, jb = p.jhi < rend ? p.jhi : rend;
-            for (int j = ja; j <= jb; ++j) {
-                const double left = j == p.jlo ? p.lo : e[(j - 1) * kSurfaceBlock], right = j == p.jhi ? p.hi : e[j * kSurfaceBlock];
-                if (right != left) acc[(j - r0) * kSurfaceBlock] += t * ((right - left) / width);
-            }
-        };
+        auto put = [&](const double *e, const RowSpan &p, double t) { add_span<kSurfaceBlock, kSurfaceBlock>(acc, e, p, t, r0, nwin); };
         const double *es = ed, *ee = ed + (size_t)m * kSurfaceBlock, *en = ed + (size_t)2 * m * kSurfaceBlock, *ew = ed + (size_t)3 * m * kSurfaceBlock;
-        SlotTh D = slot_th(surface);   // the depth of the upper interface of the next level at the four faces
-        auto below = [](const SlotTh &d, const SlotTh &th) { return SlotTh{d.e + th.e, d.n + th.n, d.s + th.s, d.w + th.w}; };
-        for (int z = 0; z < z0; z += DL) {   // above the owned levels: the depths move, no term
-            const int nlev = z0 - z < DL ? z0 - z : DL;
-            if constexpr (CT) {
-                LevelUV<T> e3[DL];
-#pragma unroll
-                for (int l = 0; l < DL; ++l)
-                    if (l < nlev) e3[l] = load_level_e3(ct, (long)(z + l) * ncell, r.c, nb);
-#pragma unroll
-                for (int l = 0; l < DL; ++l)
-                    if (l < nlev) D = below(D, level_th(e3[l], ct));
-            } else {
-                for (int l = 0; l < nlev; ++l) D = below(D, slot_th(thickness[z + l]));
-            }
-        }
-        for (int z = z0; z < z1; z += DL) {
-            const int nlev = z1 - z < DL ? z1 - z : DL;
-            LevelUV<T> x[DL];
-            LevelTau<T> tt[TR ? DL : 1];
-            LevelUV<T> e3[CT ? DL : 1];
-#pragma unroll
-            for (int l = 0; l < DL; ++l)
-                if (l < nlev) {
-                    const long o = (long)(z + l) * ncell;
-                    x[l] = load_level_uv(u, v, o, r.c, nb);
-                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
-                    if constexpr (TR) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
-                }
-#pragma unroll
-            for (int l = 0; l < DL; ++l)
-                if (l < nlev) {
-                    FaceTf tf{};
-                    if constexpr (TR) tf = level_tf(tt[l], nb, ti);
-                    SlotTh th;
-                    if constexpr (CT)
-                        th = level_th(e3[l], ct);
-                    else
-                        th = slot_th(thickness[z + l]);
-                    const Slots d = level_slots_tf<T, TR>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, tf);
-                    const SlotTh Dn = below(D, th);
-                    if (nb.south) put(es, span(es, ok_s, D.s, Dn.s), r.wa.x * d.s);
-                    put(ee, span(ee, ok_e, D.e, Dn.e), r.wa.y * d.e);
-                    put(en, span(en, ok_n, D.n, Dn.n), r.wb.x * d.n);
-                    put(ew, span(ew, ok_w, D.w, Dn.w), r.wb.y * d.w);
-                    D = Dn;
-                }
-        }
+        depth_walk<T, TR, CT>(r, nb, arc, u, v, ncell, z0, z1, thickness, fill, fill2, two, scale, sverdrup, ti, ct, surface,
+                              [&](const SlotTh &D, const SlotTh &Dn, const Slots &d, bool south) {
+                                  if (south) put(es, span(es, ok_s, D.s, Dn.s), r.wa.x * d.s);
+                                  put(ee, span(ee, ok_e, D.e, Dn.e), r.wa.y * d.e);
+                                  put(en, span(en, ok_n, D.n, Dn.n), r.wb.x * d.n);
+                                  put(ew, span(ew, ok_w, D.w, Dn.w), r.wb.y * d.w);
+                              });
     }
-    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
-#pragma unroll
-    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
-        if (seg_scan_take(key, lane, o)) take |= 1u << b;
-    const bool store = seg_run_end(key, lane, k, n);
-    for (int r = 0; r < nwin; ++r) {
-        double val[1] = {k < n ? acc[r * kSurfaceBlock] : 0.0};
-#pragma unroll
-        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
-        if (store) runsum[(long)r * n + k] = val[0];
-    }
+    window_scan_store<kSurfaceBlock>(acc, key, lane, k, n, nwin, runsum);
 }
 
-// launch_depth_t's loop over the windows; m + 2 <= 10 rows fit one window of the default size, a smaller one repeats the pass
+// m + 2 <= 10 rows fit one window of the default size, a smaller one repeats the pass
 template <typename T, typename... TI>
 static int launch_surface_t(const SurfaceArgs &a, hipStream_t s, TI... extra)
 {
     const WeightSet &ws = *a.tr.ws;
     const StepInput &in = a.in;
-    const long row_length = a.tr.row_length();
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
     SurfIn<T> sf{};
     for (int q = 0; q < a.sf.m; ++q) sf.p[q] = (const T *)a.sf.p[q];
@@ -1724,33 +1664,21 @@ static int launch_surface_t(const SurfaceArgs &a, hipStream_t s, TI... extra)
     sf.m1 = (T)a.sf.fill;
     sf.m2 = (T)a.sf.fill2;
     sf.wrap_x = a.sf.wrap_x ? 1 : 0;
-    const int nrows = a.sf.m + 2;
-    for (int r0 = 0; r0 < nrows; r0 += a.window) {
-        const int nwin = nrows - r0 < a.window ? nrows - r0 : a.window;
+    const dim3 grid((unsigned)((ws.nrec + kSurfaceBlock - 1) / kSurfaceBlock));
+    return for_each_window(a.tr, a.sf.m + 2, a.window, a.scratch, a.rows, s, [&](int r0, int nwin, int) {
         const size_t lds = sizeof(double) * ((size_t)nwin + 4 * (size_t)a.sf.m) * kSurfaceBlock;   // <= 21 KiB
-        if (ws.nrec > 0) {
-            const dim3 grid((unsigned)((ws.nrec + kSurfaceBlock - 1) / kSurfaceBlock));
-            hipLaunchKernelGGL((k_surface_segscan<T, TI...>), grid, dim3(kSurfaceBlock), lds, s, ws.cell.get(), ws.w4.get(),
-                               ws.seg.get(), ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0, in.z1,
-                               in.thickness, in.arcE, in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale,
-                               in.sverdrup, sf, a.top, r0, nwin, a.scratch, extra...);
-        }
-        launch_finalize(a.tr, ws.seg_start.get(), ws.nrec, a.scratch, a.rows + (long)r0 * row_length, row_length,
-                        (unsigned)nwin, s);
-        NF_HIP(hipGetLastError());
-    }
-    return NF_OK;
+        hipLaunchKernelGGL((k_surface_segscan<T, TI...>), grid, dim3(kSurfaceBlock), lds, s, ws.cell.get(), ws.w4.get(), ws.seg.get(),
+                           ws.nrec, (const T *)in.u, (const T *)in.v, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
+                           in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), in.scale, in.sverdrup, sf, a.top, r0, nwin,
+                           a.scratch, extra...);
+        return (int)NF_OK;
+    });
 }
 
-// the four forms of one dtype: volume or carried tracer, each with the scalar or the per-cell thicknesses
 template <typename T>
 static int launch_surface_form(const SurfaceArgs &a, hipStream_t s)
 {
-    const TauIn<T> ti = tau_of<T>(a.t);
-    if (a.t.tau && a.th.e3u) return launch_surface_t<T>(a, s, ti, thick_in<T>(a.th));
-    if (a.t.tau) return launch_surface_t<T>(a, s, ti);
-    if (a.th.e3u) return launch_surface_t<T>(a, s, thick_in<T>(a.th));
-    return launch_surface_t<T>(a, s);
+    return launch_tracer_thick_form<T>(a.t, a.th, [&](auto... extra) { return launch_surface_t<T>(a, s, extra...); });
 }
 
 int launch_surface_transport(const SurfaceArgs &a, hipStream_t s)
@@ -1860,7 +1788,8 @@ __global__ __launch_bounds__(kBlock) void k_joint_terms(const int *__restrict__ 
 
 // Stage 2 for the window [r0, r0 + nwin) of joint rows, window number `win`.  A lane reads its own table entries, z ascending:
 // the rows of kJointLevels levels first, then the terms of the levels that have a row in the window, all in flight before
-// the first add.  LDS: nwin x kBlock accumulators, k_class_segscan's layout.  skip: a block whose flag is clear adds nothing,
+// the first add.  LDS: nwin x kBlock accumulators, no edges; the add keeps an unsigned window test of its own (the rows are
+// unsigned short), the scan and the stores are window_scan_store.  skip: a block whose flag is clear adds nothing,
 // so it does not read the table; its run sums are the +0.0 that the scan of untouched accumulators gives either way.
 __global__ __launch_bounds__(kBlock) void k_joint_bin(const int *__restrict__ seg, long n, int nlev,
                                                       const dvec2 *__restrict__ terms, const usvec4 *__restrict__ rows,
@@ -1907,17 +1836,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_bin(const int *__restrict__ se
             }
         }
     }
-    unsigned take = 0;   // the flags of all six steps, kept as bits across the rows
-#pragma unroll
-    for (int o = 1, b = 0; o < kWave; o <<= 1, ++b)
-        if (seg_scan_take(key, lane, o)) take |= 1u << b;
-    const bool store = seg_run_end(key, lane, k, n);
-    for (int q = 0; q < nwin; ++q) {
-        double val[1] = {k < n ? acc[q * kBlock] : 0.0};
-#pragma unroll
-        for (int o = 1, b = 0; o < kWave; o <<= 1, ++b) seg_scan_step(val, o, take & (1u << b));
-        if (store) runsum[(long)q * n + k] = val[0];
-    }
+    window_scan_store<kBlock>(acc, key, lane, k, n, nwin, runsum);
 }
 
 // stage 2 over all `nrows` rows of a term table of `nlev` levels, `window` rows per pass, each pass finalized into its rows of
@@ -1926,16 +1845,11 @@ static int launch_joint_bins(const Transects &tr, int nrows, int nlev, int windo
                              const usvec4 *rows, const unsigned *flags, int nwords, double *scratch, double *out, hipStream_t s)
 {
     const WeightSet &ws = *tr.ws;
-    const long row_length = tr.row_length();
-    for (int r0 = 0, win = 0; r0 < nrows; r0 += window, ++win) {
-        const int nwin = nrows - r0 < window ? nrows - r0 : window;
-        if (ws.nrec > 0)
-            hipLaunchKernelGGL(k_joint_bin, record_grid(ws), dim3(kBlock), sizeof(double) * (size_t)nwin * kBlock, s, ws.seg.get(),
-                               ws.nrec, nlev, terms, rows, flags, nwords, win, skip ? 1 : 0, r0, nwin, scratch);
-        launch_finalize(tr, ws.seg_start.get(), ws.nrec, scratch, out + (long)r0 * row_length, row_length, (unsigned)nwin, s);
-        NF_HIP(hipGetLastError());
-    }
-    return NF_OK;
+    return for_each_window(tr, nrows, window, scratch, out, s, [&](int r0, int nwin, int win) {
+        hipLaunchKernelGGL(k_joint_bin, record_grid(ws), dim3(kBlock), sizeof(double) * (size_t)nwin * kBlock, s, ws.seg.get(), ws.nrec,
+                           nlev, terms, rows, flags, nwords, win, skip ? 1 : 0, r0, nwin, scratch);
+        return (int)NF_OK;
+    });
 }
 
 template <typename T, bool CARRY>
@@ -1946,9 +1860,7 @@ static int launch_joint_t(const JointArgs &a, hipStream_t s)
     const int nrows = (a.na + 2) * (a.nb + 2), nlev = in.z1 - in.z0;
     const int nwords = joint_flag_words(nrows, a.window);
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    int topa = 1, topb = 1;
-    while (2 * topa <= a.na) topa *= 2;
-    while (2 * topb <= a.nb) topb *= 2;
+    const int topa = class_top(a.na), topb = class_top(a.nb);
     dvec2 *terms = reinterpret_cast<dvec2 *>(a.table);
     usvec4 *rows = reinterpret_cast<usvec4 *>(a.table + sizeof(dvec2) * 2 * (size_t)ws.nrec * nlev);
     if (ws.nrec > 0) {
@@ -2079,8 +1991,7 @@ static int launch_gross_class_t(const GrossClassArgs &a, hipStream_t s, TI... ex
     const int nrows = 2 * (a.nedges + 2), nlev = in.z1 - in.z0;
     const int nwords = joint_flag_words(nrows, a.window);
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    int top = 1;
-    while (2 * top <= a.nedges) top *= 2;
+    const int top = class_top(a.nedges);
     dvec2 *terms = reinterpret_cast<dvec2 *>(a.table);
     usvec4 *rows = reinterpret_cast<usvec4 *>(a.table + sizeof(dvec2) * 2 * (size_t)ws.nrec * nlev);
     if (ws.nrec > 0) {
@@ -2238,8 +2149,7 @@ static int launch_class_area_t(const ClassAreaArgs &a, hipStream_t s, TI... extr
     const int nrows = 2 * (a.nedges + 2), nent = 2 * (in.z1 - in.z0);   // two table entries per owned level
     const int nwords = joint_flag_words(nrows, a.window);
     const T fill = (T)in.fill, fill2 = (T)in.fill2;
-    int top = 1;
-    while (2 * top <= a.nedges) top *= 2;
+    const int top = class_top(a.nedges);
     dvec2 *terms = reinterpret_cast<dvec2 *>(a.table);
     usvec4 *rows = reinterpret_cast<usvec4 *>(a.table + sizeof(dvec2) * 2 * (size_t)ws.nrec * nent);
     if (ws.nrec > 0) {
