@@ -813,6 +813,42 @@ int nf_sigma_eos80(void *out_dev, const void *theta_dev, const void *salt_dev, s
                    double theta_fill, double theta_missing, double salt_fill, double salt_missing, double fill_out,
                    void *hip_stream);
 
+/* The depth at which a tracer first reaches a value, column by column (nf_isodepth.hip): the depth of an isotherm or an
+ * isopycnal, the mixed-layer depth by a threshold criterion -- the surfaces of nf_field_set_depth_surfaces, computed from what
+ * the model writes.  Value-level like nf_sigma_eos80: no nf_field involved, asynchronous on hip_stream.
+ * Inputs.  tau_dev: one time step of a tracer at T-points, (nz, ny, nx), x fastest, of dtype in HBM, with two missing markers
+ * (tau_fill, tau_missing; NaN = none; NaN always counts as missing; each cast to dtype and compared in dtype).  The thicknesses
+ * of the levels: either thickness_host, nz float64 numbers on the host, one per level, read before the call returns (at most
+ * 256 levels), or e3t_dev, (nz, ny, nx) of dtype in HBM with two markers of its own (e3t_fill, e3t_missing) -- exactly one of
+ * the two is not NULL.  top: the depth of the upper interface of level 0, finite.  values: m float64 numbers on the host,
+ * 1 <= m <= 8, read before the call returns.  sense: +1, the tracer rises downward (density), or -1, it falls (temperature).
+ * Output.  out_dev: m planes (m, ny, nx) of dtype, plane j the depth of values[j], positive downward from the origin of top.
+ * All arithmetic is float64, every operation rounded on its own, no fused multiply-adds; float32 inputs are widened first and a
+ * result is rounded once to dtype.  Per column, tau_k and h_k its values at level k:
+ *   Wet levels.  Level k is wet when tau_k is present and, in the e3t form, h_k is present, finite and > 0.  The column is the
+ *     leading run of wet levels 0 .. kb; what lies below the first level that is not wet does not matter (at most one group
+ *     of 4 or 8 levels below it is still read).  No wet level: every plane gets fill_out.  (Ice-shelf cavities -- dry levels on top -- are out of scope.)
+ *   Depths.  D_0 = top, D_{k+1} = D_k + h_k, c_k = D_k + 0.5 * h_k, sequentially from level 0.
+ *   Threshold.  relative = 0: theta_j = values[j].  relative = 1: theta_j = tau_ref + values[j] (+0.03 kg m-3 on sigma0 with
+ *     sense +1, -0.2 K on theta with sense -1, zref = 10: the mixed-layer criteria), where kref is the last level of the column
+ *     with c_k <= zref (0 if there is none) and tau_ref = tau_kref when zref <= c_0 or kref = kb, else, with a = kref and
+ *     b = kref + 1, tau_ref = tau_a + (tau_b - tau_a) * ((zref - c_a) / (c_b - c_a)), in that operation order.
+ *   Reached.  R_k = tau_k >= theta_j (sense +1) or tau_k <= theta_j (sense -1).  k* = the first k in [k0, kb] with R_k; k0 = 0
+ *     with relative = 0, kref + 1 with relative = 1.
+ *   Result.  No k*: D_{kb+1}, the sea bed (the whole column is above the surface).  k* = 0: D_0, the surface outcrops.
+ *     Otherwise, with a = k* - 1 and k = k*:  R_a false: c_a + (c_k - c_a) * ((theta_j - tau_a) / (tau_k - tau_a)), in that
+ *     operation order;  R_a true (only with relative = 1 at a = kref): zref.  A result that is not finite (+-inf in the tracer)
+ *     is stored as it comes: nf_field_compute_surface_transport sends such faces to row m + 1.
+ * The result does not depend on the launch shape; no atomics.  A wave stops reading a column's levels once every lane has all
+ * its m values or has left its wet column.
+ * NF_ERR_ARG, decided before a device is needed: a null out_dev, tau_dev or values; both thickness forms or neither; m outside
+ * 1 .. 8; a bad dtype; a sense other than +-1; relative other than 0 or 1; a top, zref or value that is not finite; nz, ny or
+ * nx < 1; more than 256 levels, or a thickness that is not finite and > 0, in the thickness_host form; out_dev overlapping
+ * tau_dev or e3t_dev. */
+int nf_iso_depth(void *out_dev, const void *tau_dev, const double *thickness_host, const void *e3t_dev, long nz, long ny, long nx,
+                 int dtype, double tau_fill, double tau_missing, double e3t_fill, double e3t_missing, double top,
+                 const double *values, int m, int sense, int relative, double zref, double fill_out, void *hip_stream);
+
 /* ------------------------------------------------------------------ synthetic data (datagen.py) */
 /* Stream functions offered on device (no eval on the GPU): psi = g(z,t) * h(x,y)
  *   0 "x"                                                    README.md:26

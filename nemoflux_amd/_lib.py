@@ -207,6 +207,9 @@ _sig('nf_time_mean_weighted_steps', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_
      [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p])
 _sig('nf_sigma_eos80', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] +   # HBM addresses
      [ctypes.c_double] * 6 + [ctypes.c_void_p])
+_sig('nf_iso_depth', [ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                      ctypes.c_int] + [ctypes.c_double] * 5 + [c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                               ctypes.c_double, ctypes.c_double, ctypes.c_void_p])
 _sig('nf_datagen_bounds',[ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long] + [ctypes.c_double] * 6 +
      [ctypes.c_int, ctypes.c_void_p])
 _sig('nf_datagen_uv', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_long] * 6 + [ctypes.c_double] * 6 +

@@ -150,6 +150,13 @@ class _PinnedBlock(object):
             pass
 
 
+class _DerivedPlane(object):
+    """plane `index` of a derived item (a nemoflux_amd.surfaces.IsoDepth) in the item list of setDepthSurfaces"""
+
+    def __init__(self, item, index):
+        self.item, self.index = item, index
+
+
 class _Transect(object):
     """Entry of Field.plis: quacks like mint.PolylineIntegral.getIntegral (fluxplot.py:56).
 
@@ -653,12 +660,21 @@ class Field(object):
         read in place by offset, host arrays and file variables go one time step at a time through a pinned buffer of their
         own into a device buffer -- and _stage_slot has nf_sigma_eos80 write step t into one (nz, ny, nx) device buffer of the
         dtype of uo / vo, which the engine reads as a device-resident tracer whose fill is NaN."""
+        sg = self._sigma_inputs(sigma, 'the Sigma')
+        slot = dict(lazy=tuple(sigma.sources), step=-1, set=set_tracer, code=self._uv_code, fill=numpy.nan, missing=numpy.nan,
+                    keep=sigma, sigma=sg)
+        check(set_missing(ctypes.byref(self._h), numpy.nan))
+        return slot
+
+    def _sigma_inputs(self, sigma, what):
+        """what computing a Sigma one step at a time needs (_run_sigma): where thetao and so live, a pinned buffer and a device
+        buffer for each that is not on the device, and the (nz, ny, nx) device buffer that receives sigma"""
         uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
         if self.getSizes(sigma.shape) != (self.nt, self.nz, self.ny, self.nx):
-            raise RuntimeError(f'ERROR: thetao and so of the Sigma have shape {sigma.shape}; uo/vo have (nt, nz, ny, nx) = '
+            raise RuntimeError(f'ERROR: thetao and so of {what} have shape {sigma.shape}; uo/vo have (nt, nz, ny, nx) = '
                                f'{(self.nt, self.nz, self.ny, self.nx)}')
         if sigma.dtype != uv_dtype:
-            raise RuntimeError(f'ERROR: thetao and so of the Sigma are {sigma.dtype.name}, uo/vo are {uv_dtype.name}')
+            raise RuntimeError(f'ERROR: thetao and so of {what} are {sigma.dtype.name}, uo/vo are {uv_dtype.name}')
         nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
         inputs = []
         for src, (fill, missing) in zip(sigma.sources, sigma.markers):
@@ -671,15 +687,11 @@ class Field(object):
                 one['pinned'] = self._host_array((self.nz, self.ny, self.nx), uv_dtype)
                 one['dev'] = _lib.DeviceBuffer(nbytes)
             inputs.append(one)
-        slot = dict(lazy=tuple(sigma.sources), step=-1, set=set_tracer, code=self._uv_code, fill=numpy.nan, missing=numpy.nan,
-                    keep=sigma, sigma=dict(pref=sigma.pref, inputs=inputs, out=_lib.DeviceBuffer(nbytes), nbytes=nbytes))
-        check(set_missing(ctypes.byref(self._h), numpy.nan))
-        return slot
+        return dict(pref=sigma.pref, inputs=inputs, out=_lib.DeviceBuffer(nbytes), nbytes=nbytes)
 
-    def _stage_sigma(self, slot, tIndex):
-        """step tIndex of a Sigma slot: thetao and so of that step on the device, nf_sigma_eos80 into the slot's buffer on the
-        Field's stream, and the buffer handed over through a virtual (nt, nz, ny, nx) base"""
-        sg = slot['sigma']
+    def _run_sigma(self, sg, code, tIndex):
+        """thetao and so of step tIndex on the device and nf_sigma_eos80 into sg['out'] on the Field's stream; the stream is
+        drained when a staging buffer was used (it is written again by the next step)"""
         off = tIndex * sg['nbytes']
         ptrs = []
         for one in sg['inputs']:
@@ -693,11 +705,17 @@ class Field(object):
             check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, sg['nbytes']))
             ptrs.append(one['dev'].ptr)
         th, so = sg['inputs']
-        check(lib.nf_sigma_eos80(sg['out'].ptr, ptrs[0], ptrs[1], self.nz * self.ny * self.nx, slot['code'], sg['pref'],
+        check(lib.nf_sigma_eos80(sg['out'].ptr, ptrs[0], ptrs[1], self.nz * self.ny * self.nx, code, sg['pref'],
                                  th['fill'], th['missing'], so['fill'], so['missing'], numpy.nan, self._stream))
         if any(one['ptr'] is None for one in sg['inputs']):
             check(lib.nf_synchronize())     # the staging buffers are written again by the next step
-        check(slot['set'](ctypes.byref(self._h), sg['out'].ptr - off, self.nt, slot['code'], 1, numpy.nan))
+
+    def _stage_sigma(self, slot, tIndex):
+        """step tIndex of a Sigma slot: thetao and so of that step on the device, nf_sigma_eos80 into the slot's buffer on the
+        Field's stream, and the buffer handed over through a virtual (nt, nz, ny, nx) base"""
+        sg = slot['sigma']
+        self._run_sigma(sg, slot['code'], tIndex)
+        check(slot['set'](ctypes.byref(self._h), sg['out'].ptr - tIndex * sg['nbytes'], self.nt, slot['code'], 1, numpy.nan))
         slot['step'] = tIndex
 
     def _sigma_refused(self, what):
@@ -1640,19 +1658,33 @@ class Field(object):
         device array of another dtype raises.  fill_value / missing_value: the surfaces' own missing markers (the files' when
         not given; more than two distinct ones over the set raise); NaN always counts as missing.  wrapX: the east face of
         the last column takes column 0 as its neighbour.  A set of its own: setDepthEdges, setClassEdges and
-        setJointClassEdges do not see it.  setDepthSurfaces(None) clears it."""
+        setJointClassEdges do not see it.  setDepthSurfaces(None) clears it.
+        An item may also be a nemoflux_amd.surfaces.IsoDepth or MixedLayerDepth: surfaces derived on the GPU from a tracer --
+        the depth of an isotherm or an isopycnal, the mixed-layer depth -- one time step at a time (nf_iso_depth).  Such an
+        item counts as its number of values towards the limit of 8, varies in time and lives on the device: it may stand
+        beside device arrays of (nt, ny, nx).  Its planes carry NaN where a column has no wet level."""
+        from .surfaces import IsoDepth
         self._surfaces = None
         if surfaces is None:
             check(lib.nf_field_set_depth_surfaces(ctypes.byref(self._h), None, 0, 0, NF_F64, 0, numpy.nan, 0.0))
             return
         surfaces = list(surfaces)
-        if not 1 <= len(surfaces) <= 8:
-            raise RuntimeError(f'ERROR: setDepthSurfaces needs a list of 1 to 8 surfaces, got {len(surfaces)}')
+        count = sum(s.m if isinstance(s, IsoDepth) else 1 for s in surfaces)
+        if not 1 <= count <= 8:
+            raise RuntimeError(f'ERROR: setDepthSurfaces needs a list of 1 to 8 surfaces, got {count}')
         if not numpy.isfinite(float(top)):
             raise RuntimeError(f'ERROR: setDepthSurfaces: top must be a finite number, got {top!r}')
         uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
-        markers, items, nts, homes = [], [], [], []
+        markers, items, nts, homes, derived = [], [], [], [], []
         for k, s in enumerate(surfaces):
+            if isinstance(s, IsoDepth):
+                item = self._derived_surface(k, s)
+                derived.append(item)
+                for j in range(s.m):
+                    items.append(_DerivedPlane(item, j))
+                    nts.append(self.nt)
+                    homes.append(True)
+                continue
             if isinstance(s, tuple) and len(s) == 2 and isinstance(s[1], str):
                 var, _, d = open_uvfile(s[0], s[1], with_all=True)
                 for m in d['_markers_' + s[1]]:
@@ -1694,8 +1726,9 @@ class Field(object):
         slot = dict(items=items, nt=nts[0], on_dev=homes[0], step=-1, top=float(top), wrapX=bool(wrapX),
                     fill=numpy.nan if fill_value is None else float(fill_value),
                     missing=numpy.nan if missing_value is None else float(missing_value),
-                    buf=[self._host_array((self.ny, self.nx), uv_dtype) if hasattr(s, 'read_step') else None for s in items])
-        if not any(b is not None for b in slot['buf']):
+                    buf=[self._host_array((self.ny, self.nx), uv_dtype) if hasattr(s, 'read_step') else None for s in items],
+                    derived=derived)
+        if not derived and not any(b is not None for b in slot['buf']):
             self._set_surfaces(slot, [_lib.device_pointer(s) if slot['on_dev'] else s.ctypes.data for s in items])
         check(lib.nf_field_set_depth_surfaces_missing_value(ctypes.byref(self._h), slot['missing']))
         check(lib.nf_field_set_depth_surfaces_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
@@ -1710,6 +1743,10 @@ class Field(object):
         """make step tIndex of the file-backed surfaces the one the engine reads: each into its pinned buffer, handed over
         through a virtual (nt, ny, nx) base that the engine only dereferences at step tIndex"""
         slot = self._surfaces
+        if slot.get('derived'):
+            if slot['step'] != tIndex:
+                self._stage_derived_surfaces(slot, tIndex)
+            return
         if slot['step'] == tIndex or not any(b is not None for b in slot['buf']):
             return
         ptrs = []
@@ -1722,9 +1759,142 @@ class Field(object):
         self._set_surfaces(slot, ptrs)
         slot['step'] = tIndex
 
+    def _derived_surface(self, k, iso):
+        """what computing item k of setDepthSurfaces, an IsoDepth, one step at a time needs: where its tracer (or the thetao and
+        so of its Sigma) and its e3t live, staging buffers for what is not on the device, and the (m, ny, nx) device buffer
+        that receives the planes"""
+        from .eos import Sigma
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        full = (self.nt, self.nz, self.ny, self.nx)
+        sigma = isinstance(iso.tracer, Sigma)
+        if not sigma:
+            if self.getSizes(iso.shape) != full or len(iso.shape) not in (3, 4):
+                raise RuntimeError(f'ERROR: surface {k}: the tracer of the IsoDepth has shape {iso.shape}; uo/vo have '
+                                   f'(nt, nz, ny, nx) = {full}')
+            if iso.dtype != uv_dtype:
+                raise RuntimeError(f'ERROR: surface {k}: the tracer of the IsoDepth is {iso.dtype.name}, uo/vo are '
+                                   f'{uv_dtype.name}')
+        nt_e = None
+        if iso.e3t is None and self.nz > 256:
+            raise RuntimeError(f'ERROR: surface {k}: an IsoDepth without e3t uses the per-level thickness, which nf_iso_depth '
+                               f'takes for at most 256 levels; this Field has {self.nz}: give e3t=')
+        if iso.e3t is not None:
+            shape = tuple(int(x) for x in iso.e3t.shape)
+            nt_e = self.getSizes(shape)[0] if len(shape) in (3, 4) else -1
+            if len(shape) not in (3, 4) or self.getSizes(shape)[1:] != full[1:] or nt_e not in (1, self.nt):
+                raise RuntimeError(f'ERROR: surface {k}: the e3t of the IsoDepth has shape {shape}; need (nz, ny, nx) = '
+                                   f'{full[1:]}, (1, nz, ny, nx) or (nt, nz, ny, nx) = {full}')
+            dt = numpy.dtype(_native_dtype(iso.e3t))
+            if dt != uv_dtype:
+                raise RuntimeError(f'ERROR: surface {k}: the e3t of the IsoDepth is {dt.name}, uo/vo are {uv_dtype.name}')
+        # everything fits: the buffers
+        return dict(iso=iso, host=None, sigma=self._sigma_inputs(iso.tracer, f'the Sigma of surface {k}') if sigma else None,
+                    tracer=None if sigma else self._column_source(iso.tracer, self.nt, uv_dtype),
+                    e3t=None if nt_e is None else self._column_source(iso.e3t, nt_e, uv_dtype),
+                    out=_lib.DeviceBuffer(iso.m * self.ny * self.nx * uv_dtype.itemsize))
+
+    def _column_source(self, src, nt_src, uv_dtype):
+        """one 3-D source of a derived surface, nt_src steps of (nz, ny, nx): used in place on the device, else step by step
+        through a pinned buffer into a device buffer (_column_step)"""
+        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
+        one = dict(ptr=_lib.device_pointer(src), nt=nt_src, keep=src, step=-1, nbytes=nbytes)
+        if one['ptr'] is None:
+            one['file'] = hasattr(src, 'read_step')
+            one['rank'] = len(src.shape)
+            one['host'] = None if one['file'] else _native(src).reshape(nt_src, self.nz, self.ny, self.nx)
+            one['pinned'] = self._host_array((self.nz, self.ny, self.nx), uv_dtype)
+            one['dev'] = _lib.DeviceBuffer(nbytes)
+        return one
+
+    def _column_step(self, one, tIndex):
+        """(the device address of step tIndex of a _column_source, whether a staging buffer was written)"""
+        t = tIndex if one['nt'] > 1 else 0
+        if one['ptr'] is not None:
+            return one['ptr'] + t * one['nbytes'], False
+        if one['step'] == t:
+            return one['dev'].ptr, False
+        if not one['file']:
+            numpy.copyto(one['pinned'], one['host'][t])
+        elif one['rank'] == 3:      # a static file variable (nz, ny, nx): its first axis is what read_step walks
+            for z in range(self.nz):
+                numpy.copyto(one['pinned'][z], one['keep'].read_step(z))
+        else:
+            one['keep'].read_step(t, out=one['pinned'])
+        check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, one['nbytes']))
+        one['step'] = t
+        return one['dev'].ptr, True
+
+    def _run_iso_depth(self, item, tIndex, top):
+        """the planes of one derived item at step tIndex into its device buffer: its sources of that step on the device (a
+        Sigma through nf_sigma_eos80), then nf_iso_depth on the Field's stream"""
+        iso = item['iso']
+        nan = numpy.nan
+        staged = False
+        if item['sigma'] is not None:
+            self._run_sigma(item['sigma'], self._uv_code, tIndex)
+            tau, marks = item['sigma']['out'].ptr, (nan, nan)
+        else:
+            tau, staged = self._column_step(item['tracer'], tIndex)
+            marks = tuple(nan if x is None else x for x in iso.markers)
+        e3t, emarks, hp = None, (nan, nan), None
+        if item['e3t'] is not None:
+            e3t, wrote = self._column_step(item['e3t'], tIndex)
+            staged = staged or wrote
+            emarks = tuple(nan if x is None else x for x in iso.e3t_markers)
+        else:
+            h = numpy.ascontiguousarray(self.thickness, dtype=numpy.float64)
+            hp = _lib.dptr(h)
+        values = (ctypes.c_double * iso.m)(*iso.values)
+        check(lib.nf_iso_depth(item['out'].ptr, tau, hp, e3t, self.nz, self.ny, self.nx, self._uv_code, marks[0], marks[1],
+                               emarks[0], emarks[1], top, values, iso.m, iso.sense, 1 if iso.relative else 0, iso.zref, nan,
+                               self._stream))
+        if staged:
+            check(lib.nf_synchronize())     # the staging buffers are written again by the next step
+        item['host'] = None
+
+    def _stage_derived_surfaces(self, slot, tIndex):
+        """step tIndex of a set with derived items: every IsoDepth computed into its buffer, and all planes -- derived ones
+        and plain device arrays -- handed over through a virtual (nt, ny, nx) base that the engine dereferences at tIndex"""
+        plane = self.ny * self.nx * (4 if self._uv_code == NF_F32 else 8)
+        for item in slot.get('derived'):
+            self._run_iso_depth(item, tIndex, slot['top'])
+        ptrs = [s.item['out'].ptr + (s.index - tIndex) * plane if isinstance(s, _DerivedPlane) else _lib.device_pointer(s)
+                for s in slot['items']]
+        self._set_surfaces(slot, ptrs)
+        slot['step'] = tIndex
+
+    def getDepthSurfaces(self, tIndex):
+        """The surfaces of setDepthSurfaces in force at time step tIndex as a host array (m, ny, nx) in the dtype of uo / vo,
+        derived (IsoDepth, MixedLayerDepth: computed on the GPU for that step) or plain -- the mixed-layer depth that a section
+        plot draws over the crossings.  Missing values are as the surfaces hold them; a derived surface has NaN where a column
+        has no wet level."""
+        slot = getattr(self, '_surfaces', None)
+        if slot is None:
+            raise RuntimeError('ERROR: call setDepthSurfaces first')
+        tIndex = int(tIndex)
+        if not 0 <= tIndex < self.nt:
+            raise RuntimeError(f'ERROR: getDepthSurfaces: tIndex must be 0 .. {self.nt - 1}, got {tIndex}')
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        t = tIndex if slot['nt'] > 1 else 0
+        return numpy.stack([numpy.asarray(self._surface_step_host(s, t), dtype=uv_dtype).reshape(self.ny, self.nx)
+                            for s in slot['items']])
+
+    def _derived_host(self, item, t):
+        """the planes (m, ny, nx) of one derived item at step t on the host; the last step asked for is kept"""
+        if item['host'] is None or item['host'][0] != t:
+            slot = self._surfaces
+            self._run_iso_depth(item, t, slot['top'])
+            slot['step'] = -1       # the item's buffer no longer holds the step the engine was given
+            check(lib.nf_synchronize())
+            uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+            item['host'] = (t, item['out'].download((item['iso'].m, self.ny, self.nx), uv_dtype))
+        return item['host'][1]
+
     def _surface_step_host(self, s, t):
         """step t of one surface as a host array (ny, nx)"""
         import torch
+        if isinstance(s, _DerivedPlane):
+            return self._derived_host(s.item, t)[s.index]
         if hasattr(s, 'read_step'):
             return numpy.asarray(s.read_step(t))
         if isinstance(s, torch.Tensor):
@@ -1747,14 +1917,13 @@ class Field(object):
         with numpy.errstate(over='ignore'):
             marks = [float(dt.type(m)) for m in (slot['fill'], slot['missing']) if m == m]
         marks = [m for m in marks if m == m]
-        if slot['nt'] == 1:
+        if slot['nt'] == 1 and not slot.get('derived'):
             out = [self._as_float64(s) for s in slot['items']]
         else:
             idx, w = (list(range(t0, t1)), None) if table is None else table[:2]
-            out = []
-            for s in slot['items']:
-                num, den = numpy.zeros((self.ny, self.nx)), numpy.zeros((self.ny, self.nx))
-                for j, t in enumerate(idx):
+            sums = [(numpy.zeros((self.ny, self.nx)), numpy.zeros((self.ny, self.nx))) for _ in slot['items']]
+            for j, t in enumerate(idx):         # step by step: a derived item is computed once per step for all its planes
+                for s, (num, den) in zip(slot['items'], sums):
                     x = self._surface_step_host(s, t)
                     ok = ~numpy.isnan(x)
                     for m in marks:
@@ -1762,8 +1931,8 @@ class Field(object):
                     wj = numpy.float64(1.0 if w is None else w[j])
                     num += numpy.where(ok, wj * numpy.where(ok, x, 0).astype(numpy.float64), 0.0)
                     den += numpy.where(ok, wj, 0.0)
-                with numpy.errstate(invalid='ignore', divide='ignore'):
-                    out.append(numpy.where(den > 0, num / den, marks[0] if marks else numpy.nan))
+            with numpy.errstate(invalid='ignore', divide='ignore'):
+                out = [numpy.where(den > 0, num / den, marks[0] if marks else numpy.nan) for num, den in sums]
         mean.setDepthSurfaces(out, top=slot['top'], fill_value=marks[0] if marks else None,
                               missing_value=marks[1] if len(marks) > 1 else None, wrapX=slot['wrapX'])
 

@@ -24,6 +24,10 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --depth-surfaces mldr10_1,iso20 [--surface-file S.nc] [--depth-top 0] [--tracer thetao] [--cell-thickness]
                                   (water flow, or the transport of thetao, in the layers bounded by 2-D fields: above the first
                                   surface, between consecutive ones, below the last; a layer that a surface cuts is split)
+    ... --iso-depth 20 --iso-of thetao | --iso-depth 27.7,27.9 --sigma thetao,so [--iso-relative ZREF] [--iso-e3t e3t]
+                                  (the same layers bounded by surfaces computed on the GPU: the depth at which a variable, or
+                                  sigma_PREF of two, first reaches each value going down the column; --iso-sense rising|falling)
+    ... --mixed-layer thetao,so[,DELTA[,ZREF]]   (above and below the mixed-layer depth: sigma0 exceeds its value at ZREF by DELTA)
     ... --levels [--tracer thetao]               (water flow, or the transport of thetao, of every level: one line per level)
     ... --tracer thetao --decompose              (the transport of thetao and its throughflow, overturning and gyre parts)
     ... --tracer thetao --eddy                   (the time-mean transport of thetao, its mean-flow part and its eddy part)
@@ -507,6 +511,106 @@ def checkDepthSurfacesArgs(depthSurfaces='', surfaceFile='', depthTop=0.0, **oth
     parseSurfaces(depthSurfaces)
 
 
+def parseIsoValues(text):
+    """--iso-depth: V1[,...,Vm], 1 to 8 finite numbers"""
+    try:
+        v = [float(x) for x in text.split(',')]
+    except ValueError:
+        raise RuntimeError(f"ERROR: --iso-depth must be V1[,...,Vm] (numbers), got '{text}'")
+    if not 1 <= len(v) <= 8 or not all(numpy.isfinite(v)):
+        raise RuntimeError(f"ERROR: --iso-depth needs 1 to 8 finite values (one surface each), got '{text}'")
+    return v
+
+
+def parseMixedLayer(text):
+    """--mixed-layer: 'THETA,SALT[,DELTA[,ZREF]]' -> (theta name, salt name, delta in kg m-3, zref); defaults 0.03 and 10"""
+    parts = [x.strip() for x in text.split(',')]
+    if len(parts) not in (2, 3, 4) or not parts[0] or not parts[1]:
+        raise RuntimeError(f"ERROR: --mixed-layer must be THETA,SALT[,DELTA[,ZREF]] (two variable names, a density step and a "
+                           f"reference depth), got '{text}'")
+    try:
+        delta = float(parts[2]) if len(parts) > 2 else 0.03
+        zref = float(parts[3]) if len(parts) > 3 else 10.0
+    except ValueError:
+        raise RuntimeError(f"ERROR: --mixed-layer must be THETA,SALT[,DELTA[,ZREF]] with numbers DELTA and ZREF, got '{text}'")
+    if not (numpy.isfinite(delta) and numpy.isfinite(zref)):
+        raise RuntimeError(f"ERROR: --mixed-layer needs finite DELTA and ZREF, got '{text}'")
+    return parts[0], parts[1], delta, zref
+
+
+def checkIsoDepthArgs(isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer='', sigma='', depthSurfaces='',
+                      depthTop=0.0, **others):
+    """the --iso-depth and --mixed-layer options of the command line (transports between surfaces computed on the GPU): they
+    combine with --surface-file, --depth-top, --tracer (with --tracer-file, --tracer-ref, --tracer-scale), --cell-thickness
+    and -s as --depth-surfaces does; refused combinations raise RuntimeError.  Returns what isoSurfaceSeries takes, or None."""
+    if not (isoDepth or mixedLayer):
+        for on, opt in ((isoOf, '--iso-of'), (isoSense, '--iso-sense'), (isoRelative != '', '--iso-relative')):
+            if on:
+                raise RuntimeError(f'ERROR: {opt} needs --iso-depth V1[,...,Vm]')
+        if isoE3t:
+            raise RuntimeError('ERROR: --iso-e3t needs --iso-depth V1[,...,Vm] or --mixed-layer THETA,SALT')
+        return None
+    opt = '--iso-depth' if isoDepth else '--mixed-layer'
+    if isoDepth and mixedLayer:
+        raise RuntimeError('ERROR: --iso-depth and --mixed-layer cannot be combined: each writes the layers of its own surfaces')
+    if depthSurfaces:
+        raise RuntimeError(f'ERROR: {opt} and --depth-surfaces cannot be combined: the surfaces are either read (--depth-surfaces) '
+                           f'or computed ({opt})')
+    for name, on in others.items():
+        if on:
+            raise RuntimeError(f'ERROR: {opt} and {name} cannot be combined: {opt} writes the transport in every layer between '
+                               f'the surfaces as CSV only')
+    if not numpy.isfinite(float(depthTop)):
+        raise RuntimeError(f'ERROR: --depth-top must be a finite number, got {depthTop!r}')
+    if mixedLayer:
+        for on, name in ((isoOf, '--iso-of'), (isoSense, '--iso-sense'), (isoRelative != '', '--iso-relative'), (sigma, '--sigma')):
+            if on:
+                raise RuntimeError(f'ERROR: --mixed-layer and {name} cannot be combined: --mixed-layer THETA,SALT[,DELTA[,ZREF]] '
+                                   f'is the whole criterion')
+        theta, salt, delta, zref = parseMixedLayer(mixedLayer)
+        return dict(sigma=(theta, salt, 0.0), of='', values=[delta], sense=1, relative=True, zref=zref, e3t=isoE3t,
+                    labels=['mld'])
+    if bool(isoOf) == bool(sigma):
+        raise RuntimeError('ERROR: --iso-depth needs exactly one of --iso-of NAME (the variable whose iso-surfaces are wanted) '
+                           'and --sigma THETA,SALT[,PREF] (its potential density)')
+    values = parseIsoValues(isoDepth)
+    if isoSense and isoSense not in ('rising', 'falling'):
+        raise RuntimeError(f"ERROR: --iso-sense must be 'rising' (the variable rises downward, as density does) or 'falling' (as "
+                           f"temperature does), got '{isoSense}'")
+    sense = {'rising': 1, 'falling': -1}[isoSense or ('rising' if sigma else 'falling')]
+    relative, zref = isoRelative != '', 10.0
+    if relative:
+        try:
+            zref = float(isoRelative)
+        except ValueError:
+            zref = numpy.nan
+        if not numpy.isfinite(zref):
+            raise RuntimeError(f"ERROR: --iso-relative must be ZREF, a finite depth, got '{isoRelative}'")
+    sig = parseSigma(sigma) if sigma else None
+    name = sigmaName(sig[2]) if sig else isoOf
+    labels = [f'{name}@{zref:g}{v:+g}' if relative else f'{name}={v:g}' for v in values]
+    return dict(sigma=sig, of=isoOf, values=values, sense=sense, relative=relative, zref=zref, e3t=isoE3t, labels=labels)
+
+
+def isoSurfaceSeries(tFile, uFile, vFile, lonLatZPoints, spec, surfaceFile='', top=0.0, tracer='', tracerFile='', tracerRef=0.0,
+                     sverdrup=False, cellThickness=None):
+    """surfaceSeries with surfaces computed on the GPU (spec: checkIsoDepthArgs): (nt, m+2, ntransect) water flow -- or, with
+    `tracer`, transport of that variable -- in the layers bounded by the depths at which a variable of surfaceFile (default:
+    the T file), or the potential density of two, first reaches each value, one Field.computeSurfaceTransport per time step,
+    and the Field"""
+    from .surfaces import IsoDepth
+    path = surfaceFile or tFile
+    fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
+    if tracer:
+        fld.setTracer((tracerFile or tFile, tracer), reference=tracerRef)
+    source = _classField(path, spec['of'], '', spec['sigma'])
+    item = IsoDepth(source, spec['values'], spec['sense'], e3t=(path, spec['e3t']) if spec['e3t'] else None,
+                    relative=spec['relative'], zref=spec['zref'])
+    fld.setDepthSurfaces([item], top=top)
+    totals = numpy.array([fld.computeSurfaceTransport(t, carry=bool(tracer), prefetch_next=True)[0] for t in range(fld.nt)])
+    return totals.reshape(fld.nt, item.m + 2, len(lonLatZPoints)), fld
+
+
 def checkGrossArgs(gross=False, classes='', levels=False, decompose=False, eddy=False, show=False):
     """the --gross option of the command line: refused combinations raise RuntimeError"""
     if not gross:
@@ -718,24 +822,36 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
          classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect='', depthSurfaces='',
-         surfaceFile=''):
+         surfaceFile='', isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer=''):
     sig = None
     checkTimeMeanArgs(timeWeights, timeSelect, eddy)
-    checkDepthSurfacesArgs(depthSurfaces, surfaceFile, depthTop,
+    iso = checkIsoDepthArgs(isoDepth, isoOf, isoSense, isoRelative, isoE3t, mixedLayer, sigma, depthSurfaces, depthTop,
+                            **{'--depth-bins': depthBins, '--classes': classes, '--classes2': classes2,
+                               '--gross-classes': grossClasses, '--class-area': classArea, '--crossings': crossings,
+                               '--gross': gross, '--levels': levels, '--decompose': decompose, '--eddy': eddy, '--show': show,
+                               '--carry': carry, '--tracer2': tracer2, '--zrange': zrange,
+                               '--thickness-weighted': thicknessWeighted, '--remap': remap})
+    # --surface-file and --sigma belong to --iso-depth / --mixed-layer when one of them is given
+    checkDepthSurfacesArgs(depthSurfaces, '' if iso else surfaceFile, depthTop,
                            **{'--depth-bins': depthBins, '--classes': classes, '--classes2': classes2,
                               '--gross-classes': grossClasses, '--class-area': classArea, '--crossings': crossings, '--gross': gross,
                               '--levels': levels, '--decompose': decompose, '--eddy': eddy, '--show': show, '--carry': carry,
                               '--tracer2': tracer2, '--sigma': sigma, '--zrange': zrange,
                               '--thickness-weighted': thicknessWeighted, '--remap': remap})
-    if depthSurfaces:
+    if depthSurfaces or iso:
         checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
         checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
         unit = 'Sv' if sverdrup else 'A m^2/s'
         ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
-        surfaces = parseSurfaces(depthSurfaces)
-        totals, fld = surfaceSeries(tFile, uFile, vFile, lonLatZPoints, surfaces, surfaceFile, float(depthTop), tracer, tracerFile,
-                                    float(tracerRef), sverdrup, ct)
+        if iso:
+            surfaces = iso['labels']
+            totals, fld = isoSurfaceSeries(tFile, uFile, vFile, lonLatZPoints, iso, surfaceFile, float(depthTop), tracer,
+                                           tracerFile, float(tracerRef), sverdrup, ct)
+        else:
+            surfaces = parseSurfaces(depthSurfaces)
+            totals, fld = surfaceSeries(tFile, uFile, vFile, lonLatZPoints, surfaces, surfaceFile, float(depthTop), tracer,
+                                        tracerFile, float(tracerRef), sverdrup, ct)
         if tracer:
             totals = totals * float(tracerScale)
             title = (f'# transport of {tracer} by layer between surfaces [{tracer} x {unit}' +
@@ -1028,6 +1144,26 @@ if __name__ == '__main__':
                          '--cell-thickness the layer depths are the running sum of e3u / e3v')
     ap.add_argument('--surface-file', dest='surfaceFile', default='', metavar='FILE',
                     help='with --depth-surfaces: the file that holds the surfaces (default: the T file)')
+    ap.add_argument('--iso-depth', dest='isoDepth', default='', metavar='V1[,...,Vm]',
+                    help='the table of --depth-surfaces with surfaces computed on the GPU, one time step at a time: the depths at '
+                         'which the variable of --iso-of NAME, or the potential density of --sigma THETA,SALT[,PREF], first '
+                         'reaches each of the 1 to 8 values going down the column (linear between level centres; the sea bed '
+                         'where it never does, --depth-top where level 0 already has).  The variables are read from the T file, '
+                         'or from --surface-file.  --depth-top, --tracer, --cell-thickness and -s apply as with '
+                         '--depth-surfaces; refused together with it')
+    ap.add_argument('--iso-of', dest='isoOf', default='', metavar='NAME', help='with --iso-depth: the variable (e.g. thetao)')
+    ap.add_argument('--iso-sense', dest='isoSense', default='', metavar='rising|falling',
+                    help='with --iso-depth: whether the variable rises downward (density; the default with --sigma) or falls '
+                         '(temperature; the default with --iso-of)')
+    ap.add_argument('--iso-relative', dest='isoRelative', default='', metavar='ZREF',
+                    help="with --iso-depth: the values are offsets from the variable's own value at depth ZREF (a threshold "
+                         "criterion: --iso-of thetao --iso-depth -0.2 --iso-relative 10)")
+    ap.add_argument('--iso-e3t', dest='isoE3t', default='', metavar='NAME',
+                    help='with --iso-depth or --mixed-layer: the cell thicknesses at T-points, a variable of the same file '
+                         '(partial steps, z*); default: the level thicknesses of deptht_bounds')
+    ap.add_argument('--mixed-layer', dest='mixedLayer', default='', metavar='THETA,SALT[,DELTA[,ZREF]]',
+                    help='the table of --depth-surfaces with one surface, the mixed-layer depth: where sigma0 of THETA and SALT '
+                         'first exceeds its value at ZREF (default 10) by DELTA (default 0.03 kg m-3)')
     ap.add_argument('--tracer2', default='', metavar='NAME',
                     help='with --classes2: the second class field (e.g. so beside --tracer thetao); NAME is read from the T file')
     ap.add_argument('--tracer2-file', dest='tracer2File', default='', metavar='FILE', help='read --tracer2 from FILE instead')
