@@ -497,6 +497,38 @@ int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, 
  * 0 or 1: NF_ERR_ARG.  Changes nothing else. */
 int nf_field_compute_class_remap(nf_field **self, long tIndex, int carry, double *rows_host);        /* (nedges+2, row_length) */
 int nf_field_compute_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev);   /* HBM, field's stream */
+/* Remapped gross class transports: the inflow and the outflow of every class by conservative remapping -- the parts of
+ * nf_field_compute_gross_class_transport at the resolution in class space of nf_field_compute_class_remap, with the scalar or a
+ * per-cell thickness.  Needs nf_field_set_tracer and nf_field_set_class_edges (else NF_ERR_STATE).  One time step t over the
+ * owned levels; for every weight record, owned level z and slot i, in the order south, east, north, west:
+ *   q_i = w_i * d_i, d_i the slot's water term of nf_field_compute_gross_profile: the masked velocity, the arc, the Sverdrup
+ *        scale, and the thickness thickness[z] or, with a cell thickness set, fixth(e3u) / fixth(e3v) at the slot's own face; 0
+ *        for the south slot of row 0
+ *   c_i = q_i (carry = 0), or w_i * d_i^tau (carry = 1), d^tau the slot's term of the tracer profile as in
+ *        nf_field_compute_gross_class_transport; 0 for a face without a carried value
+ *   c_i is spread over the class rows exactly by the rule of nf_field_compute_class_remap: g_up and g_dn from the class field
+ *        (the class tracer when one is set, else the tracer; wrap_x is the tracer's) at levels z - 1 and z + 1 of the array on
+ *        the same face, lo = min, hi = max, row j of row(lo) .. row(hi) gets c_i * ((right - left) / (hi - lo)), nothing where
+ *        right == left; lo == hi: whole to row(lo); g_up, g_dn or g_dn - g_up not finite: whole to row(f_z); no class value at
+ *        level z (or NaN): whole to row n + 1
+ *   the shares go to the rows of P where q_i > 0 and to the rows of N where q_i < 0; q_i == 0 (or NaN): to neither.
+ * rows (2, n + 2, row_length): P then N, each row [segments | transects], written whole.  A lane's accumulator of a row starts
+ * at +0.0 and takes its shares level-ascending, then in slot order, then row-ascending; then the fixed tree of the transect
+ * reduction follows: no atomics, bitwise reproducible, independent of the window (the class_window knob applies; each part is
+ * built from windows of its own rows).  Hence, bit for bit: a class field that is constant in z gives the rows of
+ * nf_field_compute_gross_class_transport; the level index with edges at the half-integers gives the rows of
+ * nf_field_compute_gross_profile; negating uo and vo gives P' == -N, N' == -P; tau == ref + 1 gives the carry = 0 rows.  With
+ * carry = 0, P >= 0 >= N.  P + N is the row set of nf_field_compute_class_remap up to rounding, and these calls TAKE a cell
+ * thickness: their P + N is the route to the remapped class transports under partial steps or z* thicknesses.  Levels z - 1 and
+ * z + 1 are levels of the array, not of the owned range: under a slab range a rank reads one class-field level beyond each end
+ * of its levels, and a host-resident class field is staged with that halo (an HBM one is read in place); the thickness is read
+ * at the owned levels only.  A step this rank does not touch gives exact zeros.  carry other than 0 or 1, or a null argument:
+ * NF_ERR_ARG, decided before a device is needed; before set_tracer or set_class_edges, and for a static cell thickness uploaded
+ * for another shape: NF_ERR_STATE.  Host-resident uo / vo, tracers and time-varying cell thickness are staged per step.  The
+ * calls change neither the resident planes, |.| arrays, running max, last row, tracer planes, class / joint / depth / surface
+ * state nor a captured pass. */
+int nf_field_compute_gross_class_remap(nf_field **self, long tIndex, int carry, double *rows_host);       /* (2, n+2, row_length): P, N */
+int nf_field_compute_gross_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev);  /* HBM, field's stream */
 /* Per-cell layer thicknesses (partial steps, z* / variable-volume runs): the model's e3u / e3v, or thkcello on the U and V
  * grids, in place of the one number per level of nf_field_set_thickness.  e3u sits on the index of uo (the east face of cell
  * (j, i)), e3v on the index of vo: no interpolation, no neighbour.  Definition, with th_z read at the face:
@@ -518,7 +550,9 @@ int nf_field_compute_class_remap_async(nf_field **self, long tIndex, int carry, 
  * the markers.  Setting or clearing invalidates a captured pass; the all-steps-in-one-launch form of small grids is not used
  * while one is set.  Refused while one is set (NF_ERR_STATE, the message saying how to clear it): the forms that do not take
  * per-cell thicknesses yet -- nf_field_compute_tracer_profile*, nf_field_compute_class_transport*,
- * nf_field_compute_class_tracer_transport* and nf_field_compute_class_remap*.
+ * nf_field_compute_class_tracer_transport* and nf_field_compute_class_remap*.  P + N of
+ * nf_field_compute_gross_class_transport* is the route to the class transports under a cell thickness, and P + N of
+ * nf_field_compute_gross_class_remap* the route to the remapped ones.
  * A static host array that the handle uploaded belongs to the (nz, ny, nx) in force at that call.  After an
  * nf_field_set_bounds or nf_field_set_thickness that changes that shape (the shapes are compared, not the byte counts; a
  * call that leaves the shape as it was keeps the upload valid) every compute that would read the thickness returns

@@ -142,6 +142,8 @@ _sig('nf_field_compute_crossings', [_pp, ctypes.c_long, ctypes.c_int, c_double_p
 _sig('nf_field_compute_crossings_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_compute_gross_class_transport', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
 _sig('nf_field_compute_gross_class_transport_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
+_sig('nf_field_compute_gross_class_remap', [_pp, ctypes.c_long, ctypes.c_int, c_double_p])
+_sig('nf_field_compute_gross_class_remap_async', [_pp, ctypes.c_long, ctypes.c_int, ctypes.c_void_p])
 _sig('nf_field_compute_class_area', [_pp, ctypes.c_long, c_double_p])
 _sig('nf_field_compute_class_area_async', [_pp, ctypes.c_long, ctypes.c_void_p])
 _sig('nf_field_set_class_tracer', [_pp, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double])

@@ -992,6 +992,40 @@ static int field_gross_class_async(nf_field *f, long t, bool carry, double *rows
     return launch_gross_class_transport(a, f->stream);
 }
 
+// Remapped gross class transports of step t on the field's stream (nf_field_compute_gross_class_remap): rows_dev
+// (2, nedges + 2, row_length) = P, N, written whole.  field_class_step_async with remap = true -- the class forms' edges, window
+// and scratch, the class field staged with one halo level on each side of the owned range when it is host-resident -- with the
+// parts of field_gross_class_async and, unlike the net remap, a cell thickness (owned levels only).  Exact zeros for a step
+// this rank does not touch.  Reads the raw fields, the tracers, the cell thickness when one is set and the records; the
+// resident planes, |.| arrays, running max, last row, tracer planes, class / joint / depth / surface state, version and a
+// captured pass stay as they are.
+static int field_gross_remap_async(nf_field *f, long t, bool carry, double *rows_dev)
+{
+    const int nedges = (int)f->class_edges.host.size();
+    Levels lv;
+    NF_TRY(field_raw_step_begin(f, "compute_gross_class_remap", t, 2, rows_dev, 2 * ((size_t)nedges + 2), &lv));
+    if (lv.z1 <= lv.z0) return NF_OK;
+    NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
+    const int window = g_class_window;
+    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
+    const Levels cls_lv{std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)};
+    GrossRemapArgs a;
+    NF_TRY(field_step_input(f, t, lv, &a.in));
+    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : cls_lv, &a.cls));
+    if (carry) a.carry = a.cls;                                                     // the tracer is carried ...
+    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, cls_lv, &a.cls));   // ... and binned by the class tracer
+    NF_TRY(field_cell_thick(f, t, lv, &a.th));
+    a.edges = f->class_edges.dev.get();
+    a.nedges = nedges;
+    a.window = window;
+    a.tr = field_transects(f);
+    a.scratch = f->class_scratch.get();
+    a.scratch_len = f->class_scratch.size();
+    a.rows = rows_dev;
+    a.nz = (int)f->nz;
+    return launch_gross_class_remap(a, f->stream);
+}
+
 // Section area (A) and area-weighted tracer (B) of step t in the classes of the class field on the field's stream: rows_dev
 // (2, nedges + 2, row_length) = A, B, written whole.  Owned levels only, exact zeros for a step this rank does not touch.  The
 // class field is the class tracer when one is set, else the tracer, which is the carried one either way.  It takes a cell
@@ -2066,7 +2100,7 @@ try {
 }
 NF_API_CATCH
 
-// the checks of the two gross class calls that need no device: arguments, then the tracer and the class edges
+// the checks of the gross class calls (step rule and remap) that need no device: arguments, then the tracer and the class edges
 static int field_gross_class_args(nf_field **self, int carry, const void *rows, const char *what)
 {
     const std::string w(what);
@@ -2092,6 +2126,26 @@ try {
     nf_field *f = *self;
     NF_NEED_DEVICE();
     return field_gross_class_async(f, tIndex, carry != 0, rows_dev);
+}
+NF_API_CATCH
+
+int nf_field_compute_gross_class_remap(nf_field **self, long tIndex, int carry, double *rows_host)
+try {
+    NF_TRY(field_gross_class_args(self, carry, rows_host, "nf_field_compute_gross_class_remap"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    const size_t n = 2 * (f->class_edges.host.size() + 2) * field_row_length(f);
+    if (n == 0) return NF_OK;
+    return field_sync(f, n, rows_host, [&](double *rows) { return field_gross_remap_async(f, tIndex, carry != 0, rows); });
+}
+NF_API_CATCH
+
+int nf_field_compute_gross_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev)
+try {
+    NF_TRY(field_gross_class_args(self, carry, rows_dev, "nf_field_compute_gross_class_remap_async"));
+    nf_field *f = *self;
+    NF_NEED_DEVICE();
+    return field_gross_remap_async(f, tIndex, carry != 0, rows_dev);
 }
 NF_API_CATCH
 

@@ -671,6 +671,28 @@ struct GrossClassArgs {
 };
 int launch_gross_class_transport(const GrossClassArgs &a, hipStream_t s);
 
+// Remapped gross class transports (nf_field_compute_gross_class_remap, nf_integral.hip; the contract is in nemoflux_amd.h): the
+// terms and parts of GrossClassArgs -- rows (2, nedges + 2, row_length) = P, N -- each term spread over the class rows by the
+// rule of launch_class_remap instead of going whole to the row of its face (k_gross_remap_segscan).  No term table: like the
+// remap it walks the fields once per window of rows, here once per part and window, with ClassArgs' scratch of ws.nrec * window
+// run sums.  nz: the levels of the arrays -- the class field's levels z0 - 1 and z1 are read where the array has them; the cell
+// thickness is read at the owned levels only.
+struct GrossRemapArgs {
+    StepInput in;
+    TracerIn cls;                // the class field; its wrap_x is the rule of every face, its ref is not read
+    TracerIn carry;              // the carried tracer (the class field itself, or another array); tau == nullptr: volume form
+    CellThick th;
+    const double *edges = nullptr;   // device, nedges
+    int nedges = 0;
+    int window = 0;              // rows per pass over the fields, 1 .. kClassWindowMax
+    Transects tr;
+    double *scratch = nullptr;   // nrec * window run sums
+    size_t scratch_len = 0;
+    double *rows = nullptr;      // (2 * (nedges + 2), row_length)
+    int nz = 0;
+};
+int launch_gross_class_remap(const GrossRemapArgs &a, hipStream_t s);
+
 // Section area and area-weighted tracer in tracer classes (nf_field_compute_class_area, nf_integral.hip): the alpha and beta of
 // the area profile sent to the class row of their own face instead of their level: rows (2, nedges + 2, row_length) = A, B, row
 // part * (nedges + 2) + r of JointArgs' window bitmap, binned by the joint classes' stage 2.  A table entry holds one term per

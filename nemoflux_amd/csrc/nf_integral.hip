@@ -1256,6 +1256,32 @@ __global__ __launch_bounds__(kBlock) void k_class_segscan(const int *__restrict_
 constexpr int kRemapLevels = 4;        // levels whose 9 gathers are issued together (volume form, one-tracer carry form)
 constexpr int kRemapLevelsTwo = 2;     // ... whose 14 gathers are (carry form with a class field of its own)
 
+// The row rule above for one term, shared by k_class_remap_segscan and k_gross_remap_segscan: the window of a lane, the class
+// field's markers and the edges.  spread: the term t of the face (a, b) at a level whose class values are (a1, b1), with
+// (a0, b0) above and (a2, b2) below (up, dn: the array has that level).
+template <typename T>
+struct RemapRows {
+    WindowLds w;
+    T tfill, tfill2;
+    int nedges, top, r0, nwin;
+    __device__ void add(int row, double x) const { window_add<kBlock>(w.acc, row, r0, nwin, x); }
+    __device__ int row(double x) const { return class_row(true, x, w.e, nedges, top); }
+    __device__ void spread(T a0, T b0, T a1, T b1, T a2, T b2, bool has_b, bool up, bool dn, double t) const
+    {
+        double f, fu = 0.0, fd = 0.0;
+        const bool h = tr_face_raw<T>(a1, b1, has_b, tfill, tfill2, &f);
+        if (!h || f != f) return add(nedges + 1, t);
+        const bool hu = up && tr_face_raw<T>(a0, b0, has_b, tfill, tfill2, &fu);
+        const bool hd = dn && tr_face_raw<T>(a2, b2, has_b, tfill, tfill2, &fd);
+        const double gu = hu ? 0.5 * (fu + f) : f, gd = hd ? 0.5 * (fd + f) : f;
+        if (!(__builtin_isfinite(gu) && __builtin_isfinite(gd) && __builtin_isfinite(gd - gu))) return add(row(f), t);
+        const double lo = gu < gd ? gu : gd, hi = gu < gd ? gd : gu;
+        const int jlo = row(lo);
+        if (lo == hi) return add(jlo, t);
+        spread_span<kBlock, 1>(w.acc, w.e, RowSpan{lo, hi, jlo, row(hi)}, t, r0, r0 + nwin - 1);
+    }
+};
+
 template <typename T, bool TWO, typename... TI>
 __global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
                                                                 const int *__restrict__ seg, long n, const T *__restrict__ u,
@@ -1280,23 +1306,8 @@ __global__ __launch_bounds__(kBlock) void k_class_remap_segscan(const int *__res
         key = load_key(seg, k);
         const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, wrap_x);
         const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
-        const int rend = r0 + nwin - 1;
-        auto add = [&](int row, double x) { window_add<kBlock>(w.acc, row, r0, nwin, x); };
-        auto row = [&](double x) { return class_row(true, x, w.e, nedges, top); };
-        // the term t of the face (a, b) at a level whose class values are (a1, b1), with (a0, b0) above and (a2, b2) below
-        auto spread = [&](T a0, T b0, T a1, T b1, T a2, T b2, bool has_b, bool up, bool dn, double t) {
-            double f, fu = 0.0, fd = 0.0;
-            const bool h = tr_face_raw<T>(a1, b1, has_b, tfill, tfill2, &f);
-            if (!h || f != f) return add(nedges + 1, t);
-            const bool hu = up && tr_face_raw<T>(a0, b0, has_b, tfill, tfill2, &fu);
-            const bool hd = dn && tr_face_raw<T>(a2, b2, has_b, tfill, tfill2, &fd);
-            const double gu = hu ? 0.5 * (fu + f) : f, gd = hd ? 0.5 * (fd + f) : f;
-            if (!(__builtin_isfinite(gu) && __builtin_isfinite(gd) && __builtin_isfinite(gd - gu))) return add(row(f), t);
-            const double lo = gu < gd ? gu : gd, hi = gu < gd ? gd : gu;
-            const int jlo = row(lo);
-            if (lo == hi) return add(jlo, t);
-            spread_span<kBlock, 1>(w.acc, w.e, RowSpan{lo, hi, jlo, row(hi)}, t, r0, rend);
-        };
+        const RemapRows<T> rows{w, tfill, tfill2, nedges, top, r0, nwin};
+        auto spread = [&](auto... a) { rows.spread(a...); };
         LevelTau<T> c[RL + 2];   // the class field of levels z - 1 .. z + RL
         c[1] = load_level_tau(tau, (long)z0 * ncell, r.c, nb);
         c[0] = z0 > 0 ? load_level_tau(tau, (long)(z0 - 1) * ncell, r.c, nb) : c[1];
@@ -1436,6 +1447,146 @@ int launch_class_remap(const ClassArgs &a, hipStream_t s)
     if (in.dtype == NF_F64) return launch_class_form<double, true>(a, s);
     if (in.dtype == NF_F32) return launch_class_form<float, true>(a, s);
     NF_REQUIRE(false, NF_ERR_ARG, "class remap: dtype must be NF_F64 or NF_F32");
+}
+
+// ---- remapped gross (inflow / outflow) class transports: the gross class terms under the remap kernel's row rule -------------
+// Where k_gross_class_terms and k_class_remap_segscan cross.  Per (record, owned level, slot) the water term q = w * d and the
+// carried term c (= q in the volume form, w * d^tau with a TauIn<T> among the trailing arguments) are k_gross_class_terms'
+// (weighted_slots of level_slots_tf<T, false> / <T, true>; with a ThickIn<T> among the trailing arguments the thickness at the
+// slot's own face, level_th); c is spread over the class rows by RemapRows::spread from the rolling class-field window c[] of
+// k_class_remap_segscan.  `part` picks the terms of a launch: 0 = P, the slots with q > 0; 1 = N, those with q < 0; a slot with
+// q == 0 or NaN (row 0's south slot among them) is in neither.  The rows of a part are n + 2 window rows of their own, so no
+// window straddles the parts and a lane's adds to a row run level-ascending, then in slot order, then row-ascending, from
+// +0.0: skipping the other part's terms leaves the order of the kept ones alone, which is why negating uo / vo swaps and
+// negates the parts bit for bit.  TWO: the carried tracer is another array than the class field (5 more gathers per level).
+// Levels whose gathers are issued together: 4 (volume and one-tracer forms: 9 per level, 13 with per-cell thicknesses), 2 with
+// a class field of its own (14, 18).
+constexpr int kGrossRemapLevels = 4;
+constexpr int kGrossRemapLevelsTwo = 2;
+
+template <typename T, bool TWO, typename... TI>
+__global__ __launch_bounds__(kBlock) void k_gross_remap_segscan(const int *__restrict__ cell, const double *__restrict__ w4,
+                                                                const int *__restrict__ seg, long n, const T *__restrict__ u,
+                                                                const T *__restrict__ v, const T *__restrict__ tau, long ncell,
+                                                                unsigned nx, int z0, int z1,
+                                                                const double *__restrict__ thickness,
+                                                                const double *__restrict__ arcE,
+                                                                const double *__restrict__ arcN, T fill, T fill2, int two,
+                                                                T tfill, T tfill2, int wrap_x, double scale, int sverdrup,
+                                                                const double *__restrict__ edges, int nedges, int top, int r0,
+                                                                int nwin, double *__restrict__ runsum, int nz, int part,
+                                                                TI... extra)
+{
+    constexpr bool CARRY = (std::is_same<TI, TauIn<T>>::value || ...);
+    constexpr bool CT = (std::is_same<TI, ThickIn<T>>::value || ...);
+    constexpr int RL = TWO ? kGrossRemapLevelsTwo : kGrossRemapLevels;
+    static_assert(CARRY || !TWO, "a class field of its own needs a carried tracer");
+    const TauIn<T> ti = tau_in<T>(extra...);
+    const ThickIn<T> ct = thick_arg<T>(extra...);
+    const WindowLds w = window_lds(edges, nedges, nwin);
+    const long k = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    int key = -1;
+    if (k < n) {   // z0 < z1 <= nz: the launcher's
+        const Record r = load_record(cell, w4, k);
+        key = load_key(seg, k);
+        const ClassNeighbours nb = class_neighbours(r.c, nx, ncell, wrap_x);
+        const Arcs arc = load_arcs(arcE, arcN, r.c, nb);
+        const RemapRows<T> rows{w, tfill, tfill2, nedges, top, r0, nwin};
+        auto mine = [&](double q) { return part ? q < 0.0 : q > 0.0; };
+        LevelTau<T> c[RL + 2];   // the class field of levels z - 1 .. z + RL
+        c[1] = load_level_tau(tau, (long)z0 * ncell, r.c, nb);
+        c[0] = z0 > 0 ? load_level_tau(tau, (long)(z0 - 1) * ncell, r.c, nb) : c[1];
+        for (int z = z0; z < z1; z += RL) {
+            const int nlev = z1 - z < RL ? z1 - z : RL;
+            LevelUV<T> x[RL];
+            LevelUV<T> e3[CT ? RL : 1];
+            LevelTau<T> tt[TWO ? RL : 1];               // the carried tracer, when it is another array
+#pragma unroll
+            for (int l = 0; l < RL; ++l)
+                if (l < nlev) {
+                    const long o = (long)(z + l) * ncell;
+                    x[l] = load_level_uv(u, v, o, r.c, nb);
+                    if constexpr (CT) e3[l] = load_level_e3(ct, o, r.c, nb);
+                    c[l + 2] = z + l + 1 < nz ? load_level_tau(tau, o + ncell, r.c, nb) : c[l + 1];
+                    if constexpr (TWO) tt[l] = load_level_tau(ti.tau, o, r.c, nb);
+                }
+#pragma unroll
+            for (int l = 0; l < RL; ++l)
+                if (l < nlev) {
+                    const LevelTau<T> &p = c[l], &m = c[l + 1], &d = c[l + 2];
+                    const bool up = z + l > 0, dn = z + l + 1 < nz;
+                    SlotTh th;
+                    if constexpr (CT)
+                        th = level_th(e3[l], ct);
+                    else
+                        th = slot_th(thickness[z + l]);
+                    const Slots q = weighted_slots(
+                        r, level_slots_tf<T, false>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south, FaceTf{}));
+                    Slots t = q;
+                    if constexpr (CARRY)
+                        t = weighted_slots(r, level_slots_tf<T, true>(th, x[l], arc, fill, fill2, two, scale, sverdrup, nb.south,
+                                                                      level_tf(TWO ? tt[l] : m, nb, ti)));
+                    if (nb.south && mine(q.s)) rows.spread(p.s, p.c, m.s, m.c, d.s, d.c, true, up, dn, t.s);
+                    if (mine(q.e)) rows.spread(p.c, p.e, m.c, m.e, d.c, d.e, nb.has_e, up, dn, t.e);
+                    if (mine(q.n)) rows.spread(p.c, p.n, m.c, m.n, d.c, d.n, nb.has_n, up, dn, t.n);
+                    if (mine(q.w)) rows.spread(p.w, p.c, m.w, m.c, d.w, d.c, nb.has_w, up, dn, t.w);
+                }
+            c[0] = c[RL];
+            c[1] = c[RL + 1];
+        }
+    }
+    window_scan_store<kBlock>(w.acc, key, lane, k, n, nwin, runsum);
+}
+
+// P then N: one for_each_window loop per part over its n + 2 rows, `rows + part * (n + 2) * row_length`.  extra: the carried
+// tracer (TWO or not), then the per-cell thicknesses, each where the form has one.
+template <typename T, bool TWO, typename... TI>
+static int launch_gross_remap_t(const GrossRemapArgs &a, hipStream_t s, TI... extra)
+{
+    const WeightSet &ws = *a.tr.ws;
+    const StepInput &in = a.in;
+    const T fill = (T)in.fill, fill2 = (T)in.fill2;
+    const int top = class_top(a.nedges), wrap_x = a.cls.wrap_x ? 1 : 0, nrows = a.nedges + 2;
+    for (int part = 0; part < 2; ++part)
+        NF_TRY(for_each_window(a.tr, nrows, a.window, a.scratch, a.rows + (long)part * nrows * a.tr.row_length(), s,
+                               [&](int r0, int nwin, int) {
+            return launch_lds(&k_gross_remap_segscan<T, TWO, TI...>, record_grid(ws), dim3(kBlock),
+                              class_lds_bytes(a.nedges, nwin), s, ws.cell.get(), ws.w4.get(), ws.seg.get(), ws.nrec, (const T *)in.u,
+                              (const T *)in.v, (const T *)a.cls.tau, in.ncell, (unsigned)in.nx, in.z0, in.z1, in.thickness, in.arcE,
+                              in.arcN, fill, fill2, (int)uv_two_markers(fill, fill2), (T)a.cls.fill, (T)a.cls.fill2, wrap_x,
+                              in.scale, in.sverdrup, a.edges, a.nedges, top, r0, nwin, a.scratch, a.nz, part, extra...);
+        }));
+    return NF_OK;
+}
+
+template <typename T>
+static int launch_gross_remap_form(const GrossRemapArgs &a, hipStream_t s)
+{
+    const bool one = a.carry.tau == a.cls.tau && same_bits(a.carry.fill, a.cls.fill) && same_bits(a.carry.fill2, a.cls.fill2);
+    TracerIn carry = a.carry;   // the carried tracer with the class field's wrap rule
+    carry.wrap_x = a.cls.wrap_x;
+    return launch_tracer_thick_form<T>(carry, a.th, [&](auto... extra) {
+        if constexpr ((std::is_same<decltype(extra), TauIn<T>>::value || ...))
+            if (!one) return launch_gross_remap_t<T, true>(a, s, extra...);
+        return launch_gross_remap_t<T, false>(a, s, extra...);
+    });
+}
+
+int launch_gross_class_remap(const GrossRemapArgs &a, hipStream_t s)
+{
+    const StepInput &in = a.in;
+    NF_REQUIRE(a.nedges >= 2 && a.nedges <= kMaxClassEdges && a.edges, NF_ERR_ARG, "gross class remap: bad class edges");
+    NF_REQUIRE(a.window >= 1 && a.window <= kClassWindowMax, NF_ERR_ARG, "gross class remap: bad window");
+    NF_TRY(check_raw_step("gross class remap", in, a.tr, a.scratch_len, (size_t)a.window));
+    NF_REQUIRE(in.u && in.v && a.cls.tau && a.rows && in.thickness && in.arcE && in.arcN, NF_ERR_ARG,
+               "gross class remap: null argument");
+    NF_REQUIRE(!a.th.e3u || a.th.e3v, NF_ERR_ARG, "gross class remap: null argument");
+    NF_REQUIRE(in.z0 < in.z1 && in.z1 <= a.nz, NF_ERR_ARG, "gross class remap: bad levels");
+    if (a.tr.row_length() == 0) return NF_OK;
+    if (in.dtype == NF_F64) return launch_gross_remap_form<double>(a, s);
+    if (in.dtype == NF_F32) return launch_gross_remap_form<float>(a, s);
+    NF_REQUIRE(false, NF_ERR_ARG, "gross class remap: dtype must be NF_F64 or NF_F32");
 }
 
 // ---- transports in true-depth bins: the terms of the profile, each spread over the depth of its layer at its own face ------

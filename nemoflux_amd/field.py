@@ -771,7 +771,7 @@ class Field(object):
         array of another dtype raises.  fill_value / missing_value: the thickness's own missing markers (a file's when not
         given); a thickness that is NaN or a marker counts as 0.
         computeFlux, computeAll, update, computeFluxProfile, computeTracerFlux, computeTracerAll, computeAreaProfile, computeClassArea and
-        computeGrossProfile and computeGrossClassTransport (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
+        computeGrossProfile, computeGrossClassTransport and computeGrossClassRemap (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
         set.  timeMean and meanEddyTracerTransport carry a static thickness over to the mean state and take a time-varying one
         with thicknessWeighted=True (thickness-weighted mean velocities, mean thicknesses).  setCellThickness(None, None) goes
         back to deptht_bounds."""
@@ -1455,13 +1455,13 @@ class Field(object):
 
     _SPLIT_METHODS = ('computeTracerFlux', 'computeFluxProfile', 'computeTracerProfile', 'computeClassTransport',
                       'computeClassTracerTransport', 'computeClassRemap', 'computeDepthTransport', 'computeGrossProfile',
-                      'computeGrossClassTransport', 'computeSurfaceTransport')
+                      'computeGrossClassTransport', 'computeGrossClassRemap', 'computeSurfaceTransport')
 
     def meanEddySplit(self, method, steps=None, select=None, weights=None, thicknessWeighted=False, **kw):
         """The time mean of one per-step row product split into the part of the mean state and the rest.  method: the name of
         the product -- computeTracerFlux, computeFluxProfile, computeTracerProfile, computeClassTransport,
         computeClassTracerTransport, computeClassRemap, computeDepthTransport, computeGrossProfile,
-        computeGrossClassTransport or computeSurfaceTransport; kw goes to it (carry=).  steps / select / weights choose and weight the steps as in
+        computeGrossClassTransport, computeGrossClassRemap or computeSurfaceTransport; kw goes to it (carry=).  steps / select / weights choose and weight the steps as in
         timeMean.  Returns a dict: 'total' = sum of w_j rows_j over the visited steps / sum of w_j, formed on the host in float64
         step by step in their order; 'mean' = the same product at step 0 of 'meanField' = timeMean(steps, thicknessWeighted,
         select, weights), the transport by the mean flow of the mean tracer in the classes of the mean class field; 'eddy' =
@@ -1999,6 +1999,40 @@ class Field(object):
         else:
             rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
             check(lib.nf_field_compute_gross_class_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        return self._split_rows(rows.reshape(2, nrows, self._row_width))
+
+    def computeGrossClassRemap(self, tIndex, carry=False, out=None, prefetch_next=None):
+        """Gross transports of time step tIndex in tracer classes by conservative (piecewise-linear) remapping (setTracer and
+        setClassEdges first): what computeGrossClassTransport returns -- (totals, segments) of shape (2, nedges+2, ntransect)
+        and (2, nedges+2, nseg), part 0 = P, the inflow of every class, part 1 = N, its outflow -- with every term spread over
+        the classes by the rule of computeClassRemap (the interval between the class field's values at the layer's upper and
+        lower interface on the term's own face) instead of going whole to the class of its face.  The shares of a term go to
+        P where the water term of its slot is > 0 and to N where it is < 0.  carry=True: the terms of
+        computeClassTracerTransport, split by the direction of the water all the same.  The inflow and outflow of every class
+        are then smooth functions of the class with hundreds of edges on 75 levels, where the step rule gives a comb.  Unlike
+        computeClassRemap this call takes a cell thickness (setCellThickness): P + N is the remapped class transport -- a
+        smooth MOC(sigma), heat by sigma -- under partial steps and z* thicknesses, on the Field of
+        timeMean(thicknessWeighted=True) too; without one P + N is the rows of computeClassRemap up to rounding.  A class field
+        that is constant in z gives the parts of computeGrossClassTransport bit for bit.  The parts go as they are into
+        grossTransport, transportWeightedTracer and classStreamfunction(P + N).  Levels this rank does not own (slab_range)
+        contribute nothing, but the class field is read one level beyond them.  Leaves everything else as it is.  `out`: as
+        in computeGrossClassTransport."""
+        tIndex = int(tIndex)
+        edges = getattr(self, '_class_edges', None)
+        if edges is None:
+            raise RuntimeError('ERROR: call setClassEdges first')
+        self._stage(tIndex, prefetch_next)
+        self._stage_tracer(tIndex)
+        nrows = edges.size + 2
+        carry = 1 if carry else 0
+        if out is not None:
+            out = self._rows_out(out, 2 * nrows)
+            check(lib.nf_field_compute_gross_class_remap_async(ctypes.byref(self._h), tIndex, carry,
+                                                               ctypes.c_void_p(out.data_ptr())))
+            rows = out.cpu().numpy()
+        else:
+            rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
+            check(lib.nf_field_compute_gross_class_remap(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
         return self._split_rows(rows.reshape(2, nrows, self._row_width))
 
     def computeClassArea(self, tIndex, out=None, prefetch_next=None):

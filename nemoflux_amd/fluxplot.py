@@ -36,6 +36,8 @@ only with --show): the table is always printed or written as CSV, which is what 
     ... --gross [--tracer thetao] [--zrange 0,700] (inflow, outflow and net of every transect; what they carry, their mean thetao)
     ... --tracer sigma0 --tracer-file S.nc --gross-classes 26,27,28 [--carry thetao] [--cell-thickness]
                                   (inflow, outflow and net of every sigma0 class: one CSV line per time step, transect and class)
+    ... --sigma thetao,so --gross-classes 26,26.01,...,28 --gross-remap linear [--carry thetao] [--cell-thickness]
+                                  (the same table by conservative remapping: smooth in the class, under e3u / e3v too)
     ... --tracer sigma0 --tracer-file S.nc --class-area 26,27,28 [--carry thetao] [--cell-thickness]
                                   (section area, mean carried tracer and interface depth of every sigma0 class: one CSV line
                                   per time step, transect and class; --sigma thetao,so in place of --tracer works too)
@@ -307,10 +309,10 @@ def grossSeries(tFile, uFile, vFile, lonLatZPoints, tracer='', tracerFile='', tr
 
 
 def grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', carry='', carryFile='', carryRef=0.0,
-                     sverdrup=False, cellThickness=None, sigma=None):
+                     sverdrup=False, cellThickness=None, sigma=None, remap=False):
     """(nt, 2, nedges+2, ntransect) inflow and outflow of every class of the variable `tracer` of tracerFile (default: the T
     file), one Field.computeGrossClassTransport per time step, and the Field.  With `carry`: what they carry of that variable
-    of carryFile (reference carryRef) instead of the water."""
+    of carryFile (reference carryRef) instead of the water.  remap: one Field.computeGrossClassRemap per step instead."""
     fld = _field(tFile, uFile, vFile, lonLatZPoints, sverdrup, cellThickness)
     if carry:
         fld.setTracer((carryFile or tFile, carry), reference=carryRef)
@@ -318,8 +320,32 @@ def grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFi
     else:
         fld.setTracer(_classField(tFile, tracer, tracerFile, sigma))
     fld.setClassEdges(edges)
-    totals = numpy.array([fld.computeGrossClassTransport(t, carry=bool(carry), prefetch_next=True)[0] for t in range(fld.nt)])
+    step = fld.computeGrossClassRemap if remap else fld.computeGrossClassTransport
+    totals = numpy.array([step(t, carry=bool(carry), prefetch_next=True)[0] for t in range(fld.nt)])
     return totals.reshape(fld.nt, 2, len(edges) + 2, len(lonLatZPoints)), fld
+
+
+def grossRemapSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile='', carry='', carryFile='', carryRef=0.0,
+                     sverdrup=False, cellThickness=None, sigma=None):
+    """(nt, 2, nedges+2, ntransect) rows of grossClassSeries by conservative remapping, one Field.computeGrossClassRemap per time
+    step, and the Field: what remapSeries is to classSeries, and with cellThickness the one remapped table under e3u / e3v."""
+    return grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile, carryRef, sverdrup,
+                            cellThickness, sigma, remap=True)
+
+
+def checkGrossRemapArgs(grossRemap='', grossClasses='', classes=''):
+    """the --gross-remap option of the command line (conservative remapping of the table of --gross-classes): refused
+    combinations raise RuntimeError"""
+    if not grossRemap:
+        return
+    if grossRemap != 'linear':
+        raise RuntimeError(f"ERROR: --gross-remap must be 'linear' (piecewise-linear conservative remapping), got {grossRemap!r}")
+    if classes:
+        raise RuntimeError('ERROR: --gross-remap and --classes cannot be combined: --gross-remap applies to the table of '
+                           '--gross-classes (--remap is the option of --classes)')
+    if not grossClasses:
+        raise RuntimeError('ERROR: --gross-remap needs --gross-classes E0,...,EN (with --tracer NAME or --sigma THETA,SALT[,PREF]; '
+                           '--carry NAME and --cell-thickness apply)')
 
 
 def checkGrossClassArgs(grossClasses='', tracer='', tracerRef=0.0, tracerScale=1.0, classes='', classes2='', gross=False,
@@ -822,8 +848,9 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
          classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect='', depthSurfaces='',
-         surfaceFile='', isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer=''):
+         surfaceFile='', isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer='', grossRemap=''):
     sig = None
+    checkGrossRemapArgs(grossRemap, grossClasses, classes)
     checkTimeMeanArgs(timeWeights, timeSelect, eddy)
     iso = checkIsoDepthArgs(isoDepth, isoOf, isoSense, isoRelative, isoE3t, mixedLayer, sigma, depthSurfaces, depthTop,
                             **{'--depth-bins': depthBins, '--classes': classes, '--classes2': classes2,
@@ -953,13 +980,16 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         return totals
     if grossClasses:
         edges = parseClasses(grossClasses)
-        totals, fld = grossClassSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
-                                       float(carryRef), sverdrup, ct, sig)
+        series = grossRemapSeries if grossRemap else grossClassSeries
+        totals, fld = series(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile, float(carryRef),
+                             sverdrup, ct, sig)
         title = f'# gross water flow by {tracer} class [{unit}]'
         if carry:
             totals = totals * float(carryScale)
             title = (f'# gross transport of {carry} by {tracer} class [{carry} x {unit}' +
                      (f' x {float(carryScale):g}' if float(carryScale) != 1.0 else '') + ']')
+        if grossRemap:
+            title += ', conservative remapping'
         timeVals = [fld.timeObj.getTimeAsDate(t) for t in range(fld.nt)]
         bounds = [(-numpy.inf, edges[0])] + list(zip(edges[:-1], edges[1:])) + [(edges[-1], numpy.inf), (numpy.nan, numpy.nan)]
         lines = ['time,transect,lower,upper,' + ','.join(GROSS_COLUMNS)]
@@ -1194,6 +1224,11 @@ if __name__ == '__main__':
                          '(time,transect,lower,upper,inflow,outflow,net): the water of that class that crosses in the positive '
                          'direction, the water that comes back, and their sum; with --carry NAME what the two carry of NAME '
                          '(--carry-ref, --carry-scale, --cell-thickness and -s apply)')
+    ap.add_argument('--gross-remap', dest='grossRemap', default='', metavar='linear',
+                    help='with --gross-classes (and --carry, --cell-thickness, --sigma): conservative remapping -- a level\'s '
+                         'inflow and outflow are spread over the classes between the class field\'s values at the layer\'s two '
+                         'interfaces instead of going whole to one class: smooth inflow, outflow and net (MOC) with many classes, '
+                         'under per-cell thicknesses too')
     ap.add_argument('--class-area', dest='classArea', default='', metavar='E0,E1,...,EN',
                     help='with --tracer NAME or --sigma (the class field): one CSV line per time step, transect and class '
                          '(time,transect,lower,upper,area,mean,depth): the section area that the class occupies, the '
