@@ -883,6 +883,43 @@ int nf_iso_depth(void *out_dev, const void *tau_dev, const double *thickness_hos
                  int dtype, double tau_fill, double tau_missing, double e3t_fill, double e3t_missing, double top,
                  const double *values, int m, int sense, int relative, double zref, double fill_out, void *hip_stream);
 
+/* Layer thicknesses at the U and V faces from the thickness at T-points (nf_facethick.hip): the e3u / e3v of
+ * nf_field_set_cell_thickness computed from what the model writes -- e3t in grid_T, thkcello of CMIP6 -- where grid_U / grid_V
+ * carry none.  Value-level like nf_sigma_eos80 / nf_iso_depth: no nf_field involved, asynchronous on hip_stream.  All arrays
+ * are (nz, ny, nx), x fastest, of dtype, in HBM: e3t_dev one time step of the T-grid thickness; e3t0_dev, e3u0_dev, e3v0_dev the
+ * static thicknesses at the T, U and V points (e3t_0, e3u_0, e3v_0 of a mesh_mask), all three with NF_E3_ANOMALY, all NULL
+ * otherwise; e3u_out_dev on the index of uo (the east face of cell (j, i)), e3v_out_dev on the index of vo (its north face).
+ * Definition.  Everything is float64.  Every operation is rounded on its own, with no fused multiply-adds.  Inputs are widened
+ * first.  Each result is rounded once to dtype.
+ *   Presence.  present(x): x is not NaN and equals neither of its array's two markers, each cast to dtype and compared in
+ *     dtype.  fill / missing apply to e3t; fill0 / missing0 apply to all three statics.  NaN means "no marker".
+ *   Cell values.  For cell (z, j, i): A = e3t[z,j,i] and A0 = e3t0[z,j,i].
+ *   East (U) face.  This is the index of uo and the neighbour rule of the tracer block above.  B = e3t[z,j,i+1].  At
+ *     i = nx-1, B = e3t[z,j,0] when wrap_x is on, else no neighbour.
+ *   North (V) face.  B = e3t[z,j+1,i].  At j = ny-1 there is no neighbour.
+ *   Static neighbour.  B0 comes from e3t0 in the same way as B.
+ *   No neighbour by geometry.  Then B := A and B0 := A0.
+ *   rule = NF_E3_MIN (0; NEMO's partial-step rule e3u_0 = min(e3t_0(i), e3t_0(i+1))).  A and B both present: B < A ? B : A.
+ *     Otherwise +0.0: a face beside a cell without a thickness has no open area.
+ *   rule = NF_E3_MEAN (1).  Both present: 0.5 * (A + B).  Otherwise +0.0.
+ *   rule = NF_E3_ANOMALY (2; the z* / vvl rule of NEMO's dom_vvl_interpol WITHOUT its cell-area weights e1e2t / e1e2u: the
+ *     anomalies of the two cells count equally, which is NEMO's result only where the two cells have one area).  It needs the
+ *     three statics.  F0 is e3u0[z,j,i] for the east face and e3v0[z,j,i] for the north face.  F0 not present: +0.0.  F0
+ *     present and A, B, A0, B0 all present: F0 + 0.5 * ((A - A0) + (B - B0)), in that order.  F0 present but one of A, B, A0,
+ *     B0 missing: F0 (NEMO keeps e3u_0 on a masked face).
+ *   Non-finite or negative results are stored as they come.
+ * The result does not depend on the launch shape; there are no atomics.  3 * n * sizeof(dtype) bytes move with NF_E3_MIN and
+ * NF_E3_MEAN, 6 * n * sizeof(dtype) with NF_E3_ANOMALY (n = nz * ny * nx).
+ * NF_ERR_ARG, decided before a device is needed: a null output pointer or a null e3t_dev; a bad dtype; a bad rule; nz, ny or
+ * nx < 1; statics given with rule 0 or 1, or any of them absent with rule 2; an output that overlaps an input or the other
+ * output. */
+#define NF_E3_MIN 0
+#define NF_E3_MEAN 1
+#define NF_E3_ANOMALY 2
+int nf_face_thickness(void *e3u_out_dev, void *e3v_out_dev, const void *e3t_dev, const void *e3t0_dev, const void *e3u0_dev,
+                      const void *e3v0_dev, long nz, long ny, long nx, int dtype, int rule, int wrap_x, double fill,
+                      double missing, double fill0, double missing0, void *hip_stream);
+
 /* ------------------------------------------------------------------ synthetic data (datagen.py) */
 /* Stream functions offered on device (no eval on the GPU): psi = g(z,t) * h(x,y)
  *   0 "x"                                                    README.md:26

@@ -157,6 +157,24 @@ class _DerivedPlane(object):
         self.item, self.index = item, index
 
 
+class _DerivedThickness(object):
+    """e3u (which = 0) or e3v (1) of a time-varying derived cell thickness (nemoflux_amd.thickness.FaceThickness) as a series
+    of the time-mean walks: it lives nowhere, step t is computed straight into a device address."""
+
+    def __init__(self, field, slot, which, shape, dtype):
+        self.field, self.slot, self.which, self.shape, self.dtype = field, slot, which, shape, numpy.dtype(dtype)
+
+    def compute_step(self, tIndex, dst_ptr):
+        """step tIndex of this face thickness at the HBM address dst_ptr; the other one goes to the slot's own buffer, which
+        no longer holds the step the engine was given.  Complete at return."""
+        face = self.slot['face']
+        self.slot['step'] = -1
+        ptrs = [face['out'][0].ptr, face['out'][1].ptr]
+        ptrs[self.which] = dst_ptr
+        self.field._run_face_thickness(face, tIndex, *ptrs)
+        check(lib.nf_synchronize())
+
+
 class _Transect(object):
     """Entry of Field.plis: quacks like mint.PolylineIntegral.getIntegral (fluxplot.py:56).
 
@@ -731,6 +749,9 @@ class Field(object):
         if slot is not None and slot.get('sigma') is not None:
             if slot['step'] != tIndex:
                 self._stage_sigma(slot, tIndex)
+        elif slot is not None and slot.get('face') is not None:
+            if slot['step'] != tIndex:
+                self._stage_face_thickness(slot, tIndex)
         elif slot is not None and slot['lazy'] is not None and slot['step'] != tIndex:
             for src, buf in zip(slot['lazy'], slot['buf']):
                 src.read_step(tIndex, out=buf)
@@ -760,7 +781,7 @@ class Field(object):
                                                lib.nf_field_set_class_tracer_missing_value)
 
     # ------------------------------------------------------------------------------------------
-    def setCellThickness(self, e3u, e3v, fill_value=None, missing_value=None):
+    def setCellThickness(self, e3u, e3v=None, fill_value=None, missing_value=None):
         """Per-cell layer thicknesses (partial steps, z* / variable-volume runs) in place of the one number per level of
         deptht_bounds: e3u at the U points (the index of uo), e3v at the V points (the index of vo) -- the model's e3u / e3v,
         or thkcello on the U and V grids.  Shape (nz, ny, nx) or (1, nz, ny, nx): static; (nt, nz, ny, nx): one per time step.
@@ -774,13 +795,26 @@ class Field(object):
         computeGrossProfile, computeGrossClassTransport and computeGrossClassRemap (both forms) then integrate with these thicknesses; computeTracerProfile, computeClassTransport and computeClassTracerTransport raise while they are
         set.  timeMean and meanEddyTracerTransport carry a static thickness over to the mean state and take a time-varying one
         with thicknessWeighted=True (thickness-weighted mean velocities, mean thicknesses).  setCellThickness(None, None) goes
-        back to deptht_bounds."""
+        back to deptht_bounds.
+        setCellThickness(FaceThickness(e3t, rule, ...)) (nemoflux_amd.thickness; e3v left None): e3u and e3v derived on the GPU
+        from the thickness at T-points -- e3t of grid_T, thkcello -- a static e3t once, a time-varying one step by step into
+        two (nz, ny, nx) device buffers; the descriptor carries its own markers."""
+        from .thickness import FaceThickness
         self._e3 = None
         self._row_valid = False
+        if isinstance(e3u, FaceThickness):
+            if e3v is not None:
+                raise RuntimeError('ERROR: setCellThickness: a FaceThickness describes both e3u and e3v; leave e3v None')
+            if fill_value is not None or missing_value is not None:
+                raise RuntimeError('ERROR: a FaceThickness carries the markers of e3t and of the statics itself; give them to '
+                                   'FaceThickness(...)')
+            self._face_thickness_slot(e3u)
+            return
         if e3u is None or e3v is None:
             if e3u is not None or e3v is not None:
                 raise RuntimeError('ERROR: setCellThickness needs both e3u and e3v, or None for both')
             check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), None, None, 0, NF_F64, 0, numpy.nan))
+            self._face_keep = None
             return
         uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
         markers, arrs = [], []
@@ -850,6 +884,116 @@ class Field(object):
         check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), numpy.nan if missing_value is None
                                                             else float(missing_value)))
         self._e3 = slot
+        self._face_keep = None
+
+    def _face_thickness_slot(self, ft):
+        """The cell-thickness slot of a derived pair (nemoflux_amd.thickness.FaceThickness).  e3t stays where it is -- a device
+        array is read in place by offset, a host array or a file variable goes one time step at a time through a pinned buffer
+        into a device buffer -- the statics go to the device once, and nf_face_thickness writes two (nz, ny, nx) device buffers
+        of the dtype of uo / vo on the Field's stream.  A static e3t: computed once, here, and set as a static HBM thickness.
+        A time-varying one: _stage_slot computes step t and hands the buffers over through a virtual (nt, nz, ny, nx) base."""
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        dims = (self.nz, self.ny, self.nx)
+        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
+
+        def check_static(a, which):
+            shape = tuple(int(x) for x in a.shape)
+            if len(shape) not in (3, 4) or self.getSizes(shape) != (1,) + dims:
+                raise RuntimeError(f'ERROR: {which} has shape {shape}; need (nz, ny, nx) = {dims} or (1, nz, ny, nx)')
+            dt = numpy.dtype(_native_dtype(a))
+            if dt != uv_dtype and (_lib.device_pointer(a) is not None or dt.kind != 'f'):
+                raise RuntimeError(f'ERROR: {which} is {dt.name}, uo/vo are {uv_dtype.name}: only a static host array of '
+                                   f'another float dtype is cast')
+
+        def static_array(a):
+            """a static (nz, ny, nx) / (1, nz, ny, nx) input: on the device as it is, else read / cast and uploaded once"""
+            ptr = _lib.device_pointer(a)
+            if ptr is not None:
+                return ptr, a
+            if hasattr(a, 'read_step'):
+                a = a.read_step(0)       # a static file variable: read once
+            buf = _lib.DeviceBuffer(nbytes)
+            buf.upload(_native(numpy.asarray(a).astype(uv_dtype, copy=False)).reshape(dims))
+            return buf.ptr, buf
+
+        shape = ft.shape
+        nt_th = self.getSizes(shape)[0] if len(shape) in (3, 4) else -1
+        if len(shape) not in (3, 4) or self.getSizes(shape)[1:] != dims or nt_th not in (1, self.nt):
+            raise RuntimeError(f'ERROR: e3t has shape {shape}; need (nz, ny, nx) = {dims}, (1, nz, ny, nx) or '
+                               f'(nt, nz, ny, nx) = {(self.nt,) + dims}')
+        if nt_th == 1:
+            check_static(ft.e3t, 'e3t')
+        elif ft.dtype != uv_dtype:
+            raise RuntimeError(f'ERROR: e3t is {ft.dtype.name}, uo/vo are {uv_dtype.name}: only a static host array of '
+                               f'another float dtype is cast')
+        for a, which in zip(ft.statics, ('e3t0', 'e3u0', 'e3v0')):
+            check_static(a, which)
+        keep, statics = [ft], []
+        for a in ft.statics:
+            ptr, owner = static_array(a)
+            statics.append(ptr)
+            keep.append(owner)
+        statics += [None] * (3 - len(statics))
+        nan = numpy.nan
+        face = dict(rule=ft.code, wrap=1 if ft.wrapX else 0, statics=statics, nbytes=nbytes,
+                    marks=tuple(nan if m is None else m for m in ft.markers + ft.static_markers),
+                    out=(_lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes)))
+        if nt_th == 1:
+            ptr, owner = static_array(ft.e3t)
+            keep.append(owner)
+            face['e3t'] = dict(ptr=ptr)
+        else:
+            ptr = _lib.device_pointer(ft.e3t)
+            one = dict(ptr=ptr, src=ft.e3t)     # a borrowed buffer must outlive the handle
+            if ptr is None:
+                one['file'] = hasattr(ft.e3t, 'read_step')
+                one['host'] = None if one['file'] else _native(ft.e3t).reshape((self.nt,) + dims)
+                one['pinned'] = self._host_array(dims, uv_dtype)
+                one['dev'] = _lib.DeviceBuffer(nbytes)
+            face['e3t'] = one
+        slot = dict(lazy=None, step=-1, set=lib.nf_field_set_cell_thickness, code=self._uv_code, nt=nt_th, fill=nan, missing=nan,
+                    keep=keep, face=face)
+        if nt_th == 1:
+            self._run_face_thickness(face, 0, face['out'][0].ptr, face['out'][1].ptr)
+            check(lib.nf_synchronize())
+            slot['arrays'] = [_lib.DeviceArray(b.ptr, dims, uv_dtype, keepalive=b) for b in face['out']]
+            slot['face'] = None       # a static HBM thickness from here on
+            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), face['out'][0].ptr, face['out'][1].ptr, 1,
+                                                  self._uv_code, 1, nan))
+        else:
+            slot['lazy'] = (ft.e3t,)
+            slot['arrays'] = [_DerivedThickness(self, slot, k, (self.nt,) + dims, uv_dtype) for k in (0, 1)]
+        check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), nan))
+        self._e3 = slot
+        self._face_keep = slot       # the engine reads these buffers until another thickness is set
+
+    def _run_face_thickness(self, face, tIndex, e3u_ptr, e3v_ptr):
+        """e3t of step tIndex on the device and nf_face_thickness into the two addresses on the Field's stream; the stream is
+        drained when the staging buffer was used (it is written again by the next step)"""
+        one = face['e3t']
+        if one['ptr'] is not None:
+            src = one['ptr'] + tIndex * face['nbytes']
+        else:
+            if one['file']:
+                one['src'].read_step(tIndex, out=one['pinned'])
+            else:
+                numpy.copyto(one['pinned'], one['host'][tIndex])
+            check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, face['nbytes']))
+            src = one['dev'].ptr
+        check(lib.nf_face_thickness(e3u_ptr, e3v_ptr, src, *face['statics'], self.nz, self.ny, self.nx, self._uv_code,
+                                    face['rule'], face['wrap'], *face['marks'], self._stream))
+        if one['ptr'] is None:
+            check(lib.nf_synchronize())     # the staging buffer is written again by the next step
+
+    def _stage_face_thickness(self, slot, tIndex):
+        """step tIndex of a derived cell thickness: e3t of that step on the device, nf_face_thickness into the slot's two
+        buffers on the Field's stream, and the buffers handed over through a virtual (nt, nz, ny, nx) base"""
+        face = slot['face']
+        self._run_face_thickness(face, tIndex, face['out'][0].ptr, face['out'][1].ptr)
+        off = tIndex * face['nbytes']
+        check(slot['set'](ctypes.byref(self._h), face['out'][0].ptr - off, face['out'][1].ptr - off, self.nt, slot['code'], 1,
+                          numpy.nan))
+        slot['step'] = tIndex
 
     def _cell_thickness_lazy(self):
         e3 = getattr(self, '_e3', None)
@@ -1230,9 +1374,11 @@ class Field(object):
             cnt = torch.empty(n, dtype=torch.int32, device='cuda')
             wsum = torch.empty(n, dtype=torch.float64, device='cuda') if carry_wsum else None
             lazy = [hasattr(x, 'read_step') for x in series]
-            group = 1 if any(lazy) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
+            derived = [hasattr(x, 'compute_step') for x in series]     # a derived cell thickness: one step at a time too
+            group = 1 if any(lazy) or any(derived) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
             bufs = [self._host_array((self.nz, self.ny, self.nx), dt) if z else None for z in lazy]
-            hosts = [_native(x).reshape(self.nt, n) if st and not z else None for x, st, z in zip(series, staged, lazy)]
+            hosts = [_native(x).reshape(self.nt, n) if st and not z and not d else None
+                     for x, st, z, d in zip(series, staged, lazy, derived)]
             stage = [_lib.DeviceBuffer(min(group, len(idx)) * n * size) if st else None for st in staged]
             for j0 in range(0, len(idx), group):
                 k = min(group, len(idx) - j0)
@@ -1243,6 +1389,9 @@ class Field(object):
                         offsets.append(everywhere[j0:j0 + k])
                         continue
                     for m, t in enumerate(idx[j0:j0 + k]):      # the selected steps of this group, packed
+                        if derived[j]:      # computed straight into the staging buffer
+                            series[j].compute_step(t, stage[j].ptr + m * n * size)
+                            continue
                         if lazy[j]:
                             series[j].read_step(t, out=bufs[j])
                         check(lib.nf_memcpy_h2d(stage[j].ptr + m * n * size,
@@ -1288,9 +1437,11 @@ class Field(object):
             lazy = [hasattr(x, 'read_step') for x in series]
             # file-backed: one step at a time through a pinned buffer; host arrays: groups of steps, the staging buffers of
             # all the series together within _MEAN_STAGE_BYTES
-            group = 1 if any(lazy) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
+            derived = [hasattr(x, 'compute_step') for x in series]     # a derived cell thickness: one step at a time too
+            group = 1 if any(lazy) or any(derived) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
             bufs = [self._host_array((self.nz, self.ny, self.nx), dt) if z else None for z in lazy]
-            hosts = [_native(x).reshape(self.nt, n) if st and not z else None for x, st, z in zip(series, staged, lazy)]
+            hosts = [_native(x).reshape(self.nt, n) if st and not z and not d else None
+                     for x, st, z, d in zip(series, staged, lazy, derived)]
             stage = [_lib.DeviceBuffer(min(group, t1 - t0) * n * size) if st else None for st in staged]
             for t in range(t0, t1, group):
                 k = min(group, t1 - t)
@@ -1298,6 +1449,10 @@ class Field(object):
                 for j in range(len(series)):
                     if not staged[j]:
                         cur.append(ptrs[j] + t * n * size)
+                        continue
+                    if derived[j]:      # computed straight into the staging buffer
+                        series[j].compute_step(t, stage[j].ptr)
+                        cur.append(stage[j].ptr)
                         continue
                     if lazy[j]:
                         series[j].read_step(t, out=bufs[j])

@@ -43,6 +43,8 @@ only with --show): the table is always printed or written as CSV, which is what 
                                   per time step, transect and class; --sigma thetao,so in place of --tracer works too)
     ... --cell-thickness [--e3u NAME] [--e3v NAME] [--e3-file-u FILE] [--e3-file-v FILE]
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
+    ... --cell-thickness --e3t thkcello [--e3t-file FILE] [--e3-rule min|mean|anomaly] [--e3-static MESH[:E3T0,E3U0,E3V0]]
+                                  (the same from the thickness at T points alone: e3u, e3v derived on the GPU step by step)
 """
 import argparse
 import glob
@@ -808,6 +810,38 @@ def checkCellThicknessArgs(cellThickness=False, e3u='', e3v='', e3FileU='', e3Fi
                            'does not take per-cell thicknesses yet (--levels alone, or --tracer alone, does)')
 
 
+def cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u='', e3v='', e3FileU='', e3FileV='', e3t='', e3tFile='',
+                        e3Rule='', e3Static=''):
+    """what --cell-thickness hands to Field.setCellThickness, as a tuple of its arguments, or None without the option: the
+    (path, name) pairs of --e3u / --e3v, or with --e3t the one FaceThickness that derives both on the GPU from the thickness
+    at T points (--e3t-file, --e3-rule, --e3-static FILE[:E3T0,E3U0,E3V0]); refused combinations raise RuntimeError"""
+    if not e3t:
+        if e3tFile or e3Rule or e3Static:
+            raise RuntimeError('ERROR: --e3t-file / --e3-rule / --e3-static need --e3t NAME (and --cell-thickness)')
+        return ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    if not cellThickness:
+        raise RuntimeError('ERROR: --e3t needs --cell-thickness')
+    if e3u or e3v or e3FileU or e3FileV:
+        raise RuntimeError('ERROR: --e3t cannot be combined with --e3u / --e3v / --e3-file-u / --e3-file-v: the thicknesses at '
+                           'the U and V points are either read or derived from --e3t')
+    rule = e3Rule or 'min'
+    if rule not in ('min', 'mean', 'anomaly'):
+        raise RuntimeError(f'ERROR: --e3-rule must be min, mean or anomaly, got {e3Rule!r}')
+    if (rule == 'anomaly') != bool(e3Static):
+        raise RuntimeError('ERROR: --e3-rule anomaly and --e3-static FILE[:E3T0,E3U0,E3V0] go together')
+    statics = {}
+    if e3Static:
+        path, sep, tail = e3Static.rpartition(':')
+        names = tail.split(',') if sep and tail.count(',') == 2 and all(tail.split(',')) else None
+        if names is None:
+            if sep and ',' in tail:
+                raise RuntimeError(f'ERROR: --e3-static must be FILE or FILE:E3T0,E3U0,E3V0 (three names), got {e3Static!r}')
+            path, names = e3Static, ['e3t_0', 'e3u_0', 'e3v_0']
+        statics = dict(e3t0=(path, names[0]), e3u0=(path, names[1]), e3v0=(path, names[2]))
+    from .thickness import FaceThickness
+    return (FaceThickness((e3tFile or tFile, e3t), rule, **statics),)
+
+
 def _emit(text, output):
     if output:
         with open(output, 'w') as f:
@@ -848,7 +882,8 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          carryRef=0.0, carryScale=1.0, cellThickness=False, e3u='', e3v='', e3FileU='', e3FileV='', decompose=False,
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
          classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect='', depthSurfaces='',
-         surfaceFile='', isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer='', grossRemap=''):
+         surfaceFile='', isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer='', grossRemap='',
+         e3t='', e3tFile='', e3Rule='', e3Static=''):
     sig = None
     checkGrossRemapArgs(grossRemap, grossClasses, classes)
     checkTimeMeanArgs(timeWeights, timeSelect, eddy)
@@ -870,7 +905,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
         unit = 'Sv' if sverdrup else 'A m^2/s'
-        ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
         if iso:
             surfaces = iso['labels']
             totals, fld = isoSurfaceSeries(tFile, uFile, vFile, lonLatZPoints, iso, surfaceFile, float(depthTop), tracer,
@@ -903,7 +938,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
         unit = 'Sv' if sverdrup else 'A m^2/s'
-        ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
         edges = parseClasses(depthBins)
         totals, fld = depthSeries(tFile, uFile, vFile, lonLatZPoints, edges, float(depthTop), tracer, tracerFile,
                                   float(tracerRef), sverdrup, ct)
@@ -930,7 +965,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
                                          '--tracer-scale': float(tracerScale) != 1.0, '--remap': remap})
         checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
-        ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
         planes, _, _ = crossingsSeries(tFile, uFile, vFile, lonLatZPoints, crossings, tracer, tracerFile, float(tracerRef),
                                        parseZRange(zrange) if zrange else None, sverdrup, ct, parseSigma(sigma) if sigma else None)
         print(f'crossings: planes of shape {planes.shape} written to {crossings}')
@@ -965,7 +1000,7 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
-    ct = ((e3FileU or uFile, e3u or 'e3u'), (e3FileV or vFile, e3v or 'e3v')) if cellThickness else None
+    ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
     if classArea:
         edges = parseClasses(classArea)
         totals, fld = classAreaSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
@@ -1261,4 +1296,14 @@ if __name__ == '__main__':
     ap.add_argument('--e3v', default='', metavar='NAME', help='with --cell-thickness: the thickness at V points (default e3v)')
     ap.add_argument('--e3-file-u', dest='e3FileU', default='', metavar='FILE', help='read --e3u from FILE instead of the U file')
     ap.add_argument('--e3-file-v', dest='e3FileV', default='', metavar='FILE', help='read --e3v from FILE instead of the V file')
+    ap.add_argument('--e3t', default='', metavar='NAME',
+                    help='with --cell-thickness: derive the thicknesses at the U and V points on the GPU from the thickness NAME at '
+                         'T points (e3t, thkcello) of the T file, instead of reading --e3u / --e3v')
+    ap.add_argument('--e3t-file', dest='e3tFile', default='', metavar='FILE', help='read --e3t from FILE instead of the T file')
+    ap.add_argument('--e3-rule', dest='e3Rule', default='', metavar='min|mean|anomaly',
+                    help='with --e3t: the face takes the thinner of its two cells (min, the default: partial steps), their mean, '
+                         'or the static face thickness plus the mean anomaly of the two cells (anomaly: z*; needs --e3-static)')
+    ap.add_argument('--e3-static', dest='e3Static', default='', metavar='FILE[:E3T0,E3U0,E3V0]',
+                    help='with --e3-rule anomaly: the mesh file that holds the static thicknesses at the T, U and V points '
+                         '(default names e3t_0,e3u_0,e3v_0)')
     main(**vars(ap.parse_args()))
