@@ -920,6 +920,44 @@ int nf_face_thickness(void *e3u_out_dev, void *e3v_out_dev, const void *e3t_dev,
                       const void *e3v0_dev, long nz, long ny, long nx, int dtype, int rule, int wrap_x, double fill,
                       double missing, double fill0, double missing0, void *hip_stream);
 
+/* z* layer thicknesses at the U and V faces from the sea surface height (nf_sshthick.hip): the e3u / e3v of
+ * nf_field_set_cell_thickness for ln_vvl_zstar / key_qco / key_linssh output, which holds the 2-D ssh / zos and a static
+ * mesh_mask and no 3-D thickness: e3u(t) = e3u_0 * (1 + ssh_u(t) / hu_0).  Both calls are value-level like nf_face_thickness:
+ * no nf_field involved, asynchronous on hip_stream.  All arrays are in HBM, x fastest: ssh_dev one (ny, nx) plane of dtype, one
+ * time step of the sea surface height at T-points; e3u0_dev / e3v0_dev the static thicknesses at the U and V points (e3u_0,
+ * e3v_0 of a mesh_mask), (nz, ny, nx) of dtype, as are the outputs, e3u_out_dev on the index of uo (the east face of cell
+ * (j, i)) and e3v_out_dev on the index of vo (its north face); hu0_dev / hv0_dev the column depths at the U and V points,
+ * (ny, nx) float64 -- a mesh file's hu_0 / hv_0 or nf_column_depth of the two statics; area_t_dev, area_u_dev, area_v_dev the
+ * cell areas e1e2t, e1e2u, e1e2v, (ny, nx) float64, all three or all NULL.
+ * Definition.  Everything is float64.  Every operation is rounded on its own, with no fused multiply-adds.  Inputs are widened
+ * first.  Each result is rounded once to dtype.
+ *   Presence.  present(x): x is not NaN and equals neither of its array's two markers, each cast to dtype and compared in
+ *     dtype.  fill / missing apply to ssh; fill0 / missing0 apply to the two statics.  NaN means "no marker".
+ *   Column depth (nf_column_depth).  H = +0.0.  For k = 0 ... nz-1 in that order, H = H + (double)F0[k,j,i] where F0[k,j,i] is
+ *     present.  Values are added as they come, including negative or non-finite ones.
+ *   Neighbours.  Those of nf_face_thickness.  East (U) face of (j, i): Sa = ssh[j,i], Sb = ssh[j,i+1].  At i = nx-1,
+ *     Sb = ssh[j,0] when wrap_x is on, else no neighbour.  North (V) face: Sb = ssh[j+1,i].  At j = ny-1 there is no neighbour.
+ *   No neighbour by geometry.  Then Sb := Sa, and with areas the neighbour's area becomes the cell's own.
+ *   Face height s, without areas.  0.5 * (Sa + Sb) when both are present, else +0.0.
+ *   Face height s, with areas (NEMO's ssh_u = 1/2 (e1e2t_i ssh_i + e1e2t_i+1 ssh_i+1) / e1e2u).  p = Ta * Sa and q = Tb * Sb,
+ *     where Ta, Tb are area_t at the two cells.  s = (0.5 * (p + q)) / F, where F is area_u[j,i] or area_v[j,i].  s = +0.0
+ *     when Sa or Sb is missing, when any of Ta, Tb, F is NaN, or when F is not > 0.
+ *   Factor.  H is hu0[j,i] for the east face and hv0[j,i] for the north face.  r = s / H when H > 0, else +0.0; a NaN H also
+ *     gives +0.0.  Then f = 1.0 + r.
+ *   Result per level.  F0 is e3u0[k,j,i] for the east face and e3v0[k,j,i] for the north face.  +0.0 where F0 is not present,
+ *     else (dtype)((double)F0 * f).  Non-finite or negative results are stored as they come.
+ * The result does not depend on the launch shape; there are no atomics.  nf_ssh_thickness moves 4 * n * sizeof(dtype) bytes
+ * (n = nz * ny * nx) plus the planes.
+ * NF_ERR_ARG, decided before a device is needed: a null output, ssh_dev, static or column-depth pointer; one or two of the
+ * three area pointers given; a bad dtype; nz, ny or nx < 1; nz * ny * nx overflowing; an output that overlaps any input or the
+ * other output. */
+int nf_column_depth(double *h_out_dev, const void *e3_0_dev, long nz, long ny, long nx, int dtype, double fill0,
+                    double missing0, void *hip_stream);
+int nf_ssh_thickness(void *e3u_out_dev, void *e3v_out_dev, const void *ssh_dev, const void *e3u0_dev, const void *e3v0_dev,
+                     const double *hu0_dev, const double *hv0_dev, const double *area_t_dev, const double *area_u_dev,
+                     const double *area_v_dev, long nz, long ny, long nx, int dtype, int wrap_x, double fill, double missing,
+                     double fill0, double missing0, void *hip_stream);
+
 /* ------------------------------------------------------------------ synthetic data (datagen.py) */
 /* Stream functions offered on device (no eval on the GPU): psi = g(z,t) * h(x,y)
  *   0 "x"                                                    README.md:26

@@ -215,6 +215,10 @@ _sig('nf_iso_depth', [ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_voi
 NF_E3_MIN, NF_E3_MEAN, NF_E3_ANOMALY = 0, 1, 2
 _sig('nf_face_thickness', [ctypes.c_void_p] * 6 + [ctypes.c_long] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 +   # HBM addresses
      [ctypes.c_void_p])
+_sig('nf_column_depth', [ctypes.c_void_p] * 2 + [ctypes.c_long] * 3 + [ctypes.c_int] + [ctypes.c_double] * 2 +   # HBM addresses
+     [ctypes.c_void_p])
+_sig('nf_ssh_thickness', [ctypes.c_void_p] * 10 + [ctypes.c_long] * 3 + [ctypes.c_int] * 2 + [ctypes.c_double] * 4 +   # HBM addresses
+     [ctypes.c_void_p])
 _sig('nf_datagen_bounds',[ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long] + [ctypes.c_double] * 6 +
      [ctypes.c_int, ctypes.c_void_p])
 _sig('nf_datagen_uv', [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_long] * 6 + [ctypes.c_double] * 6 +

@@ -798,10 +798,21 @@ class Field(object):
         back to deptht_bounds.
         setCellThickness(FaceThickness(e3t, rule, ...)) (nemoflux_amd.thickness; e3v left None): e3u and e3v derived on the GPU
         from the thickness at T-points -- e3t of grid_T, thkcello -- a static e3t once, a time-varying one step by step into
-        two (nz, ny, nx) device buffers; the descriptor carries its own markers."""
-        from .thickness import FaceThickness
+        two (nz, ny, nx) device buffers; the descriptor carries its own markers.
+        setCellThickness(SshThickness(ssh, e3u0, e3v0, ...)) (the same module; e3v left None): the z* thicknesses
+        e3u0 * (1 + ssh_u / hu0) derived on the GPU from the 2-D sea surface height and the static mesh_mask thicknesses -- one
+        (ny, nx) plane per time step in place of a volume -- handled like a FaceThickness from there on."""
+        from .thickness import FaceThickness, SshThickness
         self._e3 = None
         self._row_valid = False
+        if isinstance(e3u, SshThickness):
+            if e3v is not None:
+                raise RuntimeError('ERROR: setCellThickness: an SshThickness describes both e3u and e3v; leave e3v None')
+            if fill_value is not None or missing_value is not None:
+                raise RuntimeError('ERROR: an SshThickness carries the markers of ssh and of the statics itself; give them to '
+                                   'SshThickness(...)')
+            self._ssh_thickness_slot(e3u)
+            return
         if isinstance(e3u, FaceThickness):
             if e3v is not None:
                 raise RuntimeError('ERROR: setCellThickness: a FaceThickness describes both e3u and e3v; leave e3v None')
@@ -886,6 +897,59 @@ class Field(object):
         self._e3 = slot
         self._face_keep = None
 
+    def _derived_static(self, a, dims, dtype):
+        """a static input of a derived cell thickness, shaped dims once a leading 1 is dropped: (its device address, what keeps
+        it alive) -- on the device as it is, else read / cast to dtype and uploaded once"""
+        ptr = _lib.device_pointer(a)
+        if ptr is not None:
+            return ptr, a
+        if hasattr(a, 'read_step'):
+            a = a.read_step(0)       # a static file variable: read once (a packed one of fewer than 4 dimensions decodes whole)
+        buf = _lib.DeviceBuffer(int(numpy.prod(dims)) * numpy.dtype(dtype).itemsize)
+        buf.upload(_native(numpy.asarray(a).astype(dtype, copy=False)).reshape(dims))
+        return buf.ptr, buf
+
+    def _derived_source(self, src, nt_th, dims, keep):
+        """where the per-step input of a derived cell thickness (e3t of a FaceThickness, ssh of an SshThickness), a step of which
+        is shaped dims, lives: a static one on the device; a time-varying device array in place; a time-varying host array or
+        file variable with a pinned buffer and a device buffer that _derived_step fills one time step at a time"""
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        nbytes = int(numpy.prod(dims)) * uv_dtype.itemsize
+        if nt_th == 1:
+            ptr, owner = self._derived_static(src, dims, uv_dtype)
+            keep.append(owner)
+            return dict(ptr=ptr, nbytes=nbytes)
+        ptr = _lib.device_pointer(src)
+        one = dict(ptr=ptr, src=src, nbytes=nbytes)     # a borrowed buffer must outlive the handle
+        if ptr is None:
+            one['file'] = hasattr(src, 'read_step')
+            one['host'] = None if one['file'] else _native(src).reshape((self.nt,) + tuple(dims))
+            one['pinned'] = self._host_array(dims, uv_dtype)
+            one['dev'] = _lib.DeviceBuffer(nbytes)
+        return one
+
+    def _derived_step(self, one, tIndex):
+        """the device address of step tIndex of a _derived_source"""
+        if one['ptr'] is not None:
+            return one['ptr'] + tIndex * one['nbytes']
+        if one['file']:
+            one['src'].read_step(tIndex, out=one['pinned'])
+        else:
+            numpy.copyto(one['pinned'], one['host'][tIndex])
+        check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, one['nbytes']))
+        return one['dev'].ptr
+
+    def _check_derived_static(self, a, which, dims):
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        names = ('(nz, ny, nx)', '(1, nz, ny, nx)') if len(dims) == 3 else ('(ny, nx)', '(1, ny, nx)')
+        shape = tuple(int(x) for x in a.shape)
+        if shape not in (tuple(dims), (1,) + tuple(dims)):
+            raise RuntimeError(f'ERROR: {which} has shape {shape}; need {names[0]} = {tuple(dims)} or {names[1]}')
+        dt = numpy.dtype(_native_dtype(a))
+        if dt != uv_dtype and (_lib.device_pointer(a) is not None or dt.kind != 'f'):
+            raise RuntimeError(f'ERROR: {which} is {dt.name}, uo/vo are {uv_dtype.name}: only a static host array of '
+                               f'another float dtype is cast')
+
     def _face_thickness_slot(self, ft):
         """The cell-thickness slot of a derived pair (nemoflux_amd.thickness.FaceThickness).  e3t stays where it is -- a device
         array is read in place by offset, a host array or a file variable goes one time step at a time through a pinned buffer
@@ -894,63 +958,113 @@ class Field(object):
         A time-varying one: _stage_slot computes step t and hands the buffers over through a virtual (nt, nz, ny, nx) base."""
         uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
         dims = (self.nz, self.ny, self.nx)
-        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
-
-        def check_static(a, which):
-            shape = tuple(int(x) for x in a.shape)
-            if len(shape) not in (3, 4) or self.getSizes(shape) != (1,) + dims:
-                raise RuntimeError(f'ERROR: {which} has shape {shape}; need (nz, ny, nx) = {dims} or (1, nz, ny, nx)')
-            dt = numpy.dtype(_native_dtype(a))
-            if dt != uv_dtype and (_lib.device_pointer(a) is not None or dt.kind != 'f'):
-                raise RuntimeError(f'ERROR: {which} is {dt.name}, uo/vo are {uv_dtype.name}: only a static host array of '
-                                   f'another float dtype is cast')
-
-        def static_array(a):
-            """a static (nz, ny, nx) / (1, nz, ny, nx) input: on the device as it is, else read / cast and uploaded once"""
-            ptr = _lib.device_pointer(a)
-            if ptr is not None:
-                return ptr, a
-            if hasattr(a, 'read_step'):
-                a = a.read_step(0)       # a static file variable: read once
-            buf = _lib.DeviceBuffer(nbytes)
-            buf.upload(_native(numpy.asarray(a).astype(uv_dtype, copy=False)).reshape(dims))
-            return buf.ptr, buf
-
         shape = ft.shape
         nt_th = self.getSizes(shape)[0] if len(shape) in (3, 4) else -1
         if len(shape) not in (3, 4) or self.getSizes(shape)[1:] != dims or nt_th not in (1, self.nt):
             raise RuntimeError(f'ERROR: e3t has shape {shape}; need (nz, ny, nx) = {dims}, (1, nz, ny, nx) or '
                                f'(nt, nz, ny, nx) = {(self.nt,) + dims}')
         if nt_th == 1:
-            check_static(ft.e3t, 'e3t')
+            self._check_derived_static(ft.e3t, 'e3t', dims)
         elif ft.dtype != uv_dtype:
             raise RuntimeError(f'ERROR: e3t is {ft.dtype.name}, uo/vo are {uv_dtype.name}: only a static host array of '
                                f'another float dtype is cast')
         for a, which in zip(ft.statics, ('e3t0', 'e3u0', 'e3v0')):
-            check_static(a, which)
+            self._check_derived_static(a, which, dims)
         keep, statics = [ft], []
         for a in ft.statics:
-            ptr, owner = static_array(a)
+            ptr, owner = self._derived_static(a, dims, uv_dtype)
             statics.append(ptr)
             keep.append(owner)
         statics += [None] * (3 - len(statics))
         nan = numpy.nan
-        face = dict(rule=ft.code, wrap=1 if ft.wrapX else 0, statics=statics, nbytes=nbytes,
-                    marks=tuple(nan if m is None else m for m in ft.markers + ft.static_markers),
-                    out=(_lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes)))
+        marks = tuple(nan if m is None else m for m in ft.markers + ft.static_markers)
+        rule, wrap = ft.code, 1 if ft.wrapX else 0
+
+        def run(e3u_ptr, e3v_ptr, src):
+            check(lib.nf_face_thickness(e3u_ptr, e3v_ptr, src, *statics, self.nz, self.ny, self.nx, self._uv_code, rule, wrap,
+                                        *marks, self._stream))
+
+        self._derived_slot(run, ft.e3t, nt_th, dims, keep)
+
+    def _ssh_thickness_slot(self, st):
+        """The cell-thickness slot of a z* pair derived from the sea surface height (nemoflux_amd.thickness.SshThickness).  The
+        static face thicknesses (given, or derived once from e3t0 by nf_face_thickness with NF_E3_MIN), the column depths
+        (given, or nf_column_depth of the face statics over all levels, whatever levels this rank owns) and the areas go to the
+        device once; ssh stays where it is -- a (ny, nx) plane in HBM is read in place by offset, a host plane (a file's ssh
+        is a host array by now: the descriptor read it whole) goes through a pinned buffer -- and nf_ssh_thickness writes the slot's two (nz, ny, nx) device buffers on the Field's
+        stream, as nf_face_thickness does for a FaceThickness: the rest is _derived_slot."""
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        dims, cells = (self.nz, self.ny, self.nx), (self.ny, self.nx)
+        shape = st.shape
+        nt_th = 1 if len(shape) == 2 else (shape[0] if len(shape) == 3 else -1)
+        if shape[-2:] != cells or nt_th not in (1, self.nt):
+            raise RuntimeError(f'ERROR: ssh has shape {shape}; need (ny, nx) = {cells}, (1, ny, nx) or (nt, ny, nx) = '
+                               f'{(self.nt,) + cells}')
         if nt_th == 1:
-            ptr, owner = static_array(ft.e3t)
+            self._check_derived_static(st.ssh, 'ssh', cells)
+        elif st.dtype != uv_dtype:
+            raise RuntimeError(f'ERROR: ssh is {st.dtype.name}, uo/vo are {uv_dtype.name}: only a static host array of '
+                               f'another float dtype is cast')
+        for a, which in zip(st.statics, ('e3t0',) if st.from_e3t0 else ('e3u0', 'e3v0')):
+            self._check_derived_static(a, which, dims)
+        planes = [(a, w) for a, w in zip(st.depths or (), ('hu0', 'hv0'))]
+        planes += [(a, f'areas[{k}]') for k, a in enumerate(st.areas or ())]
+        for a, which in planes:
+            shp, dt = tuple(int(x) for x in a.shape), numpy.dtype(_native_dtype(a))
+            if shp not in (cells, (1,) + cells):
+                raise RuntimeError(f'ERROR: {which} has shape {shp}; need (ny, nx) = {cells} or (1, ny, nx)')
+            if dt != numpy.float64 and (_lib.device_pointer(a) is not None or dt.kind != 'f'):
+                raise RuntimeError(f'ERROR: {which} is {dt.name}: a device array must be float64, a host array a float array')
+        nan = numpy.nan
+        keep, statics = [st], []
+        smarks = tuple(nan if m is None else m for m in st.static_markers)
+        for a in st.statics:
+            ptr, owner = self._derived_static(a, dims, uv_dtype)
+            statics.append(ptr)
             keep.append(owner)
-            face['e3t'] = dict(ptr=ptr)
-        else:
-            ptr = _lib.device_pointer(ft.e3t)
-            one = dict(ptr=ptr, src=ft.e3t)     # a borrowed buffer must outlive the handle
-            if ptr is None:
-                one['file'] = hasattr(ft.e3t, 'read_step')
-                one['host'] = None if one['file'] else _native(ft.e3t).reshape((self.nt,) + dims)
-                one['pinned'] = self._host_array(dims, uv_dtype)
-                one['dev'] = _lib.DeviceBuffer(nbytes)
-            face['e3t'] = one
+        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
+        if st.from_e3t0:
+            # NEMO's partial-step rule for e3u_0 / e3v_0: the thinner of the two cells, 0 beside a cell without a thickness
+            pair = (_lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes))
+            check(lib.nf_face_thickness(pair[0].ptr, pair[1].ptr, statics[0], None, None, None, self.nz, self.ny, self.nx,
+                                        self._uv_code, _lib.NF_E3_MIN, 1 if st.wrapX else 0, *smarks, nan, nan, self._stream))
+            keep += list(pair)
+            statics, smarks = [pair[0].ptr, pair[1].ptr], (nan, nan)
+        depths = []
+        for k in (0, 1):
+            if st.depths is not None:
+                ptr, owner = self._derived_static(st.depths[k], cells, numpy.float64)
+            else:
+                owner = _lib.DeviceBuffer(self.ny * self.nx * 8)
+                ptr = owner.ptr
+                check(lib.nf_column_depth(ptr, statics[k], self.nz, self.ny, self.nx, self._uv_code, *smarks, self._stream))
+            depths.append(ptr)
+            keep.append(owner)
+        areas = [None, None, None]
+        if st.areas is not None:
+            for k, a in enumerate(st.areas):
+                areas[k], owner = self._derived_static(a, cells, numpy.float64)
+                keep.append(owner)
+        marks = tuple(nan if m is None else m for m in st.markers) + smarks
+        wrap = 1 if st.wrapX else 0
+
+        def run(e3u_ptr, e3v_ptr, src):
+            check(lib.nf_ssh_thickness(e3u_ptr, e3v_ptr, src, *statics, *depths, *areas, self.nz, self.ny, self.nx,
+                                       self._uv_code, wrap, *marks, self._stream))
+
+        self._derived_slot(run, st.ssh, nt_th, cells, keep)
+
+    def _derived_slot(self, run, src, nt_th, step_dims, keep):
+        """the common part of the derived cell-thickness slots: run(e3u_ptr, e3v_ptr, src_ptr) writes the pair of one step of
+        src, a step of which is shaped step_dims, on the Field's stream.  A static src: computed once, here, and set as a
+        static HBM thickness.  A time-varying one: _stage_slot computes step t into the slot's two (nz, ny, nx) device buffers
+        and hands them over through a virtual (nt, nz, ny, nx) base."""
+        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        dims = (self.nz, self.ny, self.nx)
+        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
+        nan = numpy.nan
+        face = dict(run=run, nbytes=nbytes, out=(_lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes)),
+                    src=self._derived_source(src, nt_th, step_dims, keep))
         slot = dict(lazy=None, step=-1, set=lib.nf_field_set_cell_thickness, code=self._uv_code, nt=nt_th, fill=nan, missing=nan,
                     keep=keep, face=face)
         if nt_th == 1:
@@ -961,32 +1075,23 @@ class Field(object):
             check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), face['out'][0].ptr, face['out'][1].ptr, 1,
                                                   self._uv_code, 1, nan))
         else:
-            slot['lazy'] = (ft.e3t,)
+            slot['lazy'] = (src,)
             slot['arrays'] = [_DerivedThickness(self, slot, k, (self.nt,) + dims, uv_dtype) for k in (0, 1)]
         check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), nan))
         self._e3 = slot
         self._face_keep = slot       # the engine reads these buffers until another thickness is set
 
     def _run_face_thickness(self, face, tIndex, e3u_ptr, e3v_ptr):
-        """e3t of step tIndex on the device and nf_face_thickness into the two addresses on the Field's stream; the stream is
-        drained when the staging buffer was used (it is written again by the next step)"""
-        one = face['e3t']
-        if one['ptr'] is not None:
-            src = one['ptr'] + tIndex * face['nbytes']
-        else:
-            if one['file']:
-                one['src'].read_step(tIndex, out=one['pinned'])
-            else:
-                numpy.copyto(one['pinned'], one['host'][tIndex])
-            check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, face['nbytes']))
-            src = one['dev'].ptr
-        check(lib.nf_face_thickness(e3u_ptr, e3v_ptr, src, *face['statics'], self.nz, self.ny, self.nx, self._uv_code,
-                                    face['rule'], face['wrap'], *face['marks'], self._stream))
+        """the input of step tIndex on the device and the slot's kernel (nf_face_thickness or nf_ssh_thickness) into the two
+        addresses on the Field's stream; the stream is drained when the staging buffer was used (it is written again by the
+        next step)"""
+        one = face['src']
+        face['run'](e3u_ptr, e3v_ptr, self._derived_step(one, tIndex))
         if one['ptr'] is None:
             check(lib.nf_synchronize())     # the staging buffer is written again by the next step
 
     def _stage_face_thickness(self, slot, tIndex):
-        """step tIndex of a derived cell thickness: e3t of that step on the device, nf_face_thickness into the slot's two
+        """step tIndex of a derived cell thickness: its input of that step on the device, the slot's kernel into the slot's two
         buffers on the Field's stream, and the buffers handed over through a virtual (nt, nz, ny, nx) base"""
         face = slot['face']
         self._run_face_thickness(face, tIndex, face['out'][0].ptr, face['out'][1].ptr)

@@ -45,6 +45,8 @@ only with --show): the table is always printed or written as CSV, which is what 
                                   (partial steps / z*: the layer thicknesses e3u, e3v of the U and V files instead of deptht_bounds)
     ... --cell-thickness --e3t thkcello [--e3t-file FILE] [--e3-rule min|mean|anomaly] [--e3-static MESH[:E3T0,E3U0,E3V0]]
                                   (the same from the thickness at T points alone: e3u, e3v derived on the GPU step by step)
+    ... --cell-thickness --ssh zos [--ssh-file FILE] --e3-static MESH[:E3U0,E3V0] [--e3-areas E1E2T,E1E2U,E1E2V]
+                                  (z* output without a 3-D thickness: e3u, e3v from the sea surface height and the mesh file)
 """
 import argparse
 import glob
@@ -810,11 +812,51 @@ def checkCellThicknessArgs(cellThickness=False, e3u='', e3v='', e3FileU='', e3Fi
                            'does not take per-cell thicknesses yet (--levels alone, or --tracer alone, does)')
 
 
+def checkSshArgs(cellThickness, ssh='', sshFile='', e3Areas='', e3Static='', e3t='', e3tFile='', e3u='', e3v='', e3FileU='',
+                 e3FileV='', e3Rule=''):
+    """the --ssh options of the command line: None without --ssh, else (the mesh file, the names of the two static thicknesses,
+    the names of the three areas or None); refused combinations raise RuntimeError"""
+    if not ssh:
+        if sshFile or e3Areas:
+            raise RuntimeError('ERROR: --ssh-file / --e3-areas need --ssh NAME (and --cell-thickness)')
+        return None
+    if e3t or e3tFile or e3u or e3v or e3FileU or e3FileV or e3Rule:
+        raise RuntimeError('ERROR: --ssh cannot be combined with --e3t / --e3u / --e3v / --e3-rule: the thicknesses at the '
+                           'U and V points are either read, derived from --e3t or derived from --ssh')
+    if not cellThickness:
+        raise RuntimeError('ERROR: --ssh needs --cell-thickness')
+    if not e3Static:
+        raise RuntimeError('ERROR: --ssh needs --e3-static MESH[:E3U0,E3V0], the mesh file that holds the static thicknesses '
+                           'at the U and V points')
+    path, sep, tail = e3Static.rpartition(':')
+    # a tail without a path separator is a list of names (one name is an error, not a file called MESH:NAME)
+    if sep and path and '/' not in tail and '\\' not in tail:
+        names = tail.split(',')
+        if len(names) != 2 or not all(names):
+            raise RuntimeError(f'ERROR: with --ssh, --e3-static must be MESH or MESH:E3U0,E3V0 (two names), got {e3Static!r}')
+    else:
+        path, names = e3Static, ['e3u_0', 'e3v_0']
+    anames = None
+    if e3Areas:
+        anames = e3Areas.split(',')
+        if len(anames) != 3 or not all(anames):
+            raise RuntimeError(f'ERROR: --e3-areas must be E1E2T,E1E2U,E1E2V (three names of the mesh file), got {e3Areas!r}')
+    return path, names, anames
+
+
 def cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u='', e3v='', e3FileU='', e3FileV='', e3t='', e3tFile='',
-                        e3Rule='', e3Static=''):
+                        e3Rule='', e3Static='', ssh='', sshFile='', e3Areas=''):
     """what --cell-thickness hands to Field.setCellThickness, as a tuple of its arguments, or None without the option: the
     (path, name) pairs of --e3u / --e3v, or with --e3t the one FaceThickness that derives both on the GPU from the thickness
-    at T points (--e3t-file, --e3-rule, --e3-static FILE[:E3T0,E3U0,E3V0]); refused combinations raise RuntimeError"""
+    at T points (--e3t-file, --e3-rule, --e3-static FILE[:E3T0,E3U0,E3V0]), or with --ssh the one SshThickness that derives
+    both from the sea surface height and the static thicknesses of a mesh file (--ssh-file, --e3-static MESH[:E3U0,E3V0],
+    --e3-areas E1E2T,E1E2U,E1E2V); refused combinations raise RuntimeError"""
+    sshArgs = checkSshArgs(cellThickness, ssh, sshFile, e3Areas, e3Static, e3t, e3tFile, e3u, e3v, e3FileU, e3FileV, e3Rule)
+    if sshArgs:
+        path, names, anames = sshArgs
+        areas = tuple((path, n) for n in anames) if anames else None
+        from .thickness import SshThickness
+        return (SshThickness((sshFile or tFile, ssh), e3u0=(path, names[0]), e3v0=(path, names[1]), areas=areas),)
     if not e3t:
         if e3tFile or e3Rule or e3Static:
             raise RuntimeError('ERROR: --e3t-file / --e3-rule / --e3-static need --e3t NAME (and --cell-thickness)')
@@ -883,8 +925,9 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
          eddy=False, tracer2='', tracer2File='', classes2='', gross=False, thicknessWeighted=False, grossClasses='', sigma='',
          classArea='', crossings='', remap='', depthBins='', depthTop=0.0, timeWeights='', timeSelect='', depthSurfaces='',
          surfaceFile='', isoDepth='', isoOf='', isoSense='', isoRelative='', isoE3t='', mixedLayer='', grossRemap='',
-         e3t='', e3tFile='', e3Rule='', e3Static=''):
+         e3t='', e3tFile='', e3Rule='', e3Static='', ssh='', sshFile='', e3Areas=''):
     sig = None
+    checkSshArgs(cellThickness, ssh, sshFile, e3Areas, e3Static, e3t, e3tFile, e3u, e3v, e3FileU, e3FileV, e3Rule)
     checkGrossRemapArgs(grossRemap, grossClasses, classes)
     checkTimeMeanArgs(timeWeights, timeSelect, eddy)
     iso = checkIsoDepthArgs(isoDepth, isoOf, isoSense, isoRelative, isoE3t, mixedLayer, sigma, depthSurfaces, depthTop,
@@ -905,7 +948,8 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
         unit = 'Sv' if sverdrup else 'A m^2/s'
-        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
+        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static,
+                             ssh, sshFile, e3Areas)
         if iso:
             surfaces = iso['labels']
             totals, fld = isoSurfaceSeries(tFile, uFile, vFile, lonLatZPoints, iso, surfaceFile, float(depthTop), tracer,
@@ -938,7 +982,8 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
         checkTracerArgs(tracer, tracerFile, tracerRef, tracerScale, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
         unit = 'Sv' if sverdrup else 'A m^2/s'
-        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
+        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static,
+                             ssh, sshFile, e3Areas)
         edges = parseClasses(depthBins)
         totals, fld = depthSeries(tFile, uFile, vFile, lonLatZPoints, edges, float(depthTop), tracer, tracerFile,
                                   float(tracerRef), sverdrup, ct)
@@ -965,7 +1010,8 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
                                          '--tracer-scale': float(tracerScale) != 1.0, '--remap': remap})
         checkCellThicknessArgs(cellThickness, e3u, e3v, e3FileU, e3FileV, '', '', False, '')
         lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
-        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
+        ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static,
+                             ssh, sshFile, e3Areas)
         planes, _, _ = crossingsSeries(tFile, uFile, vFile, lonLatZPoints, crossings, tracer, tracerFile, float(tracerRef),
                                        parseZRange(zrange) if zrange else None, sverdrup, ct, parseSigma(sigma) if sigma else None)
         print(f'crossings: planes of shape {planes.shape} written to {crossings}')
@@ -1000,7 +1046,8 @@ def main(*, tFile, uFile, vFile, lonLatPoints='', iFiles='', sverdrup=False, out
     lonLatZPoints, names = readTargets(lonLatPoints, iFiles)
     print(f'target points:\n {lonLatZPoints}')
     unit = 'Sv' if sverdrup else 'A m^2/s'
-    ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static)
+    ct = cellThicknessSource(cellThickness, tFile, uFile, vFile, e3u, e3v, e3FileU, e3FileV, e3t, e3tFile, e3Rule, e3Static,
+                             ssh, sshFile, e3Areas)
     if classArea:
         edges = parseClasses(classArea)
         totals, fld = classAreaSeries(tFile, uFile, vFile, lonLatZPoints, tracer, edges, tracerFile, carry, carryFile,
@@ -1306,4 +1353,12 @@ if __name__ == '__main__':
     ap.add_argument('--e3-static', dest='e3Static', default='', metavar='FILE[:E3T0,E3U0,E3V0]',
                     help='with --e3-rule anomaly: the mesh file that holds the static thicknesses at the T, U and V points '
                          '(default names e3t_0,e3u_0,e3v_0)')
+    ap.add_argument('--ssh', default='', metavar='NAME',
+                    help='with --cell-thickness, for z* output that holds no 3-D thickness: derive the thicknesses at the U and V '
+                         'points on the GPU from the sea surface height NAME (ssh, zos) of the T file and the static thicknesses '
+                         'of --e3-static MESH[:E3U0,E3V0] (default names e3u_0,e3v_0): e3u_0 * (1 + ssh_u / hu_0)')
+    ap.add_argument('--ssh-file', dest='sshFile', default='', metavar='FILE', help='read --ssh from FILE instead of the T file')
+    ap.add_argument('--e3-areas', dest='e3Areas', default='', metavar='E1E2T,E1E2U,E1E2V',
+                    help="with --ssh: the cell areas at the T, U and V points in the mesh file of --e3-static, for NEMO's "
+                         'area-weighted sea surface height at the faces (default: the plain mean of the two cells)')
     main(**vars(ap.parse_args()))
