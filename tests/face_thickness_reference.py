@@ -3,8 +3,8 @@ thickness at T-points.  Everything is float64, every operation one correctly rou
 definition, inputs widened first, each result rounded once to the dtype of the inputs -- so the device gives these bits.
 
 face_thickness is the restatement, vectorised over the grid; face_thickness_loop the same definition as a scalar Python loop
-over the faces (tests/test_face_thickness_cpu.py holds the two against each other).  make_case / raw_cases / series are the
-inputs of the GPU tests: thicknesses on the lattice of the multiples of 1/8 in [0.25, 4] (tests/depth_remap_reference.py) with
+over the faces (tests/test_face_thickness_cpu.py holds the two against each other).  make_case / raw_cases / wide_cases / series are
+the inputs of the GPU tests: thicknesses on the lattice of the multiples of 1/8 in [0.25, 4] (tests/depth_remap_reference.py) with
 exact zeros, both markers and NaN scattered."""
 import numpy
 
@@ -171,6 +171,62 @@ def raw_cases():
     """(real, nz, ny, nx, rule, wrap) of the raw GPU tests"""
     return [(real, nz, ny, nx, rule, wrap) for real in ('float64', 'float32') for (nz, ny, nx) in SHAPES
             for rule in (MIN, MEAN, ANOMALY) for wrap in (True, False)]
+
+
+# Past one column chunk.  The kernels deal a row out in chunks of 256 lanes of VEC = 16 / itemsize values each, of one value
+# each when a base or nx does not allow 16-byte lanes; the shapes are the smallest that reach: one full chunk (lane 255 holds
+# the wrap); two chunks, the last of one lane (one value per lane: three chunks); three chunks with several row and level
+# groups; an odd nx (one value per lane whatever the bases).  They are kept out of SHAPES: the scalar loops run over those whole.
+WIDE_SHAPES = {'float64': [(2, 5, 512), (2, 5, 514), (9, 6, 1026), (2, 5, 515)],
+               'float32': [(2, 5, 1024), (2, 5, 1028), (9, 6, 2052), (2, 5, 1027)]}
+LANES = 256
+
+
+def wide_cases():
+    """(real, nz, ny, nx, rule, wrap) of the raw GPU tests past one column chunk"""
+    return [(real, nz, ny, nx, rule, wrap) for real in ('float64', 'float32') for (nz, ny, nx) in WIDE_SHAPES[real]
+            for rule in (MIN, MEAN, ANOMALY) for wrap in (True, False)]
+
+
+def lane_width(nx, itemsize, moved=False):
+    """the values a lane holds: 16 bytes' worth when every base is 16-byte aligned (moved: one of them is not) and nx is a
+    multiple of that, else one"""
+    vec = 16 // itemsize
+    return 1 if moved or nx % vec else vec
+
+
+def chunks_of(nx, vec):
+    return -(-nx // (LANES * vec))
+
+
+def chunk_and_lane(x, vec):
+    """where column x falls: (chunk, lane) with vec values per lane"""
+    return x // (LANES * vec), x % (LANES * vec) // vec
+
+
+def boundary_columns(nx, itemsize):
+    """the columns whose east neighbour another chunk holds, in the 16-byte lane form and in the one-value form (k * P - 1 <
+    nx - 1 for P = 256 * VEC and P = 256), and the last column, whose east neighbour is column 0 or none"""
+    cols = {nx - 1}
+    for per_chunk in (LANES * (16 // itemsize), LANES):
+        cols.update(range(per_chunk - 1, nx - 1, per_chunk))
+    return sorted(cols)
+
+
+def lane_forms(nx, itemsize):
+    """the lane forms a wide case runs in, as vec{VEC}x{chunks}: with the bases as the allocator gives them and then with one
+    of them moved by one element"""
+    forms = []
+    for moved in (False, True):
+        vec = lane_width(nx, itemsize, moved)
+        form = f'vec{vec}x{chunks_of(nx, vec)}'
+        if form not in forms:
+            forms.append(form)
+    return '+'.join(forms)
+
+
+def wide_id(case):
+    return case_id(case) + '-' + lane_forms(case[3], numpy.dtype(case[0]).itemsize)
 
 
 def case_seed(case):

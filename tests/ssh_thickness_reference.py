@@ -12,6 +12,7 @@ exact zeros, both markers and NaN; ssh on the multiples of 1/8 in [-2, 2] with b
 import numpy
 
 from face_thickness_reference import present, same_bits, _neighbours, _geometry, _present1      # noqa: F401
+from face_thickness_reference import WIDE_SHAPES, boundary_columns, chunk_and_lane, chunks_of, lane_forms, lane_width  # noqa: F401
 
 EFILL, EMISSING = 1.e20, -999.0              # the markers of ssh
 SFILL, SMISSING = 9.96921e36, -32768.0       # the markers of the statics
@@ -180,6 +181,18 @@ def raw_cases():
     """(real, nz, ny, nx, areas, wrap, supplied) of the raw GPU tests"""
     return [(real, nz, ny, nx, areas, wrap, supplied) for real in ('float64', 'float32') for (nz, ny, nx) in SHAPES
             for areas in (False, True) for wrap in (True, False) for supplied in (False, True)]
+
+
+# past one column chunk: WIDE_SHAPES of tests/face_thickness_reference.py (nz = 9: a full level group and one of one level),
+# kept out of SHAPES as they are there
+def wide_cases():
+    """(real, nz, ny, nx, areas, wrap, supplied) of the raw GPU tests past one column chunk"""
+    return [(real, nz, ny, nx, areas, wrap, supplied) for real in ('float64', 'float32') for (nz, ny, nx) in WIDE_SHAPES[real]
+            for areas in (False, True) for wrap in (True, False) for supplied in (False, True)]
+
+
+def wide_id(case):
+    return case_id(case) + '-' + lane_forms(case[3], numpy.dtype(case[0]).itemsize)
 
 
 def case_id(case):

@@ -1,7 +1,8 @@
 """Face thicknesses derived from e3t (nf_face_thickness, nemoflux_amd.thickness, fluxplot --e3t), the part that needs no GPU: the
 numpy restatement of tests/face_thickness_reference.py pinned bit for bit to a scalar Python loop on every input set of the GPU
 tests, against closed forms, and through every fallback of the definition one by one; the branches that the GPU tests' inputs
-take; the symbol exported, declared and bound; every argument error the library decides before it needs a device; the Python
+take, and that the wide inputs (past one column chunk) tell a wrong east neighbour at every chunk boundary; the symbol
+exported, declared and bound; every argument error the library decides before it needs a device; the Python
 argument checks of face_thickness, FaceThickness, Field.setCellThickness and fluxplot."""
 import ctypes
 import os
@@ -325,3 +326,87 @@ def test_fluxplot_refuses_bad_e3t_options():
             cellThicknessSource(True, *files, **kw)
     with pytest.raises(RuntimeError, match='--e3t needs --cell-thickness'):
         cellThicknessSource(False, *files, e3t='e3t')
+
+
+# ---- 6. past one column chunk: what the wide inputs of the GPU tests can tell apart -------------------------------------------
+WIDE = ref.wide_cases()
+WIDE_IDS = [ref.wide_id(c) for c in WIDE]
+
+
+def test_wide_shapes_reach_the_chunk_layouts_they_are_there_for():
+    """from the launch code of nf_facethick.hip / nf_sshthick.hip: 256 lanes of VEC = 16 / itemsize values, of one value when a
+    base is moved or nx is no multiple of VEC"""
+    assert ref.boundary_columns(512, 8) == [255, 511] and ref.boundary_columns(514, 8) == [255, 511, 513]
+    assert ref.boundary_columns(1026, 8) == [255, 511, 767, 1023, 1025] and ref.boundary_columns(515, 8) == [255, 511, 514]
+    assert ref.boundary_columns(1028, 4) == [255, 511, 767, 1023, 1027] and ref.boundary_columns(72, 8) == [71]
+    assert ref.boundary_columns(2052, 4) == [255, 511, 767, 1023, 1279, 1535, 1791, 2047, 2051]
+    layouts = {}
+    for real, shapes in ref.WIDE_SHAPES.items():
+        size = numpy.dtype(real).itemsize
+        for nz, ny, nx in shapes:
+            layouts[real, nx] = [(v, ref.chunks_of(nx, v), ref.chunk_and_lane(nx - 1, v)) for v in
+                                 (ref.lane_width(nx, size), ref.lane_width(nx, size, moved=True))]
+    assert layouts['float64', 512] == [(2, 1, (0, 255)), (1, 2, (1, 255))]            # full: the wrap sits on lane 255
+    assert layouts['float64', 514] == [(2, 2, (1, 0)), (1, 3, (2, 1))]                # a last chunk of one lane
+    assert layouts['float64', 1026] == [(2, 3, (2, 0)), (1, 5, (4, 1))]
+    assert layouts['float64', 515] == [(1, 3, (2, 2))] * 2
+    assert layouts['float32', 1024] == [(4, 1, (0, 255)), (1, 4, (3, 255))]
+    assert layouts['float32', 1028] == [(4, 2, (1, 0)), (1, 5, (4, 3))]
+    assert layouts['float32', 2052] == [(4, 3, (2, 0)), (1, 9, (8, 3))]
+    assert layouts['float32', 1027] == [(1, 5, (4, 2))] * 2
+    assert all(nx <= 73 for _, _, nx in ref.SHAPES) and len(set(WIDE_IDS)) == len(WIDE) == 48
+    assert 'float64-2x5x514-min-wrap-vec2x2+vec1x3' in WIDE_IDS and 'float32-2x5x1027-anomaly-nowrap-vec1x5' in WIDE_IDS
+
+
+@pytest.mark.parametrize('case', WIDE, ids=WIDE_IDS)
+def test_wide_restatement_equals_the_scalar_loop_on_two_rows(case):
+    """the first level and two rows of every wide case: the wide expected values rest on the definition of the narrow ones"""
+    real, nz, ny, nx, rule, wrap = case
+    e3t, *statics = (None if a is None else numpy.ascontiguousarray(a[:1, :2]) for a in ref.case_arrays(case))
+    u, v = ref.face_thickness(e3t, rule, *statics, wrap=wrap, markers=EM, static_markers=SM)
+    lu, lv = ref.face_thickness_loop(e3t, rule, *statics, wrap=wrap, markers=EM, static_markers=SM)
+    assert u.shape == (1, 2, nx) and u.dtype == numpy.dtype(real) and ref.same_bits(u, lu) and ref.same_bits(v, lv)
+
+
+def _with_column(arrays, col, source):
+    """the cell inputs (e3t, e3t0) with column col overwritten by column source; the face statics as they are"""
+    out = [None if a is None else a.copy() for a in arrays]
+    for a in out[:2]:
+        if a is not None:
+            a[..., col] = a[..., source]
+    return out
+
+
+@pytest.mark.parametrize('case', WIDE, ids=WIDE_IDS)
+def test_wide_inputs_tell_a_wrong_east_neighbour_at_every_chunk_boundary(case):
+    """a kernel that took column 0 for the east neighbour of a chunk's last column, in either lane form, would give other bits
+    in that column; so would one that wrapped without wrapX, or did not wrap with it"""
+    real, nz, ny, nx, rule, wrap = case
+    arrays = ref.case_arrays(case)
+    kw = dict(markers=EM, static_markers=SM)
+    true = ref.face_thickness(*arrays[:1], rule, *arrays[1:], wrap=wrap, **kw)[0]
+    cols = ref.boundary_columns(nx, numpy.dtype(real).itemsize)
+    assert cols[-1] == nx - 1 and len(cols) >= 2
+    for b in cols[:-1]:
+        e3t, *statics = _with_column(arrays, b + 1, 0)
+        wrong = ref.face_thickness(e3t, rule, *statics, wrap=wrap, **kw)[0]
+        assert not ref.same_bits(wrong[..., b], true[..., b]), b
+    other = ref.face_thickness(*arrays[:1], rule, *arrays[1:], wrap=not wrap, **kw)[0]
+    assert not ref.same_bits(other[..., -1], true[..., -1]) and ref.same_bits(other[..., :-1], true[..., :-1])
+    if not wrap:      # without wrapX column 0 is nothing to the last column
+        e3t, *statics = _with_column(arrays, 0, nx // 2)
+        assert not ref.same_bits(e3t[..., 0], arrays[0][..., 0])
+        moved = ref.face_thickness(e3t, rule, *statics, wrap=False, **kw)[0]
+        assert ref.same_bits(moved[..., -1], true[..., -1]) and not ref.same_bits(moved[..., 0], true[..., 0])
+
+
+@pytest.mark.parametrize('rule', ['min', 'mean', 'anomaly'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_wide_boundary_columns_take_both_present_and_absent_branches(real, rule):
+    taken = set()
+    for case in WIDE:
+        if case[0] == real and case[4] == ref.RULES[rule]:
+            bu = _restated(case)[2]
+            taken |= set(bu[..., ref.boundary_columns(case[3], numpy.dtype(real).itemsize)].reshape(-1).tolist())
+    absent = set(ref.BRANCHES[ref.RULES[rule]]) - {ref.BOTH}
+    assert ref.BOTH in taken and absent <= taken, taken

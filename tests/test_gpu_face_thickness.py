@@ -3,8 +3,9 @@ tests/face_thickness_reference.py bit for bit -- every operation of the definiti
 operation in a fixed order -- on the inputs whose branch coverage tests/test_face_thickness_cpu.py asserts: (ny, nx) = (36, 72)
 and (37, 73), nz = 1 and 7, one launch of (nz, ny, nx) = (3, 1, 5), both dtypes, the three rules, wrapX on and off, thicknesses
 on the lattice of the multiples of 1/8 in [0.25, 4] with exact zeros, both markers and NaN scattered, guard words around both
-outputs, every base pointer in turn moved by one element (no 16-byte alignment: one value per lane).  Then the Python call, and
-a static e3t given as (1, nz, ny, nx)."""
+outputs, every base pointer in turn moved by one element (no 16-byte alignment: one value per lane).  Past one column chunk of
+256 lanes (WIDE_SHAPES there: nx = 512 to 2052) in both lane forms: two, three and more chunks, a full last chunk and one of a
+single lane, the east neighbour that another chunk holds.  Then the Python call, and a static e3t given as (1, nz, ny, nx)."""
 import numpy
 import pytest
 
@@ -16,6 +17,7 @@ NF_F64, NF_F32 = 0, 1
 GUARD = -7.0
 PAD = 16
 CASES = ref.raw_cases()
+WIDE = ref.wide_cases()
 EM, SM = (ref.EFILL, ref.EMISSING), (ref.SFILL, ref.SMISSING)
 
 
@@ -55,11 +57,14 @@ def _call(e3t, rule, statics=(None, None, None), wrap=True, shifts=(0,) * 6, mar
     return res
 
 
-def _report(got, want, label):
+def _report(got, want, label, vec=None):
+    """vec: the values a lane holds in this launch; the report then names the chunk and the lane of the first differing column"""
     bad = ~((got == want) | (numpy.isnan(got) & numpy.isnan(want)))
     if bad.any():
         z, y, x = (int(i[0]) for i in numpy.nonzero(bad))
-        print(f'{label}: {int(bad.sum())} of {got.size} values differ; first: face ({z}, {y}, {x}) got {got[z, y, x]!r} '
+        where = '' if vec is None else ' = chunk %d of %d, lane %d at %d per lane' % (
+            ref.chunk_and_lane(x, vec)[0], ref.chunks_of(got.shape[-1], vec), ref.chunk_and_lane(x, vec)[1], vec)
+        print(f'{label}: {int(bad.sum())} of {got.size} values differ; first: face ({z}, {y}, {x}){where} got {got[z, y, x]!r} '
               f'want {want[z, y, x]!r}')
     return not bad.any()
 
@@ -77,6 +82,25 @@ def test_raw_abi_is_the_restatement_bit_for_bit(case):
         for g, w, name in zip(got, want, ('e3u', 'e3v')):
             label = f'{ref.case_id(case)} {name} moved={moved}'
             assert _report(g, w, label), label
+            assert ref.same_bits(g, w), label
+
+
+@pytest.mark.parametrize('case', WIDE, ids=[ref.wide_id(c) for c in WIDE])
+def test_raw_abi_past_one_column_chunk(case):
+    """rows of two and more chunks of 256 lanes, a full last chunk and one of a single lane (tests/face_thickness_reference.py,
+    WIDE_SHAPES): the bases as the allocator gives them -- 16-byte lanes where nx allows -- and e3u_out moved by one element
+    -- one value per lane, more chunks; where a last chunk holds one lane, every base in turn"""
+    real, nz, ny, nx, rule, wrap = case
+    e3t, *statics = ref.case_arrays(case)
+    want = ref.face_thickness(e3t, rule, *statics, wrap=wrap, markers=EM, static_markers=SM)
+    npointers = 6 if rule == ref.ANOMALY else 3
+    for moved in [None] + (list(range(npointers)) if nx in (514, 1028) else [0]):
+        shifts = tuple(1 if k == moved else 0 for k in range(6))
+        vec = ref.lane_width(nx, e3t.dtype.itemsize, moved is not None)
+        got = _call(e3t, rule, statics, wrap, shifts)
+        for g, w, name in zip(got, want, ('e3u', 'e3v')):
+            label = f'{ref.wide_id(case)} {name} moved={moved}'
+            assert _report(g, w, label, vec), label
             assert ref.same_bits(g, w), label
 
 

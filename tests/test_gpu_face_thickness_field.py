@@ -3,7 +3,7 @@ e3u / e3v are the series of tests/face_thickness_reference.py given as arrays --
 array_equal, both dtypes, e3t in HBM, on the host, in an .npz bundle and in a classic NetCDF-3 file, static and time-varying,
 the three rules, the steps visited 2, 0, 2, 1; the level vector broadcast as e3t against the Field without a cell thickness; two
 sharded halves; timeMean(thicknessWeighted=True) and meanEddySplit; re-use of one handle; the refusal of computeClassTransport;
-fluxplot --cell-thickness --e3t.
+fluxplot --cell-thickness --e3t; a grid of 1030 x 6 (float32: 1028 x 6), past one column chunk of the kernel.
 
 Grids 72 x 36 x 7 x 3 and 73 x 37 x 7 x 3 with the three transects of tests/test_gpu_depth_remap.py (one across the seam)."""
 import numpy
@@ -14,7 +14,7 @@ from depth_remap_reference import EDGES
 from gpu_helpers import _field, _on, _quiet, _resident, _rows
 import face_thickness_reference as ref
 from test_gpu_cellthick import FILL, MISSING, T_OPEN, T_SEAM, _case
-from test_gpu_depth_remap import DB, TH, _make, _set_tracer
+from test_gpu_depth_remap import DB, LINES, TH, _make, _set_tracer
 from test_gpu_gross import GRIDS, NT, NZ, _tau, _uv
 
 pytestmark = pytest.mark.gpu
@@ -136,6 +136,38 @@ def test_field_with_a_face_thickness_gives_the_products_of_the_restatements_seri
                 assert numpy.abs(b).max() > 0 and numpy.array_equal(a, b), (rule, kind)
             for a, b in zip(f.computeTracerAll(), g.computeTracerAll()):
                 assert numpy.abs(b).max() > 0 and numpy.array_equal(a, b), (rule, kind)
+
+
+# a grid past one column chunk of nf_face_thickness / nf_ssh_thickness: three chunks of 16-byte lanes at float64 (512 + 512 + 6),
+# two at float32, the last of one lane (1024 + 4)
+WIDE_GRID = {'float64': (1030, 6), 'float32': (1028, 6)}
+
+
+def _seam_rows(f):
+    """T_SEAM's totals of every step, level by level"""
+    return numpy.stack([numpy.asarray(f.computeFluxProfile(t)[0])[..., LINES.index(T_SEAM)] for t in range(NT)])
+
+
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_a_wide_short_grid_past_one_column_chunk(real):
+    """time-varying e3t in HBM under the anomaly rule on 1030 x 6 and 1028 x 6; T_SEAM runs through the last column, whose
+    east faces take column 0 from another chunk: with the restatement's wrapX off its rows are other rows"""
+    from nemoflux_amd.thickness import FaceThickness
+    grid = WIDE_GRID[real]
+    e3t, statics = _series(real, grid, 'anomaly')
+    want = ref.want_series(e3t, 'anomaly', statics)
+    f, g = _build(real, grid), _build(real, grid)
+    f.setCellThickness(FaceThickness(_on(e3t, True), 'anomaly', *[_on(s, True) for s in statics], **MARKS))
+    g.setCellThickness(_on(want[0], True), _on(want[1], True))
+    assert f._cell_thickness_lazy() and f._e3['nt'] == NT
+    for t in STEPS:
+        _same_products(f, g, t, ('wide', real))
+    off = ref.want_series(e3t, 'anomaly', statics, wrap=False)
+    assert ref.same_bits(off[0][..., :-1], want[0][..., :-1]) and ref.same_bits(off[1], want[1])
+    rows = _seam_rows(g)
+    assert numpy.array_equal(_seam_rows(f), rows) and numpy.abs(rows).max() > 0
+    g.setCellThickness(_on(off[0], True), _on(off[1], True))
+    assert not numpy.array_equal(_seam_rows(g), rows)
 
 
 @pytest.mark.parametrize('real', ['float64', 'float32'])

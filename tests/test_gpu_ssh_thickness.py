@@ -3,8 +3,10 @@ restatement of tests/ssh_thickness_reference.py bit for bit -- every operation o
 float64 operation in a fixed order -- on the inputs whose branch shares tests/test_ssh_thickness_cpu.py asserts: (nz, ny, nx) =
 (7, 36, 72), (7, 37, 73) (one value per lane), (1, 36, 72) and one launch of (3, 1, 5); nz = 7 and nz = 1 end in a short level
 group; both dtypes, with and without areas, wrapX on and off, supplied and computed column depths, guard words around both
-outputs and around h_out, every base pointer in turn moved by one element.  Then the three exact closed forms on the device,
-and the Python calls."""
+outputs and around h_out, every base pointer in turn moved by one element.  Past one column chunk of 256 lanes (WIDE_SHAPES
+of tests/face_thickness_reference.py: nx = 512 to 2052, nz = 9 in two level groups) in both lane forms, nf_column_depth too:
+two, three and more chunks, a full last chunk and one of a single lane, the east neighbour that another chunk holds.  Then the
+three exact closed forms on the device, and the Python calls."""
 import numpy
 import pytest
 
@@ -17,6 +19,7 @@ NF_F64, NF_F32 = 0, 1
 GUARD = -7.0
 PAD = 16
 CASES = ref.raw_cases()
+WIDE = ref.wide_cases()
 EM, SM = ref.EM, ref.SM
 NAN2 = (numpy.nan, numpy.nan)
 
@@ -82,11 +85,14 @@ def _call(ssh, e3u0, e3v0, hu0=None, hv0=None, areas=None, wrap=True, markers=EM
     return res
 
 
-def _report(got, want, label):
+def _report(got, want, label, vec=None):
+    """vec: the values a lane holds in this launch; the report then names the chunk and the lane of the first differing column"""
     bad = ~((got == want) | (numpy.isnan(got) & numpy.isnan(want)))
     if bad.any():
         z, y, x = (int(i[0]) for i in numpy.nonzero(bad))
-        print(f'{label}: {int(bad.sum())} of {got.size} values differ; first: face ({z}, {y}, {x}) got {got[z, y, x]!r} '
+        where = '' if vec is None else ' = chunk %d of %d, lane %d at %d per lane' % (
+            ref.chunk_and_lane(x, vec)[0], ref.chunks_of(got.shape[-1], vec), ref.chunk_and_lane(x, vec)[1], vec)
+        print(f'{label}: {int(bad.sum())} of {got.size} values differ; first: face ({z}, {y}, {x}){where} got {got[z, y, x]!r} '
               f'want {want[z, y, x]!r}')
     return not bad.any()
 
@@ -104,6 +110,26 @@ def test_raw_abi_is_the_restatement_bit_for_bit(case):
         for g, w, name in zip(got, want, ('e3u', 'e3v')):
             label = f'{ref.case_id(case)} {name} moved={moved}'
             assert _report(g, w, label), label
+            assert ref.same_bits(g, w), label
+
+
+@pytest.mark.parametrize('case', WIDE, ids=[ref.wide_id(c) for c in WIDE])
+def test_raw_abi_past_one_column_chunk(case):
+    """rows of two and more chunks of 256 lanes, a full last chunk and one of a single lane (tests/face_thickness_reference.py,
+    WIDE_SHAPES), nz = 9 in two level groups: the bases as the allocator gives them -- 16-byte lanes where nx allows -- and
+    e3u_out moved by one element -- one value per lane, more chunks; where a last chunk holds one lane, every base in turn.
+    The column depths that are not supplied come from nf_column_depth on the same rows."""
+    real, nz, ny, nx, areas, wrap, supplied = case
+    ssh, e3u0, e3v0, kw = ref.case_inputs(case)
+    want = ref.ssh_thickness(ssh, e3u0, e3v0, **kw)
+    pointers = list(range(7)) + ([7, 8, 9] if areas else [])
+    for moved in [None] + (pointers if nx in (514, 1028) else [0]):
+        shifts = tuple(1 if k == moved else 0 for k in range(10))
+        vec = ref.lane_width(nx, e3u0.dtype.itemsize, moved is not None)
+        got = _call(ssh, e3u0, e3v0, shifts=shifts, **kw)
+        for g, w, name in zip(got, want, ('e3u', 'e3v')):
+            label = f'{ref.wide_id(case)} {name} moved={moved}'
+            assert _report(g, w, label, vec), label
             assert ref.same_bits(g, w), label
 
 
@@ -133,6 +159,27 @@ def test_column_depth_is_the_restatement_bit_for_bit(real, shape):
     want = ref.column_depth(c['e3u0'])
     assert not ref.same_bits(want, ref.column_depth(c['e3u0'], SM))
     assert ref.same_bits(_depth(c['e3u0'], markers=NAN2), want)
+
+
+WIDE_DEPTH = [(real, shape) for real in ('float64', 'float32') for shape in ref.WIDE_SHAPES[real]]
+
+
+@pytest.mark.parametrize('real,shape', WIDE_DEPTH, ids=[
+    f'{r}-{"x".join(str(n) for n in s)}-{ref.lane_forms(s[2], numpy.dtype(r).itemsize)}' for r, s in WIDE_DEPTH])
+def test_column_depth_past_one_column_chunk(real, shape):
+    """rows of two and more chunks: e3_0 as the allocator gives it, h_out moved (the lane form of e3_0 stays), e3_0 moved (one
+    value per lane, more chunks)"""
+    nz, ny, nx = shape
+    c = ref.make_case(real, nz, ny, nx, seed=21)
+    for e3_0 in (c['e3u0'], c['e3v0']):
+        want = ref.column_depth(e3_0, SM)
+        assert (want == 0).any() and (want > 0).any()
+        for shifts in ((0, 0), (1, 0), (0, 1)):
+            vec = ref.lane_width(nx, e3_0.dtype.itemsize, shifts[1] != 0)
+            got = _depth(e3_0, shifts)
+            label = f'{real} {shape} h_out shifts={shifts}'
+            assert _report(got[None], want[None], label, vec), label
+            assert ref.same_bits(got, want), label
 
 
 @pytest.mark.parametrize('real', ['float64', 'float32'])

@@ -3,7 +3,8 @@ whose e3u / e3v are the series of tests/ssh_thickness_reference.py given as arra
 array_equal, both dtypes, ssh in HBM, on the host, in an .npz bundle and in a classic NetCDF-3 file, static and time-varying,
 e3u0 / e3v0 given and e3t0 alone, with and without areas, the steps visited 2, 0, 2, 1; ssh = 0 over the level vector against
 the Field without a cell thickness; two sharded halves; timeMean(thicknessWeighted=True), meanEddySplit and
-meanEddyTracerTransport; re-use of one handle; the refusal of computeClassTransport; fluxplot --cell-thickness --ssh.
+meanEddyTracerTransport; re-use of one handle; the refusal of computeClassTransport; fluxplot --cell-thickness --ssh; a grid
+of 1030 x 6 (float32: 1028 x 6), past one column chunk of the kernel.
 
 The grids, transects and helpers are those of tests/test_gpu_face_thickness_field.py."""
 import numpy
@@ -14,7 +15,7 @@ import face_thickness_reference as fref
 import ssh_thickness_reference as ref
 from test_gpu_cellthick import FILL, MISSING, T_OPEN, T_SEAM, _case
 from test_gpu_depth_remap import DB, TH
-from test_gpu_face_thickness_field import PRODUCTS, STEPS, _build, _flat, _same_products
+from test_gpu_face_thickness_field import PRODUCTS, STEPS, WIDE_GRID, _build, _flat, _same_products, _seam_rows
 from test_gpu_gross import GRIDS, NT, NZ, _uv
 
 pytestmark = pytest.mark.gpu
@@ -134,6 +135,28 @@ def test_field_with_an_ssh_thickness_gives_the_products_of_the_restatements_seri
             assert numpy.abs(b).max() > 0 and numpy.array_equal(a, b), config
         for a, b in zip(f.computeTracerAll(), g.computeTracerAll()):
             assert numpy.abs(b).max() > 0 and numpy.array_equal(a, b), config
+
+
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_a_wide_short_grid_past_one_column_chunk(real):
+    """time-varying ssh in HBM, the statics from e3t0, with areas, on 1030 x 6 and 1028 x 6; T_SEAM runs through the last
+    column, whose east faces take column 0 from another chunk: with the restatement's wrapX off its rows are other rows"""
+    grid = WIDE_GRID[real]
+    f, g = _build(real, grid), _build(real, grid)
+    st, want = _descriptor(real, grid, 'hbm', 'e3t0-areas', None)
+    f.setCellThickness(st)
+    g.setCellThickness(_on(want[0], True), _on(want[1], True))
+    assert f._cell_thickness_lazy() and f._e3['nt'] == NT
+    for t in STEPS:
+        _same_products(f, g, t, ('wide', real))
+    c = _series(real, grid)
+    u0, v0, sm = _statics(c, 'e3t0', wrap=False)
+    off = ref.ssh_thickness(c['ssh'], u0, v0, areas=c['areas'], wrap=False, markers=EM, static_markers=sm)
+    assert ref.same_bits(off[0][..., :-1], want[0][..., :-1]) and ref.same_bits(off[1], want[1])
+    rows = _seam_rows(g)
+    assert numpy.array_equal(_seam_rows(f), rows) and numpy.abs(rows).max() > 0
+    g.setCellThickness(_on(off[0], True), _on(off[1], True))
+    assert not numpy.array_equal(_seam_rows(g), rows)
 
 
 @pytest.mark.parametrize('real', ['float64', 'float32'])

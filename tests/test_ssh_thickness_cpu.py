@@ -1,7 +1,8 @@
 """z* thicknesses from the sea surface height (nf_column_depth, nf_ssh_thickness, nemoflux_amd.thickness, fluxplot --ssh), the part
 that needs no GPU: the numpy restatement of tests/ssh_thickness_reference.py pinned bit for bit to a scalar Python loop on every
 input set of the GPU tests, against closed forms, and through every fallback of the definition one by one; the tie to the
-anomaly rule of nf_face_thickness on a flat bottom; the branches that the GPU tests' inputs take; the two symbols exported,
+anomaly rule of nf_face_thickness on a flat bottom; the branches that the GPU tests' inputs take, and that the wide inputs
+(past one column chunk) tell a wrong east neighbour at every chunk boundary; the two symbols exported,
 declared and bound; every argument error the library decides before it needs a device; the Python argument checks of
 ssh_thickness, SshThickness, Field.setCellThickness and fluxplot."""
 import ctypes
@@ -462,3 +463,84 @@ def test_fluxplot_refuses_one_static_name_and_checks_up_front():
                dict(e3Areas='a,b,c', classes='1,2', tracer='thetao')):
         with pytest.raises(RuntimeError, match='--ssh'):
             fluxplot.main(tFile='none_T.npz', uFile='none_U.npz', vFile='none_V.npz', lonLatPoints='[(0,0),(1,1)]', **kw)
+
+
+# ---- past one column chunk: what the wide inputs of the GPU tests can tell apart ----------------------------------------------
+WIDE = ref.wide_cases()
+WIDE_IDS = [ref.wide_id(c) for c in WIDE]
+
+
+def test_wide_cases_are_the_wide_shapes_of_the_face_kernel():
+    assert ref.WIDE_SHAPES is fref.WIDE_SHAPES and all(nx <= 73 for _, _, nx in ref.SHAPES)
+    assert len(set(WIDE_IDS)) == len(WIDE) == 64
+    assert 'float64-9x6x1026-areas-wrap-computed-vec2x3+vec1x5' in WIDE_IDS
+    assert 'float32-2x5x1027-plain-nowrap-supplied-vec1x5' in WIDE_IDS
+    # nz = 9 is a full group of the kernel's 8 levels and a last one of 1
+    assert {nz for shapes in ref.WIDE_SHAPES.values() for nz, _, _ in shapes} == {2, 9}
+
+
+def _two_rows(kw):
+    kw = dict(kw)
+    for k in ('hu0', 'hv0'):
+        kw[k] = None if kw[k] is None else numpy.ascontiguousarray(kw[k][:2])
+    kw['areas'] = None if kw['areas'] is None else tuple(numpy.ascontiguousarray(a[:2]) for a in kw['areas'])
+    return kw
+
+
+@pytest.mark.parametrize('case', WIDE, ids=WIDE_IDS)
+def test_wide_restatement_equals_the_scalar_loop_on_two_rows(case):
+    """the first level and two rows of every wide case: the wide expected values rest on the definition of the narrow ones"""
+    ssh, e3u0, e3v0, kw = ref.case_inputs(case)
+    ssh, e3u0, e3v0 = (numpy.ascontiguousarray(a) for a in (ssh[:2], e3u0[:1, :2], e3v0[:1, :2]))
+    kw = _two_rows(kw)
+    u, v = ref.ssh_thickness(ssh, e3u0, e3v0, **kw)
+    lu, lv = ref.ssh_thickness_loop(ssh, e3u0, e3v0, **kw)
+    assert u.shape == (1, 2, case[3]) and u.dtype == numpy.dtype(case[0]) and ref.same_bits(u, lu) and ref.same_bits(v, lv)
+    for s in (e3u0, e3v0):
+        assert ref.same_bits(ref.column_depth(s, SM), ref.column_depth_loop(s, SM))
+
+
+def _with_column(ssh, kw, col, source):
+    """the cell inputs (ssh, area_t) with column col overwritten by column source; what belongs to the faces as it is"""
+    ssh, kw = ssh.copy(), dict(kw)
+    ssh[..., col] = ssh[..., source]
+    if kw['areas'] is not None:
+        at = kw['areas'][0].copy()
+        at[..., col] = at[..., source]
+        kw['areas'] = (at,) + tuple(kw['areas'][1:])
+    return ssh, kw
+
+
+@pytest.mark.parametrize('case', WIDE, ids=WIDE_IDS)
+def test_wide_inputs_tell_a_wrong_east_neighbour_at_every_chunk_boundary(case):
+    """a kernel that took column 0 for the east neighbour of a chunk's last column, in either lane form, would give other bits
+    in that column; so would one that wrapped without wrapX, or did not wrap with it"""
+    real, nz, ny, nx, areas, wrap, supplied = case
+    ssh, e3u0, e3v0, kw = ref.case_inputs(case)
+    true = ref.ssh_thickness(ssh, e3u0, e3v0, **kw)[0]
+    cols = ref.boundary_columns(nx, numpy.dtype(real).itemsize)
+    assert cols[-1] == nx - 1 and len(cols) >= 2
+    for b in cols[:-1]:
+        s, k = _with_column(ssh, kw, b + 1, 0)
+        wrong = ref.ssh_thickness(s, e3u0, e3v0, **k)[0]
+        assert not ref.same_bits(wrong[..., b], true[..., b]), b
+    other = ref.ssh_thickness(ssh, e3u0, e3v0, **dict(kw, wrap=not wrap))[0]
+    assert not ref.same_bits(other[..., -1], true[..., -1]) and ref.same_bits(other[..., :-1], true[..., :-1])
+    if not wrap:      # without wrapX column 0 is nothing to the last column
+        s, k = _with_column(ssh, kw, 0, nx // 2)
+        assert not ref.same_bits(s[..., 0], ssh[..., 0])
+        moved = ref.ssh_thickness(s, e3u0, e3v0, **k)[0]
+        assert ref.same_bits(moved[..., -1], true[..., -1]) and not ref.same_bits(moved[..., 0], true[..., 0])
+
+
+@pytest.mark.parametrize('areas', [False, True], ids=['plain', 'areas'])
+@pytest.mark.parametrize('real', ['float64', 'float32'])
+def test_wide_boundary_columns_take_both_present_and_absent_branches(real, areas):
+    taken = set()
+    for case in WIDE:
+        if case[0] == real and case[4] == areas:
+            ssh, e3u0, e3v0, kw = ref.case_inputs(case)
+            bu = ref.ssh_thickness(ssh, e3u0, e3v0, with_branches=True, **kw)[2]
+            cols = ref.boundary_columns(case[3], numpy.dtype(real).itemsize)
+            taken |= {b for b, m in bu.items() if m[..., cols].any()}
+    assert set(ref.branches_of((real, 0, 0, 0, areas, False, False))) <= taken, taken
