@@ -13,6 +13,7 @@ import numpy
 
 from . import _lib, mint
 from ._lib import lib, check, NF_F64, NF_F32
+from ._sources import Layout, SigmaProducer, ThicknessProducer, IsoDepthProducer, _native, _nan_if_none
 from .horizgrid import HorizGrid
 from .io import open_tfile, open_uvfile
 from .timeobj import TimeObj
@@ -32,18 +33,36 @@ def _dtype_code(a):
     raise RuntimeError(f'ERROR: unsupported dtype {dt} (need float64 or float32)')
 
 
-def _native(a):
-    """C-contiguous host array in native byte order (files may be big-endian: NetCDF classic, some HDF5)."""
-    a = numpy.ascontiguousarray(a)
-    return a if a.dtype.isnative else a.astype(a.dtype.newbyteorder('='))
-
-
 def _native_dtype(a):
     """numpy dtype, in native byte order, of a host array, a file variable, a DeviceArray or a torch tensor"""
     dt = a.dtype
     if isinstance(dt, numpy.dtype):
         return dt.newbyteorder('=')
     return numpy.dtype(str(dt).replace('torch.', ''))
+
+
+def _open_pair(a):
+    """(variable, its CF markers) of a (path, name) pair, opened with nemoflux_amd.io; anything else as it is, with none"""
+    if isinstance(a, tuple) and len(a) == 2 and isinstance(a[1], str):
+        var, _, d = open_uvfile(a[0], a[1], with_all=True)
+        return var, list(d['_markers_' + a[1]])
+    return a, []
+
+
+def _two_markers(markers, fill_value, missing_value, subject, merge=False):
+    """The engine's (fill, missing), NaN for none, from the markers the files carry and the caller's fill_value / missing_value,
+    which come first; more than two file markers raise in the words of `subject`.  merge: the caller's count among them."""
+    for m in (fill_value, missing_value) if merge else ():
+        if m is not None and float(m) == float(m) and float(m) not in markers:
+            markers.append(float(m))
+    if len(markers) > 2:
+        raise RuntimeError(f'ERROR: {subject} {len(markers)} different _FillValue / missing_value markers '
+                           f'({markers}); the engine masks at most two')
+    if fill_value is None:
+        fill_value = markers[0] if markers else None
+    if missing_value is None:
+        missing_value = markers[1] if len(markers) > 1 else None
+    return tuple(float(m) for m in _nan_if_none((fill_value, missing_value)))
 
 
 def _geometry_only(bounds_lon, bounds_lat):
@@ -161,17 +180,16 @@ class _DerivedThickness(object):
     """e3u (which = 0) or e3v (1) of a time-varying derived cell thickness (nemoflux_amd.thickness.FaceThickness) as a series
     of the time-mean walks: it lives nowhere, step t is computed straight into a device address."""
 
-    def __init__(self, field, slot, which, shape, dtype):
-        self.field, self.slot, self.which, self.shape, self.dtype = field, slot, which, shape, numpy.dtype(dtype)
+    def __init__(self, slot, producer, which, shape, dtype):
+        self.slot, self.producer, self.which, self.shape, self.dtype = slot, producer, which, shape, numpy.dtype(dtype)
 
     def compute_step(self, tIndex, dst_ptr):
         """step tIndex of this face thickness at the HBM address dst_ptr; the other one goes to the slot's own buffer, which
         no longer holds the step the engine was given.  Complete at return."""
-        face = self.slot['face']
         self.slot['step'] = -1
-        ptrs = [face['out'][0].ptr, face['out'][1].ptr]
+        ptrs = [b.ptr for b in self.producer.out]
         ptrs[self.which] = dst_ptr
-        self.field._run_face_thickness(face, tIndex, *ptrs)
+        self.producer.run(tIndex, *ptrs)
         check(lib.nf_synchronize())
 
 
@@ -448,6 +466,15 @@ class Field(object):
         buf._owner = block  # the ctypes object is the numpy array's base: it keeps the block alive
         return numpy.ctypeslib.as_array(buf).view(dtype)[:n].reshape(shape)
 
+    @property
+    def _uv_dtype(self):
+        """the dtype of uo / vo as numpy has it (_uv_code is how the C ABI has it)"""
+        return numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+
+    def _layout(self):
+        """what the producers of nemoflux_amd._sources need to know of this Field"""
+        return Layout(self.nt, self.nz, self.ny, self.nx, self._uv_dtype, self._uv_code, self._stream, self._host_array)
+
     def _host_zeros(self, shape):
         a = self._host_array(shape)
         a[...] = 0.0
@@ -637,104 +664,65 @@ class Field(object):
             if fill_value is not None or missing_value is not None:
                 raise RuntimeError('ERROR: a Sigma carries the markers of thetao and so itself; give them to Sigma(...)')
             return self._sigma_slot(tracer, set_tracer, set_missing)
-        if isinstance(tracer, tuple) and len(tracer) == 2 and isinstance(tracer[1], str):
-            path, name = tracer
-            var, _, d = open_uvfile(path, name, with_all=True)
-            markers = list(d['_markers_' + name])
-            if fill_value is None:
-                fill_value = markers[0] if markers else None
-            if missing_value is None:
-                missing_value = markers[1] if len(markers) > 1 else None
-            if len(markers) > 2:
-                raise RuntimeError(f'ERROR: tracer {name} carries {len(markers)} different _FillValue / missing_value markers '
-                                   f'({markers}); the engine masks at most two')
-            tracer = var
+        given = tracer
+        tracer, markers = _open_pair(tracer)
+        fill, missing = _two_markers(markers, fill_value, missing_value, f'tracer {given[1]} carries' if markers else '')
         shape = tuple(int(x) for x in tracer.shape)
         if self.getSizes(shape) != (self.nt, self.nz, self.ny, self.nx):
             raise RuntimeError(f'ERROR: the tracer has shape {shape}; uo/vo have (nt, nz, ny, nx) = '
                                f'{(self.nt, self.nz, self.ny, self.nx)}')
-        slot = dict(lazy=None, step=-1, set=set_tracer, code=_dtype_code(tracer),
-                    fill=numpy.nan if fill_value is None else float(fill_value),
-                    missing=numpy.nan if missing_value is None else float(missing_value))
+        slot = dict(lazy=None, step=-1, stage=None, code=_dtype_code(tracer), fill=fill, missing=missing)
         ptr = _lib.device_pointer(tracer)
         on_dev = 1
         if hasattr(tracer, 'read_step'):
             # file-backed: step t is read into one pinned host buffer and handed over as a host-resident tracer through a
             # virtual (nt, nz, ny, nx) base that the engine only dereferences at step t (as _stage does for uo / vo)
             slot['lazy'] = (tracer,)
-            slot['buf'] = (self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('=')),)
+            buf = self._host_array((self.nz, self.ny, self.nx), numpy.dtype(tracer.dtype).newbyteorder('='))
+            slot['stage'] = self._slot_stager(set_tracer, slot['code'], 0, fill, lambda t: tracer.read_step(t, out=buf),
+                                              [buf.ctypes.data], buf.nbytes)
             ptr = None
         elif ptr is None:
             tracer = _native(tracer)
             ptr, on_dev = tracer.ctypes.data, 0
         slot['keep'] = tracer    # a borrowed buffer must outlive the handle
         if ptr is not None:
-            check(set_tracer(ctypes.byref(self._h), ptr, self.nt, slot['code'], on_dev, slot['fill']))
-        check(set_missing(ctypes.byref(self._h), numpy.nan if missing_value is None else float(missing_value)))
+            check(set_tracer(ctypes.byref(self._h), ptr, self.nt, slot['code'], on_dev, fill))
+        check(set_missing(ctypes.byref(self._h), missing))
         return slot
+
+    def _slot_stager(self, set_call, code, on_dev, fill, fetch, ptrs, nbytes):
+        """stage(t) of a slot that needs work at every step -- a tracer, or the e3u / e3v pair of a time-varying cell thickness:
+        fetch(t) brings step t to the addresses ptrs (nbytes each; fetch keeps their owner alive), and set_call hands them
+        to the engine through a virtual (nt, nz, ny, nx) base that it only dereferences at step t.  (The closure holds the
+        handle, not the Field: a slot must not keep its Field alive.)"""
+        h, nt = self._h, self.nt
+
+        def stage(t):
+            fetch(t)
+            check(set_call(ctypes.byref(h), *[p - t * nbytes for p in ptrs], nt, code, on_dev, fill))
+        return stage
 
     def _sigma_slot(self, sigma, set_tracer, set_missing):
         """The slot of a derived tracer (nemoflux_amd.eos.Sigma): thetao and so each stay where they are -- device arrays are
         read in place by offset, host arrays and file variables go one time step at a time through a pinned buffer of their
-        own into a device buffer -- and _stage_slot has nf_sigma_eos80 write step t into one (nz, ny, nx) device buffer of the
+        own into a device buffer -- and _stage_slot has a SigmaProducer write step t into its (nz, ny, nx) device buffer of the
         dtype of uo / vo, which the engine reads as a device-resident tracer whose fill is NaN."""
-        sg = self._sigma_inputs(sigma, 'the Sigma')
-        slot = dict(lazy=tuple(sigma.sources), step=-1, set=set_tracer, code=self._uv_code, fill=numpy.nan, missing=numpy.nan,
-                    keep=sigma, sigma=sg)
+        self._check_sigma(sigma, 'the Sigma')
+        sg = SigmaProducer(self._layout(), sigma)
+        slot = dict(lazy=tuple(sigma.sources), step=-1, code=self._uv_code, fill=numpy.nan, missing=numpy.nan, keep=sigma, sigma=sg,
+                    stage=self._slot_stager(set_tracer, self._uv_code, 1, numpy.nan, lambda t: sg.run(t, sg.out.ptr), [sg.out.ptr],
+                                            sg.nbytes))
         check(set_missing(ctypes.byref(self._h), numpy.nan))
         return slot
 
-    def _sigma_inputs(self, sigma, what):
-        """what computing a Sigma one step at a time needs (_run_sigma): where thetao and so live, a pinned buffer and a device
-        buffer for each that is not on the device, and the (nz, ny, nx) device buffer that receives sigma"""
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+    def _check_sigma(self, sigma, what):
+        uv_dtype = self._uv_dtype
         if self.getSizes(sigma.shape) != (self.nt, self.nz, self.ny, self.nx):
             raise RuntimeError(f'ERROR: thetao and so of {what} have shape {sigma.shape}; uo/vo have (nt, nz, ny, nx) = '
                                f'{(self.nt, self.nz, self.ny, self.nx)}')
         if sigma.dtype != uv_dtype:
             raise RuntimeError(f'ERROR: thetao and so of {what} are {sigma.dtype.name}, uo/vo are {uv_dtype.name}')
-        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
-        inputs = []
-        for src, (fill, missing) in zip(sigma.sources, sigma.markers):
-            ptr = _lib.device_pointer(src)
-            one = dict(ptr=ptr, fill=numpy.nan if fill is None else fill, missing=numpy.nan if missing is None else missing,
-                       keep=src)     # a borrowed buffer must outlive the handle
-            if ptr is None:
-                one['file'] = hasattr(src, 'read_step')
-                one['host'] = None if one['file'] else _native(src).reshape(self.nt, self.nz, self.ny, self.nx)
-                one['pinned'] = self._host_array((self.nz, self.ny, self.nx), uv_dtype)
-                one['dev'] = _lib.DeviceBuffer(nbytes)
-            inputs.append(one)
-        return dict(pref=sigma.pref, inputs=inputs, out=_lib.DeviceBuffer(nbytes), nbytes=nbytes)
-
-    def _run_sigma(self, sg, code, tIndex):
-        """thetao and so of step tIndex on the device and nf_sigma_eos80 into sg['out'] on the Field's stream; the stream is
-        drained when a staging buffer was used (it is written again by the next step)"""
-        off = tIndex * sg['nbytes']
-        ptrs = []
-        for one in sg['inputs']:
-            if one['ptr'] is not None:
-                ptrs.append(one['ptr'] + off)
-                continue
-            if one['file']:
-                one['keep'].read_step(tIndex, out=one['pinned'])
-            else:
-                numpy.copyto(one['pinned'], one['host'][tIndex])
-            check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, sg['nbytes']))
-            ptrs.append(one['dev'].ptr)
-        th, so = sg['inputs']
-        check(lib.nf_sigma_eos80(sg['out'].ptr, ptrs[0], ptrs[1], self.nz * self.ny * self.nx, code, sg['pref'],
-                                 th['fill'], th['missing'], so['fill'], so['missing'], numpy.nan, self._stream))
-        if any(one['ptr'] is None for one in sg['inputs']):
-            check(lib.nf_synchronize())     # the staging buffers are written again by the next step
-
-    def _stage_sigma(self, slot, tIndex):
-        """step tIndex of a Sigma slot: thetao and so of that step on the device, nf_sigma_eos80 into the slot's buffer on the
-        Field's stream, and the buffer handed over through a virtual (nt, nz, ny, nx) base"""
-        sg = slot['sigma']
-        self._run_sigma(sg, slot['code'], tIndex)
-        check(slot['set'](ctypes.byref(self._h), sg['out'].ptr - tIndex * sg['nbytes'], self.nt, slot['code'], 1, numpy.nan))
-        slot['step'] = tIndex
 
     def _sigma_refused(self, what):
         for slot in (getattr(self, '_tracer', None), getattr(self, '_class_tracer', None)):
@@ -744,21 +732,10 @@ class Field(object):
                                    f'here: set a plain tracer')
 
     def _stage_slot(self, slot, tIndex):
-        """make step tIndex of a file-backed slot -- a tracer, or the e3u / e3v pair of a time-varying cell thickness -- the one
-        the engine reads (no-op for in-memory / HBM arrays)"""
-        if slot is not None and slot.get('sigma') is not None:
-            if slot['step'] != tIndex:
-                self._stage_sigma(slot, tIndex)
-        elif slot is not None and slot.get('face') is not None:
-            if slot['step'] != tIndex:
-                self._stage_face_thickness(slot, tIndex)
-        elif slot is not None and slot['lazy'] is not None and slot['step'] != tIndex:
-            for src, buf in zip(slot['lazy'], slot['buf']):
-                src.read_step(tIndex, out=buf)
-            # a virtual (nt, nz, ny, nx) base that the engine only dereferences at step tIndex
-            off = tIndex * slot['buf'][0].nbytes
-            check(slot['set'](ctypes.byref(self._h), *[buf.ctypes.data - off for buf in slot['buf']], self.nt, slot['code'], 0,
-                              slot['fill']))
+        """make step tIndex of a slot that needs work at every step -- a file-backed or derived tracer, or the e3u / e3v pair
+        of a time-varying cell thickness -- the one the engine reads (no-op for in-memory / HBM arrays)"""
+        if slot is not None and slot.get('stage') is not None and slot['step'] != tIndex:
+            slot['stage'](tIndex)
             slot['step'] = tIndex
 
     def _stage_tracer(self, tIndex):
@@ -827,16 +804,13 @@ class Field(object):
             check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), None, None, 0, NF_F64, 0, numpy.nan))
             self._face_keep = None
             return
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        uv_dtype = self._uv_dtype
         markers, arrs = [], []
         for e3, which in ((e3u, 'e3u'), (e3v, 'e3v')):
-            if isinstance(e3, tuple) and len(e3) == 2 and isinstance(e3[1], str):
-                path, name = e3
-                var, _, d = open_uvfile(path, name, with_all=True)
-                for m in d['_markers_' + name]:
-                    if m not in markers:
-                        markers.append(m)
-                e3 = var
+            e3, own = _open_pair(e3)
+            for m in own:
+                if m not in markers:
+                    markers.append(m)
             shape = tuple(int(x) for x in e3.shape)
             nt_th = self.getSizes(shape)[0] if len(shape) in (3, 4) else -1
             if len(shape) not in (3, 4) or self.getSizes(shape)[1:] != (self.nz, self.ny, self.nx) or nt_th not in (1, self.nt):
@@ -848,16 +822,8 @@ class Field(object):
         if arrs[0][1] != arrs[1][1]:
             raise RuntimeError(f'ERROR: e3u has {arrs[0][1]} time step(s) and e3v {arrs[1][1]}: both static or both per time step')
         nt_th = arrs[0][1]
-        if fill_value is None:
-            fill_value = markers[0] if markers else None
-        if missing_value is None:
-            missing_value = markers[1] if len(markers) > 1 else None
-        if len(markers) > 2:
-            raise RuntimeError(f'ERROR: e3u / e3v carry {len(markers)} different _FillValue / missing_value markers '
-                               f'({markers}); the engine masks at most two')
-        slot = dict(lazy=None, step=-1, set=lib.nf_field_set_cell_thickness, code=self._uv_code, nt=nt_th,
-                    fill=numpy.nan if fill_value is None else float(fill_value),
-                    missing=numpy.nan if missing_value is None else float(missing_value), keep=[], arrays=[])
+        fill, missing = _two_markers(markers, fill_value, missing_value, 'e3u / e3v carry')
+        slot = dict(lazy=None, step=-1, stage=None, code=self._uv_code, nt=nt_th, fill=fill, missing=missing, keep=[], arrays=[])
         ptrs, on_dev, lazy = [], None, []
         for (e3, _), which in zip(arrs, ('e3u', 'e3v')):
             dt = numpy.dtype(_native_dtype(e3))
@@ -887,60 +853,19 @@ class Field(object):
         if lazy[0] != lazy[1]:
             raise RuntimeError('ERROR: e3u and e3v must both be read from files one step at a time, or neither')
         if lazy[0]:
-            slot['lazy'] = (arrs[0][0], arrs[1][0])
-            slot['buf'] = tuple(ptrs)
+            slot['lazy'] = pair = (arrs[0][0], arrs[1][0])
+            slot['stage'] = self._slot_stager(lib.nf_field_set_cell_thickness, self._uv_code, 0, fill,
+                                              lambda t: [src.read_step(t, out=buf) for src, buf in zip(pair, ptrs)],
+                                              [buf.ctypes.data for buf in ptrs], ptrs[0].nbytes)
         else:
             check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), ptrs[0], ptrs[1], nt_th, self._uv_code,
-                                                  1 if on_dev else 0, slot['fill']))
-        check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), numpy.nan if missing_value is None
-                                                            else float(missing_value)))
+                                                  1 if on_dev else 0, fill))
+        check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), missing))
         self._e3 = slot
         self._face_keep = None
 
-    def _derived_static(self, a, dims, dtype):
-        """a static input of a derived cell thickness, shaped dims once a leading 1 is dropped: (its device address, what keeps
-        it alive) -- on the device as it is, else read / cast to dtype and uploaded once"""
-        ptr = _lib.device_pointer(a)
-        if ptr is not None:
-            return ptr, a
-        if hasattr(a, 'read_step'):
-            a = a.read_step(0)       # a static file variable: read once (a packed one of fewer than 4 dimensions decodes whole)
-        buf = _lib.DeviceBuffer(int(numpy.prod(dims)) * numpy.dtype(dtype).itemsize)
-        buf.upload(_native(numpy.asarray(a).astype(dtype, copy=False)).reshape(dims))
-        return buf.ptr, buf
-
-    def _derived_source(self, src, nt_th, dims, keep):
-        """where the per-step input of a derived cell thickness (e3t of a FaceThickness, ssh of an SshThickness), a step of which
-        is shaped dims, lives: a static one on the device; a time-varying device array in place; a time-varying host array or
-        file variable with a pinned buffer and a device buffer that _derived_step fills one time step at a time"""
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
-        nbytes = int(numpy.prod(dims)) * uv_dtype.itemsize
-        if nt_th == 1:
-            ptr, owner = self._derived_static(src, dims, uv_dtype)
-            keep.append(owner)
-            return dict(ptr=ptr, nbytes=nbytes)
-        ptr = _lib.device_pointer(src)
-        one = dict(ptr=ptr, src=src, nbytes=nbytes)     # a borrowed buffer must outlive the handle
-        if ptr is None:
-            one['file'] = hasattr(src, 'read_step')
-            one['host'] = None if one['file'] else _native(src).reshape((self.nt,) + tuple(dims))
-            one['pinned'] = self._host_array(dims, uv_dtype)
-            one['dev'] = _lib.DeviceBuffer(nbytes)
-        return one
-
-    def _derived_step(self, one, tIndex):
-        """the device address of step tIndex of a _derived_source"""
-        if one['ptr'] is not None:
-            return one['ptr'] + tIndex * one['nbytes']
-        if one['file']:
-            one['src'].read_step(tIndex, out=one['pinned'])
-        else:
-            numpy.copyto(one['pinned'], one['host'][tIndex])
-        check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, one['nbytes']))
-        return one['dev'].ptr
-
-    def _check_derived_static(self, a, which, dims):
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+    def _check_static_input(self, a, which, dims):
+        uv_dtype = self._uv_dtype
         names = ('(nz, ny, nx)', '(1, nz, ny, nx)') if len(dims) == 3 else ('(ny, nx)', '(1, ny, nx)')
         shape = tuple(int(x) for x in a.shape)
         if shape not in (tuple(dims), (1,) + tuple(dims)):
@@ -956,7 +881,7 @@ class Field(object):
         into a device buffer -- the statics go to the device once, and nf_face_thickness writes two (nz, ny, nx) device buffers
         of the dtype of uo / vo on the Field's stream.  A static e3t: computed once, here, and set as a static HBM thickness.
         A time-varying one: _stage_slot computes step t and hands the buffers over through a virtual (nt, nz, ny, nx) base."""
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        uv_dtype = self._uv_dtype
         dims = (self.nz, self.ny, self.nx)
         shape = ft.shape
         nt_th = self.getSizes(shape)[0] if len(shape) in (3, 4) else -1
@@ -964,27 +889,13 @@ class Field(object):
             raise RuntimeError(f'ERROR: e3t has shape {shape}; need (nz, ny, nx) = {dims}, (1, nz, ny, nx) or '
                                f'(nt, nz, ny, nx) = {(self.nt,) + dims}')
         if nt_th == 1:
-            self._check_derived_static(ft.e3t, 'e3t', dims)
+            self._check_static_input(ft.e3t, 'e3t', dims)
         elif ft.dtype != uv_dtype:
             raise RuntimeError(f'ERROR: e3t is {ft.dtype.name}, uo/vo are {uv_dtype.name}: only a static host array of '
                                f'another float dtype is cast')
         for a, which in zip(ft.statics, ('e3t0', 'e3u0', 'e3v0')):
-            self._check_derived_static(a, which, dims)
-        keep, statics = [ft], []
-        for a in ft.statics:
-            ptr, owner = self._derived_static(a, dims, uv_dtype)
-            statics.append(ptr)
-            keep.append(owner)
-        statics += [None] * (3 - len(statics))
-        nan = numpy.nan
-        marks = tuple(nan if m is None else m for m in ft.markers + ft.static_markers)
-        rule, wrap = ft.code, 1 if ft.wrapX else 0
-
-        def run(e3u_ptr, e3v_ptr, src):
-            check(lib.nf_face_thickness(e3u_ptr, e3v_ptr, src, *statics, self.nz, self.ny, self.nx, self._uv_code, rule, wrap,
-                                        *marks, self._stream))
-
-        self._derived_slot(run, ft.e3t, nt_th, dims, keep)
+            self._check_static_input(a, which, dims)
+        self._derived_slot(ThicknessProducer.face(self._layout(), ft, nt_th), ft.e3t, nt_th)
 
     def _ssh_thickness_slot(self, st):
         """The cell-thickness slot of a z* pair derived from the sea surface height (nemoflux_amd.thickness.SshThickness).  The
@@ -993,7 +904,7 @@ class Field(object):
         device once; ssh stays where it is -- a (ny, nx) plane in HBM is read in place by offset, a host plane (a file's ssh
         is a host array by now: the descriptor read it whole) goes through a pinned buffer -- and nf_ssh_thickness writes the slot's two (nz, ny, nx) device buffers on the Field's
         stream, as nf_face_thickness does for a FaceThickness: the rest is _derived_slot."""
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        uv_dtype = self._uv_dtype
         dims, cells = (self.nz, self.ny, self.nx), (self.ny, self.nx)
         shape = st.shape
         nt_th = 1 if len(shape) == 2 else (shape[0] if len(shape) == 3 else -1)
@@ -1001,12 +912,12 @@ class Field(object):
             raise RuntimeError(f'ERROR: ssh has shape {shape}; need (ny, nx) = {cells}, (1, ny, nx) or (nt, ny, nx) = '
                                f'{(self.nt,) + cells}')
         if nt_th == 1:
-            self._check_derived_static(st.ssh, 'ssh', cells)
+            self._check_static_input(st.ssh, 'ssh', cells)
         elif st.dtype != uv_dtype:
             raise RuntimeError(f'ERROR: ssh is {st.dtype.name}, uo/vo are {uv_dtype.name}: only a static host array of '
                                f'another float dtype is cast')
         for a, which in zip(st.statics, ('e3t0',) if st.from_e3t0 else ('e3u0', 'e3v0')):
-            self._check_derived_static(a, which, dims)
+            self._check_static_input(a, which, dims)
         planes = [(a, w) for a, w in zip(st.depths or (), ('hu0', 'hv0'))]
         planes += [(a, f'areas[{k}]') for k, a in enumerate(st.areas or ())]
         for a, which in planes:
@@ -1015,90 +926,29 @@ class Field(object):
                 raise RuntimeError(f'ERROR: {which} has shape {shp}; need (ny, nx) = {cells} or (1, ny, nx)')
             if dt != numpy.float64 and (_lib.device_pointer(a) is not None or dt.kind != 'f'):
                 raise RuntimeError(f'ERROR: {which} is {dt.name}: a device array must be float64, a host array a float array')
-        nan = numpy.nan
-        keep, statics = [st], []
-        smarks = tuple(nan if m is None else m for m in st.static_markers)
-        for a in st.statics:
-            ptr, owner = self._derived_static(a, dims, uv_dtype)
-            statics.append(ptr)
-            keep.append(owner)
-        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
-        if st.from_e3t0:
-            # NEMO's partial-step rule for e3u_0 / e3v_0: the thinner of the two cells, 0 beside a cell without a thickness
-            pair = (_lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes))
-            check(lib.nf_face_thickness(pair[0].ptr, pair[1].ptr, statics[0], None, None, None, self.nz, self.ny, self.nx,
-                                        self._uv_code, _lib.NF_E3_MIN, 1 if st.wrapX else 0, *smarks, nan, nan, self._stream))
-            keep += list(pair)
-            statics, smarks = [pair[0].ptr, pair[1].ptr], (nan, nan)
-        depths = []
-        for k in (0, 1):
-            if st.depths is not None:
-                ptr, owner = self._derived_static(st.depths[k], cells, numpy.float64)
-            else:
-                owner = _lib.DeviceBuffer(self.ny * self.nx * 8)
-                ptr = owner.ptr
-                check(lib.nf_column_depth(ptr, statics[k], self.nz, self.ny, self.nx, self._uv_code, *smarks, self._stream))
-            depths.append(ptr)
-            keep.append(owner)
-        areas = [None, None, None]
-        if st.areas is not None:
-            for k, a in enumerate(st.areas):
-                areas[k], owner = self._derived_static(a, cells, numpy.float64)
-                keep.append(owner)
-        marks = tuple(nan if m is None else m for m in st.markers) + smarks
-        wrap = 1 if st.wrapX else 0
+        self._derived_slot(ThicknessProducer.ssh(self._layout(), st, nt_th), st.ssh, nt_th)
 
-        def run(e3u_ptr, e3v_ptr, src):
-            check(lib.nf_ssh_thickness(e3u_ptr, e3v_ptr, src, *statics, *depths, *areas, self.nz, self.ny, self.nx,
-                                       self._uv_code, wrap, *marks, self._stream))
-
-        self._derived_slot(run, st.ssh, nt_th, cells, keep)
-
-    def _derived_slot(self, run, src, nt_th, step_dims, keep):
-        """the common part of the derived cell-thickness slots: run(e3u_ptr, e3v_ptr, src_ptr) writes the pair of one step of
-        src, a step of which is shaped step_dims, on the Field's stream.  A static src: computed once, here, and set as a
-        static HBM thickness.  A time-varying one: _stage_slot computes step t into the slot's two (nz, ny, nx) device buffers
-        and hands them over through a virtual (nt, nz, ny, nx) base."""
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
-        dims = (self.nz, self.ny, self.nx)
-        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
-        nan = numpy.nan
-        face = dict(run=run, nbytes=nbytes, out=(_lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes)),
-                    src=self._derived_source(src, nt_th, step_dims, keep))
-        slot = dict(lazy=None, step=-1, set=lib.nf_field_set_cell_thickness, code=self._uv_code, nt=nt_th, fill=nan, missing=nan,
-                    keep=keep, face=face)
+    def _derived_slot(self, producer, src, nt_th):
+        """the common part of the derived cell-thickness slots: producer.run(t, e3u_ptr, e3v_ptr) writes the pair of step t of
+        src on the Field's stream.  A static src: computed once, here, and set as a static HBM thickness.  A time-varying
+        one: _stage_slot computes step t into the producer's two (nz, ny, nx) device buffers and hands them over through a
+        virtual (nt, nz, ny, nx) base."""
+        uv_dtype, dims, nan = self._uv_dtype, (self.nz, self.ny, self.nx), numpy.nan
+        outs = [b.ptr for b in producer.out]
+        slot = dict(lazy=None, step=-1, stage=None, code=self._uv_code, nt=nt_th, fill=nan, missing=nan, keep=producer)
         if nt_th == 1:
-            self._run_face_thickness(face, 0, face['out'][0].ptr, face['out'][1].ptr)
+            producer.run(0, *outs)
             check(lib.nf_synchronize())
-            slot['arrays'] = [_lib.DeviceArray(b.ptr, dims, uv_dtype, keepalive=b) for b in face['out']]
-            slot['face'] = None       # a static HBM thickness from here on
-            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), face['out'][0].ptr, face['out'][1].ptr, 1,
-                                                  self._uv_code, 1, nan))
+            slot['arrays'] = [_lib.DeviceArray(b.ptr, dims, uv_dtype, keepalive=b) for b in producer.out]
+            check(lib.nf_field_set_cell_thickness(ctypes.byref(self._h), outs[0], outs[1], 1, self._uv_code, 1, nan))
         else:
             slot['lazy'] = (src,)
-            slot['arrays'] = [_DerivedThickness(self, slot, k, (self.nt,) + dims, uv_dtype) for k in (0, 1)]
+            slot['stage'] = self._slot_stager(lib.nf_field_set_cell_thickness, self._uv_code, 1, nan,
+                                              lambda t: producer.run(t, *outs), outs, producer.nbytes)
+            slot['arrays'] = [_DerivedThickness(slot, producer, k, (self.nt,) + dims, uv_dtype) for k in (0, 1)]
         check(lib.nf_field_set_cell_thickness_missing_value(ctypes.byref(self._h), nan))
         self._e3 = slot
         self._face_keep = slot       # the engine reads these buffers until another thickness is set
-
-    def _run_face_thickness(self, face, tIndex, e3u_ptr, e3v_ptr):
-        """the input of step tIndex on the device and the slot's kernel (nf_face_thickness or nf_ssh_thickness) into the two
-        addresses on the Field's stream; the stream is drained when the staging buffer was used (it is written again by the
-        next step)"""
-        one = face['src']
-        face['run'](e3u_ptr, e3v_ptr, self._derived_step(one, tIndex))
-        if one['ptr'] is None:
-            check(lib.nf_synchronize())     # the staging buffer is written again by the next step
-
-    def _stage_face_thickness(self, slot, tIndex):
-        """step tIndex of a derived cell thickness: its input of that step on the device, the slot's kernel into the slot's two
-        buffers on the Field's stream, and the buffers handed over through a virtual (nt, nz, ny, nx) base"""
-        face = slot['face']
-        self._run_face_thickness(face, tIndex, face['out'][0].ptr, face['out'][1].ptr)
-        off = tIndex * face['nbytes']
-        check(slot['set'](ctypes.byref(self._h), face['out'][0].ptr - off, face['out'][1].ptr - off, self.nt, slot['code'], 1,
-                          numpy.nan))
-        slot['step'] = tIndex
 
     def _cell_thickness_lazy(self):
         e3 = getattr(self, '_e3', None)
@@ -1447,14 +1297,19 @@ class Field(object):
             total = total + x
         return idx, numpy.ascontiguousarray(w), float(total)
 
-    def _time_mean_walk_table(self, series, markers, table, nacc, kernel, carry_wsum):
-        """_time_mean_walk over a table (_step_table) of selected, weighted steps.  kernel(accs, wsum, cnt, ptrs, offsets,
-        weights, nsteps, n, code, fill, missing, first, last, total_weight, fill_out) makes the C call for nsteps table entries:
-        series j's steps at the element offsets offsets[j] (int64) from the HBM address ptrs[j].  HBM: one call on the offsets
-        select * n.  Host: groups of selected steps packed into the staging buffer.  File-backed: one selected step at a time;
-        a step that is not selected is never read.  carry_wsum: the kernel carries a sum of weights (NF_MEAN_OVER_PRESENT)."""
+    def _time_mean_groups(self, series, markers, idx, nacc, contiguous, carry_wsum, call):
+        """The steps idx (ascending) of a list of (nt, nz, ny, nx) arrays of one dtype, each in any of its homes (HBM, host,
+        file-backed, derived), in groups through one of the time-mean kernels into `nacc` float64 torch CUDA tensors
+        (1, nz, ny, nx).  call(accs, wsum, cnt, ptrs, offsets, j0, k, n, code, size, fill, missing, first, last, fill_out) makes
+        the C call for the k steps idx[j0:j0 + k]: series j's steps are at the element offsets offsets[j] (int64, ascending)
+        from the HBM address ptrs[j]; fill / missing: `markers` without NaN.  All in HBM: one call on the offsets idx * n,
+        nothing carried.  Host arrays: groups of steps within _MEAN_STAGE_BYTES for all the series together, packed into
+        staging buffers -- a group in one copy when idx is `contiguous`, else step by step.  File-backed or derived: one
+        step at a time; a step that is not in idx is never read.  carry_wsum: the kernel carries a sum of weights
+        (NF_MEAN_OVER_PRESENT).  Returns the tensors and fill_out -- the first marker as the dtype of the arrays holds it, NaN
+        without one -- which stands where the value is missing at every step.  The bits do not depend on the homes or on the
+        grouping of the steps."""
         import torch
-        idx, w, total = table
         dt = numpy.dtype(_native_dtype(series[0]))
         code, size = (NF_F32 if dt == numpy.float32 else NF_F64), dt.itemsize
         marks = [float(m) for m in markers if m == m]
@@ -1466,15 +1321,14 @@ class Field(object):
         ptrs = [_lib.device_pointer(x) for x in series]
         staged = [p is None for p in ptrs]
 
-        def run(cur, offsets, j0, k, first, last, wsum=None, cnt=None):
-            offsets = [numpy.ascontiguousarray(o, dtype=numpy.int64) for o in offsets]
-            kernel([x.data_ptr() for x in accs], None if wsum is None else wsum.data_ptr(), None if cnt is None else cnt.data_ptr(),
-                   cur, offsets, None if w is None else w[j0:j0 + k], k, n, code, fill, missing, 1 if first else 0,
-                   1 if last else 0, total, fill_out)
+        def run(cur, offsets, j0, k, wsum=None, cnt=None):
+            call([x.data_ptr() for x in accs], None if wsum is None else wsum.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                 cur, [numpy.ascontiguousarray(o, dtype=numpy.int64) for o in offsets], j0, k, n, code, size, fill, missing,
+                 1 if j0 == 0 else 0, 1 if j0 + k == len(idx) else 0, fill_out)
 
         everywhere = numpy.array(idx, dtype=numpy.int64) * n
         if not any(staged):       # all in HBM: one pass, nothing carried
-            run(ptrs, [everywhere] * len(series), 0, len(idx), True, True)
+            run(ptrs, [everywhere] * len(series), 0, len(idx))
         else:
             cnt = torch.empty(n, dtype=torch.int32, device='cuda')
             wsum = torch.empty(n, dtype=torch.float64, device='cuda') if carry_wsum else None
@@ -1493,84 +1347,47 @@ class Field(object):
                         cur.append(ptrs[j])
                         offsets.append(everywhere[j0:j0 + k])
                         continue
-                    for m, t in enumerate(idx[j0:j0 + k]):      # the selected steps of this group, packed
+                    # the steps of this group, packed; (first packed step, number of steps) of every copy
+                    for m, c in [(0, k)] if contiguous and hosts[j] is not None else [(m, 1) for m in range(k)]:
+                        t, dst = idx[j0 + m], stage[j].ptr + m * n * size
                         if derived[j]:      # computed straight into the staging buffer
-                            series[j].compute_step(t, stage[j].ptr + m * n * size)
+                            series[j].compute_step(t, dst)
                             continue
                         if lazy[j]:
                             series[j].read_step(t, out=bufs[j])
-                        check(lib.nf_memcpy_h2d(stage[j].ptr + m * n * size,
-                                                bufs[j].ctypes.data if lazy[j] else hosts[j][t:t + 1].ctypes.data, n * size))
+                        check(lib.nf_memcpy_h2d(dst, bufs[j].ctypes.data if lazy[j] else hosts[j][t:t + c].ctypes.data,
+                                                c * n * size))
                     cur.append(stage[j].ptr)
                     offsets.append(numpy.arange(k, dtype=numpy.int64) * n)
-                run(cur, offsets, j0, k, j0 == 0, j0 + k == len(idx), wsum, cnt)
+                run(cur, offsets, j0, k, wsum, cnt)
                 check(lib.nf_synchronize())     # the staging buffers are written again by the next group
             for b in stage:
                 if b is not None:
                     b.free()
         check(lib.nf_synchronize())
         return accs, fill_out
+
+    def _time_mean_walk_table(self, series, markers, table, nacc, kernel, carry_wsum):
+        """_time_mean_groups over a table (_step_table) of selected, weighted steps.  kernel(accs, wsum, cnt, ptrs, offsets,
+        weights, nsteps, n, code, fill, missing, first, last, total_weight, fill_out) makes the C call for nsteps table entries:
+        series j's steps at the element offsets offsets[j] (int64) from the HBM address ptrs[j]."""
+        idx, w, total = table
+
+        def call(accs, wsum, cnt, ptrs, offsets, j0, k, n, code, size, fill, missing, first, last, fill_out):
+            kernel(accs, wsum, cnt, ptrs, offsets, None if w is None else w[j0:j0 + k], k, n, code, fill, missing, first, last,
+                   total, fill_out)
+
+        return self._time_mean_groups(series, markers, idx, nacc, False, carry_wsum, call)
 
     def _time_mean_walk(self, series, markers, t0, t1, nacc, kernel):
-        """The steps [t0, t1) of a list of (nt, nz, ny, nx) arrays of one dtype, each in any of its three homes (HBM, host,
-        file-backed), through one of the time-mean kernels into `nacc` float64 torch CUDA tensors (1, nz, ny, nx).
-        kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last, total_steps, fill_out) makes the C call for nsteps
-        steps that begin at the HBM addresses ptrs (one per series); fill / missing: `markers` without NaN.  Returns the
-        tensors and fill_out -- the first marker as the dtype of the arrays holds it, NaN without one -- which stands where
-        the value is missing at every step.  The bits do not depend on the homes or on the grouping of the steps.
-        The selected, weighted form of the walk is _time_mean_walk_table."""
-        import torch
-        dt = numpy.dtype(_native_dtype(series[0]))
-        code, size = (NF_F32 if dt == numpy.float32 else NF_F64), dt.itemsize
-        marks = [float(m) for m in markers if m == m]
-        with numpy.errstate(over='ignore'):
-            fill_out = float(dt.type(marks[0])) if marks else numpy.nan
-        fill, missing = (marks + [numpy.nan, numpy.nan])[:2]
-        n = self.nz * self.ny * self.nx
-        accs = [torch.empty((1, self.nz, self.ny, self.nx), dtype=torch.float64, device='cuda') for _ in range(nacc)]
+        """_time_mean_groups over the steps [t0, t1).  kernel(accs, cnt, ptrs, nsteps, n, code, fill, missing, first, last,
+        total_steps, fill_out) makes the C call for nsteps steps that begin at the HBM addresses ptrs (one per series).  The
+        selected, weighted form of the walk is _time_mean_walk_table."""
+        def call(accs, wsum, cnt, ptrs, offsets, j0, k, n, code, size, fill, missing, first, last, fill_out):
+            kernel(accs, cnt, [p + int(o[0]) * size for p, o in zip(ptrs, offsets)], k, n, code, fill, missing, first, last,
+                   t1 - t0, fill_out)
 
-        def run(cur, nsteps, first, last, cnt=None):
-            kernel([x.data_ptr() for x in accs], None if cnt is None else cnt.data_ptr(), cur, nsteps, n, code, fill, missing,
-                   1 if first else 0, 1 if last else 0, t1 - t0, fill_out)
-
-        ptrs = [_lib.device_pointer(x) for x in series]
-        staged = [p is None for p in ptrs]
-        if not any(staged):       # all in HBM: one pass, nothing carried
-            run([p + t0 * n * size for p in ptrs], t1 - t0, True, True)
-        else:
-            cnt = torch.empty(n, dtype=torch.int32, device='cuda')
-            lazy = [hasattr(x, 'read_step') for x in series]
-            # file-backed: one step at a time through a pinned buffer; host arrays: groups of steps, the staging buffers of
-            # all the series together within _MEAN_STAGE_BYTES
-            derived = [hasattr(x, 'compute_step') for x in series]     # a derived cell thickness: one step at a time too
-            group = 1 if any(lazy) or any(derived) else max(1, self._MEAN_STAGE_BYTES // (sum(staged) * n * size))
-            bufs = [self._host_array((self.nz, self.ny, self.nx), dt) if z else None for z in lazy]
-            hosts = [_native(x).reshape(self.nt, n) if st and not z and not d else None
-                     for x, st, z, d in zip(series, staged, lazy, derived)]
-            stage = [_lib.DeviceBuffer(min(group, t1 - t0) * n * size) if st else None for st in staged]
-            for t in range(t0, t1, group):
-                k = min(group, t1 - t)
-                cur = []
-                for j in range(len(series)):
-                    if not staged[j]:
-                        cur.append(ptrs[j] + t * n * size)
-                        continue
-                    if derived[j]:      # computed straight into the staging buffer
-                        series[j].compute_step(t, stage[j].ptr)
-                        cur.append(stage[j].ptr)
-                        continue
-                    if lazy[j]:
-                        series[j].read_step(t, out=bufs[j])
-                    check(lib.nf_memcpy_h2d(stage[j].ptr, bufs[j].ctypes.data if lazy[j] else hosts[j][t:t + k].ctypes.data,
-                                            k * n * size))
-                    cur.append(stage[j].ptr)
-                run(cur, k, t == t0, t + k == t1, cnt)
-                check(lib.nf_synchronize())     # the staging buffers are written again by the next group
-            for b in stage:
-                if b is not None:
-                    b.free()
-        check(lib.nf_synchronize())
-        return accs, fill_out
+        return self._time_mean_groups(series, markers, list(range(t0, t1)), nacc, True, False, call)
 
     def _time_mean_array(self, a, markers, rule, t0, t1, table=None):
         """The mean over the steps [t0, t1) of a (nt, nz, ny, nx) array in any of its three homes, by nf_time_mean: a float64
@@ -1693,7 +1510,7 @@ class Field(object):
         if weighted:
             mean.setCellThickness(hu, hv)       # the mean thicknesses: static, float64, in HBM, no markers
         elif e3 is not None:
-            dt = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+            dt = self._uv_dtype
             with numpy.errstate(over='ignore'):
                 marks = [none_if_nan(float(dt.type(m))) if m == m else None for m in (e3['fill'], e3['missing'])]
             mean.setCellThickness(*[self._as_float64(x) for x in e3['arrays']], fill_value=marks[0], missing_value=marks[1])
@@ -1934,23 +1751,21 @@ class Field(object):
             raise RuntimeError(f'ERROR: setDepthSurfaces needs a list of 1 to 8 surfaces, got {count}')
         if not numpy.isfinite(float(top)):
             raise RuntimeError(f'ERROR: setDepthSurfaces: top must be a finite number, got {top!r}')
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        uv_dtype = self._uv_dtype
         markers, items, nts, homes, derived = [], [], [], [], []
         for k, s in enumerate(surfaces):
             if isinstance(s, IsoDepth):
-                item = self._derived_surface(k, s)
+                item = self._derived_surface(k, s, float(top))
                 derived.append(item)
                 for j in range(s.m):
                     items.append(_DerivedPlane(item, j))
                     nts.append(self.nt)
                     homes.append(True)
                 continue
-            if isinstance(s, tuple) and len(s) == 2 and isinstance(s[1], str):
-                var, _, d = open_uvfile(s[0], s[1], with_all=True)
-                for m in d['_markers_' + s[1]]:
-                    if m not in markers:
-                        markers.append(m)
-                s = var
+            s, own = _open_pair(s)
+            for m in own:
+                if m not in markers:
+                    markers.append(m)
             shape = tuple(int(x) for x in s.shape)
             nt_s = 1 if len(shape) == 2 else (shape[0] if len(shape) == 3 else -1)
             if shape[-2:] != (self.ny, self.nx) or nt_s not in (1, self.nt):
@@ -1973,24 +1788,34 @@ class Field(object):
             raise RuntimeError(f'ERROR: setDepthSurfaces: the surfaces have {nts} time steps: all static or all per time step')
         if len(set(homes)) > 1:
             raise RuntimeError('ERROR: setDepthSurfaces: the surfaces must all be host arrays (or files) or all be device arrays')
-        for m in (fill_value, missing_value):
-            if m is not None and float(m) == float(m) and float(m) not in markers:
-                markers.append(float(m))
-        if len(markers) > 2:
-            raise RuntimeError(f'ERROR: the surfaces carry {len(markers)} different _FillValue / missing_value markers '
-                               f'({markers}); the engine masks at most two')
-        if fill_value is None:
-            fill_value = markers[0] if markers else None
-        if missing_value is None:
-            missing_value = markers[1] if len(markers) > 1 else None
-        slot = dict(items=items, nt=nts[0], on_dev=homes[0], step=-1, top=float(top), wrapX=bool(wrapX),
-                    fill=numpy.nan if fill_value is None else float(fill_value),
-                    missing=numpy.nan if missing_value is None else float(missing_value),
-                    buf=[self._host_array((self.ny, self.nx), uv_dtype) if hasattr(s, 'read_step') else None for s in items],
-                    derived=derived)
-        if not derived and not any(b is not None for b in slot['buf']):
+        fill, missing = _two_markers(markers, fill_value, missing_value, 'the surfaces carry', merge=True)
+        slot = dict(items=items, nt=nts[0], on_dev=homes[0], step=-1, stage=None, top=float(top), wrapX=bool(wrapX), fill=fill,
+                    missing=missing, derived=derived)
+        bufs = [self._host_array((self.ny, self.nx), uv_dtype) if hasattr(s, 'read_step') else None for s in items]
+        plane = self.ny * self.nx * uv_dtype.itemsize
+
+        def stage_derived(t):
+            """every IsoDepth computed into its buffer: its planes and the plain device arrays through a virtual (nt, ny, nx)
+            base that the engine dereferences at step t"""
+            for item in derived:
+                item.run(t, item.out.ptr)
+            return [s.item.out.ptr + (s.index - t) * plane if isinstance(s, _DerivedPlane) else _lib.device_pointer(s)
+                    for s in items]
+
+        def stage_files(t):
+            """each file-backed surface into its pinned buffer, handed over through a virtual (nt, ny, nx) base"""
+            for s, buf in zip(items, bufs):
+                if buf is not None:
+                    numpy.copyto(buf, s.read_step(t), casting='same_kind')
+            return [s.ctypes.data if buf is None else buf.ctypes.data - t * plane for s, buf in zip(items, bufs)]
+
+        if derived:
+            slot['stage'] = stage_derived
+        elif any(b is not None for b in bufs):
+            slot['stage'] = stage_files
+        else:
             self._set_surfaces(slot, [_lib.device_pointer(s) if slot['on_dev'] else s.ctypes.data for s in items])
-        check(lib.nf_field_set_depth_surfaces_missing_value(ctypes.byref(self._h), slot['missing']))
+        check(lib.nf_field_set_depth_surfaces_missing_value(ctypes.byref(self._h), missing))
         check(lib.nf_field_set_depth_surfaces_wrap(ctypes.byref(self._h), 1 if wrapX else 0))
         self._surfaces = slot
 
@@ -2000,31 +1825,17 @@ class Field(object):
                                               1 if slot['on_dev'] else 0, slot['fill'], slot['top']))
 
     def _stage_surfaces(self, tIndex):
-        """make step tIndex of the file-backed surfaces the one the engine reads: each into its pinned buffer, handed over
-        through a virtual (nt, ny, nx) base that the engine only dereferences at step tIndex"""
+        """make step tIndex of surfaces that need work at every step (file-backed, derived) the one the engine reads"""
         slot = self._surfaces
-        if slot.get('derived'):
-            if slot['step'] != tIndex:
-                self._stage_derived_surfaces(slot, tIndex)
-            return
-        if slot['step'] == tIndex or not any(b is not None for b in slot['buf']):
-            return
-        ptrs = []
-        for s, buf in zip(slot['items'], slot['buf']):
-            if buf is None:
-                ptrs.append(s.ctypes.data)
-            else:
-                numpy.copyto(buf, s.read_step(tIndex), casting='same_kind')
-                ptrs.append(buf.ctypes.data - tIndex * buf.nbytes)
-        self._set_surfaces(slot, ptrs)
-        slot['step'] = tIndex
+        if slot.get('stage') is not None and slot['step'] != tIndex:
+            self._set_surfaces(slot, slot['stage'](tIndex))
+            slot['step'] = tIndex
 
-    def _derived_surface(self, k, iso):
-        """what computing item k of setDepthSurfaces, an IsoDepth, one step at a time needs: where its tracer (or the thetao and
-        so of its Sigma) and its e3t live, staging buffers for what is not on the device, and the (m, ny, nx) device buffer
-        that receives the planes"""
+    def _derived_surface(self, k, iso, top):
+        """the producer of item k of setDepthSurfaces, an IsoDepth, once its tracer (or the thetao and so of its Sigma) and its
+        e3t are found to fit this Field"""
         from .eos import Sigma
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        uv_dtype = self._uv_dtype
         full = (self.nt, self.nz, self.ny, self.nx)
         sigma = isinstance(iso.tracer, Sigma)
         if not sigma:
@@ -2047,81 +1858,9 @@ class Field(object):
             dt = numpy.dtype(_native_dtype(iso.e3t))
             if dt != uv_dtype:
                 raise RuntimeError(f'ERROR: surface {k}: the e3t of the IsoDepth is {dt.name}, uo/vo are {uv_dtype.name}')
-        # everything fits: the buffers
-        return dict(iso=iso, host=None, sigma=self._sigma_inputs(iso.tracer, f'the Sigma of surface {k}') if sigma else None,
-                    tracer=None if sigma else self._column_source(iso.tracer, self.nt, uv_dtype),
-                    e3t=None if nt_e is None else self._column_source(iso.e3t, nt_e, uv_dtype),
-                    out=_lib.DeviceBuffer(iso.m * self.ny * self.nx * uv_dtype.itemsize))
-
-    def _column_source(self, src, nt_src, uv_dtype):
-        """one 3-D source of a derived surface, nt_src steps of (nz, ny, nx): used in place on the device, else step by step
-        through a pinned buffer into a device buffer (_column_step)"""
-        nbytes = self.nz * self.ny * self.nx * uv_dtype.itemsize
-        one = dict(ptr=_lib.device_pointer(src), nt=nt_src, keep=src, step=-1, nbytes=nbytes)
-        if one['ptr'] is None:
-            one['file'] = hasattr(src, 'read_step')
-            one['rank'] = len(src.shape)
-            one['host'] = None if one['file'] else _native(src).reshape(nt_src, self.nz, self.ny, self.nx)
-            one['pinned'] = self._host_array((self.nz, self.ny, self.nx), uv_dtype)
-            one['dev'] = _lib.DeviceBuffer(nbytes)
-        return one
-
-    def _column_step(self, one, tIndex):
-        """(the device address of step tIndex of a _column_source, whether a staging buffer was written)"""
-        t = tIndex if one['nt'] > 1 else 0
-        if one['ptr'] is not None:
-            return one['ptr'] + t * one['nbytes'], False
-        if one['step'] == t:
-            return one['dev'].ptr, False
-        if not one['file']:
-            numpy.copyto(one['pinned'], one['host'][t])
-        elif one['rank'] == 3:      # a static file variable (nz, ny, nx): its first axis is what read_step walks
-            for z in range(self.nz):
-                numpy.copyto(one['pinned'][z], one['keep'].read_step(z))
-        else:
-            one['keep'].read_step(t, out=one['pinned'])
-        check(lib.nf_memcpy_h2d(one['dev'].ptr, one['pinned'].ctypes.data, one['nbytes']))
-        one['step'] = t
-        return one['dev'].ptr, True
-
-    def _run_iso_depth(self, item, tIndex, top):
-        """the planes of one derived item at step tIndex into its device buffer: its sources of that step on the device (a
-        Sigma through nf_sigma_eos80), then nf_iso_depth on the Field's stream"""
-        iso = item['iso']
-        nan = numpy.nan
-        staged = False
-        if item['sigma'] is not None:
-            self._run_sigma(item['sigma'], self._uv_code, tIndex)
-            tau, marks = item['sigma']['out'].ptr, (nan, nan)
-        else:
-            tau, staged = self._column_step(item['tracer'], tIndex)
-            marks = tuple(nan if x is None else x for x in iso.markers)
-        e3t, emarks, hp = None, (nan, nan), None
-        if item['e3t'] is not None:
-            e3t, wrote = self._column_step(item['e3t'], tIndex)
-            staged = staged or wrote
-            emarks = tuple(nan if x is None else x for x in iso.e3t_markers)
-        else:
-            h = numpy.ascontiguousarray(self.thickness, dtype=numpy.float64)
-            hp = _lib.dptr(h)
-        values = (ctypes.c_double * iso.m)(*iso.values)
-        check(lib.nf_iso_depth(item['out'].ptr, tau, hp, e3t, self.nz, self.ny, self.nx, self._uv_code, marks[0], marks[1],
-                               emarks[0], emarks[1], top, values, iso.m, iso.sense, 1 if iso.relative else 0, iso.zref, nan,
-                               self._stream))
-        if staged:
-            check(lib.nf_synchronize())     # the staging buffers are written again by the next step
-        item['host'] = None
-
-    def _stage_derived_surfaces(self, slot, tIndex):
-        """step tIndex of a set with derived items: every IsoDepth computed into its buffer, and all planes -- derived ones
-        and plain device arrays -- handed over through a virtual (nt, ny, nx) base that the engine dereferences at tIndex"""
-        plane = self.ny * self.nx * (4 if self._uv_code == NF_F32 else 8)
-        for item in slot.get('derived'):
-            self._run_iso_depth(item, tIndex, slot['top'])
-        ptrs = [s.item['out'].ptr + (s.index - tIndex) * plane if isinstance(s, _DerivedPlane) else _lib.device_pointer(s)
-                for s in slot['items']]
-        self._set_surfaces(slot, ptrs)
-        slot['step'] = tIndex
+        if sigma:
+            self._check_sigma(iso.tracer, f'the Sigma of surface {k}')
+        return IsoDepthProducer(self._layout(), iso, nt_e, self.thickness, top)      # everything fits: the buffers
 
     def getDepthSurfaces(self, tIndex):
         """The surfaces of setDepthSurfaces in force at time step tIndex as a host array (m, ny, nx) in the dtype of uo / vo,
@@ -2134,21 +1873,19 @@ class Field(object):
         tIndex = int(tIndex)
         if not 0 <= tIndex < self.nt:
             raise RuntimeError(f'ERROR: getDepthSurfaces: tIndex must be 0 .. {self.nt - 1}, got {tIndex}')
-        uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        uv_dtype = self._uv_dtype
         t = tIndex if slot['nt'] > 1 else 0
         return numpy.stack([numpy.asarray(self._surface_step_host(s, t), dtype=uv_dtype).reshape(self.ny, self.nx)
                             for s in slot['items']])
 
     def _derived_host(self, item, t):
         """the planes (m, ny, nx) of one derived item at step t on the host; the last step asked for is kept"""
-        if item['host'] is None or item['host'][0] != t:
-            slot = self._surfaces
-            self._run_iso_depth(item, t, slot['top'])
-            slot['step'] = -1       # the item's buffer no longer holds the step the engine was given
+        if item.host is None or item.host[0] != t:
+            item.run(t, item.out.ptr)
+            self._surfaces['step'] = -1       # the item's buffer no longer holds the step the engine was given
             check(lib.nf_synchronize())
-            uv_dtype = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
-            item['host'] = (t, item['out'].download((item['iso'].m, self.ny, self.nx), uv_dtype))
-        return item['host'][1]
+            item.host = (t, item.out.download((item.iso.m, self.ny, self.nx), self._uv_dtype))
+        return item.host[1]
 
     def _surface_step_host(self, s, t):
         """step t of one surface as a host array (ny, nx)"""
@@ -2173,7 +1910,7 @@ class Field(object):
         slot = getattr(self, '_surfaces', None)
         if slot is None:
             return
-        dt = numpy.dtype(numpy.float32 if self._uv_code == NF_F32 else numpy.float64)
+        dt = self._uv_dtype
         with numpy.errstate(over='ignore'):
             marks = [float(dt.type(m)) for m in (slot['fill'], slot['missing']) if m == m]
         marks = [m for m in marks if m == m]
