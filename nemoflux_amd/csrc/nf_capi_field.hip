@@ -562,14 +562,14 @@ static int field_integral(nf_field *f, const double *planes, double *scratch, do
                            data_stride, row_stride);
 }
 
-// a synchronous entry point: `step` writes n doubles into the field's own device buffer, which are copied to `host` (nullptr:
-// not copied); the stream is synchronized either way
+// a synchronous entry point: `step` writes n doubles into `buf`, a device buffer of the field's own, which are copied to `host`
+// (nullptr: not copied); the stream is synchronized either way
 template <typename Step>
-static int field_sync(nf_field *f, size_t n, double *host, Step step)
+static int field_sync(nf_field *f, DevArray<double> &buf, size_t n, double *host, Step step)
 {
-    NF_TRY(f->row.reserve(n > 0 ? n : 1));
-    NF_TRY(step(f->row.get()));
-    if (host && n > 0) NF_HIP(hipMemcpyAsync(host, f->row.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
+    NF_TRY(buf.reserve(n > 0 ? n : 1));
+    NF_TRY(step(buf.get()));
+    if (host && n > 0) NF_HIP(hipMemcpyAsync(host, buf.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
     NF_HIP(hipStreamSynchronize(f->stream));
     return NF_OK;
 }
@@ -660,6 +660,40 @@ static int field_tracer_input(nf_field *f, Series &s, long t, Levels lv, TracerI
     return NF_OK;
 }
 
+// The tracer inputs of a product that bins by the class field -- the class tracer when one is set, else the tracer -- at step t:
+// *cls, the class field on the levels cls_lv, and *carry (nullptr: none), the tracer on the levels lv.  cls_lv is lv, or lv with
+// the halo of the remap (field_halo_levels): a host-resident class field is staged with it, an HBM one is read in place.
+static int field_class_inputs(nf_field *f, long t, Levels lv, Levels cls_lv, TracerIn *cls, TracerIn *carry)
+{
+    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : cls_lv, cls));
+    if (carry) *carry = *cls;                                                  // the tracer is carried ...
+    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, cls_lv, cls));   // ... and binned by the class tracer
+    return NF_OK;
+}
+
+// the levels that the remap kernels read the class field on: one above and one below the owned ones
+static Levels field_halo_levels(const nf_field *f, Levels lv) { return {std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)}; }
+
+// The window knob and the run sums of a windowed product (class, remap, depth, surface) in the arguments *a: the field's class
+// scratch, grown to the window per record.
+template <typename Args>
+static int field_class_window(nf_field *f, Args *a)
+{
+    a->window = g_class_window;
+    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * a->window));
+    a->scratch = f->class_scratch.get();
+    a->scratch_len = f->class_scratch.size();
+    return NF_OK;
+}
+
+// A product that is written whole, `doubles` of it at rows_dev, by a kernel that stores the owned levels alone: zeros for the
+// others, in every block, when this rank owns a part of the step (or nothing of it)
+static int field_zero_unowned_levels(nf_field *f, Levels lv, double *rows_dev, size_t doubles)
+{
+    if (lv.z0 > 0 || lv.z1 < f->nz) NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * doubles, f->stream));
+    return NF_OK;
+}
+
 // Depth-resolved rows of step t on the field's stream: prof_dev (nz, row_length), row z = the flux carried by level z alone.
 // Reads the raw fields and the records; leaves the resident planes, |.| arrays, running max, version and a captured pass
 // alone.  Levels this rank does not own get zeros.  The caller has checked field_ready (with the weights).
@@ -699,9 +733,7 @@ static int field_area_async(nf_field *f, long t, double *rows_dev)
     Levels lv;
     NF_TRY(field_raw_step_begin(f, "compute_area_profile", t, 1, rows_dev, 2 * (size_t)f->nz, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
-    const size_t rowlen = field_row_length(f);
-    if (lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in both blocks
-        NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * 2 * (size_t)f->nz, f->stream));
+    NF_TRY(field_zero_unowned_levels(f, lv, rows_dev, (size_t)field_row_length(f) * 2 * (size_t)f->nz));   // in both blocks
     NF_TRY(f->area_scratch.reserve((size_t)f->ws.nrec * 2 * area_chunk_now(f->uv.dtype)));
     AreaArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
@@ -724,9 +756,7 @@ static int field_gross_async(nf_field *f, long t, bool carry, double *rows_dev)
     Levels lv;
     NF_TRY(field_raw_step_begin(f, "compute_gross_profile", t, carry ? 1 : 0, rows_dev, 2 * (size_t)f->nz, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
-    const size_t rowlen = field_row_length(f);
-    if (lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in both blocks
-        NF_HIP(hipMemsetAsync(rows_dev, 0, sizeof(double) * rowlen * 2 * (size_t)f->nz, f->stream));
+    NF_TRY(field_zero_unowned_levels(f, lv, rows_dev, (size_t)field_row_length(f) * 2 * (size_t)f->nz));   // in both blocks
     NF_TRY(f->gross_scratch.reserve((size_t)f->ws.nrec * 2 * gross_chunk_now(f->uv.dtype, carry, f->e3.p[0] != nullptr)));
     GrossArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
@@ -751,8 +781,7 @@ static int field_crossings_async(nf_field *f, long t, bool carry, double *out_de
     const size_t nrec = (size_t)f->ws.nrec, nplanes = carry ? 4 : 2;
     if (nrec == 0) return NF_OK;
     const Levels lv = field_levels(f, t);
-    if (lv.z1 <= lv.z0 || lv.z0 > 0 || lv.z1 < f->nz)   // the levels that are not owned, in every plane
-        NF_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * nplanes * (size_t)f->nz * nrec, f->stream));
+    NF_TRY(field_zero_unowned_levels(f, lv, out_dev, nplanes * (size_t)f->nz * nrec));   // in every plane
     if (lv.z1 <= lv.z0) return NF_OK;
     CrossingArgs a;
     NF_TRY(field_step_input(f, t, lv, &a.in));
@@ -785,7 +814,7 @@ static int field_tracer_step_async(nf_field *f, long t, double *row_dev)
 }
 
 // the calls of the class transport need a tracer and class edges: checked before a device is needed
-static int field_class_ready(const nf_field *f, const char *what)
+static int field_class_ready(const nf_field *f, const char *what, bool /*carry*/ = false)
 {
     NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, std::string(what) + ": set_tracer first");
     NF_REQUIRE(!f->class_edges.host.empty(), NF_ERR_STATE, std::string(what) + ": set_class_edges first");
@@ -807,20 +836,13 @@ static int field_class_step_async(nf_field *f, long t, double *rows_dev, bool ca
     NF_TRY(field_raw_step_begin(f, what, t, 2, rows_dev, (size_t)nedges + 2, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
-    const int window = g_class_window;
-    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
-    const Levels cls_lv = remap ? Levels{std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)} : lv;
     ClassArgs a;
+    NF_TRY(field_class_window(f, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : cls_lv, &a.cls));
-    if (carry) a.carry = a.cls;                                                     // the tracer is carried ...
-    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, cls_lv, &a.cls));   // ... and binned by the class tracer
+    NF_TRY(field_class_inputs(f, t, lv, remap ? field_halo_levels(f, lv) : lv, &a.cls, carry ? &a.carry : nullptr));
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
-    a.window = window;
     a.tr = field_transects(f);
-    a.scratch = f->class_scratch.get();
-    a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
     a.remap_nz = (int)f->nz;   // read by launch_class_remap only
     return remap ? launch_class_remap(a, f->stream) : launch_class_transport(a, f->stream);
@@ -838,19 +860,15 @@ static int field_depth_step_async(nf_field *f, long t, bool carry, double *rows_
     NF_TRY(field_raw_step_begin(f, "compute_depth_transport", t, carry ? 1 : 0, rows_dev, (size_t)nedges + 2, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->depth_edges.upload((size_t)kMaxClassEdges, f->stream));
-    const int window = g_class_window;
-    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
     DepthArgs a;
+    NF_TRY(field_class_window(f, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
     if (carry) NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
     NF_TRY(field_cell_thick(f, t, Levels{0, lv.z1}, &a.th));
     a.edges = f->depth_edges.dev.get();
     a.nedges = nedges;
     a.top = f->depth_top;
-    a.window = window;
     a.tr = field_transects(f);
-    a.scratch = f->class_scratch.get();
-    a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
     return launch_depth_transport(a, f->stream);
 }
@@ -865,9 +883,8 @@ static int field_surface_step_async(nf_field *f, long t, bool carry, double *row
     NF_TRY(field_raw_step_begin(f, "compute_surface_transport", t, carry ? 1 : 0, rows_dev, (size_t)sf.m + 2, &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(field_matches_uv(f, sf.dtype, sf.nt, "compute_surface_transport", "depth surfaces", kStaticOk));
-    const int window = g_class_window;
-    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
     SurfaceArgs a;
+    NF_TRY(field_class_window(f, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
     if (carry) NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.t));
     NF_TRY(field_cell_thick(f, t, Levels{0, lv.z1}, &a.th));
@@ -888,16 +905,13 @@ static int field_surface_step_async(nf_field *f, long t, bool carry, double *row
     a.sf.fill2 = sf.fill2;
     a.sf.wrap_x = sf.wrap;
     a.top = sf.top;
-    a.window = window;
     a.tr = field_transects(f);
-    a.scratch = f->class_scratch.get();
-    a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
     return launch_surface_transport(a, f->stream);
 }
 
 // the calls of the joint class transport need both tracers and the joint edges: checked before a device is needed
-static int field_joint_ready(const nf_field *f, const char *what)
+static int field_joint_ready(const nf_field *f, const char *what, bool /*carry*/ = false)
 {
     NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, std::string(what) + ": set_tracer first");
     NF_REQUIRE(f->sig.p[0], NF_ERR_STATE, std::string(what) + ": set_class_tracer first");
@@ -981,9 +995,7 @@ static int field_gross_class_async(nf_field *f, long t, bool carry, double *rows
     GrossClassArgs a;
     NF_TRY(field_joint_buffers(f, "compute_gross_class_transport", kJointEntryBytes, lv, nrows, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.cls));
-    if (carry) a.carry = a.cls;                                                    // the tracer is carried ...
-    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.cls));   // ... and binned by the class tracer
+    NF_TRY(field_class_inputs(f, t, lv, lv, &a.cls, carry ? &a.carry : nullptr));
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
@@ -1006,21 +1018,14 @@ static int field_gross_remap_async(nf_field *f, long t, bool carry, double *rows
     NF_TRY(field_raw_step_begin(f, "compute_gross_class_remap", t, 2, rows_dev, 2 * ((size_t)nedges + 2), &lv));
     if (lv.z1 <= lv.z0) return NF_OK;
     NF_TRY(f->class_edges.upload((size_t)kMaxClassEdges, f->stream));
-    const int window = g_class_window;
-    NF_TRY(f->class_scratch.reserve((size_t)f->ws.nrec * window));
-    const Levels cls_lv{std::max(lv.z0 - 1, 0), std::min(lv.z1 + 1, (int)f->nz)};
     GrossRemapArgs a;
+    NF_TRY(field_class_window(f, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, f->tau, t, f->sig.p[0] ? lv : cls_lv, &a.cls));
-    if (carry) a.carry = a.cls;                                                     // the tracer is carried ...
-    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, cls_lv, &a.cls));   // ... and binned by the class tracer
+    NF_TRY(field_class_inputs(f, t, lv, field_halo_levels(f, lv), &a.cls, carry ? &a.carry : nullptr));
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
-    a.window = window;
     a.tr = field_transects(f);
-    a.scratch = f->class_scratch.get();
-    a.scratch_len = f->class_scratch.size();
     a.rows = rows_dev;
     a.nz = (int)f->nz;
     return launch_gross_class_remap(a, f->stream);
@@ -1044,9 +1049,7 @@ static int field_class_area_async(nf_field *f, long t, double *rows_dev)
     ClassAreaArgs a;
     NF_TRY(field_joint_buffers(f, "compute_class_area", kClassAreaEntryBytes, lv, nrows, &a));
     NF_TRY(field_step_input(f, t, lv, &a.in));
-    NF_TRY(field_tracer_input(f, f->tau, t, lv, &a.carry));
-    a.cls = a.carry;                                                               // the tracer is carried ...
-    if (f->sig.p[0]) NF_TRY(field_tracer_input(f, f->sig, t, lv, &a.cls));   // ... and binned by the class tracer when one is set
+    NF_TRY(field_class_inputs(f, t, lv, lv, &a.cls, &a.carry));   // the tracer is the carried one either way
     NF_TRY(field_cell_thick(f, t, lv, &a.th));
     a.edges = f->class_edges.dev.get();
     a.nedges = nedges;
@@ -1054,6 +1057,123 @@ static int field_class_area_async(nf_field *f, long t, double *rows_dev)
     a.rows = rows_dev;
     return launch_class_area(a, f->stream);
 }
+
+// ---- the per-step products: what differs between them, stated once, and the one path of their entry points -------------------
+// A per-step product is a result of one time step computed from the raw fields and the records, with two entry points: the
+// synchronous one (rows to the host) and `_async` (rows in HBM, on the field's stream).  `what` is the symbol called.
+struct Product {
+    int (*ready)(const nf_field *f, const char *what, bool carry);    // the checks of the state: before a device is asked for
+    size_t (*doubles)(const nf_field *f, bool carry);                 // the size of the result
+    int (*step)(nf_field *f, long t, bool carry, double *rows_dev);   // step t on the field's stream
+    DevArray<double> nf_field::*buffer = &nf_field::row;              // the buffer of the handle that the synchronous form stages through
+    bool empty_runs = false;   // the synchronous form runs the step of an empty result too (the crossings: kept as it was)
+};
+
+static int field_product(nf_field **self, const Product &p, const char *what, long t, int carry, double *rows, bool sync)
+{
+    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, std::string(what) + ": null argument");
+    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, std::string(what) + ": carry must be 0 or 1");
+    nf_field *f = *self;
+    NF_TRY(p.ready(f, what, carry != 0));
+    NF_NEED_DEVICE();
+    if (!sync) return p.step(f, t, carry != 0, rows);
+    const size_t n = p.doubles(f, carry != 0);
+    if (n == 0 && !p.empty_runs) return NF_OK;
+    return field_sync(f, f->*p.buffer, n, rows, [&](double *dev) { return p.step(f, t, carry != 0, dev); });
+}
+
+// the carried form of a product needs a tracer
+static int field_carry_ready(const nf_field *f, const char *what, bool carry)
+{
+    NF_REQUIRE(!carry || f->tau.p[0], NF_ERR_STATE, std::string(what) + ": set_tracer first");
+    return NF_OK;
+}
+
+// The area profile, the gross profile and the crossings ask for a device BEFORE they look at the grid, and name themselves
+// without the nf_field_ prefix there: without a GPU a handle that is not ready answers NF_ERR_NO_DEVICE, not NF_ERR_STATE.
+// Nobody chose that; it is kept as it was ("adding a product").
+static int field_ready_on_device(const nf_field *f, const char *short_name)
+{
+    NF_NEED_DEVICE();
+    return field_ready(f, short_name, true);
+}
+
+// the net class forms (step rule, carried, remap) take no cell thickness
+static int field_net_class_ready(const nf_field *f, const char *what, bool)
+{
+    NF_TRY(field_class_ready(f, what));
+    return field_no_cell_thick(f, what);
+}
+
+static size_t field_rows(const nf_field *f, size_t nrows) { return nrows * (size_t)field_row_length(f); }
+static size_t field_class_rows(const nf_field *f, bool) { return field_rows(f, f->class_edges.host.size() + 2); }
+static size_t field_two_class_rows(const nf_field *f, bool) { return 2 * field_class_rows(f, false); }
+
+// (the two profiles name themselves without the prefix in the message of field_ready: kept as it was)
+static const Product kProfile = {
+    [](const nf_field *f, const char *, bool) { return field_ready(f, "compute_profile", true); },
+    [](const nf_field *f, bool) { return field_rows(f, (size_t)f->nz); },
+    [](nf_field *f, long t, bool, double *rows) { return field_profile_async(f, t, rows); }};
+static const Product kTracerProfile = {
+    [](const nf_field *f, const char *what, bool) {
+        NF_TRY(field_carry_ready(f, what, true));
+        NF_TRY(field_no_cell_thick(f, what));
+        return field_ready(f, "compute_tracer_profile", true);
+    },
+    kProfile.doubles,
+    [](nf_field *f, long t, bool, double *rows) { return field_profile_async(f, t, rows, true); }};
+static const Product kAreaProfile = {
+    [](const nf_field *f, const char *what, bool) {
+        NF_TRY(field_carry_ready(f, what, true));
+        return field_ready_on_device(f, "compute_area_profile");
+    },
+    [](const nf_field *f, bool) { return field_rows(f, 2 * (size_t)f->nz); },
+    [](nf_field *f, long t, bool, double *rows) { return field_area_async(f, t, rows); }};
+static const Product kGrossProfile = {
+    [](const nf_field *f, const char *what, bool carry) {
+        NF_TRY(field_carry_ready(f, what, carry));
+        return field_ready_on_device(f, "compute_gross_profile");
+    },
+    kAreaProfile.doubles,
+    [](nf_field *f, long t, bool carry, double *rows) { return field_gross_async(f, t, carry, rows); }};
+static const Product kCrossings = {
+    [](const nf_field *f, const char *what, bool carry) {
+        NF_TRY(field_carry_ready(f, what, carry));
+        return field_ready_on_device(f, "compute_crossings");
+    },
+    [](const nf_field *f, bool carry) { return (carry ? 4 : 2) * (size_t)f->nz * (size_t)f->ws.nrec; },
+    [](nf_field *f, long t, bool carry, double *out) { return field_crossings_async(f, t, carry, out); },
+    &nf_field::crossings, true};
+static const Product kClassTransport = {
+    field_net_class_ready, field_class_rows,
+    [](nf_field *f, long t, bool, double *rows) { return field_class_step_async(f, t, rows); }};
+static const Product kClassTracerTransport = {
+    field_net_class_ready, field_class_rows,
+    [](nf_field *f, long t, bool, double *rows) { return field_class_step_async(f, t, rows, true); }};
+static const Product kClassRemap = {
+    field_net_class_ready, field_class_rows,
+    [](nf_field *f, long t, bool carry, double *rows) { return field_class_step_async(f, t, rows, carry, true); }};
+static const Product kDepthTransport = {
+    [](const nf_field *f, const char *what, bool carry) {
+        NF_REQUIRE(!f->depth_edges.host.empty(), NF_ERR_STATE, std::string(what) + ": set_depth_edges first");
+        NF_TRY(field_carry_ready(f, what, carry));
+        return field_ready(f, what, true);
+    },
+    [](const nf_field *f, bool) { return field_rows(f, f->depth_edges.host.size() + 2); }, field_depth_step_async};
+static const Product kSurfaceTransport = {
+    [](const nf_field *f, const char *what, bool carry) {
+        NF_REQUIRE(f->surf.m > 0, NF_ERR_STATE, std::string(what) + ": set_depth_surfaces first");
+        NF_TRY(field_carry_ready(f, what, carry));
+        return field_ready(f, what, true);
+    },
+    [](const nf_field *f, bool) { return field_rows(f, (size_t)f->surf.m + 2); }, field_surface_step_async};
+static const Product kJointClassTransport = {
+    field_joint_ready, [](const nf_field *f, bool) { return field_rows(f, field_joint_rows(f)); }, field_joint_step_async};
+static const Product kGrossClassTransport = {field_class_ready, field_two_class_rows, field_gross_class_async};
+static const Product kGrossClassRemap = {field_class_ready, field_two_class_rows, field_gross_remap_async};
+static const Product kClassArea = {
+    field_class_ready, field_two_class_rows,
+    [](nf_field *f, long t, bool, double *rows) { return field_class_area_async(f, t, rows); }};
 
 // steps t and t+1, both owned whole: flux t into geo.pair[0], flux t+1 into the resident planes (which therefore hold the later
 // step, as after two single steps), then ONE reduction of both; rows t and t+1 are contiguous in rows_dev.  last: t+1 is the
@@ -1569,7 +1689,7 @@ try {
     NF_NEED_DEVICE();
     nf_field *f = *self;
     const size_t n = f->weights_built ? field_row_length(f) : 0;   // no weights: the step alone, no row
-    return field_sync(f, n, row_host, [&](double *row) { return field_step_async(f, tIndex, n > 0 ? row : nullptr); });
+    return field_sync(f, f->row, n, row_host, [&](double *row) { return field_step_async(f, tIndex, n > 0 ? row : nullptr); });
 }
 NF_API_CATCH
 
@@ -1619,23 +1739,13 @@ NF_API_CATCH
 
 int nf_field_compute_profile(nf_field **self, long tIndex, double *prof_host)
 try {
-    NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_profile: null argument");
-    nf_field *f = *self;
-    NF_TRY(field_ready(f, "compute_profile", true));
-    NF_NEED_DEVICE();
-    const size_t n = (size_t)f->nz * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, prof_host, [&](double *prof) { return field_profile_async(f, tIndex, prof); });
+    return field_product(self, kProfile, __func__, tIndex, 0, prof_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_profile_async(nf_field **self, long tIndex, double *prof_dev)
 try {
-    NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_profile_async: null argument");
-    nf_field *f = *self;
-    NF_TRY(field_ready(f, "compute_profile", true));
-    NF_NEED_DEVICE();
-    return field_profile_async(f, tIndex, prof_dev);
+    return field_product(self, kProfile, __func__, tIndex, 0, prof_dev, false);
 }
 NF_API_CATCH
 
@@ -1687,7 +1797,8 @@ try {
     nf_field *f = *self;
     NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_flux: set_tracer first");
     NF_NEED_DEVICE();
-    return field_sync(f, field_row_length(f), row_host, [&](double *row) { return field_tracer_step_async(f, tIndex, row); });
+    return field_sync(f, f->row, field_row_length(f), row_host,
+                      [&](double *row) { return field_tracer_step_async(f, tIndex, row); });
 }
 NF_API_CATCH
 
@@ -1731,51 +1842,25 @@ NF_API_CATCH
 
 int nf_field_compute_class_transport(nf_field **self, long tIndex, double *rows_host)
 try {
-    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_transport: null argument");
-    nf_field *f = *self;
-    NF_TRY(field_class_ready(f, "nf_field_compute_class_transport"));
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport"));
-    NF_NEED_DEVICE();
-    const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows); });
+    return field_product(self, kClassTransport, __func__, tIndex, 0, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_class_transport_async(nf_field **self, long tIndex, double *rows_dev)
 try {
-    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_transport_async: null argument");
-    nf_field *f = *self;
-    NF_TRY(field_class_ready(f, "nf_field_compute_class_transport_async"));
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_transport_async"));
-    NF_NEED_DEVICE();
-    return field_class_step_async(f, tIndex, rows_dev);
+    return field_product(self, kClassTransport, __func__, tIndex, 0, rows_dev, false);
 }
 NF_API_CATCH
 
 int nf_field_compute_class_remap(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_remap: null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_class_remap: carry must be 0 or 1");
-    nf_field *f = *self;
-    NF_TRY(field_class_ready(f, "nf_field_compute_class_remap"));
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_remap"));
-    NF_NEED_DEVICE();
-    const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows, carry != 0, true); });
+    return field_product(self, kClassRemap, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_remap_async: null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_class_remap_async: carry must be 0 or 1");
-    nf_field *f = *self;
-    NF_TRY(field_class_ready(f, "nf_field_compute_class_remap_async"));
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_remap_async"));
-    NF_NEED_DEVICE();
-    return field_class_step_async(f, tIndex, rows_dev, carry != 0, true);
+    return field_product(self, kClassRemap, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
@@ -1792,34 +1877,15 @@ try {
 }
 NF_API_CATCH
 
-// the checks of the two depth calls that need no device: arguments, then the depth edges and the tracer of the carried form
-static int field_depth_args(nf_field **self, int carry, const void *rows, const char *what)
-{
-    const std::string w(what);
-    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
-    NF_REQUIRE(!(*self)->depth_edges.host.empty(), NF_ERR_STATE, w + ": set_depth_edges first");
-    NF_REQUIRE(!carry || (*self)->tau.p[0], NF_ERR_STATE, w + ": set_tracer first");
-    return field_ready(*self, what, true);
-}
-
 int nf_field_compute_depth_transport(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_TRY(field_depth_args(self, carry, rows_host, "nf_field_compute_depth_transport"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    const size_t n = (f->depth_edges.host.size() + 2) * (size_t)field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_depth_step_async(f, tIndex, carry != 0, rows); });
+    return field_product(self, kDepthTransport, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_depth_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_TRY(field_depth_args(self, carry, rows_dev, "nf_field_compute_depth_transport_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    return field_depth_step_async(f, tIndex, carry != 0, rows_dev);
+    return field_product(self, kDepthTransport, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
@@ -1882,34 +1948,15 @@ try {
 }
 NF_API_CATCH
 
-// the checks of the two surface calls that need no device: arguments, then the surfaces and the tracer of the carried form
-static int field_surface_args(nf_field **self, int carry, const void *rows, const char *what)
-{
-    const std::string w(what);
-    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
-    NF_REQUIRE((*self)->surf.m > 0, NF_ERR_STATE, w + ": set_depth_surfaces first");
-    NF_REQUIRE(!carry || (*self)->tau.p[0], NF_ERR_STATE, w + ": set_tracer first");
-    return field_ready(*self, what, true);
-}
-
 int nf_field_compute_surface_transport(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_TRY(field_surface_args(self, carry, rows_host, "nf_field_compute_surface_transport"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    const size_t n = ((size_t)f->surf.m + 2) * (size_t)field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_surface_step_async(f, tIndex, carry != 0, rows); });
+    return field_product(self, kSurfaceTransport, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_surface_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_TRY(field_surface_args(self, carry, rows_dev, "nf_field_compute_surface_transport_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    return field_surface_step_async(f, tIndex, carry != 0, rows_dev);
+    return field_product(self, kSurfaceTransport, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
@@ -1942,107 +1989,49 @@ NF_API_CATCH
 
 int nf_field_compute_joint_class_transport(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_joint_class_transport: null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_joint_class_transport: carry must be 0 or 1");
-    nf_field *f = *self;
-    NF_TRY(field_joint_ready(f, "nf_field_compute_joint_class_transport"));
-    NF_NEED_DEVICE();
-    const size_t n = field_joint_rows(f) * (size_t)field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_joint_step_async(f, tIndex, carry != 0, rows); });
+    return field_product(self, kJointClassTransport, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_joint_class_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_joint_class_transport_async: null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, "nf_field_compute_joint_class_transport_async: carry must be 0 or 1");
-    nf_field *f = *self;
-    NF_TRY(field_joint_ready(f, "nf_field_compute_joint_class_transport_async"));
-    NF_NEED_DEVICE();
-    return field_joint_step_async(f, tIndex, carry != 0, rows_dev);
+    return field_product(self, kJointClassTransport, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
 int nf_field_compute_tracer_profile(nf_field **self, long tIndex, double *prof_host)
 try {
-    NF_REQUIRE(self && *self && prof_host, NF_ERR_ARG, "nf_field_compute_tracer_profile: null argument");
-    nf_field *f = *self;
-    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_profile: set_tracer first");
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_tracer_profile"));
-    NF_TRY(field_ready(f, "compute_tracer_profile", true));
-    NF_NEED_DEVICE();
-    const size_t n = (size_t)f->nz * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, prof_host, [&](double *prof) { return field_profile_async(f, tIndex, prof, true); });
+    return field_product(self, kTracerProfile, __func__, tIndex, 0, prof_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_tracer_profile_async(nf_field **self, long tIndex, double *prof_dev)
 try {
-    NF_REQUIRE(self && *self && prof_dev, NF_ERR_ARG, "nf_field_compute_tracer_profile_async: null argument");
-    nf_field *f = *self;
-    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_tracer_profile_async: set_tracer first");
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_tracer_profile_async"));
-    NF_TRY(field_ready(f, "compute_tracer_profile", true));
-    NF_NEED_DEVICE();
-    return field_profile_async(f, tIndex, prof_dev, true);
+    return field_product(self, kTracerProfile, __func__, tIndex, 0, prof_dev, false);
 }
 NF_API_CATCH
 
 int nf_field_compute_area_profile(nf_field **self, long tIndex, double *rows_host)
 try {
-    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_area_profile: null argument");
-    nf_field *f = *self;
-    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_area_profile: set_tracer first");
-    NF_NEED_DEVICE();
-    NF_TRY(field_ready(f, "compute_area_profile", true));
-    const size_t n = 2 * (size_t)f->nz * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_area_async(f, tIndex, rows); });
+    return field_product(self, kAreaProfile, __func__, tIndex, 0, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_area_profile_async(nf_field **self, long tIndex, double *rows_dev)
 try {
-    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_area_profile_async: null argument");
-    nf_field *f = *self;
-    NF_REQUIRE(f->tau.p[0], NF_ERR_STATE, "nf_field_compute_area_profile_async: set_tracer first");
-    NF_NEED_DEVICE();
-    NF_TRY(field_ready(f, "compute_area_profile", true));
-    return field_area_async(f, tIndex, rows_dev);
+    return field_product(self, kAreaProfile, __func__, tIndex, 0, rows_dev, false);
 }
 NF_API_CATCH
 
-// the checks of the two gross calls that need no device: arguments, then the tracer of the carried form
-static int field_gross_args(nf_field **self, int carry, const void *rows, const char *what)
-{
-    const std::string w(what);
-    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
-    NF_REQUIRE(!carry || (*self)->tau.p[0], NF_ERR_STATE, w + ": set_tracer first");
-    return NF_OK;
-}
-
 int nf_field_compute_gross_profile(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_TRY(field_gross_args(self, carry, rows_host, "nf_field_compute_gross_profile"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    NF_TRY(field_ready(f, "compute_gross_profile", true));
-    const size_t n = 2 * (size_t)f->nz * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_gross_async(f, tIndex, carry != 0, rows); });
+    return field_product(self, kGrossProfile, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_gross_profile_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_TRY(field_gross_args(self, carry, rows_dev, "nf_field_compute_gross_profile_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    NF_TRY(field_ready(f, "compute_gross_profile", true));
-    return field_gross_async(f, tIndex, carry != 0, rows_dev);
+    return field_product(self, kGrossProfile, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
@@ -2077,102 +2066,49 @@ NF_API_CATCH
 
 int nf_field_compute_crossings(nf_field **self, long tIndex, int carry, double *out_host)
 try {
-    NF_TRY(field_gross_args(self, carry, out_host, "nf_field_compute_crossings"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    NF_TRY(field_ready(f, "compute_crossings", true));
-    const size_t n = (carry ? 4 : 2) * (size_t)f->nz * (size_t)f->ws.nrec;
-    NF_TRY(f->crossings.reserve(n > 0 ? n : 1));
-    NF_TRY(field_crossings_async(f, tIndex, carry != 0, f->crossings.get()));
-    if (n > 0) NF_HIP(hipMemcpyAsync(out_host, f->crossings.get(), sizeof(double) * n, hipMemcpyDeviceToHost, f->stream));
-    NF_HIP(hipStreamSynchronize(f->stream));
-    return NF_OK;
+    return field_product(self, kCrossings, __func__, tIndex, carry, out_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_crossings_async(nf_field **self, long tIndex, int carry, double *out_dev)
 try {
-    NF_TRY(field_gross_args(self, carry, out_dev, "nf_field_compute_crossings_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    NF_TRY(field_ready(f, "compute_crossings", true));
-    return field_crossings_async(f, tIndex, carry != 0, out_dev);
+    return field_product(self, kCrossings, __func__, tIndex, carry, out_dev, false);
 }
 NF_API_CATCH
 
-// the checks of the gross class calls (step rule and remap) that need no device: arguments, then the tracer and the class edges
-static int field_gross_class_args(nf_field **self, int carry, const void *rows, const char *what)
-{
-    const std::string w(what);
-    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, w + ": null argument");
-    NF_REQUIRE(carry == 0 || carry == 1, NF_ERR_ARG, w + ": carry must be 0 or 1");
-    return field_class_ready(*self, what);
-}
-
 int nf_field_compute_gross_class_transport(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_TRY(field_gross_class_args(self, carry, rows_host, "nf_field_compute_gross_class_transport"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    const size_t n = 2 * (f->class_edges.host.size() + 2) * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_gross_class_async(f, tIndex, carry != 0, rows); });
+    return field_product(self, kGrossClassTransport, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_gross_class_transport_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_TRY(field_gross_class_args(self, carry, rows_dev, "nf_field_compute_gross_class_transport_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    return field_gross_class_async(f, tIndex, carry != 0, rows_dev);
+    return field_product(self, kGrossClassTransport, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
 int nf_field_compute_gross_class_remap(nf_field **self, long tIndex, int carry, double *rows_host)
 try {
-    NF_TRY(field_gross_class_args(self, carry, rows_host, "nf_field_compute_gross_class_remap"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    const size_t n = 2 * (f->class_edges.host.size() + 2) * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_gross_remap_async(f, tIndex, carry != 0, rows); });
+    return field_product(self, kGrossClassRemap, __func__, tIndex, carry, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_gross_class_remap_async(nf_field **self, long tIndex, int carry, double *rows_dev)
 try {
-    NF_TRY(field_gross_class_args(self, carry, rows_dev, "nf_field_compute_gross_class_remap_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    return field_gross_remap_async(f, tIndex, carry != 0, rows_dev);
+    return field_product(self, kGrossClassRemap, __func__, tIndex, carry, rows_dev, false);
 }
 NF_API_CATCH
 
-// the checks of the two class area calls that need no device: arguments, then the tracer and the class edges
-static int field_class_area_args(nf_field **self, const void *rows, const char *what)
-{
-    NF_REQUIRE(self && *self && rows, NF_ERR_ARG, std::string(what) + ": null argument");
-    return field_class_ready(*self, what);
-}
-
 int nf_field_compute_class_area(nf_field **self, long tIndex, double *rows_host)
 try {
-    NF_TRY(field_class_area_args(self, rows_host, "nf_field_compute_class_area"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    const size_t n = 2 * (f->class_edges.host.size() + 2) * field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_area_async(f, tIndex, rows); });
+    return field_product(self, kClassArea, __func__, tIndex, 0, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_class_area_async(nf_field **self, long tIndex, double *rows_dev)
 try {
-    NF_TRY(field_class_area_args(self, rows_dev, "nf_field_compute_class_area_async"));
-    nf_field *f = *self;
-    NF_NEED_DEVICE();
-    return field_class_area_async(f, tIndex, rows_dev);
+    return field_product(self, kClassArea, __func__, tIndex, 0, rows_dev, false);
 }
 NF_API_CATCH
 
@@ -2266,25 +2202,13 @@ NF_API_CATCH
 
 int nf_field_compute_class_tracer_transport(nf_field **self, long tIndex, double *rows_host)
 try {
-    NF_REQUIRE(self && *self && rows_host, NF_ERR_ARG, "nf_field_compute_class_tracer_transport: null argument");
-    nf_field *f = *self;
-    NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport"));
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_tracer_transport"));
-    NF_NEED_DEVICE();
-    const size_t n = (f->class_edges.host.size() + 2) * (size_t)field_row_length(f);
-    if (n == 0) return NF_OK;
-    return field_sync(f, n, rows_host, [&](double *rows) { return field_class_step_async(f, tIndex, rows, true); });
+    return field_product(self, kClassTracerTransport, __func__, tIndex, 0, rows_host, true);
 }
 NF_API_CATCH
 
 int nf_field_compute_class_tracer_transport_async(nf_field **self, long tIndex, double *rows_dev)
 try {
-    NF_REQUIRE(self && *self && rows_dev, NF_ERR_ARG, "nf_field_compute_class_tracer_transport_async: null argument");
-    nf_field *f = *self;
-    NF_TRY(field_class_ready(f, "nf_field_compute_class_tracer_transport_async"));
-    NF_TRY(field_no_cell_thick(f, "nf_field_compute_class_tracer_transport_async"));
-    NF_NEED_DEVICE();
-    return field_class_step_async(f, tIndex, rows_dev, true);
+    return field_product(self, kClassTracerTransport, __func__, tIndex, 0, rows_dev, false);
 }
 NF_API_CATCH
 

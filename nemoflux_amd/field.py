@@ -583,16 +583,39 @@ class Field(object):
         """columns of the arrays that hold raw rows: row_length, but never 0 (a Field without transects)"""
         return max(self._rowlen, 1)
 
-    def _rows_out(self, out, nrows):
-        """The `out=` tensor of the calls that leave raw rows in HBM: (nrows, row_length) float64, contiguous, on the GPU -- the
+    def _rows_out(self, out, shape):
+        """The `out=` tensor of the calls that leave raw rows in HBM: float64 of this shape, contiguous, on the GPU -- the
         library writes that many doubles through its pointer.  A new one when out is None."""
         import torch
-        shape = (nrows, self._row_width)
         if out is None:
             return torch.empty(shape, dtype=torch.float64, device='cuda')
         if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
             raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
         return out
+
+    def _product(self, stem, tIndex, front, carry=None, tracer=True, surfaces=False, width=None, out=None, prefetch_next=None):
+        """The host rows, float64 of shape `front` + (row width,), of a per-step product of the C ABI for time step tIndex: the
+        call `stem`, or `stem`_async into the tensor `out` when one is given.  Stages step tIndex first: uo / vo and the cell
+        thickness, then the surfaces (surfaces=True), then the tracers (tracer=True).  carry (None: the call takes none) is
+        passed as 0 / 1.  width: a function that gives the last axis where it is not the row width, called once the step is
+        staged (the crossings); a result without elements makes no call."""
+        tIndex = int(tIndex)
+        self._stage(tIndex, prefetch_next)
+        if surfaces:
+            self._stage_surfaces(tIndex)
+        if tracer:
+            self._stage_tracer(tIndex)
+        shape = tuple(front) + (self._row_width if width is None else width(),)
+        args = (ctypes.byref(self._h), tIndex) + (() if carry is None else (1 if carry else 0,))
+        if out is not None:
+            out = self._rows_out(out, shape)
+            if out.numel():
+                check(getattr(lib, stem + '_async')(*args, ctypes.c_void_p(out.data_ptr())))
+            return out.cpu().numpy()
+        rows = numpy.zeros(shape, numpy.float64)
+        if rows.size:
+            check(getattr(lib, stem)(*args, _lib.dptr(rows)))
+        return rows
 
     def _split_rows(self, rows):
         """(transect totals, per-segment sums) of rows laid out [segments | transects] along their last axis."""
@@ -609,7 +632,7 @@ class Field(object):
         import torch
         lazy = self._lazy is not None or self._cell_thickness_lazy()
         if out is not None or not lazy:
-            out = self._rows_out(out, self.nt)
+            out = self._rows_out(out, (self.nt, self._row_width))
         if lazy:
             # file-backed: one step on the GPU, the next one inflating into the other pinned slot (no wrap-around prefetch
             # after the last step)
@@ -627,15 +650,7 @@ class Field(object):
         rounding).  Levels this rank does not own (slab_range) are zeros.  The resident edge fluxes, the running max and the
         row of the last computeFlux are left as they are.  `out`: optional torch CUDA tensor (nz, row_length) that receives
         the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
-        self._stage(tIndex, prefetch_next)
-        if out is not None:
-            out = self._rows_out(out, self.nz)
-            check(lib.nf_field_compute_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((self.nz, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_profile', tIndex, (self.nz,), tracer=False, out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def setTracer(self, tracer, fill_value=None, missing_value=None, reference=0.0, wrapX=True):
@@ -977,7 +992,7 @@ class Field(object):
         lazy = (self._lazy is not None or (getattr(self, '_tracer', None) or {}).get('lazy') is not None or
                 self._cell_thickness_lazy())
         if out is not None or not lazy:
-            out = self._rows_out(out, self.nt)
+            out = self._rows_out(out, (self.nt, self._row_width))
         if lazy:
             # file-backed fields or tracer: one step at a time through the host
             rows = numpy.zeros((self.nt, self._row_width), numpy.float64)
@@ -1000,16 +1015,7 @@ class Field(object):
         (slab_range) are zeros.  Leaves the resident edge fluxes, the running max, the row of the last computeFlux and the
         tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor (nz, row_length) that receives the raw
         rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
-        if out is not None:
-            out = self._rows_out(out, self.nz)
-            check(lib.nf_field_compute_tracer_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((self.nz, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_tracer_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_tracer_profile', tIndex, (self.nz,), out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def computeAreaProfile(self, tIndex, out=None, prefetch_next=None):
@@ -1022,19 +1028,7 @@ class Field(object):
         mean, not a geometric length.  Levels this rank does not own (slab_range) are zeros.  Leaves the resident edge fluxes,
         the running max, the row of the last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64
         torch CUDA tensor (2, nz, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
-        shape = (2, self.nz, self._row_width)
-        if out is not None:
-            import torch
-            if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
-                raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
-            check(lib.nf_field_compute_area_profile_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros(shape, numpy.float64)
-            check(lib.nf_field_compute_area_profile(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_area_profile', tIndex, (2, self.nz), out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows[0]), self._split_rows(rows[1])
 
     def computeGrossProfile(self, tIndex, carry=False, out=None, prefetch_next=None):
@@ -1047,28 +1041,21 @@ class Field(object):
         Levels this rank does not own (slab_range) are zeros.  Leaves the resident edge fluxes, the running max, the row of the
         last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
         (2 * nz, row_length), P's rows then N's, that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
-        self._stage(tIndex, prefetch_next)
-        if carry:
-            self._stage_tracer(tIndex)
-        if out is not None:
-            out = self._rows_out(out, 2 * self.nz)
-            check(lib.nf_field_compute_gross_profile_async(ctypes.byref(self._h), tIndex, 1 if carry else 0,
-                                                           ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((2 * self.nz, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_gross_profile(ctypes.byref(self._h), tIndex, 1 if carry else 0, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_gross_profile', tIndex, (2 * self.nz,), carry=bool(carry),
+                             tracer=carry, out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows.reshape(2, self.nz, self._row_width))
+
+    def _num_crossings(self):
+        n = ctypes.c_size_t()
+        check(lib.nf_field_num_crossings(ctypes.byref(self._h), ctypes.byref(n)))
+        return n.value
 
     def getCrossings(self):
         """The crossings of the batched transect set: a Crossings object (see there), in the record order of getWeights() --
         crossing k is entries 4k .. 4k + 3.  Identical duplicates (halo columns, a north-fold row) keep their separate records
         with the same [ta, tb] and half the weight each; a crossing found through a periodic image has ta, tb in the parameter
         of its own target segment, so its lon0 .. lon1 lie on the line as the caller gave it."""
-        n = ctypes.c_size_t()
-        check(lib.nf_field_num_crossings(ctypes.byref(self._h), ctypes.byref(n)))
-        n = n.value
+        n = self._num_crossings()
         seg, cell = numpy.zeros(n, numpy.int32), numpy.zeros(n, numpy.int64)
         ta, tb = numpy.zeros(n, numpy.float64), numpy.zeros(n, numpy.float64)
         if n:
@@ -1105,27 +1092,10 @@ class Field(object):
         the planes of sharded ranks add up exactly; levels this rank does not own (slab_range) are zeros.  Leaves the resident
         edge fluxes, the running max, the row of the last computeFlux and the tracer rows as they are.  `out`: optional
         contiguous float64 torch CUDA tensor of the result's shape that receives the planes in HBM."""
-        tIndex = int(tIndex)
         if carry not in (False, True, 0, 1):
             raise RuntimeError(f'ERROR: carry must be False or True, got {carry!r}')
-        self._stage(tIndex, prefetch_next)
-        if carry:
-            self._stage_tracer(tIndex)
-        n = ctypes.c_size_t()
-        check(lib.nf_field_num_crossings(ctypes.byref(self._h), ctypes.byref(n)))
-        shape = (4 if carry else 2, self.nz, n.value)
-        if out is not None:
-            import torch
-            if tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float64:
-                raise RuntimeError(f'ERROR: out must be a contiguous float64 CUDA tensor of shape {shape}')
-            if n.value:
-                check(lib.nf_field_compute_crossings_async(ctypes.byref(self._h), tIndex, 1 if carry else 0,
-                                                           ctypes.c_void_p(out.data_ptr())))
-            return out.cpu().numpy()
-        planes = numpy.zeros(shape, numpy.float64)
-        if n.value:
-            check(lib.nf_field_compute_crossings(ctypes.byref(self._h), tIndex, 1 if carry else 0, _lib.dptr(planes)))
-        return planes
+        return self._product('nf_field_compute_crossings', tIndex, (4 if carry else 2, self.nz), carry=bool(carry), tracer=carry,
+                             width=self._num_crossings, out=out, prefetch_next=prefetch_next)
 
     @staticmethod
     def _crossing_area(parts):
@@ -1605,20 +1575,11 @@ class Field(object):
         of its face, so the rows add up to the computeTracerFlux row (up to rounding); a face whose carried tracer is missing
         on both sides adds nothing.  Levels this rank does not own (slab_range) contribute nothing.  Leaves everything else
         as it is.  `out`: as in computeClassTransport."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
-        if out is not None:
-            out = self._rows_out(out, edges.size + 2)
-            check(lib.nf_field_compute_class_tracer_transport_async(ctypes.byref(self._h), tIndex,
-                                                                    ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_class_tracer_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_class_tracer_transport', tIndex, (edges.size + 2,), out=out,
+                             prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def setClassEdges(self, edges):
@@ -1640,19 +1601,11 @@ class Field(object):
         this rank does not own (slab_range) contribute nothing.  Leaves the resident edge fluxes, the running max, the row of
         the last computeFlux and the tracer rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
         (nedges+2, row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
-        if out is not None:
-            out = self._rows_out(out, edges.size + 2)
-            check(lib.nf_field_compute_class_transport_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_class_transport(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_class_transport', tIndex, (edges.size + 2,), out=out,
+                             prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def computeClassRemap(self, tIndex, carry=False, out=None, prefetch_next=None):
@@ -1669,20 +1622,11 @@ class Field(object):
         nothing, but the class field is read one level beyond them.  The rows go into classStreamfunction and timeMean
         Fields as those of the step forms do.  Raises while a cell thickness is set.  Leaves everything else as it is.
         `out`: as in computeClassTransport."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
-        carry = 1 if carry else 0
-        if out is not None:
-            out = self._rows_out(out, edges.size + 2)
-            check(lib.nf_field_compute_class_remap_async(ctypes.byref(self._h), tIndex, carry, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((edges.size + 2, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_class_remap(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_class_remap', tIndex, (edges.size + 2,), carry=bool(carry), out=out,
+                             prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def setDepthEdges(self, edges, top=0.0):
@@ -1706,22 +1650,11 @@ class Field(object):
         rank does not own (slab_range) contribute nothing, but the depths are summed from level 0: the thickness is read
         above the owned levels too.  The rows go into classStreamfunction as they are: the overturning streamfunction in
         depth.  Leaves everything else as it is.  `out`: as in computeClassTransport."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_depth_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setDepthEdges first')
-        nrows = edges[0].size + 2
-        self._stage(tIndex, prefetch_next)
-        if carry:
-            self._stage_tracer(tIndex)
-        carry = 1 if carry else 0
-        if out is not None:
-            out = self._rows_out(out, nrows)
-            check(lib.nf_field_compute_depth_transport_async(ctypes.byref(self._h), tIndex, carry, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((nrows, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_depth_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_depth_transport', tIndex, (edges[0].size + 2,), carry=bool(carry),
+                             tracer=carry, out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def setDepthSurfaces(self, surfaces, top=0.0, fill_value=None, missing_value=None, wrapX=True):
@@ -1946,23 +1879,11 @@ class Field(object):
         (up to rounding) and go into classStreamfunction as they are.  Levels this rank does not own (slab_range)
         contribute nothing, but the depths are summed from level 0.  Leaves everything else as it is.  `out`: as in
         computeClassTransport."""
-        tIndex = int(tIndex)
         slot = getattr(self, '_surfaces', None)
         if slot is None:
             raise RuntimeError('ERROR: call setDepthSurfaces first')
-        nrows = len(slot['items']) + 2
-        self._stage(tIndex, prefetch_next)
-        self._stage_surfaces(tIndex)
-        if carry:
-            self._stage_tracer(tIndex)
-        carry = 1 if carry else 0
-        if out is not None:
-            out = self._rows_out(out, nrows)
-            check(lib.nf_field_compute_surface_transport_async(ctypes.byref(self._h), tIndex, carry, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((nrows, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_surface_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_surface_transport', tIndex, (len(slot['items']) + 2,), carry=bool(carry),
+                             tracer=carry, surfaces=True, out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows)
 
     def computeGrossClassTransport(self, tIndex, carry=False, out=None, prefetch_next=None):
@@ -1980,22 +1901,12 @@ class Field(object):
         computeFlux and the tracer, class and joint rows as they are.  `out`: optional contiguous float64 torch CUDA tensor
         (2 * (nedges+2), row_length), P's rows then N's, that receives the raw rows in HBM (for
         nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
         nrows = edges.size + 2
-        carry = 1 if carry else 0
-        if out is not None:
-            out = self._rows_out(out, 2 * nrows)
-            check(lib.nf_field_compute_gross_class_transport_async(ctypes.byref(self._h), tIndex, carry,
-                                                                   ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_gross_class_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_gross_class_transport', tIndex, (2 * nrows,), carry=bool(carry), out=out,
+                             prefetch_next=prefetch_next)
         return self._split_rows(rows.reshape(2, nrows, self._row_width))
 
     def computeGrossClassRemap(self, tIndex, carry=False, out=None, prefetch_next=None):
@@ -2014,22 +1925,12 @@ class Field(object):
         grossTransport, transportWeightedTracer and classStreamfunction(P + N).  Levels this rank does not own (slab_range)
         contribute nothing, but the class field is read one level beyond them.  Leaves everything else as it is.  `out`: as
         in computeGrossClassTransport."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
         nrows = edges.size + 2
-        carry = 1 if carry else 0
-        if out is not None:
-            out = self._rows_out(out, 2 * nrows)
-            check(lib.nf_field_compute_gross_class_remap_async(ctypes.byref(self._h), tIndex, carry,
-                                                               ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_gross_class_remap(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_gross_class_remap', tIndex, (2 * nrows,), carry=bool(carry), out=out,
+                             prefetch_next=prefetch_next)
         return self._split_rows(rows.reshape(2, nrows, self._row_width))
 
     def computeClassArea(self, tIndex, out=None, prefetch_next=None):
@@ -2047,20 +1948,11 @@ class Field(object):
         resident edge fluxes, the running max, the row of the last computeFlux and the tracer, class and joint rows as they
         are.  `out`: optional contiguous float64 torch CUDA tensor (2 * (nedges+2), row_length), A's rows then B's, that
         receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_class_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setClassEdges first')
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
         nrows = edges.size + 2
-        if out is not None:
-            out = self._rows_out(out, 2 * nrows)
-            check(lib.nf_field_compute_class_area_async(ctypes.byref(self._h), tIndex, ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((2 * nrows, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_class_area(ctypes.byref(self._h), tIndex, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_class_area', tIndex, (2 * nrows,), out=out, prefetch_next=prefetch_next)
         return self._split_rows(rows.reshape(2, nrows, self._row_width))
 
     @staticmethod
@@ -2164,22 +2056,12 @@ class Field(object):
         1-D call binned by A, summed over ra those binned by B (up to rounding).  Levels this rank does not own (slab_range)
         contribute nothing.  Leaves everything else as it is.  `out`: optional contiguous float64 torch CUDA tensor
         ((nA+2)*(nB+2), row_length) that receives the raw rows in HBM (for nemoflux_amd.dist.reduce_rows)."""
-        tIndex = int(tIndex)
         edges = getattr(self, '_joint_edges', None)
         if edges is None:
             raise RuntimeError('ERROR: call setJointClassEdges first')
         na, nb = edges[0].size + 2, edges[1].size + 2
-        self._stage(tIndex, prefetch_next)
-        self._stage_tracer(tIndex)
-        carry = 1 if carry else 0
-        if out is not None:
-            out = self._rows_out(out, na * nb)
-            check(lib.nf_field_compute_joint_class_transport_async(ctypes.byref(self._h), tIndex, carry,
-                                                                   ctypes.c_void_p(out.data_ptr())))
-            rows = out.cpu().numpy()
-        else:
-            rows = numpy.zeros((na * nb, self._row_width), numpy.float64)
-            check(lib.nf_field_compute_joint_class_transport(ctypes.byref(self._h), tIndex, carry, _lib.dptr(rows)))
+        rows = self._product('nf_field_compute_joint_class_transport', tIndex, (na * nb,), carry=bool(carry), out=out,
+                             prefetch_next=prefetch_next)
         tot, seg = self._split_rows(rows)
         return tot.reshape((na, nb) + tot.shape[1:]), seg.reshape((na, nb) + seg.shape[1:])
 
